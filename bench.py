@@ -13,13 +13,20 @@ the ranks (vp_tile_owner), followed (N > 1) by one RCCL reduce of the HDR accumu
 configs[1] exactly.  --scaling strong: spp = 1024 whatever N (the job is fixed, the ranks share it); --scaling both
 prints the weak line with the strong measurement inside it ("strong").  Inputs are resident in HBM before the timed
 region.  Prints ONE JSON line on rank 0 -- the LAST line of stdout, at most LINE_LIMIT bytes (compact_line(): the driver
-keeps an 8 KB tail; round 4's 20 KB line was cut in the middle and never parsed): the contract fields, a trimmed roofline,
-the CPU baseline, the headline's own general class (the 12 % of its pixels that scatter) as
-"general_class_msamples_per_s", and -- at N = 1 -- under "secondary" one compact dict per workload that does physics in every
-pixel or on the reference's own streams, all inside the one run the driver times: BASELINE configs[2] (c3), the reference's
-live configuration on its own sampler.h streams (c3ref_samplerh), and the two flagged stand-ins of configs[3] (c4s; c4f, the
-frame-filling cloud, at that config's 4096 spp).  Everything else (per-class tables, stall buckets, lookups per sample, the
-sentences) goes to the file named by --full-out (default gpurun_out/bench_last_full.json), never to stdout.
+keeps an 8 KB tail; round 4's 20 KB line was cut in the middle and never parsed).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps and the line -- the contract fields and the
+headline's own general class (the 12 % of its pixels that scatter, timed by the same launches) as "general_class_msamples_per_s".
+--dump-outputs DIR then writes what the last timed step computed, rank 0's HDR accumulator of that step's frames (float32,
+H x W x 4), as DIR/hdr_accumulator.npy: the frames of a step follow from the arguments alone, so two builds run with the same
+arguments can be compared output for output.
+
+--full adds everything else: the untimed work-counter pass and the trimmed roofline built on it, the per-camera set-up time,
+the CPU baseline, at N > 1 the fixed-job (strong) measurement of --scaling auto, and -- at N = 1 -- under "secondary" one
+compact dict per workload that does physics in every pixel or on the reference's own streams: BASELINE configs[2] (c3), the
+reference's live configuration on its own sampler.h streams (c3ref_samplerh), and the two flagged stand-ins of configs[3] (c4s;
+c4f, the frame-filling cloud, at that config's 4096 spp).  The complete record of a --full run (per-class tables, stall buckets,
+lookups per sample, the sentences) goes to the file named by --full-out, never to stdout.
 """
 import argparse
 import json
@@ -43,7 +50,7 @@ REFERENCE_ESTIMATOR_BYTES_PER_SAMPLE = 8 * 97.6 + 2 * 51.3 + 16 * 1.0 + 32
 LINE_LIMIT = 3072  # bytes of the final stdout line (tests/test_host_cpu.py pins it)
 WORKLOAD_CHOICES = ["c2", "c3", "c3ref", "c1", "c4s", "c4f"]
 RNG_NAMES = {"philox": "philox2x32-10", "philox7": "philox2x32-7", "samplerh": "sampler.h"}
-# what the default N = 1 line carries besides the headline: (key, workload, stream, spp per step, timed steps, CPU seconds)
+# what the --full N = 1 line carries besides the headline: (key, workload, stream, spp per step, timed steps, CPU seconds)
 SECONDARY = [
     ("c3", "c3", "philox7", 1024, 3, 5.0),                  # BASELINE configs[2]
     ("c3ref_samplerh", "c3ref", "samplerh", 1024, 3, 5.0),  # the reference's live configuration on its own streams (host.cpp:631)
@@ -229,9 +236,11 @@ def self_launch(args, argv):
 
 
 def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=True, rng=None, warmup_spp=None, count_frames=None,
-                 split="tiles"):
+                 split="tiles", work=True):
     """Time `steps` render jobs of one workload; returns the fields of the JSON line (rank 0) or None.
     rng: the stream (default args.rng); warmup_spp: samples per pixel of a warm-up step (default: as a timed step).
+    work: also time the per-camera set-up and run the untimed work-counter pass, and report the bytes (and, with `full`, the
+    roofline) built on them -- bench.py --full; without it the run is set-up, warm-up and the timed steps.
     split: how N ranks share a step.  "tiles" (north_star): every rank renders ITS pixel tiles (vp_tile_owner) in all frames; the
     accumulators are disjoint, so the reduce is exact and the image bit-identical to one rank's.  "frames" (SURVEY section 8e's
     alternative): every rank renders ALL pixels in its contiguous share of the step's frames -- perfectly balanced whatever the
@@ -269,27 +278,31 @@ def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=
         acc = torch.zeros(H, W, 4, device=dev, dtype=torch.float32)
         image = torch.zeros(H, W, 4, device=dev, dtype=torch.float32) if rank == 0 else None
 
-        # per-camera set-up at full size (untimed region, reported): the per-pixel tables of the camera, the class split and
-        # the pixel lists (GPU kernels + one 12-byte read-back), the sun table.  Forced by moving the camera away and back.
-        cam = info["camera"]
-        moved = list(cam)
-        moved[3] += 0.01
-        vp.set_camera(moved)
-        vp.prepare(P)
-        vp.set_camera(cam)
-        vp.synchronize()
-        t0 = time.perf_counter()
-        vp.prepare(P)
-        per_camera_setup_ms = (time.perf_counter() - t0) * 1e3
+        if work:
+            # per-camera set-up at full size (untimed region, reported): the per-pixel tables of the camera, the class split and
+            # the pixel lists (GPU kernels + one 12-byte read-back), the sun table.  Forced by moving the camera away and back.
+            cam = info["camera"]
+            moved = list(cam)
+            moved[3] += 0.01
+            vp.set_camera(moved)
+            vp.prepare(P)
+            vp.set_camera(cam)
+            vp.synchronize()
+            t0 = time.perf_counter()
+            vp.prepare(P)
+            per_camera_setup_ms = (time.perf_counter() - t0) * 1e3
 
-        # work counters (untimed, counting kernel variant), per pixel class: per-sample lookups of THIS build
-        vp.enable_counters(True)
-        vp.read_counters(reset=True)
-        vp.render_frames(acc.data_ptr(), count_first, count_frames, P)
-        counters = vp.read_counters(reset=True)
-        vp.enable_counters(False)
+            # work counters (untimed, counting kernel variant), per pixel class: per-sample lookups of THIS build
+            vp.enable_counters(True)
+            vp.read_counters(reset=True)
+            vp.render_frames(acc.data_ptr(), count_first, count_frames, P)
+            counters = vp.read_counters(reset=True)
+            vp.enable_counters(False)
+        else:
+            vp.prepare(P)   # the per-camera set-up, untimed: never inside the clock, with or without warm-up
 
         def step(first, spp):
+            """One render job; returns what it leaves on rank 0 (the summed HDR accumulator of its frames)."""
             acc.zero_()
             if by_frames:
                 # this rank's contiguous share of the step's frames, all pixels; partial images gathered and added in rank order
@@ -298,7 +311,7 @@ def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=
                 total = vdist.gather_sum_in_rank_order(acc.cpu() if rehearsal else acc, dst=0)
                 if rank == 0:
                     image.add_(total.to(dev))
-                return
+                return total
             vp.render_frames(acc.data_ptr(), first, spp, P)
             if world > 1 and rehearsal:
                 host = acc.cpu()
@@ -308,6 +321,7 @@ def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=
                 dist.reduce(acc, dst=0, op=dist.ReduceOp.SUM)  # RCCL over xGMI
             if rank == 0:
                 image.add_(acc)
+            return acc
 
         for i in range(warmup):
             step(i * warmup_spp, warmup_spp)
@@ -319,7 +333,7 @@ def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=
         vp.render_class_time_ms(reset=True)
         t0 = time.perf_counter()
         for i in range(steps):
-            step(warmup * warmup_spp + i * spp_step, spp_step)
+            last = step(warmup * warmup_spp + i * spp_step, spp_step)
         barrier()
         dt = time.perf_counter() - t0
         kern_ms, launches = vp.render_time_ms(reset=True)
@@ -345,39 +359,7 @@ def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=
     samples_rank = float(pixels_rank) * frames_rank
     value = samples_total / dt / 1e6
     launch_ms = kern_ms / launches
-    n_cnt = max(counters["samples"], 1)
-    # Bytes the TIMED kernels move (SURVEY section 8d formula on the build's own counters, class by class -- ADVICE r3): the general
-    # class by the counters (8 B per density lookup that issued a load, 2 B per bound lookup, 32 B per optical-depth lookup, 16 B
-    # per environment lookup, 32 B of accumulator traffic per sample: a 16-byte staging write, read once by the reduce); a class
-    # that is a per-pixel constant (the box-missing pixels always; the light class where a null collision in empty space leaves a
-    # throughput of 1 as it is) costs ONE environment lookup per pixel and launch and its staging slot, staged once per launch; a
-    # light class that is integrated (its kernel beside the general one) fetches no cells: bound lookups + one environment lookup.
-    # The counting pass walks every light path, so its env / bound counts are split by the classes' sample shares.
     light_const = class_px["light"] > 0 and light_const_flag
-    cper = {k: counters[k] / n_cnt for k in ("density_lookups", "density_loads", "bound_lookups", "opacity_lookups", "env_lookups", "scatters")}
-    smp_g = float(class_px["general"]) * frames_rank
-    smp_l = float(class_px["light"]) * frames_rank
-    smp_m = float(class_px["misses_box"]) * frames_rank
-    # per general sample: every load, optical-depth lookup and scatter is the general class's; bound / environment lookups of the
-    # counting pass are spread over all samples that make them
-    bound_other = 1.0 if cfg["est"] != vp.EST_GLOBAL else 0.0          # a box-missing sample of a local estimator: one bound fetch
-    bytes_gen = (8.0 * cper["density_loads"] + 32.0 * cper["opacity_lookups"]) * samples_rank \
-        + (2.0 * max(cper["bound_lookups"] * samples_rank - bound_other * smp_m, 0.0) * (smp_g / max(smp_g + smp_l, 1.0))) \
-        + (16.0 + 32.0) * smp_g
-    # (a per-pixel constant is staged ONCE per launch -- LaunchDev::const_from -- and added frame by frame by the add-kernel, which
-    # reads it once and the accumulator once: 16 B written + 16 B read + 32 B of accumulator per PIXEL and launch; VP_NO_CONST_ROWS=1
-    # stages it for every frame as before: 32 B per sample)
-    const_once = os.environ.get("VP_NO_CONST_ROWS", "0") != "1"
-    stage_const = (lambda px, smp: 64.0 * px * launches) if const_once else (lambda px, smp: 32.0 * smp)
-    if light_const:
-        bytes_light = 16.0 * class_px["light"] * launches + stage_const(class_px["light"], smp_l)
-    else:
-        bytes_light = 2.0 * max(cper["bound_lookups"] * samples_rank - bound_other * smp_m, 0.0) * (smp_l / max(smp_g + smp_l, 1.0)) + (16.0 + 32.0) * smp_l
-    bytes_miss = 16.0 * class_px["misses_box"] * launches + stage_const(class_px["misses_box"], smp_m)
-    loaded_total = bytes_gen + bytes_light + bytes_miss
-    loaded_bps = loaded_total / max(samples_rank, 1.0)
-    estimator_bps = bytes_per_sample(counters, loads=False)
-    achieved = loaded_total / launches / (launch_ms * 1e-3) / 1e9
     # per pixel class: which kernel integrates how many samples at what rate (the general and the light kernel run side by
     # side, so their times overlap; each is measured with its own pair of HIP events)
     per_class = {}
@@ -387,15 +369,48 @@ def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=
         per_class[name] = {"pixels": px, "pixel_fraction": px / max(pixels_rank, 1), "samples": smp, "kernel_ms": ms,
                            "kernel_ms_per_launch": ms / launches, "msamples_per_s": (smp / (ms * 1e-3) / 1e6) if ms > 0 else None}
     per_class["light"]["per_pixel_constant"] = bool(light_const)
-    # the density lookups of the light and box-missing classes issue no load; every load belongs to the general kernel
     gen = per_class["general"]
-    if gen["kernel_ms"] > 0:
-        lookups_general = counters["density_lookups"] / n_cnt * samples_rank
-        gen["density_loads_per_s"] = counters["density_loads"] / n_cnt * samples_rank / (gen["kernel_ms"] * 1e-3)
-        gen["density_loads_per_sample"] = counters["density_loads"] / n_cnt * samples_rank / max(gen["samples"], 1.0)
-        gen["loaded_bytes_per_sample"] = bytes_gen / max(smp_g, 1.0)
-        gen["loaded_GBps"] = bytes_gen / (gen["kernel_ms"] * 1e-3) / 1e9
-        per_class["all"] = {"density_lookups_per_s": lookups_general / (kern_ms * 1e-3)}
+    if work:
+        n_cnt = max(counters["samples"], 1)
+        # Bytes the TIMED kernels move (SURVEY section 8d formula on the build's own counters, class by class -- ADVICE r3): the general
+        # class by the counters (8 B per density lookup that issued a load, 2 B per bound lookup, 32 B per optical-depth lookup, 16 B
+        # per environment lookup, 32 B of accumulator traffic per sample: a 16-byte staging write, read once by the reduce); a class
+        # that is a per-pixel constant (the box-missing pixels always; the light class where a null collision in empty space leaves a
+        # throughput of 1 as it is) costs ONE environment lookup per pixel and launch and its staging slot, staged once per launch; a
+        # light class that is integrated (its kernel beside the general one) fetches no cells: bound lookups + one environment lookup.
+        # The counting pass walks every light path, so its env / bound counts are split by the classes' sample shares.
+        cper = {k: counters[k] / n_cnt for k in ("density_lookups", "density_loads", "bound_lookups", "opacity_lookups", "env_lookups", "scatters")}
+        smp_g = float(class_px["general"]) * frames_rank
+        smp_l = float(class_px["light"]) * frames_rank
+        smp_m = float(class_px["misses_box"]) * frames_rank
+        # per general sample: every load, optical-depth lookup and scatter is the general class's; bound / environment lookups of the
+        # counting pass are spread over all samples that make them
+        bound_other = 1.0 if cfg["est"] != vp.EST_GLOBAL else 0.0          # a box-missing sample of a local estimator: one bound fetch
+        bytes_gen = (8.0 * cper["density_loads"] + 32.0 * cper["opacity_lookups"]) * samples_rank \
+            + (2.0 * max(cper["bound_lookups"] * samples_rank - bound_other * smp_m, 0.0) * (smp_g / max(smp_g + smp_l, 1.0))) \
+            + (16.0 + 32.0) * smp_g
+        # (a per-pixel constant is staged ONCE per launch -- LaunchDev::const_from -- and added frame by frame by the add-kernel, which
+        # reads it once and the accumulator once: 16 B written + 16 B read + 32 B of accumulator per PIXEL and launch; VP_NO_CONST_ROWS=1
+        # stages it for every frame as before: 32 B per sample)
+        const_once = os.environ.get("VP_NO_CONST_ROWS", "0") != "1"
+        stage_const = (lambda px, smp: 64.0 * px * launches) if const_once else (lambda px, smp: 32.0 * smp)
+        if light_const:
+            bytes_light = 16.0 * class_px["light"] * launches + stage_const(class_px["light"], smp_l)
+        else:
+            bytes_light = 2.0 * max(cper["bound_lookups"] * samples_rank - bound_other * smp_m, 0.0) * (smp_l / max(smp_g + smp_l, 1.0)) + (16.0 + 32.0) * smp_l
+        bytes_miss = 16.0 * class_px["misses_box"] * launches + stage_const(class_px["misses_box"], smp_m)
+        loaded_total = bytes_gen + bytes_light + bytes_miss
+        loaded_bps = loaded_total / max(samples_rank, 1.0)
+        estimator_bps = bytes_per_sample(counters, loads=False)
+        achieved = loaded_total / launches / (launch_ms * 1e-3) / 1e9
+        # the density lookups of the light and box-missing classes issue no load; every load belongs to the general kernel
+        if gen["kernel_ms"] > 0:
+            lookups_general = counters["density_lookups"] / n_cnt * samples_rank
+            gen["density_loads_per_s"] = counters["density_loads"] / n_cnt * samples_rank / (gen["kernel_ms"] * 1e-3)
+            gen["density_loads_per_sample"] = counters["density_loads"] / n_cnt * samples_rank / max(gen["samples"], 1.0)
+            gen["loaded_bytes_per_sample"] = bytes_gen / max(smp_g, 1.0)
+            gen["loaded_GBps"] = bytes_gen / (gen["kernel_ms"] * 1e-3) / 1e9
+            per_class["all"] = {"density_lookups_per_s": lookups_general / (kern_ms * 1e-3)}
     out = {
         "metric": "Msamples/sec (WxHxspp) + achieved HBM GB/s, Julia 256^3 @ 800x600",
         "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": steps, "warmup": warmup,
@@ -412,14 +427,15 @@ def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=
         # the class that does the physics: the pixels whose camera ray can meet the medium (the others are per-pixel constants in
         # this scene: quirk Q3, no pixel jitter) -- the number to track; `value` is BASELINE's metric, all pixels
         "general_class_msamples_per_s": gen["msamples_per_s"],
-        "per_camera_setup_ms": per_camera_setup_ms,
         "per_class": per_class,
     }
+    if work:
+        out["per_camera_setup_ms"] = per_camera_setup_ms
     if warmup_spp != spp_step:
         out["config"]["warmup_spp"] = warmup_spp
     if info.get("note"):
         out["config"]["note"] = info["note"]
-    if full:
+    if work and full:
         # counters of the render kernels from the committed rocprofv3 PMC passes of THIS workload and stream (not measured in this
         # run: PMC collection serialises kernels); scaled to this run's launch size
         pmc, traffic, valu_frac, lane_util, pmc_src, stalls = {}, None, None, None, None, None
@@ -472,7 +488,7 @@ def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=
             "reference_estimator_bytes_per_sample": REFERENCE_ESTIMATOR_BYTES_PER_SAMPLE,
             "lookups_per_sample": cper,
             "lookups_counted_on": f"frames {count_first}..{count_first + count_frames - 1} (counting kernel variant, untimed)"}
-    else:
+    elif work:
         out["loaded_GBps"] = achieved
         out["launch_ms"] = launch_ms
     if world > 1:
@@ -483,6 +499,7 @@ def run_workload(workload, args, ctx, spp_per_gpu, steps, warmup, scaling, full=
     if rehearsal:
         out["config"]["parallelism"] += " (REHEARSAL: all ranks on one GPU, gloo)"
     out["_image"] = image
+    out["_last"] = last
     out["_grid"] = info.get("grid")
     # (for the CPU baseline of a decomposition workload: the optical-depth table of this scene, read back while the scene is current)
     out["_opacity"] = vp.opacity_table((info["n"],) * 3) if (info["est"] == vp.EST_DECOMP and ctx.get("want_opacity")) else None
@@ -538,8 +555,8 @@ def main():
     ap.add_argument("--spp", type=int, default=1024, help="samples per pixel per GPU per step (weak) / per step (strong)")
     ap.add_argument("--scaling", default="auto", choices=["auto", "weak", "strong", "both"],
                     help="weak: spp * N per step (per-GPU work fixed); strong: spp per step whatever N; both: the weak line with "
-                         "the strong measurement inside it; auto (default): weak at N = 1, both at N > 1 (the fixed-job run costs "
-                         "1/N of a weak step and shows the per-shard tail the weak line hides)")
+                         "the strong measurement inside it; auto (default): both at N > 1 with --full (the fixed-job run costs "
+                         "1/N of a weak step and shows the per-shard tail the weak line hides), weak otherwise")
     ap.add_argument("--split", default="auto", choices=["auto", "tiles", "frames"],
                     help="how the ranks share a FIXED job (--scaling strong / both): tiles = pixel tiles (north_star; the weak line always), "
                          "frames = contiguous frame ranges of all pixels, partial images added in rank order; auto = measure both, report "
@@ -548,17 +565,26 @@ def main():
                     help="philox7 = Philox2x32-7 (default: the fewest rounds Random123 documents as Crush-resistant; oracle parity "
                          "like the others), philox = Philox2x32-10 (the round-1 default, 4-6 %% slower), samplerh = the reference's "
                          "sampler.h streams")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads of the N = 1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the work-counter pass and the roofline on it, the per-camera "
+                         "set-up time, the CPU baseline, the secondary workloads (N = 1), the fixed-job measurement (N > 1, --scaling "
+                         "auto), and write the complete record to --full-out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary workloads of the N = 1 line")
     ap.add_argument("--secondary", default=None, help="comma-separated subset of the secondary workloads (c3,c3ref_samplerh,c4s,c4f)")
     ap.add_argument("--call-pattern", action="store_true",
                     help="also time the reference host's own call pattern (one render_kernel per frame; an orbiting camera): the "
                          "interactive shell is out of scope (SURVEY section 2 rows 15-16), so this is off by default")
     ap.add_argument("--full-out", default=os.path.join(ROOT, "gpurun_out", "bench_last_full.json"),
-                    help="where rank 0 writes the COMPLETE record (per-class tables, stalls, lookups per sample, notes); stdout gets "
-                         "the compact line only")
+                    help="where rank 0 writes the COMPLETE record of a --full run (per-class tables, stalls, lookups per sample, notes); "
+                         "stdout gets the compact line only")
     ap.add_argument("--dump-image", default=None, help="rank 0 saves the summed HDR image (.npy) -- used by tests")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last one computed -- the HDR accumulator of its frames, float32 "
+                         "H x W x 4 -- as DIR/hdr_accumulator.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])
@@ -590,21 +616,30 @@ def main():
     stream = torch.cuda.Stream(device=dev)
     vp.set_stream(stream.cuda_stream)
     ctx = {"rank": rank, "world": world, "dev": dev, "stream": stream, "rehearsal": rehearsal,
-           "want_opacity": world == 1 and not args.no_cpu_baseline}
+           "want_opacity": world == 1 and args.full and not args.no_cpu_baseline}
 
     if args.scaling == "auto":
-        args.scaling = "both" if world > 1 else "weak"
+        args.scaling = "both" if (world > 1 and args.full) else "weak"
     first = "strong" if args.scaling == "strong" else "weak"
     out = run_workload(args.workload, args, ctx, args.spp, args.steps, args.warmup, first,
-                       split="frames" if (first == "strong" and args.split == "frames") else "tiles")
+                       split="frames" if (first == "strong" and args.split == "frames") else "tiles", work=args.full)
+    if rank == 0:
+        last = out.pop("_last")
+        if args.dump_outputs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "hdr_accumulator.npy"), np.ascontiguousarray(last.cpu().numpy(), np.float32))
+        del last
     strong, strong_alt = None, None
     if args.scaling == "both" and world > 1:
         # the fixed job (spp whatever N) both ways where the frames divide: by pixel tiles (every shard pays the tail of its own
         # deepest paths and a few per cent of imbalance) and by frame ranges (balanced by construction, every rank pays the fixed
         # cost of a launch); the better one is reported, the other kept beside it
-        strong = run_workload(args.workload, args, ctx, args.spp, args.steps, args.warmup, "strong", full=False, split="tiles")
+        strong = run_workload(args.workload, args, ctx, args.spp, args.steps, args.warmup, "strong", full=False, split="tiles",
+                              work=args.full)
         if args.split in ("auto", "frames") and args.spp % world == 0:
-            strong_alt = run_workload(args.workload, args, ctx, args.spp, args.steps, args.warmup, "strong", full=False, split="frames")
+            strong_alt = run_workload(args.workload, args, ctx, args.spp, args.steps, args.warmup, "strong", full=False, split="frames",
+                                      work=args.full)
     call_pattern = None
     if world == 1 and args.call_pattern:
         try:
@@ -612,7 +647,7 @@ def main():
         except Exception as e:   # a side measurement must not take the line down with it
             call_pattern = {"error": repr(e)}
     secondary = {}
-    if world == 1 and args.workload == "c2" and not args.no_secondary:
+    if world == 1 and args.workload == "c2" and args.full and not args.no_secondary:
         # The workloads that do physics in every pixel, or on the reference's own streams, under the same clock as the headline
         # (VERDICT r3 item 1): BASELINE configs[2] (its 8^3 brick table staged through LDS), the reference's LIVE configuration on its own sampler.h
         # streams (what src/volumeRender.cpp:631 computes, sample for sample), and the two flagged stand-ins of configs[3] -- the
@@ -623,6 +658,7 @@ def main():
                 continue
             sec = run_workload(wl, args, ctx, spp, min(steps, max(args.steps, 1)), 1, "weak", full=True, rng=rng, warmup_spp=64)
             sec.pop("_image")
+            sec.pop("_last")
             grid, opa = sec.pop("_grid"), sec.pop("_opacity")
             if not args.no_cpu_baseline:
                 sec["cpu_baseline"] = cpu_baseline(wl, seconds_hint=cpu_s, rng=rng, grid=grid, opacity=opa)
@@ -646,6 +682,7 @@ def main():
                 both["frames"] = strong_alt
             for q in both.values():
                 q.pop("_image")
+                q.pop("_last")
                 q.pop("_grid")
                 q.pop("_opacity", None)
             best = max(both, key=lambda k: both[k]["value"]) if args.split == "auto" else ("frames" if (args.split == "frames" and strong_alt) else "tiles")
@@ -661,16 +698,17 @@ def main():
         if args.dump_image:
             import numpy as np
             np.save(args.dump_image, image.cpu().numpy())
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, rng=args.rng, grid=grid, opacity=opa)
         # the complete record to a file (never to stdout), the compact line -- <= LINE_LIMIT bytes -- as the LAST line of stdout
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(args.full_out)), exist_ok=True)
-            with open(args.full_out, "w") as f:
-                json.dump(out, f, indent=1)
-            out["full"] = os.path.relpath(os.path.abspath(args.full_out), ROOT)
-        except OSError as e:
-            print(f"bench.py: could not write {args.full_out}: {e}", file=sys.stderr)
+        if args.full:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.full_out)), exist_ok=True)
+                with open(args.full_out, "w") as f:
+                    json.dump(out, f, indent=1)
+                out["full"] = os.path.relpath(os.path.abspath(args.full_out), ROOT)
+            except OSError as e:
+                print(f"bench.py: could not write {args.full_out}: {e}", file=sys.stderr)
         sys.stdout.flush()
         print(compact_line(out), flush=True)
     if world > 1:

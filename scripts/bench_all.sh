@@ -4,8 +4,10 @@
 set -e
 TAG=${1:-r05}
 LOG=gpurun_out/bench_$TAG.log
+OUT=$(dirname $LOG)
 : > $LOG
-run() { local name=$1; shift; echo "== $name: $*" >> $LOG; python bench.py --no-secondary --full-out gpurun_out/bench_${TAG}_${name}_full.json "$@" > gpurun_out/bench_${TAG}_$name.json 2>> $LOG || { echo "bench $name failed: see $LOG" >&2; tail -5 $LOG >&2; exit 1; }; }
+# --full: the records carry the roofline, the CPU baseline and the per-class tables
+run() { local name=$1; shift; echo "== $name: $*" >> $LOG; python bench.py --full --no-secondary --full-out $OUT/bench_${TAG}_${name}_full.json "$@" > $OUT/bench_${TAG}_$name.json 2>> $LOG || { echo "bench $name failed: see $LOG" >&2; tail -5 $LOG >&2; exit 1; }; }
 run c1 --workload c1 --spp 16 --steps 5 --warmup 2
 run c2 --workload c2
 run c2_philox10 --workload c2 --rng philox
@@ -16,4 +18,4 @@ run c3ref_samplerh --workload c3ref --rng samplerh
 run c4s --workload c4s
 run c4f --workload c4f
 echo "== default" >> $LOG
-python bench.py --full-out gpurun_out/bench_${TAG}_default_full.json > gpurun_out/bench_${TAG}_default.json 2>> $LOG
+python bench.py --full --full-out $OUT/bench_${TAG}_default_full.json > $OUT/bench_${TAG}_default.json 2>> $LOG

@@ -747,7 +747,8 @@ def test_bench_two_ranks_rehearsal_matches_one_rank(tmp_path):
     """bench.py's N>1 path end to end on this one-GPU box (both ranks on GPU 0, reduce over gloo), started AS TYPED --
     `python bench.py --gpus 2`, no external torchrun: bench.py starts its ranks as a child process before anything touches the
     GPU.  The 2-rank image of frames [0,8) must equal the 1-rank image bit for bit, the JSON line must be well formed, and
-    --scaling both adds the fixed-job (strong) measurement to the weak line."""
+    --scaling both adds the fixed-job (strong) measurement to the weak line.  --full: the roofline, the per-camera set-up time and the
+    complete record; --dump-outputs: the last timed step's accumulator, here (one step, no warm-up) the summed image itself."""
     import json
     import os
     import subprocess
@@ -755,10 +756,11 @@ def test_bench_two_ranks_rehearsal_matches_one_rank(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     bench = os.path.join(root, "bench.py")
     one, two = str(tmp_path / "one.npy"), str(tmp_path / "two.npy")
-    common = ["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "c1"]
+    common = ["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "c1", "--full"]
     full1, full2 = str(tmp_path / "full1.json"), str(tmp_path / "full2.json")
-    r1 = subprocess.run([sys.executable, bench, "--gpus", "1", "--spp", "8", "--dump-image", one, "--full-out", full1, "--call-pattern"] + common,
-                        capture_output=True, text=True, cwd=root)
+    out1 = tmp_path / "out1"
+    r1 = subprocess.run([sys.executable, bench, "--gpus", "1", "--spp", "8", "--dump-image", one, "--full-out", full1, "--call-pattern",
+                         "--dump-outputs", str(out1)] + common, capture_output=True, text=True, cwd=root)
     assert r1.returncode == 0, r1.stdout + r1.stderr
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["VP_BENCH_REHEARSAL"] = "1"
@@ -789,6 +791,8 @@ def test_bench_two_ranks_rehearsal_matches_one_rank(tmp_path):
     assert line2["strong"]["scaling"] == "strong" and line2["strong"]["spp_per_step"] == 4 and line2["strong"]["value"] > 0
     assert len(line2["ranks"]["kernel_ms"]) == 2 and line2["ranks"]["collective_ranks"] == 2 and line2["ranks"]["backend"] == "gloo"
     assert np.array_equal(np.load(one), np.load(two))
+    acc1 = np.load(str(out1 / "hdr_accumulator.npy"))
+    assert acc1.dtype == np.float32 and acc1.shape == (300, 400, 4) and np.array_equal(acc1, np.load(one))
 
 
 def test_bench_four_rank_rehearsal_is_bit_identical_and_its_line_short(tmp_path):
@@ -798,7 +802,8 @@ def test_bench_four_rank_rehearsal_is_bit_identical_and_its_line_short(tmp_path)
     test_cli_bin_ingest_matches_oracle_and_two_contexts_match_one's --gpus 8 and test_pixel_lists_are_the_stable_partition_of_the_tile_
     order's world = 8.)  All ranks on GPU 0, the reduce over gloo.  The tile split's image equals the one-rank image bit for bit, the
     final stdout line is one JSON object of at most 3 KB with the per-rank times, the balance, both ways of sharing the fixed job and
-    the collective's rank count."""
+    the collective's rank count.  Plain runs (no --full); --dump-outputs writes the last timed step's accumulator of rank 0, here
+    (one step, no warm-up) the summed image itself, on one rank and on four."""
     import json
     import os
     import subprocess
@@ -808,12 +813,13 @@ def test_bench_four_rank_rehearsal_is_bit_identical_and_its_line_short(tmp_path)
     one, four = str(tmp_path / "one.npy"), str(tmp_path / "four.npy")
     common = ["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "c1"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r1 = subprocess.run([sys.executable, bench, "--gpus", "1", "--spp", "16", "--dump-image", one, "--full-out", str(tmp_path / "f1.json")] + common,
-                        capture_output=True, text=True, cwd=root, env=env)
+    r1 = subprocess.run([sys.executable, bench, "--gpus", "1", "--spp", "16", "--dump-image", one, "--full-out", str(tmp_path / "f1.json"),
+                         "--dump-outputs", str(tmp_path / "o1")] + common, capture_output=True, text=True, cwd=root, env=env)
     assert r1.returncode == 0, r1.stdout + r1.stderr
     env["VP_BENCH_REHEARSAL"] = "1"
     r4 = subprocess.run([sys.executable, bench, "--gpus", "4", "--spp", "4", "--scaling", "both", "--dump-image", four,
-                         "--full-out", str(tmp_path / "f4.json")] + common, capture_output=True, text=True, cwd=root, env=env, timeout=900)
+                         "--full-out", str(tmp_path / "f4.json"), "--dump-outputs", str(tmp_path / "o4")] + common,
+                        capture_output=True, text=True, cwd=root, env=env, timeout=900)
     assert r4.returncode == 0, r4.stdout + r4.stderr
     last = r4.stdout.rstrip("\n").splitlines()[-1]
     assert last.startswith("{") and len(last) <= 3072, len(last)
@@ -823,6 +829,8 @@ def test_bench_four_rank_rehearsal_is_bit_identical_and_its_line_short(tmp_path)
     assert line["ranks"]["balance_max_over_mean"] >= 1.0 and line["strong"]["spp_per_step"] == 4
     assert set(line["strong"]["by_split"]) == {"tiles", "frames"} and line["strong"]["split"] in ("tiles", "frames")
     assert np.array_equal(np.load(one), np.load(four))
+    for d in ("o1", "o4"):
+        assert np.array_equal(np.load(str(tmp_path / d / "hdr_accumulator.npy")), np.load(one))
 
 
 def test_bench_frame_split_adds_partial_images_in_rank_order(vp, tmp_path):
