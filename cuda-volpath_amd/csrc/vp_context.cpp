@@ -664,6 +664,14 @@ int vp_set_lookahead(int max_frames)
     G.la_max = max_frames; G.la_prev_n = 0;
     return VP_OK;
 }
+int vp_set_arithmetic(int mode)
+{
+    if (mode != VP_ARITH_EXACT && mode != VP_ARITH_FAST) return fail(VP_E_ARG, "unknown arithmetic mode %d", mode);
+    if (mode == G.arith) return VP_OK;
+    if (la_quiesce()) return VP_E_NODEVICE;   // (the look-ahead key holds the mode as well: staged frames are never served across it)
+    G.arith = mode;
+    return VP_OK;
+}
 int vp_set_envmap_sampling(int mode)
 {
     if (mode != VP_ENV_PASSIVE && mode != VP_ENV_MIS) return fail(VP_E_ARG, "unknown environment sampling mode %d", mode);

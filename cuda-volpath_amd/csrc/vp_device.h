@@ -11,6 +11,7 @@
 namespace vp
 {
 struct f3 { float x, y, z; };
+VP_ARITH_BEGIN   // (vp_math.h: the device functions are the arithmetic mode's own)
 __device__ __forceinline__ f3 mk3(float x, float y, float z) { return f3{x, y, z}; }
 __device__ __forceinline__ f3 operator+(f3 a, f3 b) { return f3{a.x + b.x, a.y + b.y, a.z + b.z}; }
 __device__ __forceinline__ f3 operator-(f3 a, f3 b) { return f3{a.x - b.x, a.y - b.y, a.z - b.z}; }
@@ -22,9 +23,12 @@ __device__ __forceinline__ f3 cross(f3 a, f3 b)
 {
     return f3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
-__device__ __forceinline__ f3 normalize(f3 v) { return v * (1.0f / __builtin_sqrtf(dot(v, v))); }
+__device__ __forceinline__ f3 normalize(f3 v) { return v * rsqrt_(dot(v, v)); }
+// IEEE in both arithmetic modes: the camera ray, which the per-pixel tables are certified on
+__device__ __forceinline__ f3 normalize_ieee(f3 v) { return v * (1.0f / __builtin_sqrtf(dot(v, v))); }
 __device__ __forceinline__ float max3(f3 v) { return fmaxf(fmaxf(v.x, v.y), v.z); }
 __device__ __forceinline__ float min3(f3 v) { return fminf(fminf(v.x, v.y), v.z); }
+VP_ARITH_END
 
 // vecmath.h:9-16 evaluated in float, as the reference's constexpr does
 #define VP_PI_F 3.1415926535897932384626422832795028841971f
@@ -168,6 +172,7 @@ typedef RngPhiloxR<10> RngPhilox;   // VP_RNG_PHILOX
 typedef RngPhiloxR<7>  RngPhilox7;  // VP_RNG_PHILOX7: Random123's smallest Crush-resistant round count
 
 // ------------------------------------------------------------------ texture fetches
+VP_ARITH_BEGIN
 #define VP_U8_TRI_SCALE 2.3374372e-10f  // fl(1/(255*2^24)): full scale -> exactly 1.0f
 #define VP_U8_SCALE 0.003921569f        // fl(1/255)
 
@@ -517,7 +522,7 @@ __device__ __forceinline__ void camera_ray(const SceneDev& S, unsigned width, un
     float v = ((float)py * 2.0f - (float)height) / (float)width;
     ro      = f3{S.cam[3], S.cam[7], S.cam[11]};
     f3 dv   = f3{u, v, S.cam_z};
-    rd      = normalize(f3{dot(dv, f3{S.cam[0], S.cam[1], S.cam[2]}), dot(dv, f3{S.cam[4], S.cam[5], S.cam[6]}), dot(dv, f3{S.cam[8], S.cam[9], S.cam[10]})});
+    rd      = normalize_ieee(f3{dot(dv, f3{S.cam[0], S.cam[1], S.cam[2]}), dot(dv, f3{S.cam[4], S.cam[5], S.cam[6]}), dot(dv, f3{S.cam[8], S.cam[9], S.cam[10]})});
 }
 
 // Frame kernel.cu:557-573 (fabs(n.x) > 0.1 is a DOUBLE compare: equivalent to >= 0.1f in float)
@@ -541,22 +546,21 @@ __device__ __forceinline__ f3 hg_sample_local(float g, float rnd0, float rnd1)
     if (__builtin_fabsf(g) > 1e-6f)
     {
         float s   = 2.0f * rnd0 - 1.0f;
-        float f   = (1.0f - g * g) / (1.0f + g * s);
-        cos_theta = (0.5f / g) * (1.0f + g * g - f * f);
+        float f   = div_(1.0f - g * g, 1.0f + g * s);
+        cos_theta = div_(0.5f, g) * (1.0f + g * g - f * f);
         cos_theta = fmaxf(0.0f, fminf(1.0f, cos_theta));
     }
     else
         cos_theta = 2.0f * rnd0 - 1.0f;
-    float sin_theta = __builtin_sqrtf(1.0f - cos_theta * cos_theta);
-    float phi       = (2.0f * kPi) * rnd1;
+    float sin_theta = sqrt_(1.0f - cos_theta * cos_theta);
     float sp, cp;
-    sincosf_(phi, sp, cp);
+    sincos_turns_(rnd1, sp, cp);   // of (2 pi) rnd1
     return f3{cp * sin_theta, sp * sin_theta, cos_theta};
 }
 // HGPhaseFunction::evaluate kernel.cu:600-603
 __device__ __forceinline__ float hg_eval(float g, float cos_theta)
 {
-    return (1.0f - g * g) / ((4.0f * kPi) * pow15f_(1.0f + g * g - (2.0f * g) * cos_theta));
+    return div_(1.0f - g * g, (4.0f * kPi) * pow15f_(1.0f + g * g - (2.0f * g) * cos_theta));
 }
 
 // hyperion trick kernel.cu:2039 / :1358
@@ -564,4 +568,5 @@ __device__ __forceinline__ float hyperion_s(int n_minus)
 {
     return fmaxf(0.0f, fminf(1.0f, (float)n_minus * 0.066666666666666666667f));
 }
+VP_ARITH_END
 }  // namespace vp

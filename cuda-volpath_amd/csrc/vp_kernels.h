@@ -155,11 +155,16 @@ struct LaunchDev
 // workgroups), 2 2-bit codes into a four-entry palette through LDS (LaunchDev::bound_codes; 256-thread workgroups, plain occupancy)
 void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int lds_form, bool mis, int trk,
                    int blocks, hipStream_t st);
+// the same in the fast arithmetic mode (vp_kernels_fast.hip): counter-based streams, spectral tracking, passive environment, global
+// majorant or decomposition, no counters -- the host refuses the rest before it launches
+void launch_render_fast(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int lds_form, bool mis, int trk,
+                        int blocks, hipStream_t st);
 // the light pixel class (spectral tracking): pixels whose camera ray meets empty cells only
 void launch_render_light(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int blocks, hipStream_t st);
 void launch_miss_fill(const SceneDev& S, const LaunchDev& L, bool local_estimator, hipStream_t st);
 // the camera rays' free flights through certified-empty cells, one thread per sample of the launch (approach_k); rng: RNG_PHILOX*
 void launch_approach(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, hipStream_t st);
+void launch_approach_fast(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, hipStream_t st);
 // the per-pixel segment table of the decomposition estimator's approach walk (approach_segments_k): float4 per slot, and its builder
 unsigned segment_table_records(void);
 void launch_segment_table(const SceneDev& S, unsigned width, unsigned height, const float4* crawl, const unsigned* pixels, unsigned nslots, float4* seg,
@@ -170,6 +175,7 @@ void launch_thr_table(const ParamDev& P, float* table, unsigned count, hipStream
 // empty space leaves a throughput of 1 unchanged for every sigma_t' a light path can meet (light_identity_k)
 void launch_bound_bytes(const unsigned char* bounds, size_t nbricks, unsigned* mask, hipStream_t st);
 void launch_light_identity(const ParamDev& P, bool local, const unsigned* mask, unsigned* flag, hipStream_t st);
+void launch_light_identity_fast(const ParamDev& P, bool local, const unsigned* mask, unsigned* flag, hipStream_t st);   // (vp_kernels_fast.hip)
 // the rank's pixel lists, class by class, on the GPU (pixlist_*_k): d_row_start[tiles_y + 1] = first owned tile of each tile row,
 // d_block_counts[3 * pixel_list_blocks(ntiles)] scratch, d_totals[3] = pixels per class (general, light, box-missing)
 inline unsigned pixel_list_blocks(unsigned ntiles) { return (unsigned)(((size_t)ntiles * 64 + 1023) / 1024); }

@@ -5,11 +5,27 @@
 // so that results do not depend on which vendor libm (CUDA, ocml, glibc) evaluates them; the
 // parity tests compare this path bit for bit against an independent CPU statement of the same
 // sequences.  Cephes single-precision kernels (Moshier).  Compile with -ffp-contract=off.
+//
+// VP_ARITH_FAST (vp_kernels_fast.hip only; include/volpath.h vp_set_arithmetic): the integrator's logarithm, exponential,
+// divides, reciprocals, square roots and the phase function's sine and cosine become the hardware's single instructions
+// (v_log_f32, v_exp_f32, v_rcp_f32, v_sqrt_f32, v_rsq_f32, v_sin_f32 / v_cos_f32), each substitution written out here -- the
+// flags stay those of the exact build (no contraction, no compiler fast math), so every instance of a fast kernel computes the
+// same bits for the same sample.  The helpers then live in an inline namespace of their own: the two translation units never
+// share a definition of the same name.  Without VP_ARITH_FAST every helper is the expression the integrator has always used.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#ifdef VP_ARITH_FAST
+#define VP_ARITH_BEGIN inline namespace arith_fast {
+#define VP_ARITH_END }
+#else
+#define VP_ARITH_BEGIN
+#define VP_ARITH_END
+#endif
+
 namespace vp
 {
+VP_ARITH_BEGIN
 __device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ float u2f(unsigned u) { return __uint_as_float(u); }
 __device__ __forceinline__ unsigned f2u(float f) { return __float_as_uint(f); }
@@ -17,8 +33,8 @@ __device__ __forceinline__ unsigned f2u(float f) { return __float_as_uint(f); }
 // natural logarithm on {0} U [2^-126, inf); log(0) = -inf
 __device__ __forceinline__ float logf_(float x)
 {
-#ifdef VP_EXP_FASTLOG
-    return __builtin_amdgcn_logf(x) * 0.69314718056f;
+#if defined(VP_ARITH_FAST) || defined(VP_EXP_FASTLOG)
+    return __builtin_amdgcn_logf(x) * 0.69314718056f;   // v_log_f32 is log2; log(0) = -inf as well
 #endif
     // mantissa folded into (sqrt(2)/2, sqrt(2)] without a select: adding 2^23 - 0x3504f4 to the bit pattern carries
     // into the exponent field exactly when the mantissa field exceeds that of fl(sqrt 2) = 0x3fb504f3
@@ -51,6 +67,9 @@ __device__ __forceinline__ float expf_(float x)
 {
     if (x < -87.0f) return 0.0f;
     if (x > 88.0f) return __builtin_inff();
+#ifdef VP_ARITH_FAST
+    return __builtin_amdgcn_exp2f(x * 1.44269504088896341f);   // v_exp_f32 is 2^x
+#endif
     float fn = __builtin_floorf(fma_(x, 1.44269504088896341f, 0.5f));
     float r  = fma_(fn, -0.693359375f, x);
     r        = fma_(fn, 2.12194440e-4f, r);
@@ -131,12 +150,37 @@ __device__ __forceinline__ float atanf_(float x)
 // the quotient of the collision weights (experiment hook: VP_EXP_FASTDIV replaces the IEEE divide by v_rcp_f32)
 __device__ __forceinline__ float wdiv_(float a, float b)
 {
-#ifdef VP_EXP_FASTDIV
+#if defined(VP_ARITH_FAST) || defined(VP_EXP_FASTDIV)
     return a * __builtin_amdgcn_rcpf(b);
 #else
     return a / b;
 #endif
 }
 
-__device__ __forceinline__ float pow15f_(float x) { return x * __builtin_sqrtf(x); }
+// the integrator's other quotients, reciprocals and roots
+#ifdef VP_ARITH_FAST
+__device__ __forceinline__ float div_(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
+__device__ __forceinline__ float rcp_(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float sqrt_(float x) { return __builtin_amdgcn_sqrtf(x); }
+__device__ __forceinline__ float rsqrt_(float x) { return __builtin_amdgcn_rsqf(x); }
+#else
+__device__ __forceinline__ float div_(float a, float b) { return a / b; }
+__device__ __forceinline__ float rcp_(float x) { return 1.0f / x; }
+__device__ __forceinline__ float sqrt_(float x) { return __builtin_sqrtf(x); }
+__device__ __forceinline__ float rsqrt_(float x) { return 1.0f / __builtin_sqrtf(x); }
+#endif
+
+// sine and cosine of 2 pi t, t in [0, 1]: the azimuth of the phase-function sample (v_sin_f32 / v_cos_f32 take revolutions)
+__device__ __forceinline__ void sincos_turns_(float t, float& s, float& c)
+{
+#ifdef VP_ARITH_FAST
+    s = __builtin_amdgcn_sinf(t);
+    c = __builtin_amdgcn_cosf(t);
+#else
+    sincosf_((2.0f * 3.14159265358979323846f) * t, s, c);
+#endif
+}
+
+__device__ __forceinline__ float pow15f_(float x) { return x * sqrt_(x); }
+VP_ARITH_END
 }  // namespace vp

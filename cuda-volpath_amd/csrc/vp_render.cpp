@@ -65,6 +65,16 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     if (G.trk && G.count) return fail(VP_E_STATE, "work counters are not built for the scalar tracking kernels");
     if (G.rng == VP_RNG_PHILOX7 && (G.trk || G.env_mis))
         return fail(VP_E_STATE, "VP_RNG_PHILOX7 is built for spectral tracking with passive environment lighting only");
+    if (G.arith == VP_ARITH_FAST)
+    {
+        // the fast arithmetic is built for the counter-based streams' shipped configuration only (vp_kernels_fast.hip)
+        if (G.rng == VP_RNG_SAMPLERH) return fail(VP_E_STATE, "VP_ARITH_FAST is not built for VP_RNG_SAMPLERH (the parity mode is exact by definition)");
+        if (G.est == VP_EST_BOUNDED) return fail(VP_E_STATE, "VP_ARITH_FAST is not built for VP_EST_BOUNDED");
+        if (G.env_mis) return fail(VP_E_STATE, "VP_ARITH_FAST is built for passive environment lighting only");
+        if (G.trk) return fail(VP_E_STATE, "VP_ARITH_FAST is built for spectral tracking only");
+        if (G.count) return fail(VP_E_STATE, "work counters are not built for VP_ARITH_FAST");
+    }
+    G.last_arith = G.arith;   // (vp_last_arithmetic: the mode of the last render call, whatever classes its pixels fall in)
     if (G.est == VP_EST_DECOMP && first + nframes - 1 > 10 && !G.S.opacity)
         return fail(VP_E_NOOPACITY, "frames beyond 10 need precompute_opacity (kernel.cu:2183, host.cpp:336-343)");
     LaunchDev L = {};
@@ -117,10 +127,11 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     {
         // global majorant: one majorant for the whole walk, checked here; decomposition: approach_local_k checks each segment's own
         bool identity = true;
-        if (G.est == VP_EST_GLOBAL) rc = ensure_light_identity(p, &identity);
+        if (G.est == VP_EST_GLOBAL) rc = G.arith == VP_ARITH_FAST ? ensure_fast_identity(p, &identity) : ensure_light_identity(p, &identity);
         if (rc) return rc;
-        approach = true;
-        if (!identity)
+        // (fast arithmetic: only where its own null collision in empty space is neutral -- else render_k walks, as in a one-frame launch)
+        approach = identity || G.arith != VP_ARITH_FAST;
+        if (!identity && approach)
         {
             // the walk's null collisions change the throughput: render_k looks it up by their number (the light kernel's table)
             rc = ensure_thr_table(p, &L.thr_table);
@@ -340,7 +351,8 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
                     L.approach_steps = G.approach_steps;
                     L.approach_fshift = 0;
                     while (L.approach_fshift < G.approach_fshift_max && (2u << L.approach_fshift) <= (unsigned)f) L.approach_fshift++;
-                    launch_approach(S, L, G.est, G.rng, G.quant, T.stream);
+                    if (G.arith == VP_ARITH_FAST) launch_approach_fast(S, L, G.est, G.rng, G.quant, T.stream);
+                    else launch_approach(S, L, G.est, G.rng, G.quant, T.stream);
                     le = hipGetLastError();
                     G.last_approach = (int)L.approach;
                     G.last_approach_table = (G.est == VP_EST_DECOMP && G.quant && L.seg_table && L.approach_fshift == 6u) ? 1 : 0;
@@ -354,7 +366,8 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
                 }
                 if (le == hipSuccess)
                 {
-                    launch_render(S, L, G.est, G.rng, G.quant, G.count, lds_form, G.env_mis, G.trk, (int)blocks, T.stream);
+                    if (G.arith == VP_ARITH_FAST) launch_render_fast(S, L, G.est, G.rng, G.quant, G.count, lds_form, G.env_mis, G.trk, (int)blocks, T.stream);
+                    else launch_render(S, L, G.est, G.rng, G.quant, G.count, lds_form, G.env_mis, G.trk, (int)blocks, T.stream);
                     le = hipGetLastError();
                 }
                 // The LDS-table kernel holds 2 x 64 KiB of a CU's LDS with 2 x 512 threads: four waves per SIMD, where the
@@ -368,7 +381,8 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
                     if (!G.aux_ev[ti][1] && hipEventCreateWithFlags(&G.aux_ev[ti][1], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); G.aux_ev[ti][1] = nullptr; }
                     if (G.aux_stream[ti] && G.aux_ev[ti][1] && hipStreamWaitEvent(G.aux_stream[ti], G.aux_ev[ti][0], 0) == hipSuccess)
                     {
-                        launch_render(S, L, G.est, G.rng, G.quant, G.count, 0, G.env_mis, G.trk, G.num_cu, G.aux_stream[ti]);
+                        if (G.arith == VP_ARITH_FAST) launch_render_fast(S, L, G.est, G.rng, G.quant, G.count, 0, G.env_mis, G.trk, G.num_cu, G.aux_stream[ti]);
+                        else launch_render(S, L, G.est, G.rng, G.quant, G.count, 0, G.env_mis, G.trk, G.num_cu, G.aux_stream[ti]);
                         le = hipGetLastError();
                         if (le == hipSuccess && (hipEventRecord(G.aux_ev[ti][1], G.aux_stream[ti]) != hipSuccess || hipStreamWaitEvent(T.stream, G.aux_ev[ti][1], 0) != hipSuccess))
                             le = hipGetLastError();
@@ -481,6 +495,7 @@ int vp_last_approach_mode(void) { return G.last_approach; }
 int vp_last_approach_table(void) { return G.last_approach_table; }
 int vp_last_light_const(void) { return G.last_light_const; }
 int vp_last_lds_form(void) { return G.last_lds_form; }
+int vp_last_arithmetic(void) { return G.last_arith; }
 int vp_lookahead_stats(unsigned* launched, unsigned* cancelled_in_flight)
 {
     if (launched) *launched = G.la_launched;

@@ -171,6 +171,8 @@ struct State
     int         last_approach_table = 0;      // vp_last_approach_table
     int         last_light_const = 0;         // vp_last_light_const
     int         last_lds_form = 0;            // vp_last_lds_form
+    int         arith       = VP_ARITH_EXACT;   // vp_set_arithmetic: the general class's integrator in the exact or the fast arithmetic
+    int         last_arith  = VP_ARITH_EXACT;   // vp_last_arithmetic
     unsigned    la_launched = 0, la_cancelled = 0;   // vp_lookahead_stats
     bool        use_const_rows = true;        // VP_NO_CONST_ROWS=1: per-pixel constants are staged for every frame, as before round 4's end
     unsigned    last_const_from = 0;          // LaunchDev::const_from of the last staged launch (a look-ahead slot keeps it for its add-kernels)
@@ -195,6 +197,8 @@ struct State
     float       light_key[7] = {};
     unsigned long long light_epoch = ~0ull;
     bool        light_const = false;
+    float       fast_identity_key[5] = {};   // the same question for the global majorant in the fast arithmetic (ensure_fast_identity)
+    bool        fast_identity_valid = false, fast_identity = false;
     float*      d_thr       = nullptr;    // throughput after n null collisions in empty space (light kernel, global majorant)
     float       thr_key[5]  = {};
     bool        thr_valid   = false;
@@ -260,6 +264,7 @@ int    ensure_crawl_table(const Param* p, const float4** out);
 int    ensure_sun_clip(const unsigned short** out, float* ds);
 int    ensure_light_const(const Param* p, bool* out);
 int    ensure_light_identity(const Param* p, bool* out);
+int    ensure_fast_identity(const Param* p, bool* out);
 int    ensure_bound_mask();
 int    exit_flights(LaunchDev& L);
 int    ensure_thr_table(const Param* p, const float** out);

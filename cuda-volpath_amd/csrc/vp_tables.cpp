@@ -275,6 +275,33 @@ int ensure_light_identity(const Param* p, bool* out)
     return VP_OK;
 }
 
+// The same check for the global-majorant estimator in the fast arithmetic (vp_kernels_fast.hip: light_identity_k with v_rcp_f32): whether
+// approach_k may skip the camera ray's null collisions in empty space that the fast render_k would otherwise make.  A medium neutral in
+// IEEE binary32 need not be neutral here; where it is not, the fast mode walks without approach_k (no throughput table: that table is
+// the exact arithmetic's), so that a staged launch computes what a one-frame launch computes.
+int ensure_fast_identity(const Param* p, bool* out)
+{
+    const float key[5] = {p->sigma_t.x, p->sigma_t.y, p->sigma_t.z, p->density, p->g};
+    if (!G.fast_identity_valid || memcmp(key, G.fast_identity_key, sizeof key) != 0)
+    {
+        if (!G.d_light_flag) HIPCHK(hipMalloc((void**)&G.d_light_flag, 9 * sizeof(unsigned)));
+        const unsigned one = 1u;
+        unsigned flag = 0u;
+        HIPCHK(hipMemcpyAsync(G.d_light_flag, &one, sizeof one, hipMemcpyHostToDevice, G.stream));
+        ParamDev P;
+        memcpy(&P, p, sizeof(Param));
+        launch_light_identity_fast(P, false, G.d_light_flag + 1, G.d_light_flag, G.stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&flag, G.d_light_flag, sizeof flag, hipMemcpyDeviceToHost, G.stream));
+        HIPCHK(hipStreamSynchronize(G.stream));
+        G.fast_identity = flag == 1u;
+        memcpy(G.fast_identity_key, key, sizeof key);
+        G.fast_identity_valid = true;
+    }
+    *out = G.fast_identity;
+    return VP_OK;
+}
+
 // The light kernel of the global-majorant estimator looks the throughput of a path up by its number of null collisions
 // (vp_kernels.hip thr_table_k); the sequence depends on sigma_t, density and g only.
 int ensure_thr_table(const Param* p, const float** out)

@@ -23,6 +23,8 @@ static void usage()
     printf("volpath_render [--julia N | --bin file.bin | --vdb file.vdb] [--size W H] [--spp N] [--preset 0..12]\n"
            "               [--density D] [--g G] [--estimator decomp|global|bounded] [--brick B] [--rng samplerh|philox|philox7]\n"
            "               [--tracking spectral|scalar|multichannel] [--env passive|mis]\n"
+           "               [--arith exact|fast]             fast: hardware log/exp/rcp/sqrt/sin/cos in the integrator, within the\n"
+           "                                                tolerance of include/volpath.h (--rng philox|philox7, spectral, passive)\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -36,7 +38,7 @@ int main(int argc, char** argv)
     int         julia = 128, W = 400, H = 300, spp = 16, preset = 12, brick = 1, batch = 0;
     float       density = 800.0f, g = 0.877f, sunx = 0.5f, suny = 0.2f;
     int         philox = 0;   // 0 sampler.h, 1 Philox2x32-10, 2 Philox2x32-7
-    int         est = VP_EST_DECOMP, tracking = VP_TRACK_SPECTRAL, env_mode = VP_ENV_PASSIVE;
+    int         est = VP_EST_DECOMP, tracking = VP_TRACK_SPECTRAL, env_mode = VP_ENV_PASSIVE, arith = VP_ARITH_EXACT;
     std::string bin, vdb, out = "output0.ppm", devlist;
     int         gpus = 1;
     for (int i = 1; i < argc; i++)
@@ -66,6 +68,14 @@ int main(int argc, char** argv)
             tracking = !strcmp(t, "scalar") ? VP_TRACK_SCALAR : !strcmp(t, "multichannel") ? VP_TRACK_MULTI_CHANNEL : VP_TRACK_SPECTRAL;
         }
         else if (a == "--env") { need(1); env_mode = !strcmp(argv[++i], "mis") ? VP_ENV_MIS : VP_ENV_PASSIVE; }
+        else if (a == "--arith")
+        {
+            need(1);
+            const char* m = argv[++i];
+            if (!strcmp(m, "exact")) arith = VP_ARITH_EXACT;
+            else if (!strcmp(m, "fast")) arith = VP_ARITH_FAST;
+            else { fprintf(stderr, "unknown --arith %s\n", m); usage(); return 2; }
+        }
         else if (a == "--sun") { need(2); sunx = (float)atof(argv[++i]); suny = (float)atof(argv[++i]); }
         else if (a == "--batch") { need(1); batch = atoi(argv[++i]); }
         else if (a == "--out") { need(1); out = argv[++i]; }
@@ -90,6 +100,11 @@ int main(int argc, char** argv)
 
     // ---- the GPUs: one context per rank (a single rank runs in the default context, as the reference's host would)
     if (gpus < 1) { usage(); return 2; }
+    if (arith == VP_ARITH_FAST && (philox == 0 || est == VP_EST_BOUNDED || tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE))
+    {
+        fprintf(stderr, "--arith fast needs --rng philox|philox7, --estimator decomp|global, spectral tracking and --env passive\n");
+        return 2;
+    }
     std::vector<int> devices;
     for (size_t pos = 0; pos < devlist.size();)
     {
@@ -150,6 +165,7 @@ int main(int argc, char** argv)
         vp_set_estimator(est);
         if (vp_set_tracking(tracking) || vp_set_envmap_sampling(env_mode) || vp_set_shard(r, gpus)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
         vp_set_rng(philox == 2 ? VP_RNG_PHILOX7 : philox ? VP_RNG_PHILOX : VP_RNG_SAMPLERH, 0x9E3779B9u, 0x85EBCA6Bu);
+        if (vp_set_arithmetic(arith)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
         // frame buffer (CudaFrameBuffer host.cpp:358-389), full frame on every rank: zero outside its tiles
         accum[r] = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
         if (!accum[r]) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }

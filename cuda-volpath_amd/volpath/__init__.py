@@ -17,6 +17,9 @@ EST_GLOBAL, EST_DECOMP, EST_BOUNDED = 0, 1, 2
 RNG_SAMPLERH, RNG_PHILOX, RNG_PHILOX7 = 0, 1, 2
 ENV_PASSIVE, ENV_MIS = 0, 1
 TRACK_SPECTRAL, TRACK_SCALAR, TRACK_MULTI_CHANNEL = 0, 1, 2
+ARITH_EXACT, ARITH_FAST = 0, 1
+# include/volpath.h VP_ARITH_FAST_REL_L2: the stated bound on ||I_fast - I_exact||_2 / ||I_exact||_2 (mean images of 1024 frames)
+ARITH_FAST_REL_L2 = 2e-3
 
 # every symbol include/volpath.h declares (tests check the library exports each one)
 PART1_SYMBOLS = ["init_cuda", "set_texture_filter_mode", "free_cuda_buffers", "precompute_opacity", "init_envmap",
@@ -24,7 +27,7 @@ PART1_SYMBOLS = ["init_cuda", "set_texture_filter_mode", "free_cuda_buffers", "p
                  "render_kernel", "scale", "gamma_correct"]
 PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_device", "vp_set_stream", "vp_get_stream", "vp_synchronize",
                  "vp_set_estimator", "vp_set_rng", "vp_set_envmap_sampling", "vp_get_env_tables", "vp_set_lookahead", "vp_set_tracking", "vp_set_bound_brick", "vp_set_shard", "vp_render_frames",
-                 "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists",
+                 "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_intersect_box",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -348,6 +351,17 @@ def lookahead_stats():
 def last_lds_form():
     """0 / 1 / 2: how the last launch of the decomposition estimator read its brick table (vp_last_lds_form)"""
     return int(lib().vp_last_lds_form())
+
+
+def set_arithmetic(mode):
+    """ARITH_EXACT (the default: bit for bit the oracle's) or ARITH_FAST (hardware transcendentals and reciprocals, within
+    ARITH_FAST_REL_L2 of the exact image; counter-based streams, spectral tracking, passive environment only)"""
+    _chk(lib().vp_set_arithmetic(mode))
+
+
+def last_arithmetic():
+    """ARITH_EXACT / ARITH_FAST: the arithmetic of the last render launch of the current context (vp_last_arithmetic)"""
+    return int(lib().vp_last_arithmetic())
 
 
 def last_light_const():

@@ -165,6 +165,30 @@ int vp_set_tracking(int mode);                         /* default VP_TRACK_SPECT
 int vp_set_lookahead(int max_frames);
 enum { VP_ENV_PASSIVE = 0, VP_ENV_MIS = 1 };
 int vp_set_envmap_sampling(int mode);                  /* default VP_ENV_PASSIVE */
+/* Arithmetic of the integrator.  VP_ARITH_EXACT, the default, is the parity contract: correctly rounded
+ * binary32 divides and roots, the Cephes polynomials of vp_math.h, no contraction -- bit for bit the CPU oracle's.  VP_ARITH_FAST
+ * trades the last ulps for issue slots: the integrator's logarithm, exponential, divides, reciprocals, roots, normalisations and
+ * the phase function's sine and cosine become the hardware's single instructions (v_log_f32, v_exp_f32, v_rcp_f32, v_sqrt_f32,
+ * v_rsq_f32, v_sin_f32, v_cos_f32), each written out in the source, nothing left to the compiler.  It is deterministic like the
+ * exact mode -- two runs, render_frames against render_kernel's look-ahead, a sharded render against a whole one give the same
+ * bits -- but it is no longer the oracle's, and the same estimator's result moves within the tolerance below.
+ *   Built for: VP_RNG_PHILOX / VP_RNG_PHILOX7, VP_TRACK_SPECTRAL, VP_ENV_PASSIVE, VP_EST_GLOBAL / VP_EST_DECOMP, uchar and float
+ *   volumes, work counters off.  Any other combination makes the render fail with VP_E_STATE (the context stays usable).
+ *   Unchanged by the mode (exact in both): the per-pixel tables and certificates, the pixels whose camera ray misses the box or
+ *   meets certified-empty cells only (pixel classes 1 and 2 of vp_get_pixel_table: bit-identical), scale and gamma_correct.
+ *   Tolerance (mean-radiance images I of N frames, the same stream and keys in both modes): the relative L2 distance
+ *   ||I_fast - I_exact||_2 / ||I_exact||_2 over the whole image is at most VP_ARITH_FAST_REL_L2 = 2e-3 at N = 1024 on BASELINE
+ *   configs 2 and 3 and the chromatic c4s -- measured 4.7e-4, 3.7e-4 and 5.5e-4: the bound is 3.6 times the largest (c4f, 256
+ *   frames: 1.5e-3) --, and the image mean moves by less than 2e-3 per channel (measured: below 3e-6).  The fast mode changes
+ *   95-99 % of the general pixels' samples; it is unbiased (an estimator of the same image), not equal.  The hardware instructions
+ *   flush denormal inputs: a sample whose collision weight comes out infinite that way (a path whose throughput fell below
+ *   2^-126) is written as 0.
+ *   Speed (kernel time, 1024 frames): +12 % (c3) to +20 % (c2) on the benchmark workloads (profiles/experiments/r06_arith_fast.txt).
+ * vp_set_arithmetic is per context; it checks its argument before it touches the device and stops render_kernel's look-ahead
+ * batches in flight (frames staged in one mode are never served in the other). */
+enum { VP_ARITH_EXACT = 0, VP_ARITH_FAST = 1 };
+#define VP_ARITH_FAST_REL_L2 2e-3
+int vp_set_arithmetic(int mode);                       /* default VP_ARITH_EXACT */
 /* test hook: the tables of the current environment: cdf_y[h], cdf_x[w*h] (row CDFs), HDRpdfnormAlt; any may be NULL */
 int vp_get_env_tables(float* cdf_y, float* cdf_x, float* pdfnorm_alt);
 /* brick edge (power of two, 1 = the reference's per-voxel table) used by the NEXT init_cuda */
@@ -222,6 +246,9 @@ int vp_last_light_const(void);
  * most four distinct pairs -- binary volumes --, achromatic media, timed launches of the counter-based streams).  Performance
  * only: the three forms render the same bits (VP_NO_LDS_BOUNDS / VP_NO_LDS_COMPACT select them). */
 int vp_last_lds_form(void);
+/* VP_ARITH_EXACT / VP_ARITH_FAST: the arithmetic mode of the last render call of this context (its general pixels ran in that mode;
+ * the other pixel classes are the same in both) */
+int vp_last_arithmetic(void);
 /* test hook: look-ahead batches this context has launched so far (render_kernel's staged frames), and how many of them were told to
  * stop while they were still running (a setter, a camera move); either pointer may be NULL */
 int vp_lookahead_stats(unsigned* launched, unsigned* cancelled_in_flight);
