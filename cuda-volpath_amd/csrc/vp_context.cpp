@@ -706,13 +706,17 @@ int vp_set_shard(int rank, int world)
 }
 int vp_test_math(int which, const float* in, float* out, int n)
 {
+    if (which < 0 || which > 11) return fail(VP_E_ARG, "vp_test_math: unknown helper %d (0..11)", which);
+    if (n < 0) return fail(VP_E_ARG, "vp_test_math: negative count %d", n);
     int rc = ensure_device();
     if (rc) return rc;
+    if (n == 0) return VP_OK;
     float *di = nullptr, *d_o = nullptr;
     HIPCHK(hipMalloc((void**)&di, (size_t)n * 4));
     HIPCHK(hipMalloc((void**)&d_o, (size_t)n * 4));
     HIPCHK(hipMemcpy(di, in, (size_t)n * 4, hipMemcpyHostToDevice));
-    launch_test_math(which, di, d_o, n, G.stream);
+    if (G.arith == VP_ARITH_FAST) launch_test_math_fast(which, di, d_o, n, G.stream);   // (the helpers of the context's renders)
+    else launch_test_math(which, di, d_o, n, G.stream);
     HIPCHK(hipStreamSynchronize(G.stream));
     HIPCHK(hipMemcpy(out, d_o, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipFree(di));
@@ -776,7 +780,8 @@ int vp_test_hg(const float* g, const float* r0, const float* r1, const float* no
     HIPCHK(hipMemcpy(d1, r1, b, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dn, normal_xyz, 3 * b, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dc, cos_query, b, hipMemcpyHostToDevice));
-    launch_test_hg(dg, d0, d1, dn, dc, dd, de, n, G.stream);
+    if (G.arith == VP_ARITH_FAST) launch_test_hg_fast(dg, d0, d1, dn, dc, dd, de, n, G.stream);
+    else launch_test_hg(dg, d0, d1, dn, dc, dd, de, n, G.stream);
     HIPCHK(hipStreamSynchronize(G.stream));
     HIPCHK(hipMemcpy(dir_xyz, dd, 3 * b, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(eval, de, b, hipMemcpyDeviceToHost));

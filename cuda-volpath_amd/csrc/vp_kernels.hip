@@ -907,16 +907,8 @@ __global__ void accumulate_k(float4* dst, const float4* src, size_t n)
 }
 
 // ---- test kernels
-// the phase-function block of the integrator (kernel.cu:2301-2303 with :557-598) and HGPhaseFunction::evaluate (:600-603)
-__global__ void test_hg_k(const float* g, const float* r0, const float* r1, const float* nrm, const float* cosq, float* dir, float* ev, int n)
-{
-    int i = threadIdx.x + blockIdx.x * blockDim.x;
-    if (i >= n) return;
-    Frame fr(f3{nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]});
-    f3    d = normalize(fr.to_world(hg_sample_local(g[i], r0[i], r1[i])));
-    dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z;
-    ev[i] = hg_eval(g[i], cosq[i]);
-}
+// test_hg_k, test_math_k: vp_test_kernels.h (compiled in both arithmetic modes)
+#include "vp_test_kernels.h"
 // intersectBox kernel.cu:654-680 against the current volume box
 __global__ void test_box_k(SceneDev S, const float* o, const float* d, int* hit, float* tn, float* tf, int n)
 {
@@ -933,23 +925,6 @@ __global__ void test_env_k(SceneDev S, const float* d, float* out, int n)
     if (i >= n) return;
     f3 c = eval_envmap(S, f3{d[3 * i], d[3 * i + 1], d[3 * i + 2]});
     out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
-}
-__global__ void test_math_k(int which, const float* in, float* out, int n)
-{
-    int i = threadIdx.x + blockIdx.x * blockDim.x;
-    if (i >= n) return;
-    float x = in[i], s, c, r;
-    switch (which)
-    {
-        case 0: r = logf_(x); break;
-        case 1: r = expf_(x); break;
-        case 2: sincosf_(x, s, c); r = s; break;
-        case 3: sincosf_(x, s, c); r = c; break;
-        case 4: r = acosf_(x); break;
-        case 5: r = atanf_(x); break;
-        default: r = pow15f_(x); break;
-    }
-    out[i] = r;
 }
 template <class RNG>
 __global__ void test_rng_k(unsigned x, unsigned y, unsigned frame, unsigned k0, unsigned k1, int n, float* out)

@@ -32,6 +32,7 @@ namespace vp
 namespace fast
 {
 #include "vp_integrator.h"
+#include "vp_test_kernels.h"
 
 template <int EST, class RNG, bool QUANT, int LDSB, bool ACH>
 static void launch_render_t(const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
@@ -132,5 +133,15 @@ void launch_approach_fast(const SceneDev& S, const LaunchDev& L, int est, int rn
         abort();
 #endif
     }
+}
+
+// the test hooks in this arithmetic (vp_test_kernels.h; vp_context.cpp vp_test_math / vp_test_hg in a fast context)
+void launch_test_hg_fast(const float* g, const float* r0, const float* r1, const float* nrm, const float* cosq, float* dir, float* ev, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(fast::test_hg_k, dim3((n + 255) / 256), dim3(256), 0, st, g, r0, r1, nrm, cosq, dir, ev, n);
+}
+void launch_test_math_fast(int which, const float* in, float* out, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(fast::test_math_k, dim3((n + 255) / 256), dim3(256), 0, st, which, in, out, n);
 }
 }  // namespace vp

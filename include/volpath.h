@@ -295,7 +295,12 @@ int vp_set_exit_flights(int mode);
  * Test hook: the sequence is three float32 operations per step and can be restated anywhere. */
 int vp_get_null_collision_table(const Param* p, float* dst, size_t count);
 
-/* building blocks exposed for parity tests (device execution, host arrays) */
+/* building blocks exposed for parity tests (device execution, host arrays)
+ * vp_test_math: out[i] = helper(in[i]) for the integrator's elementary helpers (vp_math.h): 0 logf_, 1 expf_, 2 / 3 the sine /
+ * cosine of sincosf_ (radians), 4 acosf_, 5 atanf_, 6 pow15f_, 7 rcp_, 8 sqrt_, 9 rsqrt_, 10 / 11 the sine / cosine of
+ * sincos_turns_ (the argument in turns: sin(2 pi t)).  vp_test_math and vp_test_hg run the helpers of the current context's
+ * arithmetic mode (vp_set_arithmetic), as its renders do.  vp_test_math refuses a `which` outside 0..11 and n < 0 with VP_E_ARG
+ * before it touches the device. */
 int vp_test_math(int which, const float* in, float* out, int n);
 int vp_test_rng(int mode, uint32_t x, uint32_t y, uint32_t frame, uint32_t k0, uint32_t k1, int n, float* out);
 int vp_test_sample_density(const float* pos_xyz, float* out, int n);

@@ -1530,7 +1530,14 @@ void vpo_math_array(int which, const float* in, float* out, int n)
             case 3: vpo_sincosf(in[i], &s, &c); out[i] = c; break;
             case 4: out[i] = vpo_acosf(in[i]); break;
             case 5: out[i] = vpo_atanf(in[i]); break;
-            default: out[i] = vpo_pow15f(in[i]); break;
+            case 6: out[i] = vpo_pow15f(in[i]); break;
+            /* the codes of vp_test_math (include/volpath.h) for the helpers the exact GPU build writes as IEEE expressions */
+            case 7: out[i] = 1.0f / in[i]; break;
+            case 8: out[i] = sqrtf(in[i]); break;
+            case 9: out[i] = 1.0f / sqrtf(in[i]); break;
+            case 10: vpo_sincosf((2.0f * VP_PI) * in[i], &s, &c); out[i] = s; break;   /* sincos_turns_: the argument in turns */
+            case 11: vpo_sincosf((2.0f * VP_PI) * in[i], &s, &c); out[i] = c; break;
+            default: out[i] = NAN; break;
         }
     }
 }

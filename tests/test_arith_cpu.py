@@ -42,3 +42,16 @@ def test_cli_arith_flag():
     # the fast mode needs a counter-based stream: refused before any device is touched
     r = subprocess.run([EXE, "--arith", "fast", "--rng", "samplerh"], capture_output=True, text=True)
     assert r.returncode == 2 and "--arith fast" in r.stderr
+
+
+@pytest.mark.parametrize("which,n", [(-1, 4), (12, 4), (99, 4), (0, -1), (7, -5)])
+def test_test_math_refuses_bad_arguments_before_the_device(which, n):
+    """vp_test_math: `which` outside 0..11 (include/volpath.h) and n < 0 are VP_E_ARG before any device is touched -- an unknown code
+    no longer runs some helper silently"""
+    import volpath
+    assert volpath.lib().vp_test_math(which, None, None, n) == -3   # VP_E_ARG
+    assert "vp_test_math" in volpath.lib().vp_last_error().decode()
+    if n >= 0:
+        import numpy as np
+        with pytest.raises(volpath.VolpathError, match="vp_test_math"):
+            volpath.test_math(which, np.ones(n, np.float32))

@@ -262,6 +262,21 @@ def test_math_accuracy(oracle):
         [np.float32(np.pi / 2), -np.float32(np.pi / 2), 0.0]
 
 
+def test_math_array_codes_7_to_11(oracle):
+    """the codes vp_test_math shares with the oracle for the helpers the exact build writes as IEEE expressions: rcp_, sqrt_, rsqrt_
+    and sincos_turns_ (sincosf_ of fl(2 pi) * t); an unknown code is NaN, not some other helper"""
+    rng = np.random.default_rng(3)
+    x = (2.0 ** rng.uniform(-120, 120, 50000)).astype(np.float32)
+    assert np.array_equal(oracle.math_array(7, x), np.float32(1) / x)
+    assert np.array_equal(oracle.math_array(8, x), np.sqrt(x))
+    assert np.array_equal(oracle.math_array(9, x), np.float32(1) / np.sqrt(x))
+    t = rng.random(50000).astype(np.float32)
+    a = (np.float32(2 * np.pi) * t).astype(np.float32)
+    assert np.array_equal(oracle.math_array(10, t), oracle.math_array(2, a))
+    assert np.array_equal(oracle.math_array(11, t), oracle.math_array(3, a))
+    assert np.isnan(oracle.math_array(12, x[:4])).all()
+
+
 def test_scale_gamma_and_mat(oracle):
     import ctypes as C
     src = np.random.default_rng(0).random((5, 4), dtype=np.float32)

@@ -236,6 +236,22 @@ def test_math_and_rng_bits(vp, oracle):
     for which, x in cases.items():
         assert np.array_equal(vp.test_math(which, x), oracle.math_array(which, x)), which
     assert vp.test_math(0, np.zeros(1, np.float32))[0] == -np.inf
+    # the edges of the helpers' domains (test_helpers_gpu.py) and the codes of rcp_, sqrt_, rsqrt_ and sincos_turns_: the exact
+    # helpers equal the oracle there too
+    import test_helpers_gpu as TH
+    xa, xc, xt = TH._exact_only_inputs()
+    guards = np.array([-87.0, np.nextafter(np.float32(-87), np.float32(-100)), 88.0, np.nextafter(np.float32(88), np.float32(100)),
+                       0.0, -0.0, -np.inf, np.inf], np.float32)
+    xr = TH.normal_inputs(-125.0, 125.0)
+    xr[::2] = -xr[::2]
+    den = np.array([3.0e-39, 5.0e-39, 1.0e-38, 1.1e-38, 0.0], np.float32)
+    edge = {0: [TH.log_inputs(), np.array([0.0, -0.0], np.float32)], 1: [TH.exp_inputs(), guards], 2: [xa], 3: [xa],
+            4: [xc, np.array([1.5, -1.5, 2.0, -2.0], np.float32)], 5: [xt, np.array([np.inf, -np.inf, np.nan, 1e-40, -1e-40], np.float32)],
+            6: [TH.normal_inputs(-126.0, 84.0)], 7: [xr, den], 8: [TH.normal_inputs(seed=15), den], 9: [TH.normal_inputs(seed=15), den],
+            10: [TH.turns_inputs()], 11: [TH.turns_inputs()]}
+    for which, xs in edge.items():
+        x = np.concatenate(xs)
+        assert np.array_equal(vp.test_math(which, x), oracle.math_array(which, x), equal_nan=True), which
     for mode in (0, 1, 2):
         a = vp.test_rng(mode, 3, 5, 7, 64, key=(11, 22))
         b = oracle.rng_stream(mode, 3, 5, 7, 64, key=(11, 22))

@@ -50,8 +50,30 @@ def _slab(o, d, bmin=-1.0, bmax=1.0):
     return (tmax > tmin) & (tmax >= 1e-3), tmin, tmax
 
 
+@pytest.fixture
+def fast(vp):
+    """a context of its own in the fast arithmetic: the session's `vp` context stays exact"""
+    c = vp.Context(0)
+    try:
+        with c:
+            vp.set_arithmetic(vp.ARITH_FAST)
+            yield c
+    finally:
+        c.destroy()
+
+
 # ------------------------------------------------------------------------------------------ component known answers
 def test_hg_sample_and_evaluate_match_closed_forms(vp):
+    _hg_closed_forms(vp)
+
+
+def test_hg_sample_and_evaluate_match_closed_forms_fast(vp, fast):
+    """the same block with the fast helpers (a * v_rcp_f32(b), v_sqrt_f32, v_rsq_f32, v_sin_f32 / v_cos_f32 of the turns): the same
+    bounds -- each is several ulps wide where the fast instructions add about one"""
+    _hg_closed_forms(vp)
+
+
+def _hg_closed_forms(vp):
     rng = np.random.default_rng(21)
     n = 20000
     g = rng.choice(np.array([0.877, 0.5, -0.6, 0.0, 1e-7, 0.99, -0.3, 0.2], np.float32), n)
@@ -244,6 +266,18 @@ def test_white_furnace(vp, est, env_mode, track, sigma_t):
     density, phase function, majorant scheme or light-sampling strategy.  Exact (3e-4: binary32 drift of a weight that is 1 in exact arithmetic) where the estimator's weights are
     identically 1 (achromatic spectral tracking and scalar tracking, passive environment); otherwise within 5 standard
     errors per 8x8-pixel block and 0.5 % on the image mean."""
+    _white_furnace(vp, est, env_mode, track, sigma_t, fast=False)
+
+
+@pytest.mark.parametrize("est", [0, 1])
+@pytest.mark.parametrize("sigma_t", [(1, 1, 1), (1.0, 0.7, 0.4)])
+def test_white_furnace_fast(vp, fast, est, sigma_t):
+    """The furnace in the fast arithmetic, for what it builds: global majorant and decomposition, passive environment, spectral
+    tracking, achromatic and chromatic media (the same keys as the exact cases)."""
+    _white_furnace(vp, est, 0, 0, sigma_t, fast=True)
+
+
+def _white_furnace(vp, est, env_mode, track, sigma_t, fast):
     frames = 96
     try:
         P, c, W, H = _furnace_scene(vp, est, env_mode, track, sigma_t, key=(31, est * 5 + env_mode * 3 + track))
@@ -267,8 +301,21 @@ def test_white_furnace(vp, est, env_mode, track, sigma_t):
     assert (per[..., 3] > 0).mean() > 0.05                  # the medium really scatters
     mean = rgb.mean(0)
     exact = env_mode == 0 and (track == 1 or (track == 0 and len(set(sigma_t)) == 1))
-    if exact:
+    if exact and not fast:
         assert np.abs(rgb / c - 1).max() < 3e-4
+        return
+    if exact:
+        # fast: the weight of a collision is (a * ((inv_sigma * c) * v_rcp_f32(P))) with inv_sigma = v_rcp_f32(sigma'): 1 in exact
+        # arithmetic, not in binary32.  Seven roundings per collision -- five IEEE half-ulps and two v_rcp_f32 of about one ulp --
+        # bound its drift by DRIFT = 9 * 2^-24 = 5.4e-7, so a path of n collisions ends within n * DRIFT of c.  n is not recorded, but
+        # the depth d (scatters / restart segments, alpha) is: between two scatters a path makes Poisson(sigma' * chord) collisions,
+        # sigma' * chord <= density * box diagonal = 6 * 2 sqrt(3) = 20.8 (global majorant; the local majorants are smaller), so at
+        # most 20.8 + 8 sqrt(20.8) = 57 per leg across the ~1.7e5 paths (8 standard deviations) -- n <= 57 (d + 1).
+        # measured on the MI355X: largest drift 2.0e-6 (global majorant) and 7.7e-7 (decomposition), at most 5.5 % of this bound
+        n_max = 57.0 * (depth + 1.0)
+        drift = np.abs(rgb / c - 1).max(-1)
+        assert (drift <= 9 * 2.0 ** -24 * n_max + 3e-6).all(), float((drift / (9 * 2.0 ** -24 * n_max + 3e-6)).max())
+        assert np.abs(mean.mean((0, 1)) / c - 1).max() < 3e-4      # no systematic drift: the rounding goes both ways
         return
     assert np.abs(mean.mean((0, 1)) / c - 1).max() < 5e-3
     blk = rgb.reshape(frames, H // 4, 4, W // 4, 4, 3).mean(axis=(2, 4))      # 4x4-pixel blocks per frame
@@ -296,6 +343,16 @@ def _slab_scene(vp, est, albedo, env_c, sun_dir, sun_power, density, key, W=40, 
 
 @pytest.mark.parametrize("est", [0, 2])
 def test_free_flight_transmittance_of_a_homogeneous_slab(vp, est):
+    _free_flight(vp, est)
+
+
+def test_free_flight_transmittance_of_a_homogeneous_slab_fast(vp, fast):
+    """the global-majorant estimator in the fast arithmetic, with the exact case's key and bounds (statistical: the fast helpers move
+    a sample by ulps, far below the binomial error)"""
+    _free_flight(vp, 0)
+
+
+def _free_flight(vp, est):
     """Pure absorber (albedo 0) in front of a constant environment: radiance = c * P(no collision along the camera ray)
     = c * exp(-rho * chord).  Primary free flight of the global-majorant kernel (kernel.cu:1416-1452) and of the
     restart-segment kernel (:1782-1813; the chord is crossed in 0.05 pieces).  The decomposition kernel is excluded: on a
@@ -322,6 +379,15 @@ def test_free_flight_transmittance_of_a_homogeneous_slab(vp, est):
 
 @pytest.mark.parametrize("est", [0, 2])
 def test_single_scatter_sun_radiance_of_a_homogeneous_slab(vp, est):
+    _single_scatter(vp, est)
+
+
+def test_single_scatter_sun_radiance_of_a_homogeneous_slab_fast(vp, fast):
+    """the global-majorant estimator in the fast arithmetic, with the exact case's key and bounds (statistical)"""
+    _single_scatter(vp, 0)
+
+
+def _single_scatter(vp, est):
     """Black environment, directional sun, albedo a << 1: the radiance is the single-scatter integral
         a * E_sun * p(cos) * int_0^chord rho e^{-rho t} e^{-rho s(t)} dt,   s(t) = distance from x(t) to the box along the sun
     (second order is O(a) smaller).  Exercises the first-collision density, HGPhaseFunction::evaluate, the directional
