@@ -51,7 +51,7 @@ int ensure_device()
     G.num_cu = prop.multiProcessorCount;
     HIPCHK(hipStreamCreateWithFlags(&G.own_stream, hipStreamNonBlocking));
     if (!G.stream) G.stream = G.own_stream;
-    HIPCHK(hipMalloc((void**)&G.d_queue, 6 * kQueueWords * sizeof(unsigned)));  // (caller's stream + two look-ahead slots) x two tile classes
+    HIPCHK(hipMalloc((void**)&G.d_queue, 2 * kTargets * kQueueWords * sizeof(unsigned)));  // (caller's stream + two look-ahead slots + pipeline slot 1) x two tile classes
     HIPCHK(hipMalloc((void**)&G.d_counters, kCounterWords * sizeof(unsigned long long)));
     HIPCHK(hipMemset(G.d_counters, 0, kCounterWords * sizeof(unsigned long long)));
     HIPCHK(hipMalloc((void**)&G.d_cancel, 3 * sizeof(unsigned)));
@@ -121,6 +121,7 @@ int ensure_device()
     if (knob("VP_LOOKAHEAD_DIV", 1, 16, v)) G.la_div = (int)v;
     if (knob("VP_LOOKAHEAD_NO_SPECULATION", 0, 1, v)) G.la_speculate = v == 0;
     if (knob("VP_NO_LA_CANCEL", 0, 1, v)) G.la_cancel = v == 0;
+    if (knob("VP_NO_PIPELINE", 0, 1, v)) G.pipeline = v == 0;
     if (knob("VP_NO_EXIT", 0, 1, v)) G.use_exit = v == 0;
     if (knob("VP_EXIT_LOCAL", 0, 1, v)) { G.exit_local = v != 0; G.exit_local_auto = false; }
     if (knob("VP_EXIT_K", 1, VP_EXIT_TRIP, v)) G.exit_k = (unsigned)v;
@@ -407,7 +408,12 @@ void init_cuda(void* h_volume, vp_extent volumeSize, bool quantized, const vp_fl
     if (do_init_volume(h_volume, volumeSize, quantized, boxmin, boxmax)) die("init_cuda");
 }
 
-void set_texture_filter_mode(bool bLinearFilter) { G.linear = bLinearFilter; G.S.linear = bLinearFilter ? 1 : 0; }
+// (the setters below first wait for vp_render_frames' pipelined launches in flight: pipe_quiesce)
+void set_texture_filter_mode(bool bLinearFilter)
+{
+    (void)pipe_quiesce();
+    G.linear = bLinearFilter; G.S.linear = bLinearFilter ? 1 : 0;
+}
 
 void free_cuda_buffers(void)
 {
@@ -444,6 +450,7 @@ void set_sun(float* sun_dir, float* sun_power)
     // kernel.cu:1269-1283: disc radiance kept for the depth-0 sun test, directional power = p * pi * (0.45/94)^2
     float r = (float)(0.45 / (double)94.0f);
     float f = 3.1415926535897932384626422832795028841971f * (r * r);
+    (void)pipe_quiesce();
     for (int i = 0; i < 3; i++)
     {
         G.S.sun_dir[i]   = sun_dir[i];
@@ -455,6 +462,7 @@ void set_sun(float* sun_dir, float* sun_power)
 
 void copy_inv_view_matrix(float* invViewMatrix, size_t sizeofMatrix)
 {
+    (void)pipe_quiesce();
     memcpy(G.S.cam, invViewMatrix, sizeofMatrix < sizeof G.S.cam ? sizeofMatrix : sizeof G.S.cam);
     G.have_cam = true;
 }
@@ -469,6 +477,7 @@ void free_rng(void) {}                         // kernel.cu:2331
 
 void render_kernel(vp_dim3, vp_dim3, vp_float4* d_output, int spp, const Param& p)
 {
+    if (pipe_quiesce()) die("render_kernel");   // (the look-ahead's batches do not run beside pipelined launches)
     if (serve_frame(d_output, spp, &p)) die("render_kernel");
 }
 
@@ -556,7 +565,19 @@ int vp_ctx_destroy(vp_ctx* ctx)
         for (auto& ev : D.events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
         for (auto& ev : D.class_events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
         for (auto e : D.event_pool) (void)hipEventDestroy(e);
+        (void)pipe_quiesce();
+        for (int s = 0; s < 2; s++)
+        {
+            if (D.pipe_stream[s]) (void)hipStreamDestroy(D.pipe_stream[s]);
+            if (D.pipe_done[s]) (void)hipEventDestroy(D.pipe_done[s]);
+            if (D.pipe_free[s]) (void)hipEventDestroy(D.pipe_free[s]);
+            if (D.pipe_gate[s]) (void)hipEventDestroy(D.pipe_gate[s]);
+        }
+        if (D.pipe_fence_ev) (void)hipEventDestroy(D.pipe_fence_ev);
+        if (D.last_end) (void)hipEventDestroy(D.last_end);
+        for (auto e : D.class_last_end) if (e) (void)hipEventDestroy(e);
         if (D.d_stage) (void)hipFree(D.d_stage);
+        if (D.d_stage2) (void)hipFree(D.d_stage2);
         if (D.d_crawl) (void)hipFree(D.d_crawl);
         if (D.d_thr) (void)hipFree(D.d_thr);
         if (D.d_sunclip) (void)hipFree(D.d_sunclip);
@@ -566,7 +587,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
         if (D.d_tiles) (void)hipFree(D.d_tiles);
         if (D.d_tile_rows) (void)hipFree(D.d_tile_rows);
         if (D.d_tile_scratch) (void)hipFree(D.d_tile_scratch);
-        for (int i = 0; i < 3; i++)
+        for (int i = 0; i < kTargets; i++)
         {
             if (D.aux_stream[i]) { (void)hipStreamSynchronize(D.aux_stream[i]); (void)hipStreamDestroy(D.aux_stream[i]); }
             if (D.d_appr_aux[i]) (void)hipFree(D.d_appr_aux[i]);
@@ -620,12 +641,14 @@ int vp_synchronize(void)
 }
 int vp_set_estimator(int est)
 {
+    if (int rc = pipe_quiesce()) return rc;
     if (est != VP_EST_GLOBAL && est != VP_EST_DECOMP && est != VP_EST_BOUNDED) return fail(VP_E_ARG, "unknown estimator %d", est);
     G.est = est;
     return VP_OK;
 }
 int vp_set_rng(int mode, uint32_t k0, uint32_t k1)
 {
+    if (int rc = pipe_quiesce()) return rc;
     if (mode != VP_RNG_SAMPLERH && mode != VP_RNG_PHILOX && mode != VP_RNG_PHILOX7) return fail(VP_E_ARG, "unknown rng %d", mode);
     G.rng = mode; G.key0 = k0; G.key1 = k1;
     return VP_OK;
@@ -634,7 +657,7 @@ int vp_set_exit_flights(int mode)
 {
     if (mode < 0 || mode > 2) return fail(VP_E_ARG, "exit flights: 0 off, 1 global-majorant estimator (default), 2 every estimator that has them");
     int rc = ensure_device();   // (first: it parses VP_NO_EXIT / VP_EXIT_LOCAL, which a later call must not override -- ADVICE r4)
-    if (rc) return rc;
+    if (rc || (rc = pipe_quiesce())) return rc;
     G.use_exit = mode != 0; G.exit_local = mode == 2; G.exit_local_auto = false;
     if (G.use_exit && G.have_volume && !G.d_exit && G.d_danger)
     {
@@ -652,6 +675,7 @@ int vp_set_exit_flights(int mode)
 }
 int vp_set_tracking(int mode)
 {
+    if (int rc = pipe_quiesce()) return rc;
     if (mode != VP_TRACK_SPECTRAL && mode != VP_TRACK_SCALAR && mode != VP_TRACK_MULTI_CHANNEL)
         return fail(VP_E_ARG, "unknown tracking mode %d", mode);
     G.trk = mode;
@@ -674,6 +698,7 @@ int vp_set_arithmetic(int mode)
 }
 int vp_set_envmap_sampling(int mode)
 {
+    if (int rc = pipe_quiesce()) return rc;
     if (mode != VP_ENV_PASSIVE && mode != VP_ENV_MIS) return fail(VP_E_ARG, "unknown environment sampling mode %d", mode);
     int rc = ensure_device();
     if (rc) return rc;
@@ -694,12 +719,14 @@ int vp_get_env_tables(float* cdf_y, float* cdf_x, float* pdfnorm_alt)
 }
 int vp_set_bound_brick(int brick)
 {
+    if (int rc = pipe_quiesce()) return rc;
     if (brick < 1 || brick > 64 || (brick & (brick - 1))) return fail(VP_E_ARG, "brick edge must be a power of two in [1,64]");
     G.brick_next = brick;
     return VP_OK;
 }
 int vp_set_shard(int rank, int world)
 {
+    if (int rc = pipe_quiesce()) return rc;
     if (world < 1 || rank < 0 || rank >= world) return fail(VP_E_ARG, "bad shard %d/%d", rank, world);
     G.rank = (unsigned)rank; G.world = (unsigned)world;
     return VP_OK;

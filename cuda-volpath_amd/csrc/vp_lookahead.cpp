@@ -66,6 +66,8 @@ bool la_cancel_running()
 int la_quiesce()
 {
     // every caller is about to change what batches in flight read (tables, lists, the volume): stop them and wait
+    // (and for vp_render_frames' pipelined launches, which read the same: vp_render.cpp)
+    if (int rc = pipe_quiesce()) return rc;
     const bool any = la_cancel_running();
     if (G.la_spec_unserved) { G.la_habit = false; G.la_spec_unserved = false; }   // speculated and nobody came: stop speculating until a real hit
     static const bool dbg = getenv("VP_DEBUG_QUIESCE") != nullptr;

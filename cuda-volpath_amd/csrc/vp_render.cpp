@@ -3,6 +3,32 @@
 
 namespace vph __attribute__((visibility("hidden")))
 {
+// The part of a launch's span [a, b] that the launches timed before it did not cover: from max(a, end) to b, where `end` is the latest
+// end among them (nullptr: none); `end` moves to b when b is later.  Pipelined calls of vp_render_frames overlap (pipe_target): a launch
+// is reported from where its predecessor ended, so the reported times add up to at most the wall time they span.
+static float span_ms(hipEvent_t a, hipEvent_t b, hipEvent_t& end)
+{
+    float ms = 0.0f, since = 0.0f;
+    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0.0f; }
+    if (end && hipEventElapsedTime(&since, end, b) == hipSuccess)
+    {
+        if (since <= 0.0f) return 0.0f;   // inside a span already counted
+        ms = std::min(ms, since);
+    }
+    else (void)hipGetLastError();
+    end = b;
+    return std::max(ms, 0.0f);
+}
+// ... folded into a running sum: the pair goes back to the pool, except an event that is now the latest end
+static void fold_span(hipEvent_t a, hipEvent_t b, hipEvent_t& end, double& sum)
+{
+    hipEvent_t e = end;
+    if (hipEventQuery(b) == hipSuccess) sum += span_ms(a, b, e);
+    else (void)hipGetLastError();   // a launch this old that has not completed is counted without a time rather than waited for
+    put_event(a);
+    if (e == b) { put_event(end); end = b; }
+    else put_event(b);
+}
 // a pair of events around one kernel of a launch (per-class kernel time, vp_render_class_time_ms); best effort
 struct ClassTimer
 {
@@ -21,30 +47,90 @@ struct ClassTimer
         put_event(a); put_event(b); a = b = nullptr;
         while (G.class_events.size() > 3 * kMaxPendingEvents)
         {
-            auto  ev = G.class_events.front();
-            float ms = 0.0f;
+            auto ev = G.class_events.front();
             G.class_events.pop_front();
-            if (hipEventQuery(ev.b) == hipSuccess && hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) G.class_ms[ev.cls] += ms;
-            else (void)hipGetLastError();
-            put_event(ev.a); put_event(ev.b);
+            fold_span(ev.a, ev.b, G.class_last_end[ev.cls], G.class_ms[ev.cls]);
         }
     }
 };
-// keep at most kMaxPendingEvents launch pairs: fold the oldest into the running sum (its elapsed time if the pair
-// has completed; a launch this old that has not is counted without a time rather than waited for)
+// keep at most kMaxPendingEvents launch pairs: fold the oldest into the running sum
 void trim_events()
 {
     while (G.events.size() > kMaxPendingEvents)
     {
-        auto  ev = G.events.front();
-        float ms = 0.0f;
+        auto ev = G.events.front();
         G.events.pop_front();
-        if (hipEventQuery(ev.second) == hipSuccess && hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) G.timed_ms += ms;
-        else (void)hipGetLastError();
-        put_event(ev.first); put_event(ev.second);
+        fold_span(ev.first, ev.second, G.last_end, G.timed_ms);
     }
 }
 
+// Waits for the pipelined launches in flight, and has the next one wait for the caller's stream: called wherever what a launch reads
+// may change -- la_quiesce (every table, the volume, the environment, buffer growth, the look-ahead), the setters, the counters.
+int pipe_quiesce()
+{
+    G.pipe_fence = true;
+    if (!G.pipe_busy) return VP_OK;
+    for (hipStream_t st : G.pipe_stream)
+        if (st) HIPCHK(hipStreamSynchronize(st));
+    G.pipe_busy = false;
+    return VP_OK;
+}
+// Sizes pipeline slot s for a call of nframes frames in ONE launch: its staging buffer and, where the decomposition estimator's walk
+// hands over, its approach buffer, each capped as the single target's (stage_frames_cap: VP_STAGE_MB, a quarter of the free memory).
+// false: the slot cannot hold the call (the caller's stream then renders it as before, same bits).
+static bool pipe_reserve(int s, size_t per_frame, int nframes, bool aux)
+{
+    float4** stage = s ? &G.d_stage2 : &G.d_stage;
+    size_t*  bytes = s ? &G.stage2_bytes : &G.stage_bytes;
+    const int ti = s ? 3 : 0;
+    const size_t need  = per_frame * (size_t)nframes * sizeof(float4);
+    const size_t need4 = aux ? per_frame * (size_t)nframes * sizeof(uint2) : 0;
+    if (need <= *bytes && need4 <= G.appr_aux_bytes[ti]) return true;
+    if (need > *bytes && stage_frames_cap(per_frame, *bytes) < (size_t)nframes) return false;
+    // (growth: nothing may still read the old buffers -- the slots' launches, the reduces and one-frame launches on the caller's stream)
+    if (pipe_quiesce() || hipStreamSynchronize(G.stream) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (need > *bytes)
+    {
+        if (*stage) (void)hipFree(*stage);
+        *stage = nullptr; *bytes = 0;
+        if (hipMalloc((void**)stage, need) != hipSuccess) { (void)hipGetLastError(); *stage = nullptr; return false; }
+        *bytes = need;
+    }
+    if (need4 > G.appr_aux_bytes[ti])
+    {
+        if (G.d_appr_aux[ti]) (void)hipFree(G.d_appr_aux[ti]);
+        G.d_appr_aux[ti] = nullptr; G.appr_aux_bytes[ti] = 0;
+        if (hipMalloc((void**)&G.d_appr_aux[ti], need4) != hipSuccess) { (void)hipGetLastError(); G.d_appr_aux[ti] = nullptr; return false; }
+        G.appr_aux_bytes[ti] = need4;
+    }
+    return true;
+}
+// The target of a pipelined call: the next slot's stream (created on first use, lowest priority: create_internal_stream), staging,
+// approach buffer and queue words.  false: today's single target on the caller's stream.
+static bool pipe_streams()
+{
+    for (int s = 0; s < 2; s++)
+    {
+        if (!G.pipe_stream[s] && create_internal_stream(&G.pipe_stream[s]) != hipSuccess) { (void)hipGetLastError(); G.pipe_stream[s] = nullptr; return false; }
+        for (hipEvent_t* e : {&G.pipe_done[s], &G.pipe_free[s], &G.pipe_gate[s], &G.pipe_fence_ev})
+            if (!*e && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); *e = nullptr; return false; }
+    }
+    return true;
+}
+static bool pipe_target(size_t per_frame, int nframes, bool aux, Target* T)
+{
+    const int s = G.pipe_next, ti = s ? 3 : 0;
+    if (!pipe_streams() || !pipe_reserve(s, per_frame, nframes, aux)) return false;
+    *T = {G.pipe_stream[s], s ? &G.d_stage2 : &G.d_stage, s ? &G.stage2_bytes : &G.stage_bytes, G.d_queue + 2 * kQueueWords * ti, ti};
+    return true;
+}
+// the camera rays' walk ahead of the integrator is built for this estimator and volume (do_render; counting launches aside)
+static bool approach_possible(const float4* crawl)
+{
+    const bool dense_volume = G.marked_fraction > G.dense_fraction;   // (vp_state.h: little empty space for the walk to cross)
+    return G.use_approach && (G.est == VP_EST_GLOBAL || (G.est == VP_EST_DECOMP && G.use_approach_local && !dense_volume)) && !G.trk && !G.env_mis &&
+           crawl && G.n_general;
+}
 
 // where a render launch goes: the caller's stream with the shared staging buffer, or a look-ahead slot
 
@@ -57,8 +143,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     if (!G.have_sun) return fail(VP_E_STATE, "render before set_sun");
     if (!G.have_cam) return fail(VP_E_STATE, "render before copy_inv_view_matrix");
     if (!d_out || !p || nframes <= 0 || first < 0) return fail(VP_E_ARG, "bad render arguments");
-    const Target main_tgt = {G.stream, &G.d_stage, &G.stage_bytes, G.d_queue, 0};
-    const Target& T = tgt ? *tgt : main_tgt;
+    Target T = tgt ? *tgt : Target{G.stream, &G.d_stage, &G.stage_bytes, G.d_queue, 0};   // (a pipelined call: a slot's, below)
     if (p->width == 0 || p->height == 0 || p->width > 65535 || p->height > 65535)
         return fail(VP_E_ARG, "image %ux%u out of range (sampler.h packs x<<16|y)", p->width, p->height);
     if (G.trk && G.env_mis) return fail(VP_E_STATE, "scalar tracking builds exist with passive environment lighting only");
@@ -103,8 +188,6 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     L.count_clips = getenv("VP_DEBUG_COUNT_CLIPS") ? 1u : 0u;
     rc = exit_flights(L);
     if (rc) return rc;
-    // look-ahead batches carry their slot's cancel word and their number (la_render_slot, la_quiesce); the caller's own launches cannot be cancelled
-    L.cancel = tgt ? G.d_cancel + T.index : nullptr; L.batch_id = G.batch_seq[T.index];
     bool light_const = false;
     if (G.n_light)
     {
@@ -121,9 +204,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     // the camera rays' free flights through certified-empty cells in kernels of their own, ahead of the integrator (approach_k: global
     // majorant; approach_local_k: decomposition estimator; spectral tracking, passive environment, staged launches)
     bool approach = false, approach_thr = false;
-    const bool dense_volume = G.marked_fraction > G.dense_fraction;   // (vp_state.h: little empty space for the walk to cross)
-    if (G.use_approach && (G.est == VP_EST_GLOBAL || (G.est == VP_EST_DECOMP && G.use_approach_local && !dense_volume)) && !G.trk && !G.env_mis && L.crawl && G.n_general &&
-        (!G.count || getenv("VP_COUNT_APPROACH")))   // counting launches: the integrator makes every step itself unless asked (block tallies)
+    if (approach_possible(L.crawl) && (!G.count || getenv("VP_COUNT_APPROACH")))   // counting launches: the integrator makes every step itself unless asked (block tallies)
     {
         // global majorant: one majorant for the whole walk, checked here; decomposition: approach_local_k checks each segment's own
         bool identity = true;
@@ -140,12 +221,16 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
             approach_thr = true;
         }
     }
-    // (decomposition estimator: the restart segments of every general pixel's camera ray, tabulated once per view)
+    // (decomposition estimator: the restart segments of every general pixel's camera ray, tabulated once per view -- built with the
+    // crawl table and the pixel lists whatever the frame count, so that no later launch rebuilds it and waits for those in flight;
+    // read by waves of one pixel x 64 frames)
     L.seg_table = nullptr;
-    if (approach && G.est == VP_EST_DECOMP && nframes >= 64 && G.approach_fshift_max >= 6)   // (read by waves of one pixel x 64 frames)
+    if (approach && G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6)
     {
-        rc = ensure_segment_table(p, L.crawl, &L.seg_table);
+        const float4* seg = nullptr;
+        rc = ensure_segment_table(p, L.crawl, &seg);
         if (rc) return rc;
+        if (nframes >= 64) L.seg_table = seg;
     }
     const size_t per_frame = sh.per_frame;
     if (0xfffffff0u / per_frame < 1) return fail(VP_E_ARG, "image too large for the 32-bit sample queue");
@@ -157,6 +242,15 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     // state (a pair index, or sampler.h's two words) goes beside it.  Sized ONCE, before the launch loop (no synchronisation, no early
     // return between a launch's events).
     const bool appr_aux_needed = approach && G.est == VP_EST_DECOMP && (nframes > 1 || stage_only);
+    // A staged call of vp_render_frames goes to the next pipeline slot when the slot holds it in one launch (counting launches stay on the
+    // caller's stream).  Otherwise -- VP_NO_PIPELINE, no memory for the slot -- the caller's stream, as before: same bits either way.
+    const int  ps    = G.pipe_next;
+    const bool piped = !tgt && !stage_only && nframes > 1 && G.pipeline && !G.count && pipe_target(per_frame, nframes, appr_aux_needed, &T);
+    if (piped) max_f = (size_t)nframes;
+    else if (!tgt) G.pipe_fence = true;   // (the caller's stream uses slot 0's buffers: the next pipelined launch waits for it)
+    G.last_pipelined = piped ? 1 : 0;
+    // look-ahead batches carry their slot's cancel word and their number (la_render_slot, la_quiesce); the caller's own launches cannot be cancelled
+    L.cancel = tgt ? G.d_cancel + T.index : nullptr; L.batch_id = G.batch_seq[T.index];
     if (appr_aux_needed)
     {
         const int    ti    = T.index;
@@ -166,6 +260,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         const size_t need4 = per_frame * std::min<size_t>(fr4, max_f) * sizeof(uint2);
         if (per_frame * std::min<size_t>((size_t)nframes, max_f) * sizeof(uint2) > G.appr_aux_bytes[ti])
         {
+            if (!tgt && (rc = pipe_quiesce())) return rc;   // (target 0's buffers are pipeline slot 0's)
             HIPCHK(hipStreamSynchronize(T.stream));
             if (G.d_appr_aux[ti]) HIPCHK(hipFree(G.d_appr_aux[ti]));
             G.d_appr_aux[ti] = nullptr; G.appr_aux_bytes[ti] = 0;
@@ -188,6 +283,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
                 // its stream, and the batch running beside it, at every step)
                 const size_t exact = need;
                 if (stage_only) need = per_frame * std::min<size_t>(std::max<size_t>((size_t)f, (size_t)std::max(G.la_max, 1)), max_f) * sizeof(float4);
+                if (!tgt && (rc = pipe_quiesce())) return rc;   // (target 0's buffers are pipeline slot 0's)
                 HIPCHK(hipStreamSynchronize(T.stream));
                 HIPCHK(hipStreamSynchronize(G.stream));  // add-kernels of earlier frames may still read the old buffer
                 if (*T.stage) HIPCHK(hipFree(*T.stage));
@@ -218,6 +314,21 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
             L.stage_const = L.stage;
         }
         G.last_const_from = L.const_from;
+        if (piped)
+        {
+            // the slot's stream waits for the reduce that last read its staging (two calls back), for the previous call's walk
+            // (pipe_gate) and, after a change, for the caller's stream
+            if (G.pipe_free_set[ps]) HIPCHK(hipStreamWaitEvent(T.stream, G.pipe_free[ps], 0));
+            if (G.pipe_gate_set[ps ^ 1]) HIPCHK(hipStreamWaitEvent(T.stream, G.pipe_gate[ps ^ 1], 0));
+            G.pipe_gate_set[ps] = false;
+            if (G.pipe_fence)
+            {
+                HIPCHK(hipEventRecord(G.pipe_fence_ev, G.stream));
+                HIPCHK(hipStreamWaitEvent(T.stream, G.pipe_fence_ev, 0));
+                G.pipe_fence = false;
+            }
+            G.pipe_busy = true;
+        }
         HIPCHK(hipMemsetAsync(T.queue, 0, 2 * kQueueWords * sizeof(unsigned), T.stream));
         // the brick table goes through LDS when it fits (decomposition estimator, byte table <= 64 KiB)
         const bool lds_bounds = G.use_lds_bounds && G.est == VP_EST_DECOMP && G.quant && !G.env_mis && !G.trk &&
@@ -364,12 +475,20 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
                         if (!fork_recorded) (void)hipGetLastError();
                     }
                 }
+                // (a pipelined call: the next one starts from here -- its approach walk finds room only as this render_k's waves retire,
+                // i.e. in its tail; without the mark it started beside this call's own walk and the two integrators shared the chip)
+                if (piped && le == hipSuccess)
+                {
+                    if (hipEventRecord(G.pipe_gate[ps], T.stream) == hipSuccess) G.pipe_gate_set[ps] = true;
+                    else le = hipGetLastError();
+                }
                 if (le == hipSuccess)
                 {
                     if (G.arith == VP_ARITH_FAST) launch_render_fast(S, L, G.est, G.rng, G.quant, G.count, lds_form, G.env_mis, G.trk, (int)blocks, T.stream);
                     else launch_render(S, L, G.est, G.rng, G.quant, G.count, lds_form, G.env_mis, G.trk, (int)blocks, T.stream);
                     le = hipGetLastError();
                 }
+
                 // The LDS-table kernel holds 2 x 64 KiB of a CU's LDS with 2 x 512 threads: four waves per SIMD, where the
                 // registers would allow five.  The fifth comes from the SAME kernel without the LDS stage (the brick table read
                 // from global memory), one 256-thread workgroup per CU beside it on the auxiliary stream, drawing from the same
@@ -413,11 +532,23 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         L.pixels = G.d_tiles; L.nslots = (unsigned)per_frame; L.slot_base = 0;
         if (L.stage && !stage_only)
         {
-            launch_reduce(L, T.stream);
+            // (a pipelined launch: the caller-visible write stays on the caller's stream, behind the slot's launch)
+            if (piped)
+            {
+                HIPCHK(hipEventRecord(G.pipe_done[ps], T.stream));
+                HIPCHK(hipStreamWaitEvent(G.stream, G.pipe_done[ps], 0));
+            }
+            launch_reduce(L, G.stream);
             HIPCHK(hipGetLastError());
+            if (piped)
+            {
+                HIPCHK(hipEventRecord(G.pipe_free[ps], G.stream));
+                G.pipe_free_set[ps] = true;
+            }
         }
         done += f;
     }
+    if (piped) G.pipe_next = ps ^ 1;
     return VP_OK;
 }
 
@@ -430,11 +561,18 @@ int vp_render_frames(vp_float4* d_output, int first_frame, int n_frames, const P
 {
     return do_render(d_output, first_frame, n_frames, p);
 }
-int vp_enable_counters(int on) { G.count = on != 0; return VP_OK; }
+int vp_enable_counters(int on)
+{
+    int rc = pipe_quiesce();
+    if (rc) return rc;
+    G.count = on != 0;
+    return VP_OK;
+}
 int vp_read_counters(vp_counters* out, int reset)
 {
     int rc = ensure_device();
     if (rc) return rc;
+    if ((rc = pipe_quiesce())) return rc;
     HIPCHK(hipStreamSynchronize(G.stream));
     unsigned long long h[kCounterWords];
     HIPCHK(hipMemcpy(h, G.d_counters, sizeof h, hipMemcpyDeviceToHost));
@@ -471,21 +609,21 @@ int vp_render_time_ms(double* total_ms, int* launches, int reset)
 {
     int rc = ensure_device();
     if (rc) return rc;
+    if ((rc = pipe_quiesce())) return rc;
     HIPCHK(hipStreamSynchronize(G.stream));
     for (auto& sl : G.la)  // look-ahead batches still in flight are launches too
         if (sl.stream) HIPCHK(hipStreamSynchronize(sl.stream));
-    double tot = G.timed_ms;
-    for (auto& ev : G.events)
-    {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
-        tot += ms;
-    }
+    // (each launch from where the launches before it ended: span_ms)
+    double     tot = G.timed_ms;
+    hipEvent_t end = G.last_end;
+    for (auto& ev : G.events) tot += span_ms(ev.first, ev.second, end);
     if (total_ms) *total_ms = tot;
     if (launches) *launches = G.timed_n;
     if (reset)
     {
-        for (auto& ev : G.events) { put_event(ev.first); put_event(ev.second); }
+        // (the latest end is kept: a launch after the reset is still reported from where the ones before it ended)
+        for (auto& ev : G.events) { put_event(ev.first); if (ev.second != end) put_event(ev.second); }
+        if (end != G.last_end) { put_event(G.last_end); G.last_end = end; }
         G.events.clear();
         G.timed_ms = 0.0; G.timed_n = 0;
     }
@@ -496,6 +634,14 @@ int vp_last_approach_table(void) { return G.last_approach_table; }
 int vp_last_light_const(void) { return G.last_light_const; }
 int vp_last_lds_form(void) { return G.last_lds_form; }
 int vp_last_arithmetic(void) { return G.last_arith; }
+int vp_last_pipelined(void) { return G.last_pipelined; }
+int vp_set_pipeline(int on)
+{
+    int rc = pipe_quiesce();
+    if (rc) return rc;
+    G.pipeline = on != 0;
+    return VP_OK;
+}
 int vp_lookahead_stats(unsigned* launched, unsigned* cancelled_in_flight)
 {
     if (launched) *launched = G.la_launched;
@@ -506,23 +652,23 @@ int vp_render_class_time_ms(double ms[3], unsigned pixels[3], int reset)
 {
     int rc = ensure_device();
     if (rc) return rc;
+    if ((rc = pipe_quiesce())) return rc;
     HIPCHK(hipStreamSynchronize(G.stream));
     for (auto& sl : G.la)
         if (sl.stream) HIPCHK(hipStreamSynchronize(sl.stream));
-    for (int i = 0; i < 3; i++)
+    for (int i = 0; i < kTargets; i++)
         if (G.aux_stream[i]) HIPCHK(hipStreamSynchronize(G.aux_stream[i]));
-    double tot[3] = {G.class_ms[0], G.class_ms[1], G.class_ms[2]};
-    for (auto& ev : G.class_events)
-    {
-        float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, ev.a, ev.b));
-        tot[ev.cls] += t;
-    }
+    // (each class's kernel from where its predecessor of the class ended: span_ms)
+    double     tot[3] = {G.class_ms[0], G.class_ms[1], G.class_ms[2]};
+    hipEvent_t end[3] = {G.class_last_end[0], G.class_last_end[1], G.class_last_end[2]};
+    for (auto& ev : G.class_events) tot[ev.cls] += span_ms(ev.a, ev.b, end[ev.cls]);
     if (ms) for (int i = 0; i < 3; i++) ms[i] = tot[i];
     if (pixels) { pixels[0] = G.n_general; pixels[1] = G.n_light; pixels[2] = G.n_miss; }
     if (reset)
     {
-        for (auto& ev : G.class_events) { put_event(ev.a); put_event(ev.b); }
+        for (auto& ev : G.class_events) { put_event(ev.a); if (ev.b != end[ev.cls]) put_event(ev.b); }
+        for (int i = 0; i < 3; i++)
+            if (end[i] != G.class_last_end[i]) { put_event(G.class_last_end[i]); G.class_last_end[i] = end[i]; }
         G.class_events.clear();
         G.class_ms[0] = G.class_ms[1] = G.class_ms[2] = 0.0;
     }
@@ -572,6 +718,12 @@ int vp_prepare(const Param* p)
         rc = ensure_thr_table(p, &thr);
         if (rc) return rc;
     }
+    if (G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && approach_possible(table))   // (the decomposition walk's segment table: do_render)
+    {
+        const float4* seg = nullptr;
+        rc = ensure_segment_table(p, table, &seg);
+        if (rc) return rc;
+    }
     HIPCHK(hipStreamSynchronize(G.stream));
     return VP_OK;
 }
@@ -590,24 +742,29 @@ int vp_reserve_frames(const Param* p, int nframes)
     const size_t need4 = (G.est == VP_EST_DECOMP && G.use_approach && G.use_approach_local && !(G.marked_fraction > G.dense_fraction)) ? sh.per_frame * f * sizeof(uint2) : 0;
     if (need4 > G.appr_aux_bytes[0])
     {
+        if ((rc = pipe_quiesce())) return rc;   // (pipeline slot 0's buffer)
         HIPCHK(hipStreamSynchronize(G.stream));
         if (G.d_appr_aux[0]) HIPCHK(hipFree(G.d_appr_aux[0]));
         G.d_appr_aux[0] = nullptr; G.appr_aux_bytes[0] = 0;
         if (hipMalloc((void**)&G.d_appr_aux[0], need4) != hipSuccess) { (void)hipGetLastError(); G.d_appr_aux[0] = nullptr; }
         else G.appr_aux_bytes[0] = need4;
     }
-    if (need <= G.stage_bytes) return VP_OK;
-    if (la_quiesce()) return VP_E_NODEVICE;
-    HIPCHK(hipStreamSynchronize(G.stream));
-    if (G.d_stage) HIPCHK(hipFree(G.d_stage));
-    G.d_stage = nullptr; G.stage_bytes = 0;
-    if (hipMalloc((void**)&G.d_stage, need) != hipSuccess)
+    if (need > G.stage_bytes)
     {
-        (void)hipGetLastError();
-        G.d_stage = nullptr;
-        return VP_OK;   // the render call will stage smaller batches: same bits
+        if (la_quiesce()) return VP_E_NODEVICE;
+        HIPCHK(hipStreamSynchronize(G.stream));
+        if (G.d_stage) HIPCHK(hipFree(G.d_stage));
+        G.d_stage = nullptr; G.stage_bytes = 0;
+        if (hipMalloc((void**)&G.d_stage, need) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            G.d_stage = nullptr;
+            return VP_OK;   // the render call will stage smaller batches: same bits
+        }
+        G.stage_bytes = need;
     }
-    G.stage_bytes = need;
+    // ... and pipeline slot 1 where the job goes in one launch (best effort: a call the slot cannot hold renders on the caller's stream)
+    if (G.pipeline && f == (size_t)nframes && pipe_streams()) (void)pipe_reserve(1, sh.per_frame, nframes, need4 > 0);
     return VP_OK;
 }
 }  // extern "C"

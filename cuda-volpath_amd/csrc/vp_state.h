@@ -31,6 +31,8 @@ inline int bound_radius(int nx, float search_radius)
     return (int)std::ceil(search_radius / cell_size);
 }
 
+constexpr int kTargets = 4;   // render targets: the caller's stream (also pipeline slot 0), two look-ahead slots, pipeline slot 1
+
 struct State
 {
     int         device      = 0;
@@ -78,7 +80,7 @@ struct State
     // batch had finished (3-22 ms later: profiles/experiments/r04_lookahead_cancel.txt)
     hipStream_t ctrl_stream = nullptr;
     unsigned*   d_cancel    = nullptr; // [3] per render target: the newest batch number of the slot that is cancelled (LaunchDev::cancel)
-    unsigned    batch_seq[3] = {0, 0, 0};   // number of the last batch queued on each target
+    unsigned    batch_seq[kTargets] = {0, 0, 0, 0};   // number of the last batch queued on each target
     bool        la_cancel   = true;    // VP_NO_LA_CANCEL=1: batches in flight always run to their end
     int         la_prev_n   = 0;      // batch size of the last miss
     int         la_last     = -2;     // frame index of the last render_kernel call
@@ -99,6 +101,25 @@ struct State
     unsigned    rank = 0, world = 1;
     float4*     d_stage       = nullptr;
     size_t      stage_bytes   = 0;
+    // Calls of vp_render_frames alternate between two render targets (vp_render.cpp pipe_target): slot 0 is target 0's buffers (d_stage,
+    // d_appr_aux[0], the first queue words), slot 1 target 3's, each on a stream of its own, so that the approach walk and first
+    // workgroups of call N+1 run in the tail of call N.  A slot's stream waits for the reduce that last read its staging (pipe_free), for
+    // the approach walk of the call before (pipe_gate) and, after a change (pipe_quiesce), for everything on the caller's stream.
+    // VP_NO_PIPELINE=1 / vp_set_pipeline(0): every call on the caller's stream, as before.
+    bool        pipeline      = true;
+    hipStream_t pipe_stream[2] = {nullptr, nullptr};
+    hipEvent_t  pipe_done[2]   = {nullptr, nullptr};   // recorded after a slot's launch on its stream: the caller's stream waits, then reduces
+    hipEvent_t  pipe_free[2]   = {nullptr, nullptr};   // recorded on the caller's stream after that reduce: the slot is free again
+    bool        pipe_free_set[2] = {false, false};
+    hipEvent_t  pipe_gate[2]   = {nullptr, nullptr};   // recorded after a slot's approach walk: the next pipelined call starts behind it
+    bool        pipe_gate_set[2] = {false, false};
+    hipEvent_t  pipe_fence_ev = nullptr;
+    bool        pipe_fence    = true;    // something was queued on the caller's stream that the next pipelined launch must see
+    bool        pipe_busy     = false;   // a pipelined launch may still be running (pipe_quiesce waits for it)
+    int         pipe_next     = 0;       // the slot of the next pipelined call
+    int         last_pipelined = 0;      // vp_last_pipelined
+    float4*     d_stage2      = nullptr; // slot 1's staging buffer
+    size_t      stage2_bytes  = 0;
     unsigned*   d_queue       = nullptr;
     unsigned long long* d_counters = nullptr;
     bool        count       = false;
@@ -141,8 +162,8 @@ struct State
     // the light kernel runs beside the general one on a stream of its own (ALU-bound waves fill the issue slots the general
     // kernel's waves leave while they wait for cells): one auxiliary stream and two events per launch target
     bool        light_overlap = true;
-    hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t  aux_ev[3][2]  = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+    hipStream_t aux_stream[kTargets] = {};
+    hipEvent_t  aux_ev[kTargets][2]  = {};
     // resident 256-thread workgroups per CU while both kernels run (0 = the measured defaults of profiles/r02_light_overlap.txt:
     // 3 + 4 for the global-majorant estimator, 5 + 2 for the local-majorant ones)
     unsigned    general_blocks_per_cu = 0, light_blocks_per_cu = 0;
@@ -165,8 +186,8 @@ struct State
     // the samples of the light class are per-pixel constants when a null collision in empty space leaves a throughput of 1
     // exactly 1 (light_identity_k): decided per (medium, estimator, volume), then miss_fill_k writes them
     bool        use_light_const = true;
-    uint2*      d_appr_aux[3] = {nullptr, nullptr, nullptr};   // per render target (caller's stream, two look-ahead slots): LaunchDev::approach_aux
-    size_t      appr_aux_bytes[3] = {0, 0, 0};
+    uint2*      d_appr_aux[kTargets] = {};   // per render target (caller's stream, two look-ahead slots, the second pipeline slot): LaunchDev::approach_aux
+    size_t      appr_aux_bytes[kTargets] = {};
     int         last_approach = 0;            // vp_last_approach_mode
     int         last_approach_table = 0;      // vp_last_approach_table
     int         last_light_const = 0;         // vp_last_light_const
@@ -206,12 +227,14 @@ struct State
     // launch timing: a ring of the last kMaxPendingEvents launches; older pairs are folded into the running sum
     std::deque<std::pair<hipEvent_t, hipEvent_t>> events;
     std::vector<hipEvent_t> event_pool;
+    hipEvent_t  last_end    = nullptr;   // the latest end among the folded launches (span_ms: overlapping launches are not counted twice)
     double      timed_ms    = 0.0;   // folded launches
     int         timed_n     = 0;     // launches counted (folded or pending or dropped)
     // the same per pixel class: event pairs around the general kernel, the light kernel and the box-missing fill of each launch
     struct ClassEv { int cls; hipEvent_t a, b; };
     std::deque<ClassEv> class_events;
     double      class_ms[3] = {0.0, 0.0, 0.0};
+    hipEvent_t  class_last_end[3] = {nullptr, nullptr, nullptr};
     // Per-sample staging per launch.  A launch ends with a tail in which only the deepest paths are still running (about
     // 14 ms at 800x600 whatever the launch size), so launches should be long: 128 frames per launch (1 GiB) lose 9 % to
     // tails, 1024 frames (8 GB) 1 %.  288 GB of HBM make that cheap; the cap is also held to a quarter of the free memory
@@ -275,6 +298,7 @@ int    ensure_segment_table(const Param* p, const float4* crawl, const float4** 
 struct Target { hipStream_t stream; float4** stage; size_t* stage_bytes; unsigned* queue; int index; };
 int  do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only = false, const Target* tgt = nullptr);
 void trim_events();
+int  pipe_quiesce();   // waits for the pipelined launches in flight; the next one waits for the caller's stream (every change to what launches read)
 // ---- vp_lookahead.cpp
 void render_key(const Param* p, std::vector<unsigned char>& key);
 bool la_cancel_running();

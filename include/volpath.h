@@ -249,6 +249,12 @@ int vp_last_lds_form(void);
 /* VP_ARITH_EXACT / VP_ARITH_FAST: the arithmetic mode of the last render call of this context (its general pixels ran in that mode;
  * the other pixel classes are the same in both) */
 int vp_last_arithmetic(void);
+/* Staged vp_render_frames calls alternate between two render targets, each with its own staging and its own internal stream, so that
+ * the start of a call runs in the tail of the one before; the write into d_output stays on the context's stream, ordered as before.
+ * On by default where both targets fit (VP_NO_PIPELINE=1 switches it off for the process); never changes a result.  vp_set_pipeline
+ * waits for pipelined launches in flight first.  vp_last_pipelined: 1 if the last render call of this context ran on such a target. */
+int vp_set_pipeline(int on);
+int vp_last_pipelined(void);
 /* test hook: look-ahead batches this context has launched so far (render_kernel's staged frames), and how many of them were told to
  * stop while they were still running (a setter, a camera move); either pointer may be NULL */
 int vp_lookahead_stats(unsigned* launched, unsigned* cancelled_in_flight);
