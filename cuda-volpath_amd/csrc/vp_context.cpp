@@ -582,6 +582,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
         if (D.d_thr) (void)hipFree(D.d_thr);
         if (D.d_sunclip) (void)hipFree(D.d_sunclip);
         if (D.d_seg) (void)hipFree(D.d_seg);
+        if (D.d_sub_cls) (void)hipFree(D.d_sub_cls);
         if (D.d_bound_codes) (void)hipFree(D.d_bound_codes);
         if (D.d_light_flag) (void)hipFree(D.d_light_flag);
         if (D.d_tiles) (void)hipFree(D.d_tiles);
@@ -694,6 +695,30 @@ int vp_set_arithmetic(int mode)
     if (mode == G.arith) return VP_OK;
     if (la_quiesce()) return VP_E_NODEVICE;   // (the look-ahead key holds the mode as well: staged frames are never served across it)
     G.arith = mode;
+    return VP_OK;
+}
+int vp_set_subpixel(int s)
+{
+    const int shift = subpixel_shift_of(s);
+    if (shift < 0) return fail(VP_E_ARG, "sub-pixel factor %d: 1, 2, 4 or 8", s);
+    if (shift == G.sub_shift) return VP_OK;
+    // (the look-ahead key holds the factor and the keys of the per-pixel table and the pixel lists the image they were built for: frames
+    // staged and tables built under one factor are never used under another)
+    if (la_quiesce()) return VP_E_NODEVICE;
+    G.sub_shift = shift;
+    G.crawl_key.clear(); G.tiles_key.clear(); G.seg_key.clear();
+    return VP_OK;
+}
+int vp_get_subpixel(void) { return 1 << G.sub_shift; }
+int vp_subpixel_offset(unsigned x, unsigned y, int frame, int s, int* i, int* j)
+{
+    const int shift = subpixel_shift_of(s);
+    if (shift < 0) return fail(VP_E_ARG, "sub-pixel factor %d: 1, 2, 4 or 8", s);
+    if (x > 0xffffu || y > 0xffffu || frame < 0) return fail(VP_E_ARG, "vp_subpixel_offset: pixel (%u, %u) or frame %d out of range", x, y, frame);
+    unsigned oi = 0, oj = 0;
+    vp::subpixel_offset(x, y, (unsigned)frame, (unsigned)shift, oi, oj);
+    if (i) *i = (int)oi;
+    if (j) *j = (int)oj;
     return VP_OK;
 }
 int vp_set_envmap_sampling(int mode)

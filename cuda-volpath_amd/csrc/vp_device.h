@@ -78,7 +78,7 @@ struct SceneDev
 
 // ------------------------------------------------------------------------------ RNG
 // sampler.h:3-11
-__device__ __forceinline__ unsigned wang_hash(unsigned seed)
+__host__ __device__ __forceinline__ unsigned wang_hash(unsigned seed)
 {
     seed = (seed ^ 61u) ^ (seed >> 16);
     seed *= 9u;
@@ -523,6 +523,24 @@ __device__ __forceinline__ void camera_ray(const SceneDev& S, unsigned width, un
     ro      = f3{S.cam[3], S.cam[7], S.cam[11]};
     f3 dv   = f3{u, v, S.cam_z};
     rd      = normalize_ieee(f3{dot(dv, f3{S.cam[0], S.cam[1], S.cam[2]}), dot(dv, f3{S.cam[4], S.cam[5], S.cam[6]}), dot(dv, f3{S.cam[8], S.cam[9], S.cam[10]})});
+}
+
+// Sub-pixel sampling (include/volpath.h vp_set_subpixel): with factor S = 1 << m the sample of pixel (x, y) in frame f is the sample
+// of pixel (S x + i, S y + j) of the S W x S H image.  k = (f + hash(x, y)) mod S^2 with its 2m bits reversed and de-interleaved:
+// bit b of i = bit 2m-1-2b of k, bit b of j = bit 2m-2-2b of k -- any 4^t consecutive frames hit each of the 2^t x 2^t sub-squares of
+// the pixel once.  Integers only: the same function on the host (vp_subpixel_offset) and in every kernel that makes a camera ray.
+__host__ __device__ __forceinline__ void subpixel_offset(unsigned px, unsigned py, unsigned frame, unsigned m, unsigned& i, unsigned& j)
+{
+    const unsigned h = wang_hash(((px << 16) | py) ^ 0x9E3779B9u);
+    const unsigned k = (frame + h) & ((1u << (2u * m)) - 1u);
+    i = j = 0u;
+#pragma unroll
+    for (unsigned b = 0; b < 3u; b++)   // (m <= 3: VP_SUBPIXEL_MAX = 8)
+        if (b < m)
+        {
+            i |= ((k >> (2u * m - 1u - 2u * b)) & 1u) << b;
+            j |= ((k >> (2u * m - 2u - 2u * b)) & 1u) << b;
+        }
 }
 
 // Frame kernel.cu:557-573 (fabs(n.x) > 0.1 is a DOUBLE compare: equivalent to >= 0.1f in float)

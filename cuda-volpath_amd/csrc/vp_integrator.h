@@ -799,14 +799,41 @@ void render_k(SceneDev S, LaunchDev L)
                             frame = L.frame0 + (int)fl;
                             if (px < P.width && py < P.height)
                             {
-                                // camera ray, kernel.cu:1977-1987 (quirk Q3)
-                                rng.init(px, py, (unsigned)frame, L.key0, L.key1);
+                                // the pixel the sample is computed for: this one, or with a sub-pixel factor (L.sub_shift) one of the
+                                // S x S pixels of the S W x S H image that tile it -- stream, camera ray and table entries are that
+                                // pixel's; item, px, py (where the sample is written) stay this one's.  A block of its own, and the table
+                                // index recomputed where it is read (a handful of integer instructions per sample), so that the path
+                                // without a factor keeps the code it had.  (The counting instances carry no code for it: the host refuses
+                                // work counters with a factor, vp_tables.cpp subpixel_check.)
+                                auto table_index = [&]() -> size_t
+                                {
+                                    if (!COUNT && L.sub_shift)
+                                    {
+                                        unsigned si, sj;
+                                        subpixel_offset(px, py, (unsigned)frame, L.sub_shift, si, sj);
+                                        return (size_t)((px << L.sub_shift) + si) + (size_t)((py << L.sub_shift) + sj) * (P.width << L.sub_shift);
+                                    }
+                                    return (size_t)px + (size_t)py * P.width;
+                                };
+                                // camera ray, kernel.cu:1977-1987 (quirk Q3: the same ray in every frame unless a sub-pixel factor is set)
+                                if (!COUNT && L.sub_shift)
+                                {
+                                    unsigned si, sj;
+                                    subpixel_offset(px, py, (unsigned)frame, L.sub_shift, si, sj);
+                                    const unsigned fx = (px << L.sub_shift) + si, fy = (py << L.sub_shift) + sj;
+                                    rng.init(fx, fy, (unsigned)frame, L.key0, L.key1);
+                                    camera_ray(S, P.width << L.sub_shift, P.height << L.sub_shift, fx, fy, ro, rd);
+                                }
+                                else
+                                {
+                                    rng.init(px, py, (unsigned)frame, L.key0, L.key1);
+                                    camera_ray(S, P.width, P.height, px, py, ro, rd);
+                                }
                                 if (TRK == 2)
                                 {
                                     chan     = (int)fminf((1.0f - rng.next_a()) * 3.0f, 2.9999998f);  // kernel.cu:1993
                                     sig_base = density * (chan == 0 ? P.sigma_t[0] : chan == 1 ? P.sigma_t[1] : P.sigma_t[2]);
                                 }
-                                camera_ray(S, P.width, P.height, px, py, ro, rd);
                                 if (LOCAL) inv_rd = f3{1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z};   // (the camera ray: IEEE in both modes)
                                 thr = f3{1.0f, 1.0f, 1.0f};
                                 rad = f3{0.0f, 0.0f, 0.0f};
@@ -814,7 +841,7 @@ void render_k(SceneDev S, LaunchDev L)
                                 seg = 0;
                                 if (EXITC) terms = L.exit_start;
                                 if (COUNT) ex_clear = false;
-                                if (!LIGHT) t_empty = L.crawl ? L.crawl[2 * ((size_t)px + (size_t)py * P.width) + 1].x : 0.0f;
+                                if (!LIGHT) t_empty = L.crawl ? L.crawl[2 * table_index() + 1].x : 0.0f;
                                 if (LOCAL) dist = -1.0f;   // a segment starts where the ray enters it (segment_setup), unless approach_local_k got further
                                 if (APPR && L.approach)
                                 {
@@ -843,7 +870,7 @@ void render_k(SceneDev S, LaunchDev L)
                                 {
                                     // the restart crawl in front of the volume, done once per pixel by crawl_table_k: the path starts
                                     // where that crawl ends, with its draws skipped and its segments counted
-                                    float4   c = L.crawl[2 * ((size_t)px + (size_t)py * P.width)];
+                                    float4   c = L.crawl[2 * table_index()];
                                     unsigned k = f2u(c.w);
                                     ro = f3{c.x, c.y, c.z};
                                     if (!(APPR_L && L.approach)) rng.skip(k >> 16);   // (else the hand-over below carries the stream's state)

@@ -149,6 +149,11 @@ struct LaunchDev
     // ray through certified-empty cells (approach_segments_k: segment_table_records() float4 per slot); null: approach_local_k sets
     // every segment up per sample
     const float4* seg_table;
+    // Sub-pixel sampling (include/volpath.h vp_set_subpixel; appended like the fields above): log2 of the factor S, 0 = off.  A sample of
+    // pixel (x, y) in frame f is computed for pixel (S x + i, S y + j) of the S W x S H image (vp_device.h subpixel_offset): `crawl` is
+    // then that image's table, `pixels`, `out`, `stage` and P stay the W x H image's.  The host launches no approach walk, no segment
+    // table and no constant rows with it (vp_render.cpp).
+    unsigned sub_shift;
 };
 
 // lds_form: how the decomposition estimator reads its brick table -- 0 global memory, 1 the 16-bit table through LDS (512-thread
@@ -161,6 +166,7 @@ void launch_render_fast(const SceneDev& S, const LaunchDev& L, int est, int rng,
                         int blocks, hipStream_t st);
 // the light pixel class (spectral tracking): pixels whose camera ray meets empty cells only
 void launch_render_light(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int blocks, hipStream_t st);
+// (with LaunchDev::sub_shift: subpixel_fill_k, one constant per fine pixel, staged for every frame)
 void launch_miss_fill(const SceneDev& S, const LaunchDev& L, bool local_estimator, hipStream_t st);
 // the camera rays' free flights through certified-empty cells, one thread per sample of the launch (approach_k); rng: RNG_PHILOX*
 void launch_approach(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, hipStream_t st);
@@ -180,7 +186,10 @@ void launch_light_identity_fast(const ParamDev& P, bool local, const unsigned* m
 // d_block_counts[3 * pixel_list_blocks(ntiles)] scratch, d_totals[3] = pixels per class (general, light, box-missing)
 inline unsigned pixel_list_blocks(unsigned ntiles) { return (unsigned)(((size_t)ntiles * 64 + 1023) / 1024); }
 void launch_pixel_lists(unsigned width, unsigned height, unsigned rank, unsigned world, unsigned ntiles, const unsigned* d_row_start,
-                        const float4* table, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st);
+                        const float4* table, const unsigned char* cls, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st);
+// sub-pixel sampling: cls[width * height] = the class of each pixel of the width x height image from the table `fine` of the
+// (width << shift) x (height << shift) image (subpixel_class_k); launch_pixel_lists then reads cls instead of a table
+void launch_subpixel_classes(const float4* fine, unsigned width, unsigned height, unsigned shift, unsigned char* cls, hipStream_t st);
 void launch_env_tables(const float4* env, int w, int h, float* lum, float* row_sum, float* cdf_x, float* cdf_y, float* pdfnorm_alt,
                        hipStream_t st);
 void launch_crawl_table(const SceneDev& S, bool quant, unsigned width, unsigned height, bool control_draw, const unsigned char* danger, float4* table,

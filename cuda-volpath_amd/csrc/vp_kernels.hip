@@ -388,6 +388,7 @@ struct PixListDev
     unsigned ntiles;            // owned tiles
     const unsigned* row_start;  // [tiles_y + 1]: index of the first owned tile of each tile row (camera-independent, from the host)
     const float4*   table;      // pixel table, or null = every pixel is general
+    const unsigned char* cls;   // sub-pixel sampling: the class of each pixel of THIS image, reduced from the finer image's table (subpixel_class_k); else null
 };
 #define VP_PIXLIST_BLOCK 1024
 __device__ __forceinline__ unsigned pixlist_slot(const PixListDev& D, unsigned s, unsigned& pix)
@@ -409,6 +410,7 @@ __device__ __forceinline__ unsigned pixlist_slot(const PixListDev& D, unsigned s
     const unsigned x = tx * 8u + (s & 7u), y = ty * 8u + ((s >> 3) & 7u);
     if (x >= D.width || y >= D.height) return 3u;
     pix = y << 16 | x;
+    if (D.cls) return D.cls[(size_t)x + (size_t)y * D.width];
     if (!D.table) return 0u;
     const unsigned c = (unsigned)D.table[2 * ((size_t)x + (size_t)y * D.width) + 1].y;
     return c > 2u ? 0u : c;
@@ -485,6 +487,19 @@ __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void pixlist_write_k(PixListDev D
 // kernel.cu:1336-1345 / :2020-2031), background() is evaluated for the camera direction with throughput 1 (quirk Q3: no jitter)
 // and the sample is written -- no draw is consumed.  One thread per such pixel evaluates that once, with the integrator's own
 // expressions (EV_BG / EV_WRITE blocks of render_k), and writes it for every frame of the launch.
+__device__ __forceinline__ float4 unscattered_sample(const SceneDev& S, const ParamDev& P, f3 rd, bool& env_lookup)
+{
+    const f3 sun_dir = f3{S.sun_dir[0], S.sun_dir[1], S.sun_dir[2]};
+    f3   rad  = f3{0.0f, 0.0f, 0.0f};
+    const f3 thr = f3{1.0f, 1.0f, 1.0f};
+    env_lookup = false;
+    f3   bg;
+    if (dot(rd, sun_dir) > S.sun_cos) bg = f3{S.sun_orig[0], S.sun_orig[1], S.sun_orig[2]};
+    else { bg = eval_envmap(S, rd); env_lookup = true; }
+    rad = rad + bg * thr;
+    f3     r = rad * P.brightness;
+    return make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), 0.0f);  // heat: 0 scatters / segments
+}
 __global__ __launch_bounds__(256) void miss_fill_k(SceneDev S, LaunchDev L, int local_estimator)
 {
     unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
@@ -493,16 +508,8 @@ __global__ __launch_bounds__(256) void miss_fill_k(SceneDev S, LaunchDev L, int 
     unsigned pix = L.pixels[slot], px = pix & 0xffffu, py = pix >> 16;
     f3 ro, rd;
     camera_ray(S, P.width, P.height, px, py, ro, rd);
-    const f3 sun_dir = f3{S.sun_dir[0], S.sun_dir[1], S.sun_dir[2]};
-    f3   rad  = f3{0.0f, 0.0f, 0.0f};
-    const f3 thr = f3{1.0f, 1.0f, 1.0f};
     bool env_lookup = false;
-    f3   bg;
-    if (dot(rd, sun_dir) > S.sun_cos) bg = f3{S.sun_orig[0], S.sun_orig[1], S.sun_orig[2]};
-    else { bg = eval_envmap(S, rd); env_lookup = true; }
-    rad = rad + bg * thr;
-    f3     r = rad * P.brightness;
-    float4 v = make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), 0.0f);  // heat: 0 scatters / segments
+    const float4 v = unscattered_sample(S, P, rd, env_lookup);
     if (L.stage)
     {
         // (staged once where the add-kernel knows the slot for a constant: LaunchDev::const_from)
@@ -520,6 +527,57 @@ __global__ __launch_bounds__(256) void miss_fill_k(SceneDev S, LaunchDev L, int 
         atomicAdd(&L.counters[0], (unsigned long long)L.nframes);                         // samples
         if (env_lookup) atomicAdd(&L.counters[4], (unsigned long long)L.nframes);         // environment lookups
         if (local_estimator) atomicAdd(&L.counters[2], (unsigned long long)L.nframes);    // the bound fetched before the hit test
+    }
+}
+
+// ---- sub-pixel sampling (LaunchDev::sub_shift, include/volpath.h vp_set_subpixel).
+// The class of a pixel of the W x H image from the classes of the S x S pixels of the S W x S H image that tile it (`fine`: that
+// image's pixel table): 2 (box-missing) if all of them miss the box, 1 (light) if the whole chord of every one is certified empty,
+// 0 (general) otherwise -- any general one among them, or a mix of the other two (the edge of the box: the integrator handles both).
+// One byte per pixel; feeds the three-way partition above.
+__global__ __launch_bounds__(256) void subpixel_class_k(const float4* fine, unsigned width, unsigned height, unsigned shift, unsigned char* cls)
+{
+    const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= width * height) return;
+    const unsigned y = idx / width, x = idx - y * width, n = 1u << shift;
+    const size_t   fw = (size_t)width << shift;
+    unsigned seen = 0;
+    for (unsigned j = 0; j < n; j++)
+        for (unsigned i = 0; i < n; i++)
+        {
+            const unsigned c = (unsigned)fine[2 * (((size_t)x << shift) + i + (((size_t)y << shift) + j) * fw) + 1].y;
+            seen |= 1u << (c > 2u ? 0u : c);
+        }
+    cls[idx] = seen == 4u ? 2 : seen == 2u ? 1 : 0;
+}
+// miss_fill_k with a sub-pixel factor: the sample of a box-missing pixel (and of a light one where miss_fill_k would write it) is a
+// constant of the FINE pixel, and the fine pixel of frame f is number k = (f + hash) mod S^2 of the pixel's S^2.  One thread per
+// (pixel, k) evaluates that constant once, with miss_fill_k's expressions, and writes it for the frames of the launch that use it
+// (every S^2-th); a thread whose k no frame of the launch uses evaluates nothing.  No constant rows (LaunchDev::const_from) here.
+__global__ __launch_bounds__(256) void subpixel_fill_k(SceneDev S, LaunchDev L)
+{
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x, m = L.sub_shift, n2 = 1u << (2u * m);
+    if (t >= L.nslots * n2) return;   // (the host keeps nslots * 64 within 32 bits)
+    const unsigned k = t / L.nslots, slot = t - k * L.nslots;
+    const ParamDev& P = L.P;
+    const unsigned pix = L.pixels[slot], px = pix & 0xffffu, py = pix >> 16;
+    const unsigned h = wang_hash(((px << 16) | py) ^ 0x9E3779B9u);
+    unsigned fl = (k - ((unsigned)L.frame0 + h)) & (n2 - 1u);   // the first frame of the launch with (frame + h) mod S^2 == k
+    if (fl >= (unsigned)L.nframes) return;
+    unsigned i, j;
+    subpixel_offset(px, py, (unsigned)L.frame0 + fl, m, i, j);
+    f3 ro, rd;
+    camera_ray(S, P.width << m, P.height << m, (px << m) + i, (py << m) + j, ro, rd);
+    bool env_lookup = false;
+    const float4 v = unscattered_sample(S, P, rd, env_lookup);
+    if (L.stage)
+        for (; fl < (unsigned)L.nframes; fl += n2) L.stage[(size_t)fl * L.stage_stride + L.slot_base + slot] = v;
+    else
+    {
+        // (a one-frame launch: exactly one k per pixel gets here)
+        size_t idx = (size_t)px + (size_t)py * P.width;
+        float4 a   = L.out[idx];
+        L.out[idx] = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
     }
 }
 
@@ -1078,6 +1136,11 @@ void launch_thr_table(const ParamDev& P, float* table, unsigned count, hipStream
 }
 void launch_miss_fill(const SceneDev& S, const LaunchDev& L, bool local_estimator, hipStream_t st)
 {
+    if (L.sub_shift)
+    {
+        hipLaunchKernelGGL(subpixel_fill_k, dim3(((L.nslots << (2u * L.sub_shift)) + 255) / 256), dim3(256), 0, st, S, L);
+        return;
+    }
     hipLaunchKernelGGL(miss_fill_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, S, L, local_estimator ? 1 : 0);
 }
 unsigned segment_table_records(void) { return 2u * VP_SEG_CAP; }
@@ -1118,9 +1181,10 @@ void launch_approach(const SceneDev& S, const LaunchDev& L, int est, int rng, bo
     }
 }
 void launch_pixel_lists(unsigned width, unsigned height, unsigned rank, unsigned world, unsigned ntiles, const unsigned* d_row_start,
-                        const float4* table, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st)
+                        const float4* table, const unsigned char* cls, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st)
 {
     PixListDev D;
+    D.cls = cls;
     D.width = width; D.height = height; D.rank = rank; D.world = world;
     D.tiles_x = (width + 7) / 8; D.tiles_y = (height + 7) / 8; D.ntiles = ntiles; D.row_start = d_row_start; D.table = table;
     const unsigned nblocks = pixel_list_blocks(ntiles);
@@ -1310,6 +1374,10 @@ void launch_empty_table(const SceneDev& S, unsigned width, unsigned height, cons
 {
     unsigned n = width * height;
     hipLaunchKernelGGL(empty_table_k, dim3((n + 255) / 256), dim3(256), 0, st, S, width, height, danger, table);
+}
+void launch_subpixel_classes(const float4* fine, unsigned width, unsigned height, unsigned shift, unsigned char* cls, hipStream_t st)
+{
+    hipLaunchKernelGGL(subpixel_class_k, dim3((width * height + 255) / 256), dim3(256), 0, st, fine, width, height, shift, cls);
 }
 void launch_reduce(const LaunchDev& L, hipStream_t st)
 {

@@ -6,12 +6,12 @@ namespace vph __attribute__((visibility("hidden")))
 // everything a sample's value depends on besides (x, y, frame): compared bytewise between render_kernel calls
 void render_key(const Param* p, std::vector<unsigned char>& key)
 {
-    struct K { SceneDev S; Param P; int est, rng, linear, quant, mis, trk, arith; unsigned k0, k1, rank, world; unsigned long long epoch; };
+    struct K { SceneDev S; Param P; int est, rng, linear, quant, mis, trk, arith, sub; unsigned k0, k1, rank, world; unsigned long long epoch; };
     key.assign(sizeof(K), 0);
     K* k = reinterpret_cast<K*>(key.data());
     memcpy(&k->S, &G.S, sizeof(SceneDev));
     memcpy(&k->P, p, sizeof(Param));
-    k->est = G.est; k->rng = G.rng; k->linear = G.linear; k->quant = G.quant; k->mis = G.env_mis; k->trk = G.trk; k->arith = G.arith;
+    k->est = G.est; k->rng = G.rng; k->linear = G.linear; k->quant = G.quant; k->mis = G.env_mis; k->trk = G.trk; k->arith = G.arith; k->sub = G.sub_shift;
     k->k0 = G.key0; k->k1 = G.key1; k->rank = G.rank; k->world = G.world; k->epoch = G.epoch;
 }
 

@@ -128,7 +128,9 @@ static bool pipe_target(size_t per_frame, int nframes, bool aux, Target* T)
 static bool approach_possible(const float4* crawl)
 {
     const bool dense_volume = G.marked_fraction > G.dense_fraction;   // (vp_state.h: little empty space for the walk to cross)
-    return G.use_approach && (G.est == VP_EST_GLOBAL || (G.est == VP_EST_DECOMP && G.use_approach_local && !dense_volume)) && !G.trk && !G.env_mis &&
+    // (a sub-pixel factor: the integrator walks the camera ray itself -- the approach kernels and the segment table are statements about
+    // ONE camera ray per pixel, and with S^2 of them a wave of one pixel x 64 frames no longer shares a ray: DESIGN.md section 2.2)
+    return G.use_approach && !G.sub_shift && (G.est == VP_EST_GLOBAL || (G.est == VP_EST_DECOMP && G.use_approach_local && !dense_volume)) && !G.trk && !G.env_mis &&
            crawl && G.n_general;
 }
 
@@ -159,6 +161,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         if (G.trk) return fail(VP_E_STATE, "VP_ARITH_FAST is built for spectral tracking only");
         if (G.count) return fail(VP_E_STATE, "work counters are not built for VP_ARITH_FAST");
     }
+    if ((rc = subpixel_check(p))) return rc;
     G.last_arith = G.arith;   // (vp_last_arithmetic: the mode of the last render call, whatever classes its pixels fall in)
     if (G.est == VP_EST_DECOMP && first + nframes - 1 > 10 && !G.S.opacity)
         return fail(VP_E_NOOPACITY, "frames beyond 10 need precompute_opacity (kernel.cu:2183, host.cpp:336-343)");
@@ -179,7 +182,10 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         if (!G.wait_lanes_set && G.rng == VP_RNG_SAMPLERH && G.trk == VP_TRACK_SPECTRAL) L.wait_lanes = 24;
     }
     if (sh.per_frame == 0) return VP_OK;
-    rc = ensure_crawl_table(p, &L.crawl);
+    // (a sub-pixel factor: the per-pixel table of the image the samples are computed on; lists, staging and output stay this image's)
+    L.sub_shift = (unsigned)G.sub_shift;
+    const Param fine = subpixel_param(p);
+    rc = ensure_crawl_table(&fine, &L.crawl);
     if (rc) return rc;
     rc = ensure_pixel_lists(p, L.crawl, sh);
     if (rc) return rc;
@@ -308,7 +314,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         // per-pixel constants of the launch (the box-missing pixels; the light class where it is written by miss_fill_k) are staged once,
         // in the launch's first row: the slots behind the general (and an integrated light) class
         L.const_from = 0xffffffffu; L.stage_const = nullptr;
-        if (L.stage && G.use_const_rows)
+        if (L.stage && G.use_const_rows && !G.sub_shift)   // (a sub-pixel factor: constants of the FINE pixel, staged per frame by subpixel_fill_k)
         {
             L.const_from  = (unsigned)(G.n_general + ((G.n_light && !light_const) ? G.n_light : 0u));
             L.stage_const = L.stage;
@@ -701,8 +707,10 @@ int vp_prepare(const Param* p)
         G.n_general = G.n_light = G.n_miss = 0; G.tiles_key.clear();
         return VP_OK;
     }
+    if ((rc = subpixel_check(p))) return rc;
     const float4* table = nullptr;
-    rc = ensure_crawl_table(p, &table);
+    const Param fine = subpixel_param(p);
+    rc = ensure_crawl_table(&fine, &table);
     if (rc) return rc;
     rc = ensure_pixel_lists(p, table, sh);
     if (rc) return rc;
@@ -739,7 +747,7 @@ int vp_reserve_frames(const Param* p, int nframes)
     const size_t f    = std::min<size_t>((size_t)nframes, stage_frames_cap(sh.per_frame, G.stage_bytes));
     const size_t need = sh.per_frame * f * sizeof(float4);
     // (decomposition estimator: the stream's state beside each staging slot of the approach kernel's hand-over, do_render)
-    const size_t need4 = (G.est == VP_EST_DECOMP && G.use_approach && G.use_approach_local && !(G.marked_fraction > G.dense_fraction)) ? sh.per_frame * f * sizeof(uint2) : 0;
+    const size_t need4 = (G.est == VP_EST_DECOMP && G.use_approach && !G.sub_shift && G.use_approach_local && !(G.marked_fraction > G.dense_fraction)) ? sh.per_frame * f * sizeof(uint2) : 0;
     if (need4 > G.appr_aux_bytes[0])
     {
         if ((rc = pipe_quiesce())) return rc;   // (pipeline slot 0's buffer)

@@ -31,6 +31,23 @@ inline int bound_radius(int nx, float search_radius)
     return (int)std::ceil(search_radius / cell_size);
 }
 
+// log2 of a sub-pixel factor (include/volpath.h vp_set_subpixel), or -1: not one of 1, 2, 4, 8
+inline int subpixel_shift_of(long s) { return s == 1 ? 0 : s == 2 ? 1 : s == 4 ? 2 : s == 8 ? 3 : -1; }
+// VP_SUBPIXEL=<s>: the factor a new context starts with (malformed or out of range: ignored with a word on stderr, as the tuning knobs are)
+inline int subpixel_env_shift()
+{
+    const char* e = getenv("VP_SUBPIXEL");
+    if (!e || !*e) return 0;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (*end || subpixel_shift_of(v) < 0)
+    {
+        fprintf(stderr, "volpath_hip: ignoring VP_SUBPIXEL=%s (allowed 1, 2, 4, 8)\n", e);
+        return 0;
+    }
+    return subpixel_shift_of(v);
+}
+
 constexpr int kTargets = 4;   // render targets: the caller's stream (also pipeline slot 0), two look-ahead slots, pipeline slot 1
 
 struct State
@@ -194,6 +211,11 @@ struct State
     int         last_lds_form = 0;            // vp_last_lds_form
     int         arith       = VP_ARITH_EXACT;   // vp_set_arithmetic: the general class's integrator in the exact or the fast arithmetic
     int         last_arith  = VP_ARITH_EXACT;   // vp_last_arithmetic
+    // vp_set_subpixel: log2 of the sub-pixel factor S (0 = off).  With S > 1 the per-pixel table (d_crawl) is the S W x S H image's,
+    // d_sub_cls holds the classes of the W x H image's pixels reduced from it (subpixel_class_k) and the pixel lists are built from those
+    int         sub_shift   = subpixel_env_shift();
+    unsigned char* d_sub_cls = nullptr;
+    size_t      sub_cls_bytes = 0;
     unsigned    la_launched = 0, la_cancelled = 0;   // vp_lookahead_stats
     bool        use_const_rows = true;        // VP_NO_CONST_ROWS=1: per-pixel constants are staged for every frame, as before round 4's end
     unsigned    last_const_from = 0;          // LaunchDev::const_from of the last staged launch (a look-ahead slot keeps it for its add-kernels)
@@ -284,6 +306,8 @@ Shard  shard_of(const Param* p);
 size_t stage_frames_cap(size_t per_frame, size_t have_bytes);
 int    do_opacity(const float* dir);
 int    ensure_crawl_table(const Param* p, const float4** out);
+Param  subpixel_param(const Param* p);   // p for the image the samples are computed on: (width, height) << sub_shift
+int    subpixel_check(const Param* p);   // VP_E_ARG / VP_E_STATE for an image or a configuration the current factor is not built for
 int    ensure_sun_clip(const unsigned short** out, float* ds);
 int    ensure_light_const(const Param* p, bool* out);
 int    ensure_light_identity(const Param* p, bool* out);

@@ -95,6 +95,28 @@ size_t stage_frames_cap(size_t per_frame, size_t have_bytes)
     return std::max<size_t>(f, 1);
 }
 
+// Sub-pixel sampling (include/volpath.h vp_set_subpixel): the image the samples are computed on, and what the mode is built for
+Param subpixel_param(const Param* p)
+{
+    Param f = *p;
+    f.width <<= G.sub_shift; f.height <<= G.sub_shift;
+    return f;
+}
+int subpixel_check(const Param* p)
+{
+    if (!G.sub_shift) return VP_OK;
+    const unsigned s = 1u << G.sub_shift;
+    // (the fine pixel goes into the 16-bit halves of x << 16 | y: streams, hash)
+    if ((unsigned long long)p->width * s > 65536ull || (unsigned long long)p->height * s > 65536ull)
+        return fail(VP_E_ARG, "image %ux%u with sub-pixel factor %u: the %llux%llu sample image is out of range (x << 16 | y)", p->width, p->height, s,
+                    (unsigned long long)p->width * s, (unsigned long long)p->height * s);
+    if (((unsigned long long)p->width * s) * ((unsigned long long)p->height * s) > 0xfffffff0ull)
+        return fail(VP_E_ARG, "image %ux%u with sub-pixel factor %u: the sample image has too many pixels for its 32-bit table index", p->width, p->height, s);
+    if ((unsigned long long)p->width * p->height * 64ull > 0xfffffff0ull) return fail(VP_E_ARG, "image %ux%u too large for a sub-pixel factor", p->width, p->height);
+    if (G.count) return fail(VP_E_STATE, "work counters are not built for sub-pixel sampling");
+    return VP_OK;
+}
+
 // The per-pixel table of the restart crawl in front of the volume (vp_kernels.hip crawl_table_k) for the local-majorant
 // estimators.  It depends on the camera, the box, the bound table and the image size only -- not on the frame -- and is
 // rebuilt (one small kernel, synchronously: launches on other streams read it) when any of those changed.
@@ -127,6 +149,8 @@ int ensure_crawl_table(const Param* p, const float4** out)
             {
                 (void)hipGetLastError();
                 G.d_crawl = nullptr;
+                // (a sub-pixel factor multiplies the table by S^2 -- 245 MB at 800x600, S = 4 -- and its pixel classes come from it: said, not worked around)
+                if (G.sub_shift) return fail(VP_E_NOMEM, "no memory for the %ux%u per-pixel table of the sub-pixel factor %d (%zu bytes)", p->width, p->height, 1 << G.sub_shift, need);
                 return VP_OK;   // no table: the paths walk the crawl themselves, same bits
             }
             G.crawl_bytes = need;
@@ -374,6 +398,7 @@ int ensure_pixel_lists(const Param* p, const float4* table, const Shard& sh)
     K* k = reinterpret_cast<K*>(key.data());
     k->w = p->width; k->h = p->height; k->rank = G.rank; k->world = G.world; k->light = light ? 1 : 0;
     std::vector<unsigned char> shape_key = key;   // what the tile enumeration depends on (not the camera)
+    key.push_back((unsigned char)G.sub_shift);    // (with a sub-pixel factor `table` is the finer image's and the classes are reduced from it, below)
     if (light) key.insert(key.end(), G.crawl_key.begin(), G.crawl_key.end());
     if (key == G.tiles_key && G.d_tiles) return VP_OK;
     if (la_quiesce()) return VP_E_NODEVICE;   // batches in flight read the old lists
@@ -407,7 +432,23 @@ int ensure_pixel_lists(const Param* p, const float4* table, const Shard& sh)
         G.tiles_cap = sh.per_frame;
     }
     unsigned* d_totals = G.d_tile_scratch + (size_t)3 * nblocks;
-    launch_pixel_lists(p->width, p->height, G.rank, G.world, sh.owned, G.d_tile_rows, light ? table : nullptr, G.d_tile_scratch, d_totals, G.d_tiles, G.stream);
+    const unsigned char* cls = nullptr;
+    if (light && G.sub_shift)
+    {
+        // the classes of this image's pixels from the S x S finer pixels each of them samples (subpixel_class_k)
+        const size_t need = (size_t)p->width * p->height;
+        if (need > G.sub_cls_bytes)
+        {
+            if (G.d_sub_cls) HIPCHK(hipFree(G.d_sub_cls));
+            G.d_sub_cls = nullptr; G.sub_cls_bytes = 0;
+            HIPCHK(hipMalloc((void**)&G.d_sub_cls, need));
+            G.sub_cls_bytes = need;
+        }
+        launch_subpixel_classes(table, p->width, p->height, (unsigned)G.sub_shift, G.d_sub_cls, G.stream);
+        HIPCHK(hipGetLastError());
+        cls = G.d_sub_cls;
+    }
+    launch_pixel_lists(p->width, p->height, G.rank, G.world, sh.owned, G.d_tile_rows, light ? table : nullptr, cls, G.d_tile_scratch, d_totals, G.d_tiles, G.stream);
     HIPCHK(hipGetLastError());
     unsigned totals[3] = {0, 0, 0};
     HIPCHK(hipMemcpyAsync(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, G.stream));

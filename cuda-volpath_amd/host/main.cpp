@@ -25,6 +25,8 @@ static void usage()
            "               [--tracking spectral|scalar|multichannel] [--env passive|mis]\n"
            "               [--arith exact|fast]             fast: hardware log/exp/rcp/sqrt/sin/cos in the integrator, within the\n"
            "                                                tolerance of include/volpath.h (--rng philox|philox7, spectral, passive)\n"
+           "               [--aa 1|2|4|8]                   anti-aliasing: stratified sub-pixel camera rays on an S x S lattice per pixel\n"
+           "                                                (vp_set_subpixel: a box-filtered pixel; default 1, or VP_SUBPIXEL)\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -40,7 +42,7 @@ int main(int argc, char** argv)
     int         philox = 0;   // 0 sampler.h, 1 Philox2x32-10, 2 Philox2x32-7
     int         est = VP_EST_DECOMP, tracking = VP_TRACK_SPECTRAL, env_mode = VP_ENV_PASSIVE, arith = VP_ARITH_EXACT;
     std::string bin, vdb, out = "output0.ppm", devlist;
-    int         gpus = 1;
+    int         gpus = 1, aa = 0;   // (0: not given -- the contexts keep their default, VP_SUBPIXEL)
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -75,6 +77,13 @@ int main(int argc, char** argv)
             if (!strcmp(m, "exact")) arith = VP_ARITH_EXACT;
             else if (!strcmp(m, "fast")) arith = VP_ARITH_FAST;
             else { fprintf(stderr, "unknown --arith %s\n", m); usage(); return 2; }
+        }
+        else if (a == "--aa")
+        {
+            need(1);
+            const char* m = argv[++i];
+            aa = !strcmp(m, "1") ? 1 : !strcmp(m, "2") ? 2 : !strcmp(m, "4") ? 4 : !strcmp(m, "8") ? 8 : 0;
+            if (!aa) { fprintf(stderr, "unknown --aa %s (1, 2, 4 or 8)\n", m); usage(); return 2; }
         }
         else if (a == "--sun") { need(2); sunx = (float)atof(argv[++i]); suny = (float)atof(argv[++i]); }
         else if (a == "--batch") { need(1); batch = atoi(argv[++i]); }
@@ -166,6 +175,7 @@ int main(int argc, char** argv)
         if (vp_set_tracking(tracking) || vp_set_envmap_sampling(env_mode) || vp_set_shard(r, gpus)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
         vp_set_rng(philox == 2 ? VP_RNG_PHILOX7 : philox ? VP_RNG_PHILOX : VP_RNG_SAMPLERH, 0x9E3779B9u, 0x85EBCA6Bu);
         if (vp_set_arithmetic(arith)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        if (aa && vp_set_subpixel(aa)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
         // frame buffer (CudaFrameBuffer host.cpp:358-389), full frame on every rank: zero outside its tiles
         accum[r] = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
         if (!accum[r]) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }

@@ -20,6 +20,8 @@ TRACK_SPECTRAL, TRACK_SCALAR, TRACK_MULTI_CHANNEL = 0, 1, 2
 ARITH_EXACT, ARITH_FAST = 0, 1
 # include/volpath.h VP_ARITH_FAST_REL_L2: the stated bound on ||I_fast - I_exact||_2 / ||I_exact||_2 (mean images of 1024 frames)
 ARITH_FAST_REL_L2 = 2e-3
+# include/volpath.h VP_SUBPIXEL_MAX: the largest sub-pixel factor (set_subpixel takes 1, 2, 4, 8)
+SUBPIXEL_MAX = 8
 
 # every symbol include/volpath.h declares (tests check the library exports each one)
 PART1_SYMBOLS = ["init_cuda", "set_texture_filter_mode", "free_cuda_buffers", "precompute_opacity", "init_envmap",
@@ -27,7 +29,7 @@ PART1_SYMBOLS = ["init_cuda", "set_texture_filter_mode", "free_cuda_buffers", "p
                  "render_kernel", "scale", "gamma_correct"]
 PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_device", "vp_set_stream", "vp_get_stream", "vp_synchronize",
                  "vp_set_estimator", "vp_set_rng", "vp_set_envmap_sampling", "vp_get_env_tables", "vp_set_lookahead", "vp_set_tracking", "vp_set_bound_brick", "vp_set_shard", "vp_render_frames",
-                 "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists",
+                 "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_intersect_box",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -96,6 +98,8 @@ def lib():
         L.vp_get_sun_clip_table.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float)]
         L.vp_render_class_time_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int]
         L.vp_prepare.argtypes = [C.POINTER(Param)]
+        L.vp_set_subpixel.argtypes = [C.c_int]
+        L.vp_subpixel_offset.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.vp_get_pixel_lists.argtypes = [C.POINTER(Param), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
         L.vp_julia_voxelize.argtypes = [C.c_int, C.c_void_p]
         L.vp_cloud_voxelize.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
@@ -357,6 +361,23 @@ def set_arithmetic(mode):
     """ARITH_EXACT (the default: bit for bit the oracle's) or ARITH_FAST (hardware transcendentals and reciprocals, within
     ARITH_FAST_REL_L2 of the exact image; counter-based streams, spectral tracking, passive environment only)"""
     _chk(lib().vp_set_arithmetic(mode))
+
+
+def set_subpixel(s):
+    """Anti-aliasing: sub-pixel factor 1 (off, the default), 2, 4 or 8 of the current context (vp_set_subpixel): the sample of pixel
+    (x, y) in frame f is the S = 1 sample of pixel (S x + i, S y + j) of the S W x S H image, (i, j) = subpixel_offset(x, y, f, S)"""
+    _chk(lib().vp_set_subpixel(int(s)))
+
+
+def get_subpixel():
+    return int(lib().vp_get_subpixel())
+
+
+def subpixel_offset(x, y, frame, s):
+    """(i, j): which of the S x S fine pixels of pixel (x, y) frame `frame` samples (vp_subpixel_offset; no device needed)"""
+    i, j = C.c_int(0), C.c_int(0)
+    _chk(lib().vp_subpixel_offset(int(x), int(y), int(frame), int(s), C.byref(i), C.byref(j)))
+    return i.value, j.value
 
 
 def last_arithmetic():

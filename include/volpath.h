@@ -189,6 +189,37 @@ int vp_set_envmap_sampling(int mode);                  /* default VP_ENV_PASSIVE
 enum { VP_ARITH_EXACT = 0, VP_ARITH_FAST = 1 };
 #define VP_ARITH_FAST_REL_L2 2e-3
 int vp_set_arithmetic(int mode);                       /* default VP_ARITH_EXACT */
+/* Anti-aliasing: stratified sub-pixel camera rays.  A sub-pixel factor S in {1, 2, 4, 8}, m = log2 S, per
+ * context, default 1 (env VP_SUBPIXEL=<s> sets the default of new contexts).  THE DEFINITION:
+ *   With factor S, the sample of pixel (x, y) in frame f of a W x H image is, bit for bit, the sample that the same context with
+ *   S = 1 computes for pixel (S x + i, S y + j) in frame f of the S W x S H image -- same Param otherwise, same camera, stream, keys,
+ *   estimator, arithmetic mode.
+ * The camera ray, the random stream and every per-pixel certificate are the fine pixel's; only the accumulator address is the coarse
+ * pixel's, and samples are still added per pixel in frame order.  The fine image has the same field of view and aspect
+ * (u = (2 px - W) / W, v = (2 py - H) / W), so the S^2 fine rays tile the pixel's footprint: a box-filtered pixel.  Pixel x of the
+ * reference's camera is the point u = (2x - W) / W, the LEFT EDGE of the cell [x, x+1); the fine rays sample that cell at offsets
+ * i / S, j / S.  Against an S = 1 render the image content therefore moves by (S - 1) / (2 S) of a pixel: the reference's own pixel
+ * convention made visible, not an error.
+ * (i, j) is a pure integer function of (x, y, f, S), independent of the keys (vp_subpixel_offset computes it on the host):
+ *   h = wang_hash(((x << 16) | y) ^ 0x9E3779B9)     wang_hash: sampler.h:3-11
+ *   k = ((uint32) f + h) mod S^2                     uint32 wrap-around arithmetic
+ *   r = k with its 2m bits reversed                  bit b -> bit 2m-1-b
+ *   i = bits 0, 2, 4, ... of r packed into m bits,   j = bits 1, 3, 5, ... of r
+ * Any 4^t consecutive frames, t <= m, hit each of the 2^t x 2^t sub-squares of the pixel exactly once; S^2 frames cover the lattice.
+ * S = 1 gives (0, 0) always: the identity, not a bit of the default behaviour changes.
+ *   Built for: every estimator, stream, tracking and environment mode, both arithmetic modes, uchar and float volumes, shards,
+ *   vp_render_frames and render_kernel (look-ahead, pipeline) -- with work counters off: a render with S > 1 while counters are enabled
+ *   fails with VP_E_STATE (the context stays usable).
+ *   Limits: the fine coordinates go into the 16-bit halves of x << 16 | y: a render with S W > 65536 or S H > 65536 fails with VP_E_ARG.
+ *   The per-pixel table is the fine image's (S^2 x 32 bytes per pixel: 245 MB at 800x600, S = 4): VP_E_NOMEM where it does not fit.
+ *   vp_get_pixel_table(P) keeps describing exactly the image P names; vp_get_pixel_lists returns the lists of the current factor: a pixel
+ *   is general if any of its S^2 fine pixels is (or if they mix the other two classes), box-missing if all of them are, light if all are.
+ * vp_set_subpixel checks its argument before it touches the device, stops look-ahead batches in flight, waits for pipelined launches
+ * and drops the per-view tables and pixel lists.  vp_subpixel_offset needs no device; x, y <= 65535, frame >= 0. */
+#define VP_SUBPIXEL_MAX 8
+int vp_set_subpixel(int s);                            /* default 1 (VP_SUBPIXEL) */
+int vp_get_subpixel(void);
+int vp_subpixel_offset(unsigned x, unsigned y, int frame, int s, int* i, int* j);
 /* test hook: the tables of the current environment: cdf_y[h], cdf_x[w*h] (row CDFs), HDRpdfnormAlt; any may be NULL */
 int vp_get_env_tables(float* cdf_y, float* cdf_x, float* pdfnorm_alt);
 /* brick edge (power of two, 1 = the reference's per-voxel table) used by the NEXT init_cuda */
