@@ -1,0 +1,123 @@
+// vp_adaptive.cpp -- per-pixel statistics and adaptive sampling (include/volpath.h vp_pixel_stats): vp_render_frames_stats, a uniform
+// render whose reduce also takes the statistics; vp_render_adaptive, serial rounds of do_render on the ACTIVE pixels -- a compaction of
+// the context's cached lists by the FROZEN bit of the caller's records, before the first round and after each --; the output stage.
+// The integrator kernels are the plain calls', on shorter lists; the frozen set lives in the caller's buffer and nowhere else.
+#include "vp_state.h"
+
+static_assert(sizeof(vp_pixel_stats) == 24 && sizeof(vp::PixelStatsDev) == sizeof(vp_pixel_stats), "vp_pixel_stats layout (include/volpath.h)");
+static_assert(offsetof(vp_pixel_stats, sum_y2) == 8 && offsetof(vp_pixel_stats, n) == 16 && offsetof(vp_pixel_stats, flags) == 20, "vp_pixel_stats layout");
+static_assert(offsetof(vp::PixelStatsDev, n) == 16 && offsetof(vp::PixelStatsDev, flags) == 20, "PixelStatsDev mirrors vp_pixel_stats");
+
+namespace vph __attribute__((visibility("hidden")))
+{
+// the active pixels of the cached lists into G.d_act, their three counts into cnt: one small synchronisation
+static int compact_active(const Param* p, const vp_pixel_stats* d_stats, unsigned cnt[3])
+{
+    const unsigned n[3] = {G.n_general, G.n_light, G.n_miss};
+    const unsigned nblocks = compact_blocks(n[0] + n[1] + n[2]);
+    unsigned* d_totals = G.d_act_scratch + (size_t)3 * nblocks;
+    launch_compact_active(G.d_tiles, n, p->width, (const PixelStatsDev*)d_stats, G.d_act_scratch, d_totals, G.d_act, G.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cnt, d_totals, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, G.stream));
+    HIPCHK(hipStreamSynchronize(G.stream));
+    if (cnt[0] > n[0] || cnt[1] > n[1] || cnt[2] > n[2]) return fail(VP_E_STATE, "active lists hold more pixels than the lists they come from");
+    return VP_OK;
+}
+// the context's buffers for a list of n pixels: grown on demand, freed with the context
+static int reserve_active(size_t n)
+{
+    const size_t words = (size_t)3 * compact_blocks((unsigned)n) + 4;
+    if (n <= G.act_cap && words <= G.act_scratch_words) return VP_OK;
+    HIPCHK(hipStreamSynchronize(G.stream));
+    if (n > G.act_cap)
+    {
+        if (G.d_act) HIPCHK(hipFree(G.d_act));
+        G.d_act = nullptr; G.act_cap = 0;
+        HIPCHK(hipMalloc((void**)&G.d_act, n * sizeof(unsigned)));
+        G.act_cap = n;
+    }
+    if (words > G.act_scratch_words)
+    {
+        if (G.d_act_scratch) HIPCHK(hipFree(G.d_act_scratch));
+        G.d_act_scratch = nullptr; G.act_scratch_words = 0;
+        HIPCHK(hipMalloc((void**)&G.d_act_scratch, words * sizeof(unsigned)));
+        G.act_scratch_words = words;
+    }
+    return VP_OK;
+}
+}  // namespace vph
+
+using namespace vph;
+
+extern "C" {
+int vp_render_frames_stats(vp_float4* d_output, vp_pixel_stats* d_stats, int first_frame, int n_frames, const Param* p)
+{
+    if (!d_output || !d_stats || !p || n_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "vp_render_frames_stats: bad arguments");
+    StatsDev T = {};
+    T.stats = (PixelStatsDev*)d_stats;
+    return do_render(d_output, first_frame, n_frames, p, false, nullptr, nullptr, &T);
+}
+int vp_render_adaptive(vp_float4* d_output, vp_pixel_stats* d_stats, int first_frame, int max_frames, const Param* p, const vp_adaptive* a,
+                       vp_adaptive_result* result)
+{
+    if (result) memset(result, 0, sizeof *result);
+    if (!d_output || !d_stats || !p || !a) return fail(VP_E_ARG, "vp_render_adaptive: null pointer");
+    if (max_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "vp_render_adaptive: frames [%d, %d + %d) out of range", first_frame, first_frame, max_frames);
+    if (a->min_frames < 2) return fail(VP_E_ARG, "vp_render_adaptive: min_frames %d (a variance estimate needs two samples)", a->min_frames);
+    if (a->round_frames < 1) return fail(VP_E_ARG, "vp_render_adaptive: round_frames %d", a->round_frames);
+    if (!(a->rel_tol >= 0.0f) || !(a->floor_y >= 0.0f)) return fail(VP_E_ARG, "vp_render_adaptive: rel_tol and floor_y must be numbers >= 0");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (G.count) return fail(VP_E_STATE, "vp_render_adaptive is not built for work counters");
+    if (!G.have_volume) return fail(VP_E_STATE, "render before init_cuda");
+    if (!G.have_env) return fail(VP_E_STATE, "render before init_envmap");
+    if (!G.have_sun) return fail(VP_E_STATE, "render before set_sun");
+    if (!G.have_cam) return fail(VP_E_STATE, "render before copy_inv_view_matrix");
+    if (G.est == VP_EST_DECOMP && (long long)first_frame + max_frames - 1 > 10 && !G.S.opacity)
+        return fail(VP_E_NOOPACITY, "frames beyond 10 need precompute_opacity (kernel.cu:2183, host.cpp:336-343)");
+    // rounds are serial and run on the caller's stream: look-ahead batches stop, pipelined launches are waited for
+    if ((rc = la_quiesce())) return rc;
+    if ((rc = vp_prepare(p))) return rc;   // the cached lists of p: what is compacted
+    const size_t n_all = (size_t)G.n_general + G.n_light + G.n_miss;
+    if (n_all == 0) return VP_OK;          // a shard without a tile
+    if ((rc = reserve_active(n_all))) return rc;
+    StatsDev T = {};
+    T.stats = (PixelStatsDev*)d_stats; T.adaptive = 1u; T.min_frames = (unsigned)a->min_frames;
+    T.tol = (double)a->rel_tol; T.fl = (double)a->floor_y;
+    unsigned cnt[3] = {0, 0, 0};
+    if ((rc = compact_active(p, d_stats, cnt))) return rc;
+    int done = 0;
+    unsigned rounds = 0;
+    unsigned long long samples = 0;
+    while (done < max_frames && (size_t)cnt[0] + cnt[1] + cnt[2] > 0)
+    {
+        const int f = std::min(a->round_frames, max_frames - done);
+        const PixelLists PL = {G.d_act, cnt[0], cnt[1], cnt[2]};
+        if ((rc = do_render(d_output, first_frame + done, f, p, false, nullptr, &PL, &T))) return rc;
+        samples += ((unsigned long long)cnt[0] + cnt[1] + cnt[2]) * (unsigned long long)f;
+        done += f; rounds++;
+        if (result) { result->samples = samples; result->rounds = rounds; result->frames_used = (uint32_t)done; }
+        if ((rc = compact_active(p, d_stats, cnt))) return rc;   // round k + 1 needs round k's decisions
+    }
+    if (result) result->active_left = cnt[0] + cnt[1] + cnt[2];
+    return VP_OK;
+}
+int vp_scale_by_count(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, int size, float scale)
+{
+    if (!dst || !src || !d_stats || size < 0) return fail(VP_E_ARG, "vp_scale_by_count: bad arguments");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (size) launch_scale_by_count((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, size, scale, G.stream);
+    HIPCHK(hipGetLastError());
+    return VP_OK;
+}
+int vp_stats_rel_error(float* dst, const vp_pixel_stats* d_stats, int size, float floor_y)
+{
+    if (!dst || !d_stats || size < 0 || !(floor_y >= 0.0f)) return fail(VP_E_ARG, "vp_stats_rel_error: bad arguments");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (size) launch_stats_rel_error(dst, (const PixelStatsDev*)d_stats, size, floor_y, G.stream);
+    HIPCHK(hipGetLastError());
+    return VP_OK;
+}
+}  // extern "C"

@@ -588,6 +588,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
         if (D.d_tiles) (void)hipFree(D.d_tiles);
         if (D.d_tile_rows) (void)hipFree(D.d_tile_rows);
         if (D.d_tile_scratch) (void)hipFree(D.d_tile_scratch);
+        if (D.d_act) (void)hipFree(D.d_act);
+        if (D.d_act_scratch) (void)hipFree(D.d_act_scratch);
         for (int i = 0; i < kTargets; i++)
         {
             if (D.aux_stream[i]) { (void)hipStreamSynchronize(D.aux_stream[i]); (void)hipStreamDestroy(D.aux_stream[i]); }

@@ -202,6 +202,25 @@ void launch_empty_table(const SceneDev& S, unsigned width, unsigned height, cons
 // the direction table of the exit flights from the danger volume: planes = 3 * nx*ny*nz bytes; one small kernel per slice and direction
 void launch_exit_table(const unsigned char* danger, unsigned char* planes, int nx, int ny, int nz, hipStream_t st);
 void launch_reduce(const LaunchDev& L, hipStream_t st);
+// Per-pixel statistics (include/volpath.h vp_pixel_stats, the same 24 bytes) and what launch_reduce_stats does with them: the
+// reduce of a staged launch that also adds each sample's luminance to its pixel's record, and -- adaptive: a round of
+// vp_render_adaptive -- freezes the records whose criterion holds (tol, fl: the binary32 arguments widened)
+struct PixelStatsDev { double sum_y, sum_y2; unsigned n, flags; };
+struct StatsDev
+{
+    PixelStatsDev* stats;   // width * height records, indexed like the accumulator
+    unsigned adaptive;      // 1: evaluate the criterion and set VP_STATS_FROZEN; 0: `flags` is neither read nor written
+    unsigned min_frames;
+    double   tol, fl;
+};
+void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st);
+// the pixels of the class-ordered list src (n[0] general, n[1] light, n[2] box-missing) whose record is not frozen, in src's order,
+// class by class, into d_out (room for all of src), and their three counts into d_totals; d_block_counts[3 * compact_blocks(n)] scratch
+inline unsigned compact_blocks(unsigned n) { return (n + 1023u) / 1024u; }
+void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PixelStatsDev* stats, unsigned* d_block_counts,
+                           unsigned* d_totals, unsigned* d_out, hipStream_t st);
+void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st);
+void launch_stats_rel_error(float* dst, const PixelStatsDev* stats, int size, float floor_y, hipStream_t st);
 // bricks: cells in 4x4x4 bricks (vp_device.h cell_index); the buffer then holds ceil(n/4)^3 * 64 cells
 void launch_pack_u8(const unsigned char* vol, uint2* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);
 void launch_pack_f32(const float* vol, float* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);

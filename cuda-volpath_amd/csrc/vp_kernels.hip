@@ -483,6 +483,136 @@ __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void pixlist_write_k(PixListDev D
     out[class_base + block_offsets[3 * blockIdx.x + c] + before + rank_in_wave] = pix;
 }
 
+// ---- per-pixel statistics and adaptive sampling (include/volpath.h vp_pixel_stats; vp_adaptive.cpp).  reduce_stage_k's job with the
+// statistics of the definition taken where the samples are summed: per slot of L.pixels (ALL pixels of the launch -- the rank's, or the
+// ACTIVE ones of an adaptive round) the staged frames are added to the accumulator in frame order, exactly as reduce_stage_k adds
+// them, and each sample's luminance goes into the record of its pixel: binary32 luminance, binary64 sums, one after the other (no
+// closed form for the per-pixel constants either: n sequential additions are not one product).  T.adaptive: the record's criterion
+// is evaluated after the round and the FROZEN bit set; otherwise `flags` is neither read nor written.
+__device__ __forceinline__ float stats_luminance(const float4& v) { return (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z; }
+__device__ __forceinline__ bool stats_converged(double sy, double sy2, unsigned n, double tol, double fl)
+{
+    const double nd  = (double)n;
+    const double lhs = nd * sy2 - sy * sy;
+    const double nf  = nd * fl;
+    const double m   = sy > nf ? sy : nf;
+    const double rhs = ((tol * tol) * (nd - 1.0)) * (m * m);
+    return lhs <= rhs;   // (false when either side is NaN)
+}
+__global__ __launch_bounds__(256) void reduce_stats_k(LaunchDev L, StatsDev T)
+{
+    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.nslots) return;
+    unsigned pix = L.pixels[slot];
+    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
+    float4   a   = L.out[idx];
+    PixelStatsDev* rec = T.stats + idx;
+    double   sy = rec->sum_y, sy2 = rec->sum_y2;
+    if (slot >= L.const_from)
+    {
+        const float4 v = L.stage_const[slot];
+        const double y = (double)stats_luminance(v), yy = y * y;
+        for (int f = 0; f < L.nframes; f++)
+        {
+            a   = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
+            sy  = sy + y;
+            sy2 = sy2 + yy;
+        }
+    }
+    else
+        for (int f = 0; f < L.nframes; f++)
+        {
+            float4 v = L.stage[(size_t)f * L.stage_stride + slot];
+            a        = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
+            const double y = (double)stats_luminance(v);
+            sy  = sy + y;
+            sy2 = sy2 + y * y;
+        }
+    L.out[idx] = a;
+    const unsigned n = rec->n + (unsigned)L.nframes;
+    rec->sum_y = sy; rec->sum_y2 = sy2; rec->n = n;
+    if (T.adaptive && n >= T.min_frames && stats_converged(sy, sy2, n, T.tol, T.fl)) rec->flags |= 1u;   // VP_STATS_FROZEN
+}
+// A stable compaction of a class-ordered pixel list (src: n[0] general, n[1] light, n[2] box-missing pixels) by the FROZEN bit of the
+// pixels' records: the active pixels of each class in the order they have in src, class by class, and the three counts.  The pattern of
+// pixlist_*_k: per-block class counts, pixlist_scan_k over them, the scatter with wave-ballot ranks.
+struct CompactDev
+{
+    const unsigned* src;
+    unsigned n[3];
+    unsigned width;
+    const PixelStatsDev* stats;
+};
+__device__ __forceinline__ unsigned compact_slot(const CompactDev& D, unsigned s, unsigned& pix)
+{
+    // class of slot s of src (3 = beyond the list, or frozen) and its pixel
+    pix = 0;
+    if (s >= D.n[0] + D.n[1] + D.n[2]) return 3u;
+    pix = D.src[s];
+    if (D.stats[(size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * D.width].flags & 1u) return 3u;
+    return s < D.n[0] ? 0u : s < D.n[0] + D.n[1] ? 1u : 2u;
+}
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_count_k(CompactDev D, unsigned* block_counts)
+{
+    __shared__ unsigned cnt[3];
+    if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned pix;
+    const unsigned c = compact_slot(D, blockIdx.x * VP_PIXLIST_BLOCK + threadIdx.x, pix);
+    for (unsigned k = 0; k < 3; k++)
+    {
+        const unsigned long long m = __ballot(c == k);
+        if ((threadIdx.x & 63u) == 0 && m) atomicAdd(&cnt[k], (unsigned)__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) block_counts[3 * blockIdx.x + threadIdx.x] = cnt[threadIdx.x];
+}
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_write_k(CompactDev D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
+{
+    __shared__ unsigned wave_cnt[VP_PIXLIST_BLOCK / 64][3];
+    unsigned pix;
+    const unsigned c    = compact_slot(D, blockIdx.x * VP_PIXLIST_BLOCK + threadIdx.x, pix);
+    const unsigned wave = threadIdx.x >> 6;
+    unsigned rank_in_wave = 0;
+    for (unsigned k = 0; k < 3; k++)
+    {
+        const unsigned long long m = __ballot(c == k);
+        if (c == k) rank_in_wave = lane_rank(m);
+        if ((threadIdx.x & 63u) == 0) wave_cnt[wave][k] = (unsigned)__popcll(m);
+    }
+    __syncthreads();
+    if (c > 2u) return;
+    unsigned before = 0;
+    for (unsigned w = 0; w < wave; w++) before += wave_cnt[w][c];
+    const unsigned class_base = c == 0 ? 0u : c == 1 ? totals[0] : totals[0] + totals[1];
+    // (at most as many active pixels as src holds: `out` has room for all of src)
+    out[class_base + block_offsets[3 * blockIdx.x + c] + before + rank_in_wave] = pix;
+}
+// the output stage of a render with per-pixel sample counts: dst = src * (scale / n), a correctly rounded binary32 divide; n = 0 gives 0
+__global__ void scale_by_count_k(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float scale)
+{
+    int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= size) return;
+    const unsigned n = stats[idx].n;
+    float4 v = src[idx];
+    if (!n) { dst[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); return; }
+    const float s = scale / (float)n;
+    dst[idx] = make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
+}
+// the noise map: the estimated standard error of the mean luminance over max(mean, floor), binary64, rounded once
+__global__ void stats_rel_error_k(float* dst, const PixelStatsDev* stats, int size, double fl)
+{
+    int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= size) return;
+    const PixelStatsDev r = stats[idx];
+    if (r.n < 2u) { dst[idx] = 0.0f; return; }
+    const double nd  = (double)r.n;
+    const double lhs = nd * r.sum_y2 - r.sum_y * r.sum_y;
+    const double var = (lhs > 0.0 ? lhs : 0.0) / (nd * nd * (nd - 1.0));
+    const double mean = r.sum_y / nd;
+    dst[idx] = (float)(sqrt(var) / (mean > fl ? mean : fl));
+}
+
 // The samples of a pixel whose camera ray misses the box are the same in every frame: set-up finds no hit (intersectBox,
 // kernel.cu:1336-1345 / :2020-2031), background() is evaluated for the camera direction with throughput 1 (quirk Q3: no jitter)
 // and the sample is written -- no draw is consumed.  One thread per such pixel evaluates that once, with the integrator's own
@@ -1383,6 +1513,28 @@ void launch_reduce(const LaunchDev& L, hipStream_t st)
 {
     unsigned per_frame = L.nslots;
     hipLaunchKernelGGL(reduce_stage_k, dim3((per_frame + 255) / 256), dim3(256), 0, st, L);
+}
+void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st)
+{
+    hipLaunchKernelGGL(reduce_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, T);
+}
+void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PixelStatsDev* stats, unsigned* d_block_counts,
+                           unsigned* d_totals, unsigned* d_out, hipStream_t st)
+{
+    CompactDev D;
+    D.src = src; D.n[0] = n[0]; D.n[1] = n[1]; D.n[2] = n[2]; D.width = width; D.stats = stats;
+    const unsigned nblocks = compact_blocks(n[0] + n[1] + n[2]);
+    hipLaunchKernelGGL(compact_count_k, dim3(nblocks), dim3(VP_PIXLIST_BLOCK), 0, st, D, d_block_counts);
+    hipLaunchKernelGGL(pixlist_scan_k, dim3(1), dim3(VP_PIXLIST_BLOCK), 0, st, d_block_counts, nblocks, d_totals);
+    hipLaunchKernelGGL(compact_write_k, dim3(nblocks), dim3(VP_PIXLIST_BLOCK), 0, st, D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
+}
+void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st)
+{
+    hipLaunchKernelGGL(scale_by_count_k, dim3((size + 255) / 256), dim3(256), 0, st, dst, src, stats, size, s);
+}
+void launch_stats_rel_error(float* dst, const PixelStatsDev* stats, int size, float floor_y, hipStream_t st)
+{
+    hipLaunchKernelGGL(stats_rel_error_k, dim3((size + 255) / 256), dim3(256), 0, st, dst, stats, size, (double)floor_y);
 }
 void launch_pack_u8(const unsigned char* vol, uint2* cells, int nx, int ny, int nz, bool bricks, hipStream_t st)
 {

@@ -125,18 +125,18 @@ static bool pipe_target(size_t per_frame, int nframes, bool aux, Target* T)
     return true;
 }
 // the camera rays' walk ahead of the integrator is built for this estimator and volume (do_render; counting launches aside)
-static bool approach_possible(const float4* crawl)
+static bool approach_possible(const float4* crawl, unsigned n_general)
 {
     const bool dense_volume = G.marked_fraction > G.dense_fraction;   // (vp_state.h: little empty space for the walk to cross)
     // (a sub-pixel factor: the integrator walks the camera ray itself -- the approach kernels and the segment table are statements about
     // ONE camera ray per pixel, and with S^2 of them a wave of one pixel x 64 frames no longer shares a ray: DESIGN.md section 2.2)
     return G.use_approach && !G.sub_shift && (G.est == VP_EST_GLOBAL || (G.est == VP_EST_DECOMP && G.use_approach_local && !dense_volume)) && !G.trk && !G.env_mis &&
-           crawl && G.n_general;
+           crawl && n_general;
 }
 
 // where a render launch goes: the caller's stream with the shared staging buffer, or a look-ahead slot
 
-int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only, const Target* tgt)
+int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only, const Target* tgt, const PixelLists* lists, const StatsDev* stats)
 {
     int rc = ensure_device();
     if (rc) return rc;
@@ -182,6 +182,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         if (!G.wait_lanes_set && G.rng == VP_RNG_SAMPLERH && G.trk == VP_TRACK_SPECTRAL) L.wait_lanes = 24;
     }
     if (sh.per_frame == 0) return VP_OK;
+    if ((lists || stats) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics");
     // (a sub-pixel factor: the per-pixel table of the image the samples are computed on; lists, staging and output stay this image's)
     L.sub_shift = (unsigned)G.sub_shift;
     const Param fine = subpixel_param(p);
@@ -189,19 +190,26 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     if (rc) return rc;
     rc = ensure_pixel_lists(p, L.crawl, sh);
     if (rc) return rc;
+    // the lists this call launches on: the context's cached ones, or the caller's (vp_adaptive.cpp: the active pixels of a round --
+    // a class-ordered subset of the cached lists; staging rows, sample queues and the reduce are then that subset's)
+    const PixelLists PL = lists ? *lists : PixelLists{G.d_tiles, G.n_general, G.n_light, G.n_miss};
+    const size_t per_frame = (size_t)PL.n_general + PL.n_light + PL.n_miss;
+    if (per_frame == 0) return VP_OK;
+    // a call with statistics is staged whatever its length (render_k's direct accumulation has none) and stays on the caller's stream
+    const bool staged = nframes > 1 || stage_only || stats;
     rc = ensure_sun_clip(&L.sun_clip, &L.clip_ds);
     if (rc) return rc;
     L.count_clips = getenv("VP_DEBUG_COUNT_CLIPS") ? 1u : 0u;
     rc = exit_flights(L);
     if (rc) return rc;
     bool light_const = false;
-    if (G.n_light)
+    if (PL.n_light)
     {
         rc = ensure_light_const(p, &light_const);
         if (rc) return rc;
     }
     G.last_light_const = light_const ? 1 : 0;
-    if (G.est == VP_EST_GLOBAL && G.n_light && !light_const)
+    if (G.est == VP_EST_GLOBAL && PL.n_light && !light_const)
     {
         rc = ensure_thr_table(p, &L.thr_table);
         if (rc) return rc;
@@ -210,7 +218,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     // the camera rays' free flights through certified-empty cells in kernels of their own, ahead of the integrator (approach_k: global
     // majorant; approach_local_k: decomposition estimator; spectral tracking, passive environment, staged launches)
     bool approach = false, approach_thr = false;
-    if (approach_possible(L.crawl) && (!G.count || getenv("VP_COUNT_APPROACH")))   // counting launches: the integrator makes every step itself unless asked (block tallies)
+    if (approach_possible(L.crawl, PL.n_general) && (!G.count || getenv("VP_COUNT_APPROACH")))   // counting launches: the integrator makes every step itself unless asked (block tallies)
     {
         // global majorant: one majorant for the whole walk, checked here; decomposition: approach_local_k checks each segment's own
         bool identity = true;
@@ -231,27 +239,26 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     // crawl table and the pixel lists whatever the frame count, so that no later launch rebuilds it and waits for those in flight;
     // read by waves of one pixel x 64 frames)
     L.seg_table = nullptr;
-    if (approach && G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6)
+    if (approach && G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && !lists)
     {
         const float4* seg = nullptr;
         rc = ensure_segment_table(p, L.crawl, &seg);
         if (rc) return rc;
         if (nframes >= 64) L.seg_table = seg;
     }
-    const size_t per_frame = sh.per_frame;
     if (0xfffffff0u / per_frame < 1) return fail(VP_E_ARG, "image too large for the 32-bit sample queue");
     L.stage_stride = (unsigned)per_frame;
-    size_t max_f = (nframes > 1 || stage_only) ? stage_frames_cap(per_frame, *T.stage_bytes) : 1;
+    size_t max_f = staged ? stage_frames_cap(per_frame, *T.stage_bytes) : 1;
     SceneDev S = G.S;
     S.linear   = G.linear ? 1 : 0;
     // The staging slot of the decomposition estimator's hand-over holds the segment origin and the distance reached in it: the stream's
     // state (a pair index, or sampler.h's two words) goes beside it.  Sized ONCE, before the launch loop (no synchronisation, no early
     // return between a launch's events).
-    const bool appr_aux_needed = approach && G.est == VP_EST_DECOMP && (nframes > 1 || stage_only);
+    const bool appr_aux_needed = approach && G.est == VP_EST_DECOMP && staged;
     // A staged call of vp_render_frames goes to the next pipeline slot when the slot holds it in one launch (counting launches stay on the
     // caller's stream).  Otherwise -- VP_NO_PIPELINE, no memory for the slot -- the caller's stream, as before: same bits either way.
     const int  ps    = G.pipe_next;
-    const bool piped = !tgt && !stage_only && nframes > 1 && G.pipeline && !G.count && pipe_target(per_frame, nframes, appr_aux_needed, &T);
+    const bool piped = !tgt && !stage_only && !lists && !stats && nframes > 1 && G.pipeline && !G.count && pipe_target(per_frame, nframes, appr_aux_needed, &T);
     if (piped) max_f = (size_t)nframes;
     else if (!tgt) G.pipe_fence = true;   // (the caller's stream uses slot 0's buffers: the next pipelined launch waits for it)
     G.last_pipelined = piped ? 1 : 0;
@@ -280,7 +287,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         if (stage_only && f != nframes) return fail(VP_E_ARG, "look-ahead batch does not fit the staging buffer");
         L.frame0 = first + done;
         L.nframes = f;
-        if (f > 1 || stage_only)
+        if (staged)
         {
             size_t need = per_frame * (size_t)f * sizeof(float4);
             if (need > *T.stage_bytes)
@@ -316,7 +323,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         L.const_from = 0xffffffffu; L.stage_const = nullptr;
         if (L.stage && G.use_const_rows && !G.sub_shift)   // (a sub-pixel factor: constants of the FINE pixel, staged per frame by subpixel_fill_k)
         {
-            L.const_from  = (unsigned)(G.n_general + ((G.n_light && !light_const) ? G.n_light : 0u));
+            L.const_from  = (unsigned)(PL.n_general + ((PL.n_light && !light_const) ? PL.n_light : 0u));
             L.stage_const = L.stage;
         }
         G.last_const_from = L.const_from;
@@ -367,9 +374,9 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         // COUPLING (two tuning decisions that depend on each other): approach_local_k needs 47 vector registers (kernel_resources.py);
         // beside four 97-102-register LDS-table waves AND the helper's fifth 96-register wave a SIMD has 27 left, beside the four
         // alone 124.  If approach_local_k's register count or the helper's occupancy changes, re-measure the `!tgt` below.
-        const bool lds_helper = lds_form == 1 && G.lds_helper && G.n_general && !(G.n_light && !light_const) && !tgt;
+        const bool lds_helper = lds_form == 1 && G.lds_helper && PL.n_general && !(PL.n_light && !light_const) && !tgt;
         bool fork_recorded = false;
-        if ((G.n_light && G.n_general && !light_const && G.light_overlap) || lds_helper)
+        if ((PL.n_light && PL.n_general && !light_const && G.light_overlap) || lds_helper)
         {
             const int ti = T.index;
             if (!G.aux_ev[ti][0] && hipEventCreateWithFlags(&G.aux_ev[ti][0], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); G.aux_ev[ti][0] = nullptr; }
@@ -382,12 +389,12 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         // one launch per pixel class: the general pixels, then the light ones (their own kernel, their own sample queues)
         for (int cls = 0; cls < 2 && le == hipSuccess; cls++)
         {
-            const unsigned nt = cls ? G.n_light : G.n_general;
+            const unsigned nt = cls ? PL.n_light : PL.n_general;
             if (!nt) continue;
             if (G.debug_only_class >= 0 && G.debug_only_class != cls) continue;  // VP_DEBUG_ONLY_CLASS: block tallies of one kernel
-            L.pixels      = G.d_tiles + (cls ? G.n_general : 0);
+            L.pixels      = PL.pixels + (cls ? PL.n_general : 0);
             L.nslots      = nt;
-            L.slot_base   = cls ? G.n_general : 0u;
+            L.slot_base   = cls ? PL.n_general : 0u;
             L.total_items = (unsigned)((size_t)nt * (size_t)f);
             L.queue       = T.queue + (cls ? kQueueWords : 0);
             // chunks of pixels x frames (general class): only when the frame count is a multiple of the frame block
@@ -398,7 +405,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
             const unsigned bsz  = ldsb ? VP_BLOCK_LDS : VP_BLOCK;
             unsigned waves  = (L.total_items + 63) / 64;
             unsigned blocks = (waves + (bsz / 64) - 1) / (bsz / 64);
-            const bool     both = G.n_light && G.n_general && !light_const;
+            const bool     both = PL.n_light && PL.n_general && !light_const;
             unsigned       bpc  = G.blocks_per_cu;
             // what fits a SIMD's 512 vector registers side by side: global majorant 4 x 96 + 2 x 64,
             // local majorant 5 x 96 + ... the light kernel's blocks take what is left as general blocks retire
@@ -517,12 +524,12 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
                 ct.stop();
             }
         }
-        if (G.n_miss && le == hipSuccess)
+        if (PL.n_miss && le == hipSuccess)
         {
             // the pixels whose camera ray misses the box: one constant per pixel, written for every frame (miss_fill_k)
-            L.pixels      = G.d_tiles + G.n_general + G.n_light;
-            L.nslots      = G.n_miss;
-            L.slot_base   = G.n_general + G.n_light;
+            L.pixels      = PL.pixels + PL.n_general + PL.n_light;
+            L.nslots      = PL.n_miss;
+            L.slot_base   = PL.n_general + PL.n_light;
             L.total_items = 0;
             ClassTimer ct(2, T.stream);
             launch_miss_fill(S, L, G.est != VP_EST_GLOBAL, T.stream);
@@ -535,7 +542,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         else { put_event(e0); put_event(e1); }
         if (le != hipSuccess) return fail(VP_E_NODEVICE, "render launch -> %s", hipGetErrorString(le));
         // for the add-kernel: all tiles of the rank
-        L.pixels = G.d_tiles; L.nslots = (unsigned)per_frame; L.slot_base = 0;
+        L.pixels = PL.pixels; L.nslots = (unsigned)per_frame; L.slot_base = 0;
         if (L.stage && !stage_only)
         {
             // (a pipelined launch: the caller-visible write stays on the caller's stream, behind the slot's launch)
@@ -544,7 +551,15 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
                 HIPCHK(hipEventRecord(G.pipe_done[ps], T.stream));
                 HIPCHK(hipStreamWaitEvent(G.stream, G.pipe_done[ps], 0));
             }
-            launch_reduce(L, G.stream);
+            if (stats)
+            {
+                // (an adaptive round that the staging cap splits into several launches: the criterion is the ROUND's, evaluated in its
+                // last launch -- a record frozen on a part of the round would stay frozen)
+                StatsDev R = *stats;
+                R.adaptive = stats->adaptive && done + f == nframes ? 1u : 0u;
+                launch_reduce_stats(L, R, G.stream);
+            }
+            else launch_reduce(L, G.stream);
             HIPCHK(hipGetLastError());
             if (piped)
             {
@@ -726,7 +741,7 @@ int vp_prepare(const Param* p)
         rc = ensure_thr_table(p, &thr);
         if (rc) return rc;
     }
-    if (G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && approach_possible(table))   // (the decomposition walk's segment table: do_render)
+    if (G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && approach_possible(table, G.n_general))   // (the decomposition walk's segment table: do_render)
     {
         const float4* seg = nullptr;
         rc = ensure_segment_table(p, table, &seg);

@@ -1,7 +1,8 @@
 // vp_state.h -- what the host-side translation units of libvolpath_hip.so share: the per-context State, the error helpers and the
 // internal functions of vp_context.cpp (device, volume, environment, contexts, Part 1 and the setters of include/volpath.h),
 // vp_tables.cpp (the tables a launch reads: optical depth, per-pixel, sun, exit, pixel lists), vp_render.cpp (do_render: one
-// staged launch; counters and timing) and vp_lookahead.cpp (render_kernel's frame look-ahead: frozen since round 4, see there).
+// staged launch; counters and timing), vp_lookahead.cpp (render_kernel's frame look-ahead: frozen since round 4, see there) and
+// vp_adaptive.cpp (per-pixel statistics and adaptive sampling: rounds of do_render on the pixels whose record is not frozen).
 // Round 5 split of the former vp_api.cpp (2 200 lines), no behaviour change.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -176,6 +177,13 @@ struct State
     unsigned*   d_tile_rows = nullptr;    // first owned tile of each tile row (pixlist kernels)
     unsigned*   d_tile_scratch = nullptr; // per-block class counts + the three totals
     std::vector<unsigned char> tiles_shape_key;
+    // vp_render_adaptive (vp_adaptive.cpp): the ACTIVE pixels of the lists above -- those whose record is not frozen --, class by class
+    // in the same order, rebuilt from the caller's records at the start of a call and after every round (compact_*_k); the block
+    // counts and three totals of that compaction.  Never the cached lists: those, their key and vp_get_pixel_lists stay as they are.
+    unsigned*   d_act       = nullptr;
+    size_t      act_cap     = 0;
+    unsigned*   d_act_scratch = nullptr;
+    size_t      act_scratch_words = 0;
     // the light kernel runs beside the general one on a stream of its own (ALU-bound waves fill the issue slots the general
     // kernel's waves leave while they wait for cells): one auxiliary stream and two events per launch target
     bool        light_overlap = true;
@@ -320,7 +328,13 @@ int    ensure_segment_table(const Param* p, const float4* crawl, const float4** 
 // ---- vp_render.cpp
 // where a launch stages its samples: the caller's stream and buffers, or a look-ahead slot's
 struct Target { hipStream_t stream; float4** stage; size_t* stage_bytes; unsigned* queue; int index; };
-int  do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only = false, const Target* tgt = nullptr);
+// the pixel lists a launch runs on, class by class: n_general general pixels, n_light light ones, n_miss box-missing ones (y << 16 | x)
+struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss; };
+// lists: null = the context's cached lists of p (built on demand: the plain entry points), else the caller's own -- a class-ordered
+// subset of them (vp_adaptive.cpp).  stats: the reduce also takes the statistics of include/volpath.h (launch_reduce_stats); such a
+// call is staged even for one frame and runs on the caller's stream, not on a pipeline slot.
+int  do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only = false, const Target* tgt = nullptr,
+               const PixelLists* lists = nullptr, const StatsDev* stats = nullptr);
 void trim_events();
 int  pipe_quiesce();   // waits for the pipelined launches in flight; the next one waits for the caller's stream (every change to what launches read)
 // ---- vp_lookahead.cpp

@@ -27,6 +27,12 @@ static void usage()
            "                                                tolerance of include/volpath.h (--rng philox|philox7, spectral, passive)\n"
            "               [--aa 1|2|4|8]                   anti-aliasing: stratified sub-pixel camera rays on an S x S lattice per pixel\n"
            "                                                (vp_set_subpixel: a box-filtered pixel; default 1, or VP_SUBPIXEL)\n"
+           "               [--noise TOL [--min-spp N] [--round N] [--noise-out FILE.hdr]]\n"
+           "                                                adaptive sampling (vp_render_adaptive): a pixel is sampled in rounds of --round\n"
+           "                                                frames (default 32) until the estimated standard error of its mean luminance is\n"
+           "                                                at most TOL x max(mean, 1e-3), from --min-spp frames (default 16) on; --spp is the\n"
+           "                                                maximum.  The image is sum / n per pixel; --noise-out writes the noise map\n"
+           "                                                (vp_stats_rel_error) as HDR.  One GPU: statistics are not reduced across ranks\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -43,6 +49,11 @@ int main(int argc, char** argv)
     int         est = VP_EST_DECOMP, tracking = VP_TRACK_SPECTRAL, env_mode = VP_ENV_PASSIVE, arith = VP_ARITH_EXACT;
     std::string bin, vdb, out = "output0.ppm", devlist;
     int         gpus = 1, aa = 0;   // (0: not given -- the contexts keep their default, VP_SUBPIXEL)
+    bool        adaptive = false;
+    float       noise_tol = 0.0f;
+    const float noise_floor = 1e-3f;
+    int         min_spp = 16, round_frames = 32;   // (the round: not measured yet)
+    std::string noise_out;
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -85,6 +96,17 @@ int main(int argc, char** argv)
             aa = !strcmp(m, "1") ? 1 : !strcmp(m, "2") ? 2 : !strcmp(m, "4") ? 4 : !strcmp(m, "8") ? 8 : 0;
             if (!aa) { fprintf(stderr, "unknown --aa %s (1, 2, 4 or 8)\n", m); usage(); return 2; }
         }
+        else if (a == "--noise")
+        {
+            need(1);
+            char* end = nullptr;
+            noise_tol = strtof(argv[++i], &end);
+            if (end == argv[i] || *end || !(noise_tol >= 0.0f)) { fprintf(stderr, "--noise %s: a tolerance >= 0\n", argv[i]); usage(); return 2; }
+            adaptive = true;
+        }
+        else if (a == "--min-spp") { need(1); min_spp = atoi(argv[++i]); }
+        else if (a == "--round") { need(1); round_frames = atoi(argv[++i]); }
+        else if (a == "--noise-out") { need(1); noise_out = argv[++i]; }
         else if (a == "--sun") { need(2); sunx = (float)atof(argv[++i]); suny = (float)atof(argv[++i]); }
         else if (a == "--batch") { need(1); batch = atoi(argv[++i]); }
         else if (a == "--out") { need(1); out = argv[++i]; }
@@ -109,6 +131,13 @@ int main(int argc, char** argv)
 
     // ---- the GPUs: one context per rank (a single rank runs in the default context, as the reference's host would)
     if (gpus < 1) { usage(); return 2; }
+    if (adaptive && gpus > 1)
+    {
+        fprintf(stderr, "--noise with --gpus %d: reducing per-pixel statistics across ranks is not part of adaptive sampling; use one GPU\n", gpus);
+        return 2;
+    }
+    if (adaptive && (min_spp < 2 || round_frames < 1)) { fprintf(stderr, "--noise needs --min-spp >= 2 and --round >= 1\n"); usage(); return 2; }
+    if (!adaptive && !noise_out.empty()) { fprintf(stderr, "--noise-out needs --noise\n"); return 2; }
     if (arith == VP_ARITH_FAST && (philox == 0 || est == VP_EST_BOUNDED || tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE))
     {
         fprintf(stderr, "--arith fast needs --rng philox|philox7, --estimator decomp|global, spectral tracking and --env passive\n");
@@ -195,7 +224,19 @@ int main(int argc, char** argv)
     auto t0 = std::chrono::high_resolution_clock::now();
     vp_dim3 block = {8, 8, 1}, grid = {(unsigned)(W + 7) / 8, (unsigned)(H + 7) / 8, 1};
     bool    have_opacity = false;
-    for (int s = 0; s < spp;)
+    vp_pixel_stats*    stats = nullptr;
+    vp_adaptive_result ares = {};
+    if (adaptive)
+    {
+        // rounds on the pixels that still need samples, --spp frames at most (vp_render_adaptive)
+        use(0);
+        stats = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
+        if (!stats || vp_memset(stats, 0, (size_t)npix * sizeof(vp_pixel_stats))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        if (est == VP_EST_DECOMP && spp > 11) precompute_opacity(&sky.sun_dir.x);   // host.cpp:336-343
+        const vp_adaptive ad = {noise_tol, noise_floor, min_spp, round_frames};
+        if (vp_render_adaptive(accum[0], stats, 0, spp, &P, &ad, &ares)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+    }
+    for (int s = adaptive ? spp : 0; s < spp;)
     {
         if (!have_opacity && est == VP_EST_DECOMP && (s > 10 || (batch > 0 && s + batch > 11)))
         {
@@ -223,7 +264,14 @@ int main(int argc, char** argv)
     if (gpus > 1 && !reducer.reduce_to_root(ctx, accum, streams, (size_t)npix, rerr)) { fprintf(stderr, "%s\n", rerr.c_str()); return 1; }
     for (int r = gpus - 1; r >= 0; r--) { use(r); vp_synchronize(); }
     double sec = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    printf("%f M samples / s, %d x %d, %d spp, %f s\n", (double)W * H * spp / sec / 1e6, W, H, spp, sec);
+    if (adaptive)
+    {
+        const double all = (double)W * H * spp;
+        printf("adaptive: %llu of %.0f samples (%.1f %%), %u rounds of %d frames, %u pixels still above --noise %g after %u frames\n",
+               (unsigned long long)ares.samples, all, 100.0 * (double)ares.samples / all, ares.rounds, round_frames, ares.active_left, noise_tol, ares.frames_used);
+        printf("%f M samples / s, %d x %d, at most %d spp, %f s\n", (double)ares.samples / sec / 1e6, W, H, spp, sec);
+    }
+    else printf("%f M samples / s, %d x %d, %d spp, %f s\n", (double)W * H * spp / sec / 1e6, W, H, spp, sec);
     if (gpus > 1)
     {
         double tmax = 0, tsum = 0;
@@ -243,12 +291,35 @@ int main(int argc, char** argv)
     use(0);
     bool  hdr = out.size() > 4 && out.substr(out.size() - 4) == ".hdr";
     Image image(W, H);
-    if (hdr) scale(disp, accum[0], npix, 1.0f / spp);
+    if (adaptive)
+    {
+        // every pixel by its own count (the reference's scale assumes one count for all)
+        if (vp_scale_by_count(disp, accum[0], stats, npix, 1.0f)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
+    }
+    else if (hdr) scale(disp, accum[0], npix, 1.0f / spp);
     else gamma_correct(disp, accum[0], npix, 1.0f / spp, 2.2f);
     vp_download(image.buffer(), disp, (size_t)npix * sizeof(vp_float4));
     if (hdr) image.dump_hdr(out.c_str());
     else image.dump_ppm(out.c_str());
     printf("wrote %s\n", out.c_str());
+    if (adaptive && !noise_out.empty())
+    {
+        // the noise map: estimated standard error of the mean luminance over max(mean, floor), grey, as HDR
+        float* d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
+        std::vector<float> noise((size_t)npix);
+        if (!d_noise || vp_stats_rel_error(d_noise, stats, npix, noise_floor) || vp_download(noise.data(), d_noise, (size_t)npix * sizeof(float)))
+        {
+            fprintf(stderr, "%s\n", vp_last_error());
+            return 1;
+        }
+        Image nm(W, H);
+        for (int k = 0; k < npix; k++) { float* px = nm.buffer() + 4 * (size_t)k; px[0] = px[1] = px[2] = noise[(size_t)k]; px[3] = 1.0f; }
+        nm.dump_hdr(noise_out.c_str());
+        printf("wrote %s\n", noise_out.c_str());
+        vp_free(d_noise);
+    }
+    if (stats) vp_free(stats);
     vp_free(disp);
     for (int r = 0; r < gpus; r++)
     {

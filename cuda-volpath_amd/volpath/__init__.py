@@ -30,6 +30,7 @@ PART1_SYMBOLS = ["init_cuda", "set_texture_filter_mode", "free_cuda_buffers", "p
 PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_device", "vp_set_stream", "vp_get_stream", "vp_synchronize",
                  "vp_set_estimator", "vp_set_rng", "vp_set_envmap_sampling", "vp_get_env_tables", "vp_set_lookahead", "vp_set_tracking", "vp_set_bound_brick", "vp_set_shard", "vp_render_frames",
                  "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists",
+                 "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_intersect_box",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -62,6 +63,29 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class PixelStats(C.Structure):
+    """include/volpath.h vp_pixel_stats: 24 bytes per pixel, indexed like the accumulator"""
+    _fields_ = [("sum_y", C.c_double), ("sum_y2", C.c_double), ("n", C.c_uint32), ("flags", C.c_uint32)]
+
+
+# the same record as a numpy dtype (StatsBuffer.download)
+PIXEL_STATS_DTYPE = np.dtype([("sum_y", np.float64), ("sum_y2", np.float64), ("n", np.uint32), ("flags", np.uint32)])
+STATS_FROZEN = 1
+
+
+class Adaptive(C.Structure):
+    """include/volpath.h vp_adaptive"""
+    _fields_ = [("rel_tol", C.c_float), ("floor_y", C.c_float), ("min_frames", C.c_int), ("round_frames", C.c_int)]
+
+
+class AdaptiveResult(C.Structure):
+    """include/volpath.h vp_adaptive_result"""
+    _fields_ = [("samples", C.c_uint64), ("rounds", C.c_uint32), ("active_left", C.c_uint32), ("frames_used", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class VolpathError(RuntimeError):
     pass
 
@@ -89,6 +113,10 @@ def lib():
         L.vp_set_rng.argtypes = [C.c_int, C.c_uint32, C.c_uint32]
         L.vp_get_env_tables.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.vp_render_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_render_frames_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_render_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param), C.POINTER(Adaptive), C.POINTER(AdaptiveResult)]
+        L.vp_scale_by_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float]
+        L.vp_stats_rel_error.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
         L.vp_read_counters.argtypes = [C.POINTER(Counters), C.c_int]
         L.vp_render_time_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
         L.vp_get_bound_table.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 5
@@ -302,6 +330,71 @@ def render_kernel(buf_ptr, spp, P):
 
 def render_frames(buf_ptr, first, n, P):
     _chk(lib().vp_render_frames(buf_ptr, first, n, C.byref(P)))
+
+
+class StatsBuffer:
+    """A caller-owned buffer of width * height PixelStats records in HBM, zeroed (include/volpath.h vp_pixel_stats)."""
+
+    def __init__(self, width, height):
+        self.width, self.height = width, height
+        self.nbytes = width * height * C.sizeof(PixelStats)
+        self.ptr = lib().vp_malloc(self.nbytes)
+        if not self.ptr:
+            raise VolpathError(lib().vp_last_error().decode())
+        self.reset()
+
+    def reset(self):
+        _chk(lib().vp_memset(self.ptr, 0, self.nbytes))
+
+    def upload(self, arr):
+        arr = np.ascontiguousarray(arr, PIXEL_STATS_DTYPE)
+        assert arr.nbytes == self.nbytes
+        _chk(lib().vp_upload(self.ptr, _p(arr), self.nbytes))
+
+    def download(self):
+        """(height, width) structured array of PIXEL_STATS_DTYPE"""
+        out = np.empty((self.height, self.width), PIXEL_STATS_DTYPE)
+        _chk(lib().vp_download(_p(out), self.ptr, self.nbytes))
+        return out
+
+    def free(self):
+        if self.ptr:
+            lib().vp_free(self.ptr)
+            self.ptr = None
+
+
+def render_frames_stats(buf_ptr, stats_ptr, first, n, P):
+    """render_frames that also adds every sample's luminance to its pixel's record (vp_render_frames_stats): the same accumulator bits"""
+    _chk(lib().vp_render_frames_stats(buf_ptr, stats_ptr, first, n, C.byref(P)))
+
+
+def render_adaptive(buf_ptr, stats_ptr, first, max_frames, P, rel_tol, floor_y=1e-3, min_frames=16, round_frames=32):
+    """Rounds of round_frames frames on the pixels whose record is not frozen, until none is left or max_frames are used
+    (vp_render_adaptive); returns {"samples", "rounds", "active_left", "frames_used"}"""
+    a = Adaptive(rel_tol, floor_y, min_frames, round_frames)
+    r = AdaptiveResult()
+    _chk(lib().vp_render_adaptive(buf_ptr, stats_ptr, first, max_frames, C.byref(P), C.byref(a), C.byref(r)))
+    return r.as_dict()
+
+
+def scale_by_count(dst_ptr, src_ptr, stats_ptr, n, s):
+    """dst[i] = src[i] * (s / n_i) per channel, 0 where n_i == 0 (vp_scale_by_count); in place is allowed"""
+    _chk(lib().vp_scale_by_count(dst_ptr, src_ptr, stats_ptr, n, s))
+
+
+def stats_rel_error(stats_ptr, width, height, floor_y=1e-3):
+    """(height, width) float32 noise map: estimated standard error of the mean luminance over max(mean, floor_y) (vp_stats_rel_error)"""
+    n = width * height
+    d = lib().vp_malloc(n * 4)
+    if not d:
+        raise VolpathError(lib().vp_last_error().decode())
+    try:
+        _chk(lib().vp_stats_rel_error(d, stats_ptr, n, floor_y))
+        out = np.empty((height, width), np.float32)
+        _chk(lib().vp_download(_p(out), d, n * 4))
+    finally:
+        lib().vp_free(d)
+    return out
 
 
 def enable_counters(on=True):

@@ -235,6 +235,63 @@ int vp_tile_owner(unsigned tx, unsigned ty, int world);
  * render_kernel calls bit for bit.  Asynchronous. */
 int vp_render_frames(vp_float4* d_output, int first_frame, int n_frames, const Param* p);
 
+/* Per-pixel noise estimates and adaptive sampling.  THE DEFINITION:
+ * d_stats is a caller-owned device buffer of width * height records, zeroed by the caller (vp_memset), indexed like the accumulator.
+ * For every sample v (the float4 that is added to the accumulator) that a stats-carrying render adds to pixel i, record i receives
+ *   y = (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z      in binary32, no contraction
+ *   sum_y  += (double)y
+ *   sum_y2 += (double)y * (double)y
+ *   n      += 1
+ * Per pixel the samples are added in frame order, like the accumulator, so the sums are bit-defined.
+ *
+ * vp_render_frames_stats: a uniform render with statistics.  d_output ends up bit-identical to what vp_render_frames writes.  It
+ * never reads or sets `flags`: a record's FROZEN bit stays as the caller left it, and frozen pixels are sampled like any other.  It
+ * touches only the records of the pixels the context owns (vp_set_shard).
+ *
+ * vp_render_adaptive: a pixel is ACTIVE while its record's FROZEN bit is clear.  The frozen set is exactly what d_stats says: there
+ * is no hidden per-context state, so a second call continues a first one.  With B = round_frames, round k = 0, 1, ... covers frames
+ * [first_frame + k B, first_frame + min((k + 1) B, max_frames)).  Every owned pixel that is active at the start of a round receives
+ * all frames of the round, in frame order; a frozen pixel receives none.  After the round each pixel that was active in it is frozen
+ * iff n >= min_frames and the criterion holds, evaluated in binary64, no contraction, operations in the order written, with
+ * nd = (double)n, tol = (double)rel_tol, fl = (double)floor_y (the binary32 arguments widened):
+ *   lhs = nd * sum_y2 - sum_y * sum_y
+ *   m   = max(sum_y, nd * fl)                                 max(a, b) is a > b ? a : b
+ *   rhs = ((tol * tol) * (nd - 1.0)) * (m * m)
+ *   frozen  <=>  lhs <= rhs                                   false when either side is NaN
+ * i.e. "the estimated standard error of the mean luminance is at most rel_tol * max(mean, floor_y)", cleared of divisions and
+ * roots: multiplies, adds and a compare only, so a float64 restatement gives the same bits.  The call ends when no owned pixel is
+ * active or the frames are used up.  Freezing is permanent.  The set of samples a pixel receives depends on nothing but this
+ * definition: not on launch sizes, staging caps, pixel classes, shards or the pipeline.  `result` (may be NULL) reports the samples
+ * added by the call, the rounds it ran, the owned pixels still active at its end and the frames its longest-running pixel received
+ * from it (the frames of the rounds run).
+ *   Refused before the device is touched, with VP_E_ARG: NULL pointers (result excepted), max_frames <= 0 or first_frame < 0,
+ *   min_frames < 2, round_frames < 1, rel_tol or floor_y negative or NaN.  VP_E_STATE: work counters enabled (the context stays
+ *   usable).  VP_E_NOOPACITY as vp_render_frames would give for frame first_frame + max_frames - 1.
+ *   Built for: every estimator, stream, tracking and environment mode, both arithmetic modes, uchar and float volumes, shards
+ *   (each context its own pixels; reducing statistics across processes is the caller's business) and every sub-pixel factor.
+ *   Rounds are serial -- round k + 1 needs round k's decisions -- and run on the context's stream: the call stops look-ahead
+ *   batches, waits for pipelined launches and reads three counts back per round (it synchronises).  The cached pixel lists of the
+ *   view and vp_get_pixel_lists are never modified by it.
+ * What adaptive sampling is and is not: it stops sampling a pixel when the ESTIMATE of its error is small.  The stopping rule looks
+ * at the estimate it stops, so the result carries the small bias every such scheme has (a pixel whose first samples happen to agree
+ * is stopped early and keeps that mean); min_frames is the guard against a pixel freezing on a lucky start.  The image of an
+ * adaptive render is sum / n per pixel (vp_scale_by_count), not the sum times one factor.  The exact-parity product -- bit for bit the
+ * reference's estimator, every pixel the same frames -- stays vp_render_frames.
+ *
+ * Output stage (the reference's `scale` assumes one count for all pixels).  vp_scale_by_count: each channel of dst[i] is
+ * src[i].c * (scale / (float)n_i), the divide binary32 and correctly rounded; n_i == 0 gives 0; in place is allowed.
+ * vp_stats_rel_error, the noise map: dst[i] = sqrt(max(lhs, 0) / (nd * nd * (nd - 1))) / max(sum_y / nd, fl), computed in binary64
+ * and rounded to binary32; n < 2 gives 0.  A diagnostic image. */
+typedef struct { double sum_y, sum_y2; uint32_t n, flags; } vp_pixel_stats;   /* 24 bytes */
+#define VP_STATS_FROZEN 1u
+typedef struct { float rel_tol, floor_y; int min_frames, round_frames; } vp_adaptive;
+typedef struct { uint64_t samples; uint32_t rounds, active_left, frames_used; } vp_adaptive_result;
+int vp_render_frames_stats(vp_float4* d_output, vp_pixel_stats* d_stats, int first_frame, int n_frames, const Param* p);
+int vp_render_adaptive(vp_float4* d_output, vp_pixel_stats* d_stats, int first_frame, int max_frames, const Param* p,
+                       const vp_adaptive* a, vp_adaptive_result* result);
+int vp_scale_by_count(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, int size, float scale);
+int vp_stats_rel_error(float* dst, const vp_pixel_stats* d_stats, int size, float floor_y);
+
 typedef struct
 {
     uint64_t samples;
