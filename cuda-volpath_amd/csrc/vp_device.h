@@ -586,5 +586,69 @@ __device__ __forceinline__ float hyperion_s(int n_minus)
 {
     return fmaxf(0.0f, fminf(1.0f, (float)n_minus * 0.066666666666666666667f));
 }
+
+// The collision block's scene constants, one row per distinct value of hyperion_s (render_k's prologue fills the table in LDS, once
+// per workgroup).  hyperion_s(n) is +0 for every n <= 0 (the product is +0 or negative) and 1 for every n >= 15 (the constant is the
+// float above 1/15: the product is above 1 before it is rounded, and rounding is monotonic), so hyperion_s(n) ==
+// hyperion_s(clamp(n, 0, 15)) bit for bit: sixteen rows.  A row holds what the integrator computed per collision from s and Param
+// alone, by the same expressions in the same order (and in the arithmetic mode of the translation unit that fills it):
+enum : int
+{
+    CR_G    = 0,   // phase_g = (1 - s) g
+    CR_OMG2 = 1,   // 1 - g g          hg_eval's and hg_sample_local's numerator
+    CR_OPG2 = 2,   // 1 + g g
+    CR_2G   = 3,   // 2 g
+    CR_HOG  = 4,   // div_(0.5, g)     (infinite in the row with g = 0, where hg_sample_local does not read it)
+    CR_DENS = 5,   // the Hyperion-reduced density: cur_density of a segment, dp2 of a shadow ray
+    CR_STP  = 6,   // max_sig * CR_DENS: the global majorant's sigma_t' (the local estimators multiply by the segment's d_max themselves)
+    CR_INV  = 7,   // rcp_(CR_STP)
+    CR_WORDS = 8
+};
+#define VP_COLL_ROWS 16
+__device__ __forceinline__ void coll_row_fill(float* row, int n, float g0, float density, float max_sig, bool local)
+{
+    const float s = hyperion_s(n);
+    const float g = (1.0f - s) * g0;
+    row[CR_G]     = g;
+    row[CR_OMG2]  = 1.0f - g * g;
+    row[CR_OPG2]  = 1.0f + g * g;
+    row[CR_2G]    = 2.0f * g;
+    row[CR_HOG]   = div_(0.5f, g);
+    float dens;
+    if (local)
+    {
+        const float reduction = (1.0f - s) + s * (1.0f - g0);
+        dens                  = reduction * density;
+    }
+    else
+        dens = (1.0f - s) * density + s * density * (1.0f - g0);
+    const float stp = max_sig * dens;
+    row[CR_DENS]    = dens;
+    row[CR_STP]     = stp;
+    row[CR_INV]     = rcp_(stp);
+}
+// hg_sample_local and hg_eval with the g-only parts read from a row
+__device__ __forceinline__ f3 hg_sample_local_row(const float* row, float rnd0, float rnd1)
+{
+    const float g = row[CR_G];
+    float cos_theta;
+    if (__builtin_fabsf(g) > 1e-6f)
+    {
+        float s   = 2.0f * rnd0 - 1.0f;
+        float f   = div_(row[CR_OMG2], 1.0f + g * s);
+        cos_theta = row[CR_HOG] * (row[CR_OPG2] - f * f);
+        cos_theta = fmaxf(0.0f, fminf(1.0f, cos_theta));
+    }
+    else
+        cos_theta = 2.0f * rnd0 - 1.0f;
+    float sin_theta = sqrt_(1.0f - cos_theta * cos_theta);
+    float sp, cp;
+    sincos_turns_(rnd1, sp, cp);   // of (2 pi) rnd1
+    return f3{cp * sin_theta, sp * sin_theta, cos_theta};
+}
+__device__ __forceinline__ float hg_eval_row(const float* row, float cos_theta)
+{
+    return div_(row[CR_OMG2], (4.0f * kPi) * pow15f_(row[CR_OPG2] - row[CR_2G] * cos_theta));
+}
 VP_ARITH_END
 }  // namespace vp

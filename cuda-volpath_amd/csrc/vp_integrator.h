@@ -236,9 +236,21 @@ void render_k(SceneDev S, LaunchDev L)
     {
         const unsigned* src = (const unsigned*)__builtin_amdgcn_kernarg_segment_ptr();
         for (unsigned w = threadIdx.x; w < KARG_WDS_; w += (LDSB == 1 ? VP_BLOCK_LDS : VP_BLOCK)) kargs_lds_[w] = src[w];
-        __syncthreads();
     }
     constexpr bool LOCAL = EST != EST_GLOBAL;  // the two local-majorant estimators share the segment logic
+    // The collision block's scene constants (vp_device.h coll_row_fill): what a collision, the shadow ray it starts and the segment
+    // after it need from the scatter count and Param alone -- the Hyperion-reduced phase parameter with the g-only parts of the phase
+    // function, the reduced density, the global majorant and its reciprocal: two IEEE reciprocals, a division and ~25 other
+    // instructions per collision -- takes sixteen values per launch.  Thread n fills row n; a collision reads two rows.  Spectral
+    // tracking without MIS only; not the 16-bit LDS-table kernel, whose two workgroups per CU leave no byte of LDS over.
+    constexpr bool TAB = TRK == 0 && LDSB != 1 && !LIGHT && !MIS;
+    __shared__ __attribute__((aligned(16))) float coll_tab_[TAB ? VP_COLL_ROWS : 1][CR_WORDS];
+    if (TAB && threadIdx.x < VP_COLL_ROWS)
+        coll_row_fill(coll_tab_[threadIdx.x], (int)threadIdx.x, L.P.g, L.P.density, max3(f3{L.P.sigma_t[0], L.P.sigma_t[1], L.P.sigma_t[2]}), LOCAL);
+    __syncthreads();
+    auto coll_row = [&](int n) __attribute__((always_inline)) -> const float* {
+        return TAB ? coll_tab_[n < 0 ? 0 : (n > VP_COLL_ROWS - 1 ? VP_COLL_ROWS - 1 : n)] : nullptr;
+    };
     // Counter-based streams, passive environment: ONE event visit per collision.  The shadow ray draws from a sub-stream of its own,
     // so the two phase-function variates -- the path's next draws -- are the same whether they are taken before or after it: the
     // new direction is sampled in the collision block (and, global majorant, the box is intersected for it), the shadow ray is
@@ -274,7 +286,7 @@ void render_k(SceneDev S, LaunchDev L)
     constexpr int  CS_  = COLD ? VP_BLOCK : 1;
     // (the occupancy these kernels are budgeted for holds only while that many workgroups' cold state fits the CU's LDS --
     // a workgroup is one wave per SIMD, so waves per SIMD = workgroups per CU; gfx950: 160 KiB)
-    static_assert(!COLD || (VP_GLOBAL_MIN_WAVES > VP_LOCAL_MIN_WAVES ? VP_GLOBAL_MIN_WAVES : VP_LOCAL_MIN_WAVES) * (14 * VP_BLOCK * 4 + KARG_WDS_ * 4 + (LDSB == 2 ? VP_LDS_BOUND_ENTRIES / 4 : 0)) <= VP_LDS_BYTES_PER_CU,
+    static_assert(!COLD || (LOCAL ? VP_LOCAL_MIN_WAVES : VP_GLOBAL_MIN_WAVES) * (14 * VP_BLOCK * 4 + KARG_WDS_ * 4 + VP_COLL_ROWS * CR_WORDS * 4 + (LDSB == 2 ? VP_LDS_BOUND_ENTRIES / 4 : 0)) <= VP_LDS_BYTES_PER_CU,
                   "cold per-path state: more workgroups per CU than the LDS holds -- lower VP_*_MIN_WAVES for this ARCH");
     __shared__ float cold_[COLD ? 14 : 1][CS_];
     float* const cold_p = &cold_[0][COLD ? threadIdx.x : 0];
@@ -425,7 +437,8 @@ void render_k(SceneDev S, LaunchDev L)
         // Local-majorant estimators: the Hyperion-reduced phase function and density of a segment (kernel.cu:2038-2046)
         // depend on the scatter count only, which restarts do not change: set where the count changes, not per restart.
         auto segment_medium = [&]() __attribute__((always_inline)) {
-            if (LOCAL)
+            if (LOCAL && TAB) cur_density = coll_row(nsc - 5)[CR_DENS];   // (the phase parameter: read from the row at the collision)
+            else if (LOCAL)
             {
                 float s         = hyperion_s(nsc - 5);
                 phase_g         = (1.0f - s) * P.g;
@@ -458,9 +471,19 @@ void render_k(SceneDev S, LaunchDev L)
             t_empty = 0.0f;  // the certificate is for the unscattered camera ray only
             if (LOCAL) nsc = nsc + 1;  // num_scatters += !through, kernel.cu:2146
             // "to match passive result": post-increment count (DECOMP :2168) / i-4 (GLOBAL :1465)
-            float s2 = hyperion_s((LOCAL) ? (nsc - 5) : (nsc - 4));
+            // TAB: row n2 is the shadow ray's medium and the next segment's (the global majorant's depth index is one higher then,
+            // the local estimators' count is the one just incremented); row n2 - 1 is the one this segment's phase_g was set from
+            const int          n2   = LOCAL ? (nsc - 5) : (nsc - 4);
+            const float* const row2 = coll_row(n2);
+            const float* const rowp = coll_row(n2 - 1);
+            float s2 = hyperion_s(n2);
             float dp2, stp2;
-            if (TRK)
+            if (TAB)
+            {
+                dp2  = row2[CR_DENS];
+                stp2 = LOCAL ? row2[CR_STP] * d_max : row2[CR_STP];  // quirk Q4: the local majorant for the whole shadow ray
+            }
+            else if (TRK)
             {
                 thr  = thr * f3{P.albedo[0], P.albedo[1], P.albedo[2]};  // kernel.cu:2157-2159
                 stp2 = LOCAL ? ((1.0f - s2) + s2 * (1.0f - P.g)) * sig_base : (1.0f - s2) * sig_base + s2 * sig_base * (1.0f - P.g);
@@ -477,7 +500,7 @@ void render_k(SceneDev S, LaunchDev L)
                 dp2  = (1.0f - s2) * density + s2 * density * (1.0f - P.g);
                 stp2 = max_sig * dp2;
             }
-            ph = hg_eval(phase_g, dot(rd, sun_dir));
+            ph = TAB ? hg_eval_row(rowp, dot(rd, sun_dir)) : hg_eval(phase_g, dot(rd, sun_dir));
             pd = rd;
             if (EARLY)
             {
@@ -485,7 +508,7 @@ void render_k(SceneDev S, LaunchDev L)
                 Frame fr(rd);
                 float r0 = rng.next_a();
                 float r1 = rng.next_b();
-                pd       = normalize(fr.to_world(hg_sample_local(phase_g, r0, r1)));
+                pd       = normalize(fr.to_world(TAB ? hg_sample_local_row(rowp, r0, r1) : hg_sample_local(phase_g, r0, r1)));
                 if (LOCAL) { const f3 pdv = pd; inv_rd = f3{rcp_(pdv.x), rcp_(pdv.y), rcp_(pdv.z)}; }
             }
             if (MIS)
@@ -523,7 +546,7 @@ void render_k(SceneDev S, LaunchDev L)
             }
             else
             {
-                start_shadow(sun_dir * 1e10f, rcp_(stp2), dp2, 0u);
+                start_shadow(sun_dir * 1e10f, (TAB && !LOCAL) ? row2[CR_INV] : rcp_(stp2), dp2, 0u);
                 if (EARLY && st == EV_NEE) finish_light();   // the ray misses the box
                 if (EARLY && EST == EST_GLOBAL && st == ST_SHADOW)
                 {
@@ -534,6 +557,9 @@ void render_k(SceneDev S, LaunchDev L)
                     bool  hit2 = intersect_box(ro, pd, S, tn2, tf2);
                     t_empty    = tn2 < 0.0f ? 0.0f : tn2;
                     t_far      = hit2 ? tf2 : -1.0f;
+                    // TAB: ... and its medium, which is the shadow ray's (row n2: cur_density and inv_sigma are set by start_shadow);
+                    // the two values below are read by primary steps only, so light_done() has nothing left to compute
+                    if (TAB) { sigma_t_prime = row2[CR_STP]; inv_sigma_t = row2[CR_INV]; }
                 }
             }
         }
@@ -611,7 +637,8 @@ void render_k(SceneDev S, LaunchDev L)
             Frame fr(pd);
             float r0 = rng.next_a();
             float r1 = rng.next_b();
-            rd       = normalize(fr.to_world(hg_sample_local(phase_g, r0, r1)));
+            // (TAB: the row phase_g was set from -- the count has not moved since the collision)
+            rd       = normalize(fr.to_world(TAB ? hg_sample_local_row(coll_row((LOCAL ? (nsc - 5) : (nsc - 4)) - 1), r0, r1) : hg_sample_local(phase_g, r0, r1)));
             if (LOCAL) inv_rd = f3{rcp_(rd.x), rcp_(rd.y), rcp_(rd.z)};
             next_segment();
         }
@@ -917,8 +944,14 @@ void render_k(SceneDev S, LaunchDev L)
                     t_end         = tf;
                     dist          = (APPR && fresh) ? dist : t_near;
                     float s       = hyperion_s(nsc - 5);
-                    phase_g       = (1.0f - s) * P.g;
-                    if (TRK)
+                    if (!TAB) phase_g = (1.0f - s) * P.g;
+                    if (TAB)
+                    {
+                        const float* const row = coll_row(nsc - 5);
+                        cur_density   = row[CR_DENS];
+                        sigma_t_prime = row[CR_STP];
+                    }
+                    else if (TRK)
                     {
                         sigma_t_prime = (1.0f - s) * sig_base + s * sig_base * (1.0f - P.g);  // kernel.cu:1363
                         cur_density   = sigma_t_prime;  // vol_sigma_t(pos, sigma_t_prime), kernel.cu:1436
@@ -928,7 +961,7 @@ void render_k(SceneDev S, LaunchDev L)
                         cur_density   = (1.0f - s) * density + s * density * (1.0f - P.g);
                         sigma_t_prime = max_sig * cur_density;
                     }
-                    inv_sigma     = rcp_(sigma_t_prime);
+                    inv_sigma     = TAB ? coll_row(nsc - 5)[CR_INV] : rcp_(sigma_t_prime);
                     inv_sigma_t   = inv_sigma;
                     st            = ST_TRACK;
                 }
@@ -1053,8 +1086,13 @@ ends_done:
                     dist          = t_empty;
                     t_empty       = 0.0f;
                     float s       = hyperion_s(nsc - 5);
-                    phase_g       = (1.0f - s) * P.g;
-                    if (TRK)
+                    if (!TAB) phase_g = (1.0f - s) * P.g;
+                    if (TAB)
+                    {
+                        // the medium of depth index nsc is the shadow ray's (cur_density, inv_sigma: still in place); sigma_t_prime
+                        // and inv_sigma_t were set beside it in the collision block
+                    }
+                    else if (TRK)
                     {
                         sigma_t_prime = (1.0f - s) * sig_base + s * sig_base * (1.0f - P.g);
                         cur_density   = sigma_t_prime;
@@ -1064,8 +1102,11 @@ ends_done:
                         cur_density   = (1.0f - s) * density + s * density * (1.0f - P.g);
                         sigma_t_prime = max_sig * cur_density;
                     }
-                    inv_sigma     = rcp_(sigma_t_prime);
-                    inv_sigma_t   = inv_sigma;
+                    if (!TAB)
+                    {
+                        inv_sigma   = rcp_(sigma_t_prime);
+                        inv_sigma_t = inv_sigma;
+                    }
                     st            = ST_TRACK;
                 }
             }
@@ -1075,10 +1116,14 @@ ends_done:
                 dist = -1.0f;
                 if (EST == EST_BOUNDED) seg++;
                 if ((EST == EST_BOUNDED ? seg : nsc) >= 800) st = EV_WRITE;
-                float s         = hyperion_s(nsc - 5);
-                phase_g         = (1.0f - s) * P.g;
-                float reduction = (1.0f - s) + s * (1.0f - P.g);
-                cur_density     = TRK ? reduction * sig_base : reduction * density;
+                if (TAB) cur_density = coll_row(nsc - 5)[CR_DENS];
+                else
+                {
+                    float s         = hyperion_s(nsc - 5);
+                    phase_g         = (1.0f - s) * P.g;
+                    float reduction = (1.0f - s) + s * (1.0f - P.g);
+                    cur_density     = TRK ? reduction * sig_base : reduction * density;
+                }
             }
         };
         auto tracking_step = [&]() __attribute__((always_inline)) {
