@@ -27,22 +27,10 @@ static int compact_active(const Param* p, const vp_pixel_stats* d_stats, unsigne
 static int reserve_active(size_t n)
 {
     const size_t words = (size_t)3 * compact_blocks((unsigned)n) + 4;
-    if (n <= G.act_cap && words <= G.act_scratch_words) return VP_OK;
+    if (n * sizeof(unsigned) <= G.d_act.bytes && words * sizeof(unsigned) <= G.d_act_scratch.bytes) return VP_OK;
     HIPCHK(hipStreamSynchronize(G.stream));
-    if (n > G.act_cap)
-    {
-        if (G.d_act) HIPCHK(hipFree(G.d_act));
-        G.d_act = nullptr; G.act_cap = 0;
-        HIPCHK(hipMalloc((void**)&G.d_act, n * sizeof(unsigned)));
-        G.act_cap = n;
-    }
-    if (words > G.act_scratch_words)
-    {
-        if (G.d_act_scratch) HIPCHK(hipFree(G.d_act_scratch));
-        G.d_act_scratch = nullptr; G.act_scratch_words = 0;
-        HIPCHK(hipMalloc((void**)&G.d_act_scratch, words * sizeof(unsigned)));
-        G.act_scratch_words = words;
-    }
+    HIPCHK(G.d_act.grow(n * sizeof(unsigned)));
+    HIPCHK(G.d_act_scratch.grow(words * sizeof(unsigned)));
     return VP_OK;
 }
 }  // namespace vph
@@ -69,12 +57,7 @@ int vp_render_adaptive(vp_float4* d_output, vp_pixel_stats* d_stats, int first_f
     int rc = ensure_device();
     if (rc) return rc;
     if (G.count) return fail(VP_E_STATE, "vp_render_adaptive is not built for work counters");
-    if (!G.have_volume) return fail(VP_E_STATE, "render before init_cuda");
-    if (!G.have_env) return fail(VP_E_STATE, "render before init_envmap");
-    if (!G.have_sun) return fail(VP_E_STATE, "render before set_sun");
-    if (!G.have_cam) return fail(VP_E_STATE, "render before copy_inv_view_matrix");
-    if (G.est == VP_EST_DECOMP && (long long)first_frame + max_frames - 1 > 10 && !G.S.opacity)
-        return fail(VP_E_NOOPACITY, "frames beyond 10 need precompute_opacity (kernel.cu:2183, host.cpp:336-343)");
+    if ((rc = check_render(CHK_STATE | CHK_OPACITY, p, (long long)first_frame + max_frames - 1))) return rc;
     // rounds are serial and run on the caller's stream: look-ahead batches stop, pipelined launches are waited for
     if ((rc = la_quiesce())) return rc;
     if ((rc = vp_prepare(p))) return rc;   // the cached lists of p: what is compacted

@@ -558,7 +558,6 @@ int vp_ctx_destroy(vp_ctx* ctx)
         free_envmap();
         for (auto& sl : D.la)
         {
-            if (sl.buf) (void)hipFree(sl.buf);
             if (sl.done) (void)hipEventDestroy(sl.done);
             if (sl.stream) (void)hipStreamDestroy(sl.stream);
         }
@@ -566,35 +565,19 @@ int vp_ctx_destroy(vp_ctx* ctx)
         for (auto& ev : D.class_events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
         for (auto e : D.event_pool) (void)hipEventDestroy(e);
         (void)pipe_quiesce();
-        for (int s = 0; s < 2; s++)
+        for (hipStream_t st : D.pipe_stream) if (st) (void)hipStreamDestroy(st);
+        for (hipEvent_t e : {D.pipe_done[0], D.pipe_done[1], D.pipe_free[0], D.pipe_free[1], D.pipe_gate[0], D.pipe_gate[1], D.pipe_fence_ev, D.last_end,
+                             D.class_last_end[0], D.class_last_end[1], D.class_last_end[2]})
+            if (e) (void)hipEventDestroy(e);
+        D.d_crawl.release(); D.d_seg.release(); D.d_sub_cls.release(); D.d_tiles.release(); D.d_act.release(); D.d_act_scratch.release();
+        for (void* q : {(void*)D.d_thr, (void*)D.d_sunclip, (void*)D.d_bound_codes, (void*)D.d_light_flag, (void*)D.d_tile_rows, (void*)D.d_tile_scratch})
+            if (q) (void)hipFree(q);
+        for (RenderTarget& t : D.target)
         {
-            if (D.pipe_stream[s]) (void)hipStreamDestroy(D.pipe_stream[s]);
-            if (D.pipe_done[s]) (void)hipEventDestroy(D.pipe_done[s]);
-            if (D.pipe_free[s]) (void)hipEventDestroy(D.pipe_free[s]);
-            if (D.pipe_gate[s]) (void)hipEventDestroy(D.pipe_gate[s]);
-        }
-        if (D.pipe_fence_ev) (void)hipEventDestroy(D.pipe_fence_ev);
-        if (D.last_end) (void)hipEventDestroy(D.last_end);
-        for (auto e : D.class_last_end) if (e) (void)hipEventDestroy(e);
-        if (D.d_stage) (void)hipFree(D.d_stage);
-        if (D.d_stage2) (void)hipFree(D.d_stage2);
-        if (D.d_crawl) (void)hipFree(D.d_crawl);
-        if (D.d_thr) (void)hipFree(D.d_thr);
-        if (D.d_sunclip) (void)hipFree(D.d_sunclip);
-        if (D.d_seg) (void)hipFree(D.d_seg);
-        if (D.d_sub_cls) (void)hipFree(D.d_sub_cls);
-        if (D.d_bound_codes) (void)hipFree(D.d_bound_codes);
-        if (D.d_light_flag) (void)hipFree(D.d_light_flag);
-        if (D.d_tiles) (void)hipFree(D.d_tiles);
-        if (D.d_tile_rows) (void)hipFree(D.d_tile_rows);
-        if (D.d_tile_scratch) (void)hipFree(D.d_tile_scratch);
-        if (D.d_act) (void)hipFree(D.d_act);
-        if (D.d_act_scratch) (void)hipFree(D.d_act_scratch);
-        for (int i = 0; i < kTargets; i++)
-        {
-            if (D.aux_stream[i]) { (void)hipStreamSynchronize(D.aux_stream[i]); (void)hipStreamDestroy(D.aux_stream[i]); }
-            if (D.d_appr_aux[i]) (void)hipFree(D.d_appr_aux[i]);
-            for (int q = 0; q < 2; q++) if (D.aux_ev[i][q]) (void)hipEventDestroy(D.aux_ev[i][q]);
+            if (t.aux_stream) { (void)hipStreamSynchronize(t.aux_stream); (void)hipStreamDestroy(t.aux_stream); }
+            t.stage.release();
+            t.handover.release();
+            for (hipEvent_t e : t.aux_ev) if (e) (void)hipEventDestroy(e);
         }
         if (D.d_queue) (void)hipFree(D.d_queue);
         if (D.d_counters) (void)hipFree(D.d_counters);

@@ -103,13 +103,13 @@ int la_render_slot(int si, vp_float4* d_out, int first, int n, const Param* p, c
     HIPCHK(hipEventRecord(ev, G.stream));
     HIPCHK(hipStreamWaitEvent(s.stream, ev, 0));
     put_event(ev);
-    const Target t = {s.stream, &s.buf, &s.bytes, G.d_queue + 2 * kQueueWords * (si + 1), si + 1};
+    const Target t = {&G.target[si + 1], s.stream};
     G.la_launched++;
-    G.batch_seq[si + 1]++;   // (numbers only grow: a cancel of an earlier batch of this slot can never reach this one)
+    G.target[si + 1].batch_seq++;   // (numbers only grow: a cancel of an earlier batch of this slot can never reach this one)
     int rc = do_render(d_out, first, n, p, true, &t);
     if (rc) return rc;
     HIPCHK(hipEventRecord(s.done, s.stream));
-    s.launched_seq = G.batch_seq[si + 1];
+    s.launched_seq = G.target[si + 1].batch_seq;
     s.const_from = G.last_const_from;
     s.valid = true; s.first = first; s.count = n; s.key = key;
     return VP_OK;
@@ -146,7 +146,7 @@ int serve_frame(vp_float4* d_out, int frame, const Param* p)
             // and most of it is thrown away when the camera moves on after a few hundred frames
             int want = std::min(s.count * 2, G.la_max);
             while (want > G.la_floor && want > (next - G.la_run_first) / G.la_div) want >>= 1;
-            int n = la_limit(next, want, per_frame, o.bytes);
+            int n = la_limit(next, want, per_frame, G.target[(si ^ 1) + 1].stage.bytes);
             if (n > 1 && la_render_slot(si ^ 1, d_out, next, n, p, key)) G.la[si ^ 1].valid = false;  // best effort
             // (that launch may have rebuilt a table and quiesced -- stopping THIS batch, whose frames are then not to be
             // served: today every table key equals the running batch's, but nothing else enforces it)
@@ -164,8 +164,8 @@ int serve_frame(vp_float4* d_out, int frame, const Param* p)
         memcpy(&L.P, p, sizeof(Param));
         L.pixels = G.d_tiles; L.nslots = (unsigned)per_frame; L.stage_stride = (unsigned)per_frame;
         L.out = (float4*)d_out;
-        L.stage = s.buf + (size_t)(frame - s.first) * per_frame;
-        L.const_from = s.const_from; L.stage_const = s.buf;
+        L.stage = G.target[si + 1].stage + (size_t)(frame - s.first) * per_frame;
+        L.const_from = s.const_from; L.stage_const = G.target[si + 1].stage;
         L.nframes = 1;
         launch_reduce(L, G.stream);
         HIPCHK(hipGetLastError());
@@ -181,7 +181,7 @@ int serve_frame(vp_float4* d_out, int frame, const Param* p)
     // and every batch has its successor, twice its size, queued behind it)
     int n = (same && frame == G.la_last + 1) ? std::min(std::max(G.la_prev_n * 2, G.la_ramp_from), std::min(G.la_max, G.la_floor)) : 1;
     if (n == 1) G.la_run_first = frame;
-    if (n > 1) n = std::max(la_limit(frame, n, per_frame, G.la[0].bytes), 1);
+    if (n > 1) n = std::max(la_limit(frame, n, per_frame, G.target[1].stage.bytes), 1);
     G.la_key = key; G.la_last = frame; G.la_prev_n = n;
     // The habit decays: a speculative batch none of whose frames was asked for -- an interactive drag: every call is frame 0
     // of a new camera -- cost the first frame after the move 2 ms and returned nothing; no more of them until a staged frame is served again
@@ -196,7 +196,7 @@ int serve_frame(vp_float4* d_out, int frame, const Param* p)
         // both are bound by their deepest paths, not by the chip.
         if (G.la_habit && G.la_speculate && per_frame && d_out && n == 1)
         {
-            const int m = la_limit(frame + 1, std::min(G.la_ramp_from, std::min(G.la_max, G.la_floor)), per_frame, G.la[0].bytes);
+            const int m = la_limit(frame + 1, std::min(G.la_ramp_from, std::min(G.la_max, G.la_floor)), per_frame, G.target[1].stage.bytes);
             if (m > 1)
             {
                 if (la_render_slot(0, d_out, frame + 1, m, p, key)) G.la[0].valid = false;   // best effort

@@ -1,4 +1,7 @@
-// vp_render.cpp -- do_render: one staged launch of the integrator (approach kernel, render_k per pixel class, per-pixel constants, the add-kernel); counters, timing, vp_prepare / vp_reserve_frames
+// vp_render.cpp -- the launch path.  do_render: one render call as a sequence of stages -- the precondition check, the tables the launches
+// read, the launch plan (lists, staging, approach walk, pipeline slot), then per launch the staging reserve, the pipeline waits, one
+// function per pixel class (approach kernel and render_k, the light kernel or its constants, the box-missing constants) and the
+// add-kernel; the render targets' buffers; counters, timing, vp_prepare / vp_reserve_frames
 #include "vp_state.h"
 
 namespace vph __attribute__((visibility("hidden")))
@@ -75,38 +78,60 @@ int pipe_quiesce()
     G.pipe_busy = false;
     return VP_OK;
 }
+// ---- render targets (vp_state.h RenderTarget): queue words by index, and the two buffers a launch needs on one
+static int       target_index(const RenderTarget* rt) { return (int)(rt - G.target); }
+static unsigned* target_queue(const RenderTarget* rt) { return G.d_queue + 2 * kQueueWords * (size_t)target_index(rt); }   // two tile classes each
+static bool      is_lookahead(const RenderTarget* rt) { return rt == &G.target[1] || rt == &G.target[2]; }
+static const int kPipeTarget[2] = {0, kTargets - 1};   // the render targets of the two pipeline slots
+// nothing may read a buffer while it is replaced: the target's stream and, where its buffers are a pipeline slot's, the pipelined launches
+static int drain_target(const Target& T)
+{
+    if (int rc = is_lookahead(T.rt) ? VP_OK : pipe_quiesce()) return rc;
+    HIPCHK(hipStreamSynchronize(T.stream));
+    return VP_OK;
+}
+// The staging buffer of T for a launch of `exact` bytes: grown to `want` >= exact or, failing that, to `exact`.  drained: the caller
+// has waited for the readers itself.  An allocation that fails is no error here: the buffer is then smaller than `exact`, and what
+// follows is the caller's (a smaller launch, no pipeline slot, VP_E_NOMEM).
+static int reserve_stage(const Target& T, size_t exact, size_t want, bool drained = false)
+{
+    if (exact <= T.rt->stage.bytes) return VP_OK;
+    if (!drained)
+    {
+        if (int rc = drain_target(T)) return rc;
+        HIPCHK(hipStreamSynchronize(G.stream));  // add-kernels of earlier frames may still read the old buffer
+    }
+    if (T.rt->stage.grow(want) != hipSuccess && want > exact) (void)T.rt->stage.grow(exact);
+    return VP_OK;
+}
+// The hand-over buffer likewise.  Needed is `exact`, allocated is `want`: a look-ahead slot asks for its largest batch at once (a slot
+// that grew with every doubling of the ramp would synchronise its stream -- and the batch running beside it -- at every step), but a
+// slot that already holds THIS batch is left alone.  Without the buffer there is no walk ahead of the integrator: same bits.
+static int reserve_handover(const Target& T, size_t exact, size_t want, bool drained = false)
+{
+    if (exact <= T.rt->handover.bytes) return VP_OK;
+    if (int rc = drained ? VP_OK : drain_target(T)) return rc;
+    (void)T.rt->handover.grow(want);
+    return VP_OK;
+}
+// ---- the pipeline of vp_render_frames calls (vp_state.h)
 // Sizes pipeline slot s for a call of nframes frames in ONE launch: its staging buffer and, where the decomposition estimator's walk
 // hands over, its approach buffer, each capped as the single target's (stage_frames_cap: VP_STAGE_MB, a quarter of the free memory).
 // false: the slot cannot hold the call (the caller's stream then renders it as before, same bits).
 static bool pipe_reserve(int s, size_t per_frame, int nframes, bool aux)
 {
-    float4** stage = s ? &G.d_stage2 : &G.d_stage;
-    size_t*  bytes = s ? &G.stage2_bytes : &G.stage_bytes;
-    const int ti = s ? 3 : 0;
+    const Target T = {&G.target[kPipeTarget[s]], G.stream};
     const size_t need  = per_frame * (size_t)nframes * sizeof(float4);
     const size_t need4 = aux ? per_frame * (size_t)nframes * sizeof(uint2) : 0;
-    if (need <= *bytes && need4 <= G.appr_aux_bytes[ti]) return true;
-    if (need > *bytes && stage_frames_cap(per_frame, *bytes) < (size_t)nframes) return false;
+    if (need <= T.rt->stage.bytes && need4 <= T.rt->handover.bytes) return true;
+    if (need > T.rt->stage.bytes && stage_frames_cap(per_frame, T.rt->stage.bytes) < (size_t)nframes) return false;
     // (growth: nothing may still read the old buffers -- the slots' launches, the reduces and one-frame launches on the caller's stream)
     if (pipe_quiesce() || hipStreamSynchronize(G.stream) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (need > *bytes)
-    {
-        if (*stage) (void)hipFree(*stage);
-        *stage = nullptr; *bytes = 0;
-        if (hipMalloc((void**)stage, need) != hipSuccess) { (void)hipGetLastError(); *stage = nullptr; return false; }
-        *bytes = need;
-    }
-    if (need4 > G.appr_aux_bytes[ti])
-    {
-        if (G.d_appr_aux[ti]) (void)hipFree(G.d_appr_aux[ti]);
-        G.d_appr_aux[ti] = nullptr; G.appr_aux_bytes[ti] = 0;
-        if (hipMalloc((void**)&G.d_appr_aux[ti], need4) != hipSuccess) { (void)hipGetLastError(); G.d_appr_aux[ti] = nullptr; return false; }
-        G.appr_aux_bytes[ti] = need4;
-    }
-    return true;
+    (void)reserve_stage(T, need, need, true);
+    if (need > T.rt->stage.bytes) return false;
+    (void)reserve_handover(T, need4, need4, true);
+    return need4 <= T.rt->handover.bytes;
 }
-// The target of a pipelined call: the next slot's stream (created on first use, lowest priority: create_internal_stream), staging,
-// approach buffer and queue words.  false: today's single target on the caller's stream.
 static bool pipe_streams()
 {
     for (int s = 0; s < 2; s++)
@@ -117,54 +142,445 @@ static bool pipe_streams()
     }
     return true;
 }
+// The target of a pipelined call: the next slot's stream (created on first use, lowest priority: create_internal_stream) and render
+// target.  false: today's single target on the caller's stream.
 static bool pipe_target(size_t per_frame, int nframes, bool aux, Target* T)
 {
-    const int s = G.pipe_next, ti = s ? 3 : 0;
+    const int s = G.pipe_next;
     if (!pipe_streams() || !pipe_reserve(s, per_frame, nframes, aux)) return false;
-    *T = {G.pipe_stream[s], s ? &G.d_stage2 : &G.d_stage, s ? &G.stage2_bytes : &G.stage_bytes, G.d_queue + 2 * kQueueWords * ti, ti};
+    *T = {&G.target[kPipeTarget[s]], G.pipe_stream[s]};
     return true;
 }
-// the camera rays' walk ahead of the integrator is built for this estimator and volume (do_render; counting launches aside)
-static bool approach_possible(const float4* crawl, unsigned n_general)
+// Before a pipelined launch: the slot's stream waits for the reduce that last read its staging (two calls back), for the previous
+// call's walk (pipe_gate) and, after a change, for the caller's stream
+static int pipe_await_slot_free(int ps, hipStream_t st)
+{
+    if (G.pipe_free_set[ps]) HIPCHK(hipStreamWaitEvent(st, G.pipe_free[ps], 0));
+    if (G.pipe_gate_set[ps ^ 1]) HIPCHK(hipStreamWaitEvent(st, G.pipe_gate[ps ^ 1], 0));
+    G.pipe_gate_set[ps] = false;
+    if (G.pipe_fence)
+    {
+        HIPCHK(hipEventRecord(G.pipe_fence_ev, G.stream));
+        HIPCHK(hipStreamWaitEvent(st, G.pipe_fence_ev, 0));
+        G.pipe_fence = false;
+    }
+    G.pipe_busy = true;
+    return VP_OK;
+}
+// Before its reduce: the caller-visible write stays on the caller's stream, behind the slot's launch
+static int pipe_await_launch(int ps, hipStream_t st)
+{
+    HIPCHK(hipEventRecord(G.pipe_done[ps], st));
+    HIPCHK(hipStreamWaitEvent(G.stream, G.pipe_done[ps], 0));
+    return VP_OK;
+}
+// ---- preconditions
+int check_render(unsigned what, const Param* p, long long last_frame)
+{
+    if (what & CHK_STATE)
+    {
+        if (!G.have_volume) return fail(VP_E_STATE, "render before init_cuda");
+        if (!G.have_env) return fail(VP_E_STATE, "render before init_envmap");
+        if (!G.have_sun) return fail(VP_E_STATE, "render before set_sun");
+        if (!G.have_cam) return fail(VP_E_STATE, "render before copy_inv_view_matrix");
+    }
+    if ((what & CHK_IMAGE) && (p->width == 0 || p->height == 0 || p->width > 65535 || p->height > 65535))
+        return fail(VP_E_ARG, (what & CHK_IMAGE_NOTE) ? "image %ux%u out of range (sampler.h packs x<<16|y)" : "image %ux%u out of range", p->width, p->height);
+    if (what & CHK_MODES)
+    {
+        if (G.trk && G.env_mis) return fail(VP_E_STATE, "scalar tracking builds exist with passive environment lighting only");
+        if (G.trk && G.count) return fail(VP_E_STATE, "work counters are not built for the scalar tracking kernels");
+        if (G.rng == VP_RNG_PHILOX7 && (G.trk || G.env_mis))
+            return fail(VP_E_STATE, "VP_RNG_PHILOX7 is built for spectral tracking with passive environment lighting only");
+        if (G.arith == VP_ARITH_FAST)
+        {
+            // the fast arithmetic is built for the counter-based streams' shipped configuration only (vp_kernels_fast.hip)
+            if (G.rng == VP_RNG_SAMPLERH) return fail(VP_E_STATE, "VP_ARITH_FAST is not built for VP_RNG_SAMPLERH (the parity mode is exact by definition)");
+            if (G.est == VP_EST_BOUNDED) return fail(VP_E_STATE, "VP_ARITH_FAST is not built for VP_EST_BOUNDED");
+            if (G.env_mis) return fail(VP_E_STATE, "VP_ARITH_FAST is built for passive environment lighting only");
+            if (G.trk) return fail(VP_E_STATE, "VP_ARITH_FAST is built for spectral tracking only");
+            if (G.count) return fail(VP_E_STATE, "work counters are not built for VP_ARITH_FAST");
+        }
+        if (int rc = subpixel_check(p)) return rc;
+    }
+    if ((what & CHK_OPACITY) && G.est == VP_EST_DECOMP && last_frame > 10 && !G.S.opacity)
+        return fail(VP_E_NOOPACITY, "frames beyond 10 need precompute_opacity (kernel.cu:2183, host.cpp:336-343)");
+    return VP_OK;
+}
+// the camera rays' walk ahead of the integrator is built for this estimator and configuration (whatever the lists: vp_reserve_frames)
+static bool approach_built()
 {
     const bool dense_volume = G.marked_fraction > G.dense_fraction;   // (vp_state.h: little empty space for the walk to cross)
     // (a sub-pixel factor: the integrator walks the camera ray itself -- the approach kernels and the segment table are statements about
     // ONE camera ray per pixel, and with S^2 of them a wave of one pixel x 64 frames no longer shares a ray: DESIGN.md section 2.2)
-    return G.use_approach && !G.sub_shift && (G.est == VP_EST_GLOBAL || (G.est == VP_EST_DECOMP && G.use_approach_local && !dense_volume)) && !G.trk && !G.env_mis &&
-           crawl && n_general;
+    return G.use_approach && !G.sub_shift && (G.est == VP_EST_GLOBAL || (G.est == VP_EST_DECOMP && G.use_approach_local && !dense_volume)) && !G.trk && !G.env_mis;
+}
+// ... and has a table and pixels to walk for (do_render; counting launches aside)
+static bool approach_possible(const float4* crawl, unsigned n_general) { return approach_built() && crawl && n_general; }
+// ---- the plan of a call: what every launch of it has in common
+struct LaunchPlan
+{
+    Target     T;                 // where its launches run: the caller's stream, the look-ahead slot handed in, or a pipeline slot
+    bool       lookahead;         // ... a look-ahead batch (cancellable, never one of the caller's timed launches)
+    bool       stage_only;        // ... which is staged whole and not reduced
+    const StatsDev* stats;        // the reduce also takes the statistics
+    PixelLists PL;                // the lists in use: the context's cached ones, or the caller's
+    size_t     per_frame;         // ... and their pixels = samples per frame
+    bool       staged;            // samples go through the staging buffer and a reduce (false: render_k accumulates one frame directly)
+    bool       light_const;       // the light class is written by miss_fill_k
+    bool       approach, approach_thr, appr_aux_needed;   // a walk ahead of the integrator; with the throughput table; with a hand-over buffer
+    bool       piped; int slot;   // on pipeline slot `slot`
+    size_t     max_f;             // frames per launch
+    bool both() const { return PL.n_light && PL.n_general && !light_const; }   // the general and the light KERNEL have work
+    // frames to size a buffer for when a launch of f needs it: a look-ahead slot's for the largest batch at once (reserve_handover)
+    size_t sized_frames(int f) const { return std::min<size_t>(stage_only ? std::max<size_t>((size_t)f, (size_t)std::max(G.la_max, 1)) : (size_t)f, max_f); }
+};
+// The tables the launches read, into L, and what they decide, into A: in this order (some synchronise or quiesce).  A.per_frame == 0: nothing to render
+static int prepare_tables(const Param* p, const Shard& sh, int nframes, const PixelLists* lists, LaunchDev& L, LaunchPlan& A)
+{
+    int rc = VP_OK;
+    // (a sub-pixel factor: the per-pixel table of the image the samples are computed on; lists, staging and output stay this image's)
+    L.sub_shift = (unsigned)G.sub_shift;
+    const Param fine = subpixel_param(p);
+    if ((rc = ensure_crawl_table(&fine, &L.crawl))) return rc;
+    if ((rc = ensure_pixel_lists(p, L.crawl, sh))) return rc;
+    // the lists this call launches on: the context's cached ones, or the caller's (vp_adaptive.cpp: the active pixels of a round --
+    // a class-ordered subset of the cached lists; staging rows, sample queues and the reduce are then that subset's)
+    const PixelLists& PL = A.PL = lists ? *lists : PixelLists{G.d_tiles, G.n_general, G.n_light, G.n_miss};
+    A.per_frame = (size_t)PL.n_general + PL.n_light + PL.n_miss;
+    if (A.per_frame == 0) return VP_OK;
+    if ((rc = ensure_sun_clip(&L.sun_clip, &L.clip_ds))) return rc;
+    L.count_clips = getenv("VP_DEBUG_COUNT_CLIPS") ? 1u : 0u;
+    if ((rc = exit_flights(L))) return rc;
+    A.light_const = false;
+    if (PL.n_light && (rc = ensure_light_const(p, &A.light_const))) return rc;
+    G.last_light_const = A.light_const ? 1 : 0;
+    if (G.est == VP_EST_GLOBAL && PL.n_light && !A.light_const)
+    {
+        if ((rc = ensure_thr_table(p, &L.thr_table))) return rc;
+        L.thr_n = G.thr_entries;
+    }
+    // the camera rays' free flights through certified-empty cells in kernels of their own, ahead of the integrator (approach_k: global
+    // majorant; approach_local_k: decomposition estimator; spectral tracking, passive environment, staged launches)
+    A.approach = A.approach_thr = false;
+    if (approach_possible(L.crawl, PL.n_general) && (!G.count || getenv("VP_COUNT_APPROACH")))   // counting launches: the integrator makes every step itself unless asked (block tallies)
+    {
+        // global majorant: one majorant for the whole walk, checked here; decomposition: approach_local_k checks each segment's own
+        bool identity = true;
+        if (G.est == VP_EST_GLOBAL) rc = G.arith == VP_ARITH_FAST ? ensure_fast_identity(p, &identity) : ensure_light_identity(p, &identity);
+        if (rc) return rc;
+        // (fast arithmetic: only where its own null collision in empty space is neutral -- else render_k walks, as in a one-frame launch)
+        A.approach = identity || G.arith != VP_ARITH_FAST;
+        if (!identity && A.approach)
+        {
+            // the walk's null collisions change the throughput: render_k looks it up by their number (the light kernel's table)
+            if ((rc = ensure_thr_table(p, &L.thr_table))) return rc;
+            L.thr_n  = G.thr_entries;
+            A.approach_thr = true;
+        }
+    }
+    // (decomposition estimator: the restart segments of every general pixel's camera ray, tabulated once per view -- built with the
+    // crawl table and the pixel lists whatever the frame count, so that no later launch rebuilds it and waits for those in flight;
+    // read by waves of one pixel x 64 frames)
+    L.seg_table = nullptr;
+    if (A.approach && G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && !lists)
+    {
+        const float4* seg = nullptr;
+        if ((rc = ensure_segment_table(p, L.crawl, &seg))) return rc;
+        if (nframes >= 64) L.seg_table = seg;
+    }
+    return VP_OK;
+}
+// Where the call runs and how it is cut into launches: staging, the hand-over buffer, the pipeline slot
+static int plan_target(int nframes, const Target* tgt, const PixelLists* lists, LaunchPlan& A)
+{
+    // a call with statistics is staged whatever its length (render_k's direct accumulation has none) and stays on the caller's stream
+    A.staged = nframes > 1 || A.stage_only || A.stats;
+    A.T      = tgt ? *tgt : Target{&G.target[0], G.stream};   // (a pipelined call: a slot's, below)
+    A.max_f  = A.staged ? stage_frames_cap(A.per_frame, A.T.rt->stage.bytes) : 1;
+    // The staging slot of the decomposition estimator's hand-over holds the segment origin and the distance reached in it: the stream's
+    // state (a pair index, or sampler.h's two words) goes beside it.  Sized ONCE, before the launch loop (no synchronisation, no early
+    // return between a launch's events).
+    A.appr_aux_needed = A.approach && G.est == VP_EST_DECOMP && A.staged;
+    // A staged call of vp_render_frames goes to the next pipeline slot when the slot holds it in one launch (counting launches stay on the
+    // caller's stream).  Otherwise -- VP_NO_PIPELINE, no memory for the slot -- the caller's stream, as before: same bits either way.
+    A.slot  = G.pipe_next;
+    A.piped = !tgt && !A.stage_only && !lists && !A.stats && nframes > 1 && G.pipeline && !G.count && pipe_target(A.per_frame, nframes, A.appr_aux_needed, &A.T);
+    if (A.piped) A.max_f = (size_t)nframes;
+    else if (!tgt) G.pipe_fence = true;   // (the caller's stream uses slot 0's buffers: the next pipelined launch waits for it)
+    G.last_pipelined = A.piped ? 1 : 0;
+    if (!A.appr_aux_needed) return VP_OK;
+    const size_t one = A.per_frame * sizeof(uint2);
+    return reserve_handover(A.T, one * std::min<size_t>((size_t)nframes, A.max_f), one * A.sized_frames(nframes));
+}
+// The staging of a launch of f frames.  *smaller: another allocator took the memory since it was measured -- A.max_f is halved, and a
+// smaller batch renders the same bits
+static int reserve_launch_stage(LaunchPlan& A, int f, bool* smaller)
+{
+    *smaller = false;
+    const size_t exact = A.per_frame * (size_t)f * sizeof(float4);
+    const int rc = reserve_stage(A.T, exact, A.per_frame * A.sized_frames(f) * sizeof(float4));
+    if (rc || exact <= A.T.rt->stage.bytes) return rc;
+    if (A.stage_only) return fail(VP_E_NOMEM, "no memory for a look-ahead batch of %d frames", f);
+    if (f <= 1) return fail(VP_E_NOMEM, "no memory for one staged frame (%zu bytes)", exact);
+    A.max_f = (size_t)std::max(f / 2, 1);
+    *smaller = true;
+    return VP_OK;
 }
 
-// where a render launch goes: the caller's stream with the shared staging buffer, or a look-ahead slot
+// ---- one launch
+// The form the brick table takes in the general class's kernel: 0 global memory, 1 16-bit pairs through LDS, 2 2-bit codes through LDS
+static int brick_table_form(const LaunchPlan& A, const Param* p, const SceneDev& S)
+{
+    // the brick table goes through LDS when it fits (decomposition estimator, byte table <= 64 KiB)
+    const bool lds_bounds = G.use_lds_bounds && G.est == VP_EST_DECOMP && G.quant && !G.env_mis && !G.trk &&
+                            (size_t)S.bnx * S.bny * S.bnz <= (size_t)VP_LDS_BOUND_ENTRIES;
+    // ... as 2-bit codes where it has at most four distinct pairs (round 5): the plain kernel's registers and occupancy with the table
+    // in LDS.  Timed launches of the counter-based streams; counting launches and look-ahead batches keep the 16-bit form.
+    // Chromatic media too, since their kernel fits six waves per SIMD (79 registers: intersect_box axis by axis, vp_device.h): c4s
+    // 1935 with the 16-bit table and its helper, 2001 from global memory, 2024 with the codes (profiles/experiments/r05_box_sequence.txt;
+    // before that change 1.7 % behind the 16-bit table: r05_lds_compact_table.txt).  VP_LDS_COMPACT_CHROMATIC=0: not.
+    // A table that cannot go as codes: for those launches from GLOBAL memory (six / five waves) rather than as 16-bit pairs through LDS
+    // (four waves and a helper workgroup) -- c4f +1.6 %; C3 was level already (round 5).  VP_LDS_PAIRS=1: the pairs.
+    const bool ach_lds = p->sigma_t.x == p->sigma_t.y && p->sigma_t.y == p->sigma_t.z && p->albedo.x == p->albedo.y && p->albedo.y == p->albedo.z;
+    // (the sequential sampler.h stream has no codes kernel; its timed launches, too, are ahead without the pairs: c3 +2.2 %, c4s +4.3 %)
+    const bool timed_l  = !G.count && !A.lookahead;                // a timed launch (not a counting one, not a look-ahead batch)
+    const bool timed_cb = timed_l && G.rng != VP_RNG_SAMPLERH;    // ... of a counter-based stream
+    return !lds_bounds ? 0 : (G.bound_codes_ok && G.d_bound_codes && timed_cb && (ach_lds || G.lds_compact_chromatic)) ? 2
+                             : (timed_l && !G.lds_pairs) ? 0 : 1;
+}
+// ... and whether the 16-bit form gets its helper workgroups (launch_general_class) on the auxiliary stream
+// (not for look-ahead batches: two of them overlap -- the next one's approach walk and first workgroups run beside the current
+// one's body and tail -- only if the current one leaves registers free: four LDS-table waves per SIMD do, the helper's fifth does
+// not.  C3 host loop 1301 -> 1510 Msamples/s without it, profiles/r03_render_kernel_lookahead.txt)
+// COUPLING (two tuning decisions that depend on each other): approach_local_k needs 47 vector registers (kernel_resources.py);
+// beside four 97-102-register LDS-table waves AND the helper's fifth 96-register wave a SIMD has 27 left, beside the four
+// alone 124.  If approach_local_k's register count or the helper's occupancy changes, re-measure the `!A.lookahead` below.
+static bool brick_table_helper(const LaunchPlan& A, int lds_form) { return lds_form == 1 && G.lds_helper && A.PL.n_general && !(A.PL.n_light && !A.light_const) && !A.lookahead; }
+// The grid of a class's kernel (cls 0 the general, 1 the light one) over total_items samples: workgroups, the most that are resident,
+// and how long a wave stays in the tracking loop
+struct ClassGrid { bool ldsb; unsigned blocks, cap, wait_iters; };
+static ClassGrid class_grid(const LaunchPlan& A, int cls, int lds_form, unsigned total_items)
+{
+    ClassGrid g;
+    g.ldsb = lds_form == 1 && !cls;   // (the 16-bit table: 512-thread workgroups, two per CU)
+    const unsigned bsz  = g.ldsb ? VP_BLOCK_LDS : VP_BLOCK;
+    unsigned waves  = (total_items + 63) / 64;
+    g.blocks = (waves + (bsz / 64) - 1) / (bsz / 64);
+    const bool     both = A.both();
+    unsigned       bpc  = G.blocks_per_cu;
+    // what fits a SIMD's 512 vector registers side by side: global majorant 4 x 96 + 2 x 64,
+    // local majorant 5 x 96 + ... the light kernel's blocks take what is left as general blocks retire
+    // (local majorant, five 96-register general waves per SIMD: the light kernel's workgroups find room as general ones retire,
+    // i.e. mostly at the end -- then as many of them as fit)
+    if (both && cls) bpc = G.light_blocks_per_cu ? G.light_blocks_per_cu : (G.est == VP_EST_GLOBAL ? 2u : 6u);
+    if (!both && cls) bpc = 8u;   // the light kernel alone: 64 registers
+    if (both && !cls) bpc = G.general_blocks_per_cu ? G.general_blocks_per_cu : (G.est == VP_EST_GLOBAL ? 4u : 5u);
+    // look-ahead batches overlap in pairs: the next batch's approach walk (23 / 47 registers) must find room beside the current
+    // batch's integrator -- six of its 72-register workgroups leave 80 registers per SIMD lane, five 80-register ones 112
+    if (A.lookahead && !cls && !both) bpc = std::min(bpc, G.est == VP_EST_GLOBAL ? 6u : 5u);
+    g.cap = (unsigned)G.num_cu * (g.ldsb ? 2u : bpc);
+    if (g.blocks > g.cap) g.blocks = g.cap;
+    // the light kernel's paths are long and end rarely: its waves leave the tracking loop for the (refill / environment /
+    // write) pass less often than the general kernel's do for their collisions
+    g.wait_iters = cls ? (G.light_wait_iters ? G.light_wait_iters : (G.est == VP_EST_GLOBAL ? 128u : 64u)) : G.wait_iters;
+    return g;
+}
+// A target's auxiliary stream beside its own for one kernel of a launch -- the light kernel beside the general one, or the helper
+// workgroups of the LDS-table kernel: forked from everything queued on the target's stream so far, joined before the stream goes on.
+// Stream and events are created on first use.  Best effort: whatever fails, the work goes to the target's stream or is left out.
+struct AuxBranch
+{
+    RenderTarget& rt; hipStream_t main; bool forked = false;
+    static bool make(hipEvent_t& e) { if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); e = nullptr; } return e != nullptr; }
+    // the fork point: the auxiliary stream will start behind what is on the target's stream now
+    void fork() { if (!(forked = make(rt.aux_ev[0]) && hipEventRecord(rt.aux_ev[0], main) == hipSuccess)) (void)hipGetLastError(); }
+    // the auxiliary stream, waiting at the fork point; null: not this time (it is used only if both the record and the wait succeeded:
+    // waiting on an unrecorded event returns at once)
+    hipStream_t begin()
+    {
+        if (!rt.aux_stream && create_internal_stream(&rt.aux_stream) != hipSuccess) { (void)hipGetLastError(); rt.aux_stream = nullptr; }
+        if (!make(rt.aux_ev[1]) || !rt.aux_stream || !forked) return nullptr;
+        if (hipStreamWaitEvent(rt.aux_stream, rt.aux_ev[0], 0) == hipSuccess) return rt.aux_stream;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    // the target's stream goes on (end-of-launch event, add-kernel) only when the auxiliary stream's kernel is done too
+    hipError_t join() { return hipEventRecord(rt.aux_ev[1], rt.aux_stream) != hipSuccess || hipStreamWaitEvent(main, rt.aux_ev[1], 0) != hipSuccess ? hipGetLastError() : hipSuccess; }
+};
+// the integrator and the walk ahead of it in the call's arithmetic: chosen once (vp_kernels_fast.hip)
+struct Kernels { decltype(&launch_render) render; decltype(&launch_approach) approach; };
+// what the class functions of a launch share
+struct Launch { const LaunchPlan& A; const SceneDev& S; LaunchDev& L; int f; int lds_form; bool lds_helper; Kernels k; AuxBranch aux; };
+// the part of L that names a class's pixels, slots and sample queues
+static void select_class(const LaunchPlan& A, LaunchDev& L, int cls, int f)
+{
+    const unsigned nt = cls ? A.PL.n_light : A.PL.n_general;
+    L.pixels      = A.PL.pixels + (cls ? A.PL.n_general : 0);
+    L.nslots      = nt;
+    L.slot_base   = cls ? A.PL.n_general : 0u;
+    L.total_items = (unsigned)((size_t)nt * (size_t)f);
+    L.queue       = target_queue(A.T.rt) + (cls ? kQueueWords : 0);
+    // chunks of pixels x frames (general class): only when the frame count is a multiple of the frame block
+    L.chunk_fshift = (!cls && G.chunk_fshift && f % (1 << G.chunk_fshift) == 0) ? G.chunk_fshift : 0u;
+    // the pixels of the class split into VP_NQUEUES bands (whole 64-pixel groups, the last band takes the rest)
+    for (unsigned q = 0; q <= VP_NQUEUES; q++) L.q_start[q] = q == VP_NQUEUES ? nt : (unsigned)((unsigned long long)(nt / 64u) * q / VP_NQUEUES) * 64u;
+}
+// The general class: the approach walk, the mark the next pipelined call starts behind, the integrator, the LDS-table kernel's helper
+static hipError_t launch_general_class(Launch& X, const ClassGrid& g)
+{
+    const LaunchPlan& A = X.A; LaunchDev& L = X.L; const Target& T = A.T;
+    hipError_t le = hipSuccess;
+    ClassTimer ct(0, T.stream);
+    L.approach = 0;
+    G.last_approach = 0;
+    G.last_approach_table = 0;
+    const bool aux_ok = !A.appr_aux_needed || T.rt->handover.p != nullptr;
+    if (A.appr_aux_needed) L.approach_aux = T.rt->handover;
+    if (A.approach && aux_ok && L.stage && X.f <= 65535)
+    {
+        L.approach       = A.approach_thr ? 2u : 1u;
+        L.approach_steps = G.approach_steps;
+        L.approach_fshift = 0;
+        while (L.approach_fshift < G.approach_fshift_max && (2u << L.approach_fshift) <= (unsigned)X.f) L.approach_fshift++;
+        X.k.approach(X.S, L, G.est, G.rng, G.quant, T.stream);
+        le = hipGetLastError();
+        G.last_approach = (int)L.approach;
+        G.last_approach_table = (G.est == VP_EST_DECOMP && G.quant && L.seg_table && L.approach_fshift == 6u) ? 1 : 0;
+        // the helper workgroups of the LDS-table kernel (auxiliary stream, below) read the staging slots as well: their
+        // fork point moves behind the walk
+        if (X.lds_helper && X.aux.forked && le == hipSuccess) X.aux.fork();
+    }
+    // (a pipelined call: the next one starts from here -- its approach walk finds room only as this render_k's waves retire,
+    // i.e. in its tail; without the mark it started beside this call's own walk and the two integrators shared the chip)
+    if (A.piped && le == hipSuccess)
+    {
+        if (hipEventRecord(G.pipe_gate[A.slot], T.stream) == hipSuccess) G.pipe_gate_set[A.slot] = true;
+        else le = hipGetLastError();
+    }
+    if (le == hipSuccess)
+    {
+        X.k.render(X.S, L, G.est, G.rng, G.quant, G.count, X.lds_form, G.env_mis, G.trk, (int)g.blocks, T.stream);
+        le = hipGetLastError();
+    }
+    // The LDS-table kernel holds 2 x 64 KiB of a CU's LDS with 2 x 512 threads: four waves per SIMD, where the
+    // registers would allow five.  The fifth comes from the SAME kernel without the LDS stage (the brick table read
+    // from global memory), one 256-thread workgroup per CU beside it on the auxiliary stream, drawing from the same
+    // sample queues: a sample is computed by whichever wave takes its chunk, with the same bits.
+    if (X.lds_helper && g.ldsb && le == hipSuccess && X.aux.forked && g.blocks >= g.cap)
+        if (hipStream_t hs = X.aux.begin())
+        {
+            X.k.render(X.S, L, G.est, G.rng, G.quant, G.count, 0, G.env_mis, G.trk, G.num_cu, hs);
+            le = hipGetLastError();
+            if (le == hipSuccess) le = X.aux.join();
+        }
+    ct.stop();
+    return le;
+}
+// The light class: one constant per pixel where its samples do not depend on the draws in this medium (written for every frame: the
+// environment along the camera ray, as for the box-missing pixels), else the light kernel -- beside the general one on the target's
+// auxiliary stream when both classes have work
+static hipError_t launch_light_class(Launch& X, const ClassGrid& g)
+{
+    const LaunchPlan& A = X.A; const Target& T = A.T;
+    hipStream_t ls = nullptr;
+    if (!A.light_const && A.both() && G.light_overlap) ls = X.aux.begin();   // (behind the fork point: queue heads zeroed, the previous launch's reduce, uploads)
+    ClassTimer ct(1, ls ? ls : T.stream);
+    if (A.light_const) launch_miss_fill(X.S, X.L, false, T.stream);
+    else launch_render_light(X.S, X.L, G.est, G.rng, G.quant, G.count, (int)g.blocks, ls ? ls : T.stream);
+    hipError_t le = hipGetLastError();
+    ct.stop();
+    if (ls && le == hipSuccess) le = X.aux.join();
+    return le;
+}
+// the pixels whose camera ray misses the box: one constant per pixel, written for every frame (miss_fill_k)
+static hipError_t launch_miss_class(Launch& X)
+{
+    const PixelLists& PL = X.A.PL;
+    X.L.pixels      = PL.pixels + PL.n_general + PL.n_light;
+    X.L.nslots      = PL.n_miss;
+    X.L.slot_base   = PL.n_general + PL.n_light;
+    X.L.total_items = 0;
+    ClassTimer ct(2, X.A.T.stream);
+    launch_miss_fill(X.S, X.L, G.est != VP_EST_GLOBAL, X.A.T.stream);
+    const hipError_t le = hipGetLastError();
+    ct.stop();
+    return le;
+}
+// One launch of f frames on the plan's target, between the two events of its time: queue heads, one kernel per pixel class
+static int launch_classes(const LaunchPlan& A, const SceneDev& S, LaunchDev& L, const Param* p, int f)
+{
+    const Target& T = A.T;
+    HIPCHK(hipMemsetAsync(target_queue(T.rt), 0, 2 * kQueueWords * sizeof(unsigned), T.stream));
+    const int lds_form = brick_table_form(A, p, S);
+    G.last_lds_form = lds_form;
+    L.bound_codes = lds_form == 2 ? G.d_bound_codes : nullptr;
+    L.bound_pal[0] = G.bound_pal[0]; L.bound_pal[1] = G.bound_pal[1];
+    hipEvent_t e0 = get_event(), e1 = get_event();
+    bool timed = e0 && e1 && hipEventRecord(e0, T.stream) == hipSuccess;
+    hipError_t le = hipSuccess;
+    Launch X = {A, S, L, f, lds_form, brick_table_helper(A, lds_form),
+                G.arith == VP_ARITH_FAST ? Kernels{launch_render_fast, launch_approach_fast} : Kernels{launch_render, launch_approach},
+                AuxBranch{*T.rt, T.stream}};
+    // the fork point of the light kernel's auxiliary stream: BEFORE the general kernel is queued (the two run side by side),
+    // after the queue heads are zeroed
+    // (the same fork serves the helper workgroups of the LDS-table kernel when no light kernel needs the stream)
+    if ((A.both() && G.light_overlap) || X.lds_helper) X.aux.fork();
+    // one launch per pixel class: the general pixels, then the light ones (their own kernel, their own sample queues)
+    for (int cls = 0; cls < 2 && le == hipSuccess; cls++)
+    {
+        if (!(cls ? A.PL.n_light : A.PL.n_general)) continue;
+        if (G.debug_only_class >= 0 && G.debug_only_class != cls) continue;  // VP_DEBUG_ONLY_CLASS: block tallies of one kernel
+        select_class(A, L, cls, f);
+        const ClassGrid g = class_grid(A, cls, lds_form, L.total_items);
+        L.wait_iters = g.wait_iters;
+        le = cls ? launch_light_class(X, g) : launch_general_class(X, g);
+    }
+    if (A.PL.n_miss && le == hipSuccess) le = launch_miss_class(X);
+    timed = timed && le == hipSuccess && hipEventRecord(e1, T.stream) == hipSuccess;
+    G.timed_n++;
+    if (timed) { G.events.emplace_back(e0, e1); trim_events(); }
+    else { put_event(e0); put_event(e1); }
+    if (le != hipSuccess) return fail(VP_E_NODEVICE, "render launch -> %s", hipGetErrorString(le));
+    return VP_OK;
+}
+// The reduce of a staged launch into the caller's image, on the caller's stream (last: the call's last launch)
+static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
+{
+    // for the add-kernel: all tiles of the rank
+    L.pixels = A.PL.pixels; L.nslots = (unsigned)A.per_frame; L.slot_base = 0;
+    if (!L.stage || A.stage_only) return VP_OK;
+    if (A.piped)
+        if (int rc = pipe_await_launch(A.slot, A.T.stream)) return rc;
+    if (A.stats)
+    {
+        // (an adaptive round that the staging cap splits into several launches: the criterion is the ROUND's, evaluated in its
+        // last launch -- a record frozen on a part of the round would stay frozen)
+        StatsDev R = *A.stats;
+        R.adaptive = A.stats->adaptive && last ? 1u : 0u;
+        launch_reduce_stats(L, R, G.stream);
+    }
+    else launch_reduce(L, G.stream);
+    HIPCHK(hipGetLastError());
+    if (A.piped)
+    {
+        HIPCHK(hipEventRecord(G.pipe_free[A.slot], G.stream));   // (the slot is free again once this reduce has read its staging)
+        G.pipe_free_set[A.slot] = true;
+    }
+    return VP_OK;
+}
 
+// One render call: check, prepare the tables, plan, then launch by launch -- reserve the staging, wire the pipeline, launch the
+// classes (timed), reduce
 int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only, const Target* tgt, const PixelLists* lists, const StatsDev* stats)
 {
     int rc = ensure_device();
     if (rc) return rc;
-    if (!G.have_volume) return fail(VP_E_STATE, "render before init_cuda");
-    if (!G.have_env) return fail(VP_E_STATE, "render before init_envmap");
-    if (!G.have_sun) return fail(VP_E_STATE, "render before set_sun");
-    if (!G.have_cam) return fail(VP_E_STATE, "render before copy_inv_view_matrix");
+    if ((rc = check_render(CHK_STATE, p))) return rc;
     if (!d_out || !p || nframes <= 0 || first < 0) return fail(VP_E_ARG, "bad render arguments");
-    Target T = tgt ? *tgt : Target{G.stream, &G.d_stage, &G.stage_bytes, G.d_queue, 0};   // (a pipelined call: a slot's, below)
-    if (p->width == 0 || p->height == 0 || p->width > 65535 || p->height > 65535)
-        return fail(VP_E_ARG, "image %ux%u out of range (sampler.h packs x<<16|y)", p->width, p->height);
-    if (G.trk && G.env_mis) return fail(VP_E_STATE, "scalar tracking builds exist with passive environment lighting only");
-    if (G.trk && G.count) return fail(VP_E_STATE, "work counters are not built for the scalar tracking kernels");
-    if (G.rng == VP_RNG_PHILOX7 && (G.trk || G.env_mis))
-        return fail(VP_E_STATE, "VP_RNG_PHILOX7 is built for spectral tracking with passive environment lighting only");
-    if (G.arith == VP_ARITH_FAST)
-    {
-        // the fast arithmetic is built for the counter-based streams' shipped configuration only (vp_kernels_fast.hip)
-        if (G.rng == VP_RNG_SAMPLERH) return fail(VP_E_STATE, "VP_ARITH_FAST is not built for VP_RNG_SAMPLERH (the parity mode is exact by definition)");
-        if (G.est == VP_EST_BOUNDED) return fail(VP_E_STATE, "VP_ARITH_FAST is not built for VP_EST_BOUNDED");
-        if (G.env_mis) return fail(VP_E_STATE, "VP_ARITH_FAST is built for passive environment lighting only");
-        if (G.trk) return fail(VP_E_STATE, "VP_ARITH_FAST is built for spectral tracking only");
-        if (G.count) return fail(VP_E_STATE, "work counters are not built for VP_ARITH_FAST");
-    }
-    if ((rc = subpixel_check(p))) return rc;
+    if ((rc = check_render(CHK_IMAGE | CHK_IMAGE_NOTE | CHK_MODES, p))) return rc;
     G.last_arith = G.arith;   // (vp_last_arithmetic: the mode of the last render call, whatever classes its pixels fall in)
-    if (G.est == VP_EST_DECOMP && first + nframes - 1 > 10 && !G.S.opacity)
-        return fail(VP_E_NOOPACITY, "frames beyond 10 need precompute_opacity (kernel.cu:2183, host.cpp:336-343)");
+    if ((rc = check_render(CHK_OPACITY, p, (long long)first + nframes - 1))) return rc;
     LaunchDev L = {};
     static_assert(sizeof(ParamDev) == sizeof(Param) && sizeof(Param) == 44, "Param layout (param.h:4-12)");
     memcpy(&L.P, p, sizeof(Param));
@@ -173,403 +589,63 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     L.counters = G.count ? G.d_counters : nullptr;
     L.key0 = G.key0; L.key1 = G.key1;
     L.wait_lanes = G.wait_lanes; L.wait_iters = G.wait_iters; L.setup_lanes = G.setup_lanes; L.end_lanes = G.end_lanes;
-    {
-        // (Rounds 4-5 gave the chromatic local-majorant kernels 32 parked lanes: their event pass was the most expensive.  Since the event
-        // section reads its uniforms from LDS -- vp_kernels.hip kargs_lds_ -- a visit is cheap enough that the general default is the
-        // better one there too: c4s +1.1 %, c4f +0.9 % at 28, profiles/experiments/r05_kargs_lds.txt.  Performance only.)
-        // the sequential sampler.h stream (the parity mode): its shadow rays walk to their ends, a wave's lanes park later -- 24 lanes, the
-        // default of rounds 1-4, stays 0.8 % ahead of 28 on the reference's live configuration (profiles/r05_raw/sweep_samplerh.txt)
-        if (!G.wait_lanes_set && G.rng == VP_RNG_SAMPLERH && G.trk == VP_TRACK_SPECTRAL) L.wait_lanes = 24;
-    }
+    // (Rounds 4-5 gave the chromatic local-majorant kernels 32 parked lanes: their event pass was the most expensive.  Since the event
+    // section reads its uniforms from LDS -- vp_kernels.hip kargs_lds_ -- a visit is cheap enough that the general default is the
+    // better one there too: c4s +1.1 %, c4f +0.9 % at 28, profiles/experiments/r05_kargs_lds.txt.  Performance only.)
+    // the sequential sampler.h stream (the parity mode): its shadow rays walk to their ends, a wave's lanes park later -- 24 lanes, the
+    // default of rounds 1-4, stays 0.8 % ahead of 28 on the reference's live configuration (profiles/r05_raw/sweep_samplerh.txt)
+    if (!G.wait_lanes_set && G.rng == VP_RNG_SAMPLERH && G.trk == VP_TRACK_SPECTRAL) L.wait_lanes = 24;
     if (sh.per_frame == 0) return VP_OK;
     if ((lists || stats) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics");
-    // (a sub-pixel factor: the per-pixel table of the image the samples are computed on; lists, staging and output stay this image's)
-    L.sub_shift = (unsigned)G.sub_shift;
-    const Param fine = subpixel_param(p);
-    rc = ensure_crawl_table(&fine, &L.crawl);
-    if (rc) return rc;
-    rc = ensure_pixel_lists(p, L.crawl, sh);
-    if (rc) return rc;
-    // the lists this call launches on: the context's cached ones, or the caller's (vp_adaptive.cpp: the active pixels of a round --
-    // a class-ordered subset of the cached lists; staging rows, sample queues and the reduce are then that subset's)
-    const PixelLists PL = lists ? *lists : PixelLists{G.d_tiles, G.n_general, G.n_light, G.n_miss};
-    const size_t per_frame = (size_t)PL.n_general + PL.n_light + PL.n_miss;
-    if (per_frame == 0) return VP_OK;
-    // a call with statistics is staged whatever its length (render_k's direct accumulation has none) and stays on the caller's stream
-    const bool staged = nframes > 1 || stage_only || stats;
-    rc = ensure_sun_clip(&L.sun_clip, &L.clip_ds);
-    if (rc) return rc;
-    L.count_clips = getenv("VP_DEBUG_COUNT_CLIPS") ? 1u : 0u;
-    rc = exit_flights(L);
-    if (rc) return rc;
-    bool light_const = false;
-    if (PL.n_light)
-    {
-        rc = ensure_light_const(p, &light_const);
-        if (rc) return rc;
-    }
-    G.last_light_const = light_const ? 1 : 0;
-    if (G.est == VP_EST_GLOBAL && PL.n_light && !light_const)
-    {
-        rc = ensure_thr_table(p, &L.thr_table);
-        if (rc) return rc;
-        L.thr_n = G.thr_entries;
-    }
-    // the camera rays' free flights through certified-empty cells in kernels of their own, ahead of the integrator (approach_k: global
-    // majorant; approach_local_k: decomposition estimator; spectral tracking, passive environment, staged launches)
-    bool approach = false, approach_thr = false;
-    if (approach_possible(L.crawl, PL.n_general) && (!G.count || getenv("VP_COUNT_APPROACH")))   // counting launches: the integrator makes every step itself unless asked (block tallies)
-    {
-        // global majorant: one majorant for the whole walk, checked here; decomposition: approach_local_k checks each segment's own
-        bool identity = true;
-        if (G.est == VP_EST_GLOBAL) rc = G.arith == VP_ARITH_FAST ? ensure_fast_identity(p, &identity) : ensure_light_identity(p, &identity);
-        if (rc) return rc;
-        // (fast arithmetic: only where its own null collision in empty space is neutral -- else render_k walks, as in a one-frame launch)
-        approach = identity || G.arith != VP_ARITH_FAST;
-        if (!identity && approach)
-        {
-            // the walk's null collisions change the throughput: render_k looks it up by their number (the light kernel's table)
-            rc = ensure_thr_table(p, &L.thr_table);
-            if (rc) return rc;
-            L.thr_n  = G.thr_entries;
-            approach_thr = true;
-        }
-    }
-    // (decomposition estimator: the restart segments of every general pixel's camera ray, tabulated once per view -- built with the
-    // crawl table and the pixel lists whatever the frame count, so that no later launch rebuilds it and waits for those in flight;
-    // read by waves of one pixel x 64 frames)
-    L.seg_table = nullptr;
-    if (approach && G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && !lists)
-    {
-        const float4* seg = nullptr;
-        rc = ensure_segment_table(p, L.crawl, &seg);
-        if (rc) return rc;
-        if (nframes >= 64) L.seg_table = seg;
-    }
-    if (0xfffffff0u / per_frame < 1) return fail(VP_E_ARG, "image too large for the 32-bit sample queue");
-    L.stage_stride = (unsigned)per_frame;
-    size_t max_f = staged ? stage_frames_cap(per_frame, *T.stage_bytes) : 1;
+    LaunchPlan A = {};
+    A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats;
+    if ((rc = prepare_tables(p, sh, nframes, lists, L, A)) || A.per_frame == 0) return rc;
+    if (0xfffffff0u / A.per_frame < 1) return fail(VP_E_ARG, "image too large for the 32-bit sample queue");
+    L.stage_stride = (unsigned)A.per_frame;
     SceneDev S = G.S;
     S.linear   = G.linear ? 1 : 0;
-    // The staging slot of the decomposition estimator's hand-over holds the segment origin and the distance reached in it: the stream's
-    // state (a pair index, or sampler.h's two words) goes beside it.  Sized ONCE, before the launch loop (no synchronisation, no early
-    // return between a launch's events).
-    const bool appr_aux_needed = approach && G.est == VP_EST_DECOMP && staged;
-    // A staged call of vp_render_frames goes to the next pipeline slot when the slot holds it in one launch (counting launches stay on the
-    // caller's stream).  Otherwise -- VP_NO_PIPELINE, no memory for the slot -- the caller's stream, as before: same bits either way.
-    const int  ps    = G.pipe_next;
-    const bool piped = !tgt && !stage_only && !lists && !stats && nframes > 1 && G.pipeline && !G.count && pipe_target(per_frame, nframes, appr_aux_needed, &T);
-    if (piped) max_f = (size_t)nframes;
-    else if (!tgt) G.pipe_fence = true;   // (the caller's stream uses slot 0's buffers: the next pipelined launch waits for it)
-    G.last_pipelined = piped ? 1 : 0;
+    if ((rc = plan_target(nframes, tgt, lists, A))) return rc;
     // look-ahead batches carry their slot's cancel word and their number (la_render_slot, la_quiesce); the caller's own launches cannot be cancelled
-    L.cancel = tgt ? G.d_cancel + T.index : nullptr; L.batch_id = G.batch_seq[T.index];
-    if (appr_aux_needed)
-    {
-        const int    ti    = T.index;
-        // (a look-ahead slot is sized for the largest batch at once: a slot that grew with every doubling of the ramp would
-        // synchronise its stream -- and the batch running beside it -- at every step)
-        const size_t fr4   = stage_only ? std::max<size_t>((size_t)nframes, (size_t)std::max(G.la_max, 1)) : (size_t)nframes;
-        const size_t need4 = per_frame * std::min<size_t>(fr4, max_f) * sizeof(uint2);
-        if (per_frame * std::min<size_t>((size_t)nframes, max_f) * sizeof(uint2) > G.appr_aux_bytes[ti])
-        {
-            if (!tgt && (rc = pipe_quiesce())) return rc;   // (target 0's buffers are pipeline slot 0's)
-            HIPCHK(hipStreamSynchronize(T.stream));
-            if (G.d_appr_aux[ti]) HIPCHK(hipFree(G.d_appr_aux[ti]));
-            G.d_appr_aux[ti] = nullptr; G.appr_aux_bytes[ti] = 0;
-            if (hipMalloc((void**)&G.d_appr_aux[ti], need4) != hipSuccess) { (void)hipGetLastError(); G.d_appr_aux[ti] = nullptr; }   // no walk ahead then
-            else G.appr_aux_bytes[ti] = need4;
-        }
-    }
+    L.cancel = tgt ? G.d_cancel + target_index(A.T.rt) : nullptr; L.batch_id = A.T.rt->batch_seq;
     for (int done = 0; done < nframes;)
     {
-        int f = (int)std::min<size_t>((size_t)(nframes - done), max_f);
+        const int f = (int)std::min<size_t>((size_t)(nframes - done), A.max_f);
         if (stage_only && f != nframes) return fail(VP_E_ARG, "look-ahead batch does not fit the staging buffer");
+        bool smaller = false;
+        if (A.staged && (rc = reserve_launch_stage(A, f, &smaller))) return rc;
+        if (smaller) continue;
         L.frame0 = first + done;
         L.nframes = f;
-        if (staged)
-        {
-            size_t need = per_frame * (size_t)f * sizeof(float4);
-            if (need > *T.stage_bytes)
-            {
-                // (a look-ahead slot is sized for the largest batch at once: growing with every doubling of the ramp would synchronise
-                // its stream, and the batch running beside it, at every step)
-                const size_t exact = need;
-                if (stage_only) need = per_frame * std::min<size_t>(std::max<size_t>((size_t)f, (size_t)std::max(G.la_max, 1)), max_f) * sizeof(float4);
-                if (!tgt && (rc = pipe_quiesce())) return rc;   // (target 0's buffers are pipeline slot 0's)
-                HIPCHK(hipStreamSynchronize(T.stream));
-                HIPCHK(hipStreamSynchronize(G.stream));  // add-kernels of earlier frames may still read the old buffer
-                if (*T.stage) HIPCHK(hipFree(*T.stage));
-                *T.stage = nullptr; *T.stage_bytes = 0;
-                hipError_t me = hipMalloc((void**)T.stage, need);
-                if (me != hipSuccess && need > exact) { (void)hipGetLastError(); need = exact; me = hipMalloc((void**)T.stage, need); }
-                if (me != hipSuccess)
-                {
-                    // another allocator took the memory since it was measured: a smaller batch renders the same bits
-                    (void)hipGetLastError();
-                    *T.stage = nullptr;
-                    if (stage_only) return fail(VP_E_NOMEM, "no memory for a look-ahead batch of %d frames", f);
-                    if (f > 1) { max_f = (size_t)std::max(f / 2, 1); continue; }
-                    return fail(VP_E_NOMEM, "no memory for one staged frame (%zu bytes)", need);
-                }
-                *T.stage_bytes = need;
-            }
-            L.stage = *T.stage;
-        }
-        else
-            L.stage = nullptr;
+        L.stage = A.staged ? A.T.rt->stage.p : nullptr;
         // per-pixel constants of the launch (the box-missing pixels; the light class where it is written by miss_fill_k) are staged once,
         // in the launch's first row: the slots behind the general (and an integrated light) class
         L.const_from = 0xffffffffu; L.stage_const = nullptr;
         if (L.stage && G.use_const_rows && !G.sub_shift)   // (a sub-pixel factor: constants of the FINE pixel, staged per frame by subpixel_fill_k)
         {
-            L.const_from  = (unsigned)(PL.n_general + ((PL.n_light && !light_const) ? PL.n_light : 0u));
+            L.const_from  = (unsigned)(A.PL.n_general + ((A.PL.n_light && !A.light_const) ? A.PL.n_light : 0u));
             L.stage_const = L.stage;
         }
         G.last_const_from = L.const_from;
-        if (piped)
-        {
-            // the slot's stream waits for the reduce that last read its staging (two calls back), for the previous call's walk
-            // (pipe_gate) and, after a change, for the caller's stream
-            if (G.pipe_free_set[ps]) HIPCHK(hipStreamWaitEvent(T.stream, G.pipe_free[ps], 0));
-            if (G.pipe_gate_set[ps ^ 1]) HIPCHK(hipStreamWaitEvent(T.stream, G.pipe_gate[ps ^ 1], 0));
-            G.pipe_gate_set[ps] = false;
-            if (G.pipe_fence)
-            {
-                HIPCHK(hipEventRecord(G.pipe_fence_ev, G.stream));
-                HIPCHK(hipStreamWaitEvent(T.stream, G.pipe_fence_ev, 0));
-                G.pipe_fence = false;
-            }
-            G.pipe_busy = true;
-        }
-        HIPCHK(hipMemsetAsync(T.queue, 0, 2 * kQueueWords * sizeof(unsigned), T.stream));
-        // the brick table goes through LDS when it fits (decomposition estimator, byte table <= 64 KiB)
-        const bool lds_bounds = G.use_lds_bounds && G.est == VP_EST_DECOMP && G.quant && !G.env_mis && !G.trk &&
-                                (size_t)S.bnx * S.bny * S.bnz <= (size_t)VP_LDS_BOUND_ENTRIES;
-        // ... as 2-bit codes where it has at most four distinct pairs (round 5): the plain kernel's registers and occupancy with the table
-        // in LDS.  Timed launches of the counter-based streams; counting launches and look-ahead batches keep the 16-bit form.
-        // Chromatic media too, since their kernel fits six waves per SIMD (79 registers: intersect_box axis by axis, vp_device.h): c4s
-        // 1935 with the 16-bit table and its helper, 2001 from global memory, 2024 with the codes (profiles/experiments/r05_box_sequence.txt;
-        // before that change 1.7 % behind the 16-bit table: r05_lds_compact_table.txt).  VP_LDS_COMPACT_CHROMATIC=0: not.
-        // A table that cannot go as codes: for those launches from GLOBAL memory (six / five waves) rather than as 16-bit pairs through LDS
-        // (four waves and a helper workgroup) -- c4f +1.6 %; C3 was level already (round 5).  VP_LDS_PAIRS=1: the pairs.
-        const bool ach_lds = p->sigma_t.x == p->sigma_t.y && p->sigma_t.y == p->sigma_t.z && p->albedo.x == p->albedo.y && p->albedo.y == p->albedo.z;
-        // (the sequential sampler.h stream has no codes kernel; its timed launches, too, are ahead without the pairs: c3 +2.2 %, c4s +4.3 %)
-        const bool timed_l  = !G.count && !tgt;                       // a timed launch (not a counting one, not a look-ahead batch)
-        const bool timed_cb = timed_l && G.rng != VP_RNG_SAMPLERH;    // ... of a counter-based stream
-        const int lds_form = !lds_bounds ? 0 : (G.bound_codes_ok && G.d_bound_codes && timed_cb && (ach_lds || G.lds_compact_chromatic)) ? 2
-                                             : (timed_l && !G.lds_pairs) ? 0 : 1;
-        G.last_lds_form = lds_form;
-        L.bound_codes = lds_form == 2 ? G.d_bound_codes : nullptr;
-        L.bound_pal[0] = G.bound_pal[0]; L.bound_pal[1] = G.bound_pal[1];
-        hipEvent_t e0 = get_event(), e1 = get_event();
-        bool timed = e0 && e1 && hipEventRecord(e0, T.stream) == hipSuccess;
-        hipError_t le = hipSuccess;
-        // the fork point of the light kernel's auxiliary stream: BEFORE the general kernel is queued (the two run side by side),
-        // after the queue heads are zeroed; an event of its own, created on first use
-        // (the same fork serves the helper workgroups of the LDS-table kernel, below, when no light kernel needs the stream)
-        // (not for look-ahead batches: two of them overlap -- the next one's approach walk and first workgroups run beside the current
-        // one's body and tail -- only if the current one leaves registers free: four LDS-table waves per SIMD do, the helper's fifth does
-        // not.  C3 host loop 1301 -> 1510 Msamples/s without it, profiles/r03_render_kernel_lookahead.txt)
-        // COUPLING (two tuning decisions that depend on each other): approach_local_k needs 47 vector registers (kernel_resources.py);
-        // beside four 97-102-register LDS-table waves AND the helper's fifth 96-register wave a SIMD has 27 left, beside the four
-        // alone 124.  If approach_local_k's register count or the helper's occupancy changes, re-measure the `!tgt` below.
-        const bool lds_helper = lds_form == 1 && G.lds_helper && PL.n_general && !(PL.n_light && !light_const) && !tgt;
-        bool fork_recorded = false;
-        if ((PL.n_light && PL.n_general && !light_const && G.light_overlap) || lds_helper)
-        {
-            const int ti = T.index;
-            if (!G.aux_ev[ti][0] && hipEventCreateWithFlags(&G.aux_ev[ti][0], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); G.aux_ev[ti][0] = nullptr; }
-            if (G.aux_ev[ti][0])
-            {
-                fork_recorded = hipEventRecord(G.aux_ev[ti][0], T.stream) == hipSuccess;
-                if (!fork_recorded) (void)hipGetLastError();
-            }
-        }
-        // one launch per pixel class: the general pixels, then the light ones (their own kernel, their own sample queues)
-        for (int cls = 0; cls < 2 && le == hipSuccess; cls++)
-        {
-            const unsigned nt = cls ? PL.n_light : PL.n_general;
-            if (!nt) continue;
-            if (G.debug_only_class >= 0 && G.debug_only_class != cls) continue;  // VP_DEBUG_ONLY_CLASS: block tallies of one kernel
-            L.pixels      = PL.pixels + (cls ? PL.n_general : 0);
-            L.nslots      = nt;
-            L.slot_base   = cls ? PL.n_general : 0u;
-            L.total_items = (unsigned)((size_t)nt * (size_t)f);
-            L.queue       = T.queue + (cls ? kQueueWords : 0);
-            // chunks of pixels x frames (general class): only when the frame count is a multiple of the frame block
-            L.chunk_fshift = (!cls && G.chunk_fshift && f % (1 << G.chunk_fshift) == 0) ? G.chunk_fshift : 0u;
-            // the pixels of the class split into VP_NQUEUES bands (whole 64-pixel groups, the last band takes the rest)
-            for (unsigned q = 0; q <= VP_NQUEUES; q++) L.q_start[q] = q == VP_NQUEUES ? nt : (unsigned)((unsigned long long)(nt / 64u) * q / VP_NQUEUES) * 64u;
-            const bool     ldsb = lds_form == 1 && !cls;   // (the 16-bit table: 512-thread workgroups, two per CU)
-            const unsigned bsz  = ldsb ? VP_BLOCK_LDS : VP_BLOCK;
-            unsigned waves  = (L.total_items + 63) / 64;
-            unsigned blocks = (waves + (bsz / 64) - 1) / (bsz / 64);
-            const bool     both = PL.n_light && PL.n_general && !light_const;
-            unsigned       bpc  = G.blocks_per_cu;
-            // what fits a SIMD's 512 vector registers side by side: global majorant 4 x 96 + 2 x 64,
-            // local majorant 5 x 96 + ... the light kernel's blocks take what is left as general blocks retire
-            // (local majorant, five 96-register general waves per SIMD: the light kernel's workgroups find room as general ones retire,
-            // i.e. mostly at the end -- then as many of them as fit)
-            if (both && cls) bpc = G.light_blocks_per_cu ? G.light_blocks_per_cu : (G.est == VP_EST_GLOBAL ? 2u : 6u);
-            if (!both && cls) bpc = 8u;   // the light kernel alone: 64 registers
-            if (both && !cls) bpc = G.general_blocks_per_cu ? G.general_blocks_per_cu : (G.est == VP_EST_GLOBAL ? 4u : 5u);
-            // look-ahead batches overlap in pairs: the next batch's approach walk (23 / 47 registers) must find room beside the current
-            // batch's integrator -- six of its 72-register workgroups leave 80 registers per SIMD lane, five 80-register ones 112
-            if (tgt && !cls && !both) bpc = std::min(bpc, G.est == VP_EST_GLOBAL ? 6u : 5u);
-            unsigned cap    = (unsigned)G.num_cu * (ldsb ? 2u : bpc);
-            if (blocks > cap) blocks = cap;
-            // the light kernel's paths are long and end rarely: its waves leave the tracking loop for the (refill / environment /
-            // write) pass less often than the general kernel's do for their collisions
-            L.wait_iters = cls ? (G.light_wait_iters ? G.light_wait_iters : (G.est == VP_EST_GLOBAL ? 128u : 64u)) : G.wait_iters;
-            if (cls && light_const)
-            {
-                // the samples of the light class do not depend on the draws in this medium: one constant per pixel, written for
-                // every frame (the environment along the camera ray, as for the box-missing pixels)
-                ClassTimer ct(1, T.stream);
-                launch_miss_fill(S, L, false, T.stream);
-                le = hipGetLastError();
-                ct.stop();
-            }
-            else if (cls)
-            {
-                // the light kernel: beside the general one on the target's auxiliary stream when both classes have work
-                hipStream_t ls = T.stream;
-                if (both && G.light_overlap)
-                {
-                    const int ti = T.index;
-                    if (!G.aux_stream[ti] && create_internal_stream(&G.aux_stream[ti]) != hipSuccess) { (void)hipGetLastError(); G.aux_stream[ti] = nullptr; }
-                    for (int q = 0; q < 2; q++)
-                        if (!G.aux_ev[ti][q] && hipEventCreateWithFlags(&G.aux_ev[ti][q], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); G.aux_ev[ti][q] = nullptr; }
-                    // the auxiliary stream starts at the fork point recorded above (queue heads zeroed, the previous launch's reduce,
-                    // uploads: everything queued on the target stream before the general kernel); it is used only if both the record
-                    // and the wait succeeded (waiting on an unrecorded event returns at once)
-                    if (G.aux_stream[ti] && G.aux_ev[ti][0] && G.aux_ev[ti][1] && fork_recorded)
-                    {
-                        if (hipStreamWaitEvent(G.aux_stream[ti], G.aux_ev[ti][0], 0) == hipSuccess) ls = G.aux_stream[ti];
-                        else (void)hipGetLastError();
-                    }
-                }
-                ClassTimer ct(1, ls);
-                launch_render_light(S, L, G.est, G.rng, G.quant, G.count, (int)blocks, ls);
-                le = hipGetLastError();
-                ct.stop();
-                if (ls != T.stream && le == hipSuccess)
-                {
-                    // the target stream goes on (end-of-launch event, add-kernel) only when the light kernel is done too
-                    if (hipEventRecord(G.aux_ev[T.index][1], ls) != hipSuccess || hipStreamWaitEvent(T.stream, G.aux_ev[T.index][1], 0) != hipSuccess)
-                        le = hipGetLastError();
-                }
-            }
-            else
-            {
-                ClassTimer ct(0, T.stream);
-                L.approach = 0;
-                G.last_approach = 0;
-                G.last_approach_table = 0;
-                const bool aux_ok = !appr_aux_needed || G.d_appr_aux[T.index] != nullptr;
-                if (appr_aux_needed) L.approach_aux = G.d_appr_aux[T.index];
-                if (approach && aux_ok && L.stage && f <= 65535)
-                {
-                    L.approach       = approach_thr ? 2u : 1u;
-                    L.approach_steps = G.approach_steps;
-                    L.approach_fshift = 0;
-                    while (L.approach_fshift < G.approach_fshift_max && (2u << L.approach_fshift) <= (unsigned)f) L.approach_fshift++;
-                    if (G.arith == VP_ARITH_FAST) launch_approach_fast(S, L, G.est, G.rng, G.quant, T.stream);
-                    else launch_approach(S, L, G.est, G.rng, G.quant, T.stream);
-                    le = hipGetLastError();
-                    G.last_approach = (int)L.approach;
-                    G.last_approach_table = (G.est == VP_EST_DECOMP && G.quant && L.seg_table && L.approach_fshift == 6u) ? 1 : 0;
-                    // the helper workgroups of the LDS-table kernel (auxiliary stream, below) read the staging slots as well: their
-                    // fork point moves behind the walk
-                    if (lds_helper && fork_recorded && le == hipSuccess)
-                    {
-                        fork_recorded = hipEventRecord(G.aux_ev[T.index][0], T.stream) == hipSuccess;
-                        if (!fork_recorded) (void)hipGetLastError();
-                    }
-                }
-                // (a pipelined call: the next one starts from here -- its approach walk finds room only as this render_k's waves retire,
-                // i.e. in its tail; without the mark it started beside this call's own walk and the two integrators shared the chip)
-                if (piped && le == hipSuccess)
-                {
-                    if (hipEventRecord(G.pipe_gate[ps], T.stream) == hipSuccess) G.pipe_gate_set[ps] = true;
-                    else le = hipGetLastError();
-                }
-                if (le == hipSuccess)
-                {
-                    if (G.arith == VP_ARITH_FAST) launch_render_fast(S, L, G.est, G.rng, G.quant, G.count, lds_form, G.env_mis, G.trk, (int)blocks, T.stream);
-                    else launch_render(S, L, G.est, G.rng, G.quant, G.count, lds_form, G.env_mis, G.trk, (int)blocks, T.stream);
-                    le = hipGetLastError();
-                }
-
-                // The LDS-table kernel holds 2 x 64 KiB of a CU's LDS with 2 x 512 threads: four waves per SIMD, where the
-                // registers would allow five.  The fifth comes from the SAME kernel without the LDS stage (the brick table read
-                // from global memory), one 256-thread workgroup per CU beside it on the auxiliary stream, drawing from the same
-                // sample queues: a sample is computed by whichever wave takes its chunk, with the same bits.
-                if (lds_helper && ldsb && le == hipSuccess && fork_recorded && blocks >= cap)
-                {
-                    const int ti = T.index;
-                    if (!G.aux_stream[ti] && create_internal_stream(&G.aux_stream[ti]) != hipSuccess) { (void)hipGetLastError(); G.aux_stream[ti] = nullptr; }
-                    if (!G.aux_ev[ti][1] && hipEventCreateWithFlags(&G.aux_ev[ti][1], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); G.aux_ev[ti][1] = nullptr; }
-                    if (G.aux_stream[ti] && G.aux_ev[ti][1] && hipStreamWaitEvent(G.aux_stream[ti], G.aux_ev[ti][0], 0) == hipSuccess)
-                    {
-                        if (G.arith == VP_ARITH_FAST) launch_render_fast(S, L, G.est, G.rng, G.quant, G.count, 0, G.env_mis, G.trk, G.num_cu, G.aux_stream[ti]);
-                        else launch_render(S, L, G.est, G.rng, G.quant, G.count, 0, G.env_mis, G.trk, G.num_cu, G.aux_stream[ti]);
-                        le = hipGetLastError();
-                        if (le == hipSuccess && (hipEventRecord(G.aux_ev[ti][1], G.aux_stream[ti]) != hipSuccess || hipStreamWaitEvent(T.stream, G.aux_ev[ti][1], 0) != hipSuccess))
-                            le = hipGetLastError();
-                    }
-                    else (void)hipGetLastError();
-                }
-                ct.stop();
-            }
-        }
-        if (PL.n_miss && le == hipSuccess)
-        {
-            // the pixels whose camera ray misses the box: one constant per pixel, written for every frame (miss_fill_k)
-            L.pixels      = PL.pixels + PL.n_general + PL.n_light;
-            L.nslots      = PL.n_miss;
-            L.slot_base   = PL.n_general + PL.n_light;
-            L.total_items = 0;
-            ClassTimer ct(2, T.stream);
-            launch_miss_fill(S, L, G.est != VP_EST_GLOBAL, T.stream);
-            le = hipGetLastError();
-            ct.stop();
-        }
-        timed = timed && le == hipSuccess && hipEventRecord(e1, T.stream) == hipSuccess;
-        G.timed_n++;
-        if (timed) { G.events.emplace_back(e0, e1); trim_events(); }
-        else { put_event(e0); put_event(e1); }
-        if (le != hipSuccess) return fail(VP_E_NODEVICE, "render launch -> %s", hipGetErrorString(le));
-        // for the add-kernel: all tiles of the rank
-        L.pixels = PL.pixels; L.nslots = (unsigned)per_frame; L.slot_base = 0;
-        if (L.stage && !stage_only)
-        {
-            // (a pipelined launch: the caller-visible write stays on the caller's stream, behind the slot's launch)
-            if (piped)
-            {
-                HIPCHK(hipEventRecord(G.pipe_done[ps], T.stream));
-                HIPCHK(hipStreamWaitEvent(G.stream, G.pipe_done[ps], 0));
-            }
-            if (stats)
-            {
-                // (an adaptive round that the staging cap splits into several launches: the criterion is the ROUND's, evaluated in its
-                // last launch -- a record frozen on a part of the round would stay frozen)
-                StatsDev R = *stats;
-                R.adaptive = stats->adaptive && done + f == nframes ? 1u : 0u;
-                launch_reduce_stats(L, R, G.stream);
-            }
-            else launch_reduce(L, G.stream);
-            HIPCHK(hipGetLastError());
-            if (piped)
-            {
-                HIPCHK(hipEventRecord(G.pipe_free[ps], G.stream));
-                G.pipe_free_set[ps] = true;
-            }
-        }
+        if (A.piped && (rc = pipe_await_slot_free(A.slot, A.T.stream))) return rc;
+        if ((rc = launch_classes(A, S, L, p, f))) return rc;
+        if ((rc = reduce_launch(A, L, done + f == nframes))) return rc;
         done += f;
     }
-    if (piped) G.pipe_next = ps ^ 1;
+    if (A.piped) G.pipe_next = A.slot ^ 1;
+    return VP_OK;
+}
+// what the counters and the timers read is complete: the pipelined launches, the caller's stream and, for the timers, the look-ahead batches
+// still in flight (launches too) and the auxiliary streams (class timers)
+static int await_launches(bool lookahead, bool aux)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = pipe_quiesce())) return rc;
+    HIPCHK(hipStreamSynchronize(G.stream));
+    for (auto& sl : G.la)
+        if (lookahead && sl.stream) HIPCHK(hipStreamSynchronize(sl.stream));
+    for (RenderTarget& t : G.target)
+        if (aux && t.aux_stream) HIPCHK(hipStreamSynchronize(t.aux_stream));
     return VP_OK;
 }
 
@@ -591,10 +667,7 @@ int vp_enable_counters(int on)
 }
 int vp_read_counters(vp_counters* out, int reset)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if ((rc = pipe_quiesce())) return rc;
-    HIPCHK(hipStreamSynchronize(G.stream));
+    if (int rc = await_launches(false, false)) return rc;
     unsigned long long h[kCounterWords];
     HIPCHK(hipMemcpy(h, G.d_counters, sizeof h, hipMemcpyDeviceToHost));
     if (out)
@@ -602,38 +675,37 @@ int vp_read_counters(vp_counters* out, int reset)
         memset(out, 0, sizeof *out);
         out->samples = h[0]; out->density_lookups = h[1]; out->density_loads = h[12]; out->bound_lookups = h[2];
         out->opacity_lookups = h[3]; out->env_lookups = h[4]; out->scatters = h[5];
-        if (getenv("VP_DEBUG_COUNTERS") && h[6]) fprintf(stderr, "[vp] wave-iterations %llu, active lane-steps %llu (%.1f per iteration), slow-path visits %llu (every %.1f iterations), shadow lane-steps %llu; wave cycles: slow path %llu, fast loop %llu (%.1f%% slow, %.0f cycles per visit, %.0f per step)\n", h[6], h[7], h[6] ? (double)h[7] / h[6] : 0.0, h[8], h[8] ? (double)h[6] / h[8] : 0.0, h[9], h[10], h[11], 100.0 * h[10] / (double)(h[10] + h[11] + 1), h[8] ? (double)h[10] / h[8] : 0.0, h[6] ? (double)h[11] / h[6] : 0.0);
+        if (getenv("VP_DEBUG_COUNTERS") && h[6])
+            fprintf(stderr, "[vp] wave-iterations %llu, active lane-steps %llu (%.1f per iteration), slow-path visits %llu (every %.1f iterations), "
+                    "shadow lane-steps %llu; wave cycles: slow path %llu, fast loop %llu (%.1f%% slow, %.0f cycles per visit, %.0f per step)\n",
+                    h[6], h[7], h[6] ? (double)h[7] / h[6] : 0.0, h[8], h[8] ? (double)h[6] / h[8] : 0.0, h[9], h[10], h[11],
+                    100.0 * h[10] / (double)(h[10] + h[11] + 1), h[8] ? (double)h[10] / h[8] : 0.0, h[6] ? (double)h[11] / h[6] : 0.0);
     }
-        if (getenv("VP_DEBUG_COUNTERS"))
+    if (getenv("VP_DEBUG_COUNTERS"))
+    {
+        static const char* names[15] = {"setup", "half-step", "lookup+collision", "segment/ray end", "scatter", "nee", "phase", "background", "write", "refill", "global set-up", "fetch", "zero fetch (path)", "zero fetch (shadow)", "exit test"};
+        fprintf(stderr, "[vp] exit flights: %llu tests, %llu paths ended; %llu null collisions in empty space on flights that WALKED out of the box (global majorant)\n", h[13], h[15], h[14]);
+        fprintf(stderr, "[vp] block: wave executions, lanes per execution (of 64)\n");
+        for (int b = 0; b < 15; b++)
+            if (h[16 + 2 * b]) fprintf(stderr, "[vp]   %-18s %14llu  %5.1f\n", names[b], h[16 + 2 * b], (double)h[17 + 2 * b] / (double)h[16 + 2 * b]);
+        if (h[72]) fprintf(stderr, "[vp]   %-18s %14llu  %5.1f\n", "control component", h[72], (double)h[73] / (double)h[72]);
+        static const char* hn[3] = {"scatter", "segment/ray end", "setup"};
+        for (int q = 0; q < 3; q++)
         {
-            static const char* names[15] = {"setup", "half-step", "lookup+collision", "segment/ray end", "scatter", "nee", "phase", "background", "write", "refill", "global set-up", "fetch", "zero fetch (path)", "zero fetch (shadow)", "exit test"};
-            fprintf(stderr, "[vp] exit flights: %llu tests, %llu paths ended; %llu null collisions in empty space on flights that WALKED out of the box (global majorant)\n", h[13], h[15], h[14]);
-            fprintf(stderr, "[vp] block: wave executions, lanes per execution (of 64)\n");
-            for (int b = 0; b < 15; b++)
-                if (h[16 + 2 * b]) fprintf(stderr, "[vp]   %-18s %14llu  %5.1f\n", names[b], h[16 + 2 * b], (double)h[17 + 2 * b] / (double)h[16 + 2 * b]);
-            if (h[72]) fprintf(stderr, "[vp]   %-18s %14llu  %5.1f\n", "control component", h[72], (double)h[73] / (double)h[72]);
-            static const char* hn[3] = {"scatter", "segment/ray end", "setup"};
-            for (int q = 0; q < 3; q++)
-            {
-                unsigned long long tot = 0;
-                for (int k = 0; k < 8; k++) tot += h[48 + 8 * q + k];
-                if (!tot) continue;
-                fprintf(stderr, "[vp]   executions of %-16s by lanes 1-8 .. 57-64 (%%):", hn[q]);
-                for (int k = 0; k < 8; k++) fprintf(stderr, " %5.1f", 100.0 * (double)h[48 + 8 * q + k] / (double)tot);
-                fprintf(stderr, "\n");
-            }
+            unsigned long long tot = 0;
+            for (int k = 0; k < 8; k++) tot += h[48 + 8 * q + k];
+            if (!tot) continue;
+            fprintf(stderr, "[vp]   executions of %-16s by lanes 1-8 .. 57-64 (%%):", hn[q]);
+            for (int k = 0; k < 8; k++) fprintf(stderr, " %5.1f", 100.0 * (double)h[48 + 8 * q + k] / (double)tot);
+            fprintf(stderr, "\n");
         }
+    }
     if (reset) HIPCHK(hipMemset(G.d_counters, 0, sizeof h));
     return VP_OK;
 }
 int vp_render_time_ms(double* total_ms, int* launches, int reset)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if ((rc = pipe_quiesce())) return rc;
-    HIPCHK(hipStreamSynchronize(G.stream));
-    for (auto& sl : G.la)  // look-ahead batches still in flight are launches too
-        if (sl.stream) HIPCHK(hipStreamSynchronize(sl.stream));
+    if (int rc = await_launches(true, false)) return rc;
     // (each launch from where the launches before it ended: span_ms)
     double     tot = G.timed_ms;
     hipEvent_t end = G.last_end;
@@ -671,14 +743,7 @@ int vp_lookahead_stats(unsigned* launched, unsigned* cancelled_in_flight)
 }
 int vp_render_class_time_ms(double ms[3], unsigned pixels[3], int reset)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if ((rc = pipe_quiesce())) return rc;
-    HIPCHK(hipStreamSynchronize(G.stream));
-    for (auto& sl : G.la)
-        if (sl.stream) HIPCHK(hipStreamSynchronize(sl.stream));
-    for (int i = 0; i < kTargets; i++)
-        if (G.aux_stream[i]) HIPCHK(hipStreamSynchronize(G.aux_stream[i]));
+    if (int rc = await_launches(true, true)) return rc;
     // (each class's kernel from where its predecessor of the class ended: span_ms)
     double     tot[3] = {G.class_ms[0], G.class_ms[1], G.class_ms[2]};
     hipEvent_t end[3] = {G.class_last_end[0], G.class_last_end[1], G.class_last_end[2]};
@@ -714,7 +779,7 @@ int vp_prepare(const Param* p)
     if (rc) return rc;
     if (!p) return fail(VP_E_ARG, "vp_prepare: null Param");
     if (!G.have_volume || !G.have_cam) return fail(VP_E_STATE, "vp_prepare needs a volume and a camera");
-    if (p->width == 0 || p->height == 0 || p->width > 65535 || p->height > 65535) return fail(VP_E_ARG, "image %ux%u out of range", p->width, p->height);
+    if ((rc = check_render(CHK_IMAGE, p))) return rc;
     const Shard sh = shard_of(p);
     if (sh.per_frame == 0)
     {
@@ -723,30 +788,16 @@ int vp_prepare(const Param* p)
         return VP_OK;
     }
     if ((rc = subpixel_check(p))) return rc;
-    const float4* table = nullptr;
+    const float4 *table = nullptr, *seg = nullptr;
+    const unsigned short* sc = nullptr; float ds = 0.0f;
+    const float* thr = nullptr;
     const Param fine = subpixel_param(p);
-    rc = ensure_crawl_table(&fine, &table);
-    if (rc) return rc;
-    rc = ensure_pixel_lists(p, table, sh);
-    if (rc) return rc;
-    if (G.have_sun)
-    {
-        const unsigned short* sc = nullptr; float ds = 0.0f;
-        rc = ensure_sun_clip(&sc, &ds);
-        if (rc) return rc;
-    }
-    if (G.est == VP_EST_GLOBAL && G.n_light)
-    {
-        const float* thr = nullptr;
-        rc = ensure_thr_table(p, &thr);
-        if (rc) return rc;
-    }
-    if (G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && approach_possible(table, G.n_general))   // (the decomposition walk's segment table: do_render)
-    {
-        const float4* seg = nullptr;
-        rc = ensure_segment_table(p, table, &seg);
-        if (rc) return rc;
-    }
+    if ((rc = ensure_crawl_table(&fine, &table))) return rc;
+    if ((rc = ensure_pixel_lists(p, table, sh))) return rc;
+    if (G.have_sun && (rc = ensure_sun_clip(&sc, &ds))) return rc;
+    if (G.est == VP_EST_GLOBAL && G.n_light && (rc = ensure_thr_table(p, &thr))) return rc;
+    // (the decomposition walk's segment table: do_render)
+    if (G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && approach_possible(table, G.n_general) && (rc = ensure_segment_table(p, table, &seg))) return rc;
     HIPCHK(hipStreamSynchronize(G.stream));
     return VP_OK;
 }
@@ -755,36 +806,23 @@ int vp_reserve_frames(const Param* p, int nframes)
     int rc = ensure_device();
     if (rc) return rc;
     if (!p || nframes <= 0) return fail(VP_E_ARG, "vp_reserve_frames: bad arguments");
-    if (p->width == 0 || p->height == 0 || p->width > 65535 || p->height > 65535) return fail(VP_E_ARG, "image %ux%u out of range", p->width, p->height);
+    if ((rc = check_render(CHK_IMAGE, p))) return rc;
     const Shard sh = shard_of(p);
     if (sh.per_frame == 0 || nframes == 1) return VP_OK;
     // what do_render would allocate for the first launch of such a job (a one-frame call accumulates directly and stages nothing)
-    const size_t f    = std::min<size_t>((size_t)nframes, stage_frames_cap(sh.per_frame, G.stage_bytes));
-    const size_t need = sh.per_frame * f * sizeof(float4);
-    // (decomposition estimator: the stream's state beside each staging slot of the approach kernel's hand-over, do_render)
-    const size_t need4 = (G.est == VP_EST_DECOMP && G.use_approach && !G.sub_shift && G.use_approach_local && !(G.marked_fraction > G.dense_fraction)) ? sh.per_frame * f * sizeof(uint2) : 0;
-    if (need4 > G.appr_aux_bytes[0])
-    {
-        if ((rc = pipe_quiesce())) return rc;   // (pipeline slot 0's buffer)
-        HIPCHK(hipStreamSynchronize(G.stream));
-        if (G.d_appr_aux[0]) HIPCHK(hipFree(G.d_appr_aux[0]));
-        G.d_appr_aux[0] = nullptr; G.appr_aux_bytes[0] = 0;
-        if (hipMalloc((void**)&G.d_appr_aux[0], need4) != hipSuccess) { (void)hipGetLastError(); G.d_appr_aux[0] = nullptr; }
-        else G.appr_aux_bytes[0] = need4;
-    }
-    if (need > G.stage_bytes)
+    const Target T      = {&G.target[0], G.stream};
+    const size_t f      = std::min<size_t>((size_t)nframes, stage_frames_cap(sh.per_frame, T.rt->stage.bytes));
+    const size_t need   = sh.per_frame * f * sizeof(float4);
+    // (decomposition estimator: the stream's state beside each staging slot of the approach kernel's hand-over, where a launch of this
+    // configuration can walk ahead at all -- do_render asks the same)
+    const size_t need4  = (G.est == VP_EST_DECOMP && approach_built()) ? sh.per_frame * f * sizeof(uint2) : 0;
+    if ((rc = reserve_handover(T, need4, need4))) return rc;   // (failing: no walk ahead then)
+    if (need > T.rt->stage.bytes)
     {
         if (la_quiesce()) return VP_E_NODEVICE;
         HIPCHK(hipStreamSynchronize(G.stream));
-        if (G.d_stage) HIPCHK(hipFree(G.d_stage));
-        G.d_stage = nullptr; G.stage_bytes = 0;
-        if (hipMalloc((void**)&G.d_stage, need) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            G.d_stage = nullptr;
-            return VP_OK;   // the render call will stage smaller batches: same bits
-        }
-        G.stage_bytes = need;
+        (void)reserve_stage(T, need, need, true);
+        if (need > T.rt->stage.bytes) return VP_OK;   // the render call will stage smaller batches: same bits
     }
     // ... and pipeline slot 1 where the job goes in one launch (best effort: a call the slot cannot hold renders on the caller's stream)
     if (G.pipeline && f == (size_t)nframes && pipe_streams()) (void)pipe_reserve(1, sh.per_frame, nframes, need4 > 0);

@@ -1,7 +1,8 @@
 // vp_state.h -- what the host-side translation units of libvolpath_hip.so share: the per-context State, the error helpers and the
 // internal functions of vp_context.cpp (device, volume, environment, contexts, Part 1 and the setters of include/volpath.h),
-// vp_tables.cpp (the tables a launch reads: optical depth, per-pixel, sun, exit, pixel lists), vp_render.cpp (do_render: one
-// staged launch; counters and timing), vp_lookahead.cpp (render_kernel's frame look-ahead: frozen since round 4, see there) and
+// vp_tables.cpp (the tables a launch reads: optical depth, per-pixel, sun, exit, pixel lists), vp_render.cpp (do_render: the launch
+// plan of a call and its launches, stage by stage; counters, timing, vp_prepare / vp_reserve_frames), vp_lookahead.cpp (render_kernel's
+// frame look-ahead: frozen since round 4, see there) and
 // vp_adaptive.cpp (per-pixel statistics and adaptive sampling: rounds of do_render on the pixels whose record is not frozen).
 // Round 5 split of the former vp_api.cpp (2 200 lines), no behaviour change.
 #pragma once
@@ -49,7 +50,37 @@ inline int subpixel_env_shift()
     return subpixel_shift_of(v);
 }
 
+// A device buffer that only grows.  grow(need) frees the old block BEFORE it allocates the new one (peak memory: a staging buffer is
+// a quarter of the free memory) and leaves {nullptr, 0} behind when the allocation fails (the error is cleared: out of memory is not
+// sticky, later calls may succeed).  Whoever may still read the old block is the caller's to wait for, before the call.
+template <class T> struct DevBuf
+{
+    T* p = nullptr; size_t bytes = 0;
+    operator T*() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    hipError_t grow(size_t need)
+    {
+        if (need <= bytes) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc((void**)&p, need);
+        if (e == hipSuccess) bytes = need;
+        else { (void)hipGetLastError(); p = nullptr; }
+        return e;
+    }
+};
+
 constexpr int kTargets = 4;   // render targets: the caller's stream (also pipeline slot 0), two look-ahead slots, pipeline slot 1
+// What a launch on one of them owns (its queue words and cancel word are G.d_queue's and G.d_cancel's, by index: vp_render.cpp)
+struct RenderTarget
+{
+    DevBuf<float4> stage;      // per-sample staging of a launch: what the reduce reads
+    DevBuf<uint2>  handover;   // LaunchDev::approach_aux: the stream's state beside each staging slot of the decomposition walk's hand-over
+    // the light kernel runs beside the general one on a stream of its own (ALU-bound waves fill the issue slots the general
+    // kernel's waves leave while they wait for cells): one auxiliary stream, its fork and its join event
+    hipStream_t    aux_stream = nullptr;
+    hipEvent_t     aux_ev[2]  = {nullptr, nullptr};
+    unsigned       batch_seq  = 0;   // number of the last batch queued on the target
+};
 
 struct State
 {
@@ -80,9 +111,7 @@ struct State
     int         la_overlap_from = 2;  // a batch of at least this many frames has its successor queued behind it on the other slot (VP_LOOKAHEAD_OVERLAP_FROM)
     struct LaSlot  // one staged batch of frames, rendered on its own stream so that two batches overlap
     {
-        float4*     buf = nullptr;
-        size_t      bytes = 0;
-        hipStream_t stream = nullptr;
+        hipStream_t stream = nullptr;  // (its staging: target[1 + slot])
         hipEvent_t  done = nullptr;   // recorded after the batch's render
         bool        valid = false;
         unsigned    const_from = 0;   // LaunchDev::const_from of the batch (slots whose samples are per-pixel constants, staged once in the batch's first row)
@@ -98,7 +127,7 @@ struct State
     // batch had finished (3-22 ms later: profiles/experiments/r04_lookahead_cancel.txt)
     hipStream_t ctrl_stream = nullptr;
     unsigned*   d_cancel    = nullptr; // [3] per render target: the newest batch number of the slot that is cancelled (LaunchDev::cancel)
-    unsigned    batch_seq[kTargets] = {0, 0, 0, 0};   // number of the last batch queued on each target
+    RenderTarget target[kTargets];
     bool        la_cancel   = true;    // VP_NO_LA_CANCEL=1: batches in flight always run to their end
     int         la_prev_n   = 0;      // batch size of the last miss
     int         la_last     = -2;     // frame index of the last render_kernel call
@@ -117,10 +146,8 @@ struct State
     int         rng         = VP_RNG_SAMPLERH;
     unsigned    key0 = 0, key1 = 0;
     unsigned    rank = 0, world = 1;
-    float4*     d_stage       = nullptr;
-    size_t      stage_bytes   = 0;
-    // Calls of vp_render_frames alternate between two render targets (vp_render.cpp pipe_target): slot 0 is target 0's buffers (d_stage,
-    // d_appr_aux[0], the first queue words), slot 1 target 3's, each on a stream of its own, so that the approach walk and first
+    // Calls of vp_render_frames alternate between two render targets (vp_render.cpp pipe_target): slot 0 is target 0's buffers and
+    // queue words, slot 1 target 3's, each on a stream of its own, so that the approach walk and first
     // workgroups of call N+1 run in the tail of call N.  A slot's stream waits for the reduce that last read its staging (pipe_free), for
     // the approach walk of the call before (pipe_gate) and, after a change (pipe_quiesce), for everything on the caller's stream.
     // VP_NO_PIPELINE=1 / vp_set_pipeline(0): every call on the caller's stream, as before.
@@ -136,8 +163,6 @@ struct State
     bool        pipe_busy     = false;   // a pipelined launch may still be running (pipe_quiesce waits for it)
     int         pipe_next     = 0;       // the slot of the next pipelined call
     int         last_pipelined = 0;      // vp_last_pipelined
-    float4*     d_stage2      = nullptr; // slot 1's staging buffer
-    size_t      stage2_bytes  = 0;
     unsigned*   d_queue       = nullptr;
     unsigned long long* d_counters = nullptr;
     bool        count       = false;
@@ -170,8 +195,7 @@ struct State
     int         debug_only_class = -1;    // VP_DEBUG_ONLY_CLASS = 0 / 1: launch only the general / only the light kernel (INCOMPLETE images;
                                           // for the block tallies of one kernel)
     // the pixels this context owns (those of its tiles), class by class: [general..., light...], each y << 16 | x
-    unsigned*   d_tiles     = nullptr;
-    size_t      tiles_cap   = 0;
+    DevBuf<unsigned> d_tiles;
     unsigned    n_general   = 0, n_light = 0, n_miss = 0;
     std::vector<unsigned char> tiles_key;
     unsigned*   d_tile_rows = nullptr;    // first owned tile of each tile row (pixlist kernels)
@@ -180,21 +204,13 @@ struct State
     // vp_render_adaptive (vp_adaptive.cpp): the ACTIVE pixels of the lists above -- those whose record is not frozen --, class by class
     // in the same order, rebuilt from the caller's records at the start of a call and after every round (compact_*_k); the block
     // counts and three totals of that compaction.  Never the cached lists: those, their key and vp_get_pixel_lists stay as they are.
-    unsigned*   d_act       = nullptr;
-    size_t      act_cap     = 0;
-    unsigned*   d_act_scratch = nullptr;
-    size_t      act_scratch_words = 0;
-    // the light kernel runs beside the general one on a stream of its own (ALU-bound waves fill the issue slots the general
-    // kernel's waves leave while they wait for cells): one auxiliary stream and two events per launch target
-    bool        light_overlap = true;
-    hipStream_t aux_stream[kTargets] = {};
-    hipEvent_t  aux_ev[kTargets][2]  = {};
+    DevBuf<unsigned> d_act, d_act_scratch;
+    bool        light_overlap = true;     // the light kernel beside the general one on the target's auxiliary stream (RenderTarget)
     // resident 256-thread workgroups per CU while both kernels run (0 = the measured defaults of profiles/r02_light_overlap.txt:
     // 3 + 4 for the global-majorant estimator, 5 + 2 for the local-majorant ones)
     unsigned    general_blocks_per_cu = 0, light_blocks_per_cu = 0;
     unsigned char* d_danger = nullptr;    // per cell: a non-empty cell within its 3x3x3 neighbourhood (danger_k)
-    float4*     d_crawl     = nullptr;
-    size_t      crawl_bytes = 0;
+    DevBuf<float4> d_crawl;
     std::vector<unsigned char> crawl_key;
     // counter-based streams: where a sun shadow ray has only empty cells left (sun_clip_k), per cell; rebuilt when the volume, the
     // box or the sun direction changes
@@ -211,8 +227,6 @@ struct State
     // the samples of the light class are per-pixel constants when a null collision in empty space leaves a throughput of 1
     // exactly 1 (light_identity_k): decided per (medium, estimator, volume), then miss_fill_k writes them
     bool        use_light_const = true;
-    uint2*      d_appr_aux[kTargets] = {};   // per render target (caller's stream, two look-ahead slots, the second pipeline slot): LaunchDev::approach_aux
-    size_t      appr_aux_bytes[kTargets] = {};
     int         last_approach = 0;            // vp_last_approach_mode
     int         last_approach_table = 0;      // vp_last_approach_table
     int         last_light_const = 0;         // vp_last_light_const
@@ -222,14 +236,12 @@ struct State
     // vp_set_subpixel: log2 of the sub-pixel factor S (0 = off).  With S > 1 the per-pixel table (d_crawl) is the S W x S H image's,
     // d_sub_cls holds the classes of the W x H image's pixels reduced from it (subpixel_class_k) and the pixel lists are built from those
     int         sub_shift   = subpixel_env_shift();
-    unsigned char* d_sub_cls = nullptr;
-    size_t      sub_cls_bytes = 0;
+    DevBuf<unsigned char> d_sub_cls;
     unsigned    la_launched = 0, la_cancelled = 0;   // vp_lookahead_stats
     bool        use_const_rows = true;        // VP_NO_CONST_ROWS=1: per-pixel constants are staged for every frame, as before round 4's end
     unsigned    last_const_from = 0;          // LaunchDev::const_from of the last staged launch (a look-ahead slot keeps it for its add-kernels)
     bool        use_approach_table = true;    // ... with the restart segments of a pixel's camera ray tabulated per pixel (VP_NO_APPROACH_TABLE=1: set up per sample)
-    float4*     d_seg = nullptr;              // the table (approach_segments_k), its size and what it was built for
-    size_t      seg_bytes = 0;
+    DevBuf<float4> d_seg;                     // the table (approach_segments_k) and what it was built for
     std::vector<unsigned char> seg_key;
     bool        use_approach_local = true;    // ... and approach_local_k ahead of the decomposition estimator (VP_NO_APPROACH_LOCAL=1: off)
     bool        use_approach = true;          // approach_k ahead of the global-majorant integrator (VP_NO_APPROACH=1: off)
@@ -326,8 +338,8 @@ int    ensure_thr_table(const Param* p, const float** out);
 int    ensure_pixel_lists(const Param* p, const float4* table, const Shard& sh);
 int    ensure_segment_table(const Param* p, const float4* crawl, const float4** out);
 // ---- vp_render.cpp
-// where a launch stages its samples: the caller's stream and buffers, or a look-ahead slot's
-struct Target { hipStream_t stream; float4** stage; size_t* stage_bytes; unsigned* queue; int index; };
+// where a launch runs and stages its samples: one of G.target and the stream that serves it (the caller's, a look-ahead slot's, a pipeline slot's)
+struct Target { RenderTarget* rt; hipStream_t stream; };
 // the pixel lists a launch runs on, class by class: n_general general pixels, n_light light ones, n_miss box-missing ones (y << 16 | x)
 struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss; };
 // lists: null = the context's cached lists of p (built on demand: the plain entry points), else the caller's own -- a class-ordered
@@ -335,6 +347,9 @@ struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss;
 // call is staged even for one frame and runs on the caller's stream, not on a pipeline slot.
 int  do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only = false, const Target* tgt = nullptr,
                const PixelLists* lists = nullptr, const StatsDev* stats = nullptr);
+// the preconditions of a render call, each caller with the subset it needs (p: the image checks; last_frame: the opacity rule)
+enum : unsigned { CHK_STATE = 1, CHK_IMAGE = 2, CHK_IMAGE_NOTE = 4, CHK_MODES = 8, CHK_OPACITY = 16 };
+int  check_render(unsigned what, const Param* p, long long last_frame = 0);
 void trim_events();
 int  pipe_quiesce();   // waits for the pipelined launches in flight; the next one waits for the caller's stream (every change to what launches read)
 // ---- vp_lookahead.cpp

@@ -141,19 +141,15 @@ int ensure_crawl_table(const Param* p, const float4** out)
     {
         if (la_quiesce()) return VP_E_NODEVICE;   // batches in flight read the old table
         HIPCHK(hipStreamSynchronize(G.stream));
-        if (need > G.crawl_bytes)
+        if (need > G.d_crawl.bytes)
         {
-            if (G.d_crawl) HIPCHK(hipFree(G.d_crawl));
-            G.d_crawl = nullptr; G.crawl_bytes = 0; G.crawl_key.clear();
-            if (hipMalloc((void**)&G.d_crawl, need) != hipSuccess)
+            G.crawl_key.clear();
+            if (G.d_crawl.grow(need) != hipSuccess)
             {
-                (void)hipGetLastError();
-                G.d_crawl = nullptr;
                 // (a sub-pixel factor multiplies the table by S^2 -- 245 MB at 800x600, S = 4 -- and its pixel classes come from it: said, not worked around)
                 if (G.sub_shift) return fail(VP_E_NOMEM, "no memory for the %ux%u per-pixel table of the sub-pixel factor %d (%zu bytes)", p->width, p->height, 1 << G.sub_shift, need);
                 return VP_OK;   // no table: the paths walk the crawl themselves, same bits
             }
-            G.crawl_bytes = need;
         }
         if (global)
         {
@@ -368,17 +364,10 @@ int ensure_segment_table(const Param* p, const float4* crawl, const float4** out
     {
         if (la_quiesce()) return VP_E_NODEVICE;   // batches in flight read the old table
         HIPCHK(hipStreamSynchronize(G.stream));
-        if (need > G.seg_bytes)
+        if (need > G.d_seg.bytes)
         {
-            if (G.d_seg) HIPCHK(hipFree(G.d_seg));
-            G.d_seg = nullptr; G.seg_bytes = 0; G.seg_key.clear();
-            if (hipMalloc((void**)&G.d_seg, need) != hipSuccess)
-            {
-                (void)hipGetLastError();
-                G.d_seg = nullptr;
-                return VP_OK;   // no table: every sample sets its segments up itself, same bits
-            }
-            G.seg_bytes = need;
+            G.seg_key.clear();
+            if (G.d_seg.grow(need) != hipSuccess) return VP_OK;   // no table: every sample sets its segments up itself, same bits
         }
         SceneDev S = G.S;
         S.linear   = G.linear ? 1 : 0;
@@ -424,26 +413,17 @@ int ensure_pixel_lists(const Param* p, const float4* table, const Shard& sh)
         HIPCHK(hipStreamSynchronize(G.stream));   // `rows` goes out of scope
         G.tiles_shape_key = shape_key;
     }
-    if (sh.per_frame > G.tiles_cap)
+    if (sh.per_frame * sizeof(unsigned) > G.d_tiles.bytes)
     {
-        if (G.d_tiles) HIPCHK(hipFree(G.d_tiles));
-        G.d_tiles = nullptr; G.tiles_cap = 0; G.tiles_key.clear();
-        HIPCHK(hipMalloc((void**)&G.d_tiles, sh.per_frame * sizeof(unsigned)));
-        G.tiles_cap = sh.per_frame;
+        G.tiles_key.clear();
+        HIPCHK(G.d_tiles.grow(sh.per_frame * sizeof(unsigned)));
     }
     unsigned* d_totals = G.d_tile_scratch + (size_t)3 * nblocks;
     const unsigned char* cls = nullptr;
     if (light && G.sub_shift)
     {
         // the classes of this image's pixels from the S x S finer pixels each of them samples (subpixel_class_k)
-        const size_t need = (size_t)p->width * p->height;
-        if (need > G.sub_cls_bytes)
-        {
-            if (G.d_sub_cls) HIPCHK(hipFree(G.d_sub_cls));
-            G.d_sub_cls = nullptr; G.sub_cls_bytes = 0;
-            HIPCHK(hipMalloc((void**)&G.d_sub_cls, need));
-            G.sub_cls_bytes = need;
-        }
+        HIPCHK(G.d_sub_cls.grow((size_t)p->width * p->height));
         launch_subpixel_classes(table, p->width, p->height, (unsigned)G.sub_shift, G.d_sub_cls, G.stream);
         HIPCHK(hipGetLastError());
         cls = G.d_sub_cls;
