@@ -2,6 +2,9 @@
 // render whose reduce also takes the statistics; vp_render_adaptive, serial rounds of do_render on the ACTIVE pixels -- a compaction of
 // the context's cached lists by the FROZEN bit of the caller's records, before the first round and after each --; the output stage.
 // The integrator kernels are the plain calls', on shorter lists; the frozen set lives in the caller's buffer and nowhere else.
+// vp_denoise: the filter of the output stage that reads the records (vp_denoise.hip).
+#include <climits>
+
 #include "vp_state.h"
 
 static_assert(sizeof(vp_pixel_stats) == 24 && sizeof(vp::PixelStatsDev) == sizeof(vp_pixel_stats), "vp_pixel_stats layout (include/volpath.h)");
@@ -103,4 +106,30 @@ int vp_stats_rel_error(float* dst, const vp_pixel_stats* d_stats, int size, floa
     HIPCHK(hipGetLastError());
     return VP_OK;
 }
+int vp_denoise(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
+               int width, int height, const vp_denoise_params* dp)
+{
+    if (!dst || !src || !d_stats || !dp) return fail(VP_E_ARG, "vp_denoise: null pointer");
+    if (!guide != !d_guide_stats) return fail(VP_E_ARG, "vp_denoise: guide and d_guide_stats are given together or not at all");
+    if (dst == src || dst == guide) return fail(VP_E_ARG, "vp_denoise: in place is not possible (the call reads neighbours)");
+    if (width < 1 || height < 1 || (long long)width * height > INT_MAX) return fail(VP_E_ARG, "vp_denoise: image %d x %d", width, height);
+    if (dp->radius < 0 || dp->radius > VP_DENOISE_MAX_RADIUS) return fail(VP_E_ARG, "vp_denoise: radius %d outside 0..%d", dp->radius, VP_DENOISE_MAX_RADIUS);
+    if (dp->patch < 0 || dp->patch > VP_DENOISE_MAX_PATCH) return fail(VP_E_ARG, "vp_denoise: patch %d outside 0..%d", dp->patch, VP_DENOISE_MAX_PATCH);
+    if (!std::isfinite(dp->k) || !(dp->k > 0.0f)) return fail(VP_E_ARG, "vp_denoise: k must be a finite number > 0");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (!guide) { guide = src; d_guide_stats = d_stats; }
+    launch_denoise((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, width, height,
+                   dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
+    HIPCHK(hipGetLastError());
+    G.last_denoise_form = G.denoise_form;
+    return VP_OK;
+}
+int vp_set_denoise_form(int form)
+{
+    if (form != 0 && form != 1) return fail(VP_E_ARG, "vp_set_denoise_form: unknown form %d", form);
+    G.denoise_form = form;
+    return VP_OK;
+}
+int vp_last_denoise_form(void) { return G.last_denoise_form; }
 }  // extern "C"

@@ -1,0 +1,220 @@
+// vp_denoise.hip -- the variance-guided NL-means filter of the output stage (include/volpath.h vp_denoise).
+//
+// Both kernels compute the definition of the header to the bit: binary32, no contraction, the patch distance as row sums left to
+// right and their sum top to bottom, the weights summed over the offsets in raster order, expf_ in the exact arithmetic (this file
+// is compiled without VP_ARITH_FAST, like the output stage of vp_kernels.hip).
+//   denoise_tiled_k (form 0): one 256-thread workgroup per 32 x 8 pixel tile.  (y, v) of the tile plus an R + F halo and the mean
+//     colours of the tile plus an R halo are staged in LDS once, fetched with clamped coordinates; per offset the pair terms e of the
+//     tile's F-halo plane are computed once each into LDS (2.1 per thread at F = 3 instead of 49) and every thread sums its patch
+//     from there.  The plane is double buffered: one barrier per offset.
+//   denoise_plain_k (form 1): one thread per pixel, straight from global memory, looping over the definition.  The cross-check.
+// LDS layout (cdna_hip_programming.md section 2: ds_read_b32 / ds_write_b32 bank = dword address mod 32 within a 32-lane half):
+// every plane is one float per element, structure of arrays, and a half-wave is one tile row, so the patch reads and the colour
+// reads of a half-wave are 32 consecutive dwords whatever the pitch.  The fill of the e plane walks it linearly, so a half-wave can
+// straddle two of its rows; the pitch of the (y, v) planes is the e plane's plus 32, which makes the dword addresses of such a
+// half-wave consecutive mod 32 again.
+#include <hip/hip_runtime.h>
+
+#include "vp_kernels.h"
+#include "vp_math.h"
+
+namespace vp
+{
+namespace
+{
+constexpr int DN_TX = 32, DN_TY = 8;   // the tile: a half-wave per row
+constexpr float DN_EPS = 1e-20f;
+
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
+// s = 1 / n (0 where n == 0) and the mean colour A.xyz * s: the bits of scale_by_count_k with scale 1.0f
+__device__ __forceinline__ float inv_count(unsigned n) { return n ? 1.0f / (float)n : 0.0f; }
+__device__ __forceinline__ float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+// variance of the mean luminance, binary64, rounded once
+__device__ __forceinline__ float mean_variance(const PixelStatsDev& T)
+{
+    if (T.n < 2u) return 0.0f;
+    const double nd  = (double)T.n;
+    const double lhs = nd * T.sum_y2 - T.sum_y * T.sum_y;
+    return (float)((lhs > 0.0 ? lhs : 0.0) / (nd * nd * (nd - 1.0)));
+}
+// (y, v) of the pair (accumulator, records) at pixel i
+__device__ __forceinline__ void guide_yv(const float4* acc, const PixelStatsDev* stats, int i, float& y, float& v)
+{
+    const PixelStatsDev T = stats[i];
+    const float4 A = acc[i];
+    const float  s = inv_count(T.n);
+    y = luminance(A.x * s, A.y * s, A.z * s);
+    v = mean_variance(T);
+}
+__device__ __forceinline__ float pair_term(float ya, float va, float yb, float vb, float k2)
+{
+    const float d = ya - yb;
+    return (d * d - (va + (vb < va ? vb : va))) / (DN_EPS + k2 * (va + vb));
+}
+__device__ __forceinline__ float patch_weight(float D, float inv_area)
+{
+    D = D * inv_area;
+    D = D > 0.0f ? D : 0.0f;
+    return expf_(-D);
+}
+
+template <int F>
+__global__ __launch_bounds__(DN_TX * DN_TY) void denoise_tiled_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
+                                                                  const PixelStatsDev* gstats, int W, int H, int R, float k2)
+{
+    constexpr int EW = DN_TX + 2 * F, EH = DN_TY + 2 * F;   // the e plane: the tile plus an F halo
+    constexpr int YW = EW + 32;                             // pitch of the (y, v) planes (>= DN_TX + 2 (R + F) for R <= 16)
+    extern __shared__ float lds[];
+    const int YH = DN_TY + 2 * (R + F), CW = DN_TX + 2 * R, CH = DN_TY + 2 * R;
+    float* Ly = lds;
+    float* Lv = Ly + YW * YH;
+    float* Lc = Lv + YW * YH;             // three planes of CW * CH
+    float* Le = Lc + 3 * CW * CH;         // two planes of EW * EH
+    const int tid = threadIdx.x, tx = tid & (DN_TX - 1), ty = tid / DN_TX;
+    const int x0 = blockIdx.x * DN_TX, y0 = blockIdx.y * DN_TY;
+    const int px = x0 + tx, py = y0 + ty;
+    const bool inside = px < W && py < H;
+    const int  pi = clampi(py, H - 1) * W + clampi(px, W - 1);
+    // the thread's own pixel: mean colour, heat and the guide's variance
+    const float4 A  = src[pi];
+    const float  sp = inv_count(stats[pi].n);
+    const float  vme = mean_variance(gstats[pi]);
+    float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
+    // a tile without a noisy pixel (the per-pixel-constant classes) is the plain output stage
+    if (!__syncthreads_or(inside && vme != 0.0f))
+    {
+        if (inside) dst[pi] = out;
+        return;
+    }
+    const int halo = R + F;
+    for (int i = tid; i < (DN_TX + 2 * halo) * YH; i += DN_TX * DN_TY)
+    {
+        const int r = i / (DN_TX + 2 * halo), c = i - r * (DN_TX + 2 * halo);
+        float y, v;
+        guide_yv(guide, gstats, clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1), y, v);
+        Ly[r * YW + c] = y;
+        Lv[r * YW + c] = v;
+    }
+    for (int i = tid; i < CW * CH; i += DN_TX * DN_TY)
+    {
+        const int r = i / CW, c = i - r * CW;
+        const int g = clampi(y0 - R + r, H - 1) * W + clampi(x0 - R + c, W - 1);
+        const float4 B = src[g];
+        const float  s = inv_count(stats[g].n);
+        Lc[i] = B.x * s;
+        Lc[CW * CH + i] = B.y * s;
+        Lc[2 * CW * CH + i] = B.z * s;
+    }
+    __syncthreads();
+    const bool  filtered = inside && vme != 0.0f;
+    const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
+    float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
+    int buf = 0;
+    for (int oy = -R; oy <= R; oy++)
+        for (int ox = -R; ox <= R; ox++, buf ^= 1)
+        {
+            float* E = Le + buf * (EW * EH);
+            const int shift = oy * YW + ox;
+            for (int i = tid; i < EW * EH; i += DN_TX * DN_TY)
+            {
+                const int r = i / EW, c = i - r * EW;
+                const int a = (r + R) * YW + (c + R);
+                E[i] = pair_term(Ly[a], Lv[a], Ly[a + shift], Lv[a + shift], k2);
+            }
+            __syncthreads();   // (the other buffer is written next: its readers passed this barrier)
+            const int qx = px + ox, qy = py + oy;
+            if (filtered && qx >= 0 && qx < W && qy >= 0 && qy < H)
+            {
+                float D = 0.0f;
+#pragma unroll
+                for (int dy = 0; dy <= 2 * F; dy++)
+                {
+                    float row = 0.0f;
+#pragma unroll
+                    for (int dx = 0; dx <= 2 * F; dx++) row = row + E[(ty + dy) * EW + tx + dx];
+                    D = D + row;
+                }
+                const float w = patch_weight(D, inv_area);
+                const int   ci = (ty + R + oy) * CW + tx + R + ox;
+                den = den + w;
+                nr  = nr + w * Lc[ci];
+                ng  = ng + w * Lc[CW * CH + ci];
+                nb  = nb + w * Lc[2 * CW * CH + ci];
+            }
+        }
+    if (filtered) { out.x = nr / den; out.y = ng / den; out.z = nb / den; }
+    if (inside) dst[pi] = out;
+}
+
+__global__ __launch_bounds__(256) void denoise_plain_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
+                                                       const PixelStatsDev* gstats, int W, int H, int R, int F, float k2)
+{
+    const int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= W * H) return;
+    const int py = idx / W, px = idx - py * W;
+    const float4 A  = src[idx];
+    const float  sp = inv_count(stats[idx].n);
+    float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
+    if (mean_variance(gstats[idx]) != 0.0f)
+    {
+        const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
+        float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
+        for (int oy = -R; oy <= R; oy++)
+            for (int ox = -R; ox <= R; ox++)
+            {
+                const int qx = px + ox, qy = py + oy;
+                if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                float D = 0.0f;
+                for (int dy = -F; dy <= F; dy++)
+                {
+                    float row = 0.0f;
+                    for (int dx = -F; dx <= F; dx++)
+                    {
+                        float ya, va, yb, vb;
+                        guide_yv(guide, gstats, clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1), ya, va);
+                        guide_yv(guide, gstats, clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1), yb, vb);
+                        row = row + pair_term(ya, va, yb, vb, k2);
+                    }
+                    D = D + row;
+                }
+                const float  w = patch_weight(D, inv_area);
+                const int    q = qy * W + qx;
+                const float4 B = src[q];
+                const float  s = inv_count(stats[q].n);
+                den = den + w;
+                nr  = nr + w * (B.x * s);
+                ng  = ng + w * (B.y * s);
+                nb  = nb + w * (B.z * s);
+            }
+        out.x = nr / den; out.y = ng / den; out.z = nb / den;
+    }
+    dst[idx] = out;
+}
+}  // namespace
+
+size_t denoise_lds_bytes(int R, int F)
+{
+    const size_t yv = (size_t)(DN_TX + 2 * F + 32) * (DN_TY + 2 * (R + F));
+    const size_t c  = (size_t)(DN_TX + 2 * R) * (DN_TY + 2 * R);
+    const size_t e  = (size_t)(DN_TX + 2 * F) * (DN_TY + 2 * F);
+    return (2 * yv + 3 * c + 2 * e) * sizeof(float);
+}
+void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, int W, int H, int R,
+                    int F, float k2, int form, hipStream_t st)
+{
+    if (form == 1)
+    {
+        hipLaunchKernelGGL(denoise_plain_k, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, st, dst, src, stats, guide, gstats, W, H, R, F, k2);
+        return;
+    }
+    const dim3   grid((W + DN_TX - 1) / DN_TX, (H + DN_TY - 1) / DN_TY), block(DN_TX * DN_TY);
+    const size_t lds = denoise_lds_bytes(R, F);
+    switch (F)
+    {
+    case 0: hipLaunchKernelGGL(denoise_tiled_k<0>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
+    case 1: hipLaunchKernelGGL(denoise_tiled_k<1>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
+    case 2: hipLaunchKernelGGL(denoise_tiled_k<2>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
+    default: hipLaunchKernelGGL(denoise_tiled_k<3>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
+    }
+}
+}  // namespace vp

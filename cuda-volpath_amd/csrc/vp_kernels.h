@@ -221,6 +221,11 @@ void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned wi
                            unsigned* d_totals, unsigned* d_out, hipStream_t st);
 void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st);
 void launch_stats_rel_error(float* dst, const PixelStatsDev* stats, int size, float floor_y, hipStream_t st);
+// the NL-means filter of the output stage (vp_denoise.hip; include/volpath.h vp_denoise): weights from (guide, gstats), colours from
+// (src, stats), k2 = k * k; form 0 tiled through LDS (denoise_lds_bytes(R, F) of it per workgroup), 1 one thread per pixel from global memory
+size_t denoise_lds_bytes(int R, int F);
+void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, int W, int H, int R,
+                    int F, float k2, int form, hipStream_t st);
 // bricks: cells in 4x4x4 bricks (vp_device.h cell_index); the buffer then holds ceil(n/4)^3 * 64 cells
 void launch_pack_u8(const unsigned char* vol, uint2* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);
 void launch_pack_f32(const float* vol, float* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);

@@ -233,6 +233,7 @@ struct State
     int         last_lds_form = 0;            // vp_last_lds_form
     int         arith       = VP_ARITH_EXACT;   // vp_set_arithmetic: the general class's integrator in the exact or the fast arithmetic
     int         last_arith  = VP_ARITH_EXACT;   // vp_last_arithmetic
+    int         denoise_form = 0, last_denoise_form = 0;   // vp_set_denoise_form / vp_last_denoise_form
     // vp_set_subpixel: log2 of the sub-pixel factor S (0 = off).  With S > 1 the per-pixel table (d_crawl) is the S W x S H image's,
     // d_sub_cls holds the classes of the W x H image's pixels reduced from it (subpixel_class_k) and the pixel lists are built from those
     int         sub_shift   = subpixel_env_shift();

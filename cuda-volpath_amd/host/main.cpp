@@ -4,6 +4,7 @@
 // scale / gamma_correct) and writes what the 'c' key captures (host.cpp:585-610): a .ppm of the
 // gamma-corrected image or a .hdr of the scaled accumulator.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -33,6 +34,11 @@ static void usage()
            "                                                at most TOL x max(mean, 1e-3), from --min-spp frames (default 16) on; --spp is the\n"
            "                                                maximum.  The image is sum / n per pixel; --noise-out writes the noise map\n"
            "                                                (vp_stats_rel_error) as HDR.  One GPU: statistics are not reduced across ranks\n"
+           "               [--denoise [--denoise-radius R] [--denoise-patch F] [--denoise-k K]]\n"
+           "                                                --out receives the NL-means filtered mean image (vp_denoise: weights from the\n"
+           "                                                per-pixel luminance variance; search window (2R+1)^2, R <= 10, default 5; patch\n"
+           "                                                (2F+1)^2, F <= 3, default 1; strength K > 0, default 0.45).  The frames then go\n"
+           "                                                through vp_render_frames_stats (or --noise).  One GPU, like --noise\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -54,6 +60,8 @@ int main(int argc, char** argv)
     const float noise_floor = 1e-3f;
     int         min_spp = 16, round_frames = 32;   // (the round: not measured yet)
     std::string noise_out;
+    bool        denoise = false;
+    vp_denoise_params dn = {5, 1, 0.45f};   // (from a 64 x 48 table, not tuned: DESIGN.md section 2.4)
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -107,6 +115,27 @@ int main(int argc, char** argv)
         else if (a == "--min-spp") { need(1); min_spp = atoi(argv[++i]); }
         else if (a == "--round") { need(1); round_frames = atoi(argv[++i]); }
         else if (a == "--noise-out") { need(1); noise_out = argv[++i]; }
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-radius" || a == "--denoise-patch" || a == "--denoise-k")
+        {
+            need(1);
+            char* end = nullptr;
+            const char* v = argv[++i];
+            bool ok;
+            if (a == "--denoise-k") { dn.k = strtof(v, &end); ok = end != v && !*end && std::isfinite(dn.k) && dn.k > 0.0f; }
+            else
+            {
+                const long n = strtol(v, &end, 10);
+                ok = end != v && !*end && n >= 0 && n <= (a == "--denoise-radius" ? VP_DENOISE_MAX_RADIUS : VP_DENOISE_MAX_PATCH);
+                (a == "--denoise-radius" ? dn.radius : dn.patch) = (int)n;
+            }
+            if (!ok)
+            {
+                fprintf(stderr, "%s %s: radius 0..%d, patch 0..%d, k a finite number > 0\n", a.c_str(), v, VP_DENOISE_MAX_RADIUS, VP_DENOISE_MAX_PATCH);
+                usage();
+                return 2;
+            }
+        }
         else if (a == "--sun") { need(2); sunx = (float)atof(argv[++i]); suny = (float)atof(argv[++i]); }
         else if (a == "--batch") { need(1); batch = atoi(argv[++i]); }
         else if (a == "--out") { need(1); out = argv[++i]; }
@@ -134,6 +163,11 @@ int main(int argc, char** argv)
     if (adaptive && gpus > 1)
     {
         fprintf(stderr, "--noise with --gpus %d: reducing per-pixel statistics across ranks is not part of adaptive sampling; use one GPU\n", gpus);
+        return 2;
+    }
+    if (denoise && gpus > 1)
+    {
+        fprintf(stderr, "--denoise with --gpus %d: the filter reads per-pixel statistics, which are not reduced across ranks; use one GPU\n", gpus);
         return 2;
     }
     if (adaptive && (min_spp < 2 || round_frames < 1)) { fprintf(stderr, "--noise needs --min-spp >= 2 and --round >= 1\n"); usage(); return 2; }
@@ -236,6 +270,12 @@ int main(int argc, char** argv)
         const vp_adaptive ad = {noise_tol, noise_floor, min_spp, round_frames};
         if (vp_render_adaptive(accum[0], stats, 0, spp, &P, &ad, &ares)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
     }
+    if (denoise && !adaptive)
+    {
+        // the filter needs the records: the frames go through vp_render_frames_stats (the same accumulator bits)
+        stats = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
+        if (!stats || vp_memset(stats, 0, (size_t)npix * sizeof(vp_pixel_stats))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+    }
     for (int s = adaptive ? spp : 0; s < spp;)
     {
         if (!have_opacity && est == VP_EST_DECOMP && (s > 10 || (batch > 0 && s + batch > 11)))
@@ -243,7 +283,13 @@ int main(int argc, char** argv)
             for (int r = 0; r < gpus; r++) { use(r); precompute_opacity(&sky.sun_dir.x); }  // host.cpp:336-343
             have_opacity = true;
         }
-        if (batch > 0)
+        if (denoise)
+        {
+            const int n = batch > 0 ? std::min(batch, spp - s) : 1;
+            if (vp_render_frames_stats(accum[0], stats, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            s += n;
+        }
+        else if (batch > 0)
         {
             int n = std::min(batch, spp - s);
             for (int r = 0; r < gpus; r++)  // asynchronous: every rank's launch is queued before any is waited for
@@ -291,7 +337,14 @@ int main(int argc, char** argv)
     use(0);
     bool  hdr = out.size() > 4 && out.substr(out.size() - 4) == ".hdr";
     Image image(W, H);
-    if (adaptive)
+    if (denoise)
+    {
+        // the filtered mean image: the division by each pixel's count is part of the call
+        if (vp_denoise(disp, accum[0], stats, nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
+        printf("denoised: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
+    }
+    else if (adaptive)
     {
         // every pixel by its own count (the reference's scale assumes one count for all)
         if (vp_scale_by_count(disp, accum[0], stats, npix, 1.0f)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }

@@ -31,6 +31,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_set_estimator", "vp_set_rng", "vp_set_envmap_sampling", "vp_get_env_tables", "vp_set_lookahead", "vp_set_tracking", "vp_set_bound_brick", "vp_set_shard", "vp_render_frames",
                  "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists",
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
+                 "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_intersect_box",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -86,6 +87,14 @@ class AdaptiveResult(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class DenoiseParams(C.Structure):
+    """include/volpath.h vp_denoise_params"""
+    _fields_ = [("radius", C.c_int), ("patch", C.c_int), ("k", C.c_float)]
+
+
+DENOISE_MAX_RADIUS, DENOISE_MAX_PATCH = 10, 3
+
+
 class VolpathError(RuntimeError):
     pass
 
@@ -117,6 +126,8 @@ def lib():
         L.vp_render_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param), C.POINTER(Adaptive), C.POINTER(AdaptiveResult)]
         L.vp_scale_by_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float]
         L.vp_stats_rel_error.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
+        L.vp_denoise.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(DenoiseParams)]
+        L.vp_set_denoise_form.argtypes = [C.c_int]
         L.vp_read_counters.argtypes = [C.POINTER(Counters), C.c_int]
         L.vp_render_time_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
         L.vp_get_bound_table.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 5
@@ -395,6 +406,22 @@ def stats_rel_error(stats_ptr, width, height, floor_y=1e-3):
     finally:
         lib().vp_free(d)
     return out
+
+
+def denoise(dst_ptr, src_ptr, stats_ptr, width, height, radius=5, patch=1, k=0.45, guide_ptr=None, guide_stats_ptr=None):
+    """dst = the NL-means filtered MEAN image of the accumulator src and its records (vp_denoise): weights from the guide pair
+    (default: src itself), colours from src; queued on the context's stream, never synchronises"""
+    dp = DenoiseParams(radius, patch, k)
+    _chk(lib().vp_denoise(dst_ptr, src_ptr, stats_ptr, guide_ptr, guide_stats_ptr, width, height, C.byref(dp)))
+
+
+def set_denoise_form(form):
+    """test hook: 0 tiled through LDS (default), 1 one thread per pixel from global memory; the same bits"""
+    _chk(lib().vp_set_denoise_form(form))
+
+
+def last_denoise_form():
+    return lib().vp_last_denoise_form()
 
 
 def enable_counters(on=True):

@@ -292,6 +292,50 @@ int vp_render_adaptive(vp_float4* d_output, vp_pixel_stats* d_stats, int first_f
 int vp_scale_by_count(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, int size, float scale);
 int vp_stats_rel_error(float* dst, const vp_pixel_stats* d_stats, int size, float floor_y);
 
+/* vp_denoise: a variance-guided non-local-means filter for the output stage (the reference's other output stage, scaledOutput ->
+ * denoise -> gamma_correct, is OptiX; this is what stands in its place: the NL-means filter with a variance-cancelled patch distance
+ * of Rousselle, Knaus and Zwicker 2012, which needs exactly the per-pixel records above).  `src` is an accumulator of sums and
+ * d_stats its records; dst receives a MEAN image (the division by the count is part of the call).  The pair (guide, d_guide_stats)
+ * supplies the weights, `src` the colours; both NULL: the guide is src itself.  With two half-buffers (even frames in one, odd
+ * frames in the other) a caller cross-filters: two calls with the roles swapped, then vp_accumulate and scale.
+ *   Everything is binary32, no contraction, operations in the order written, unless marked binary64.  min(a, b) is a < b ? a : b,
+ *   max(a, b) is a > b ? a : b, clamp() clamps a coordinate pair into the image.  Per pixel a of a pair (accumulator A, records T):
+ *     s_a = T.n == 0 ? 0 : 1.0f / (float)T.n          c_a = A.xyz * s_a   (the bits vp_scale_by_count(..., 1.0f) writes)
+ *     y_a = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z                                          (of the guide pair)
+ *     v_a = variance of the mean luminance from the guide's records, binary64 rounded once:  nd = (double)n;
+ *           lhs = nd * sum_y2 - sum_y * sum_y;  v = (float)(max(lhs, 0.0) / (nd * nd * (nd - 1.0)));  n < 2 gives 0.  `flags` is never read.
+ *   Pair term for unclamped positions a, b with a' = clamp(a), b' = clamp(b), eps = 1e-20f, k2 = k * k:
+ *     e(a, b) = ((y_a' - y_b') * (y_a' - y_b') - (v_a' + min(v_b', v_a'))) / (eps + k2 * (v_a' + v_b'))
+ *   Patch distance of pixel p and offset o, F = patch: row sums first, for ty = -F..F
+ *     row_ty = sum over tx = -F..F, left to right, starting from 0.0f, of e(p + (tx, ty), p + o + (tx, ty))
+ *     D = sum over ty, top to bottom, starting from 0.0f, of row_ty;   D = max(D * (1.0f / (float)((2F+1) * (2F+1))), 0.0f)
+ *     w = expf_(-D), the exact-mode exponential of the integrator whatever vp_set_arithmetic says (as for scale and gamma_correct)
+ *   dst[p].xyz = (sum over o of w * c_(p+o)) / (sum over o of w): both sums start from 0.0f and run over oy = -R..R (outer) and
+ *   ox = -R..R (inner), R = radius; offsets whose p + o lies outside the image are skipped; per channel num = num + w * c; one
+ *   correctly rounded divide per channel.  The two sum orders are fixed so that a shared pass over a tile and a per-thread loop give
+ *   the same bits (running sums would not, and are not used).
+ *   Exceptions: where the guide's v_p == 0 -- a noise-free or unmeasured pixel, every per-pixel-constant class -- dst[p].xyz = c_p,
+ *   unfiltered.  dst[p].w = src[p].w * s_p always: the heat channel is never filtered.
+ *   Inputs are assumed finite; then no NaN arises (e >= -1 / k2, and the centre weight is exactly 1: the denominator is >= 1).
+ *   Refused with VP_E_ARG before the device is touched: NULL dst, src, d_stats or dp; exactly one of the two guide pointers; dst == src
+ *   or dst == guide (the call reads neighbours: in place is not possible); width or height < 1; radius outside
+ *   0..VP_DENOISE_MAX_RADIUS; patch outside 0..VP_DENOISE_MAX_PATCH; k not finite or not > 0.
+ *   Needs no scene (it works before init_cuda, like scale); runs asynchronously on the context's stream, behind the renders queued
+ *   there; never synchronises.
+ * What this is and is not: the filter sees LUMINANCE variance only -- purely chromatic noise is invisible to it.  Like every such
+ * filter it trades variance for bias.  Weights taken from the buffer they filter are correlated with it: the guide pair is the
+ * remedy.  The variance estimates themselves are not pre-filtered.  The exact-parity product stays vp_render_frames plus scale.
+ * vp_set_denoise_form (test hook): 0 = one workgroup per pixel tile, (y, v), the colours and the pair terms of an offset shared through
+ * LDS (default); 1 = one thread per pixel from global memory.  The same bits.  vp_last_denoise_form: the form of the last call. */
+typedef struct { int radius, patch; float k; } vp_denoise_params;   /* search window (2R+1)^2, patch (2F+1)^2, strength */
+#define VP_DENOISE_MAX_RADIUS 10
+#define VP_DENOISE_MAX_PATCH  3
+int vp_denoise(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats,
+               const vp_float4* guide, const vp_pixel_stats* d_guide_stats,      /* both NULL: guide = src */
+               int width, int height, const vp_denoise_params* dp);
+int vp_set_denoise_form(int form);
+int vp_last_denoise_form(void);
+
 typedef struct
 {
     uint64_t samples;
