@@ -88,6 +88,16 @@ __host__ __device__ __forceinline__ unsigned wang_hash(unsigned seed)
     return seed;
 }
 
+// A stream's 32-bit word as a float in [0, 1): the 23 high bits under the exponent of 1.0f, less 1.  The word
+// 0x3f800000 | (w >> 9) is the 64-bit value (0x7f : w) shifted right by nine: one v_alignbit_b32 instead of a shift and an or.
+// For the Philox streams only: v_alignbit_b32 issues at nearly the cost of the two (1.97 against 2.32 ns per wave-instruction and
+// SIMD), and in the sampler.h kernels, whose word() is alignbits and a full multiply already, it LOST 2.4 % (c3ref on sampler.h:
+// 267.4 against 261.1 ms per step; profiles/experiments/r11_tracking_step.txt) -- RngSamplerH::next keeps the shift and the or.
+__device__ __forceinline__ float draw_to_float(unsigned w)
+{
+    return u2f(__builtin_amdgcn_alignbit(0x7fu, w, 9u)) - 1.0f;
+}
+
 // sampler.h-compatible stream (parity mode; quirk Q2)
 struct RngSamplerH
 {
@@ -150,9 +160,9 @@ struct RngPhiloxR
         }
         w1 = c1;
         pair++;
-        return u2f(0x3f800000u | (c0 >> 9)) - 1.0f;
+        return draw_to_float(c0);
     }
-    __device__ __forceinline__ float next_b() { return u2f(0x3f800000u | (w1 >> 9)) - 1.0f; }
+    __device__ __forceinline__ float next_b() { return draw_to_float(w1); }
     // discard n pairs: the counter moves, nothing is computed
     __device__ __forceinline__ void skip(unsigned n) { pair += n; }
     // A shadow ray draws from a sub-stream of its own: pair indices 0x80000000 + (id << 20) + 0, 1, 2, ... with
@@ -188,9 +198,11 @@ __device__ __forceinline__ void axis_linear(float pn, int n, int& i, float& fw)
     float xb = fma_(pn, (float)n, -0.5f);  // the unit's own scaling: one rounding
     // below the first texel centre both taps clamp to texel 0: the same as sitting exactly on it (i = 0, w = 0)
     xb       = __builtin_fmaxf(xb, 0.0f);
-    float fl = __builtin_floorf(xb);
-    float fr = xb - fl;
-    i        = (int)fl;
+    // xb >= 0: xb - floorf(xb) is exact and below 1, so v_fract_f32 (which clamps its result below 1) gives the same bits, and the
+    // conversion truncates toward zero, which is the floor.  (axis_linear_f32 below cannot do this: its xb may be negative, and
+    // for a tiny negative xb the difference rounds to 1.0f where the instruction clamps.)
+    float fr = __builtin_amdgcn_fractf(xb);
+    i        = (int)xb;
     fw       = __builtin_floorf(fma_(fr, 256.0f, 0.5f)) * (1.0f / 256.0f);  // round-to-nearest of fr*256, /256
     // the packed cell of voxel i already holds the clamped (i, i+1) pair
     i = i > n - 1 ? n - 1 : i;

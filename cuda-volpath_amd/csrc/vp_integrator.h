@@ -69,7 +69,8 @@ __device__ __forceinline__ unsigned lane_rank(unsigned long long mask)
 // Cold per-path state (round 4).  A path's radiance sum, the direction it resumes after a shadow ray, its sample
 // coordinates, scatter count, phase-function parameters and the stream position saved across a shadow ray are touched in the event
 // blocks and where a shadow ray ends -- never in the free-flight step.  In the plain kernels they live in LDS, one word per lane
-// and field (14 words: 14 KB per workgroup), so that the kernel fits SIX waves per SIMD (80 registers) where it held five:
+// and field (14 words: 14 KB per workgroup; 15 or 17 where the sun's light is summed in the event pass: DEFER in render_k), so that the
+// kernel fits SIX waves per SIMD (80 registers) where it held five:
 // +4 % on both estimators (profiles/experiments/r04_cold_state_in_lds.txt).  ColdVal / ColdF3 are that word or triple in LDS
 // (COLD = true) or an ordinary variable (the LDS-table kernel, whose LDS is the table's, and the light kernels, which fit seven
 // or eight waves as they are).
@@ -271,6 +272,14 @@ void render_k(SceneDev S, LaunchDev L)
     // event pass anyway, lanes that have counted K are tested: one byte load, no loop, no parking.  Not for the bounded estimator (its
     // heat channel counts the segments of that walk), the scalar builds and MIS.
     constexpr bool EXITC = TRK == 0 && !MIS && !LIGHT && EST != EST_BOUNDED && (QUANT || EST == EST_GLOBAL);
+    // A lane whose collision is real parks with ro, rd and dist untouched: the collision point ro + rd * dist is formed where it is
+    // used, at the top of the collision block, not under `if (real)` in the tracking step -- where the assignment made the compiler
+    // keep two copies of the origin and move between them on every path, in all four unrolled steps.  The control collision of the
+    // decomposition estimator parks the same way, with dist = distc.  (The MIS kernels, which also keep the segment origin, do not.)
+    constexpr bool PARK = !MIS;
+    // DEFER: the sun's light of a shadow ray that ended in the tracking loop is added at the lane's next event visit (see the flush at
+    // the top of the event pass).  Spectral tracking only: the scalar builds keep the sum where the ray ends.
+    constexpr bool DEFER = EARLY && TRK == 0;
     const ParamDev& P = L.P;
     const f3    sig_t     = f3{P.sigma_t[0], P.sigma_t[1], P.sigma_t[2]};
     const f3    sig_s     = sig_t * f3{P.albedo[0], P.albedo[1], P.albedo[2]};
@@ -286,9 +295,12 @@ void render_k(SceneDev S, LaunchDev L)
     constexpr int  CS_  = COLD ? VP_BLOCK : 1;
     // (the occupancy these kernels are budgeted for holds only while that many workgroups' cold state fits the CU's LDS --
     // a workgroup is one wave per SIMD, so waves per SIMD = workgroups per CU; gfx950: 160 KiB)
-    static_assert(!COLD || (LOCAL ? VP_LOCAL_MIN_WAVES : VP_GLOBAL_MIN_WAVES) * (14 * VP_BLOCK * 4 + KARG_WDS_ * 4 + VP_COLL_ROWS * CR_WORDS * 4 + (LDSB == 2 ? VP_LDS_BOUND_ENTRIES / 4 : 0)) <= VP_LDS_BYTES_PER_CU,
+    // DEFER: the light weight of the shadow ray in flight takes the place of `ph` (one word, achromatic) or that word and two more
+    // (chromatic); one more word holds the ended ray's termination bits until the event pass has added its light
+    constexpr int NCOLD = 14 + (DEFER ? (ACH ? 1 : 3) : 0);
+    static_assert(!COLD || (LOCAL ? VP_LOCAL_MIN_WAVES : VP_GLOBAL_MIN_WAVES) * (NCOLD * VP_BLOCK * 4 + KARG_WDS_ * 4 + VP_COLL_ROWS * CR_WORDS * 4 + (LDSB == 2 ? VP_LDS_BOUND_ENTRIES / 4 : 0)) <= VP_LDS_BYTES_PER_CU,
                   "cold per-path state: more workgroups per CU than the LDS holds -- lower VP_*_MIN_WAVES for this ARCH");
-    __shared__ float cold_[COLD ? 14 : 1][CS_];
+    __shared__ float cold_[COLD ? NCOLD : 1][CS_];
     float* const cold_p = &cold_[0][COLD ? threadIdx.x : 0];
     ColdF3<COLD, CS_>       rad(cold_p), pd(cold_p + 3 * CS_);   // radiance sum; primary direction, kept while the shadow ray is tracked
     ColdVal<float, COLD>    ph(cold_p + 6 * CS_), phase_g(cold_p + 7 * CS_);
@@ -297,7 +309,13 @@ void render_k(SceneDev S, LaunchDev L)
     ColdVal<int, COLD>      frame(cold_p + 11 * CS_);
     ColdVal<int, COLD>      nsc(cold_p + 12 * CS_);              // num_scatters (DECOMP, BOUNDED) / depth i (GLOBAL)
     ColdVal<unsigned, COLD> rng_saved(cold_p + 13 * CS_);        // the path's own stream position while a shadow ray draws from its sub-stream
+    // DEFER: lw = (ACH ? thr.x : thr) * ph, the weight of the sun's light at the last collision (lw_x in ph's word); light_bits = the
+    // termination bits of a shadow ray that has ended and whose light is not in `rad` yet, LIGHT_NONE otherwise
+    constexpr unsigned LIGHT_NONE = 0xffffffffu;
+    ColdVal<float, COLD>    lw_x(cold_p + 6 * CS_), lw_y(cold_p + (DEFER && !ACH ? 14 : 6) * CS_), lw_z(cold_p + (DEFER && !ACH ? 15 : 6) * CS_);
+    ColdVal<unsigned, COLD> light_bits(cold_p + (DEFER ? NCOLD - 1 : 6) * CS_);
     if (COLD) { rad = f3{0.0f, 0.0f, 0.0f}; pd = f3{0.0f, 0.0f, 0.0f}; ph = 0.0f; phase_g = 0.0f; item = 0u; px = 0u; py = 0u; frame = 0; nsc = 0; rng_saved = 0u; }
+    if (DEFER) { lw_x = 0.0f; if (!ACH) { lw_y = 0.0f; lw_z = 0.0f; } light_bits = LIGHT_NONE; }
     RNG      rng;
     f3       ro = {}, rd = {};   // the ray being tracked (primary, or the shadow ray while ST_SHADOW)
     f3       inv_rd = {};        // 1 / rd of the primary ray (decomposition set-up)
@@ -457,10 +475,27 @@ void render_k(SceneDev S, LaunchDev L)
         };
         // EARLY: the light estimate is known without a shadow ray (optical-depth table, or the ray misses the box)
         auto finish_light = [&]() __attribute__((always_inline)) {
-            rad = rad + sun_power * (((ACH ? f3{thr.x, thr.x, thr.x} : thr) * ph) * nee_a);
+            if (DEFER) rad = rad + sun_power * ((ACH ? f3{lw_x, lw_x, lw_x} : f3{lw_x, lw_y, lw_z}) * nee_a);
+            else rad = rad + sun_power * (((ACH ? f3{thr.x, thr.x, thr.x} : thr) * ph) * nee_a);
             rd  = pd;
             next_segment();
         };
+        // ---- DEFER: the sun's light of a shadow ray that ended in the tracking loop.  light_done() left the ray's termination bits;
+        // the sum is made here, for every lane that has one pending (lanes that ride along included), with the expression and the
+        // order of operations it had at the ray's end: thr does not change during a shadow ray, so lw holds the bits of the product
+        // formed there, and nothing adds to `rad` between the ray's end and this visit.  Before the collision block (whose
+        // finish_light() adds to `rad`), the exit-flight test and the path-end chain.  A zero transmittance is not skipped: inf * 0.
+        if (DEFER)
+        {
+            const unsigned lb = light_bits;
+            if (lb != LIGHT_NONE)
+            {
+                const int tb = (int)lb;
+                const f3  na = f3{(float)(1 - (tb & 1)), (float)(1 - ((tb >> 1) & 1)), (float)(1 - ((tb >> 2) & 1))};   // kernel.cu:807
+                rad          = rad + sun_power * ((ACH ? f3{lw_x, lw_x, lw_x} : f3{lw_x, lw_y, lw_z}) * na);
+                light_bits   = LIGHT_NONE;
+            }
+        }
         // ---- collision: direct lighting set-up (kernel.cu:2161-2217 / :1458-1491)
         tally(B_SCATTER, st == EV_SCATTER);
         if (!LIGHT && st == EV_SCATTER)
@@ -468,6 +503,7 @@ void render_k(SceneDev S, LaunchDev L)
             vp_pad<VP_PAD_COLL>();
             if (COUNT) c_sca++;
             if (PROF) zrun = 0;
+            if (PARK) ro = ro + rd * dist;   // the collision point: the lane parked with the step's ro, rd and dist (or distc)
             t_empty = 0.0f;  // the certificate is for the unscattered camera ray only
             if (LOCAL) nsc = nsc + 1;  // num_scatters += !through, kernel.cu:2146
             // "to match passive result": post-increment count (DECOMP :2168) / i-4 (GLOBAL :1465)
@@ -500,7 +536,13 @@ void render_k(SceneDev S, LaunchDev L)
                 dp2  = (1.0f - s2) * density + s2 * density * (1.0f - P.g);
                 stp2 = max_sig * dp2;
             }
-            ph = TAB ? hg_eval_row(rowp, dot(rd, sun_dir)) : hg_eval(phase_g, dot(rd, sun_dir));
+            const float phv = TAB ? hg_eval_row(rowp, dot(rd, sun_dir)) : hg_eval(phase_g, dot(rd, sun_dir));
+            if (DEFER)
+            {
+                lw_x = thr.x * phv;
+                if (!ACH) { lw_y = thr.y * phv; lw_z = thr.z * phv; }
+            }
+            else ph = phv;
             pd = rd;
             if (EARLY)
             {
@@ -517,9 +559,9 @@ void render_k(SceneDev S, LaunchDev L)
                 sh_density   = dp2;
                 nee_stage    = 0;
                 nee_c        = sun_power;
-                nee_t        = (ACH ? f3{thr.x, thr.x, thr.x} : thr) * ph;
+                nee_t        = (ACH ? f3{thr.x, thr.x, thr.x} : thr) * phv;
             }
-            // here ro already holds the collision point (set by the tracking step)
+            // here ro already holds the collision point (set at the top of this block, or by the tracking step)
             if (EST == EST_DECOMP && frame > 10 && nsc > 20)
             {
                 // precomputed optical depth kernel.cu:2183-2189 (quirk Q5)
@@ -1060,6 +1102,8 @@ ends_done:
             }
         };
         // EARLY: a shadow ray has ended (nee_a known): add the light and go on with the segment prepared in the collision block
+        // (DEFER: it leaves the termination bits for the event pass, which adds the light -- no conversion, no read of the sun's power,
+        // no sum here, where 5-10 of 64 lanes are active -- and goes on)
         auto light_done = [&]() __attribute__((always_inline)) {
 #ifdef VP_EXP_FLAT_KARGS
             const char* ka_ = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1069,9 +1113,13 @@ ends_done:
             asm volatile("" : "+v"(ko2_));
             const char* ka_ = reinterpret_cast<const char*>(kargs_lds_) + ko2_;
 #endif
-            const SceneDev& S2 = *reinterpret_cast<const SceneDev*>(ka_);
-            const f3 sunp = f3{S2.sun_power[0], S2.sun_power[1], S2.sun_power[2]};
-            rad = rad + sunp * (((ACH ? f3{thr.x, thr.x, thr.x} : thr) * ph) * nee_a);
+            if (DEFER) light_bits = (unsigned)terms;
+            else
+            {
+                const SceneDev& S2 = *reinterpret_cast<const SceneDev*>(ka_);
+                const f3 sunp = f3{S2.sun_power[0], S2.sun_power[1], S2.sun_power[2]};
+                rad = rad + sunp * (((ACH ? f3{thr.x, thr.x, thr.x} : thr) * ph) * nee_a);
+            }
             rd  = pd;
             if (EXITC) terms = reinterpret_cast<const LaunchDev*>(ka_ + KARG_L_)->exit_start;
             if (EST == EST_GLOBAL)
@@ -1166,7 +1214,7 @@ ends_done:
                     if (shadow)
                     {
                         // Tr_spectral returns 1 - terminated flags (kernel.cu:807)
-                        nee_a = f3{(float)(1 - (terms & 1)), (float)(1 - ((terms >> 1) & 1)), (float)(1 - ((terms >> 2) & 1))};
+                        if (!DEFER) nee_a = f3{(float)(1 - (terms & 1)), (float)(1 - ((terms >> 1) & 1)), (float)(1 - ((terms >> 2) & 1))};
                         st    = EV_NEE;
                         rng.leave_shadow(rng_saved);
                         if (EARLY) light_done();
@@ -1186,7 +1234,8 @@ ends_done:
                         else
                         {
                             if (MIS) seg_o = ro;
-                            ro = ro + rd * distc;  // control collision kernel.cu:2088
+                            if (PARK) dist = distc;  // control collision kernel.cu:2088: ro + rd * distc, formed in the collision block
+                            else ro = ro + rd * distc;
                             st = LIGHT ? EV_WRITE : EV_SCATTER;  // (LIGHT: excluded by the pixel class, which checks the brick minima)
                         }
                     }
@@ -1234,7 +1283,7 @@ ends_done:
                         if (e < den * inv_sigma)
                         {
                             if (shadow) { nee_a = f3{0.0f, 0.0f, 0.0f}; st = EV_NEE; rng.leave_shadow(rng_saved); if (EARLY) light_done(); }
-                            else { ro = p; st = EV_SCATTER; }
+                            else { if (!PARK) ro = p; st = EV_SCATTER; }
                         }
                     }
                     else if (shadow)
@@ -1266,7 +1315,7 @@ ends_done:
                         if (real)
                         {
                             if (MIS) seg_o = ro;
-                            ro = p;
+                            if (!PARK) ro = p;
                             st = LIGHT ? EV_WRITE : EV_SCATTER;  // (LIGHT: den = +0 makes `real` false)
                         }
                         else if (EXITC && den == 0.0f)
@@ -1299,7 +1348,7 @@ ends_done:
                         if (real)
                         {
                             if (MIS) seg_o = ro;
-                            ro = p;
+                            if (!PARK) ro = p;
                             st = LIGHT ? EV_WRITE : EV_SCATTER;  // (LIGHT: den = +0 makes `real` false)
                         }
                         else if (EXITC && den == 0.0f)

@@ -13,6 +13,7 @@ __global__ __launch_bounds__(256) void rate_k(unsigned long long* out, float see
     double d0 = a0, d1 = a1, d2 = a2, d3 = a3, d4 = a4, d5 = a5, d6 = a6, d7 = a7;
     if (OP == 49) asm volatile("s_mov_b64 vcc, 0x5555" ::: "vcc");
     if (OP == 36) asm volatile("s_mov_b64 s[10:11], 0x5555" ::: "s10", "s11");
+    if (OP == 64) asm volatile("s_mov_b32 s10, 0x7f" ::: "s10");
     unsigned long long t0 = __builtin_amdgcn_s_memtime();
     for (int i = 0; i < iters; i++)
     {
@@ -89,6 +90,9 @@ __global__ __launch_bounds__(256) void rate_k(unsigned long long* out, float see
         if (OP == 61) { R8F(asm volatile("v_sub_f32 %0, %0, %0" : "+v"(x));) }
         if (OP == 62) { R8F(asm volatile("v_min_f32 %0, %0, %0" : "+v"(x));) }
         if (OP == 63) { R8F(asm volatile("s_nop 0" ::: );) }
+        // a stream word as a float's bits, 0x3f800000 | (w >> 9): one alignbit with the 0x7f in a scalar register, against the shift and the or
+        if (OP == 64) { R8U(asm volatile("v_alignbit_b32 %0, s10, %0, 9" : "+v"(x) :: "s10");) }
+        if (OP == 65) { R8U(asm volatile("v_lshrrev_b32 %0, 9, %0\n v_or_b32 %0, 0x3f800000, %0" : "+v"(x));) }
     }
     unsigned long long t1 = __builtin_amdgcn_s_memtime();
     a0 += (float)(d0 + d1 + d2 + d3 + d4 + d5 + d6 + d7);
@@ -136,6 +140,7 @@ int main()
         RUN(44, "v_xad_u32"); RUN(45, "v_mov_b32"); RUN(46, "v_lshl_or_b32"); RUN(47, "v_mul_f64"); RUN(48, "v_med3_f32"); RUN(49, "v_cndmask_vcc_set");
         RUN(50, "cmp+cndmask_vcc(x2)"); RUN(51, "v_cndmask_e64_vcc"); RUN(52, "7fma+cndmask_vcc"); RUN(53, "6fma+cmp+cnd_vcc"); RUN(54, "6fma+cmp+cnd_sgpr"); RUN(55, "v_addc_co_u32");
         RUN(56, "v_bfi_b32"); RUN(57, "v_ashrrev_i32"); RUN(58, "v_mul_f32_lit"); RUN(59, "v_mul_f32_e64"); RUN(60, "v_add_f32_e64"); RUN(61, "v_sub_f32"); RUN(62, "v_min_f32"); RUN(63, "s_nop");
+        RUN(64, "v_alignbit_sgpr_9"); RUN(65, "lshr+or_lit(x2)");
     }
     return 0;
 }
