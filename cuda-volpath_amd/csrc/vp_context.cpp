@@ -802,6 +802,27 @@ struct DevArrays
         return q;
     }
 };
+int vp_test_roots(int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches, uint32_t* first_bad)
+{
+    if (which < 0 || which > 1) return fail(VP_E_ARG, "vp_test_roots: unknown helper %d (0 sqrt_inrange_, 1 rsqrt_unit_)", which);
+    if (lo_bits > hi_bits || !mismatches || !first_bad) return fail(VP_E_ARG, "vp_test_roots: bad range %08x..%08x or null result", lo_bits, hi_bits);
+    if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "vp_test_roots: the in-range helpers belong to the exact arithmetic");
+    int rc = ensure_device();
+    if (rc) return rc;
+    DevArrays D;
+    unsigned long long* dm = (unsigned long long*)D.get(8);
+    unsigned*           df = (unsigned*)D.get(4);
+    if (!dm || !df) return fail(VP_E_NOMEM, "vp_test_roots: no device memory");
+    HIPCHK(hipMemsetAsync(dm, 0, 8, G.stream));
+    HIPCHK(hipMemsetAsync(df, 0xff, 4, G.stream));
+    launch_test_roots(which, lo_bits, hi_bits, dm, df, G.stream);
+    HIPCHK(hipStreamSynchronize(G.stream));
+    unsigned long long m = 0;
+    HIPCHK(hipMemcpy(&m, dm, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(first_bad, df, 4, hipMemcpyDeviceToHost));
+    *mismatches = m;
+    return VP_OK;
+}
 int vp_test_hg(const float* g, const float* r0, const float* r1, const float* normal_xyz, const float* cos_query, float* dir_xyz, float* eval, int n)
 {
     int rc = ensure_device();

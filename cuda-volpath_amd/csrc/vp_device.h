@@ -26,6 +26,8 @@ __device__ __forceinline__ f3 cross(f3 a, f3 b)
 __device__ __forceinline__ f3 normalize(f3 v) { return v * rsqrt_(dot(v, v)); }
 // IEEE in both arithmetic modes: the camera ray, which the per-pixel tables are certified on
 __device__ __forceinline__ f3 normalize_ieee(f3 v) { return v * (1.0f / __builtin_sqrtf(dot(v, v))); }
+// normalize for a vector whose squared length is in [2^-8, 2] by construction (rsqrt_unit_, vp_math.h): the same bits
+__device__ __forceinline__ f3 normalize_unit(f3 v) { return v * rsqrt_unit_(dot(v, v)); }
 __device__ __forceinline__ float max3(f3 v) { return fmaxf(fmaxf(v.x, v.y), v.z); }
 __device__ __forceinline__ float min3(f3 v) { return fminf(fminf(v.x, v.y), v.z); }
 VP_ARITH_END
@@ -556,6 +558,7 @@ __host__ __device__ __forceinline__ void subpixel_offset(unsigned px, unsigned p
 }
 
 // Frame kernel.cu:557-573 (fabs(n.x) > 0.1 is a DOUBLE compare: equivalent to >= 0.1f in float)
+struct UnitNormal {};   // tag: the normal handed to Frame is the output of a normalize
 struct Frame
 {
     f3 n, t, b;
@@ -564,6 +567,18 @@ struct Frame
         n    = normal;
         f3 a = (__builtin_fabsf(n.x) >= 0.1f) ? f3{0.0f, 1.0f, 0.0f} : f3{1.0f, 0.0f, 0.0f};
         t    = normalize(cross(a, n));
+        b    = cross(n, t);
+    }
+    // The same frame for a normal of unit length (the integrator's ray directions: outputs of normalize, |n|^2 = 1 +- 1e-6).
+    // cross(a, n) is (n.z, 0, -n.x) on the |n.x| >= 0.1 branch: its squared length n.z^2 + n.x^2 is at least 0.0099 (0.1f squared,
+    // less the roundings) -- and (0, -n.z, n.y) on the other: n.z^2 + n.y^2 = |n|^2 - n.x^2 >= 0.98.  Both are at most |n|^2 < 2:
+    // inside rsqrt_unit_'s [2^-8, 2], where it returns the bits of the general form (vp_math.h).
+    __device__ __forceinline__ Frame(f3 normal, UnitNormal)
+    {
+        n    = normal;
+        f3 a = (__builtin_fabsf(n.x) >= 0.1f) ? f3{0.0f, 1.0f, 0.0f} : f3{1.0f, 0.0f, 0.0f};
+        f3 c = cross(a, n);
+        t    = c * rsqrt_unit_(dot(c, c));
         b    = cross(n, t);
     }
     __device__ __forceinline__ f3 to_world(f3 c) const { return (t * c.x + b * c.y) + n * c.z; }
@@ -582,7 +597,9 @@ __device__ __forceinline__ f3 hg_sample_local(float g, float rnd0, float rnd1)
     }
     else
         cos_theta = 2.0f * rnd0 - 1.0f;
-    float sin_theta = sqrt_(1.0f - cos_theta * cos_theta);
+    // cos_theta is in [-1, 1] (clamped to [0, 1] above; 2 rnd0 - 1 with rnd0 in [0, 1) otherwise): its square rounds to 1 or to at
+    // most 1 - 2^-24, the float below 1, so the difference (exact, by Sterbenz, for squares >= 0.5) is 0 or in [2^-24, 1]
+    float sin_theta = sqrt_inrange_(1.0f - cos_theta * cos_theta);
     float sp, cp;
     sincos_turns_(rnd1, sp, cp);   // of (2 pi) rnd1
     return f3{cp * sin_theta, sp * sin_theta, cos_theta};
@@ -653,7 +670,9 @@ __device__ __forceinline__ f3 hg_sample_local_row(const float* row, float rnd0, 
     }
     else
         cos_theta = 2.0f * rnd0 - 1.0f;
-    float sin_theta = sqrt_(1.0f - cos_theta * cos_theta);
+    // cos_theta is in [-1, 1] (clamped to [0, 1] above; 2 rnd0 - 1 with rnd0 in [0, 1) otherwise): its square rounds to 1 or to at
+    // most 1 - 2^-24, the float below 1, so the difference (exact, by Sterbenz, for squares >= 0.5) is 0 or in [2^-24, 1]
+    float sin_theta = sqrt_inrange_(1.0f - cos_theta * cos_theta);
     float sp, cp;
     sincos_turns_(rnd1, sp, cp);   // of (2 pi) rnd1
     return f3{cp * sin_theta, sp * sin_theta, cos_theta};

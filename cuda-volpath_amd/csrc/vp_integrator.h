@@ -409,7 +409,16 @@ void render_k(SceneDev S, LaunchDev L)
         // Tr_spectral set-up kernel.cu:763-780: shadow ray from the collision point ro toward `end`
         // stage: 0 = the sun ray, 1 = the environment ray of the one-sample MIS
         auto start_shadow = [&](f3 end, float inv_s, float den, unsigned stage) __attribute__((always_inline)) {
-            f3    sd = normalize(end - ro);
+            // the ray's length |end - ro| is the root normalize() takes: formed once (ro - end is -(end - ro) exactly, so the squares
+            // and their left-to-right sum are the same bits), then the reciprocal -- normalize's own v * (1.0f / sqrtf(dot(v, v)))
+            const f3    dv = end - ro;
+            const float d2 = dot(dv, dv);
+            const float len = sqrt_(d2);
+#ifdef VP_ARITH_FAST
+            f3 sd = dv * rsqrt_(d2);   // (the fast mode keeps its two instructions, v_sqrt_f32 and v_rsq_f32, and its bits)
+#else
+            f3 sd = dv * rcp_(len);
+#endif
             float tn, tf;
             bool  hitv = intersect_box(ro, sd, S, tn, tf);
             if (!hitv)
@@ -420,8 +429,7 @@ void render_k(SceneDev S, LaunchDev L)
             else
             {
                 if (tn < 0.0f) tn = 0.0f;
-                f3 se       = ro - end;
-                t_end       = fminf(tf, sqrt_(dot(se, se)));
+                t_end       = fminf(tf, len);
                 dist        = tn;
                 terms       = 0;
                 rd          = sd;
@@ -546,11 +554,15 @@ void render_k(SceneDev S, LaunchDev L)
             pd = rd;
             if (EARLY)
             {
-                // the direction the path takes up when the light estimate is in (kernel.cu:2301-2303)
-                Frame fr(rd);
+                // the direction the path takes up when the light estimate is in (kernel.cu:2301-2303).  In-range roots (vp_math.h):
+                // rd is the camera ray's normalize_ieee or an earlier collision's pd, i.e. the output of a normalize -- the frame's
+                // tangent has its range from that (vp_device.h Frame); the sampled vector is a unit local vector (sin^2 + cos^2 of
+                // hg_sample_local, 1 +- 2e-7) in a frame that is orthonormal to a few 1e-7, so its squared length is 1 +- 1e-5:
+                // inside rsqrt_unit_'s [2^-8, 2]
+                Frame fr(rd, UnitNormal{});
                 float r0 = rng.next_a();
                 float r1 = rng.next_b();
-                pd       = normalize(fr.to_world(TAB ? hg_sample_local_row(rowp, r0, r1) : hg_sample_local(phase_g, r0, r1)));
+                pd       = normalize_unit(fr.to_world(TAB ? hg_sample_local_row(rowp, r0, r1) : hg_sample_local(phase_g, r0, r1)));
                 if (LOCAL) { const f3 pdv = pd; inv_rd = f3{rcp_(pdv.x), rcp_(pdv.y), rcp_(pdv.z)}; }
             }
             if (MIS)
@@ -676,11 +688,11 @@ void render_k(SceneDev S, LaunchDev L)
         tally(B_HG, st == EV_HG);
         if (!LIGHT && !EARLY && st == EV_HG)
         {
-            Frame fr(pd);
+            Frame fr(pd, UnitNormal{});   // (pd: the colliding ray's direction, the output of a normalize; ranges as in the collision block)
             float r0 = rng.next_a();
             float r1 = rng.next_b();
             // (TAB: the row phase_g was set from -- the count has not moved since the collision)
-            rd       = normalize(fr.to_world(TAB ? hg_sample_local_row(coll_row((LOCAL ? (nsc - 5) : (nsc - 4)) - 1), r0, r1) : hg_sample_local(phase_g, r0, r1)));
+            rd       = normalize_unit(fr.to_world(TAB ? hg_sample_local_row(coll_row((LOCAL ? (nsc - 5) : (nsc - 4)) - 1), r0, r1) : hg_sample_local(phase_g, r0, r1)));
             if (LOCAL) inv_rd = f3{rcp_(rd.x), rcp_(rd.y), rcp_(rd.z)};
             next_segment();
         }

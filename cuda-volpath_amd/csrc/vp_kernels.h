@@ -242,6 +242,7 @@ void launch_test_hg(const float* g, const float* r0, const float* r1, const floa
 void launch_test_box(const SceneDev& S, const float* o, const float* d, int* hit, float* tn, float* tf, int n, hipStream_t st);
 void launch_test_env(const SceneDev& S, const float* d, float* out, int n, hipStream_t st);
 void launch_test_math(int which, const float* in, float* out, int n, hipStream_t st);
+void launch_test_roots(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad, hipStream_t st);   // (exact arithmetic only)
 // the same two hooks compiled in the fast arithmetic (vp_kernels_fast.hip)
 void launch_test_hg_fast(const float* g, const float* r0, const float* r1, const float* nrm, const float* cosq, float* dir, float* ev, int n, hipStream_t st);
 void launch_test_math_fast(int which, const float* in, float* out, int n, hipStream_t st);

@@ -1097,6 +1097,22 @@ __global__ void accumulate_k(float4* dst, const float4* src, size_t n)
 // ---- test kernels
 // test_hg_k, test_math_k: vp_test_kernels.h (compiled in both arithmetic modes)
 #include "vp_test_kernels.h"
+// vp_test_roots: the in-range root helpers of vp_math.h against the general forms compiled here, on every bit pattern in [lo, hi]
+__global__ void test_roots_k(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad)
+{
+    const unsigned long long n = (unsigned long long)hi - lo + 1ull;
+    unsigned long long bad = 0;
+    unsigned           fb  = 0xffffffffu;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x)
+    {
+        const unsigned b = lo + (unsigned)i;
+        const float    x = u2f(b);
+        const float    a = which ? rsqrt_unit_(x) : sqrt_inrange_(x);
+        const float    r = which ? 1.0f / __builtin_sqrtf(x) : __builtin_sqrtf(x);
+        if (f2u(a) != f2u(r)) { bad++; fb = b < fb ? b : fb; }
+    }
+    if (bad) { atomicAdd(mismatches, bad); atomicMin(first_bad, fb); }
+}
 // intersectBox kernel.cu:654-680 against the current volume box
 __global__ void test_box_k(SceneDev S, const float* o, const float* d, int* hit, float* tn, float* tf, int n)
 {
@@ -1626,6 +1642,10 @@ void launch_test_env(const SceneDev& S, const float* d, float* out, int n, hipSt
 void launch_test_math(int which, const float* in, float* out, int n, hipStream_t st)
 {
     hipLaunchKernelGGL(test_math_k, dim3((n + 255) / 256), dim3(256), 0, st, which, in, out, n);
+}
+void launch_test_roots(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad, hipStream_t st)
+{
+    hipLaunchKernelGGL(test_roots_k, dim3(2048), dim3(256), 0, st, which, lo, hi, mismatches, first_bad);
 }
 void launch_test_rng(int mode, unsigned x, unsigned y, unsigned f, unsigned k0, unsigned k1, int n, float* out, hipStream_t st)
 {

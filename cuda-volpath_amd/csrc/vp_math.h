@@ -163,11 +163,44 @@ __device__ __forceinline__ float div_(float a, float b) { return a * __builtin_a
 __device__ __forceinline__ float rcp_(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float sqrt_(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float rsqrt_(float x) { return __builtin_amdgcn_rsqf(x); }
+// (the in-range forms below belong to the exact mode: here they are the single instructions)
+__device__ __forceinline__ float sqrt_inrange_(float x) { return __builtin_amdgcn_sqrtf(x); }
+__device__ __forceinline__ float rsqrt_unit_(float x) { return __builtin_amdgcn_rsqf(x); }
 #else
 __device__ __forceinline__ float div_(float a, float b) { return a / b; }
 __device__ __forceinline__ float rcp_(float x) { return 1.0f / x; }
 __device__ __forceinline__ float sqrt_(float x) { return __builtin_sqrtf(x); }
 __device__ __forceinline__ float rsqrt_(float x) { return 1.0f / __builtin_sqrtf(x); }
+// The same root and reciprocal root for operands that are in range BY CONSTRUCTION at the call site (each site derives its range):
+// the compiler's own expansion of __builtin_sqrtf and of 1.0f / s without the steps that are identities there.  The square root
+// of binary32 is v_sqrt_f32 (1 ulp) and two one-ulp corrections, each decided by the sign of an exact fma residual; around them
+// the compiler scales operands below 2^-96 by 2^32 and passes 0, inf and NaN through a class test -- seven of sixteen instructions.
+// The quotient 1 / s is v_rcp_f32, one Newton step on the reciprocal, q = 1 * r, two residual corrections of q; around them two
+// v_div_scale (identities unless s or 1 / s is near the ends of the exponent range), v_div_fmas (an fma when nothing was scaled)
+// and v_div_fixup (passes the quotient through unless an operand is 0, inf or NaN).  A correctly rounded result is unique, so the
+// shortened forms return the bits of the general ones wherever their preconditions hold; vp_test_roots (include/volpath.h)
+// compares the two on every bit pattern of the stated ranges.
+// PRECONDITION: x == 0, or 2^-24 <= x <= 2.  (x = 0: v_sqrt_f32 gives 0; the lower neighbour's pattern is a NaN, whose residual
+// compares false; the upper neighbour's residual is fma(-2^-149, 0, 0) = 0, not positive: 0 is returned.)
+__device__ __forceinline__ float sqrt_inrange_(float x)
+{
+    float       s  = __builtin_amdgcn_sqrtf(x);
+    const float dn = u2f(f2u(s) - 1u), up = u2f(f2u(s) + 1u);
+    const float rd = fma_(-dn, s, x), ru = fma_(-up, s, x);
+    s = (rd <= 0.0f) ? dn : s;
+    s = (ru > 0.0f) ? up : s;
+    return s;
+}
+// PRECONDITION: 2^-8 <= x <= 2, so the root s lies in [2^-4, 1.42] and 1 / s in [0.70, 16].
+__device__ __forceinline__ float rsqrt_unit_(float x)
+{
+    const float s = sqrt_inrange_(x);
+    float       r = __builtin_amdgcn_rcpf(s);
+    r             = fma_(fma_(-s, r, 1.0f), r, r);
+    float q       = r;                                // the numerator 1 times r
+    q             = fma_(fma_(-s, q, 1.0f), r, q);
+    return fma_(fma_(-s, q, 1.0f), r, q);
+}
 #endif
 
 // sine and cosine of 2 pi t, t in [0, 1]: the azimuth of the phase-function sample (v_sin_f32 / v_cos_f32 take revolutions)

@@ -32,7 +32,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists",
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
-                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_intersect_box",
+                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_intersect_box",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
                  "vp_upload", "vp_download"]
@@ -143,6 +143,7 @@ def lib():
         L.vp_julia_voxelize.argtypes = [C.c_int, C.c_void_p]
         L.vp_cloud_voxelize.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
         L.vp_test_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.vp_test_roots.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.vp_test_rng.argtypes = [C.c_int] + [C.c_uint32] * 5 + [C.c_int, C.c_void_p]
         L.vp_test_sample_density.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.vp_test_hg.argtypes = [C.c_void_p] * 7 + [C.c_int]
@@ -591,6 +592,14 @@ def test_math(which, x):
     out = np.empty_like(x)
     _chk(lib().vp_test_math(which, _p(x), _p(out), x.size))
     return out
+
+
+def test_roots(which, lo_bits, hi_bits):
+    """(mismatches, first bad bit pattern or None) of the in-range root helper `which` (0 sqrt_inrange_, 1 rsqrt_unit_) against the
+    general form, over every binary32 bit pattern in [lo_bits, hi_bits]; walked on the device"""
+    m, f = C.c_uint64(0), C.c_uint32(0)
+    _chk(lib().vp_test_roots(which, lo_bits, hi_bits, C.byref(m), C.byref(f)))
+    return m.value, (None if m.value == 0 else f.value)
 
 
 def test_rng(mode, x, y, frame, n, key=(0, 0)):

@@ -440,6 +440,11 @@ int vp_get_null_collision_table(const Param* p, float* dst, size_t count);
  * arithmetic mode (vp_set_arithmetic), as its renders do.  vp_test_math refuses a `which` outside 0..11 and n < 0 with VP_E_ARG
  * before it touches the device. */
 int vp_test_math(int which, const float* in, float* out, int n);
+/* vp_test_roots: the exact arithmetic's in-range root helpers (vp_math.h: which = 0 sqrt_inrange_, 1 rsqrt_unit_) against the general
+ * forms (sqrtf(x), 1.0f / sqrtf(x)) on EVERY binary32 bit pattern in [lo_bits, hi_bits], walked on the device: *mismatches = how many
+ * patterns differ, *first_bad = the lowest of them (0xffffffff: none).  VP_E_ARG for another `which`, lo_bits > hi_bits or a null
+ * result, before the device is touched; VP_E_STATE in the fast arithmetic mode, which has no such helpers. */
+int vp_test_roots(int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches, uint32_t* first_bad);
 int vp_test_rng(int mode, uint32_t x, uint32_t y, uint32_t frame, uint32_t k0, uint32_t k1, int n, float* out);
 int vp_test_sample_density(const float* pos_xyz, float* out, int n);
 /* component hooks for known-answer tests against float64 closed forms (no oracle involved):
