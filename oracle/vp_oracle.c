@@ -1,6 +1,10 @@
 /* vp_oracle.c -- TEST INFRASTRUCTURE.  Plain-C CPU restatement of the per-pixel Monte-Carlo
  * radiance integrator of RNG65536/CUDA-volpath (see vp_oracle.h for pin status and rules).
  *
+ * Parity: pinned bit for bit against the reference's own kernel file and bound builder, compiled for the CPU behind
+ * oracle/refshim (tests/test_reference_kernel_cpu.py; cases in DESIGN.md section 3), under the two definitions this file shares
+ * with that shim: the elementary functions and the texture fetch rule of the arithmetic contract below.
+ *
  * Every function cites the reference lines it follows; "kernel.cu" = src/volumeRender_kernel.cu,
  * "host.cpp" = src/volumeRender.cpp.  Compile-time configuration restated: SPECTRAL_TRACKING=1,
  * MULTI_CHANNEL=0, SUN_LIGHT=1, PASSIVE_ENVMAP=1, PRECOMPUTE_OPACITY=1, USE_MODEL_TRANSFORM=0,
@@ -520,9 +524,11 @@ static inline float luminance3(float r, float g, float b)
 }
 
 /* init_envmap kernel.cu:1144-1168 + build_cdf_1d/2d :1036-1070, configuration MULT_PDF 0, PRE_WARP 1 (:855-856):
- * row CDFs of luminance*sin(phi), CDF of the row sums, and HDRpdfnormAlt.  pdfX/pdfY are only read under MULT_PDF
- * and are not produced.  All sums are sequential float sums in texel order, as in the reference. */
-void vpo_build_env_tables(const float* env, int width, int height, float* cdf_y, float* cdf_x, float* pdfnorm_alt)
+ * row CDFs of luminance*sin(phi), CDF of the row sums, and HDRpdfnormAlt.  pdfX/pdfY are only read under MULT_PDF:
+ * the integrator never sees them and they are produced on request only (pdf_y, pdf_x may be NULL).  All sums are
+ * sequential float sums in texel order, as in the reference. */
+void vpo_build_env_tables_pdf(const float* env, int width, int height, float* cdf_y, float* cdf_x, float* pdf_y, float* pdf_x,
+                              float* pdfnorm_alt)
 {
     size_t total = (size_t)width * (size_t)height;
     float* lum   = (float*)malloc(total * sizeof(float));
@@ -548,7 +554,13 @@ void vpo_build_env_tables(const float* env, int width, int height, float* cdf_y,
         for (int i = 0; i < width; i++) sum += f[i];
         float norm = 1.0f / sum;
         float I    = 0.0f;
-        for (int i = 0; i < width; i++) { I += f[i] * norm; cdf[i] = I; }
+        for (int i = 0; i < width; i++)
+        {
+            float p = f[i] * norm;
+            I += p;
+            if (pdf_x) pdf_x[i + (size_t)y * width] = p;
+            cdf[i] = I;
+        }
         cdf[width - 1] = 1.0f;
         rows[y]        = sum;
     }
@@ -557,10 +569,20 @@ void vpo_build_env_tables(const float* env, int width, int height, float* cdf_y,
         for (int i = 0; i < height; i++) sum += rows[i];
         float norm = 1.0f / sum;
         float I    = 0.0f;
-        for (int i = 0; i < height; i++) { I += rows[i] * norm; cdf_y[i] = I; }
+        for (int i = 0; i < height; i++)
+        {
+            float p = rows[i] * norm;
+            I += p;
+            if (pdf_y) pdf_y[i] = p;
+            cdf_y[i] = I;
+        }
         cdf_y[height - 1] = 1.0f;
     }
     free(lum); free(rows);
+}
+void vpo_build_env_tables(const float* env, int width, int height, float* cdf_y, float* cdf_x, float* pdfnorm_alt)
+{
+    vpo_build_env_tables_pdf(env, width, height, cdf_y, cdf_x, NULL, NULL, pdfnorm_alt);
 }
 
 /* sample_y / sample_x kernel.cu:904-943: lower-bound binary search on a point-sampled CDF texture */

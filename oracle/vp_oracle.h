@@ -4,10 +4,10 @@
  * and only as the checker / the reported CPU baseline -- never as something the product calls.
  *
  * PARITY PIN STATUS (see DESIGN.md "Oracle"):
- *   - the reference's integrator lives in one CUDA translation unit (src/volumeRender_kernel.cu)
- *     that needs cuda_runtime.h and texture hardware: it is UNBUILDABLE in this image without
- *     writing stand-in headers, so it was not built.  The reference has no tests and no golden
- *     vectors of its own.
+ *   - the reference's integrator lives in one CUDA translation unit (src/volumeRender_kernel.cu).  It is built for the CPU
+ *     behind stand-in headers of our own (oracle/refshim, `make -C oracle ref`), with the bound builder of src/volumeRender.cpp,
+ *     and this oracle is compared with it bit for bit (tests/test_reference_kernel_cpu.py; see the last item).  The reference has
+ *     no tests and no golden vectors of its own.
  *   - pinned: RNG (sampler.h) by the known-answer values recorded from the reference in
  *     SURVEY.md section 4; the sun/sky inputs by oracle/_ref (the reference's own Hosek sources
  *     compiled where they lie); the Julia voxeliser by the occupancy figure and the integrator
@@ -24,8 +24,16 @@
  *     tests/test_oracle_cpu.py::test_julia_interior_matches_the_references_own_screenshot.  And the one quirk with a first-order
  *     effect on that image, Q9 (the "Hyperion" reduction): the same fit WITHOUT it (vpo_debug_set_what_if) misses the screenshot by
  *     more than twice the residual (test_julia_interior_prefers_the_reference_as_read).
- *   - everything else -- the quirks Q4-Q8, the tex3D rule, bounds, opacity as such: "parity unpinned" -- a line-by-line
- *     restatement citing file:line.
+ *   - pinned by the reference's OWN KERNEL CODE, bit for bit (whole accumulators and tables, sampler.h stream): the three
+ *     kernels __d_render, __d_render_bounded, __d_render_bounded_decomp in the shipped build and in the PASSIVE_ENVMAP 0,
+ *     SPECTRAL_TRACKING 0 and MULTI_CHANNEL 1 builds -- every quirk Q1-Q13, the |g| <= 1e-6 branch, the 800-segment and
+ *     800-scatter caps, point filtering, user boxes, cameras, float and uchar volumes, 16 random scenes, the zero-pdf `continue`
+ *     -- and compute_volume_value_bound, _precompute_opacity, init_envmap's CDF tables, set_sun, scale, gamma_correct.  The
+ *     cases are listed in DESIGN.md section 3.  The what-if misreadings of Q1, Q4, Q7, Q8 below are told apart by that code.
+ *     Two things are DEFINITION in that comparison, not measurement (oracle/refshim): the elementary functions (vpo_math.h) and
+ *     the texture fetch rule (texel-centre, clamp, 8-bit weights, uchar filtered in integers).  Their closeness to CUDA hardware
+ *     rests on the screenshot pins above.  Host compiler of the recipe: clang++ (argument evaluation left to right, as nvcc's
+ *     front end; g++ swaps the two draws of phase.sample(frame, rng.next(), rng.next())).
  */
 #ifndef VP_ORACLE_H
 #define VP_ORACLE_H
@@ -123,6 +131,9 @@ float    vpo_sample_density(const vpo_scene* S, const float pos[3]);
 void     vpo_sample_bound(const vpo_scene* S, const float pos[3], float out_max_min[2]);
 float    vpo_sample_opacity(const vpo_scene* S, const float pos[3]);
 void     vpo_build_env_tables(const float* env, int width, int height, float* cdf_y, float* cdf_x, float* pdfnorm_alt);
+/* the same, with the pdfY / pdfX tables the reference uploads beside them (kernel.cu:1169-1209; read under MULT_PDF only) */
+void     vpo_build_env_tables_pdf(const float* env, int width, int height, float* cdf_y, float* cdf_x, float* pdf_y, float* pdf_x,
+                                  float* pdfnorm_alt);
 void     vpo_debug_set_what_if(int mask); /* test hook: variants of the restatement for the radiometric pin (0 = the restatement; vp_oracle.c) */
 uint64_t vpo_debug_shadow_overflow(void); /* test hook: shadow rays that drew more than the 2^20 pairs of their sub-stream (must stay 0) */
 uint64_t vpo_debug_mis_zero_pdf(void); /* test hook: zero-pdf `continue`s taken so far (kernel.cu:2266) */

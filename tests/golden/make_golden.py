@@ -15,6 +15,15 @@ Sources, by authority:
                      roll and pan fitted; the distance held at the reference's default 4.0).  Pins the geometry chain -- Julia
                      voxeliser, volume box, camera matrix, field of view, pixel-to-ray map, box intersection -- against an output
                      the reference itself holds.
+  ref_kernel.npz     outputs of the reference's OWN kernel code: src/volumeRender_kernel.cu and the bound builder of
+                     src/volumeRender.cpp, compiled for the CPU behind oracle/refshim (oracle/_ref/libkernel_ref*.so, oracle/Makefile
+                     target `ref`).  Accumulators of the three estimators on the cases tests/ref_cases.py marks `golden` (shipped build,
+                     PASSIVE_ENVMAP 0, SPECTRAL_TRACKING 0, MULTI_CHANNEL 1), the bound, optical-depth and environment tables, the
+                     directional sun power, scale and gamma_correct.  REFERENCE-MADE: the authority for the oracle
+                     (tests/test_reference_kernel_cpu.py) and for the HIP kernels (tests/test_reference_kernel_gpu.py), under the two
+                     definitions of oracle/refshim (texture fetch rule, elementary functions).  Data only; inputs are rebuilt from
+                     tests/ref_cases.py and tests/scenes.py.  Tables above 16 KiB are kept as the SHA-256 of their bytes plus every
+                     97th element.
 """
 import ctypes as C
 import json
@@ -115,9 +124,22 @@ def ref_julia_silhouette(pose=None):
                         camera=np.asarray(F.camera(pose), np.float32), centre=F.CENTRE)
 
 
+def ref_kernel():
+    """tests/golden/ref_kernel.npz, computed by the reference libraries (never by the oracle)"""
+    import ref_cases as RC
+    import ref_lib
+    for v in ref_lib.VARIANTS:
+        assert ref_lib.status(v) == "ok", f"{ref_lib.path(v)} is missing: make -C oracle ref"
+    out = {}
+    for name, thunk in RC.entries(RC.ReferenceBackend(ref_lib, O)):
+        RC.pack(out, name, thunk())
+    np.savez_compressed(os.path.join(HERE, "ref_kernel.npz"), **out)
+
+
 if __name__ == "__main__":
     O.build()
     hosek_ref()
     oracle_renders()
     ref_julia_silhouette()
+    ref_kernel()
     print("golden fixtures written to", HERE)

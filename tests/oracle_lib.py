@@ -73,6 +73,7 @@ def lib():
         L.vpo_sample_opacity.restype = C.c_float
         L.vpo_mat.argtypes = [C.c_void_p] + [C.c_float] * 6
         L.vpo_build_env_tables.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vpo_build_env_tables_pdf.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.vpo_debug_mis_zero_pdf.restype = C.c_uint64
         L.vpo_debug_shadow_overflow.restype = C.c_uint64
         L.vpo_debug_set_what_if.argtypes = [C.c_int]
@@ -190,11 +191,13 @@ class OracleScene:
         S.env_pdfnorm_alt = norm.value
         self.pdfnorm_alt = norm.value
 
-    def precompute_opacity(self, threads=0):
+    def precompute_opacity(self, threads=0, light_dir=None):
+        """light_dir: the direction handed to precompute_opacity (default: the scene's sun, as host.cpp:341 does)"""
         threads = threads or DEFAULT_THREADS
         S = self.S
         self.opacity = np.empty((S.nz, S.ny, S.nx), np.float32)
-        lib().vpo_precompute_opacity(C.byref(S), S.sun_dir, _p(self.opacity), threads)
+        d = S.sun_dir if light_dir is None else (C.c_float * 3)(*[float(v) for v in light_dir])
+        lib().vpo_precompute_opacity(C.byref(S), d, _p(self.opacity), threads)
         S.opacity = _p(self.opacity).value
         return self.opacity
 
@@ -222,6 +225,17 @@ class OracleScene:
         cnt = Counters()
         lib().vpo_render_sample(C.byref(self.S), C.byref(P), x, y, frame, out, C.byref(cnt))
         return np.array(out[:], np.float32), cnt
+
+
+def env_tables_pdf(env):
+    """cdfY, cdfX, pdfY, pdfX, HDRpdfnormAlt of init_envmap's !PASSIVE_ENVMAP branch (kernel.cu:1144-1209)"""
+    env = np.ascontiguousarray(env, np.float32)
+    h, w = env.shape[:2]
+    cdf_y, pdf_y = np.empty(h, np.float32), np.empty(h, np.float32)
+    cdf_x, pdf_x = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    norm = C.c_float()
+    lib().vpo_build_env_tables_pdf(_p(env), w, h, _p(cdf_y), _p(cdf_x), _p(pdf_y), _p(pdf_x), C.byref(norm))
+    return cdf_y, cdf_x, pdf_y, pdf_x, np.float32(norm.value)
 
 
 def rng_stream(mode, x, y, frame, n, key=(0, 0)):
