@@ -9,6 +9,7 @@ import hashlib
 
 import numpy as np
 
+import degenerate_cases as DC
 import scenes
 
 EST_GLOBAL, EST_DECOMP, EST_BOUNDED = 0, 1, 2      # oracle_lib.EST_* / vp.EST_* / ref_render's `which`
@@ -57,6 +58,8 @@ def ragged(quantized):
 def grid(name, oracle):
     if name.startswith("julia"):
         return oracle.julia(int(name[5:]))
+    if name in ("odd_u8", "solid7"):
+        return DC.grid(name, oracle)
     return {"blob_f32": scenes.blob_volume_f32, "blob_u8": scenes.blob_volume_u8, "soft_u8": soft_u8,
             "tiny": lambda: np.array([[[0, 255], [128, 7], [3, 90]]], np.uint8),           # nz = 1, ny = 3, nx = 2
             "solid16": lambda: np.full((16, 16, 16), 255, np.uint8),
@@ -77,10 +80,16 @@ def env(name):
 
 
 def _case(name, grid="julia32", env="sky", kw=None, preset=None, box=None, linear=True, cam=None, frames=(0, 1), est=ALL_EST,
-          variant="", size=(W, H), golden=None, gframes=None):
+          variant="", size=(W, H), golden=None, gframes=None, sun=scenes.DEFAULT_SUN_DIR):
     """golden: the estimators whose reference-made accumulators the fixture keeps (over gframes, default: frames)"""
     return dict(name=name, grid=grid, env=env, kw=kw or {}, preset=preset, box=box, linear=linear, cam=cam, frames=tuple(frames),
-                est=tuple(est), variant=variant, size=size, golden=tuple(golden or ()), gframes=tuple(gframes or frames))
+                est=tuple(est), variant=variant, size=size, golden=tuple(golden or ()), gframes=tuple(gframes or frames),
+                sun=tuple(sun))
+
+
+def _degenerate(name, grid, position, axis, sign, **kw):
+    """a camera of tests/degenerate_cases.py at 16x12 in a medium thin enough that rays cross the volume (density 60)"""
+    return _case(name, grid=grid, kw=dict(density=60.0), cam=DC.camera(grid, position, axis, sign), size=(DC.W, DC.H), **kw)
 
 
 # frames: 10 is the last that never reads the optical-depth table, 11 the first that may (spp > 10, kernel.cu:2183)
@@ -100,6 +109,16 @@ RENDERS = [
     _case("brightness", kw=dict(brightness=2.5), frames=(1, 11)),
     # a solid, dense, non-absorbing block: paths run into max_depth = 800 (kernel.cu:34): heat 0.8 (segments) / 800 (scatters)
     _case("caps", grid="solid16", kw=dict(density=4000.0, g=0.0), frames=(0,), size=(24, 16), golden=(EST_DECOMP, EST_BOUNDED)),
+    # degenerate geometry (tests/degenerate_cases.py): signed-permutation cameras whose centre row, column and pixel have exact zero
+    # direction components, snapped to a face plane (inf * 0 = NaN in the slab test: fminf / fmaxf decide), a box edge, a face, a
+    # cell-boundary plane of an odd grid and the box centre; axis-parallel suns
+    _degenerate("deg_in_face_plane", "julia32", "in_face_plane", 0, 1, golden=ALL_EST),
+    _degenerate("deg_along_edge", "julia32", "along_edge", 1, -1, golden=(EST_DECOMP, EST_GLOBAL)),
+    _degenerate("deg_on_face", "julia32", "on_face", 2, 1),
+    _degenerate("deg_in_cell_plane", "odd_u8", "in_cell_plane", 0, -1, golden=ALL_EST),
+    _degenerate("deg_centre", "solid7", "centre", 1, 1),
+    _degenerate("deg_sun_zenith", "julia32", "outside", 2, -1, sun=DC.SUNS["+y"], frames=(0, 11), golden=(EST_DECOMP, EST_GLOBAL)),
+    _degenerate("deg_sun_x", "julia32", "outside", 0, 1, sun=DC.SUNS["+x"], frames=(0, 11)),
 ]
 VARIANT_RENDERS = [
     _case("mis_black_texel", env="black_texel", kw=dict(density=150.0, g=0.6), frames=(8, 12), variant="_mis", golden=ALL_EST),
@@ -135,14 +154,14 @@ def key(c, est):
 
 def oracle_scene(oracle, c, est):
     track = TRACK_OF_VARIANT[c["variant"]]
-    return oracle.OracleScene(grid(c["grid"], oracle), env(c["env"]), scenes.DEFAULT_SUN_DIR, scenes.DEFAULT_SUN_POWER, box=c["box"],
+    return oracle.OracleScene(grid(c["grid"], oracle), env(c["env"]), c["sun"], scenes.DEFAULT_SUN_POWER, box=c["box"],
                               brick=1, linear=c["linear"], estimator=est, rng_mode=oracle.RNG_SAMPLERH, inv_view=c["cam"],
                               env_mis=c["variant"] == "_mis", track_mode=track)
 
 
 def reference_scene(ref, oracle, c):
     """ref: tests/ref_lib.py; the oracle module supplies inputs only (the Julia voxels, the default camera)"""
-    return ref.RefScene(grid(c["grid"], oracle), env(c["env"]), scenes.DEFAULT_SUN_DIR, scenes.DEFAULT_SUN_POWER, box=c["box"],
+    return ref.RefScene(grid(c["grid"], oracle), env(c["env"]), c["sun"], scenes.DEFAULT_SUN_POWER, box=c["box"],
                         linear=c["linear"], inv_view=c["cam"], variant=c["variant"])
 
 

@@ -7,6 +7,8 @@ physics and the reference's formulas say in float64:
   * component known answers through the vp_test_* hooks: HGPhaseFunction::sample / ::evaluate incl. quirk Q1
     (kernel.cu:575-619), intersectBox (kernel.cu:654-680), tex3D's documented 8-bit-weight trilinear rule
     (kernel.cu:173-178, :682-695) restated in numpy, eval_envmap's direction -> texel mapping (kernel.cu:882-973);
+    intersectBox also bit for bit against a binary32 restatement on enumerated degenerate rays (zero, denormal and tiny
+    direction components, origins in the slab planes: the NaN cases);
   * white furnace: albedo 1, constant environment, no sun => every pixel is the environment constant, for the three
     estimators, passive and MIS environment lighting, spectral / scalar / multi-channel tracking;
   * homogeneous slab: E[unscattered fraction] = exp(-sigma_t * rho * chord) for the primary free flight
@@ -24,9 +26,9 @@ PI = np.pi
 CAM = np.array([0.0, 0.207912, 0.978148, 3.922986, 0.0, 0.978148, -0.207912, -0.782739, -1.0, 0.0, 0.0, 0.03])  # H4
 
 
-def _camera_rays(W, H):
+def _camera_rays(W, H, cam=None):
     """kernel.cu:1977-1987 in float64: origin and unit direction per pixel, arrays [H, W, 3]"""
-    M = CAM.reshape(3, 4)
+    M = (CAM if cam is None else np.asarray(cam, np.float64)).reshape(3, 4)
     x = np.arange(W)[None, :].repeat(H, 0).astype(np.float64)
     y = np.arange(H)[:, None].repeat(W, 1).astype(np.float64)
     u = (x * 2 - W) / W
@@ -152,6 +154,66 @@ def test_intersect_box_matches_float64_slab_test(vp):
     # tolerance 2e-6 relative + 2e-6 absolute (three binary32 operations per slab)
     assert np.allclose(tn[fin], tmin[fin], rtol=2e-6, atol=2e-6) and np.allclose(tf[fin], tmax[fin], rtol=2e-6, atol=2e-6)
     assert np.array_equal(np.isinf(tn), np.isinf(tmin)) and np.array_equal(np.isinf(tf), np.isinf(tmax))
+
+
+def _fmin32(a, b):
+    """fminf on binary32: the operand that is not NaN (np.fmin); of two zeros the negative one -- the reference's device orders
+    -0 below +0 in min and max (PTX ISA, min.f32 / max.f32), where C leaves the choice open"""
+    r = np.fmin(a, b)
+    return np.where((a == 0) & (b == 0), np.where(np.signbit(a) | np.signbit(b), np.float32(-0.0), np.float32(0.0)), r).astype(np.float32)
+
+
+def _fmax32(a, b):
+    r = np.fmax(a, b)
+    return np.where((a == 0) & (b == 0), np.where(np.signbit(a) & np.signbit(b), np.float32(-0.0), np.float32(0.0)), r).astype(np.float32)
+
+
+def test_intersect_box_is_the_binary32_slab_test_bit_for_bit(vp):
+    """intersectBox (kernel.cu:654-680) restated in numpy binary32 -- correctly rounded divides and products, fminf / fmaxf that
+    return the operand that is not NaN, max_of / min_of nested as the reference nests them (kernel.cu:67, :71) -- on an ENUMERATED
+    set of degenerate rays: every direction with components from {+0, -0, +-1, +-2^-149, +-1e-30}, normalised in binary32 as the
+    callers normalise (v * (1 / sqrt(v.v))), from every origin with coordinates at bmin, at bmax, between them and outside on either
+    side.  The set holds the rays in one, two and three slab planes (inf * 0 = NaN: the answer rests on the NaN rule of min and
+    max), along edges, through corners, and the directions no caller can make (v.v underflows: infinite and NaN components).
+    hit, tnear and tfar are compared as bit patterns; nothing is masked out.  NaN results count as one pattern: the payload of a
+    NaN is not defined by the operation that makes it."""
+    f = np.float32
+    grid = np.zeros((8, 12, 16), np.uint8)             # box = +-(1, 12/16, 8/16): exact in binary32
+    vp.init_volume(grid)
+    bmin, bmax = np.array([-1, -0.75, -0.5], f), np.array([1, 0.75, 0.5], f)
+    comp = np.array([0.0, -0.0, 1.0, -1.0, 2.0 ** -149, -2.0 ** -149, 1e-30, -1e-30], f)
+    v = np.stack(np.meshgrid(comp, comp, comp, indexing="ij"), -1).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        dot = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+        dirs = (v * (f(1.0) / np.sqrt(dot, dtype=f))[:, None]).astype(f)
+    per_axis = [np.array([bmin[a], bmax[a], bmin[a] + f(0.3125) * (bmax[a] - bmin[a]), bmax[a] + f(2.0), bmin[a] - f(1.5)], f) for a in range(3)]
+    orgs = np.stack(np.meshgrid(*per_axis, indexing="ij"), -1).reshape(-1, 3)
+    o = np.repeat(orgs, len(dirs), 0)
+    d = np.tile(dirs, (len(orgs), 1))
+    assert len(o) == 125 * 512
+    hit, tn, tf = vp.test_intersect_box(o, d)
+    with np.errstate(all="ignore"):
+        inv = f(1.0) / d
+        tbot, ttop = inv * (bmin - o), inv * (bmax - o)
+        tmin, tmax = _fmin32(ttop, tbot), _fmax32(ttop, tbot)
+        near = _fmax32(_fmax32(tmin[:, 0], tmin[:, 1]), tmin[:, 2])
+        far = _fmin32(_fmin32(tmax[:, 0], tmax[:, 1]), tmax[:, 2])
+        want = (far > near) & (far >= f(1e-3))
+    assert tbot.dtype == f and near.dtype == f
+
+    def bits(a):
+        return np.where(np.isnan(a), np.uint32(0x7fc00000), np.ascontiguousarray(a, f).view(np.uint32))
+
+    bad = np.nonzero((hit != want) | (bits(tn) != bits(near)) | (bits(tf) != bits(far)))[0]
+    assert len(bad) == 0, (len(bad), [(o[i].tolist(), d[i].tolist(), bool(hit[i]), bool(want[i]), float(tn[i]), float(near[i]), float(tf[i]), float(far[i]))
+                                      for i in bad[:5]])
+    # the set is what it claims to be
+    finite = np.isfinite(d).all(1)
+    nan_slabs = (np.isnan(tbot) | np.isnan(ttop)).sum(1)
+    assert finite.sum() == 125 * (512 - 216) and all(((nan_slabs == k) & finite).sum() > 100 for k in (1, 2))      # (a third needs a direction without a finite reciprocal)
+    assert not (want & finite & (nan_slabs > 0)).any()       # a ray IN a slab plane misses: its NaN leaves tmin = +inf or tmax = -inf
+    assert (want & finite).sum() > 1000 and (~want & finite).sum() > 1000
+    assert (np.signbit(near) & (near == 0)).any() and np.isinf(near[finite]).any() and np.isinf(far[finite]).any()
 
 
 def _tex3d_u8_numpy(grid, pos, bmin, bmax, linear=True):
@@ -457,6 +519,43 @@ def test_pixel_table_certificates_hold_in_float64(vp, est):
     whose 2x2x2 texels are all zero; (b) class 2 = the ray misses the box, class 1 = the whole chord is empty; (c) for the
     local-majorant estimators the recorded origin is the camera origin moved by `segments` steps of 0.05 along the ray, all
     of them in front of the box, and no draw beyond one per segment (the Julia grid has no brick with a positive minimum)."""
+    st = _pixel_table_certificates(vp, est, None, 160, 120)
+    assert st["classes"] == {0, 1, 2}
+    if est:
+        assert st["mean_segments_hit"] > 30
+    assert st["checked"] > 100000
+    # the certificate is not vacuous: most box-hitting rays get one, and a good share of them is certified to the end
+    assert st["certified"] > 0.8 and st["light"] > 0.3
+
+
+@pytest.mark.parametrize("est", [0, 1])
+@pytest.mark.parametrize("position,axis,sign", [("outside", 2, -1), ("in_cell_plane", 0, 1)])
+def test_pixel_table_certificates_hold_for_axis_cameras(vp, est, position, axis, sign):
+    """The same checks (a), (b) and (c) from two cameras of tests/degenerate_cases.py that look along an axis: with the even image
+    size row H/2 and column W/2 have one exact zero direction component and pixel (W/2, H/2) has two; from `in_cell_plane` that
+    pixel's ray runs inside a cell-boundary plane of the grid (x * 48 - 0.5 = 22 exactly, all along).  The centre row, the centre
+    column and the two-zero pixel are among the rays walked.  No ray of these cameras lies in a face plane of the box, so
+    `decided` excludes what it excludes for the default camera: pixels whose float64 slab test grazes the box."""
+    import degenerate_cases as DC
+    W, H = 160, 120
+    cam = DC.camera("julia48", position, axis, sign)
+    zeros = DC.ray_census(cam, W, H)
+    assert zeros[H // 2, W // 2] == 2 and (zeros == 1).sum() == W + H - 2
+    forced = [(H // 2, x) for x in range(W)] + [(y, W // 2) for y in range(H)]
+    try:
+        st = _pixel_table_certificates(vp, est, cam, W, H, forced)
+    finally:
+        vp.set_camera()
+    assert st["classes"] == {0, 1, 2}
+    assert st["hit"][H // 2, W // 2] and st["decided"][H // 2, W // 2]              # the axis-parallel ray meets the box, squarely
+    assert st["forced_walked"] >= 40 and (H // 2, W // 2) in st["walked"]
+    assert st["checked"] > 100000 and st["certified"] > 0.8 and st["light"] > 0.1
+
+
+def _pixel_table_certificates(vp, est, cam, W, H, forced=()):
+    """checks (a), (b), (c) of test_pixel_table_certificates_hold_in_float64 for the camera `cam` (None: the default camera);
+    `forced`: pixels (y, x) walked in (a) beside the 400 random ones, where they have a certificate.  Returns what the callers
+    need to see that the checks were not vacuous."""
     import scenes
     rng = np.random.default_rng(8)
     n = 48
@@ -464,20 +563,18 @@ def test_pixel_table_certificates_hold_in_float64(vp, est):
     vp.init_volume(grid, brick=4 if est else 1, linear=True)
     vp.init_envmap(scenes.synthetic_env())
     vp.set_sun(scenes.DEFAULT_SUN_DIR, scenes.DEFAULT_SUN_POWER)
-    vp.set_camera()
+    vp.set_camera() if cam is None else vp.set_camera(tuple(float(v) for v in cam))
     vp.set_estimator(est)
     vp.set_tracking(0)
     vp.set_shard(0, 1)
-    W, H = 160, 120
     P = vp.make_param(W, H)
     t = vp.pixel_table(P)
-    o, d = _camera_rays(W, H)
+    o, d = _camera_rays(W, H, cam)
     hit, tmin, tmax = _slab(o, d)
     cls = t[..., 5].astype(int)
     t_left = t[..., 4].astype(np.float64)
     packed = t[..., 3].view(np.uint32)
     segs, draws = (packed & 0xffff).astype(int), (packed >> 16).astype(int)
-    assert set(np.unique(cls)) == {0, 1, 2}
     decided = np.abs(tmax - tmin) > 1e-4
     assert np.array_equal((cls == 2)[decided], ~hit[decided])
     # non-empty cells of the volume: any texel of the clamped 2x2x2 neighbourhood non-zero
@@ -495,7 +592,7 @@ def test_pixel_table_certificates_hold_in_float64(vp, est):
         assert np.all(draws == segs)
         front = hit & (tmin > 0)
         assert np.all((tmin - walked)[front] <= 0.05 + 1e-4) and np.all((tmin - walked)[front] > -1e-4)
-        assert segs[hit].mean() > 30 and np.all(segs[~hit & decided] == 0)
+        assert np.all(segs[~hit & decided] == 0)
         start = walked
     else:
         assert np.all(segs == 0)
@@ -503,9 +600,11 @@ def test_pixel_table_certificates_hold_in_float64(vp, est):
     # (a): dense sampling (1/20 cell) of [box entry, certified distance)
     ys, xs = np.nonzero(hit & (t_left > 0))
     pick = rng.choice(len(ys), 400, replace=False)
+    rays = list(zip(ys[pick], xs[pick])) + [(y, x) for y, x in forced if hit[y, x] and t_left[y, x] > 0]
     cell = 2.0 / n
     checked = 0
-    for y, x in zip(ys[pick], xs[pick]):
+    walked_px = set()
+    for y, x in rays:
         t0 = max(tmin[y, x], 0.0)
         t1 = min(start[y, x] + t_left[y, x], tmax[y, x])
         if t1 <= t0:
@@ -515,15 +614,16 @@ def test_pixel_table_certificates_hold_in_float64(vp, est):
         idx = np.clip(np.floor(np.maximum(p, 0)).astype(int), 0, n - 1)
         assert not cell_nonempty[idx[:, 2], idx[:, 1], idx[:, 0]].any(), (y, x)
         checked += len(tt)
+        walked_px.add((int(y), int(x)))
         if cls[y, x] == 1:
             assert t_left[y, x] > 1e29
-    assert checked > 100000
-    # the certificate is not vacuous: most box-hitting rays get one, and a good share of them is certified to the end
-    assert (t_left[hit] > 0).mean() > 0.8 and (cls[hit] == 1).mean() > 0.3
+    return dict(classes=set(np.unique(cls).tolist()), mean_segments_hit=segs[hit].mean(), checked=checked, hit=hit, decided=decided,
+                certified=(t_left[hit] > 0).mean(), light=(cls[hit] == 1).mean(), walked=walked_px,
+                forced_walked=len(walked_px & {(int(y), int(x)) for y, x in forced}))
 
 
 @pytest.mark.parametrize("kind", ["julia", "ragged"])
-@pytest.mark.parametrize("sun", [(-0.0, 0.951057, -0.309017), (0.6, -0.3, 0.74), (0.0, 0.0, -1.0)])
+@pytest.mark.parametrize("sun", [(-0.0, 0.951057, -0.309017), (0.6, -0.3, 0.74), (0.0, 0.0, -1.0), (0.0, 1.0, 0.0), (1.0, 0.0, 0.0)])
 def test_sun_clip_certificate_holds_in_float64(vp, sun, kind):
     """Counter-based streams end a sun shadow ray where it has only empty cells left (vp_kernels.hip sun_clip_k).  The table is
     a claim about geometry, checked here in float64 against the raw volume, without the oracle: from random start points in
@@ -582,6 +682,26 @@ def test_sun_clip_certificate_holds_in_float64(vp, sun, kind):
         assert not cell_nonempty[idx[:, 2], idx[:, 1], idx[:, 0]].any(), (k, j, i)
         checked += len(ts)
     assert checked > (50000 if kind == "julia" else 5000)
+    # start points ON cell boundaries -- the cell's corner, edge midpoints and face centres (offsets 0 / 0.5 per axis, not all 0.5:
+    # the cell of a boundary point is the one floor assigns, which is (i, j, k)) -- walked in cell coordinates, where an axis-parallel
+    # sun keeps the ray exactly inside its cell-boundary plane
+    e = sun * N / (bmax - bmin)                                   # cell units per unit of distance
+    offsets = [np.array(o) * 0.5 for o in np.ndindex(2, 2, 2)][:7]
+    on_boundary = 0
+    for n_, (k, j, i) in enumerate(zip(ks[pick], js[pick], is_[pick])):
+        xb0 = np.array([i, j, k]) + offsets[n_ % 7]
+        t0 = float(table[k, j, i]) * step
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tt = np.where(e > 0, (N - 0.5 - xb0) / e, np.where(e < 0, (-0.5 - xb0) / e, np.inf))
+        t1 = float(tt.min())
+        if t1 <= t0:
+            continue
+        ts = np.arange(t0, t1, cell_edges.min() / 20)
+        q = xb0 + e * ts[:, None]
+        idx = np.clip(np.floor(np.maximum(q, 0)).astype(int), 0, (N - 1).astype(int))
+        assert not cell_nonempty[idx[:, 2], idx[:, 1], idx[:, 0]].any(), (k, j, i, xb0)
+        on_boundary += len(ts)
+    assert on_boundary > (50000 if kind == "julia" else 5000) // 2
     # not vacuous: some of the non-empty cells see the sun within a few cells, and on average a ray ends well before the box does
     assert (table[cell_nonempty] * step < 4 * cell_edges.max()).mean() > 0.04
     assert (table[cell_nonempty] * step).mean() < 0.5 * np.linalg.norm(bmax - bmin)
@@ -643,6 +763,42 @@ def test_exit_table_certificates_hold_in_float64(vp, kind):
         checked += len(ts)
         rays += 1
     assert rays > 800 and checked > 100000
+    # Degenerate directions, given IN CELL UNITS so that ties and zeros are exact: the 6 axis directions, the 12 face diagonals and
+    # the 8 body diagonals (components 0, +-1: every nonzero component ties for the dominant axis), and the 24 directions (+-2, +-1, 0)
+    # with one zero component and no tie.  Start points are the cell's corner, its edge midpoints, its face centres and its centre
+    # (offsets 0 / 0.5 per axis: the cell of a boundary point is the one floor assigns, which is `c`).  The walk to the box exit is
+    # the same float64 walk, made in cell coordinates, where it is exact: a ray inside a cell-boundary plane stays in it.  The class
+    # bit as the header defines it: a zero component counts as "not > 0".  With a tie the certificate must hold for EVERY axis that
+    # ties (binary32 rounding of d * N / extent may pick any of them).
+    units = [np.array(e, np.float64) for e in np.ndindex(3, 3, 3)]
+    units = [e - 1 for e in units if (e != 1).any()]
+    skew = [np.array(p, np.float64) * s for p in ((2, 1, 0), (2, 0, 1), (1, 2, 0), (0, 2, 1), (1, 0, 2), (0, 1, 2))
+            for s in ((1, 1, 1), (-1, 1, 1), (1, -1, 1), (-1, -1, 1), (1, 1, -1), (-1, 1, -1), (1, -1, -1), (-1, -1, -1))]
+    skew = [np.array(t) for t in {tuple(e + 0.0) for e in skew}]
+    assert len(units) == 26 and len(skew) == 24
+    offsets = [np.array(o) * 0.5 for o in np.ndindex(2, 2, 2)]
+    rays2 = checked2 = ties = zeros = 0
+    for _ in range(400):
+        c = np.array([rng.integers(0, nx), rng.integers(0, ny), rng.integers(0, nz)])
+        xb0 = c + offsets[rng.integers(0, 8)]
+        for e in units + skew:
+            ae = np.abs(e)
+            for A in np.nonzero(ae == ae.max())[0]:
+                B, Cx = [a for a in range(3) if a != A]
+                cls = int(e[A] > 0) | int(e[B] > 0) << 1 | int(e[Cx] > 0) << 2
+                if not (table[A, c[2], c[1], c[0]] >> cls) & 1:
+                    continue
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    tt = np.where(e > 0, (N - 0.5 - xb0) / e, np.where(e < 0, (-0.5 - xb0) / e, np.inf))
+                ss = np.arange(0.0, float(tt.min()) + 0.05 / ae.max(), 0.05 / ae.max())
+                q = xb0 + e * ss[:, None]
+                idx = np.clip(np.floor(np.maximum(q, 0)).astype(int), 0, (N - 1).astype(int))
+                assert not cell_nonempty[idx[:, 2], idx[:, 1], idx[:, 0]].any(), (c, xb0, e, A)
+                checked2 += len(ss)
+                rays2 += 1
+                ties += int((ae == ae.max()).sum() > 1)
+                zeros += int((e == 0).any())
+    assert rays2 > 500 and ties > 100 and zeros > 100 and checked2 > 10000, (rays2, ties, zeros, checked2)
     # not vacuous: cells on the faces of the box certify the directions that leave through their face at once
     assert (table[0, :, :, nx - 1] & 0xaa).any() and (table[0, :, :, 0] & 0x55).any()
     assert (table != 0).mean() > 0.3

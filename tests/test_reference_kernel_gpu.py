@@ -34,13 +34,13 @@ class GpuBackend:
     def __init__(self, vp, oracle, per_frame):
         self.vp, self.O, self.per_frame = vp, oracle, per_frame
 
-    def _scene(self, g, e="sky", box=None, linear=True, cam=None):
+    def _scene(self, g, e="sky", box=None, linear=True, cam=None, sun=scenes.DEFAULT_SUN_DIR):
         vp = self.vp
         vp.set_arithmetic(vp.ARITH_EXACT)
         vp.set_subpixel(1)
         vp.init_volume(RC.grid(g, self.O), box=box, brick=1, linear=linear)
         vp.init_envmap(RC.env(e))
-        vp.set_sun(scenes.DEFAULT_SUN_DIR, scenes.DEFAULT_SUN_POWER)
+        vp.set_sun(sun, scenes.DEFAULT_SUN_POWER)
         vp.set_camera() if cam is None else vp.set_camera(cam)
         vp.set_rng(vp.RNG_SAMPLERH, (0, 0))
         vp.set_shard(0, 1)
@@ -51,10 +51,10 @@ class GpuBackend:
         try:
             vp.set_tracking(RC.TRACK_OF_VARIANT[c["variant"]])
             vp.set_envmap_sampling(vp.ENV_MIS if c["variant"] == "_mis" else vp.ENV_PASSIVE)
-            self._scene(c["grid"], c["env"], c["box"], c["linear"], c["cam"])
+            self._scene(c["grid"], c["env"], c["box"], c["linear"], c["cam"], c["sun"])
             vp.set_estimator(est)
             if RC.needs_opacity(c, est, frames):
-                vp.precompute_opacity(scenes.DEFAULT_SUN_DIR)
+                vp.precompute_opacity(c["sun"])
             P = RC.param(vp.make_param, vp.mat, c)
             if self.per_frame:          # the reference's call pattern (the Part-1 ABI), look-ahead on
                 vp.set_lookahead(vp.LOOKAHEAD_DEFAULT)
