@@ -163,7 +163,8 @@ int free_volume()
     G.d_cells = G.d_bounds = nullptr;
     G.d_opacity   = nullptr;
     G.S.cells_u8  = nullptr;
-    G.S.cells_f32 = nullptr;
+    G.S.cells_f32 = nullptr;   // (and cells_f16: the same slot)
+    G.cells_bytes = 0;
     G.S.bounds_u8 = nullptr;
     G.S.bounds_f32 = nullptr;
     G.S.opacity    = nullptr;
@@ -171,10 +172,10 @@ int free_volume()
     return VP_OK;
 }
 
-static int do_init_volume_(const void* h_volume, vp_extent ext, bool quantized, const vp_float3* bmin, const vp_float3* bmax);
-int do_init_volume(const void* h_volume, vp_extent ext, bool quantized, const vp_float3* bmin, const vp_float3* bmax)
+static int do_init_volume_(const void* h_volume, vp_extent ext, int format, const vp_float3* bmin, const vp_float3* bmax);
+int do_init_volume(const void* h_volume, vp_extent ext, int format, const vp_float3* bmin, const vp_float3* bmax)
 {
-    int rc = do_init_volume_(h_volume, ext, quantized, bmin, bmax);
+    int rc = do_init_volume_(h_volume, ext, format, bmin, bmax);
     if (rc)
     {
         // a failed upload leaves no half-built scene behind (free_volume keeps the error text of the failure)
@@ -184,8 +185,11 @@ int do_init_volume(const void* h_volume, vp_extent ext, bool quantized, const vp
     }
     return rc;
 }
-int do_init_volume_(const void* h_volume, vp_extent ext, bool quantized, const vp_float3* bmin, const vp_float3* bmax)
+int do_init_volume_(const void* h_volume, vp_extent ext, int format, const vp_float3* bmin, const vp_float3* bmax)
 {
+    // binary16 cells take the float side of everything but the cell itself: `quantized` is the uchar form alone
+    const bool   quantized = format == VP_VOL_U8, half = format == VP_VOL_F16;
+    const size_t cell_size = quantized ? 8 : (half ? 16 : 32);
     G.epoch++;  // staged look-ahead frames no longer describe this scene ...
     (void)la_quiesce();  // ... and batches in flight must not see device buffers change under them
 
@@ -214,6 +218,7 @@ int do_init_volume_(const void* h_volume, vp_extent ext, bool quantized, const v
     }
     for (int a = 0; a < 3; a++) S.linv[a] = 1.0f / (S.bmax[a] - S.bmin[a]);  // kernel.cu:313
     G.quant = quantized;
+    G.vol_format = format;
     // volume -> packed neighbourhood cells.  The three scratch buffers belong to a guard: every early return frees them.
     struct Scratch
     {
@@ -223,7 +228,7 @@ int do_init_volume_(const void* h_volume, vp_extent ext, bool quantized, const v
     void*& d_raw = tmp.p[0];
     void*& d_ta  = tmp.p[1];
     void*& d_tb  = tmp.p[2];
-    const size_t vbytes = n * (quantized ? 1 : 4);
+    const size_t vbytes = n * (quantized ? 1 : (half ? 2 : 4));
     HIPCHK(hipMalloc(&d_raw, vbytes));
     HIPCHK(hipMemcpyAsync(d_raw, h_volume, vbytes, hipMemcpyHostToDevice, G.stream));
     // cell layout: x fastest (default), or 4x4x4 bricks of cells (VP_CELL_BRICKS=1).  Measured on every workload incl. the two
@@ -234,9 +239,11 @@ int do_init_volume_(const void* h_volume, vp_extent ext, bool quantized, const v
     const bool   bricks = G.cell_bricks > 0;
     const size_t ncells = bricks ? ncells_bricks : n;
     S.cell_bricks = bricks ? 1 : 0;
-    HIPCHK(hipMalloc(&G.d_cells, ncells * (quantized ? 8 : 32)));
-    if (bricks && ncells != n) HIPCHK(hipMemsetAsync(G.d_cells, 0, ncells * (quantized ? 8 : 32), G.stream));   // the padding of partial bricks
+    HIPCHK(hipMalloc(&G.d_cells, ncells * cell_size));
+    G.cells_bytes = ncells * cell_size;
+    if (bricks && ncells != n) HIPCHK(hipMemsetAsync(G.d_cells, 0, ncells * cell_size, G.stream));   // the padding of partial bricks
     if (quantized) launch_pack_u8((const unsigned char*)d_raw, (uint2*)G.d_cells, nx, ny, nz, bricks, G.stream);
+    else if (half) launch_pack_f16((const unsigned short*)d_raw, (uint4*)G.d_cells, nx, ny, nz, bricks, G.stream);
     else launch_pack_f32((const float*)d_raw, (float*)G.d_cells, nx, ny, nz, bricks, G.stream);
     HIPCHK(hipGetLastError());
     // bound table: three separable max/min passes + brick reduction on the GPU (replaces host.cpp:1088-1267)
@@ -252,7 +259,7 @@ int do_init_volume_(const void* h_volume, vp_extent ext, bool quantized, const v
     HIPCHK(hipMalloc(&d_tb, n * psize));
     HIPCHK(hipMalloc(&G.d_bounds, nb * psize + 16));  // padded: the LDS stage copies whole 16-byte words
     HIPCHK(hipMemsetAsync(G.d_bounds, 0, nb * psize + 16, G.stream));
-    launch_build_bounds(d_raw, quantized, G.d_bounds, d_ta, d_tb, nx, ny, nz, G.radius, G.brick, G.stream);
+    launch_build_bounds(d_raw, quantized, half, G.d_bounds, d_ta, d_tb, nx, ny, nz, G.radius, G.brick, G.stream);
     HIPCHK(hipGetLastError());
     if (quantized)
     {
@@ -262,7 +269,8 @@ int do_init_volume_(const void* h_volume, vp_extent ext, bool quantized, const v
     else
     {
         S.bounds_f32 = (const float*)G.d_bounds;
-        S.cells_f32  = (const float*)G.d_cells;
+        if (half) S.cells_f16 = (const uint4*)G.d_cells;
+        else S.cells_f32 = (const float*)G.d_cells;
     }
     // The compact form of the brick table (render_k<..., LDSB = 2>, vp_kernels.h LaunchDev::bound_codes): where the table fits the LDS
     // stage and holds at most FOUR distinct (max,min) byte pairs -- a binary volume such as the Julia sets has three -- 2-bit codes
@@ -309,7 +317,7 @@ int do_init_volume_(const void* h_volume, vp_extent ext, bool quantized, const v
         // (the counter: the last word of the work-counter block is nobody's)
         unsigned long long* d_marked = G.d_counters + (kCounterWords - 1);
         HIPCHK(hipMemsetAsync(d_marked, 0, sizeof(unsigned long long), G.stream));
-        launch_danger(S, quantized, G.d_danger, d_marked, G.stream);
+        launch_danger(S, quantized, half, G.d_danger, d_marked, G.stream);
         HIPCHK(hipGetLastError());
         unsigned long long marked = 0;
         HIPCHK(hipMemcpyAsync(&marked, d_marked, sizeof marked, hipMemcpyDeviceToHost, G.stream));
@@ -405,7 +413,7 @@ void init_cuda(void* h_volume, vp_extent volumeSize, bool quantized, const vp_fl
         fprintf(stderr, "cannot init without host volume\n");  // kernel.cu:360-364
         exit(1);
     }
-    if (do_init_volume(h_volume, volumeSize, quantized, boxmin, boxmax)) die("init_cuda");
+    if (do_init_volume(h_volume, volumeSize, quantized ? VP_VOL_U8 : VP_VOL_F32, boxmin, boxmax)) die("init_cuda");
 }
 
 // (the setters below first wait for vp_render_frames' pipelined launches in flight: pipe_quiesce)
@@ -727,6 +735,24 @@ int vp_get_env_tables(float* cdf_y, float* cdf_x, float* pdfnorm_alt)
     if (pdfnorm_alt) *pdfnorm_alt = G.S.env_pdfnorm_alt;
     return VP_OK;
 }
+int vp_init_volume(const void* h_volume, vp_extent ext, int format, const vp_float3* bmin, const vp_float3* bmax)
+{
+    // (refused before the device is touched)
+    if (!h_volume) return fail(VP_E_ARG, "vp_init_volume: null volume");
+    if (format != VP_VOL_U8 && format != VP_VOL_F32 && format != VP_VOL_F16) return fail(VP_E_ARG, "vp_init_volume: unknown volume format %d", format);
+    if (ext.width == 0 || ext.height == 0 || ext.depth == 0) return fail(VP_E_ARG, "empty volume extent");
+    return do_init_volume(h_volume, ext, format, bmin, bmax);
+}
+int vp_get_volume_info(vp_volume_info* out)
+{
+    if (!out) return fail(VP_E_ARG, "vp_get_volume_info: null result");
+    if (!G.have_volume) return fail(VP_E_STATE, "no volume");
+    out->format = G.vol_format;
+    out->nx = G.S.nx; out->ny = G.S.ny; out->nz = G.S.nz;
+    out->cell_bytes  = G.quant ? 8 : (G.half() ? 16 : 32);
+    out->cells_bytes = (uint64_t)G.cells_bytes;
+    return VP_OK;
+}
 int vp_set_bound_brick(int brick)
 {
     if (int rc = pipe_quiesce()) return rc;
@@ -781,7 +807,7 @@ int vp_test_sample_density(const float* pos_xyz, float* out, int n)
     HIPCHK(hipMemcpy(dp, pos_xyz, (size_t)n * 12, hipMemcpyHostToDevice));
     SceneDev S = G.S;
     S.linear   = G.linear ? 1 : 0;
-    launch_test_density(S, G.quant, dp, dq, n, G.stream);
+    launch_test_density(S, G.quant, G.half(), dp, dq, n, G.stream);
     HIPCHK(hipStreamSynchronize(G.stream));
     HIPCHK(hipMemcpy(out, dq, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipFree(dp));

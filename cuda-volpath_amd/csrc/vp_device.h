@@ -55,7 +55,12 @@ struct ParamDev
 struct SceneDev
 {
     const uint2*         cells_u8;   // quantized volume: the 2x2x2 texel neighbourhood of each voxel in 8 bytes
-    const float*         cells_f32;  // float volume: the same neighbourhood as 8 floats
+    union   // (one volume, one form: the pointers share a slot, so the argument block of every kernel keeps its layout)
+    {
+        const float* cells_f32;  // float volume: the same neighbourhood as 8 floats
+        const uint4* cells_f16;  // binary16 volume (include/volpath.h VP_VOL_F16): as 8 halves in 16 bytes, the same tap order; its
+                                 // bound table is bounds_f32, built from the widened values
+    };
     const unsigned char* bounds_u8;  // (max,min) byte pairs per brick
     const float*         bounds_f32; // (max,min) float pairs per brick
     const float*         opacity;    // optical depth toward the sun, N^3 floats (or null): what precompute_opacity computes (vp_get_opacity)
@@ -282,10 +287,17 @@ __device__ __forceinline__ size_t cell_index(const SceneDev& S, int i, int j, in
     return (size_t)((unsigned)i + __umul24((unsigned)S.nx, (unsigned)j + __umul24((unsigned)S.ny, (unsigned)k)));
 }
 
+// the two binary16 values of a dword, widened: exact, subnormals included (v_cvt_f32_f16, the high half through SDWA)
+__device__ __forceinline__ float half_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+__device__ __forceinline__ float half_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+
 // normalised density in [0,1] at a world position: tex3D<float>(density_tex) of kernel.cu:692
-template <bool QUANT>
+// HALF (with QUANT = false): a binary16 volume -- one 16-byte load, eight widenings, then the float filter's lerps as they stand: the
+// bits of the float volume that holds the widened values (include/volpath.h vp_init_volume)
+template <bool QUANT, bool HALF = false>
 __device__ __forceinline__ float sample_density01(const SceneDev& S, f3 pos)
 {
+    static_assert(!(QUANT && HALF), "a binary16 volume takes the float branches");
     f3    p = to_local(S, pos);
     int   i, j, k;
     float fx, fy, fz;
@@ -317,6 +329,23 @@ __device__ __forceinline__ float sample_density01(const SceneDev& S, f3 pos)
     {
         uint2 c = S.cells_u8[idx];
         return filter_cell_u8(c, fx, fy, fz);
+    }
+    else if (HALF)
+    {
+        // dword t holds the x pair of taps (y, z) = (t & 1, t >> 1).  The `low` rule of the float path below, applied where it is
+        // cheapest: along y and z a copied pair is a copied dword, along x the second tap is chosen as it is widened.  Copying and
+        // widening commute, so the lerps see the values the float path's see.
+        uint4 c = S.cells_f16[idx];
+        if (ly) { c.y = c.x; c.w = c.z; }
+        if (lz) { c.z = c.x; c.w = c.y; }
+        const float t00 = half_lo(c.x), t10 = half_lo(c.y), t01 = half_lo(c.z), t11 = half_lo(c.w);
+        float x00 = lerpf(t00, lx ? t00 : half_hi(c.x), fx);
+        float x10 = lerpf(t10, lx ? t10 : half_hi(c.y), fx);
+        float x01 = lerpf(t01, lx ? t01 : half_hi(c.z), fx);
+        float x11 = lerpf(t11, lx ? t11 : half_hi(c.w), fx);
+        float y0  = lerpf(x00, x10, fy);
+        float y1  = lerpf(x01, x11, fy);
+        return lerpf(y0, y1, fz);
     }
     else
     {

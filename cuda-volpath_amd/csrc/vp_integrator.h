@@ -192,7 +192,7 @@ constexpr int render_min_waves(int est, bool count, int ldsb, bool ach, bool mis
     if (trk) return 4;                                                                     // scalar tracking builds
     return (ach && !cancel) ? VP_LOCAL_MIN_WAVES : 5;                                      // local majorants: achromatic six, chromatic / look-ahead five
 }
-template <int EST, class RNG, bool QUANT, bool COUNT, int LDSB, bool ACH, bool MIS, int TRK, bool LIGHT = false, bool CANCEL = false>
+template <int EST, class RNG, bool QUANT, bool COUNT, int LDSB, bool ACH, bool MIS, int TRK, bool LIGHT = false, bool CANCEL = false, bool HALF = false>
 // Occupancy (round 4: the cold per-path state in LDS, ColdVal above; profiles/r04_kernel_resources.txt).  The achromatic
 // global-majorant kernel needs 72 registers: SEVEN waves per SIMD (C2 2541 -> 2781 Msamples/s); the chromatic one and the plain
 // achromatic local-majorant kernels 80: six (c3ref 2398 -> 2513); the LDS-table kernel keeps its state in registers (its LDS is the
@@ -1271,7 +1271,7 @@ ends_done:
                         den = 0.0f;
                         if (shadow || !(dist < t_empty))
                         {
-                            den = sample_density01<QUANT>(S, p) * cur_density;  // vol_sigma_t kernel.cu:682-695
+                            den = sample_density01<QUANT, HALF>(S, p) * cur_density;  // vol_sigma_t kernel.cu:682-695
                             if (COUNT && !(shadow && dist >= t_clip) && !(!shadow && ex_clear)) c_load++;
                         }
                     }
@@ -1281,7 +1281,7 @@ ends_done:
                         den = 0.0f;
                         if (shadow || !(dist < t_empty))
                         {
-                            den = sample_density01<QUANT>(S, p) * cur_density;  // vol_sigma_t kernel.cu:682-695
+                            den = sample_density01<QUANT, HALF>(S, p) * cur_density;  // vol_sigma_t kernel.cu:682-695
                             if (COUNT && !(shadow && dist >= t_clip) && !(!shadow && ex_clear)) c_load++;
                         }
                     }

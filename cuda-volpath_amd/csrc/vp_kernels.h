@@ -158,11 +158,12 @@ struct LaunchDev
 
 // lds_form: how the decomposition estimator reads its brick table -- 0 global memory, 1 the 16-bit table through LDS (512-thread
 // workgroups), 2 2-bit codes into a four-entry palette through LDS (LaunchDev::bound_codes; 256-thread workgroups, plain occupancy)
-void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int lds_form, bool mis, int trk,
+// half (with quant = false): binary16 cells (SceneDev::cells_f16); everything else of such a volume is the float volume's
+void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
                    int blocks, hipStream_t st);
 // the same in the fast arithmetic mode (vp_kernels_fast.hip): counter-based streams, spectral tracking, passive environment, global
 // majorant or decomposition, no counters -- the host refuses the rest before it launches
-void launch_render_fast(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int lds_form, bool mis, int trk,
+void launch_render_fast(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
                         int blocks, hipStream_t st);
 // the light pixel class (spectral tracking): pixels whose camera ray meets empty cells only
 void launch_render_light(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int blocks, hipStream_t st);
@@ -195,7 +196,7 @@ void launch_env_tables(const float4* env, int w, int h, float* lum, float* row_s
 void launch_crawl_table(const SceneDev& S, bool quant, unsigned width, unsigned height, bool control_draw, const unsigned char* danger, float4* table,
                         hipStream_t st);
 // marked (may be null): a device counter that receives the number of cells marked (a non-empty cell in the 3x3x3 neighbourhood)
-void launch_danger(const SceneDev& S, bool quant, unsigned char* out, unsigned long long* marked, hipStream_t st);
+void launch_danger(const SceneDev& S, bool quant, bool half, unsigned char* out, unsigned long long* marked, hipStream_t st);
 float sun_clip_step(const SceneDev& S);  // the table's distance unit: a quarter of the smallest cell edge
 void launch_sun_clip(const SceneDev& S, const unsigned char* danger, float ds, unsigned short* out, hipStream_t st);
 void launch_empty_table(const SceneDev& S, unsigned width, unsigned height, const unsigned char* danger, float4* table, hipStream_t st);
@@ -229,9 +230,10 @@ void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, 
 // bricks: cells in 4x4x4 bricks (vp_device.h cell_index); the buffer then holds ceil(n/4)^3 * 64 cells
 void launch_pack_u8(const unsigned char* vol, uint2* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);
 void launch_pack_f32(const float* vol, float* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);
+void launch_pack_f16(const unsigned short* vol, uint4* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);   // 8 halves per cell, the order of pack_f32
 // lds: uchar volumes through opacity_lds_k (the density grid staged through LDS tile by tile), else opacity_k: the same bits
-void launch_opacity(const SceneDev& S, bool quant, bool lds, const float dir[3], float* out, hipStream_t st);
-void launch_build_bounds(const void* d_vol, bool quant, void* d_out, void* d_tmp_a, void* d_tmp_b, int nx, int ny, int nz, int radius, int brick,
+void launch_opacity(const SceneDev& S, bool quant, bool half, bool lds, const float dir[3], float* out, hipStream_t st);
+void launch_build_bounds(const void* d_vol, bool quant, bool half, void* d_out, void* d_tmp_a, void* d_tmp_b, int nx, int ny, int nz, int radius, int brick,
                          hipStream_t st);
 void launch_julia(unsigned char* grid, int n, hipStream_t st);
 void launch_cloud(float* grid, int n, unsigned seed, hipStream_t st);
@@ -247,5 +249,5 @@ void launch_test_roots(int which, unsigned lo, unsigned hi, unsigned long long* 
 void launch_test_hg_fast(const float* g, const float* r0, const float* r1, const float* nrm, const float* cosq, float* dir, float* ev, int n, hipStream_t st);
 void launch_test_math_fast(int which, const float* in, float* out, int n, hipStream_t st);
 void launch_test_rng(int mode, unsigned x, unsigned y, unsigned f, unsigned k0, unsigned k1, int n, float* out, hipStream_t st);
-void launch_test_density(const SceneDev& S, bool quant, const float* pos, float* out, int n, hipStream_t st);
+void launch_test_density(const SceneDev& S, bool quant, bool half, const float* pos, float* out, int n, hipStream_t st);
 }  // namespace vp

@@ -136,7 +136,8 @@ __global__ __launch_bounds__(256) void crawl_table_k(SceneDev S, unsigned width,
 // in an empty cell itself -- with three quarters of a cell to spare against the 1e-6 differences between the positions the
 // march and the integrator compute.  The integrator's free-flight steps before that distance skip the fetch and use the +0
 // it would have produced (render_k, tracking_step): same bits, ~65 fewer instructions and no memory access per step.
-template <bool QUANT>
+// (HALF: a binary16 cell is empty when its eight halves are +0 or -0, as a float cell is when its floats compare equal to zero)
+template <bool QUANT, bool HALF = false>
 __global__ __launch_bounds__(256) void danger_k(SceneDev S, unsigned char* out, unsigned long long* marked)
 {
     size_t n   = (size_t)S.nx * S.ny * S.nz;
@@ -151,6 +152,7 @@ __global__ __launch_bounds__(256) void danger_k(SceneDev S, unsigned char* out, 
                 int a = min(max(i + di, 0), S.nx - 1), b = min(max(j + dj, 0), S.ny - 1), c = min(max(k + dk, 0), S.nz - 1);
                 size_t o = cell_index(S, a, b, c);
                 if (QUANT) { uint2 v = S.cells_u8[o]; any = any || (v.x | v.y) != 0u; }
+                else if (HALF) { uint4 v = S.cells_f16[o]; any = any || ((v.x | v.y | v.z | v.w) & 0x7fff7fffu) != 0u; }
                 else
                 {
                     const float4* q = reinterpret_cast<const float4*>(S.cells_f32) + o * 2;
@@ -163,6 +165,7 @@ __global__ __launch_bounds__(256) void danger_k(SceneDev S, unsigned char* out, 
     {
         size_t o = cell_index(S, i, j, k);
         if (QUANT) { uint2 v = S.cells_u8[o]; self = (v.x | v.y) != 0u; }
+        else if (HALF) { uint4 v = S.cells_f16[o]; self = ((v.x | v.y | v.z | v.w) & 0x7fff7fffu) != 0u; }
         else
         {
             const float4* q = reinterpret_cast<const float4*>(S.cells_f32) + o * 2;
@@ -781,6 +784,18 @@ __global__ void pack_cells_f32_k(const float* vol, float* cells, int nx, int ny,
     q[0] = make_float4(at(i, j, k), at(i1, j, k), at(i, j1, k), at(i1, j1, k));
     q[1] = make_float4(at(i, j, k1), at(i1, j, k1), at(i, j1, k1), at(i1, j1, k1));
 }
+// binary16 volume: the same eight taps as halves, tap t in bits 16 (t & 1) of dword t >> 1 (the order of pack_cells_f32_k)
+__global__ void pack_f16_k(const unsigned short* vol, uint4* cells, int nx, int ny, int nz, int bricks)
+{
+    size_t n   = (size_t)nx * ny * nz;
+    size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    int i = (int)(idx % nx), j = (int)((idx / nx) % ny), k = (int)(idx / ((size_t)nx * ny));
+    int i1 = i + 1 < nx ? i + 1 : nx - 1, j1 = j + 1 < ny ? j + 1 : ny - 1, k1 = k + 1 < nz ? k + 1 : nz - 1;
+    auto at = [&](int a, int b, int c) -> unsigned { return vol[(size_t)a + (size_t)nx * ((size_t)b + (size_t)ny * c)]; };
+    cells[pack_index(nx, ny, i, j, k, bricks)] = make_uint4(at(i, j, k) | (at(i1, j, k) << 16), at(i, j1, k) | (at(i1, j1, k) << 16),
+                                                            at(i, j, k1) | (at(i1, j, k1) << 16), at(i, j1, k1) | (at(i1, j1, k1) << 16));
+}
 
 // ---- local (max,min) bound table (compute_volume_value_bound_, host.cpp:1088-1267) on the GPU.
 // Per voxel, max and min of the density over the (2r+1)^3 window clipped to the grid; max/min filters are
@@ -807,6 +822,12 @@ __global__ __launch_bounds__(256) void bounds_init_k(const typename PR::T* vol, 
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = PR::make(vol[i], vol[i]);
+}
+// a binary16 volume starts the float table from its widened values: what bounds_init_k<PairF32> makes of the widened grid
+__global__ __launch_bounds__(256) void bounds_init_f16_k(const unsigned short* vol, float2* out, size_t n)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { const float v = half_lo(vol[i]); out[i] = make_float2(v, v); }
 }
 // one 1-D pass along `axis` (stride in elements, extent na); threads run along x so every read is coalesced
 template <class PR>
@@ -855,7 +876,7 @@ __global__ __launch_bounds__(256) void bounds_brick_k(const typename PR::P* in, 
 }
 
 // _precompute_opacity kernel.cu:483-524 with intersect_box :453-481; one thread per voxel
-template <bool QUANT>
+template <bool QUANT, bool HALF = false>
 __global__ __launch_bounds__(256) void opacity_k(SceneDev S, f3 light_dir, float* out)
 {
     size_t n   = (size_t)S.nx * S.ny * S.nz;
@@ -873,7 +894,7 @@ __global__ __launch_bounds__(256) void opacity_k(SceneDev S, f3 light_dir, float
     float opacity = 0.0f;
     if (hit)
     {
-        for (float t = tn; t < tf; t += dt) opacity += sample_density01<QUANT>(S, start + light_dir * t);
+        for (float t = tn; t < tf; t += dt) opacity += sample_density01<QUANT, HALF>(S, start + light_dir * t);
         opacity *= dt;
     }
     out[idx] = opacity;
@@ -1138,17 +1159,17 @@ __global__ void test_rng_k(unsigned x, unsigned y, unsigned frame, unsigned k0, 
     r.init(x, y, frame, k0, k1);
     for (int i = 0; i < n; i++) out[i] = (i & 1) ? r.next_b() : r.next_a();
 }
-template <bool QUANT>
+template <bool QUANT, bool HALF = false>
 __global__ void test_density_k(SceneDev S, const float* pos, float* out, int n)
 {
     int i = threadIdx.x + blockIdx.x * blockDim.x;
     if (i >= n) return;
-    out[i] = sample_density01<QUANT>(S, f3{pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]});
+    out[i] = sample_density01<QUANT, HALF>(S, f3{pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]});
 }
 
 // ------------------------------------------------------------------ host-side launchers
 template <int EST, class RNG, int LDSB, bool ACH, bool MIS>
-static void launch_render5(const SceneDev& S, const LaunchDev& L, bool quant, bool count, int blocks, hipStream_t st)
+static void launch_render5(const SceneDev& S, const LaunchDev& L, bool quant, bool half, bool count, int blocks, hipStream_t st)
 {
     const dim3 blk(LDSB == 1 ? VP_BLOCK_LDS : VP_BLOCK);
     if constexpr (LDSB == 2)
@@ -1160,7 +1181,7 @@ static void launch_render5(const SceneDev& S, const LaunchDev& L, bool quant, bo
     else
     {
 #ifdef VP_DEV_BUILD
-    quant = true;
+    quant = true; (void)half;
     if (MIS) return;
     if constexpr (!MIS)
     {
@@ -1177,6 +1198,13 @@ static void launch_render5(const SceneDev& S, const LaunchDev& L, bool quant, bo
         else if (CAN && L.cancel) hipLaunchKernelGGL((render_k<EST, RNG, true, false, LDSB, ACH, MIS, 0, false, CAN>), dim3(blocks), blk, 0, st, S, L);
         else hipLaunchKernelGGL((render_k<EST, RNG, true, false, LDSB, ACH, MIS, 0>), dim3(blocks), blk, 0, st, S, L);
     }
+    else if (half)
+    {
+        // (binary16 cells: the float instances' arguments with HALF set)
+        if (count) hipLaunchKernelGGL((render_k<EST, RNG, false, true, false, ACH, MIS, 0, false, false, true>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
+        else if (CAN && L.cancel) hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, ACH, MIS, 0, false, CAN, true>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
+        else hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, ACH, MIS, 0, false, false, true>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
+    }
     else
     {
         if (count) hipLaunchKernelGGL((render_k<EST, RNG, false, true, false, ACH, MIS, 0>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
@@ -1189,13 +1217,18 @@ static void launch_render5(const SceneDev& S, const LaunchDev& L, bool quant, bo
 // scalar tracking builds (the reference's compiled-out SPECTRAL_TRACKING 0 / MULTI_CHANNEL 1): three-channel throughput, no
 // LDS / MIS / counting specialisations
 template <int EST, class RNG>
-static void launch_render_scalar(const SceneDev& S, const LaunchDev& L, bool quant, int trk, int blocks, hipStream_t st)
+static void launch_render_scalar(const SceneDev& S, const LaunchDev& L, bool quant, bool half, int trk, int blocks, hipStream_t st)
 {
     const dim3 blk(VP_BLOCK);
     if (quant)
     {
         if (trk == 1) hipLaunchKernelGGL((render_k<EST, RNG, true, false, false, false, false, 1>), dim3(blocks), blk, 0, st, S, L);
         else hipLaunchKernelGGL((render_k<EST, RNG, true, false, false, false, false, 2>), dim3(blocks), blk, 0, st, S, L);
+    }
+    else if (half)
+    {
+        if (trk == 1) hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, false, false, 1, false, false, true>), dim3(blocks), blk, 0, st, S, L);
+        else hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, false, false, 2, false, false, true>), dim3(blocks), blk, 0, st, S, L);
     }
     else
     {
@@ -1204,24 +1237,24 @@ static void launch_render_scalar(const SceneDev& S, const LaunchDev& L, bool qua
     }
 }
 template <int EST, class RNG, int LDSB>
-static void launch_render3(const SceneDev& S, const LaunchDev& L, bool quant, bool count, bool ach, bool mis, int blocks, hipStream_t st)
+static void launch_render3(const SceneDev& S, const LaunchDev& L, bool quant, bool half, bool count, bool ach, bool mis, int blocks, hipStream_t st)
 {
     if (mis)
     {
         // active environment sampling: the rarely used build, kept off the LDS specialisation
-        if (ach) launch_render5<EST, RNG, 0, true, true>(S, L, quant, count, blocks, st);
-        else launch_render5<EST, RNG, 0, false, true>(S, L, quant, count, blocks, st);
+        if (ach) launch_render5<EST, RNG, 0, true, true>(S, L, quant, half, count, blocks, st);
+        else launch_render5<EST, RNG, 0, false, true>(S, L, quant, half, count, blocks, st);
     }
-    else if (ach) launch_render5<EST, RNG, LDSB, true, false>(S, L, quant, count, blocks, st);
-    else launch_render5<EST, RNG, LDSB, false, false>(S, L, quant, count, blocks, st);
+    else if (ach) launch_render5<EST, RNG, LDSB, true, false>(S, L, quant, half, count, blocks, st);
+    else launch_render5<EST, RNG, LDSB, false, false>(S, L, quant, half, count, blocks, st);
 }
 
 // VP_RNG_PHILOX7: the shipped configuration only (spectral tracking, passive environment)
 template <int EST, int LDSB>
-static void launch_render_p7(const SceneDev& S, const LaunchDev& L, bool quant, bool count, bool ach, int blocks, hipStream_t st)
+static void launch_render_p7(const SceneDev& S, const LaunchDev& L, bool quant, bool half, bool count, bool ach, int blocks, hipStream_t st)
 {
-    if (ach) launch_render5<EST, RngPhilox7, LDSB, true, false>(S, L, quant, count, blocks, st);
-    else launch_render5<EST, RngPhilox7, LDSB, false, false>(S, L, quant, count, blocks, st);
+    if (ach) launch_render5<EST, RngPhilox7, LDSB, true, false>(S, L, quant, half, count, blocks, st);
+    else launch_render5<EST, RngPhilox7, LDSB, false, false>(S, L, quant, half, count, blocks, st);
 }
 
 template <int EST, class RNGT>
@@ -1340,7 +1373,7 @@ void launch_pixel_lists(unsigned width, unsigned height, unsigned rank, unsigned
     hipLaunchKernelGGL(pixlist_write_k, dim3(nblocks), dim3(VP_PIXLIST_BLOCK), 0, st, D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
 }
 
-void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int lds_form, bool mis, int trk,
+void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
                    int blocks, hipStream_t st)
 {
     const bool lds_bounds = lds_form != 0;
@@ -1350,8 +1383,8 @@ void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool
     {
         const ParamDev& Pc = L.P;
         const bool achc = Pc.sigma_t[0] == Pc.sigma_t[1] && Pc.sigma_t[1] == Pc.sigma_t[2] && Pc.albedo[0] == Pc.albedo[1] && Pc.albedo[1] == Pc.albedo[2];
-        if (rng == RNG_PHILOX7) launch_render_p7<EST_DECOMP, 2>(S, L, true, false, achc, blocks, st);
-        else launch_render3<EST_DECOMP, RngPhilox, 2>(S, L, true, false, achc, false, blocks, st);
+        if (rng == RNG_PHILOX7) launch_render_p7<EST_DECOMP, 2>(S, L, true, false, false, achc, blocks, st);
+        else launch_render3<EST_DECOMP, RngPhilox, 2>(S, L, true, false, false, achc, false, blocks, st);
         return;
     }
 #ifdef VP_DEV_BUILD
@@ -1367,26 +1400,26 @@ void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool
         }
         if (rng == RNG_PHILOX7)
         {
-            if (est == EST_DECOMP && lds_bounds) launch_render_p7<EST_DECOMP, 1>(S, L, true, count, achd, blocks, st);
-            else if (est == EST_DECOMP) launch_render_p7<EST_DECOMP, 0>(S, L, true, count, achd, blocks, st);
-            else launch_render_p7<EST_GLOBAL, 0>(S, L, true, count, achd, blocks, st);
+            if (est == EST_DECOMP && lds_bounds) launch_render_p7<EST_DECOMP, 1>(S, L, true, false, count, achd, blocks, st);
+            else if (est == EST_DECOMP) launch_render_p7<EST_DECOMP, 0>(S, L, true, false, count, achd, blocks, st);
+            else launch_render_p7<EST_GLOBAL, 0>(S, L, true, false, count, achd, blocks, st);
             return;
         }
         if (est == EST_DECOMP)
         {
-            if (lds_bounds) launch_render3<EST_DECOMP, RngPhilox, 1>(S, L, true, count, achd, false, blocks, st);
-            else launch_render3<EST_DECOMP, RngPhilox, 0>(S, L, true, count, achd, false, blocks, st);
+            if (lds_bounds) launch_render3<EST_DECOMP, RngPhilox, 1>(S, L, true, false, count, achd, false, blocks, st);
+            else launch_render3<EST_DECOMP, RngPhilox, 0>(S, L, true, false, count, achd, false, blocks, st);
         }
-        else launch_render3<EST_GLOBAL, RngPhilox, 0>(S, L, true, count, achd, false, blocks, st);
+        else launch_render3<EST_GLOBAL, RngPhilox, 0>(S, L, true, false, count, achd, false, blocks, st);
         return;
     }
 #else
     if (trk)
     {
         const bool ph = rng == RNG_PHILOX;
-        if (est == EST_DECOMP) { if (ph) launch_render_scalar<EST_DECOMP, RngPhilox>(S, L, quant, trk, blocks, st); else launch_render_scalar<EST_DECOMP, RngSamplerH>(S, L, quant, trk, blocks, st); }
-        else if (est == EST_BOUNDED) { if (ph) launch_render_scalar<EST_BOUNDED, RngPhilox>(S, L, quant, trk, blocks, st); else launch_render_scalar<EST_BOUNDED, RngSamplerH>(S, L, quant, trk, blocks, st); }
-        else { if (ph) launch_render_scalar<EST_GLOBAL, RngPhilox>(S, L, quant, trk, blocks, st); else launch_render_scalar<EST_GLOBAL, RngSamplerH>(S, L, quant, trk, blocks, st); }
+        if (est == EST_DECOMP) { if (ph) launch_render_scalar<EST_DECOMP, RngPhilox>(S, L, quant, half, trk, blocks, st); else launch_render_scalar<EST_DECOMP, RngSamplerH>(S, L, quant, half, trk, blocks, st); }
+        else if (est == EST_BOUNDED) { if (ph) launch_render_scalar<EST_BOUNDED, RngPhilox>(S, L, quant, half, trk, blocks, st); else launch_render_scalar<EST_BOUNDED, RngSamplerH>(S, L, quant, half, trk, blocks, st); }
+        else { if (ph) launch_render_scalar<EST_GLOBAL, RngPhilox>(S, L, quant, half, trk, blocks, st); else launch_render_scalar<EST_GLOBAL, RngSamplerH>(S, L, quant, half, trk, blocks, st); }
         return;
     }
     // achromatic medium: identical extinction and albedo in the three channels (e.g. preset #13, host.cpp:1308)
@@ -1396,35 +1429,35 @@ void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool
     if (rng == RNG_PHILOX7)
     {
         // (mis and trk were rejected by the API for this generator)
-        if (est == EST_DECOMP && lds_bounds && quant) launch_render_p7<EST_DECOMP, 1>(S, L, quant, count, ach, blocks, st);
-        else if (est == EST_DECOMP) launch_render_p7<EST_DECOMP, 0>(S, L, quant, count, ach, blocks, st);
-        else if (est == EST_BOUNDED) launch_render_p7<EST_BOUNDED, 0>(S, L, quant, count, ach, blocks, st);
-        else launch_render_p7<EST_GLOBAL, 0>(S, L, quant, count, ach, blocks, st);
+        if (est == EST_DECOMP && lds_bounds && quant) launch_render_p7<EST_DECOMP, 1>(S, L, quant, half, count, ach, blocks, st);
+        else if (est == EST_DECOMP) launch_render_p7<EST_DECOMP, 0>(S, L, quant, half, count, ach, blocks, st);
+        else if (est == EST_BOUNDED) launch_render_p7<EST_BOUNDED, 0>(S, L, quant, half, count, ach, blocks, st);
+        else launch_render_p7<EST_GLOBAL, 0>(S, L, quant, half, count, ach, blocks, st);
         return;
     }
     if (est == EST_DECOMP)
     {
         if (lds_bounds && quant && !mis)
         {
-            if (rng == RNG_PHILOX) launch_render3<EST_DECOMP, RngPhilox, 1>(S, L, quant, count, ach, mis, blocks, st);
-            else launch_render3<EST_DECOMP, RngSamplerH, 1>(S, L, quant, count, ach, mis, blocks, st);
+            if (rng == RNG_PHILOX) launch_render3<EST_DECOMP, RngPhilox, 1>(S, L, quant, half, count, ach, mis, blocks, st);
+            else launch_render3<EST_DECOMP, RngSamplerH, 1>(S, L, quant, half, count, ach, mis, blocks, st);
         }
         else
         {
-            if (rng == RNG_PHILOX) launch_render3<EST_DECOMP, RngPhilox, 0>(S, L, quant, count, ach, mis, blocks, st);
-            else launch_render3<EST_DECOMP, RngSamplerH, 0>(S, L, quant, count, ach, mis, blocks, st);
+            if (rng == RNG_PHILOX) launch_render3<EST_DECOMP, RngPhilox, 0>(S, L, quant, half, count, ach, mis, blocks, st);
+            else launch_render3<EST_DECOMP, RngSamplerH, 0>(S, L, quant, half, count, ach, mis, blocks, st);
         }
     }
     else if (est == EST_BOUNDED)
     {
         // the dead reference variant: no LDS specialisation, it is there for completeness
-        if (rng == RNG_PHILOX) launch_render3<EST_BOUNDED, RngPhilox, 0>(S, L, quant, count, ach, mis, blocks, st);
-        else launch_render3<EST_BOUNDED, RngSamplerH, 0>(S, L, quant, count, ach, mis, blocks, st);
+        if (rng == RNG_PHILOX) launch_render3<EST_BOUNDED, RngPhilox, 0>(S, L, quant, half, count, ach, mis, blocks, st);
+        else launch_render3<EST_BOUNDED, RngSamplerH, 0>(S, L, quant, half, count, ach, mis, blocks, st);
     }
     else
     {
-        if (rng == RNG_PHILOX) launch_render3<EST_GLOBAL, RngPhilox, 0>(S, L, quant, count, ach, mis, blocks, st);
-        else launch_render3<EST_GLOBAL, RngSamplerH, 0>(S, L, quant, count, ach, mis, blocks, st);
+        if (rng == RNG_PHILOX) launch_render3<EST_GLOBAL, RngPhilox, 0>(S, L, quant, half, count, ach, mis, blocks, st);
+        else launch_render3<EST_GLOBAL, RngSamplerH, 0>(S, L, quant, half, count, ach, mis, blocks, st);
     }
 #endif
 }
@@ -1486,11 +1519,12 @@ void launch_crawl_table(const SceneDev& S, bool quant, unsigned width, unsigned 
     if (quant) hipLaunchKernelGGL(crawl_table_k<true>, dim3((n + 255) / 256), dim3(256), 0, st, S, width, height, control_draw ? 1 : 0, danger, table);
     else hipLaunchKernelGGL(crawl_table_k<false>, dim3((n + 255) / 256), dim3(256), 0, st, S, width, height, control_draw ? 1 : 0, danger, table);
 }
-void launch_danger(const SceneDev& S, bool quant, unsigned char* out, unsigned long long* marked, hipStream_t st)
+void launch_danger(const SceneDev& S, bool quant, bool half, unsigned char* out, unsigned long long* marked, hipStream_t st)
 {
     size_t n = (size_t)S.nx * S.ny * S.nz;
     dim3   g((unsigned)((n + 255) / 256));
     if (quant) hipLaunchKernelGGL(danger_k<true>, g, dim3(256), 0, st, S, out, marked);
+    else if (half) hipLaunchKernelGGL((danger_k<false, true>), g, dim3(256), 0, st, S, out, marked);
     else hipLaunchKernelGGL(danger_k<false>, g, dim3(256), 0, st, S, out, marked);
 }
 void launch_exit_table(const unsigned char* danger, unsigned char* planes, int nx, int ny, int nz, hipStream_t st)
@@ -1562,7 +1596,12 @@ void launch_pack_f32(const float* vol, float* cells, int nx, int ny, int nz, boo
     size_t n = (size_t)nx * ny * nz;
     hipLaunchKernelGGL(pack_cells_f32_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, vol, cells, nx, ny, nz, bricks ? 1 : 0);
 }
-void launch_opacity(const SceneDev& S, bool quant, bool lds, const float dir[3], float* out, hipStream_t st)
+void launch_pack_f16(const unsigned short* vol, uint4* cells, int nx, int ny, int nz, bool bricks, hipStream_t st)
+{
+    size_t n = (size_t)nx * ny * nz;
+    hipLaunchKernelGGL(pack_f16_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, vol, cells, nx, ny, nz, bricks ? 1 : 0);
+}
+void launch_opacity(const SceneDev& S, bool quant, bool half, bool lds, const float dir[3], float* out, hipStream_t st)
 {
     size_t n = (size_t)S.nx * S.ny * S.nz;
     f3     d = f3{dir[0], dir[1], dir[2]};
@@ -1579,16 +1618,18 @@ void launch_opacity(const SceneDev& S, bool quant, bool lds, const float dir[3],
         hipLaunchKernelGGL(opacity_lds_k, dim3(nb), dim3(VP_OPA_B * VP_OPA_B * VP_OPA_B), 0, st, S, d, out, chunk);
     }
     else if (quant) hipLaunchKernelGGL(opacity_k<true>, g, dim3(256), 0, st, S, d, out);
+    else if (half) hipLaunchKernelGGL((opacity_k<false, true>), g, dim3(256), 0, st, S, d, out);
     else hipLaunchKernelGGL(opacity_k<false>, g, dim3(256), 0, st, S, d, out);
 }
 template <class PR>
-static void build_bounds_t(const void* d_vol, void* d_out, void* d_tmp_a, void* d_tmp_b, int nx, int ny, int nz, int radius, int brick, hipStream_t st)
+static void build_bounds_t(const void* d_vol, bool half, void* d_out, void* d_tmp_a, void* d_tmp_b, int nx, int ny, int nz, int radius, int brick, hipStream_t st)
 {
     typedef typename PR::P P;
     size_t   n = (size_t)nx * ny * nz;
     unsigned g = (unsigned)((n + 255) / 256);
     P *a = (P*)d_tmp_a, *b = (P*)d_tmp_b;
-    hipLaunchKernelGGL(bounds_init_k<PR>, dim3(g), dim3(256), 0, st, (const typename PR::T*)d_vol, a, n);
+    if (half) hipLaunchKernelGGL(bounds_init_f16_k, dim3(g), dim3(256), 0, st, (const unsigned short*)d_vol, (float2*)d_tmp_a, n);
+    else hipLaunchKernelGGL(bounds_init_k<PR>, dim3(g), dim3(256), 0, st, (const typename PR::T*)d_vol, a, n);
     for (int axis = 0; axis < 3; axis++)
     {
         hipLaunchKernelGGL(bounds_pass_k<PR>, dim3(g), dim3(256), 0, st, (const P*)a, b, nx, ny, nz, axis, radius);
@@ -1598,12 +1639,13 @@ static void build_bounds_t(const void* d_vol, void* d_out, void* d_tmp_a, void* 
     size_t nb = (size_t)bnx * bny * bnz;
     hipLaunchKernelGGL(bounds_brick_k<PR>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, (const P*)a, (P*)d_out, nx, ny, nz, brick, bnx, bny, bnz);
 }
-// d_tmp_a / d_tmp_b: two scratch buffers of nx*ny*nz pairs (2 B uchar, 8 B float)
-void launch_build_bounds(const void* d_vol, bool quant, void* d_out, void* d_tmp_a, void* d_tmp_b, int nx, int ny, int nz, int radius, int brick,
+// d_tmp_a / d_tmp_b: two scratch buffers of nx*ny*nz pairs (2 B uchar, 8 B float); half: d_vol holds binary16 values, the table is the
+// float one of their widened values (the halves are read once, by the first pass: no widened copy of the grid)
+void launch_build_bounds(const void* d_vol, bool quant, bool half, void* d_out, void* d_tmp_a, void* d_tmp_b, int nx, int ny, int nz, int radius, int brick,
                          hipStream_t st)
 {
-    if (quant) build_bounds_t<PairU8>(d_vol, d_out, d_tmp_a, d_tmp_b, nx, ny, nz, radius, brick, st);
-    else build_bounds_t<PairF32>(d_vol, d_out, d_tmp_a, d_tmp_b, nx, ny, nz, radius, brick, st);
+    if (quant) build_bounds_t<PairU8>(d_vol, false, d_out, d_tmp_a, d_tmp_b, nx, ny, nz, radius, brick, st);
+    else build_bounds_t<PairF32>(d_vol, half, d_out, d_tmp_a, d_tmp_b, nx, ny, nz, radius, brick, st);
 }
 void launch_julia(unsigned char* grid, int n, hipStream_t st)
 {
@@ -1653,9 +1695,10 @@ void launch_test_rng(int mode, unsigned x, unsigned y, unsigned f, unsigned k0, 
     else if (mode == RNG_PHILOX7) hipLaunchKernelGGL(test_rng_k<RngPhilox7>, dim3(1), dim3(64), 0, st, x, y, f, k0, k1, n, out);
     else hipLaunchKernelGGL(test_rng_k<RngSamplerH>, dim3(1), dim3(64), 0, st, x, y, f, k0, k1, n, out);
 }
-void launch_test_density(const SceneDev& S, bool quant, const float* pos, float* out, int n, hipStream_t st)
+void launch_test_density(const SceneDev& S, bool quant, bool half, const float* pos, float* out, int n, hipStream_t st)
 {
     if (quant) hipLaunchKernelGGL(test_density_k<true>, dim3((n + 255) / 256), dim3(256), 0, st, S, pos, out, n);
+    else if (half) hipLaunchKernelGGL((test_density_k<false, true>), dim3((n + 255) / 256), dim3(256), 0, st, S, pos, out, n);
     else hipLaunchKernelGGL(test_density_k<false>, dim3((n + 255) / 256), dim3(256), 0, st, S, pos, out, n);
 }
 }  // namespace vp

@@ -14,7 +14,7 @@
 // flights and the decomposition walks), so that a staged launch skips exactly what a one-frame launch would compute as a no-op.
 //
 // Built: the counter-based streams (Philox2x32-10 and -7), spectral tracking, passive environment, the global-majorant and
-// decomposition estimators, uchar and float volumes, LDS forms 0/1/2, achromatic and chromatic media, the look-ahead's CANCEL
+// decomposition estimators, uchar, float and binary16 volumes, LDS forms 0/1/2, achromatic and chromatic media, the look-ahead's CANCEL
 // instances.  Not built (vp_render.cpp refuses them with VP_E_STATE): the sampler.h stream, the bounded estimator, MIS, scalar and
 // multi-channel tracking, work counters.
 #define VP_ARITH_FAST 1
@@ -34,35 +34,37 @@ namespace fast
 #include "vp_integrator.h"
 #include "vp_test_kernels.h"
 
-template <int EST, class RNG, bool QUANT, int LDSB, bool ACH>
+template <int EST, class RNG, bool QUANT, int LDSB, bool ACH, bool HALF>
 static void launch_render_t(const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
 {
     const dim3 g(blocks), b(LDSB == 1 ? VP_BLOCK_LDS : VP_BLOCK);
     if constexpr (LDSB == 2)
-        hipLaunchKernelGGL((render_k<EST, RNG, QUANT, false, 2, ACH, false, 0>), g, b, 0, st, S, L);   // timed launches only
+        hipLaunchKernelGGL((render_k<EST, RNG, QUANT, false, 2, ACH, false, 0, false, false, HALF>), g, b, 0, st, S, L);   // timed launches only
     else if (L.cancel)
-        hipLaunchKernelGGL((render_k<EST, RNG, QUANT, false, LDSB, ACH, false, 0, false, true>), g, b, 0, st, S, L);
+        hipLaunchKernelGGL((render_k<EST, RNG, QUANT, false, LDSB, ACH, false, 0, false, true, HALF>), g, b, 0, st, S, L);
     else
-        hipLaunchKernelGGL((render_k<EST, RNG, QUANT, false, LDSB, ACH, false, 0>), g, b, 0, st, S, L);
+        hipLaunchKernelGGL((render_k<EST, RNG, QUANT, false, LDSB, ACH, false, 0, false, false, HALF>), g, b, 0, st, S, L);
 }
-template <int EST, class RNG, bool QUANT, int LDSB>
+template <int EST, class RNG, bool QUANT, int LDSB, bool HALF = false>
 static void launch_render_a(const SceneDev& S, const LaunchDev& L, bool ach, int blocks, hipStream_t st)
 {
-    if (ach) launch_render_t<EST, RNG, QUANT, LDSB, true>(S, L, blocks, st);
-    else launch_render_t<EST, RNG, QUANT, LDSB, false>(S, L, blocks, st);
+    if (ach) launch_render_t<EST, RNG, QUANT, LDSB, true, HALF>(S, L, blocks, st);
+    else launch_render_t<EST, RNG, QUANT, LDSB, false, HALF>(S, L, blocks, st);
 }
 template <class RNG>
-static void launch_render_r(const SceneDev& S, const LaunchDev& L, int est, bool quant, int lds_form, bool ach, int blocks, hipStream_t st)
+static void launch_render_r(const SceneDev& S, const LaunchDev& L, int est, bool quant, bool half, int lds_form, bool ach, int blocks, hipStream_t st)
 {
     if (est == EST_GLOBAL)
     {
 #ifndef VP_DEV_BUILD
+        if (half) { launch_render_a<EST_GLOBAL, RNG, false, 0, true>(S, L, ach, blocks, st); return; }
         if (!quant) { launch_render_a<EST_GLOBAL, RNG, false, 0>(S, L, ach, blocks, st); return; }
 #endif
         launch_render_a<EST_GLOBAL, RNG, true, 0>(S, L, ach, blocks, st);
         return;
     }
 #ifndef VP_DEV_BUILD
+    if (half) { launch_render_a<EST_DECOMP, RNG, false, 0, true>(S, L, ach, blocks, st); return; }
     if (!quant) { launch_render_a<EST_DECOMP, RNG, false, 0>(S, L, ach, blocks, st); return; }
 #endif
     // (the same choice of LDS form as vp_kernels.hip launch_render: the compact table for timed launches only)
@@ -72,7 +74,7 @@ static void launch_render_r(const SceneDev& S, const LaunchDev& L, int est, bool
 }
 }  // namespace fast
 
-void launch_render_fast(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int lds_form, bool mis, int trk,
+void launch_render_fast(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
                         int blocks, hipStream_t st)
 {
     if (count || mis || trk || (est != EST_GLOBAL && est != EST_DECOMP) || (rng != RNG_PHILOX && rng != RNG_PHILOX7))
@@ -85,8 +87,8 @@ void launch_render_fast(const SceneDev& S, const LaunchDev& L, int est, int rng,
 #endif
     const ParamDev& P = L.P;
     const bool ach = P.sigma_t[0] == P.sigma_t[1] && P.sigma_t[1] == P.sigma_t[2] && P.albedo[0] == P.albedo[1] && P.albedo[1] == P.albedo[2];
-    if (rng == RNG_PHILOX7) fast::launch_render_r<RngPhilox7>(S, L, est, quant, lds_form, ach, blocks, st);
-    else fast::launch_render_r<RngPhilox>(S, L, est, quant, lds_form, ach, blocks, st);
+    if (rng == RNG_PHILOX7) fast::launch_render_r<RngPhilox7>(S, L, est, quant, half, lds_form, ach, blocks, st);
+    else fast::launch_render_r<RngPhilox>(S, L, est, quant, half, lds_form, ach, blocks, st);
 }
 
 // light_identity_k in this arithmetic (global majorant: the host lets approach_k skip the walk's null collisions only where this says

@@ -11,7 +11,7 @@ void render_key(const Param* p, std::vector<unsigned char>& key)
     K* k = reinterpret_cast<K*>(key.data());
     memcpy(&k->S, &G.S, sizeof(SceneDev));
     memcpy(&k->P, p, sizeof(Param));
-    k->est = G.est; k->rng = G.rng; k->linear = G.linear; k->quant = G.quant; k->mis = G.env_mis; k->trk = G.trk; k->arith = G.arith; k->sub = G.sub_shift;
+    k->est = G.est; k->rng = G.rng; k->linear = G.linear; k->quant = G.vol_format; k->mis = G.env_mis; k->trk = G.trk; k->arith = G.arith; k->sub = G.sub_shift;
     k->k0 = G.key0; k->k1 = G.key1; k->rank = G.rank; k->world = G.world; k->epoch = G.epoch;
 }
 

@@ -460,7 +460,7 @@ static hipError_t launch_general_class(Launch& X, const ClassGrid& g)
     }
     if (le == hipSuccess)
     {
-        X.k.render(X.S, L, G.est, G.rng, G.quant, G.count, X.lds_form, G.env_mis, G.trk, (int)g.blocks, T.stream);
+        X.k.render(X.S, L, G.est, G.rng, G.quant, G.half(), G.count, X.lds_form, G.env_mis, G.trk, (int)g.blocks, T.stream);
         le = hipGetLastError();
     }
     // The LDS-table kernel holds 2 x 64 KiB of a CU's LDS with 2 x 512 threads: four waves per SIMD, where the
@@ -470,7 +470,7 @@ static hipError_t launch_general_class(Launch& X, const ClassGrid& g)
     if (X.lds_helper && g.ldsb && le == hipSuccess && X.aux.forked && g.blocks >= g.cap)
         if (hipStream_t hs = X.aux.begin())
         {
-            X.k.render(X.S, L, G.est, G.rng, G.quant, G.count, 0, G.env_mis, G.trk, G.num_cu, hs);
+            X.k.render(X.S, L, G.est, G.rng, G.quant, G.half(), G.count, 0, G.env_mis, G.trk, G.num_cu, hs);
             le = hipGetLastError();
             if (le == hipSuccess) le = X.aux.join();
         }

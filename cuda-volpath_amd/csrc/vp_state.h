@@ -90,7 +90,10 @@ struct State
     hipStream_t own_stream  = nullptr;
     hipStream_t stream      = nullptr;
     SceneDev    S           = {};
-    bool        quant       = true;
+    bool        quant       = true;       // uchar cells and byte bound table; false: float OR binary16 cells, float bound table
+    int         vol_format  = VP_VOL_U8;  // what vp_init_volume was given (include/volpath.h VP_VOL_*)
+    bool        half() const { return vol_format == VP_VOL_F16; }   // binary16 cells: wherever quant decides, the float side
+    size_t      cells_bytes = 0;          // size of d_cells (vp_get_volume_info)
     bool        have_volume = false, have_env = false, have_sun = false, have_cam = false;
     void*       d_cells     = nullptr;
     void*       d_bounds    = nullptr;
@@ -315,7 +318,7 @@ int fail(int code, const char* fmt, ...);
 int        ensure_device();
 hipError_t create_internal_stream(hipStream_t* st);
 int        free_volume();
-int        do_init_volume(const void* h_volume, vp_extent ext, bool quantized, const vp_float3* bmin, const vp_float3* bmax);
+int        do_init_volume(const void* h_volume, vp_extent ext, int format, const vp_float3* bmin, const vp_float3* bmax);   // format: VP_VOL_*
 int        do_envmap(const vp_float4* data, int w, int h);
 int        build_env_tables();
 hipEvent_t get_event();   // an event from the pool, or a new one; nullptr if the runtime cannot create one (the launch then goes untimed)

@@ -13,7 +13,7 @@ int do_opacity(const float* dir)
     if (!G.d_opacity) HIPCHK(hipMalloc((void**)&G.d_opacity, n * sizeof(float)));
     SceneDev S = G.S;
     S.linear   = G.linear ? 1 : 0;
-    launch_opacity(S, G.quant, G.opacity_lds, dir, G.d_opacity, G.stream);
+    launch_opacity(S, G.quant, G.half(), G.opacity_lds, dir, G.d_opacity, G.stream);
     HIPCHK(hipGetLastError());
     // the integrator's copy: per voxel its clamped 2x2x2 neighbourhood, 32 bytes -- a lookup (frames > 10, more than 20 scatters:
     // 20 per sample on the frame-filling cloud) touches one cache line instead of four
@@ -135,7 +135,7 @@ int ensure_crawl_table(const Param* p, const float4** out)
     memset(k->S.sun_dir, 0, sizeof k->S.sun_dir); memset(k->S.sun_power, 0, sizeof k->S.sun_power); memset(k->S.sun_orig, 0, sizeof k->S.sun_orig);
     k->w = p->width; k->h = p->height;
     k->control = (G.est == VP_EST_DECOMP && G.trk == VP_TRACK_SPECTRAL) ? 1 : 0;
-    k->quant = G.quant; k->epoch = G.epoch; k->global = global ? 1 : 0;
+    k->quant = G.vol_format; k->epoch = G.epoch; k->global = global ? 1 : 0;
     const size_t need = (size_t)p->width * p->height * 2 * sizeof(float4);
     if (key != G.crawl_key || !G.d_crawl)
     {
@@ -182,7 +182,7 @@ int ensure_sun_clip(const unsigned short** out, float* ds)
     struct K { int nx, ny, nz, quant; float bmin[3], bmax[3], sun[3]; unsigned long long epoch; };
     std::vector<unsigned char> key(sizeof(K), 0);
     K* k = reinterpret_cast<K*>(key.data());
-    k->nx = G.S.nx; k->ny = G.S.ny; k->nz = G.S.nz; k->quant = G.quant; k->epoch = G.epoch;
+    k->nx = G.S.nx; k->ny = G.S.ny; k->nz = G.S.nz; k->quant = G.vol_format; k->epoch = G.epoch;
     memcpy(k->bmin, G.S.bmin, sizeof k->bmin); memcpy(k->bmax, G.S.bmax, sizeof k->bmax); memcpy(k->sun, G.S.sun_dir, sizeof k->sun);
     if (key != G.sunclip_key || !G.d_sunclip)
     {

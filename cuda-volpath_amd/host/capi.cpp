@@ -77,6 +77,9 @@ int vph_image_ops(float* rgba, int w, int h, int op, float arg)
 }
 // volume ingest; returned pointers are malloc'ed, release with vph_free
 void* vph_load_binary(const char* path, int* w, int* h, int* d, int quantized) { return loadBinaryFile(path, *w, *h, *d, quantized != 0); }
+void* vph_load_binary_as(const char* path, int* w, int* h, int* d, int format) { return loadBinaryFileAs(path, *w, *h, *d, format); }
+void* vph_load_vdb_as(const char* path, int* w, int* h, int* d, int format) { return loadVdbFileAs(path, *w, *h, *d, format); }
+void  vph_float_to_half(const float* src, size_t n, unsigned short* dst) { float_to_half_rne(src, n, dst); }
 void* vph_load_raw(const char* path, size_t size) { return loadRawFile(path, size); }
 void* vph_load_vdb(const char* path, int* w, int* h, int* d, int quantized) { return loadVdbFile(path, *w, *h, *d, quantized != 0); }
 int   vph_dump_dense(const char* path, const float* data, int nx, int ny, int nz) { return dump_dense_volume(path, data, nx, ny, nz) ? 0 : -1; }

@@ -22,6 +22,10 @@
 static void usage()
 {
     printf("volpath_render [--julia N | --bin file.bin | --vdb file.vdb] [--size W H] [--spp N] [--preset 0..12]\n"
+           "               [--volume-format u8|f32|f16]     how --bin / --vdb densities are stored on the device (vp_init_volume): u8, the\n"
+           "                                                default, quantises to bytes (8-byte cells); f32 keeps the floats (32-byte cells);\n"
+           "                                                f16 rounds them to IEEE binary16 (16-byte cells, rendered as the widened floats).\n"
+           "                                                --julia voxelises to bytes: u8 only\n"
            "               [--density D] [--g G] [--estimator decomp|global|bounded] [--brick B] [--rng samplerh|philox|philox7]\n"
            "               [--tracking spectral|scalar|multichannel] [--env passive|mis]\n"
            "               [--arith exact|fast]             fast: hardware log/exp/rcp/sqrt/sin/cos in the integrator, within the\n"
@@ -54,6 +58,8 @@ int main(int argc, char** argv)
     int         philox = 0;   // 0 sampler.h, 1 Philox2x32-10, 2 Philox2x32-7
     int         est = VP_EST_DECOMP, tracking = VP_TRACK_SPECTRAL, env_mode = VP_ENV_PASSIVE, arith = VP_ARITH_EXACT;
     std::string bin, vdb, out = "output0.ppm", devlist;
+    int         vol_format = VP_VOL_U8;
+    static_assert((int)VOLUME_U8 == (int)VP_VOL_U8 && (int)VOLUME_F32 == (int)VP_VOL_F32 && (int)VOLUME_F16 == (int)VP_VOL_F16, "the loaders' formats are vp_init_volume's");
     int         gpus = 1, aa = 0;   // (0: not given -- the contexts keep their default, VP_SUBPIXEL)
     bool        adaptive = false;
     float       noise_tol = 0.0f;
@@ -69,6 +75,15 @@ int main(int argc, char** argv)
         if (a == "--julia") { need(1); julia = atoi(argv[++i]); }
         else if (a == "--bin") { need(1); bin = argv[++i]; }
         else if (a == "--vdb") { need(1); vdb = argv[++i]; }
+        else if (a == "--volume-format")
+        {
+            need(1);
+            const char* f = argv[++i];
+            if (!strcmp(f, "u8")) vol_format = VP_VOL_U8;
+            else if (!strcmp(f, "f32")) vol_format = VP_VOL_F32;
+            else if (!strcmp(f, "f16")) vol_format = VP_VOL_F16;
+            else { fprintf(stderr, "unknown --volume-format %s (u8, f32 or f16)\n", f); usage(); return 2; }
+        }
         else if (a == "--size") { need(2); W = atoi(argv[++i]); H = atoi(argv[++i]); }
         else if (a == "--spp") { need(1); spp = atoi(argv[++i]); }
         else if (a == "--preset") { need(1); preset = atoi(argv[++i]); }
@@ -158,6 +173,11 @@ int main(int argc, char** argv)
     P.g       = g;
     if (!material_preset(P, preset)) { fprintf(stderr, "preset must be 0..12\n"); return 2; }
 
+    if (vol_format != VP_VOL_U8 && bin.empty() && vdb.empty())
+    {
+        fprintf(stderr, "--volume-format %s needs --bin or --vdb: --julia voxelises to bytes (u8)\n", vol_format == VP_VOL_F16 ? "f16" : "f32");
+        return 2;
+    }
     // ---- the GPUs: one context per rank (a single rank runs in the default context, as the reference's host would)
     if (gpus < 1) { usage(); return 2; }
     if (adaptive && gpus > 1)
@@ -201,8 +221,8 @@ int main(int argc, char** argv)
     // ---- volume (host.cpp:1330-1344): loaded once, uploaded to every rank (all read-only scene data is replicated)
     int   width = 0, height = 0, depth = 0;
     void* h_volume = nullptr;
-    if (!bin.empty()) h_volume = loadBinaryFile(bin.c_str(), width, height, depth, true);
-    else if (!vdb.empty()) h_volume = loadVdbFile(vdb.c_str(), width, height, depth, true);
+    if (!bin.empty()) h_volume = loadBinaryFileAs(bin.c_str(), width, height, depth, vol_format);
+    else if (!vdb.empty()) h_volume = loadVdbFileAs(vdb.c_str(), width, height, depth, vol_format);
     else
     {
         width = height = depth = julia;
@@ -228,7 +248,12 @@ int main(int argc, char** argv)
     {
         use(r);
         vp_set_bound_brick(brick);
-        init_cuda(h_volume, vp_extent{(size_t)width, (size_t)height, (size_t)depth}, true, &box_min, &box_max);
+        if (vol_format == VP_VOL_U8) init_cuda(h_volume, vp_extent{(size_t)width, (size_t)height, (size_t)depth}, true, &box_min, &box_max);
+        else if (vp_init_volume(h_volume, vp_extent{(size_t)width, (size_t)height, (size_t)depth}, vol_format, &box_min, &box_max))
+        {
+            fprintf(stderr, "%s\n", vp_last_error());
+            return 1;
+        }
         set_texture_filter_mode(true);
         copy_inv_model_matrix(identity, sizeof(identity));  // host.cpp:1350-1353
         copy_inv_view_matrix(m, sizeof(m));                 // host.cpp:617-623

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 void* loadRawFile(const char* filename, size_t size)
 {
@@ -31,6 +32,60 @@ void quantize_unit(const float* src, size_t n, VolumeType* dst)
 void quantize_by_max(const float* src, size_t n, float max_value, VolumeType* dst)
 {
     for (size_t i = 0; i < n; i++) dst[i] = VolumeType(std::max(0.0f, src[i]) / max_value * 255.0f);
+}
+
+void float_to_half_rne(const float* src, size_t n, uint16_t* dst)
+{
+    for (size_t i = 0; i < n; i++)
+    {
+        uint32_t x;
+        memcpy(&x, src + i, 4);
+        const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+        uint32_t h;
+        if (a > 0x7f800000u) { h = 0x7c00u | (a >> 13 & 0x3ffu); if (h == 0x7c00u) h++; }   // NaN: the payload's high bits, never infinity
+        else if (a >= 0x477ff000u) h = 0x7c00u;   // 65520 = halfway between 65504 and 2^16 ties to the even 2^16: infinity from there on
+        else if (a >= 0x38800000u)
+        {
+            // a normal half (|v| >= 2^-14): rebias the exponent, round the 13 dropped bits to nearest even; a carry moves the exponent
+            uint32_t r = a - 0x38000000u;
+            r += 0xfffu + ((r >> 13) & 1u);
+            h = r >> 13;
+        }
+        else if (a < 0x33000000u) h = 0;   // below 2^-25, half of the smallest subnormal: zero (2^-25 itself ties to the even zero below)
+        else
+        {
+            // a subnormal half: the 24-bit significand in units of 2^-24
+            const uint32_t e = a >> 23, m = (a & 0x7fffffu) | 0x800000u, shift = 126u - e;   // 14..24
+            uint32_t q = m >> shift;
+            const uint32_t rem = m & ((1u << shift) - 1u), halfway = 1u << (shift - 1u);
+            if (rem > halfway || (rem == halfway && (q & 1u))) q++;
+            h = q;   // (a carry out of the subnormal range gives 0x0400 = 2^-14: right)
+        }
+        dst[i] = (uint16_t)(sign | h);
+    }
+}
+
+static void* to_half(float* dataf, size_t total)
+{
+    uint16_t* data = reinterpret_cast<uint16_t*>(malloc(std::max<size_t>(total, 1) * sizeof(uint16_t)));
+    if (data) float_to_half_rne(dataf, total, data);
+    else fprintf(stderr, "Out of memory converting %zu voxels to binary16\n", total);
+    free(dataf);
+    return data;
+}
+void* loadBinaryFileAs(const char* filename, int& width, int& height, int& depth, int format)
+{
+    if (format == VOLUME_U8 || format == VOLUME_F32) return loadBinaryFile(filename, width, height, depth, format == VOLUME_U8);
+    if (format != VOLUME_F16) { fprintf(stderr, "Unknown volume format %d\n", format); return nullptr; }
+    float* dataf = reinterpret_cast<float*>(loadBinaryFile(filename, width, height, depth, false));
+    return dataf ? to_half(dataf, size_t(width) * size_t(height) * size_t(depth)) : nullptr;
+}
+void* loadVdbFileAs(const char* filename, int& width, int& height, int& depth, int format)
+{
+    if (format == VOLUME_U8 || format == VOLUME_F32) return loadVdbFile(filename, width, height, depth, format == VOLUME_U8);
+    if (format != VOLUME_F16) { fprintf(stderr, "Unknown volume format %d\n", format); return nullptr; }
+    float* dataf = reinterpret_cast<float*>(loadVdbFile(filename, width, height, depth, false));
+    return dataf ? to_half(dataf, size_t(width) * size_t(height) * size_t(depth)) : nullptr;
 }
 
 void* loadBinaryFile(const char* filename, int& width, int& height, int& depth, bool quantized)

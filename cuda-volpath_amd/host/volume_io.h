@@ -4,6 +4,7 @@
 #ifndef VOLPATH_HOST_VOLUME_IO_H
 #define VOLPATH_HOST_VOLUME_IO_H
 #include <cstddef>
+#include <cstdint>
 
 typedef unsigned char VolumeType;
 
@@ -21,6 +22,15 @@ void* loadVdbFile(const char* filename, int& width, int& height, int& depth, boo
 float* load_vdb(char* filename, int& width, int& height, int& depth, float& min_value, float& max_value);
 // the dump format of vdbloader/load_vdb.cpp:52-69 (Volume::dump): int32 nx,ny,nz then nx*ny*nz float32, x fastest
 bool dump_dense_volume(const char* filename, const float* data, int nx, int ny, int nz);
+// What a loader hands back, with the values of include/volpath.h VP_VOL_* (vp_init_volume takes the array as it is)
+enum VolumeFormat { VOLUME_U8 = 0, VOLUME_F32 = 1, VOLUME_F16 = 2 };
+// float -> IEEE binary16 bit patterns: round to nearest even, overflow to +-inf (from 65520 on), subnormal results produced, not
+// flushed; NaN stays NaN.  Integer arithmetic only: no compiler half type.
+void float_to_half_rne(const float* src, size_t n, uint16_t* dst);
+// the two loaders with the format named: VOLUME_U8 and VOLUME_F32 are quantized = true / false above; VOLUME_F16 is the float array
+// (loadVdbFile: the raw grid values, as for VOLUME_F32) rounded by float_to_half_rne, uint16_t per voxel.  nullptr for another format.
+void* loadBinaryFileAs(const char* filename, int& width, int& height, int& depth, int format);
+void* loadVdbFileAs(const char* filename, int& width, int& height, int& depth, int format);
 // the two quantisers on their own (host.cpp:955, :1009)
 void quantize_unit(const float* src, size_t n, VolumeType* dst);
 void quantize_by_max(const float* src, size_t n, float max_value, VolumeType* dst);

@@ -18,6 +18,7 @@ RNG_SAMPLERH, RNG_PHILOX, RNG_PHILOX7 = 0, 1, 2
 ENV_PASSIVE, ENV_MIS = 0, 1
 TRACK_SPECTRAL, TRACK_SCALAR, TRACK_MULTI_CHANNEL = 0, 1, 2
 ARITH_EXACT, ARITH_FAST = 0, 1
+VOL_U8, VOL_F32, VOL_F16 = 0, 1, 2   # VP_VOL_*: the formats of vp_init_volume
 # include/volpath.h VP_ARITH_FAST_REL_L2: the stated bound on ||I_fast - I_exact||_2 / ||I_exact||_2 (mean images of 1024 frames)
 ARITH_FAST_REL_L2 = 2e-3
 # include/volpath.h VP_SUBPIXEL_MAX: the largest sub-pixel factor (set_subpixel takes 1, 2, 4, 8)
@@ -28,7 +29,7 @@ PART1_SYMBOLS = ["init_cuda", "set_texture_filter_mode", "free_cuda_buffers", "p
                  "free_envmap", "set_sun", "copy_inv_view_matrix", "copy_inv_model_matrix", "init_rng", "free_rng",
                  "render_kernel", "scale", "gamma_correct"]
 PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_device", "vp_set_stream", "vp_get_stream", "vp_synchronize",
-                 "vp_set_estimator", "vp_set_rng", "vp_set_envmap_sampling", "vp_get_env_tables", "vp_set_lookahead", "vp_set_tracking", "vp_set_bound_brick", "vp_set_shard", "vp_render_frames",
+                 "vp_set_estimator", "vp_set_rng", "vp_set_envmap_sampling", "vp_get_env_tables", "vp_set_lookahead", "vp_set_tracking", "vp_set_bound_brick", "vp_set_shard", "vp_render_frames", "vp_init_volume", "vp_get_volume_info",
                  "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists",
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
@@ -44,6 +45,12 @@ class Float3(C.Structure):
 
 class Dim3(C.Structure):
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("z", C.c_uint32)]
+
+
+class VolumeInfo(C.Structure):
+    """vp_volume_info"""
+    _fields_ = [("format", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("cell_bytes", C.c_int),
+                ("cells_bytes", C.c_uint64)]
 
 
 class Extent(C.Structure):
@@ -158,6 +165,8 @@ def lib():
         L.vp_tile_owner.argtypes = [C.c_uint, C.c_uint, C.c_int]
         L.init_cuda.argtypes = [C.c_void_p, Extent, C.c_bool, C.POINTER(Float3), C.POINTER(Float3)]
         L.init_cuda.restype = None
+        L.vp_init_volume.argtypes = [C.c_void_p, Extent, C.c_int, C.POINTER(Float3), C.POINTER(Float3)]
+        L.vp_get_volume_info.argtypes = [C.POINTER(VolumeInfo)]
         L.set_texture_filter_mode.argtypes = [C.c_bool]
         L.precompute_opacity.argtypes = [C.POINTER(C.c_float)]
         L.init_envmap.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -257,20 +266,32 @@ def synchronize():
 
 
 def init_volume(grid, box=None, brick=1, linear=True):
-    """init_cuda + set_texture_filter_mode as host.cpp:1336-1344 calls them. grid[k][j][i], uint8 or float32."""
+    """init_cuda + set_texture_filter_mode as host.cpp:1336-1344 calls them. grid[k][j][i]: uint8, float32, or float16 (a binary16
+    volume, vp_init_volume(VP_VOL_F16): the bits of the float32 volume grid.astype(float32) from 16-byte cells); any other dtype is
+    converted to float32."""
     L = lib()
     grid = np.ascontiguousarray(grid)
     quantized = grid.dtype == np.uint8
-    if not quantized:
+    if not quantized and grid.dtype != np.float16:
         grid = np.ascontiguousarray(grid, np.float32)
     nz, ny, nx = grid.shape
     _chk(L.vp_set_bound_brick(brick))
     ext = Extent(nx, ny, nz)
-    if box is None:
+    if grid.dtype == np.float16:
+        bmin, bmax = (None, None) if box is None else (C.byref(Float3(*box[0])), C.byref(Float3(*box[1])))
+        _chk(L.vp_init_volume(_p(grid), ext, VOL_F16, bmin, bmax))
+    elif box is None:
         L.init_cuda(_p(grid), ext, quantized, None, None)
     else:
         L.init_cuda(_p(grid), ext, quantized, C.byref(Float3(*box[0])), C.byref(Float3(*box[1])))
     L.set_texture_filter_mode(bool(linear))
+
+
+def volume_info():
+    """vp_get_volume_info: the current volume's format (VOL_*), extent, bytes per packed cell and bytes of all cells on the device"""
+    v = VolumeInfo()
+    _chk(lib().vp_get_volume_info(C.byref(v)))
+    return {"format": v.format, "nx": v.nx, "ny": v.ny, "nz": v.nz, "cell_bytes": v.cell_bytes, "cells_bytes": v.cells_bytes}
 
 
 def init_envmap(env):

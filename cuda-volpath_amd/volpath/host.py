@@ -29,6 +29,11 @@ def lib():
         L.vph_load_raw.argtypes = [C.c_char_p, C.c_size_t]
         L.vph_load_vdb.restype = C.c_void_p
         L.vph_load_vdb.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+        L.vph_load_binary_as.restype = C.c_void_p
+        L.vph_load_binary_as.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+        L.vph_load_vdb_as.restype = C.c_void_p
+        L.vph_load_vdb_as.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+        L.vph_float_to_half.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         L.vph_dump_dense.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.vph_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]
         L.vph_free.argtypes = [C.c_void_p]
@@ -99,6 +104,31 @@ def load_binary(path, quantized=True):
     return arr
 
 
+VOL_U8, VOL_F32, VOL_F16 = 0, 1, 2   # host/volume_io.h VolumeFormat = include/volpath.h VP_VOL_*
+_VOL_DTYPES = {VOL_U8: np.uint8, VOL_F32: np.float32, VOL_F16: np.float16}
+
+
+def load_binary_as(path, fmt):
+    """loadBinaryFileAs: the dense dump as uint8, float32 or float16 [nz, ny, nx]; None on error (an unknown format included)"""
+    w, h, d = C.c_int(), C.c_int(), C.c_int()
+    ptr = lib().vph_load_binary_as(path.encode(), C.byref(w), C.byref(h), C.byref(d), int(fmt))
+    if not ptr:
+        return None
+    dt = np.dtype(_VOL_DTYPES[fmt])
+    n = w.value * h.value * d.value
+    raw = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n * dt.itemsize,)).copy()
+    lib().vph_free(ptr)
+    return raw.view(dt).reshape(d.value, h.value, w.value)
+
+
+def float_to_half(values):
+    """float_to_half_rne: float32 -> binary16 (round to nearest even), returned as a float16 array of the same shape"""
+    v = np.ascontiguousarray(values, np.float32)
+    out = np.empty(v.shape, np.uint16)
+    lib().vph_float_to_half(_p(v), v.size, _p(out))
+    return out.view(np.float16)
+
+
 def dump_dense(path, vol):
     v = np.ascontiguousarray(vol, np.float32)
     nz, ny, nx = v.shape
@@ -110,6 +140,12 @@ def quantize(vol, max_value=0.0):
     out = np.empty(v.shape, np.uint8)
     lib().vph_quantize(_p(v), v.size, max_value, _p(out))
     return out
+
+
+def load_vdb_as(path, fmt):
+    w, h, d = C.c_int(), C.c_int(), C.c_int()
+    ptr = lib().vph_load_vdb_as(path.encode(), C.byref(w), C.byref(h), C.byref(d), int(fmt))
+    return ptr or None
 
 
 def load_vdb(path, quantized=True):

@@ -224,6 +224,22 @@ int vp_subpixel_offset(unsigned x, unsigned y, int frame, int s, int* i, int* j)
 int vp_get_env_tables(float* cdf_y, float* cdf_x, float* pdfnorm_alt);
 /* brick edge (power of two, 1 = the reference's per-voxel table) used by the NEXT init_cuda */
 int vp_set_bound_brick(int brick);
+
+/* Volume formats.  vp_init_volume is init_cuda with the format named and an error code instead of exit():
+ * VP_VOL_U8 is init_cuda(quantized = true), VP_VOL_F32 init_cuda(quantized = false), the same code path, the same bits.
+ * VP_VOL_F16: h_volume holds IEEE binary16 values (x fastest).  THE DEFINITION: a binary16 volume h renders, in every mode, exactly
+ * what the float volume widen(h) renders, widen = each element converted to binary32 (exact; subnormal halves are NOT flushed) --
+ * images, work counters, the bound table (float (max, min) pairs of the widened values), the opacity table, pixel classes and every
+ * certificate.  The filter is the float filter applied to the widened taps.  Only the stored cell differs: 8 halves in 16 bytes
+ * instead of 8 floats in 32, one 16-byte load per fetch instead of two; the forms that exist for uchar volumes alone (the brick table in
+ * LDS, the staged opacity march, the segment table, local-majorant exit flights) stay theirs.  Finite values are the contract.
+ * VP_E_ARG before the device is touched: NULL volume, unknown format, an empty extent.  boxmin / boxmax may be NULL as in init_cuda. */
+enum { VP_VOL_U8 = 0, VP_VOL_F32 = 1, VP_VOL_F16 = 2 };
+int vp_init_volume(const void* h_volume, vp_extent ext, int format, const vp_float3* bmin, const vp_float3* bmax);
+/* what the current volume occupies: cell_bytes per packed 2x2x2 neighbourhood cell (8, 32, 16), cells_bytes of them on the device
+ * (nx ny nz cells; with VP_CELL_BRICKS=1 the 4x4x4-brick-padded count).  VP_E_STATE without a volume. */
+typedef struct { int format; int nx, ny, nz; int cell_bytes; uint64_t cells_bytes; } vp_volume_info;
+int vp_get_volume_info(vp_volume_info* out);
 /* Pixel-tile sharding: this context renders the 8x8 pixel tiles (tx, ty) with vp_tile_owner(tx, ty, world) == rank: within
  * a tile row every world-th tile, the rows shifted against each other by a hash of the row index, so that neither columns
  * nor rows nor diagonals of the image belong to one rank whatever tiles_x % world is. */
