@@ -1615,6 +1615,7 @@ __global__ __launch_bounds__(256) void approach_local_k(SceneDev S, LaunchDev L)
 // computed per launch with the integrator's own expressions: they depend on Param), and makes what is left: the draws, the
 // logarithms, the sums and the compares.  Same hand-over, same bits (uchar bound tables; float tables keep approach_local_k).
 #define VP_SEG_CAP 96   // records per pixel: a box diagonal of 4.7 at 0.05 per segment; a longer chain is handed over where the table ends
+// (chains that reach the cap, inside a long box and in front of a far one: tests/test_long_rays_gpu.py, record by record through vp_get_segment_table)
 // layout per pixel slot, 2 * VP_SEG_CAP float4: [n] = (t_near, t_far, bound byte | stop << 8, t_empty at the segment's start),
 // [VP_SEG_CAP + n] = the segment's origin (read once per sample, at the hand-over)
 

@@ -110,6 +110,7 @@ __global__ __launch_bounds__(256) void crawl_table_k(SceneDev S, unsigned width,
     float t_left = S.linear ? certified_empty_distance(S, ro, rd, danger, cls) : 0.0f;
     if (cls == 1.0f && chord_has_positive_minimum<QUANT>(S, ro, rd)) cls = 0.0f;
     unsigned segs = 0, draws = 0;
+    // (cameras 35 to 60 units away reach the cap below: tests/test_long_rays_gpu.py against a binary32 restatement and the oracle)
     for (; segs < 700u; segs++)   // far below the bounded kernel's 800-segment cap, and both counts stay within 16 bits
     {
         float t_near, tf;

@@ -760,6 +760,13 @@ int vp_render_class_time_ms(double ms[3], unsigned pixels[3], int reset)
     }
     return VP_OK;
 }
+// the decomposition walk's segment table where this configuration has one (do_render asks the same): vp_prepare and vp_get_segment_table
+static int prepare_segment_table(const Param* p, const float4* table, const float4** seg)
+{
+    *seg = nullptr;
+    if (G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && approach_possible(table, G.n_general)) return ensure_segment_table(p, table, seg);
+    return VP_OK;
+}
 int vp_get_pixel_lists(const Param* p, uint32_t* dst, size_t count, unsigned counts[3])
 {
     int rc = vp_prepare(p);
@@ -796,9 +803,25 @@ int vp_prepare(const Param* p)
     if ((rc = ensure_pixel_lists(p, table, sh))) return rc;
     if (G.have_sun && (rc = ensure_sun_clip(&sc, &ds))) return rc;
     if (G.est == VP_EST_GLOBAL && G.n_light && (rc = ensure_thr_table(p, &thr))) return rc;
-    // (the decomposition walk's segment table: do_render)
-    if (G.est == VP_EST_DECOMP && G.approach_fshift_max >= 6 && approach_possible(table, G.n_general) && (rc = ensure_segment_table(p, table, &seg))) return rc;
+    if ((rc = prepare_segment_table(p, table, &seg))) return rc;
     HIPCHK(hipStreamSynchronize(G.stream));
+    return VP_OK;
+}
+int vp_get_segment_table(const Param* p, float* dst, size_t count, int* cap)
+{
+    if (cap) *cap = (int)(segment_table_records() / 2u);
+    if (!dst) return VP_OK;
+    int rc = vp_prepare(p);
+    if (rc) return rc;
+    // what vp_prepare has just built, if this configuration has a table at all (both tables are found cached)
+    const float4 *table = nullptr, *seg = nullptr;
+    const Param fine = subpixel_param(p);
+    if ((rc = ensure_crawl_table(&fine, &table))) return rc;
+    if ((rc = prepare_segment_table(p, table, &seg))) return rc;
+    if (!seg) return fail(VP_E_STATE, "no segment table in this configuration (decomposition estimator on a uchar volume, approach walk and table switched on)");
+    const size_t need = (size_t)G.n_general * segment_table_records() * 4;
+    if (count < need) return fail(VP_E_ARG, "segment table needs %zu floats", need);
+    HIPCHK(hipMemcpy(dst, seg, need * sizeof(float), hipMemcpyDeviceToHost));
     return VP_OK;
 }
 int vp_reserve_frames(const Param* p, int nframes)

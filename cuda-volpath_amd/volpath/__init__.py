@@ -30,7 +30,7 @@ PART1_SYMBOLS = ["init_cuda", "set_texture_filter_mode", "free_cuda_buffers", "p
                  "render_kernel", "scale", "gamma_correct"]
 PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_device", "vp_set_stream", "vp_get_stream", "vp_synchronize",
                  "vp_set_estimator", "vp_set_rng", "vp_set_envmap_sampling", "vp_get_env_tables", "vp_set_lookahead", "vp_set_tracking", "vp_set_bound_brick", "vp_set_shard", "vp_render_frames", "vp_init_volume", "vp_get_volume_info",
-                 "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists",
+                 "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists", "vp_get_segment_table",
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_intersect_box",
@@ -147,6 +147,7 @@ def lib():
         L.vp_set_subpixel.argtypes = [C.c_int]
         L.vp_subpixel_offset.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.vp_get_pixel_lists.argtypes = [C.POINTER(Param), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.vp_get_segment_table.argtypes = [C.POINTER(Param), C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
         L.vp_julia_voxelize.argtypes = [C.c_int, C.c_void_p]
         L.vp_cloud_voxelize.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
         L.vp_test_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
@@ -593,6 +594,19 @@ def pixel_table(P):
     out = np.empty((P.height, P.width, 8), np.float32)
     _chk(lib().vp_get_pixel_table(C.byref(P), _p(out), out.size))
     return out
+
+
+def segment_table(P):
+    """(records, origins, cap): float32 [n_general, cap, 4] and [n_general, cap, 4], the per-view segment table of the decomposition
+    estimator's approach walk for the general pixels in the order of pixel_lists(P)[0]; records[..., 2] viewed as uint32 = the brick's
+    maximum byte | stop << 8; what lies behind a chain's stop record was never written (include/volpath.h vp_get_segment_table).
+    Raises VolpathError where the configuration has no table."""
+    cap = C.c_int()
+    _chk(lib().vp_get_segment_table(C.byref(P), None, 0, C.byref(cap)))
+    n = len(pixel_lists(P)[0])
+    out = np.empty((n, 2, cap.value, 4), np.float32)
+    _chk(lib().vp_get_segment_table(C.byref(P), _p(out), out.size, C.byref(cap)))
+    return out[:, 0], out[:, 1], cap.value
 
 
 def null_collision_table(P, count):

@@ -427,6 +427,15 @@ int vp_get_opacity(float* dst, size_t count);
  * certified to meet only empty cells, [5] the pixel class (0 general; 1 the whole chord is certified empty: light kernel; 2 the
  * camera ray misses the box: one constant per pixel), [6..7] unused.  Test hook for the certificates. */
 int vp_get_pixel_table(const Param* p, float* dst, size_t count);
+/* test hook: the per-view segment table of the decomposition estimator's approach walk (approach_segments_k), built as vp_prepare
+ * builds it.  *cap = the records a pixel's chain can hold.  dst (count >= n_general * 2 * *cap * 4 floats; NULL: *cap only, nothing is built)
+ * receives, for slot s = 0 .. n_general - 1 -- the order the walk reads them in, which is the order of the general pixels in
+ * vp_get_pixel_lists: slot s is the pixel dst[s] of that call -- 2 * *cap records of 4 floats: record n < *cap = (t_near, t_far,
+ * bits: the brick's maximum byte | stop << 8, certified-empty distance left at the segment's start), record *cap + n = the origin
+ * of segment n (x, y, z, 0).  A chain ends at its first record with the stop bit; the records behind it are not written.
+ * VP_E_STATE where this configuration has no table: float and binary16 volumes, the other estimators, VP_NO_APPROACH_TABLE=1, or
+ * no approach walk at all. */
+int vp_get_segment_table(const Param* p, float* dst, size_t count, int* cap);
 /* Counter-based streams (VP_RNG_PHILOX / VP_RNG_PHILOX7): a shadow ray draws from a sub-stream of its own, so the path's later
  * draws do not depend on the number of steps it takes, and a sun shadow ray ends once it has only empty cells in front of it.
  * dst[cell] (x fastest, count >= nx*ny*nz) = that distance from anywhere in the cell, in units of *step (world units), or

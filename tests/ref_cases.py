@@ -10,6 +10,7 @@ import hashlib
 import numpy as np
 
 import degenerate_cases as DC
+import long_ray_cases as LC
 import scenes
 
 EST_GLOBAL, EST_DECOMP, EST_BOUNDED = 0, 1, 2      # oracle_lib.EST_* / vp.EST_* / ref_render's `which`
@@ -60,6 +61,8 @@ def grid(name, oracle):
         return oracle.julia(int(name[5:]))
     if name in ("odd_u8", "solid7"):
         return DC.grid(name, oracle)
+    if name == "long_box":
+        return LC.long_box()
     return {"blob_f32": scenes.blob_volume_f32, "blob_u8": scenes.blob_volume_u8, "soft_u8": soft_u8,
             "tiny": lambda: np.array([[[0, 255], [128, 7], [3, 90]]], np.uint8),           # nz = 1, ny = 3, nx = 2
             "solid16": lambda: np.full((16, 16, 16), 255, np.uint8),
@@ -92,6 +95,11 @@ def _degenerate(name, grid, position, axis, sign, **kw):
     return _case(name, grid=grid, kw=dict(density=60.0), cam=DC.camera(grid, position, axis, sign), size=(DC.W, DC.H), **kw)
 
 
+def _far(name, **kw):
+    """a telephoto camera of tests/long_ray_cases.py, `name` units in front of the Julia box, at 16x12 in the medium of _degenerate"""
+    return _case("far_" + name, grid=LC.FAR_GRID, kw=dict(density=60.0), cam=LC.far_camera(name), size=(DC.W, DC.H), frames=(0, 11), **kw)
+
+
 # frames: 10 is the last that never reads the optical-depth table, 11 the first that may (spp > 10, kernel.cu:2183)
 RENDERS = [
     _case("julia_default", frames=(0, 1, 10, 11, 12), golden=ALL_EST, gframes=(0, 1, 11, 12)),
@@ -119,6 +127,15 @@ RENDERS = [
     _degenerate("deg_centre", "solid7", "centre", 1, 1),
     _degenerate("deg_sun_zenith", "julia32", "outside", 2, -1, sun=DC.SUNS["+y"], frames=(0, 11), golden=(EST_DECOMP, EST_GLOBAL)),
     _degenerate("deg_sun_x", "julia32", "outside", 0, 1, sun=DC.SUNS["+x"], frames=(0, 11)),
+    # long rays (tests/long_ray_cases.py): the restart crawl in front of the box over 699 and over more than 700 segments of 0.05 (the
+    # HIP path tabulates 700 of them per pixel and walks the rest), the bounded kernel's segment count running into max_depth = 800
+    # on the way (from 38.5 units some paths arrive, from 41.5 none: heat 0.8, no radiance), and a box seven units long that is
+    # empty between its ends (110 and more restart segments inside the box before the first brick that holds anything)
+    _far("d34.97"),
+    _far("d35.2", golden=(EST_DECOMP, EST_BOUNDED)),
+    _far("d38.5"),
+    _far("d41.5", golden=(EST_BOUNDED,)),
+    _case("long_box", grid="long_box", box=LC.LONG_BOX, cam=LC.long_camera("axis"), frames=(0, 1, 11), golden=(EST_DECOMP,), gframes=(0, 11)),
 ]
 VARIANT_RENDERS = [
     _case("mis_black_texel", env="black_texel", kw=dict(density=150.0, g=0.6), frames=(8, 12), variant="_mis", golden=ALL_EST),

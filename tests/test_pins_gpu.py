@@ -23,33 +23,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 PI = np.pi
-CAM = np.array([0.0, 0.207912, 0.978148, 3.922986, 0.0, 0.978148, -0.207912, -0.782739, -1.0, 0.0, 0.0, 0.03])  # H4
 
 
-def _camera_rays(W, H, cam=None):
-    """kernel.cu:1977-1987 in float64: origin and unit direction per pixel, arrays [H, W, 3]"""
-    M = (CAM if cam is None else np.asarray(cam, np.float64)).reshape(3, 4)
-    x = np.arange(W)[None, :].repeat(H, 0).astype(np.float64)
-    y = np.arange(H)[:, None].repeat(W, 1).astype(np.float64)
-    u = (x * 2 - W) / W
-    v = (y * 2 - H) / W
-    z = -1.0 / np.tan(54.43 * 0.00872664626)
-    dv = np.stack([u, v, np.full_like(u, z)], -1)
-    d = dv @ M[:, :3].T
-    d /= np.linalg.norm(d, axis=-1, keepdims=True)
-    o = np.broadcast_to(M[:, 3], d.shape)
-    return o, d
-
-
-def _slab(o, d, bmin=-1.0, bmax=1.0):
-    """intersectBox kernel.cu:654-680 in float64"""
-    with np.errstate(divide="ignore", invalid="ignore"):
-        inv = 1.0 / d
-        tb = inv * (bmin - o)
-        tt = inv * (bmax - o)
-    tmin = np.minimum(tt, tb).max(-1)
-    tmax = np.maximum(tt, tb).min(-1)
-    return (tmax > tmin) & (tmax >= 1e-3), tmin, tmax
+from long_ray_cases import CAM, camera_rays64 as _camera_rays, fmax32 as _fmax32, fmin32 as _fmin32, slab64 as _slab   # (shared with the CPU tests)
 
 
 @pytest.fixture
@@ -154,18 +130,6 @@ def test_intersect_box_matches_float64_slab_test(vp):
     # tolerance 2e-6 relative + 2e-6 absolute (three binary32 operations per slab)
     assert np.allclose(tn[fin], tmin[fin], rtol=2e-6, atol=2e-6) and np.allclose(tf[fin], tmax[fin], rtol=2e-6, atol=2e-6)
     assert np.array_equal(np.isinf(tn), np.isinf(tmin)) and np.array_equal(np.isinf(tf), np.isinf(tmax))
-
-
-def _fmin32(a, b):
-    """fminf on binary32: the operand that is not NaN (np.fmin); of two zeros the negative one -- the reference's device orders
-    -0 below +0 in min and max (PTX ISA, min.f32 / max.f32), where C leaves the choice open"""
-    r = np.fmin(a, b)
-    return np.where((a == 0) & (b == 0), np.where(np.signbit(a) | np.signbit(b), np.float32(-0.0), np.float32(0.0)), r).astype(np.float32)
-
-
-def _fmax32(a, b):
-    r = np.fmax(a, b)
-    return np.where((a == 0) & (b == 0), np.where(np.signbit(a) & np.signbit(b), np.float32(-0.0), np.float32(0.0)), r).astype(np.float32)
 
 
 def test_intersect_box_is_the_binary32_slab_test_bit_for_bit(vp):
