@@ -670,6 +670,10 @@ static inline f3 frame_to_world(const frame_t* f, f3 c)
  * bit 1: Henyey-Greenstein sampling with cos(theta) clamped to [-1, 1] instead of [0, 1] (quirk Q1). */
 static int g_what_if = 0;
 void vpo_debug_set_what_if(int mask) { g_what_if = mask; }
+/* test hook: Henyey-Greenstein samples whose cos(theta) was a NaN before the clamp (g = 1 and a draw of exactly 0: 0 / 0); the
+ * clamp of kernel.cu:590, fmaxf(0, fminf(1, NaN)), makes it 1 */
+static uint64_t g_hg_nan_clamp = 0;
+uint64_t vpo_debug_hg_nan_clamp(void) { return __atomic_load_n(&g_hg_nan_clamp, __ATOMIC_RELAXED); }
 /* HGPhaseFunction::sample kernel.cu:580-598 (quirk Q1: cos_theta clamped to [0,1]) */
 static f3 hg_sample_local(float g, float rnd0, float rnd1)
 {
@@ -679,6 +683,7 @@ static f3 hg_sample_local(float g, float rnd0, float rnd1)
         float s   = 2.0f * rnd0 - 1.0f;
         float f   = (1.0f - g * g) / (1.0f + g * s);
         cos_theta = (0.5f / g) * (1.0f + g * g - f * f);
+        if (cos_theta != cos_theta) __atomic_fetch_add(&g_hg_nan_clamp, 1, __ATOMIC_RELAXED);
         cos_theta = fmaxf((g_what_if & 2) ? -1.0f : 0.0f, fminf(1.0f, cos_theta));
     }
     else
@@ -770,6 +775,24 @@ static f3 tr_spectral(const vpo_scene* S, f3 bmin, f3 bmax, f3 start, f3 end, fl
     rng_leave_shadow(rng);
     return mk3((float)(1 - xterm), (float)(1 - yterm), (float)(1 - zterm));
 }
+
+/* test hook: samples in which a NONZERO throughput component was subnormal at a collision of the spectral integrators (counted once
+ * per sample; tests/test_extreme_media_cpu.py: the case that claims to run a channel through the subnormals does) */
+static uint64_t g_subnormal_throughput = 0;
+uint64_t vpo_debug_subnormal_throughput(void) { return __atomic_load_n(&g_subnormal_throughput, __ATOMIC_RELAXED); }
+static int subnormal_component(f3 t)
+{
+    return fpclassify(t.x) == FP_SUBNORMAL || fpclassify(t.y) == FP_SUBNORMAL || fpclassify(t.z) == FP_SUBNORMAL;
+}
+#define NOTE_SUBNORMAL(seen, t)                                               \
+    do                                                                        \
+    {                                                                         \
+        if (!(seen) && subnormal_component(t))                                \
+        {                                                                     \
+            (seen) = 1;                                                       \
+            __atomic_fetch_add(&g_subnormal_throughput, 1, __ATOMIC_RELAXED); \
+        }                                                                     \
+    } while (0)
 
 /* test hook: how often the zero-pdf `continue` of the MIS block was taken (it needs a draw of exactly 0) */
 static uint64_t g_mis_zero_pdf = 0;
@@ -875,6 +898,7 @@ static void sample_decomp(const vpo_scene* S, const vpo_param* P, uint32_t x, ui
 
     f3 radiance   = mk3(0, 0, 0);
     f3 throughput = mk3(1, 1, 1);
+    int subnormal_seen = 0;
 
     f3    sigma_t_spectral = mk3(P->sigma_t[0], P->sigma_t[1], P->sigma_t[2]);
     f3    sigma_s_spectral = mul3(sigma_t_spectral, mk3(P->albedo[0], P->albedo[1], P->albedo[2]));
@@ -945,6 +969,7 @@ static void sample_decomp(const vpo_scene* S, const vpo_param* P, uint32_t x, ui
                 sigma_s_den = sub3(muls(sigma_s_spectral, den), mul3(sigma_c_spectral, mk3(P->albedo[0], P->albedo[1], P->albedo[2])));
             f3 sigma_null_den = sub3(mk3(sigma_t_prime, sigma_t_prime, sigma_t_prime), sigma_t_den);
 
+            NOTE_SUBNORMAL(subnormal_seen, throughput);
             float Ps = fabsf(sigma_t_den.x * throughput.x) + fabsf(sigma_t_den.y * throughput.y) +
                        fabsf(sigma_t_den.z * throughput.z);
             float Pn = fabsf(sigma_null_den.x * throughput.x) + fabsf(sigma_null_den.y * throughput.y) +
@@ -1039,6 +1064,7 @@ static void sample_bounded(const vpo_scene* S, const vpo_param* P, uint32_t x, u
 
     f3 radiance   = mk3(0, 0, 0);
     f3 throughput = mk3(1, 1, 1);
+    int subnormal_seen = 0;
     f3    sigma_t_spectral = mk3(P->sigma_t[0], P->sigma_t[1], P->sigma_t[2]);
     f3    sigma_s_spectral = mul3(sigma_t_spectral, mk3(P->albedo[0], P->albedo[1], P->albedo[2]));
     float max_sigma_t      = max_of3(sigma_t_spectral);
@@ -1082,6 +1108,7 @@ static void sample_bounded(const vpo_scene* S, const vpo_param* P, uint32_t x, u
             f3    sigma_t_den    = muls(sigma_t_spectral, den);
             f3    sigma_s_den    = muls(sigma_s_spectral, den);
             f3    sigma_null_den = sub3(mk3(sigma_t_prime, sigma_t_prime, sigma_t_prime), sigma_t_den);
+            NOTE_SUBNORMAL(subnormal_seen, throughput);
             float Ps = fabsf(sigma_t_den.x * throughput.x) + fabsf(sigma_t_den.y * throughput.y) +
                        fabsf(sigma_t_den.z * throughput.z);
             float Pn = fabsf(sigma_null_den.x * throughput.x) + fabsf(sigma_null_den.y * throughput.y) +
@@ -1153,6 +1180,7 @@ static void sample_global(const vpo_scene* S, const vpo_param* P, uint32_t x, ui
 
     f3 radiance   = mk3(0, 0, 0);
     f3 throughput = mk3(1, 1, 1);
+    int subnormal_seen = 0;
     f3    sigma_t_spectral = mk3(P->sigma_t[0], P->sigma_t[1], P->sigma_t[2]);
     f3    sigma_s_spectral = mul3(sigma_t_spectral, mk3(P->albedo[0], P->albedo[1], P->albedo[2]));
     float max_sigma_t      = max_of3(sigma_t_spectral);
@@ -1190,6 +1218,7 @@ static void sample_global(const vpo_scene* S, const vpo_param* P, uint32_t x, ui
             f3 sigma_s_den    = muls(sigma_s_spectral, den);
             f3 sigma_null_den = sub3(mk3(sigma_t_prime, sigma_t_prime, sigma_t_prime), sigma_t_den);
             float Pa = 0.0f;
+            NOTE_SUBNORMAL(subnormal_seen, throughput);
             float Ps = fabsf(sigma_t_den.x * throughput.x) + fabsf(sigma_t_den.y * throughput.y) +
                        fabsf(sigma_t_den.z * throughput.z);
             float Pn = fabsf(sigma_null_den.x * throughput.x) + fabsf(sigma_null_den.y * throughput.y) +

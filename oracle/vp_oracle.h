@@ -137,6 +137,8 @@ void     vpo_build_env_tables_pdf(const float* env, int width, int height, float
 void     vpo_debug_set_what_if(int mask); /* test hook: variants of the restatement for the radiometric pin (0 = the restatement; vp_oracle.c) */
 uint64_t vpo_debug_shadow_overflow(void); /* test hook: shadow rays that drew more than the 2^20 pairs of their sub-stream (must stay 0) */
 uint64_t vpo_debug_mis_zero_pdf(void); /* test hook: zero-pdf `continue`s taken so far (kernel.cu:2266) */
+uint64_t vpo_debug_subnormal_throughput(void); /* test hook: samples whose throughput had a nonzero subnormal component at a collision */
+uint64_t vpo_debug_hg_nan_clamp(void); /* test hook: phase-function samples whose cos(theta) was a NaN before the clamp (g = 1, a draw of 0) */
 void     vpo_eval_envmap(const vpo_scene* S, const float dir[3], float rgb[3]);
 void     vpo_hg_sample(float g, const float n[3], float u0, float u1, float out[3]);
 float    vpo_hg_eval(float g, float cos_theta);

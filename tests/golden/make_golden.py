@@ -24,6 +24,10 @@ Sources, by authority:
                      definitions of oracle/refshim (texture fetch rule, elementary functions).  Data only; inputs are rebuilt from
                      tests/ref_cases.py and tests/scenes.py.  Tables above 16 KiB are kept as the SHA-256 of their bytes plus every
                      97th element.
+  ref_media.npz      the same libraries (shipped build) on the extreme media of tests/extreme_media.py: g = +-1 and both sides of the
+                     |g| > 1e-6f switch, dead, underflowing and amplifying channels, zero and wide sigma_t, sigma_t' zero and
+                     subnormal.  REFERENCE-MADE accumulators of the estimators tests/test_extreme_media_cpu.py names
+                     (golden_estimators); held to 200 KiB like ref_kernel.npz.
 """
 import ctypes as C
 import json
@@ -136,10 +140,23 @@ def ref_kernel():
     np.savez_compressed(os.path.join(HERE, "ref_kernel.npz"), **out)
 
 
+def ref_media():
+    """tests/golden/ref_media.npz, computed by the reference libraries (never by the oracle)"""
+    import ref_cases as RC
+    import ref_lib
+    import test_extreme_media_cpu as T
+    assert ref_lib.status("") == "ok", f"{ref_lib.path('')} is missing: make -C oracle ref"
+    out = {}
+    for name, thunk in T.entries(RC.ReferenceBackend(ref_lib, O)):
+        RC.pack(out, name, thunk())
+    np.savez_compressed(os.path.join(HERE, "ref_media.npz"), **out)
+
+
 if __name__ == "__main__":
     O.build()
     hosek_ref()
     oracle_renders()
     ref_julia_silhouette()
     ref_kernel()
+    ref_media()
     print("golden fixtures written to", HERE)

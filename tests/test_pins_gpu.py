@@ -20,6 +20,8 @@ Tolerances are stated at each assert (DESIGN.md section 2 lists them).
 import numpy as np
 import pytest
 
+import extreme_media as EM
+
 pytestmark = pytest.mark.gpu
 
 PI = np.pi
@@ -811,7 +813,7 @@ def test_null_collision_table_is_the_float32_recurrence(vp):
     moved = 0
     for sigma_t, density, g in (((1, 1, 1), 800.0, 0.877), ((1, 1, 1), 333.3, 0.0), ((0.953, 1.0, 0.843), 800.0, 0.877),
                                 ((0.3, 0.7, 0.9), 57.3, -0.4), ((1, 1, 1), 1.0e-3, 0.5), ((1, 1, 1), 209.0, 0.877),
-                                ((0.3, 0.7, 1.0), 246.0, -0.4)):
+                                ((0.3, 0.7, 1.0), 246.0, -0.4)) + EM.finite_null_collision_media():
         P = vp.make_param(8, 8, density=density, g=g, sigma_t=sigma_t)
         n = 6000   # beyond the 4096 entries the kernel keeps: same recurrence either way
         got = vp.null_collision_table(P, n)
