@@ -50,6 +50,12 @@ struct ParamDev
     float    g;
     float    sigma_t[3];
 };
+// achromatic medium: identical extinction and albedo in the three channels (e.g. preset #13, host.cpp:1308) -- the ACH instances of
+// render_k carry one throughput channel and compute the bits of the three-channel ones
+inline bool achromatic(const ParamDev& P)
+{
+    return P.sigma_t[0] == P.sigma_t[1] && P.sigma_t[1] == P.sigma_t[2] && P.albedo[0] == P.albedo[1] && P.albedo[1] == P.albedo[2];
+}
 
 // Everything the integrator reads besides Param; uniform (kernel argument, scalar loads)
 struct SceneDev

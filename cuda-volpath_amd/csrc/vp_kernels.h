@@ -156,6 +156,9 @@ struct LaunchDev
     unsigned sub_shift;
 };
 
+// render_k and the approach kernels: which instance a launch runs, and which of them a build compiles, is decided in vp_dispatch.h.
+// A request for an instance that the build lacks (the API refuses every such configuration first: vp_render.cpp check_render) ends here:
+[[noreturn]] void kernel_not_built();
 // lds_form: how the decomposition estimator reads its brick table -- 0 global memory, 1 the 16-bit table through LDS (512-thread
 // workgroups), 2 2-bit codes into a four-entry palette through LDS (LaunchDev::bound_codes; 256-thread workgroups, plain occupancy)
 // half (with quant = false): binary16 cells (SceneDev::cells_f16); everything else of such a volume is the float volume's

@@ -31,6 +31,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 #include "vp_device.h"
 #include "vp_kernels.h"
@@ -1169,138 +1170,23 @@ __global__ void test_density_k(SceneDev S, const float* pos, float* out, int n)
 }
 
 // ------------------------------------------------------------------ host-side launchers
-template <int EST, class RNG, int LDSB, bool ACH, bool MIS>
-static void launch_render5(const SceneDev& S, const LaunchDev& L, bool quant, bool half, bool count, int blocks, hipStream_t st)
+// render_k and the approach kernels: the choice of instance, the set this build compiles and the launch are vp_dispatch.h's
+#include "vp_dispatch.h"
+[[noreturn]] void kernel_not_built()
 {
-    const dim3 blk(LDSB == 1 ? VP_BLOCK_LDS : VP_BLOCK);
-    if constexpr (LDSB == 2)
-    {
-        // the compact LDS table: the timed instance only (the host sends counting launches and look-ahead batches elsewhere)
-        hipLaunchKernelGGL((render_k<EST, RNG, true, false, 2, ACH, false, 0>), dim3(blocks), blk, 0, st, S, L);
-        return;
-    }
-    else
-    {
-#ifdef VP_DEV_BUILD
-    quant = true; (void)half;
-    if (MIS) return;
-    if constexpr (!MIS)
-    {
-        if (count) hipLaunchKernelGGL((render_k<EST, RNG, true, true, LDSB, ACH, false, 0>), dim3(blocks), blk, 0, st, S, L);
-        else if (L.cancel) hipLaunchKernelGGL((render_k<EST, RNG, true, false, LDSB, ACH, false, 0, false, true>), dim3(blocks), blk, 0, st, S, L);
-        else hipLaunchKernelGGL((render_k<EST, RNG, true, false, LDSB, ACH, false, 0>), dim3(blocks), blk, 0, st, S, L);
-    }
-#else
-    // (look-ahead batches of the shipped configuration -- passive environment -- run the instance that can be stopped at once: CANCEL)
-    constexpr bool CAN = !MIS;
-    if (quant)
-    {
-        if (count) hipLaunchKernelGGL((render_k<EST, RNG, true, true, LDSB, ACH, MIS, 0>), dim3(blocks), blk, 0, st, S, L);
-        else if (CAN && L.cancel) hipLaunchKernelGGL((render_k<EST, RNG, true, false, LDSB, ACH, MIS, 0, false, CAN>), dim3(blocks), blk, 0, st, S, L);
-        else hipLaunchKernelGGL((render_k<EST, RNG, true, false, LDSB, ACH, MIS, 0>), dim3(blocks), blk, 0, st, S, L);
-    }
-    else if (half)
-    {
-        // (binary16 cells: the float instances' arguments with HALF set)
-        if (count) hipLaunchKernelGGL((render_k<EST, RNG, false, true, false, ACH, MIS, 0, false, false, true>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
-        else if (CAN && L.cancel) hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, ACH, MIS, 0, false, CAN, true>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
-        else hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, ACH, MIS, 0, false, false, true>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
-    }
-    else
-    {
-        if (count) hipLaunchKernelGGL((render_k<EST, RNG, false, true, false, ACH, MIS, 0>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
-        else if (CAN && L.cancel) hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, ACH, MIS, 0, false, CAN>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
-        else hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, ACH, MIS, 0>), dim3(blocks), dim3(VP_BLOCK), 0, st, S, L);
-    }
-#endif
-    }
+    fprintf(stderr, "volpath_hip: this kernel variant is not compiled (development build, fast arithmetic mode, or a configuration the API refuses)\n");
+    abort();
 }
-// scalar tracking builds (the reference's compiled-out SPECTRAL_TRACKING 0 / MULTI_CHANNEL 1): three-channel throughput, no
-// LDS / MIS / counting specialisations
-template <int EST, class RNG>
-static void launch_render_scalar(const SceneDev& S, const LaunchDev& L, bool quant, bool half, int trk, int blocks, hipStream_t st)
+void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
+                   int blocks, hipStream_t st)
 {
-    const dim3 blk(VP_BLOCK);
-    if (quant)
-    {
-        if (trk == 1) hipLaunchKernelGGL((render_k<EST, RNG, true, false, false, false, false, 1>), dim3(blocks), blk, 0, st, S, L);
-        else hipLaunchKernelGGL((render_k<EST, RNG, true, false, false, false, false, 2>), dim3(blocks), blk, 0, st, S, L);
-    }
-    else if (half)
-    {
-        if (trk == 1) hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, false, false, 1, false, false, true>), dim3(blocks), blk, 0, st, S, L);
-        else hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, false, false, 2, false, false, true>), dim3(blocks), blk, 0, st, S, L);
-    }
-    else
-    {
-        if (trk == 1) hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, false, false, 1>), dim3(blocks), blk, 0, st, S, L);
-        else hipLaunchKernelGGL((render_k<EST, RNG, false, false, false, false, false, 2>), dim3(blocks), blk, 0, st, S, L);
-    }
-}
-template <int EST, class RNG, int LDSB>
-static void launch_render3(const SceneDev& S, const LaunchDev& L, bool quant, bool half, bool count, bool ach, bool mis, int blocks, hipStream_t st)
-{
-    if (mis)
-    {
-        // active environment sampling: the rarely used build, kept off the LDS specialisation
-        if (ach) launch_render5<EST, RNG, 0, true, true>(S, L, quant, half, count, blocks, st);
-        else launch_render5<EST, RNG, 0, false, true>(S, L, quant, half, count, blocks, st);
-    }
-    else if (ach) launch_render5<EST, RNG, LDSB, true, false>(S, L, quant, half, count, blocks, st);
-    else launch_render5<EST, RNG, LDSB, false, false>(S, L, quant, half, count, blocks, st);
-}
-
-// VP_RNG_PHILOX7: the shipped configuration only (spectral tracking, passive environment)
-template <int EST, int LDSB>
-static void launch_render_p7(const SceneDev& S, const LaunchDev& L, bool quant, bool half, bool count, bool ach, int blocks, hipStream_t st)
-{
-    if (ach) launch_render5<EST, RngPhilox7, LDSB, true, false>(S, L, quant, half, count, blocks, st);
-    else launch_render5<EST, RngPhilox7, LDSB, false, false>(S, L, quant, half, count, blocks, st);
-}
-
-template <int EST, class RNGT>
-static void launch_light2(const SceneDev& S, const LaunchDev& L, bool quant, bool count, bool ach, int blocks, hipStream_t st)
-{
-    // A light path never collides with matter: its throughput starts at (1,1,1) and every null collision in empty space multiplies
-    // the three channels by the same factor (sigma_t' - 0 in each), so they stay bitwise equal whatever the medium -- the
-    // one-channel (ACH) instance computes exactly what the three-channel one would.
-    const dim3 g(blocks), b(VP_BLOCK);
-    // QUANT only selects how the bound table of the local-majorant estimators is read; the light kernels fetch no cells
-    constexpr bool LOC = EST != EST_GLOBAL;
-#define VP_LL(Q, C, A) hipLaunchKernelGGL((render_k<EST, RNGT, Q, C, false, A, false, 0, true>), g, b, 0, st, S, L)
-    (void)ach;
-    if (LOC && !quant) { if (count) VP_LL(false, true, true); else VP_LL(false, false, true); }
-    else { if (count) VP_LL(true, true, true); else VP_LL(true, false, true); }
-#undef VP_LL
+    dispatch_render(S, L, est, rng, quant, half, count, lds_form, mis, trk, blocks, st);
 }
 void launch_render_light(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int blocks, hipStream_t st)
 {
-    const ParamDev& P = L.P;
-    const bool ach = P.sigma_t[0] == P.sigma_t[1] && P.sigma_t[1] == P.sigma_t[2] && P.albedo[0] == P.albedo[1] && P.albedo[1] == P.albedo[2];
-#ifdef VP_DEV_BUILD
-    if (rng == RNG_SAMPLERH || est == EST_BOUNDED) { fprintf(stderr, "volpath_hip DEV build: this kernel variant is not compiled\n"); abort(); }
-#define VP_LE(RNGT)                                                                             \
-    do                                                                                          \
-    {                                                                                           \
-        if (est == EST_DECOMP) launch_light2<EST_DECOMP, RNGT>(S, L, true, count, ach, blocks, st);  \
-        else launch_light2<EST_GLOBAL, RNGT>(S, L, true, count, ach, blocks, st);                    \
-    } while (0)
-    if (rng == RNG_PHILOX) VP_LE(RngPhilox);
-    else VP_LE(RngPhilox7);
-#else
-#define VP_LE(RNGT)                                                                             \
-    do                                                                                          \
-    {                                                                                           \
-        if (est == EST_DECOMP) launch_light2<EST_DECOMP, RNGT>(S, L, quant, count, ach, blocks, st);        \
-        else if (est == EST_BOUNDED) launch_light2<EST_BOUNDED, RNGT>(S, L, quant, count, ach, blocks, st); \
-        else launch_light2<EST_GLOBAL, RNGT>(S, L, quant, count, ach, blocks, st);                          \
-    } while (0)
-    if (rng == RNG_PHILOX) VP_LE(RngPhilox);
-    else if (rng == RNG_PHILOX7) VP_LE(RngPhilox7);
-    else VP_LE(RngSamplerH);
-#endif
-#undef VP_LE
+    dispatch_light(S, L, est, rng, quant, count, blocks, st);
 }
+void launch_approach(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, hipStream_t st) { dispatch_approach(S, L, est, rng, quant, st); }
 void launch_bound_bytes(const unsigned char* bounds, size_t nbricks, unsigned* mask, hipStream_t st)
 {
     unsigned blocks = (unsigned)std::fmin((double)((nbricks + 255) / 256), 1024.0);
@@ -1329,37 +1215,6 @@ void launch_segment_table(const SceneDev& S, unsigned width, unsigned height, co
 {
     hipLaunchKernelGGL(approach_segments_k, dim3((nslots + 255u) / 256u), dim3(256), 0, st, S, width, height, crawl, pixels, nslots, seg);
 }
-void launch_approach(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, hipStream_t st)
-{
-    const unsigned sh = L.approach_fshift, spb = 256u >> sh;   // pixel slots per workgroup
-    const dim3 grid((L.nslots + spb - 1u) / spb, ((unsigned)L.nframes + (1u << sh) - 1u) >> sh);
-    if (est == EST_GLOBAL)
-    {
-        if (rng == RNG_PHILOX7) hipLaunchKernelGGL(approach_k<RngPhilox7>, grid, dim3(256), 0, st, S, L);
-        else if (rng == RNG_PHILOX) hipLaunchKernelGGL(approach_k<RngPhilox>, grid, dim3(256), 0, st, S, L);
-        else hipLaunchKernelGGL(approach_k<RngSamplerH>, grid, dim3(256), 0, st, S, L);
-    }
-    else if (quant && L.seg_table && sh == 6u)
-    {
-        static_assert(VP_SEG_CAP > 64 && VP_SEG_CAP <= 128, "approach_local_tab_k copies a chain with two loads per lane");
-        // (uchar bound table, the per-pixel segment table built: the set-up of every restart segment comes from it)
-        if (rng == RNG_PHILOX7) hipLaunchKernelGGL(approach_local_tab_k<RngPhilox7>, grid, dim3(256), 0, st, S, L);
-        else if (rng == RNG_PHILOX) hipLaunchKernelGGL(approach_local_tab_k<RngPhilox>, grid, dim3(256), 0, st, S, L);
-        else hipLaunchKernelGGL(approach_local_tab_k<RngSamplerH>, grid, dim3(256), 0, st, S, L);
-    }
-    else if (quant)
-    {
-        if (rng == RNG_PHILOX7) hipLaunchKernelGGL((approach_local_k<RngPhilox7, true>), grid, dim3(256), 0, st, S, L);
-        else if (rng == RNG_PHILOX) hipLaunchKernelGGL((approach_local_k<RngPhilox, true>), grid, dim3(256), 0, st, S, L);
-        else hipLaunchKernelGGL((approach_local_k<RngSamplerH, true>), grid, dim3(256), 0, st, S, L);
-    }
-    else
-    {
-        if (rng == RNG_PHILOX7) hipLaunchKernelGGL((approach_local_k<RngPhilox7, false>), grid, dim3(256), 0, st, S, L);
-        else if (rng == RNG_PHILOX) hipLaunchKernelGGL((approach_local_k<RngPhilox, false>), grid, dim3(256), 0, st, S, L);
-        else hipLaunchKernelGGL((approach_local_k<RngSamplerH, false>), grid, dim3(256), 0, st, S, L);
-    }
-}
 void launch_pixel_lists(unsigned width, unsigned height, unsigned rank, unsigned world, unsigned ntiles, const unsigned* d_row_start,
                         const float4* table, const unsigned char* cls, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st)
 {
@@ -1372,95 +1227,6 @@ void launch_pixel_lists(unsigned width, unsigned height, unsigned rank, unsigned
     hipLaunchKernelGGL(pixlist_count_k, dim3(nblocks), dim3(VP_PIXLIST_BLOCK), 0, st, D, d_block_counts);
     hipLaunchKernelGGL(pixlist_scan_k, dim3(1), dim3(VP_PIXLIST_BLOCK), 0, st, d_block_counts, nblocks, d_totals);
     hipLaunchKernelGGL(pixlist_write_k, dim3(nblocks), dim3(VP_PIXLIST_BLOCK), 0, st, D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
-}
-
-void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
-                   int blocks, hipStream_t st)
-{
-    const bool lds_bounds = lds_form != 0;
-    // lds_form 2: the brick table as 2-bit codes beside the cold state (decomposition, uchar volume, counter-based streams, timed
-    // launches only: the host checks all of it, vp_render.cpp)
-    if (lds_form == 2 && est == EST_DECOMP && quant && !count && !mis && !trk && !L.cancel && (rng == RNG_PHILOX7 || rng == RNG_PHILOX))
-    {
-        const ParamDev& Pc = L.P;
-        const bool achc = Pc.sigma_t[0] == Pc.sigma_t[1] && Pc.sigma_t[1] == Pc.sigma_t[2] && Pc.albedo[0] == Pc.albedo[1] && Pc.albedo[1] == Pc.albedo[2];
-        if (rng == RNG_PHILOX7) launch_render_p7<EST_DECOMP, 2>(S, L, true, false, false, achc, blocks, st);
-        else launch_render3<EST_DECOMP, RngPhilox, 2>(S, L, true, false, false, achc, false, blocks, st);
-        return;
-    }
-#ifdef VP_DEV_BUILD
-    // development build (make DEV=1 -> libvolpath_hip_dev.so): only the kernels of the bench workloads are compiled
-    // (Philox streams, uchar volume, spectral tracking, passive environment; global-majorant and decomposition estimators)
-    {
-        const ParamDev& Pd = L.P;
-        const bool achd = Pd.sigma_t[0] == Pd.sigma_t[1] && Pd.sigma_t[1] == Pd.sigma_t[2] && Pd.albedo[0] == Pd.albedo[1] && Pd.albedo[1] == Pd.albedo[2];
-        if (trk || mis || !quant || (rng != RNG_PHILOX && rng != RNG_PHILOX7) || est == EST_BOUNDED)
-        {
-            fprintf(stderr, "volpath_hip DEV build: this kernel variant is not compiled\n");
-            abort();
-        }
-        if (rng == RNG_PHILOX7)
-        {
-            if (est == EST_DECOMP && lds_bounds) launch_render_p7<EST_DECOMP, 1>(S, L, true, false, count, achd, blocks, st);
-            else if (est == EST_DECOMP) launch_render_p7<EST_DECOMP, 0>(S, L, true, false, count, achd, blocks, st);
-            else launch_render_p7<EST_GLOBAL, 0>(S, L, true, false, count, achd, blocks, st);
-            return;
-        }
-        if (est == EST_DECOMP)
-        {
-            if (lds_bounds) launch_render3<EST_DECOMP, RngPhilox, 1>(S, L, true, false, count, achd, false, blocks, st);
-            else launch_render3<EST_DECOMP, RngPhilox, 0>(S, L, true, false, count, achd, false, blocks, st);
-        }
-        else launch_render3<EST_GLOBAL, RngPhilox, 0>(S, L, true, false, count, achd, false, blocks, st);
-        return;
-    }
-#else
-    if (trk)
-    {
-        const bool ph = rng == RNG_PHILOX;
-        if (est == EST_DECOMP) { if (ph) launch_render_scalar<EST_DECOMP, RngPhilox>(S, L, quant, half, trk, blocks, st); else launch_render_scalar<EST_DECOMP, RngSamplerH>(S, L, quant, half, trk, blocks, st); }
-        else if (est == EST_BOUNDED) { if (ph) launch_render_scalar<EST_BOUNDED, RngPhilox>(S, L, quant, half, trk, blocks, st); else launch_render_scalar<EST_BOUNDED, RngSamplerH>(S, L, quant, half, trk, blocks, st); }
-        else { if (ph) launch_render_scalar<EST_GLOBAL, RngPhilox>(S, L, quant, half, trk, blocks, st); else launch_render_scalar<EST_GLOBAL, RngSamplerH>(S, L, quant, half, trk, blocks, st); }
-        return;
-    }
-    // achromatic medium: identical extinction and albedo in the three channels (e.g. preset #13, host.cpp:1308)
-    const ParamDev& P = L.P;
-    const bool ach = P.sigma_t[0] == P.sigma_t[1] && P.sigma_t[1] == P.sigma_t[2] && P.albedo[0] == P.albedo[1] &&
-                     P.albedo[1] == P.albedo[2];
-    if (rng == RNG_PHILOX7)
-    {
-        // (mis and trk were rejected by the API for this generator)
-        if (est == EST_DECOMP && lds_bounds && quant) launch_render_p7<EST_DECOMP, 1>(S, L, quant, half, count, ach, blocks, st);
-        else if (est == EST_DECOMP) launch_render_p7<EST_DECOMP, 0>(S, L, quant, half, count, ach, blocks, st);
-        else if (est == EST_BOUNDED) launch_render_p7<EST_BOUNDED, 0>(S, L, quant, half, count, ach, blocks, st);
-        else launch_render_p7<EST_GLOBAL, 0>(S, L, quant, half, count, ach, blocks, st);
-        return;
-    }
-    if (est == EST_DECOMP)
-    {
-        if (lds_bounds && quant && !mis)
-        {
-            if (rng == RNG_PHILOX) launch_render3<EST_DECOMP, RngPhilox, 1>(S, L, quant, half, count, ach, mis, blocks, st);
-            else launch_render3<EST_DECOMP, RngSamplerH, 1>(S, L, quant, half, count, ach, mis, blocks, st);
-        }
-        else
-        {
-            if (rng == RNG_PHILOX) launch_render3<EST_DECOMP, RngPhilox, 0>(S, L, quant, half, count, ach, mis, blocks, st);
-            else launch_render3<EST_DECOMP, RngSamplerH, 0>(S, L, quant, half, count, ach, mis, blocks, st);
-        }
-    }
-    else if (est == EST_BOUNDED)
-    {
-        // the dead reference variant: no LDS specialisation, it is there for completeness
-        if (rng == RNG_PHILOX) launch_render3<EST_BOUNDED, RngPhilox, 0>(S, L, quant, half, count, ach, mis, blocks, st);
-        else launch_render3<EST_BOUNDED, RngSamplerH, 0>(S, L, quant, half, count, ach, mis, blocks, st);
-    }
-    else
-    {
-        if (rng == RNG_PHILOX) launch_render3<EST_GLOBAL, RngPhilox, 0>(S, L, quant, half, count, ach, mis, blocks, st);
-        else launch_render3<EST_GLOBAL, RngSamplerH, 0>(S, L, quant, half, count, ach, mis, blocks, st);
-    }
-#endif
 }
 
 // ------------------------------------------------------------------ environment CDF tables (init_envmap, kernel.cu:1144-1210)
