@@ -849,6 +849,55 @@ int vp_test_roots(int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* misma
     *mismatches = m;
     return VP_OK;
 }
+int vp_test_log_forms(int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches, uint32_t* first_bad)
+{
+    if (which < 0 || which > 1) return fail(VP_E_ARG, "vp_test_log_forms: unknown form %d (0 logf_, 1 logf_pos_)", which);
+    if (lo_bits > hi_bits || !mismatches || !first_bad) return fail(VP_E_ARG, "vp_test_log_forms: bad range %08x..%08x or null result", lo_bits, hi_bits);
+    int rc = ensure_device();
+    if (rc) return rc;
+    DevArrays D;
+    unsigned long long* dm = (unsigned long long*)D.get(8);
+    unsigned*           df = (unsigned*)D.get(4);
+    if (!dm || !df) return fail(VP_E_NOMEM, "vp_test_log_forms: no device memory");
+    HIPCHK(hipMemsetAsync(dm, 0, 8, G.stream));
+    HIPCHK(hipMemsetAsync(df, 0xff, 4, G.stream));
+    if (G.arith == VP_ARITH_FAST) launch_test_log_forms_fast(which, lo_bits, hi_bits, dm, df, G.stream);
+    else launch_test_log_forms(which, lo_bits, hi_bits, dm, df, G.stream);
+    HIPCHK(hipStreamSynchronize(G.stream));
+    unsigned long long m = 0;
+    HIPCHK(hipMemcpy(&m, dm, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(first_bad, df, 4, hipMemcpyDeviceToHost));
+    *mismatches = m;
+    return VP_OK;
+}
+int vp_test_approach_walk(int kind, int n, const float* params, const uint32_t* script, const uint32_t* words, uint32_t n_words, uint32_t* out_new,
+                          uint32_t* out_ref)
+{
+    if (kind < 0 || kind > 1) return fail(VP_E_ARG, "vp_test_approach_walk: unknown walk %d (0 approach_k's, 1 the local walks' inner loop)", kind);
+    if (n < 0) return fail(VP_E_ARG, "vp_test_approach_walk: negative count %d", n);
+    if (!params || !script || !out_new || !out_ref || (n_words && !words)) return fail(VP_E_ARG, "vp_test_approach_walk: null argument");
+    for (int i = 0; i < n; i++)   // every case's script lies inside `words`: the kernel reads nothing else
+        if (script[4 * (size_t)i + 1] > n_words || script[4 * (size_t)i + 2] > n_words - script[4 * (size_t)i + 1])
+            return fail(VP_E_ARG, "vp_test_approach_walk: the script of case %d (%u words from %u) leaves the %u words given", i, script[4 * (size_t)i + 2],
+                        script[4 * (size_t)i + 1], n_words);
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (n == 0) return VP_OK;
+    DevArrays D;
+    const size_t c = (size_t)n;
+    float*    dp = (float*)D.get(c * 16);
+    unsigned *ds = (unsigned*)D.get(c * 16), *dw = (unsigned*)D.get((size_t)n_words * 4), *dn = (unsigned*)D.get(c * 20), *dr = (unsigned*)D.get(c * 20);
+    if (!dp || !ds || !dw || !dn || !dr) return fail(VP_E_NOMEM, "vp_test_approach_walk: no device memory");
+    HIPCHK(hipMemcpy(dp, params, c * 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ds, script, c * 16, hipMemcpyHostToDevice));
+    if (n_words) HIPCHK(hipMemcpy(dw, words, (size_t)n_words * 4, hipMemcpyHostToDevice));
+    if (G.arith == VP_ARITH_FAST) launch_test_approach_walk_fast(kind, n, dp, ds, dw, dn, dr, G.stream);
+    else launch_test_approach_walk(kind, n, dp, ds, dw, dn, dr, G.stream);
+    HIPCHK(hipStreamSynchronize(G.stream));
+    HIPCHK(hipMemcpy(out_new, dn, c * 20, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_ref, dr, c * 20, hipMemcpyDeviceToHost));
+    return VP_OK;
+}
 int vp_test_hg(const float* g, const float* r0, const float* r1, const float* normal_xyz, const float* cos_query, float* dir_xyz, float* eval, int n)
 {
     int rc = ensure_device();

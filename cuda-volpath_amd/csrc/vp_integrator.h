@@ -1471,6 +1471,139 @@ __device__ __forceinline__ bool approach_cancelled(const LaunchDev& L)
     if ((threadIdx.x & 63u) == 0u) w = __hip_atomic_load(L.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return (unsigned)__builtin_amdgcn_readfirstlane((int)w) >= L.batch_id;
 }
+// The walks themselves: free flights from `dist` for as long as they end in front of a limit.  Per step a counter-based stream
+// pays for the draw, the logarithm, the flight and ONE compare of the distance (profiles/experiments/approach_step.txt):
+//  - the two limits of a walk are folded into their minimum before the loop (a NaN limit makes the minimum NaN or leaves the other
+//    compare to decide: the walk stops where the two compares stopped it);
+//  - a draw of exactly 0 (a word below 512: one step in 2^23) is a flight of +inf * inv_sigma, which passes every limit or is NaN --
+//    where inv_sigma does not carry a minus sign (-0 included).  The loop tests the draw itself and takes logf_pos_, the logarithm
+//    without its answer for 0; what the flight would have been is formed behind the loop where a caller needs it.  A majorant with a
+//    minus sign (a negative density or extinction: the flights run backwards, whatever is rendered means nothing) keeps the loop
+//    that asks logf_ -- one branch in front of the walk, the same way for every lane: the sign is the medium's -- so that the bits
+//    stay what they were even there;
+//  - the state of a counter-based stream is its pair index, the steps made: it is formed once behind the loop, not saved per step.
+// A sequential stream (RngSamplerH) moves past the collision test's variate and saves its two words after every step, as before.
+// The walks' loops leave through their exits: an empty statement the compiler may not move keeps it from turning the few
+// instructions behind a `break` into selects that every lane executes at every step (and the loop's uniform counter into a vector).
+#define VP_KEEP_BRANCH() asm volatile("")
+#define VP_WALK_UNROLL 2   // steps per iteration of the counter-based walks below, written out (scripts/approach_step_isa.py divides by it)
+// the one limit of a walk: the nearer of the segment's (or the box's) end, which is no NaN, and the certified-empty distance
+__device__ __forceinline__ float walk_limit(float t_box, float t_empty) { return t_box < t_empty ? t_box : t_empty; }
+__device__ __forceinline__ bool walks_backwards(float inv_sigma) { return (f2u(inv_sigma) >> 31) != 0u; }
+
+// approach_k's walk: steps of at most `cap` (a bound on the loop's uniform counter) from `dist`, each ending in front of t_lim.
+// Out: the distance reached in `dist`, the steps made (returned), the stream's state before the flight in hand in (sa, sb).
+template <class RNG>
+__device__ __forceinline__ unsigned approach_walk(float& dist, const float t_lim, const float inv_sigma, const unsigned cap, RNG& rng, unsigned& sa,
+                                                  unsigned& sb)
+{
+    unsigned steps = 0;
+    rng.save(sa, sb);
+    if (!RNG::kShadowSubstream || walks_backwards(inv_sigma))
+    {
+        for (; steps < cap; steps++)
+        {
+            const float d2 = dist + -logf_(rng.next_a()) * inv_sigma;   // kernel.cu:1419
+            if (!(d2 < t_lim)) break;                                    // the integrator's step: a fetch, or the way out
+            dist = d2;
+            (void)rng.next_b();   // the collision test's variate: `real` is false whatever it is; a sequential stream moves past it
+            rng.save(sa, sb);
+        }
+        return steps;
+    }
+    // Two steps per iteration, the distance in turn in `a` and in `b`: each flight is summed straight into the other variable
+    // BEFORE its test, so a lane that stops leaves its own distance where it was and a lane that goes on copies nothing.  After an
+    // even number of steps the distance reached is in `a`, after an odd number in `b`, wherever the lane left the loop.
+    const unsigned base = sa;
+    float          a = dist, b = dist;
+    unsigned       twos = 0;       // iterations the lane has completed: the loop's one per-lane counter
+    bool           odd  = false;   // ... and whether it left in the middle of one, behind the first of its two steps
+    for (unsigned i = 0; i < cap; i += 2u)
+    {
+        rng.set_pair(base + i);   // (the pair index from the uniform counter: its first Philox round stays scalar)
+        const float ua = rng.next_a();
+        b              = a + -logf_pos_(ua) * inv_sigma;   // kernel.cu:1419
+        if (ua == 0.0f || !(b < t_lim)) break;
+        VP_KEEP_BRANCH();
+        odd = true;
+        if (i + 1u == cap) break;
+        rng.set_pair(base + i + 1u);
+        const float ub = rng.next_a();
+        a              = b + -logf_pos_(ub) * inv_sigma;
+        if (ub == 0.0f || !(a < t_lim)) break;
+        VP_KEEP_BRANCH();
+        odd = false;
+        twos++;
+    }
+    dist  = odd ? b : a;
+    steps = 2u * twos + (odd ? 1u : 0u);
+    rng.set_pair(base + steps);
+    rng.save(sa, sb);
+    return steps;
+}
+
+// The inner loop of approach_local_k and approach_local_tab_k: flights inside one restart segment, from `dist`, until one passes the
+// segment's end t_far (returns true: `through`, kernel.cu:2145) or the certified-empty distance (false: a fetch, render_k's).  In: the
+// stream's state in (ta, tb).  Out: the distance reached, the steps made added to `n_steps`, (ta, tb) the state before the flight that
+// ended the walk, `rng` behind that flight.  VP_WALK_GUARD bounds the flights of one segment (a majorant of 1e-4 * 0.05 needs a
+// handful; the guard is for a broken one): a bound on the loop's uniform counter, which ends the walk as a fetch does.
+#define VP_WALK_GUARD 60002u   // (even: the loop makes two steps per iteration)
+template <class RNG>
+__device__ __forceinline__ bool approach_segment_walk(float& dist, const float t_far, const float t_empty, const float inv_sigma, RNG& rng, unsigned& ta,
+                                                      unsigned& tb, unsigned long long& n_steps)
+{
+    if (!RNG::kShadowSubstream || walks_backwards(inv_sigma))
+    {
+        unsigned steps   = 0;
+        bool     through = false;
+        for (;;)
+        {
+            const float d2 = dist + -logf_(rng.next_a()) * inv_sigma;   // kernel.cu:2085
+            if (d2 >= t_far) { through = true; break; }                   // t_end = min(1e20, t_far): `through`, kernel.cu:2145
+            if (!(d2 < t_empty) || steps > 60000u) break;                 // a fetch: render_k's
+            dist = d2;
+            (void)rng.next_b();   // the collision test's variate (`real` is false whatever it is): a sequential stream moves past it
+            rng.save(ta, tb);
+            steps++;
+        }
+        n_steps += steps;
+        return through;
+    }
+    // two steps per iteration, the distance in turn in `a` and `b`, as in approach_walk; the loop's one per-lane counter is the
+    // stream's own pair index (the lanes of a wave stand at different indices behind their first segment)
+    const float    t_stop = walk_limit(t_far, t_empty);
+    const unsigned base   = ta;
+    float          a = dist, b = dist, ua = 1.0f, ub = 1.0f;
+    bool           odd = false;   // the lane left behind the first of an iteration's two steps
+    for (unsigned k = 0; k < VP_WALK_GUARD; k += 2u)
+    {
+        ua = rng.next_a();
+        b  = a + -logf_pos_(ua) * inv_sigma;   // kernel.cu:2085
+        if (ua == 0.0f || !(b < t_stop)) break;
+        VP_KEEP_BRANCH();
+        odd = true;
+        ub  = rng.next_a();
+        a   = b + -logf_pos_(ub) * inv_sigma;
+        if (ub == 0.0f || !(a < t_stop)) break;
+        VP_KEEP_BRANCH();
+        odd = false;
+    }
+    // a flight that ended the walk has been drawn and counted by the stream; the guard (behind a whole iteration) draws nothing
+    const float u       = odd ? ub : ua;
+    float       d2      = odd ? a : b;
+    dist                = odd ? b : a;
+    const bool  stopped = odd || ua == 0.0f || !(b < t_stop);
+    if (u == 0.0f) d2 = dist + __builtin_inff() * inv_sigma;   // the flight of a zero draw, as logf_ has it
+    unsigned at, unused;
+    rng.save(at, unused);
+    const unsigned steps = at - base - (stopped ? 1u : 0u);
+    n_steps += steps;
+    RNG before = rng;
+    before.set_pair(base + steps);
+    before.save(ta, tb);
+    return stopped && d2 >= t_far;
+}
+
 template <class RNG>
 __global__ __launch_bounds__(256) void approach_k(SceneDev S, LaunchDev L)
 {
@@ -1501,15 +1634,8 @@ __global__ __launch_bounds__(256) void approach_k(SceneDev S, LaunchDev L)
         const float sigma_t_prime = max3(f3{P.sigma_t[0], P.sigma_t[1], P.sigma_t[2]}) * cur_density;
         const float inv_sigma     = rcp_(sigma_t_prime);
         rng.init(px, py, (unsigned)(L.frame0 + (int)fl), L.key0, L.key1);
-        rng.save(sa, sb);
-        for (; pairs < L.approach_steps; pairs++)
-        {
-            const float d2 = dist + -logf_(rng.next_a()) * inv_sigma;   // kernel.cu:1419
-            if (!(d2 < t_empty) || d2 >= t_end) break;                   // the integrator's step: a fetch, or the way out
-            dist = d2;
-            (void)rng.next_b();   // the collision test's variate: `real` is false whatever it is; a sequential stream moves past it
-            rng.save(sa, sb);
-        }
+        // a flight that passes t_empty is the integrator's step (a fetch), one that passes t_end its way out (t_end is no NaN here)
+        pairs = approach_walk(dist, walk_limit(t_end, t_empty), inv_sigma, L.approach_steps, rng, sa, sb);
     }
     L.stage[(size_t)fl * L.stage_stride + L.slot_base + slot] = make_float4(dist, u2f(sa), u2f(sb), u2f(pairs));
     if (L.counters && pairs) atomicAdd(&L.counters[1], (unsigned long long)pairs);   // density lookups the estimator makes on these steps
@@ -1567,20 +1693,8 @@ __global__ __launch_bounds__(256) void approach_local_k(SceneDev S, LaunchDev L)
         // asks it of every majorant in the table, light_identity_k): where it does not, the integrator goes on from here
         if (!(null_collision_in_empty_space(1.0f, sigma_t_prime, inv_sigma) == 1.0f)) break;
         float    dist = t_near;
-        unsigned steps = 0;
-        bool     through = false;
         unsigned ta = sa, tb = sb;   // the stream before the flight in hand
-        for (;;)
-        {
-            const float d2 = dist + -logf_(rng.next_a()) * inv_sigma;   // kernel.cu:2085
-            if (d2 >= t_far) { through = true; break; }                   // t_end = min(1e20, t_far): `through`, kernel.cu:2145
-            if (!(d2 < t_empty) || steps > 60000u) break;                 // a fetch: render_k's
-            dist = d2;
-            (void)rng.next_b();   // the collision test's variate (`real` is false whatever it is): a sequential stream moves past it
-            rng.save(ta, tb);
-            steps++;
-        }
-        n_steps += steps;
+        const bool through = approach_segment_walk(dist, t_far, t_empty, inv_sigma, rng, ta, tb, n_steps);
         if (!through)
         {
             // the flight in hand needs a fetch: render_k takes the path up INSIDE this segment -- its own set-up of the segment at `ro`
@@ -1675,20 +1789,8 @@ __global__ __launch_bounds__(256) void approach_local_tab_k(SceneDev S, LaunchDe
         if ((bits & 0x100u) || n >= L.approach_steps || !ok_tab[bits & 0xffu]) break;   // handed over at this segment's origin
         const float inv_sigma = inv_tab[bits & 0xffu], t_far = A.y, t_empty = A.w;
         float    dist = A.x;
-        unsigned steps = 0;
-        bool     through = false;
         unsigned ta = sa, tb = sb;   // the stream before the flight in hand
-        for (;;)
-        {
-            const float d2 = dist + -logf_(rng.next_a()) * inv_sigma;   // kernel.cu:2085
-            if (d2 >= t_far) { through = true; break; }
-            if (!(d2 < t_empty) || steps > 60000u) break;                 // a fetch: render_k's
-            dist = d2;
-            (void)rng.next_b();
-            rng.save(ta, tb);
-            steps++;
-        }
-        n_steps += steps;
+        const bool through = approach_segment_walk(dist, t_far, t_empty, inv_sigma, rng, ta, tb, n_steps);
         if (!through) { d_reached = dist; sa = ta; sb = tb; break; }
         rng.save(sa, sb);
         n_segs++;

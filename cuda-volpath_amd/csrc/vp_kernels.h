@@ -251,6 +251,12 @@ void launch_test_roots(int which, unsigned lo, unsigned hi, unsigned long long* 
 // the same two hooks compiled in the fast arithmetic (vp_kernels_fast.hip)
 void launch_test_hg_fast(const float* g, const float* r0, const float* r1, const float* nrm, const float* cosq, float* dir, float* ev, int n, hipStream_t st);
 void launch_test_math_fast(int which, const float* in, float* out, int n, hipStream_t st);
+// vp_test_log_forms / vp_test_approach_walk (vp_test_kernels.h), in the exact and in the fast arithmetic
+void launch_test_log_forms(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad, hipStream_t st);
+void launch_test_log_forms_fast(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad, hipStream_t st);
+void launch_test_approach_walk(int kind, int n, const float* par, const unsigned* scr, const unsigned* words, unsigned* out_new, unsigned* out_ref, hipStream_t st);
+void launch_test_approach_walk_fast(int kind, int n, const float* par, const unsigned* scr, const unsigned* words, unsigned* out_new, unsigned* out_ref,
+                                    hipStream_t st);
 void launch_test_rng(int mode, unsigned x, unsigned y, unsigned f, unsigned k0, unsigned k1, int n, float* out, hipStream_t st);
 void launch_test_density(const SceneDev& S, bool quant, bool half, const float* pos, float* out, int n, hipStream_t st);
 }  // namespace vp

@@ -1118,7 +1118,7 @@ __global__ void accumulate_k(float4* dst, const float4* src, size_t n)
 }
 
 // ---- test kernels
-// test_hg_k, test_math_k: vp_test_kernels.h (compiled in both arithmetic modes)
+// test_hg_k, test_math_k, test_log_forms_k, test_approach_walk_k: vp_test_kernels.h (compiled in both arithmetic modes)
 #include "vp_test_kernels.h"
 // vp_test_roots: the in-range root helpers of vp_math.h against the general forms compiled here, on every bit pattern in [lo, hi]
 __global__ void test_roots_k(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad)
@@ -1455,6 +1455,14 @@ void launch_test_math(int which, const float* in, float* out, int n, hipStream_t
 void launch_test_roots(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad, hipStream_t st)
 {
     hipLaunchKernelGGL(test_roots_k, dim3(2048), dim3(256), 0, st, which, lo, hi, mismatches, first_bad);
+}
+void launch_test_log_forms(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad, hipStream_t st)
+{
+    hipLaunchKernelGGL(test_log_forms_k, dim3(2048), dim3(256), 0, st, which, lo, hi, mismatches, first_bad);
+}
+void launch_test_approach_walk(int kind, int n, const float* par, const unsigned* scr, const unsigned* words, unsigned* out_new, unsigned* out_ref, hipStream_t st)
+{
+    hipLaunchKernelGGL(test_approach_walk_k, dim3((n + 63) / 64), dim3(64), 0, st, kind, n, par, scr, words, out_new, out_ref);
 }
 void launch_test_rng(int mode, unsigned x, unsigned y, unsigned f, unsigned k0, unsigned k1, int n, float* out, hipStream_t st)
 {

@@ -64,4 +64,13 @@ void launch_test_math_fast(int which, const float* in, float* out, int n, hipStr
 {
     hipLaunchKernelGGL(fast::test_math_k, dim3((n + 255) / 256), dim3(256), 0, st, which, in, out, n);
 }
+void launch_test_log_forms_fast(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad, hipStream_t st)
+{
+    hipLaunchKernelGGL(fast::test_log_forms_k, dim3(2048), dim3(256), 0, st, which, lo, hi, mismatches, first_bad);
+}
+void launch_test_approach_walk_fast(int kind, int n, const float* par, const unsigned* scr, const unsigned* words, unsigned* out_new, unsigned* out_ref,
+                                    hipStream_t st)
+{
+    hipLaunchKernelGGL(fast::test_approach_walk_k, dim3((n + 63) / 64), dim3(64), 0, st, kind, n, par, scr, words, out_new, out_ref);
+}
 }  // namespace vp

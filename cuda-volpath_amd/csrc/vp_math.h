@@ -30,17 +30,18 @@ __device__ __forceinline__ float fma_(float a, float b, float c) { return __buil
 __device__ __forceinline__ float u2f(unsigned u) { return __uint_as_float(u); }
 __device__ __forceinline__ unsigned f2u(float f) { return __float_as_uint(f); }
 
-// natural logarithm on {0} U [2^-126, inf); log(0) = -inf
-__device__ __forceinline__ float logf_(float x)
+// The logarithm's chain on [2^-126, inf) (Cephes logf), without the answer for 0: logf_ and logf_pos_ below.
+// The mantissa is folded into (sqrt(2)/2, sqrt(2)] without a select: adding 2^23 - 0x3504f4 to the bit pattern carries into the
+// exponent field exactly when the mantissa field exceeds that of fl(sqrt 2) = 0x3fb504f3.  The exponent's bias goes into the same
+// constant (0x004afb0c - 0x3f800000 mod 2^32: a multiple of 2^23 less, so the low 23 bits are the same) and an arithmetic shift
+// reads the unbiased exponent off: the same integer as (iy >> 23) - 127 of the unfolded sum for every pattern below 0xbf3504f4 --
+// all non-negative floats, +inf and the positive NaNs (tests/test_approach_step_cpu.py pins the range; vp_test_log_forms compares
+// the chain with the unfolded one on every pattern of it).
+__device__ __forceinline__ float logf_chain_(float x)
 {
-#if defined(VP_ARITH_FAST) || defined(VP_EXP_FASTLOG)
-    return __builtin_amdgcn_logf(x) * 0.69314718056f;   // v_log_f32 is log2; log(0) = -inf as well
-#endif
-    // mantissa folded into (sqrt(2)/2, sqrt(2)] without a select: adding 2^23 - 0x3504f4 to the bit pattern carries
-    // into the exponent field exactly when the mantissa field exceeds that of fl(sqrt 2) = 0x3fb504f3
     unsigned ix = f2u(x);
-    unsigned iy = ix + 0x004afb0cu;
-    int      e  = (int)(iy >> 23) - 127;
+    unsigned iy = ix + 0xc0cafb0cu;
+    int      e  = (int)iy >> 23;
     float    m  = u2f((iy & 0x007fffffu) + 0x3f3504f4u);
     float    r  = m - 1.0f;
     float z     = r * r;
@@ -58,8 +59,28 @@ __device__ __forceinline__ float logf_(float x)
     y           = fma_(fe, -2.12194440e-4f, y);
     y           = fma_(z, -0.5f, y);
     float res   = r + y;
-    res         = fma_(fe, 0.693359375f, res);
+    return fma_(fe, 0.693359375f, res);
+}
+
+// natural logarithm on {0} U [2^-126, inf); log(0) = -inf
+__device__ __forceinline__ float logf_(float x)
+{
+#if defined(VP_ARITH_FAST) || defined(VP_EXP_FASTLOG)
+    return __builtin_amdgcn_logf(x) * 0.69314718056f;   // v_log_f32 is log2; log(0) = -inf as well
+#endif
+    const float res = logf_chain_(x);
     return x == 0.0f ? -__builtin_inff() : res;
+}
+
+// natural logarithm on [2^-126, inf) ONLY: logf_ without its answer for 0 (a compare and a select less; at 0 the chain returns a
+// finite number that means nothing).  For callers that test for 0 themselves: the approach walks (vp_integrator.h approach_walk).
+// In the fast arithmetic it is logf_, whose one instruction answers 0 as well.
+__device__ __forceinline__ float logf_pos_(float x)
+{
+#if defined(VP_ARITH_FAST) || defined(VP_EXP_FASTLOG)
+    return logf_(x);
+#endif
+    return logf_chain_(x);
 }
 
 // exponential; used on arguments <= 0; results below 2^-126 flush to 0

@@ -1,4 +1,5 @@
-// vp_test_kernels.h -- the test hooks of the integrator's arithmetic: vp_test_math (test_math_k) and vp_test_hg (test_hg_k).
+// vp_test_kernels.h -- the test hooks of the integrator's arithmetic: vp_test_math (test_math_k), vp_test_hg (test_hg_k),
+// vp_test_log_forms (test_log_forms_k) and vp_test_approach_walk (test_approach_walk_k).
 // Included INSIDE a namespace by both translation units, like vp_integrator.h: vp_kernels.hip (namespace vp, the exact helpers) and
 // vp_kernels_fast.hip (namespace vp::fast, VP_ARITH_FAST).  vp_context.cpp launches the pair of the context's arithmetic mode, so
 // the hooks test the helpers the context's renders run.
@@ -36,4 +37,139 @@ __global__ void test_math_k(int which, const float* in, float* out, int n)
         default: r = __builtin_nanf(""); break;
     }
     out[i] = r;
+}
+
+// ---- vp_test_log_forms, vp_test_approach_walk: the approach walks' step against the forms it had before its instructions were cut
+// (profiles/experiments/approach_step.txt).  TEST-ONLY code below: the earlier forms, kept word for word as the reference.
+
+// logf_ as it stood: the exponent's bias taken off after the shift, the answer for 0 selected at the end
+__device__ __forceinline__ float logf_ref_(float x)
+{
+#if defined(VP_ARITH_FAST) || defined(VP_EXP_FASTLOG)
+    return __builtin_amdgcn_logf(x) * 0.69314718056f;   // v_log_f32 is log2; log(0) = -inf as well
+#endif
+    unsigned ix = f2u(x);
+    unsigned iy = ix + 0x004afb0cu;
+    int      e  = (int)(iy >> 23) - 127;
+    float    m  = u2f((iy & 0x007fffffu) + 0x3f3504f4u);
+    float    r  = m - 1.0f;
+    float z     = r * r;
+    float p     = 7.0376836292E-2f;
+    p           = fma_(p, r, -1.1514610310E-1f);
+    p           = fma_(p, r, 1.1676998740E-1f);
+    p           = fma_(p, r, -1.2420140846E-1f);
+    p           = fma_(p, r, 1.4249322787E-1f);
+    p           = fma_(p, r, -1.6668057665E-1f);
+    p           = fma_(p, r, 2.0000714765E-1f);
+    p           = fma_(p, r, -2.4999993993E-1f);
+    p           = fma_(p, r, 3.3333331174E-1f);
+    float fe    = (float)e;
+    float y     = (r * z) * p;
+    y           = fma_(fe, -2.12194440e-4f, y);
+    y           = fma_(z, -0.5f, y);
+    float res   = r + y;
+    res         = fma_(fe, 0.693359375f, res);
+    return x == 0.0f ? -__builtin_inff() : res;
+}
+// which = 0: logf_, 1: logf_pos_, against logf_ref_ on every bit pattern in [lo, hi]
+__global__ void test_log_forms_k(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad)
+{
+    const unsigned long long n = (unsigned long long)hi - lo + 1ull;
+    unsigned long long bad = 0;
+    unsigned           fb  = 0xffffffffu;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x)
+    {
+        const unsigned b = lo + (unsigned)i;
+        const float    x = u2f(b);
+        const float    a = which ? logf_pos_(x) : logf_(x);
+        if (f2u(a) != f2u(logf_ref_(x))) { bad++; fb = b < fb ? b : fb; }
+    }
+    if (bad) { atomicAdd(mismatches, bad); atomicMin(first_bad, fb); }
+}
+
+// A scripted stream: next_a() returns the caller's words in turn (0 behind the last of them: a draw of exactly 0), counted in pairs
+// like Philox, with sub-streams for shadow rays in name (kShadowSubstream: the walks treat it as a counter-based stream).
+struct RngScript
+{
+    const unsigned* words;
+    unsigned        count, pair0, pair;   // the script's first word is pair index pair0
+    static constexpr bool kShadowSubstream = true;
+    __device__ __forceinline__ float next_a()
+    {
+        const unsigned i = pair - pair0, w = i < count ? words[i] : 0u;
+        pair++;
+        return draw_to_float(w);
+    }
+    __device__ __forceinline__ float next_b() { return 0.5f; }
+    __device__ __forceinline__ void set_pair(unsigned n) { pair = n; }
+    __device__ __forceinline__ void save(unsigned& a, unsigned& b) const { a = pair; b = 0u; }
+    __device__ __forceinline__ void load(unsigned a, unsigned) { pair = a; }
+};
+// approach_k's loop as it stood (two compares, logf_ with its select, the state saved after every step)
+template <class RNG>
+__device__ __forceinline__ void approach_walk_ref_(float& dist, const float t_empty, const float t_end, const float inv_sigma, const unsigned cap, RNG& rng,
+                                                   unsigned& pairs, unsigned& sa, unsigned& sb)
+{
+    rng.save(sa, sb);
+    for (; pairs < cap; pairs++)
+    {
+        const float d2 = dist + -logf_ref_(rng.next_a()) * inv_sigma;   // kernel.cu:1419
+        if (!(d2 < t_empty) || d2 >= t_end) break;                       // the integrator's step: a fetch, or the way out
+        dist = d2;
+        (void)rng.next_b();   // the collision test's variate: `real` is false whatever it is; a sequential stream moves past it
+        rng.save(sa, sb);
+    }
+}
+// the inner loop of approach_local_k / approach_local_tab_k as it stood
+template <class RNG>
+__device__ __forceinline__ bool approach_segment_walk_ref_(float& dist, const float t_far, const float t_empty, const float inv_sigma, RNG& rng, unsigned& ta,
+                                                           unsigned& tb, unsigned& steps)
+{
+    bool through = false;
+    for (;;)
+    {
+        const float d2 = dist + -logf_ref_(rng.next_a()) * inv_sigma;   // kernel.cu:2085
+        if (d2 >= t_far) { through = true; break; }                       // t_end = min(1e20, t_far): `through`, kernel.cu:2145
+        if (!(d2 < t_empty) || steps > 60000u) break;                     // a fetch: render_k's
+        dist = d2;
+        (void)rng.next_b();   // the collision test's variate (`real` is false whatever it is): a sequential stream moves past it
+        rng.save(ta, tb);
+        steps++;
+    }
+    return through;
+}
+// One thread per case.  par[4 i ..] = (distance at the start, t_empty, t_end (kind 0) or t_far (kind 1), inv_sigma); scr[4 i ..] =
+// (step cap (kind 0), first word of the case's script, its number of words, the stream's pair index at the start).  out_new /
+// out_ref[5 i ..] = the hand-over of the walk as built / as it stood: (bits of the distance reached, steps, the stream's two state
+// words before the flight in hand, through).  kind 0: approach_walk (approach_k); kind 1: approach_segment_walk (the local walks).
+__global__ void test_approach_walk_k(int kind, int n, const float* par, const unsigned* scr, const unsigned* words, unsigned* out_new, unsigned* out_ref)
+{
+    const int i = threadIdx.x + blockIdx.x * blockDim.x;
+    if (i >= n) return;
+    const float    dist0 = par[4 * i], t_empty = par[4 * i + 1], t_box = par[4 * i + 2], inv_sigma = par[4 * i + 3];
+    const unsigned cap = scr[4 * i];
+    for (int ref = 0; ref < 2; ref++)
+    {
+        RngScript rng{words + scr[4 * i + 1], scr[4 * i + 2], scr[4 * i + 3], scr[4 * i + 3]};
+        float     dist = dist0;
+        unsigned  sa = 0, sb = 0, steps = 0, through = 0;
+        if (kind == 0)
+        {
+            if (ref) approach_walk_ref_(dist, t_empty, t_box, inv_sigma, cap, rng, steps, sa, sb);
+            else steps = approach_walk(dist, walk_limit(t_box, t_empty), inv_sigma, cap, rng, sa, sb);
+        }
+        else
+        {
+            rng.save(sa, sb);
+            if (ref) through = approach_segment_walk_ref_(dist, t_box, t_empty, inv_sigma, rng, sa, sb, steps) ? 1u : 0u;
+            else
+            {
+                unsigned long long n_steps = 0;
+                through = approach_segment_walk(dist, t_box, t_empty, inv_sigma, rng, sa, sb, n_steps) ? 1u : 0u;
+                steps   = (unsigned)n_steps;
+            }
+        }
+        unsigned* o = (ref ? out_ref : out_new) + 5 * (size_t)i;
+        o[0] = f2u(dist); o[1] = steps; o[2] = sa; o[3] = sb; o[4] = through;
+    }
 }

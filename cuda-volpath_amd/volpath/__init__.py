@@ -33,7 +33,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists", "vp_get_segment_table",
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
-                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_intersect_box",
+                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_intersect_box",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
                  "vp_upload", "vp_download"]
@@ -152,6 +152,8 @@ def lib():
         L.vp_cloud_voxelize.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
         L.vp_test_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.vp_test_roots.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        L.vp_test_log_forms.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        L.vp_test_approach_walk.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.vp_test_rng.argtypes = [C.c_int] + [C.c_uint32] * 5 + [C.c_int, C.c_void_p]
         L.vp_test_sample_density.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.vp_test_hg.argtypes = [C.c_void_p] * 7 + [C.c_int]
@@ -635,6 +637,29 @@ def test_roots(which, lo_bits, hi_bits):
     m, f = C.c_uint64(0), C.c_uint32(0)
     _chk(lib().vp_test_roots(which, lo_bits, hi_bits, C.byref(m), C.byref(f)))
     return m.value, (None if m.value == 0 else f.value)
+
+
+def test_log_forms(which, lo_bits, hi_bits):
+    """(mismatches, first bad bit pattern or None) of the logarithm `which` (0 logf_, 1 logf_pos_) against the chain as it stood, over
+    every binary32 bit pattern in [lo_bits, hi_bits]; walked on the device"""
+    m, f = C.c_uint64(0), C.c_uint32(0)
+    _chk(lib().vp_test_log_forms(which, lo_bits, hi_bits, C.byref(m), C.byref(f)))
+    return m.value, (None if m.value == 0 else f.value)
+
+
+def test_approach_walk(kind, params, script, words):
+    """(new, ref): uint32 [n, 5] hand-overs (distance bits, steps, two state words, through) of the approach walk `kind` (0 approach_k's,
+    1 the local walks' inner loop) as built and as it stood, on n scripted cases: params float32 [n, 4] = (distance, t_empty, t_end or
+    t_far, 1 / majorant), script uint32 [n, 4] = (cap, first word, words, first pair index), words uint32 (include/volpath.h)"""
+    params = np.ascontiguousarray(params, np.float32).reshape(-1, 4)
+    script = np.ascontiguousarray(script, np.uint32).reshape(-1, 4)
+    words = np.ascontiguousarray(words, np.uint32).ravel()
+    n = params.shape[0]
+    if script.shape[0] != n:
+        raise ValueError("params and script describe different numbers of cases")
+    new, ref = np.zeros((n, 5), np.uint32), np.zeros((n, 5), np.uint32)
+    _chk(lib().vp_test_approach_walk(kind, n, _p(params), _p(script), _p(words), words.size, _p(new), _p(ref)))
+    return new, ref
 
 
 def test_rng(mode, x, y, frame, n, key=(0, 0)):

@@ -470,6 +470,23 @@ int vp_test_math(int which, const float* in, float* out, int n);
  * patterns differ, *first_bad = the lowest of them (0xffffffff: none).  VP_E_ARG for another `which`, lo_bits > hi_bits or a null
  * result, before the device is touched; VP_E_STATE in the fast arithmetic mode, which has no such helpers. */
 int vp_test_roots(int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches, uint32_t* first_bad);
+/* vp_test_log_forms: the logarithm of the current arithmetic (vp_math.h: which = 0 logf_, 1 logf_pos_, the form without the answer
+ * for 0 that the approach walks take) against the chain as it stood before the exponent's bias was folded into its first constant
+ * (kept word for word in the test kernels), bit for bit on EVERY binary32 pattern in [lo_bits, hi_bits], walked on the device.
+ * logf_ holds on [0, 0x7f800000], logf_pos_ on [0x00800000, 0x7f800000].  Results and VP_E_ARG as vp_test_roots; runs in both
+ * arithmetic modes (in the fast one all three are the hardware's instruction). */
+int vp_test_log_forms(int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches, uint32_t* first_bad);
+/* vp_test_approach_walk: the free-flight walks of the approach kernels (kind 0: approach_k's; kind 1: the inner loop of
+ * approach_local_k and approach_local_tab_k) and the loops they replaced (kept word for word in the test kernels), each on n cases
+ * with a SCRIPTED stream: next_a() returns the case's words in turn as draws (a word below 512 is a draw of exactly 0; behind the
+ * last word every draw is 0), counted in pairs like Philox.  params[4 i ..] = (distance at the start, t_empty, t_end (kind 0) or
+ * t_far (kind 1), the majorant's reciprocal), script[4 i ..] = (step cap (kind 0 only), index of the case's first word in `words`,
+ * its number of words, the stream's pair index at the start).  out_new / out_ref[5 i ..] = the hand-over as built / as it stood:
+ * (bits of the distance reached, steps made, the stream's two state words before the flight in hand, through (kind 1)).  The two
+ * agree bit for bit wherever the reciprocal carries no minus sign and a segment needs fewer than 60 000 flights.  VP_E_ARG, before
+ * the device is touched, for another kind, n < 0, a null array or a script outside the n_words given. */
+int vp_test_approach_walk(int kind, int n, const float* params, const uint32_t* script, const uint32_t* words, uint32_t n_words,
+                          uint32_t* out_new, uint32_t* out_ref);
 int vp_test_rng(int mode, uint32_t x, uint32_t y, uint32_t frame, uint32_t k0, uint32_t k1, int n, float* out);
 int vp_test_sample_density(const float* pos_xyz, float* out, int n);
 /* component hooks for known-answer tests against float64 closed forms (no oracle involved):
