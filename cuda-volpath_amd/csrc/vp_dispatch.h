@@ -11,6 +11,8 @@
 //   render_built()     which instances this translation unit compiles -- its truth set IS the set of render_k kernels in the object,
 //                      because launch_instance() names a kernel only under `if constexpr (render_built(...))`
 //   launch_instance()  the run-time instance lifted to template arguments; kernel_not_built() (vp_kernels.h) for the rest
+//   launch_layers_instance()  the same for a layers launch (LaunchDev::layers): render_k's twelfth argument, LYR, for the subset
+//                      layers_built() states -- only where the kernels above have that argument (VP_RENDER_K_HAS_LAYERS)
 // and the same, smaller, for the approach walk (approach_built(), launch_approach_walk()).  dispatch_render(), dispatch_light() and
 // dispatch_approach() are what the launch_* functions of vp_kernels.h call.
 
@@ -172,15 +174,56 @@ static void launch_instance(const RenderInst& v, const SceneDev& S, const Launch
 {
     launch_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st);
 }
+// ---- the instances of a layers launch (LaunchDev::layers; render_k's LYR argument).  Compiled where the kernels that precede this
+// file have the argument (vp_integrator.h defines VP_RENDER_K_HAS_LAYERS).  The subset: spectral tracking, passive environment, the
+// three estimators, the three streams, the three volume formats, every LDS form, general and light class; no work counters, no
+// look-ahead (a layers call quiesces it), the exact translation unit only -- vp_render.cpp refuses everything else first.
+#ifdef VP_RENDER_K_HAS_LAYERS
+constexpr bool layers_built(const RenderInst& v)
+{
+    return render_built(v) && !kFastArith && !v.trk && !v.mis && !v.count && !v.cancel;
+}
+template <unsigned I>
+static void launch_layers_instance_at(const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
+{
+    constexpr RenderInst v = render_at(I);
+    using RNG = typename RngOf<v.rng>::type;
+    constexpr unsigned block = v.ldsb == 1 ? VP_BLOCK_LDS : VP_BLOCK;
+    hipLaunchKernelGGL((render_k<v.est, RNG, v.quant, v.count, v.ldsb, v.ach, v.mis, v.trk, v.light, v.cancel, v.half, true>), dim3(blocks), dim3(block), 0, st, S, L);
+}
+template <unsigned I>
+constexpr RenderLaunchFn layers_launcher()
+{
+    if constexpr (layers_built(render_at(I))) return &launch_layers_instance_at<I>;
+    else return nullptr;
+}
+template <unsigned... I>
+static void launch_layers_instance(const RenderInst& v, std::integer_sequence<unsigned, I...>, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
+{
+    static constexpr RenderLaunchFn table[kRenderInsts] = {layers_launcher<I>()...};
+    const unsigned i = render_index(v);
+    if (i >= kRenderInsts || !table[i]) kernel_not_built();
+    table[i](S, L, blocks, st);
+}
+#endif
+static void launch_instance_of(const RenderInst& v, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
+{
+#ifdef VP_RENDER_K_HAS_LAYERS
+    if (L.layers) { launch_layers_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st); return; }
+#else
+    if (L.layers) kernel_not_built();
+#endif
+    launch_instance(v, S, L, blocks, st);
+}
 // what launch_render / launch_render_fast and launch_render_light are
 static void dispatch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
                             int blocks, hipStream_t st)
 {
-    launch_instance(render_instance(render_request(L, est, rng, quant, half, count, lds_form, mis, trk)), S, L, blocks, st);
+    launch_instance_of(render_instance(render_request(L, est, rng, quant, half, count, lds_form, mis, trk)), S, L, blocks, st);
 }
 static void dispatch_light(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool count, int blocks, hipStream_t st)
 {
-    launch_instance(light_instance(est, rng, quant, count), S, L, blocks, st);
+    launch_instance_of(light_instance(est, rng, quant, count), S, L, blocks, st);
 }
 
 // ---- the approach walk: the camera rays' free flights through certified-empty cells, ahead of the integrator

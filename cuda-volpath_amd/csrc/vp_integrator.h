@@ -192,7 +192,10 @@ constexpr int render_min_waves(int est, bool count, int ldsb, bool ach, bool mis
     if (trk) return 4;                                                                     // scalar tracking builds
     return (ach && !cancel) ? VP_LOCAL_MIN_WAVES : 5;                                      // local majorants: achromatic six, chromatic / look-ahead five
 }
-template <int EST, class RNG, bool QUANT, bool COUNT, int LDSB, bool ACH, bool MIS, int TRK, bool LIGHT = false, bool CANCEL = false, bool HALF = false>
+// LYR: the instance of a layers launch (include/volpath.h vp_render_frames_layers; LaunchDev::layers): vp_dispatch.h names it for the
+// subset the feature is built for.  Every other instance carries no code for it.
+#define VP_RENDER_K_HAS_LAYERS 1
+template <int EST, class RNG, bool QUANT, bool COUNT, int LDSB, bool ACH, bool MIS, int TRK, bool LIGHT = false, bool CANCEL = false, bool HALF = false, bool LYR = false>
 // Occupancy (round 4: the cold per-path state in LDS, ColdVal above; profiles/r04_kernel_resources.txt).  The achromatic
 // global-majorant kernel needs 72 registers: SEVEN waves per SIMD (C2 2541 -> 2781 Msamples/s); the chromatic one and the plain
 // achromatic local-majorant kernels 80: six (c3ref 2398 -> 2513); the LDS-table kernel keeps its state in registers (its LDS is the
@@ -280,6 +283,10 @@ void render_k(SceneDev S, LaunchDev L)
     // DEFER: the sun's light of a shadow ray that ended in the tracking loop is added at the lane's next event visit (see the flush at
     // the top of the event pass).  Spectral tracking only: the scalar builds keep the sum where the ray ends.
     constexpr bool DEFER = EARLY && TRK == 0;
+    // Layers launches (LaunchDev::layers) run instances of their own (LYR), built for spectral tracking with the passive environment,
+    // without work counters and look-ahead: the host refuses the rest.
+    constexpr bool LAYERS = LYR;
+    static_assert(!LYR || (TRK == 0 && !MIS && !COUNT && !CANCEL), "layers instances: spectral tracking, passive environment, no counters, no look-ahead");
     const ParamDev& P = L.P;
     const f3    sig_t     = f3{P.sigma_t[0], P.sigma_t[1], P.sigma_t[2]};
     const f3    sig_s     = sig_t * f3{P.albedo[0], P.albedo[1], P.albedo[2]};
@@ -769,6 +776,7 @@ void render_k(SceneDev S, LaunchDev L)
         {
             vp_pad<VP_PAD_END>();
             bool fresh = false;   // APPR: this lane took a new sample in this round, `dist` holds where approach_k left its camera ray
+            bool trans = false;   // layers launch (LaunchDev::layers): the path that ends in this round is unscattered -- its sample is its throughput
             // order: a path that ends here is written, its lane refilled and the new segment set up in ONE round
             // ---- ray left the medium: background() kernel.cu:1258-1267 (quirk Q11)
             tally(B_BG, st == EV_BG);
@@ -777,8 +785,12 @@ void render_k(SceneDev S, LaunchDev L)
                 // with active environment sampling only unscattered paths see it directly (kernel.cu:2026-2030, :1340-1344)
                 if (!MIS || nsc == 0)
                 {
+                    // (a layers launch: an unscattered path's sample is the transmittance layer's, its throughput -- the sum below with a
+                    // background of 1 --, marked for reduce_layers_k in EV_WRITE; include/volpath.h vp_render_frames_layers)
+                    if (LAYERS) trans = nsc == 0;
                     f3 bg;
-                    if (nsc == 0 && dot(rd, sun_dir) > S.sun_cos) bg = f3{S.sun_orig[0], S.sun_orig[1], S.sun_orig[2]};
+                    if (LAYERS && trans) bg = f3{1.0f, 1.0f, 1.0f};
+                    else if (nsc == 0 && dot(rd, sun_dir) > S.sun_cos) bg = f3{S.sun_orig[0], S.sun_orig[1], S.sun_orig[2]};
                     else { bg = eval_envmap(S, rd); if (COUNT) c_env++; }
                     if (LIGHT && !LOCAL)
                     {
@@ -796,7 +808,7 @@ void render_k(SceneDev S, LaunchDev L)
             tally(B_WRITE, st == EV_WRITE);
             if (st == EV_WRITE)
             {
-                f3     r    = rad * P.brightness;
+                f3     r    = rad * ((LAYERS && trans) ? 1.0f : P.brightness);
 #ifdef VP_ARITH_FAST
                 // v_rcp_f32 / v_rsq_f32 / v_log_f32 flush denormal inputs: the collision weight of a path whose throughput has sunk
                 // below 2^-126 can come out infinite where the IEEE quotient is finite.  Such a path carries ~1e-38 of the light it
@@ -805,6 +817,10 @@ void render_k(SceneDev S, LaunchDev L)
 #endif
                 // heat: num_scatters (:2307) or loop index * 0.001 in double (:1581, :1942)
                 float  heat = (EST == EST_DECOMP) ? (float)nsc : (float)((double)(EST == EST_BOUNDED ? seg : nsc) * 0.001);
+                // (never negative otherwise: the sign bit, -0.0f included, marks a transmittance sample.  Not in the light kernels: every
+                // sample of theirs is one, reduce_layers_k knows their slots, and the mark costs the local-majorant ones two registers
+                // and their eighth wave: profiles/layers_kernel_resources.txt)
+                if (LAYERS && !LIGHT && trans) heat = -heat;
                 float4 v    = make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), heat);
                 if (TRK == 2)  // kernel.cu:2311-2313: the drawn channel only, times three
                     v = make_float4(chan == 0 ? v.x * 3.0f : 0.0f, chan == 1 ? v.y * 3.0f : 0.0f, chan == 2 ? v.z * 3.0f : 0.0f, heat);

@@ -154,6 +154,11 @@ struct LaunchDev
     // then that image's table, `pixels`, `out`, `stage` and P stay the W x H image's.  The host launches no approach walk, no segment
     // table and no constant rows with it (vp_render.cpp).
     unsigned sub_shift;
+    // A layers launch (include/volpath.h vp_render_frames_layers; appended like the fields above): 1 = a sample that reaches the
+    // environment unscattered is staged as (max(thr, 0), -heat) -- its throughput, no background, no brightness; the sign bit of w,
+    // -0.0f included, marks it (the light kernel, whose every sample is one, stages heat as it is) -- and reduce_layers_k splits the
+    // staged samples into the two accumulators.  0: the beauty sample, as ever.
+    unsigned layers;
 };
 
 // render_k and the approach kernels: which instance a launch runs, and which of them a build compiles, is decided in vp_dispatch.h.
@@ -206,6 +211,9 @@ void launch_empty_table(const SceneDev& S, unsigned width, unsigned height, cons
 // the direction table of the exit flights from the danger volume: planes = 3 * nx*ny*nz bytes; one small kernel per slice and direction
 void launch_exit_table(const unsigned char* danger, unsigned char* planes, int nx, int ny, int nz, hipStream_t st);
 void launch_reduce(const LaunchDev& L, hipStream_t st);
+// the reduce of a layers launch (LaunchDev::layers): L.out is the foreground accumulator, trans the transmittance accumulator; the slots
+// [light_from, light_to) of the list are the light kernel's, whose samples are transmittance samples without the mark
+void launch_reduce_layers(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st);
 // Per-pixel statistics (include/volpath.h vp_pixel_stats, the same 24 bytes) and what launch_reduce_stats does with them: the
 // reduce of a staged launch that also adds each sample's luminance to its pixel's record, and -- adaptive: a round of
 // vp_render_adaptive -- freezes the records whose criterion holds (tol, fl: the binary32 arguments widened)
@@ -241,6 +249,8 @@ void launch_build_bounds(const void* d_vol, bool quant, bool half, void* d_out, 
 void launch_julia(unsigned char* grid, int n, hipStream_t st);
 void launch_cloud(float* grid, int n, unsigned seed, hipStream_t st);
 void launch_scale(float4* dst, const float4* src, int size, float s, hipStream_t st);
+// dst = fg * s + (trans * s) o B, dst.w = 1 - trans.w * s; B = plate[i].xyz, or the constant (r, g, b) where plate is null (composite_k)
+void launch_composite(float4* dst, const float4* fg, const float4* trans, const float4* plate, float r, float g, float b, int size, float s, hipStream_t st);
 void launch_gamma(float4* dst, const float4* src, int size, float s, float inv_gamma, hipStream_t st);
 void launch_accumulate(float4* dst, const float4* src, size_t n, hipStream_t st);
 void launch_test_hg(const float* g, const float* r0, const float* r1, const float* nrm, const float* cosq, float* dir, float* ev, int n, hipStream_t st);

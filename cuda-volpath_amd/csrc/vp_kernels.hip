@@ -382,6 +382,42 @@ __global__ __launch_bounds__(256) void reduce_stage_k(LaunchDev L)
     L.out[idx] = a;
 }
 
+// reduce_stage_k's job for a layers launch (LaunchDev::layers): a staged sample whose w has the sign bit clear is a foreground sample
+// and goes to L.out whole; one with the sign bit set is an unscattered path's throughput: (x, y, z, 1) goes to `trans`, its heat |w| to
+// L.out.  The slots [light_from, light_to) are those of the light kernel (render_k<LIGHT>), whose every sample is such a throughput
+// and carries no mark.  Both accumulators in frame order; a constant of the launch is added nframes times, as reduce_stage_k adds it.
+__device__ __forceinline__ void add_layer_sample(float4& a, float4& t, const float4 v, bool unmarked)
+{
+    if (unmarked || __builtin_signbit(v.w))
+    {
+        a = make_float4(a.x + 0.0f, a.y + 0.0f, a.z + 0.0f, a.w + __builtin_fabsf(v.w));
+        t = make_float4(t.x + v.x, t.y + v.y, t.z + v.z, t.w + 1.0f);
+    }
+    else
+    {
+        a = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
+        t = make_float4(t.x + 0.0f, t.y + 0.0f, t.z + 0.0f, t.w + 0.0f);
+    }
+}
+__global__ __launch_bounds__(256) void reduce_layers_k(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to)
+{
+    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.nslots) return;
+    unsigned pix = L.pixels[slot];
+    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
+    float4   a = L.out[idx], t = trans[idx];
+    const bool unmarked = slot >= light_from && slot < light_to;
+    if (slot >= L.const_from)
+    {
+        const float4 v = L.stage_const[slot];
+        for (int f = 0; f < L.nframes; f++) add_layer_sample(a, t, v, unmarked);
+    }
+    else
+        for (int f = 0; f < L.nframes; f++) add_layer_sample(a, t, L.stage[(size_t)f * L.stage_stride + slot], unmarked);
+    L.out[idx] = a;
+    trans[idx] = t;
+}
+
 // ---- the pixel lists of a rank, built on the GPU (vp_tables.cpp ensure_pixel_lists): a stable partition of the rank's pixels --
 // those of its 8x8 tiles, tile by tile (row-major tiles, row-major pixels within a tile) -- by pixel class (0 general, 1 the whole
 // chord is certified empty, 2 the camera ray misses the box; pixel table [1].y).  Padded slot s = 64 * (n-th owned tile) + 8 * row +
@@ -622,8 +658,10 @@ __global__ void stats_rel_error_k(float* dst, const PixelStatsDev* stats, int si
 // kernel.cu:1336-1345 / :2020-2031), background() is evaluated for the camera direction with throughput 1 (quirk Q3: no jitter)
 // and the sample is written -- no draw is consumed.  One thread per such pixel evaluates that once, with the integrator's own
 // expressions (EV_BG / EV_WRITE blocks of render_k), and writes it for every frame of the launch.
-__device__ __forceinline__ float4 unscattered_sample(const SceneDev& S, const ParamDev& P, f3 rd, bool& env_lookup)
+// (a layers launch: the transmittance sample of such a path -- throughput 1, heat 0 with the sign bit set: LaunchDev::layers)
+__device__ __forceinline__ float4 unscattered_sample(const SceneDev& S, const ParamDev& P, f3 rd, bool& env_lookup, unsigned layers)
 {
+    if (layers) { env_lookup = false; return make_float4(1.0f, 1.0f, 1.0f, -0.0f); }
     const f3 sun_dir = f3{S.sun_dir[0], S.sun_dir[1], S.sun_dir[2]};
     f3   rad  = f3{0.0f, 0.0f, 0.0f};
     const f3 thr = f3{1.0f, 1.0f, 1.0f};
@@ -644,7 +682,7 @@ __global__ __launch_bounds__(256) void miss_fill_k(SceneDev S, LaunchDev L, int 
     f3 ro, rd;
     camera_ray(S, P.width, P.height, px, py, ro, rd);
     bool env_lookup = false;
-    const float4 v = unscattered_sample(S, P, rd, env_lookup);
+    const float4 v = unscattered_sample(S, P, rd, env_lookup, L.layers);
     if (L.stage)
     {
         // (staged once where the add-kernel knows the slot for a constant: LaunchDev::const_from)
@@ -704,7 +742,7 @@ __global__ __launch_bounds__(256) void subpixel_fill_k(SceneDev S, LaunchDev L)
     f3 ro, rd;
     camera_ray(S, P.width << m, P.height << m, (px << m) + i, (py << m) + j, ro, rd);
     bool env_lookup = false;
-    const float4 v = unscattered_sample(S, P, rd, env_lookup);
+    const float4 v = unscattered_sample(S, P, rd, env_lookup, L.layers);
     if (L.stage)
         for (; fl < (unsigned)L.nframes; fl += n2) L.stage[(size_t)fl * L.stage_stride + L.slot_base + slot] = v;
     else
@@ -1023,6 +1061,17 @@ __global__ void scale_k(float4* dst, const float4* src, int size, float s)
     float4 v = src[idx];
     dst[idx] = make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
 }
+// include/volpath.h vp_composite: foreground plus transmittance times a plate (or a constant colour), both layers scaled first; one
+// multiply and one add per term, in this order (the build has no contraction); w = coverage
+__global__ void composite_k(float4* dst, const float4* fg, const float4* trans, const float4* plate, float r, float g, float b, int size, float s)
+{
+    int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= size) return;
+    const float4 f = fg[idx], t = trans[idx];
+    float bx = r, by = g, bz = b;
+    if (plate) { const float4 q = plate[idx]; bx = q.x; by = q.y; bz = q.z; }
+    dst[idx] = make_float4(f.x * s + (t.x * s) * bx, f.y * s + (t.y * s) * by, f.z * s + (t.z * s) * bz, 1.0f - t.w * s);
+}
 __device__ __forceinline__ float pow_pos(float x, float y) { return x <= 0.0f ? 0.0f : expf_(logf_(x) * y); }
 // __gamma_correct kernel.cu:2348-2357 (inv_gamma = 1/gamma computed by the host wrapper, :2361)
 __global__ void gamma_k(float4* dst, const float4* src, int size, float s, float inv_gamma)
@@ -1331,6 +1380,10 @@ void launch_reduce(const LaunchDev& L, hipStream_t st)
     unsigned per_frame = L.nslots;
     hipLaunchKernelGGL(reduce_stage_k, dim3((per_frame + 255) / 256), dim3(256), 0, st, L);
 }
+void launch_reduce_layers(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st)
+{
+    hipLaunchKernelGGL(reduce_layers_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, trans, light_from, light_to);
+}
 void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st)
 {
     hipLaunchKernelGGL(reduce_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, T);
@@ -1423,6 +1476,10 @@ void launch_cloud(float* grid, int n, unsigned seed, hipStream_t st)
 {
     size_t total = (size_t)n * n * n;
     hipLaunchKernelGGL(cloud_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, grid, n, seed);
+}
+void launch_composite(float4* dst, const float4* fg, const float4* trans, const float4* plate, float r, float g, float b, int size, float s, hipStream_t st)
+{
+    hipLaunchKernelGGL(composite_k, dim3((size + 255) / 256), dim3(256), 0, st, dst, fg, trans, plate, r, g, b, size, s);
 }
 void launch_scale(float4* dst, const float4* src, int size, float s, hipStream_t st)
 {

@@ -224,6 +224,10 @@ struct LaunchPlan
     bool       lookahead;         // ... a look-ahead batch (cancellable, never one of the caller's timed launches)
     bool       stage_only;        // ... which is staged whole and not reduced
     const StatsDev* stats;        // the reduce also takes the statistics
+    float4*    layers;            // a layers call (vp_render_frames_layers): the transmittance accumulator; the reduce splits the samples (reduce_layers_k)
+    // the slots of the list, general pixels first: where the class a kernel integrates ends (the general class and a light class that
+    // is not written as constants), i.e. where the per-pixel constants of a launch begin -- const_from and the layers reduce's range
+    unsigned integrated_end() const { return PL.n_general + ((PL.n_light && !light_const) ? PL.n_light : 0u); }
     PixelLists PL;                // the lists in use: the context's cached ones, or the caller's
     size_t     per_frame;         // ... and their pixels = samples per frame
     bool       staged;            // samples go through the staging buffer and a reduce (false: render_k accumulates one frame directly)
@@ -295,7 +299,8 @@ static int prepare_tables(const Param* p, const Shard& sh, int nframes, const Pi
 static int plan_target(int nframes, const Target* tgt, const PixelLists* lists, LaunchPlan& A)
 {
     // a call with statistics is staged whatever its length (render_k's direct accumulation has none) and stays on the caller's stream
-    A.staged = nframes > 1 || A.stage_only || A.stats;
+    // (a layers call too: the direct accumulation has no second target)
+    A.staged = nframes > 1 || A.stage_only || A.stats || A.layers;
     A.T      = tgt ? *tgt : Target{&G.target[0], G.stream};   // (a pipelined call: a slot's, below)
     A.max_f  = A.staged ? stage_frames_cap(A.per_frame, A.T.rt->stage.bytes) : 1;
     // The staging slot of the decomposition estimator's hand-over holds the segment origin and the distance reached in it: the stream's
@@ -305,7 +310,7 @@ static int plan_target(int nframes, const Target* tgt, const PixelLists* lists, 
     // A staged call of vp_render_frames goes to the next pipeline slot when the slot holds it in one launch (counting launches stay on the
     // caller's stream).  Otherwise -- VP_NO_PIPELINE, no memory for the slot -- the caller's stream, as before: same bits either way.
     A.slot  = G.pipe_next;
-    A.piped = !tgt && !A.stage_only && !lists && !A.stats && nframes > 1 && G.pipeline && !G.count && pipe_target(A.per_frame, nframes, A.appr_aux_needed, &A.T);
+    A.piped = !tgt && !A.stage_only && !lists && !A.stats && !A.layers && nframes > 1 && G.pipeline && !G.count && pipe_target(A.per_frame, nframes, A.appr_aux_needed, &A.T);
     if (A.piped) A.max_f = (size_t)nframes;
     else if (!tgt) G.pipe_fence = true;   // (the caller's stream uses slot 0's buffers: the next pipelined launch waits for it)
     G.last_pipelined = A.piped ? 1 : 0;
@@ -560,6 +565,7 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
         R.adaptive = A.stats->adaptive && last ? 1u : 0u;
         launch_reduce_stats(L, R, G.stream);
     }
+    else if (A.layers) launch_reduce_layers(L, A.layers, A.PL.n_general, A.integrated_end(), G.stream);   // (the light kernel's slots: its samples carry no mark)
     else launch_reduce(L, G.stream);
     HIPCHK(hipGetLastError());
     if (A.piped)
@@ -572,7 +578,8 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
 
 // One render call: check, prepare the tables, plan, then launch by launch -- reserve the staging, wire the pipeline, launch the
 // classes (timed), reduce
-int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only, const Target* tgt, const PixelLists* lists, const StatsDev* stats)
+int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only, const Target* tgt, const PixelLists* lists, const StatsDev* stats,
+              vp_float4* d_trans)
 {
     int rc = ensure_device();
     if (rc) return rc;
@@ -596,9 +603,11 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     // default of rounds 1-4, stays 0.8 % ahead of 28 on the reference's live configuration (profiles/r05_raw/sweep_samplerh.txt)
     if (!G.wait_lanes_set && G.rng == VP_RNG_SAMPLERH && G.trk == VP_TRACK_SPECTRAL) L.wait_lanes = 24;
     if (sh.per_frame == 0) return VP_OK;
-    if ((lists || stats) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics");
+    if ((lists || stats || d_trans) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics or layers");
+    if (d_trans && (lists || stats)) return fail(VP_E_ARG, "a layers call renders the cached lists without statistics");
     LaunchPlan A = {};
-    A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats;
+    A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats; A.layers = (float4*)d_trans;
+    L.layers = d_trans ? 1u : 0u;
     if ((rc = prepare_tables(p, sh, nframes, lists, L, A)) || A.per_frame == 0) return rc;
     if (0xfffffff0u / A.per_frame < 1) return fail(VP_E_ARG, "image too large for the 32-bit sample queue");
     L.stage_stride = (unsigned)A.per_frame;
@@ -622,7 +631,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         L.const_from = 0xffffffffu; L.stage_const = nullptr;
         if (L.stage && G.use_const_rows && !G.sub_shift)   // (a sub-pixel factor: constants of the FINE pixel, staged per frame by subpixel_fill_k)
         {
-            L.const_from  = (unsigned)(A.PL.n_general + ((A.PL.n_light && !A.light_const) ? A.PL.n_light : 0u));
+            L.const_from  = A.integrated_end();
             L.stage_const = L.stage;
         }
         G.last_const_from = L.const_from;
@@ -657,6 +666,33 @@ extern "C" {
 int vp_render_frames(vp_float4* d_output, int first_frame, int n_frames, const Param* p)
 {
     return do_render(d_output, first_frame, n_frames, p);
+}
+// Compositing layers (include/volpath.h): the call's samples are vp_render_frames' -- same plan, lists, tables, walks and kernels, with
+// LaunchDev::layers set --, staged on the caller's stream whatever the frame count, and reduce_layers_k splits them into the two
+// accumulators.  What the switch is not built for is refused before anything is launched (and before the device is asked for).
+int vp_render_frames_layers(vp_float4* d_fg, vp_float4* d_trans, int first_frame, int n_frames, const Param* p)
+{
+    if (!d_fg || !d_trans || d_fg == d_trans || !p || n_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "vp_render_frames_layers: bad arguments");
+    if (G.env_mis) return fail(VP_E_STATE, "vp_render_frames_layers is defined for passive environment lighting only (VP_ENV_MIS: scattered paths never see the sky)");
+    if (G.trk) return fail(VP_E_STATE, "vp_render_frames_layers is built for spectral tracking only");
+    if (G.count) return fail(VP_E_STATE, "vp_render_frames_layers is not built for work counters");
+    if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "vp_render_frames_layers is built for the exact arithmetic only (its kernel instances are the exact unit's)");
+    int rc = ensure_device();
+    if (rc) return rc;
+    // the call is serial and runs on the caller's stream: look-ahead batches stop, pipelined launches are waited for
+    if ((rc = la_quiesce())) return rc;
+    return do_render(d_fg, first_frame, n_frames, p, false, nullptr, nullptr, nullptr, d_trans);
+}
+int vp_composite(vp_float4* dst, const vp_float4* fg, const vp_float4* trans, const vp_float4* plate, const float plate_rgb[3], int size, float scale)
+{
+    if (!dst || !fg || !trans || size < 0 || (!plate && !plate_rgb)) return fail(VP_E_ARG, "vp_composite: bad arguments");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (size)
+        launch_composite((float4*)dst, (const float4*)fg, (const float4*)trans, (const float4*)plate, plate ? 0.0f : plate_rgb[0], plate ? 0.0f : plate_rgb[1],
+                         plate ? 0.0f : plate_rgb[2], size, scale, G.stream);
+    HIPCHK(hipGetLastError());
+    return VP_OK;
 }
 int vp_enable_counters(int on)
 {

@@ -348,9 +348,11 @@ struct Target { RenderTarget* rt; hipStream_t stream; };
 struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss; };
 // lists: null = the context's cached lists of p (built on demand: the plain entry points), else the caller's own -- a class-ordered
 // subset of them (vp_adaptive.cpp).  stats: the reduce also takes the statistics of include/volpath.h (launch_reduce_stats); such a
-// call is staged even for one frame and runs on the caller's stream, not on a pipeline slot.
+// call is staged even for one frame and runs on the caller's stream, not on a pipeline slot.  d_trans: a layers call
+// (vp_render_frames_layers) -- d_out is the foreground accumulator, d_trans the transmittance accumulator; staged and on the caller's
+// stream likewise, with the cached lists and without statistics.
 int  do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only = false, const Target* tgt = nullptr,
-               const PixelLists* lists = nullptr, const StatsDev* stats = nullptr);
+               const PixelLists* lists = nullptr, const StatsDev* stats = nullptr, vp_float4* d_trans = nullptr);
 // the preconditions of a render call, each caller with the subset it needs (p: the image checks; last_frame: the opacity rule)
 enum : unsigned { CHK_STATE = 1, CHK_IMAGE = 2, CHK_IMAGE_NOTE = 4, CHK_MODES = 8, CHK_OPACITY = 16 };
 int  check_render(unsigned what, const Param* p, long long last_frame = 0);

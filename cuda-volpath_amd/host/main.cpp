@@ -43,6 +43,14 @@ static void usage()
            "                                                per-pixel luminance variance; search window (2R+1)^2, R <= 10, default 5; patch\n"
            "                                                (2F+1)^2, F <= 3, default 1; strength K > 0, default 0.45).  The frames then go\n"
            "                                                through vp_render_frames_stats (or --noise).  One GPU, like --noise\n"
+           "               [--layers-out PREFIX] [--over R G B]\n"
+           "                                                compositing layers (vp_render_frames_layers): the frames are rendered as a\n"
+           "                                                foreground F and a per-channel transmittance T, pixel = F + T o B for any\n"
+           "                                                background B.  --layers-out writes the two mean layers as PREFIX_fg.hdr and\n"
+           "                                                PREFIX_trans.hdr (trans.w: the fraction of unscattered samples); --over writes\n"
+           "                                                the composite over the constant colour (R, G, B) to --out (vp_composite; its w is\n"
+           "                                                coverage).  Without --over no --out image is written: the context's own sky is in\n"
+           "                                                neither layer.  One GPU; not with --noise or --denoise; spectral, --env passive, --arith exact\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -68,6 +76,9 @@ int main(int argc, char** argv)
     std::string noise_out;
     bool        denoise = false;
     vp_denoise_params dn = {5, 1, 0.45f};   // (from a 64 x 48 table, not tuned: DESIGN.md section 2.4)
+    std::string layers_out;
+    bool        over = false;
+    float       over_rgb[3] = {0.0f, 0.0f, 0.0f};
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -151,6 +162,18 @@ int main(int argc, char** argv)
                 return 2;
             }
         }
+        else if (a == "--layers-out") { need(1); layers_out = argv[++i]; }
+        else if (a == "--over")
+        {
+            need(3);
+            for (int c = 0; c < 3; c++)
+            {
+                char* end = nullptr;
+                over_rgb[c] = strtof(argv[++i], &end);
+                if (end == argv[i] || *end || !std::isfinite(over_rgb[c])) { fprintf(stderr, "--over %s: three finite numbers\n", argv[i]); usage(); return 2; }
+            }
+            over = true;
+        }
         else if (a == "--sun") { need(2); sunx = (float)atof(argv[++i]); suny = (float)atof(argv[++i]); }
         else if (a == "--batch") { need(1); batch = atoi(argv[++i]); }
         else if (a == "--out") { need(1); out = argv[++i]; }
@@ -188,6 +211,18 @@ int main(int argc, char** argv)
     if (denoise && gpus > 1)
     {
         fprintf(stderr, "--denoise with --gpus %d: the filter reads per-pixel statistics, which are not reduced across ranks; use one GPU\n", gpus);
+        return 2;
+    }
+    const bool layers = over || !layers_out.empty();
+    if (layers && (gpus > 1 || adaptive || denoise))
+    {
+        fprintf(stderr, "--layers-out / --over with %s: layers are not reduced across ranks and carry no per-pixel statistics; use one GPU without --noise and --denoise\n",
+                gpus > 1 ? "--gpus" : adaptive ? "--noise" : "--denoise");
+        return 2;
+    }
+    if (layers && (tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE || arith != VP_ARITH_EXACT))
+    {
+        fprintf(stderr, "--layers-out / --over need spectral tracking, --env passive and --arith exact\n");
         return 2;
     }
     if (adaptive && (min_spp < 2 || round_frames < 1)) { fprintf(stderr, "--noise needs --min-spp >= 2 and --round >= 1\n"); usage(); return 2; }
@@ -301,6 +336,12 @@ int main(int argc, char** argv)
         stats = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
         if (!stats || vp_memset(stats, 0, (size_t)npix * sizeof(vp_pixel_stats))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
     }
+    vp_float4* trans = nullptr;   // --layers-out / --over: accum[0] is the foreground accumulator, this the transmittance accumulator
+    if (layers)
+    {
+        trans = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+        if (!trans || vp_memset(trans, 0, (size_t)npix * sizeof(vp_float4))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+    }
     for (int s = adaptive ? spp : 0; s < spp;)
     {
         if (!have_opacity && est == VP_EST_DECOMP && (s > 10 || (batch > 0 && s + batch > 11)))
@@ -308,7 +349,13 @@ int main(int argc, char** argv)
             for (int r = 0; r < gpus; r++) { use(r); precompute_opacity(&sky.sun_dir.x); }  // host.cpp:336-343
             have_opacity = true;
         }
-        if (denoise)
+        if (layers)
+        {
+            const int n = batch > 0 ? std::min(batch, spp - s) : 1;
+            if (vp_render_frames_layers(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            s += n;
+        }
+        else if (denoise)
         {
             const int n = batch > 0 ? std::min(batch, spp - s) : 1;
             if (vp_render_frames_stats(accum[0], stats, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
@@ -362,7 +409,25 @@ int main(int argc, char** argv)
     use(0);
     bool  hdr = out.size() > 4 && out.substr(out.size() - 4) == ".hdr";
     Image image(W, H);
-    if (denoise)
+    if (layers)
+    {
+        // the two mean layers as they are; the composite over --over's colour in place of the beauty image
+        if (!layers_out.empty())
+            for (int k = 0; k < 2; k++)
+            {
+                const std::string name = layers_out + (k ? "_trans.hdr" : "_fg.hdr");
+                scale(disp, k ? trans : accum[0], npix, 1.0f / spp);
+                vp_download(image.buffer(), disp, (size_t)npix * sizeof(vp_float4));
+                image.dump_hdr(name.c_str());
+                printf("wrote %s\n", name.c_str());
+            }
+        if (over)
+        {
+            if (vp_composite(disp, accum[0], trans, nullptr, over_rgb, npix, 1.0f / spp)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
+        }
+    }
+    else if (denoise)
     {
         // the filtered mean image: the division by each pixel's count is part of the call
         if (vp_denoise(disp, accum[0], stats, nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
@@ -377,10 +442,13 @@ int main(int argc, char** argv)
     }
     else if (hdr) scale(disp, accum[0], npix, 1.0f / spp);
     else gamma_correct(disp, accum[0], npix, 1.0f / spp, 2.2f);
-    vp_download(image.buffer(), disp, (size_t)npix * sizeof(vp_float4));
-    if (hdr) image.dump_hdr(out.c_str());
-    else image.dump_ppm(out.c_str());
-    printf("wrote %s\n", out.c_str());
+    if (!layers || over)
+    {
+        vp_download(image.buffer(), disp, (size_t)npix * sizeof(vp_float4));
+        if (hdr) image.dump_hdr(out.c_str());
+        else image.dump_ppm(out.c_str());
+        printf("wrote %s\n", out.c_str());
+    }
     if (adaptive && !noise_out.empty())
     {
         // the noise map: estimated standard error of the mean luminance over max(mean, floor), grey, as HDR
@@ -398,6 +466,7 @@ int main(int argc, char** argv)
         vp_free(d_noise);
     }
     if (stats) vp_free(stats);
+    if (trans) vp_free(trans);
     vp_free(disp);
     for (int r = 0; r < gpus; r++)
     {

@@ -33,6 +33,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists", "vp_get_segment_table",
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
+                 "vp_render_frames_layers", "vp_composite",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_intersect_box",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -135,6 +136,8 @@ def lib():
         L.vp_stats_rel_error.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
         L.vp_denoise.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(DenoiseParams)]
         L.vp_set_denoise_form.argtypes = [C.c_int]
+        L.vp_render_frames_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_int, C.c_float]
         L.vp_read_counters.argtypes = [C.POINTER(Counters), C.c_int]
         L.vp_render_time_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
         L.vp_get_bound_table.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 5
@@ -411,6 +414,19 @@ def render_adaptive(buf_ptr, stats_ptr, first, max_frames, P, rel_tol, floor_y=1
     r = AdaptiveResult()
     _chk(lib().vp_render_adaptive(buf_ptr, stats_ptr, first, max_frames, C.byref(P), C.byref(a), C.byref(r)))
     return r.as_dict()
+
+
+def render_frames_layers(fg_ptr, trans_ptr, first, n, P):
+    """the frames of render_frames as two compositing layers (vp_render_frames_layers): foreground sums into fg_ptr, per-channel
+    transmittance sums (w: the count of unscattered samples) into trans_ptr; pixel = fg + trans * background"""
+    _chk(lib().vp_render_frames_layers(fg_ptr, trans_ptr, first, n, C.byref(P)))
+
+
+def composite(dst_ptr, fg_ptr, trans_ptr, n, s, plate_ptr=None, plate_rgb=None):
+    """dst.xyz = fg.xyz * s + (trans.xyz * s) * B, dst.w = 1 - trans.w * s (vp_composite); B is the plate's pixel, or the constant
+    plate_rgb where plate_ptr is None"""
+    rgb = (C.c_float * 3)(*[float(v) for v in plate_rgb]) if plate_rgb is not None else None
+    _chk(lib().vp_composite(dst_ptr, fg_ptr, trans_ptr, plate_ptr, rgb, n, s))
 
 
 def scale_by_count(dst_ptr, src_ptr, stats_ptr, n, s):

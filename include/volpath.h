@@ -352,6 +352,37 @@ int vp_denoise(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_sta
 int vp_set_denoise_form(int form);
 int vp_last_denoise_form(void);
 
+/* Compositing layers: a foreground F and a per-channel transmittance T with  pixel = F + T o B  for any
+ * background B -- another sky, a plate, a second render.  vp_render_frames bakes the context's own sky into every sample and keeps
+ * the reference's heat value in w; these two calls are what a compositor needs instead.
+ *
+ * vp_render_frames_layers.  Take the sample (x, y, frame) that vp_render_frames computes: same path, same draws, same streams.  Let
+ * thr be its throughput where it leaves the medium for the environment and heat its fourth channel.  The path is UNSCATTERED if it
+ * gets there without a scatter event (a camera ray that misses the box, or one tracked through the box with null collisions only).
+ *   unscattered:  fg sample (0, 0, 0, heat)                 trans sample (max(thr.x, 0), max(thr.y, 0), max(thr.z, 0), 1)
+ *   otherwise:    fg sample = the vp_render_frames sample    trans sample (0, 0, 0, 0)
+ * No brightness and no background enter a trans sample; the fg sample of a scattered path includes the sky light it sees after
+ * scattering.  Both caller-owned accumulators (width * height float4 each, not the same buffer) receive their samples in frame
+ * order, like vp_render_frames' accumulator.  So fg.w is bit-equal to vp_render_frames' w; trans.w / n is the fraction of unscattered
+ * samples; 1 - trans.xyz / n is the per-channel alpha.  Equivalently: the trans RGB of an unscattered sample is the vp_render_frames
+ * sample of the same scene with every environment texel (1, 1, 1), a sun disc of (1, 1, 1) and brightness 1 -- with the passive
+ * environment none of those influences a draw.
+ *   Obeys vp_set_shard, vp_set_estimator, vp_set_rng and vp_set_subpixel (every value each), every volume format and cell order.
+ *   It runs kernel instances of its own, built in the exact arithmetic only; vp_render_frames' kernels carry no code for it.  The call stops look-ahead batches, waits for pipelined launches and runs staged on the
+ *   context's stream, for one frame too; it leaves nothing behind: a vp_render_frames call after it renders the bits it rendered
+ *   before.
+ *   Refused before anything is launched and before the device is touched, with VP_E_ARG: NULL pointers, d_fg == d_trans,
+ *   n_frames <= 0, first_frame < 0; with VP_E_STATE: VP_ENV_MIS (scattered paths never see the sky there: another definition),
+ *   scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST.  Both buffers are then untouched.  Other errors as vp_render_frames.
+ *   Statistics, adaptive rounds and vp_denoise on layers, and reducing layers across processes, are not built.
+ *
+ * vp_composite, the output stage: for i < size, with B = plate[i].xyz where plate is non-NULL, else plate_rgb[0..2],
+ *   dst[i].xyz = fg[i].xyz * scale + (trans[i].xyz * scale) * B        dst[i].w = 1 - trans[i].w * scale   (coverage)
+ * in binary32: one multiply and one add per term in this order, no contraction.  scale is 1 / frames.  dst may be fg or trans.
+ * Needs no scene; runs asynchronously on the context's stream.  VP_E_ARG: NULL dst, fg or trans, both plate pointers NULL, size < 0. */
+int vp_render_frames_layers(vp_float4* d_fg, vp_float4* d_trans, int first_frame, int n_frames, const Param* p);
+int vp_composite(vp_float4* dst, const vp_float4* fg, const vp_float4* trans, const vp_float4* plate, const float plate_rgb[3], int size, float scale);
+
 typedef struct
 {
     uint64_t samples;

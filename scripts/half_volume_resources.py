@@ -50,6 +50,11 @@ def parse(text):
             if d[i] == "(" and depth == 0:
                 d = d[:i]
                 break
+        # render_k's twelfth argument (LYR: a layers instance) is not part of the name here, so that HALF
+        # stays the last one: a plain instance drops it, a layers instance is listed as render_k[layers]<...>
+        if "render_k<" in d and d.count(",") == 11:
+            d, lyr = d.rsplit(", ", 1)
+            d = (d if lyr == "false>" else d.replace("render_k<", "render_k[layers]<")) + ">"
         out[d] = rows[n]
     return out
 
