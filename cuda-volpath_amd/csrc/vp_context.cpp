@@ -898,6 +898,27 @@ int vp_test_approach_walk(int kind, int n, const float* params, const uint32_t* 
     HIPCHK(hipMemcpy(out_ref, dr, c * 20, hipMemcpyDeviceToHost));
     return VP_OK;
 }
+int vp_test_sun_start(int n, const float* origin_xyz, const float* sun_dir, const float* box, uint32_t* out_new, uint32_t* out_ref)
+{
+    if (n < 0) return fail(VP_E_ARG, "vp_test_sun_start: negative count %d", n);
+    if (!origin_xyz || !sun_dir || !box || !out_new || !out_ref) return fail(VP_E_ARG, "vp_test_sun_start: null argument");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (n == 0) return VP_OK;
+    DevArrays D;
+    const size_t c = (size_t)n;
+    float*    dor = (float*)D.get(c * 12), *db = (float*)D.get(24);
+    unsigned *dn = (unsigned*)D.get(c * 32), *dr = (unsigned*)D.get(c * 32);
+    if (!dor || !db || !dn || !dr) return fail(VP_E_NOMEM, "vp_test_sun_start: no device memory");
+    HIPCHK(hipMemcpy(dor, origin_xyz, c * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db, box, 24, hipMemcpyHostToDevice));
+    if (G.arith == VP_ARITH_FAST) launch_test_sun_start_fast(n, dor, sun_dir, db, dn, dr, G.stream);
+    else launch_test_sun_start(n, dor, sun_dir, db, dn, dr, G.stream);
+    HIPCHK(hipStreamSynchronize(G.stream));
+    HIPCHK(hipMemcpy(out_new, dn, c * 32, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_ref, dr, c * 32, hipMemcpyDeviceToHost));
+    return VP_OK;
+}
 int vp_test_hg(const float* g, const float* r0, const float* r1, const float* normal_xyz, const float* cos_query, float* dir_xyz, float* eval, int n)
 {
     int rc = ensure_device();

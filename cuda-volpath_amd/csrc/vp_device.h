@@ -716,5 +716,94 @@ __device__ __forceinline__ float hg_eval_row(const float* row, float cos_theta)
 {
     return div_(row[CR_OMG2], (4.0f * kPi) * pow15f_(row[CR_OPG2] - row[CR_2G] * cos_theta));
 }
+
+// The sun shadow ray's constants: one more row, filled once per workgroup beside the sixteen above.  The ray runs from the collision
+// point ro toward end = sun_dir * 1e10f, whose components are of order 1e9-1e10 (ulp 64-1024) unless sun_dir has a small one: the
+// difference end - ro then rounds to end itself, and the squared length absorbs the square of a small component.  What the ray's
+// start computes from those operands is what it computes for ro = 0 -- the row holds exactly that, by the integrator's own
+// expressions in the same order and in the arithmetic mode of the translation unit:
+enum : int
+{
+    SR_E    = 0,    // end = sun_dir * 1e10f                                  (three words)
+    SR_D2   = 3,    // dot(end, end), left to right
+    SR_LEN  = 4,    // sqrt_(D2): the ray's length
+    SR_R    = 5,    // what the difference is multiplied by: rcp_(LEN) in the exact unit, rsqrt_(D2) in the fast one
+    SR_IR   = 6,    // 1.0f / (end.c * R): the box test's slab reciprocal of a direction component, IEEE   (three words)
+    SR_WORDS = 9
+};
+__device__ __forceinline__ void sun_row_fill(float* row, f3 sun_dir)
+{
+    const f3    e   = sun_dir * 1e10f;
+    const float d2  = dot(e, e);
+    const float len = sqrt_(d2);
+#ifdef VP_ARITH_FAST
+    const float r = rsqrt_(d2);
+#else
+    const float r = rcp_(len);
+#endif
+    const f3 sd = e * r;
+    row[SR_E] = e.x; row[SR_E + 1] = e.y; row[SR_E + 2] = e.z;
+    row[SR_D2]  = d2;
+    row[SR_LEN] = len;
+    row[SR_R]   = r;
+    row[SR_IR] = 1.0f / sd.x; row[SR_IR + 1] = 1.0f / sd.y; row[SR_IR + 2] = 1.0f / sd.z;
+}
+// One slab of intersect_box with the reciprocal either read (a wave whose operands are the row's) or divided for
+// (the box is read behind the division, as intersect_box's scheduling has it: two registers less across the sequence)
+__device__ __forceinline__ void sun_start_slab(const float* row, int c, bool axis_const, float sdc, float oc, const float* bmin, const float* bmax, float& tmn, float& tmx)
+{
+    float ir;
+    if (axis_const) ir = row[SR_IR + c];
+    else ir = 1.0f / sdc;
+    const float tb = ir * (bmin[c] - oc), tt = ir * (bmax[c] - oc);
+    tmn = fminf(tt, tb); tmx = fmaxf(tt, tb);
+}
+// The start of a sun shadow ray (render_k start_shadow, stage 0) for instances that have the row: direction sd, length len and the
+// box test, with the values start_shadow and intersect_box compute, bit for bit.  MEMOISATION ON EXACT OPERAND BITS, decided per
+// wave at run time: a root, a reciprocal or a division is skipped only where its operands have the bit patterns the row's results
+// were computed from, so no statement about where ro can lie is needed and nothing about the box test changes -- the slab products,
+// min, max and the hit test are intersect_box's, axis by axis with its sched_barriers (the integrator's register peak: the
+// direction is complete before the first slab, as it is there, so the factor and the difference are dead by then).  The compares
+// are INTEGER compares of the patterns (-0 is not +0 -- its reciprocal differs -- and a NaN equals a NaN of the same payload),
+// reduced over the lanes active here with one ballot each: the branches are wave-uniform, so a wave either skips a sequence or runs
+// it, never both.  A per-axis constant is valid only with the constant factor R: dv.c * R is end.c * R, and its reciprocal the row's
+// IR.c, where both operands have the row's bits.
+// (`taken`, the test hook's: bit 0 = the wave read the length and the factor, bits 1..3 = the slab reciprocal of x, y, z)
+__device__ __forceinline__ bool sun_start(const float* row, f3 o, const float* bmin, const float* bmax, f3& sd, float& len, float& tnear, float& tfar,
+                                          unsigned* taken = nullptr)
+{
+    const f3    dv = f3{row[SR_E], row[SR_E + 1], row[SR_E + 2]} - o;
+    const float d2 = dot(dv, dv);
+    const bool  factor_const = __ballot(f2u(d2) != f2u(row[SR_D2])) == 0ull;
+    const bool  x_const = factor_const && __ballot(f2u(dv.x) != f2u(row[SR_E])) == 0ull;
+    const bool  y_const = factor_const && __ballot(f2u(dv.y) != f2u(row[SR_E + 1])) == 0ull;
+    const bool  z_const = factor_const && __ballot(f2u(dv.z) != f2u(row[SR_E + 2])) == 0ull;
+    if (taken) *taken = (factor_const ? 1u : 0u) | (x_const ? 2u : 0u) | (y_const ? 4u : 0u) | (z_const ? 8u : 0u);
+    float       r;
+    if (factor_const)
+    {
+        len = row[SR_LEN];
+        r   = row[SR_R];
+    }
+    else
+    {
+        len = sqrt_(d2);
+#ifdef VP_ARITH_FAST
+        r = rsqrt_(d2);
+#else
+        r = rcp_(len);
+#endif
+    }
+    sd = dv * r;   // (one multiply per axis either way: a product of the row's bits is end.c * R, which is what IR.c is the reciprocal of)
+    float tmn, tmx, tmn_y, tmx_y, tmn_z, tmx_z;
+    sun_start_slab(row, 0, x_const, sd.x, o.x, bmin, bmax, tmn, tmx);
+    __builtin_amdgcn_sched_barrier(0);
+    sun_start_slab(row, 1, y_const, sd.y, o.y, bmin, bmax, tmn_y, tmx_y);
+    __builtin_amdgcn_sched_barrier(0);
+    sun_start_slab(row, 2, z_const, sd.z, o.z, bmin, bmax, tmn_z, tmx_z);
+    const float lt = max3(f3{tmn, tmn_y, tmn_z}), st_ = min3(f3{tmx, tmx_y, tmx_z});
+    tnear = lt; tfar = st_;
+    return st_ > lt && st_ >= 1e-3f;
+}
 VP_ARITH_END
 }  // namespace vp

@@ -236,21 +236,36 @@ void render_k(SceneDev S, LaunchDev L)
     // VP_EXP_FLAT_KARGS: the flat loads, for the A/B (profiles/experiments/r05_kargs_lds.txt).
     constexpr unsigned KARG_L_   = ((sizeof(SceneDev) + alignof(LaunchDev) - 1) / alignof(LaunchDev)) * alignof(LaunchDev);
     constexpr unsigned KARG_WDS_ = (KARG_L_ + sizeof(LaunchDev) + 3) / 4;
-    __shared__ __attribute__((aligned(16))) unsigned kargs_lds_[KARG_WDS_];
+    constexpr bool LOCAL = EST != EST_GLOBAL;  // the two local-majorant estimators share the segment logic
+    constexpr bool TAB   = TRK == 0 && LDSB != 1 && !LIGHT && !MIS;   // the instances with the collision block's tables, below
+    // SUNROW: the sun ray's row (vp_device.h sun_row_fill) lies behind the copy, so that the event section's opaque offset reaches it
+    // too.  The instances with the tables except the bounded estimator's: its achromatic kernels run a wave ABOVE the occupancy their
+    // register budget asks for (71 registers: seven waves where six are budgeted) and the second path costs them that wave, so
+    // they keep the general start.  Not with VP_EXP_BOX_PARALLEL either: sun_start's box test is the axis-by-axis sequence, and
+    // that experiment's build is to run the other form everywhere.
+#ifdef VP_EXP_BOX_PARALLEL
+    constexpr bool SUNROW = false;
+#else
+    constexpr bool SUNROW = TAB && EST != EST_BOUNDED;
+#endif
+    __shared__ __attribute__((aligned(16))) unsigned kargs_lds_[KARG_WDS_ + (SUNROW ? SR_WORDS : 0)];
     {
         const unsigned* src = (const unsigned*)__builtin_amdgcn_kernarg_segment_ptr();
         for (unsigned w = threadIdx.x; w < KARG_WDS_; w += (LDSB == 1 ? VP_BLOCK_LDS : VP_BLOCK)) kargs_lds_[w] = src[w];
     }
-    constexpr bool LOCAL = EST != EST_GLOBAL;  // the two local-majorant estimators share the segment logic
     // The collision block's scene constants (vp_device.h coll_row_fill): what a collision, the shadow ray it starts and the segment
     // after it need from the scatter count and Param alone -- the Hyperion-reduced phase parameter with the g-only parts of the phase
     // function, the reduced density, the global majorant and its reciprocal: two IEEE reciprocals, a division and ~25 other
     // instructions per collision -- takes sixteen values per launch.  Thread n fills row n; a collision reads two rows.  Spectral
     // tracking without MIS only; not the 16-bit LDS-table kernel, whose two workgroups per CU leave no byte of LDS over.
-    constexpr bool TAB = TRK == 0 && LDSB != 1 && !LIGHT && !MIS;
+    // The sun shadow ray's constants (sun_row_fill): what its start computes from sun_dir alone -- the far end, the length, the
+    // direction and the box test's slab reciprocals -- takes one value each per launch wherever the collision point is absorbed by
+    // the far end's magnitude.  One more thread fills that row; start_shadow compares operand bits per wave (vp_device.h sun_start).
     __shared__ __attribute__((aligned(16))) float coll_tab_[TAB ? VP_COLL_ROWS : 1][CR_WORDS];
     if (TAB && threadIdx.x < VP_COLL_ROWS)
         coll_row_fill(coll_tab_[threadIdx.x], (int)threadIdx.x, L.P.g, L.P.density, max3(f3{L.P.sigma_t[0], L.P.sigma_t[1], L.P.sigma_t[2]}), LOCAL);
+    if (SUNROW && threadIdx.x == VP_COLL_ROWS)
+        sun_row_fill(reinterpret_cast<float*>(kargs_lds_ + KARG_WDS_), f3{S.sun_dir[0], S.sun_dir[1], S.sun_dir[2]});
     __syncthreads();
     auto coll_row = [&](int n) __attribute__((always_inline)) -> const float* {
         return TAB ? coll_tab_[n < 0 ? 0 : (n > VP_COLL_ROWS - 1 ? VP_COLL_ROWS - 1 : n)] : nullptr;
@@ -305,7 +320,7 @@ void render_k(SceneDev S, LaunchDev L)
     // DEFER: the light weight of the shadow ray in flight takes the place of `ph` (one word, achromatic) or that word and two more
     // (chromatic); one more word holds the ended ray's termination bits until the event pass has added its light
     constexpr int NCOLD = 14 + (DEFER ? (ACH ? 1 : 3) : 0);
-    static_assert(!COLD || (LOCAL ? VP_LOCAL_MIN_WAVES : VP_GLOBAL_MIN_WAVES) * (NCOLD * VP_BLOCK * 4 + KARG_WDS_ * 4 + VP_COLL_ROWS * CR_WORDS * 4 + (LDSB == 2 ? VP_LDS_BOUND_ENTRIES / 4 : 0)) <= VP_LDS_BYTES_PER_CU,
+    static_assert(!COLD || (LOCAL ? VP_LOCAL_MIN_WAVES : VP_GLOBAL_MIN_WAVES) * (NCOLD * VP_BLOCK * 4 + KARG_WDS_ * 4 + VP_COLL_ROWS * CR_WORDS * 4 + (SUNROW ? SR_WORDS * 4 : 0) + (LDSB == 2 ? VP_LDS_BOUND_ENTRIES / 4 : 0)) <= VP_LDS_BYTES_PER_CU,
                   "cold per-path state: more workgroups per CU than the LDS holds -- lower VP_*_MIN_WAVES for this ARCH");
     __shared__ float cold_[COLD ? NCOLD : 1][CS_];
     float* const cold_p = &cold_[0][COLD ? threadIdx.x : 0];
@@ -418,16 +433,32 @@ void render_k(SceneDev S, LaunchDev L)
         auto start_shadow = [&](f3 end, float inv_s, float den, unsigned stage) __attribute__((always_inline)) {
             // the ray's length |end - ro| is the root normalize() takes: formed once (ro - end is -(end - ro) exactly, so the squares
             // and their left-to-right sum are the same bits), then the reciprocal -- normalize's own v * (1.0f / sqrtf(dot(v, v)))
-            const f3    dv = end - ro;
-            const float d2 = dot(dv, dv);
-            const float len = sqrt_(d2);
-#ifdef VP_ARITH_FAST
-            f3 sd = dv * rsqrt_(d2);   // (the fast mode keeps its two instructions, v_sqrt_f32 and v_rsq_f32, and its bits)
+            f3    sd;
+            float len, tn, tf;
+            bool  hitv;
+            if (SUNROW && stage == 0u)
+            {
+                // the sun ray, with the row of its constants: the same values, the roots and divisions taken only where a wave's
+                // operands differ in a bit from the row's (`end` is the row's first three words)
+#ifdef VP_EXP_FLAT_KARGS
+                const float* const srow = reinterpret_cast<const float*>(kargs_lds_ + KARG_WDS_);
 #else
-            f3 sd = dv * rcp_(len);
+                const float* const srow = reinterpret_cast<const float*>(kargs_ + KARG_WDS_ * 4u);
 #endif
-            float tn, tf;
-            bool  hitv = intersect_box(ro, sd, S, tn, tf);
+                hitv = sun_start(srow, ro, S.bmin, S.bmax, sd, len, tn, tf);
+            }
+            else
+            {
+                const f3    dv = end - ro;
+                const float d2 = dot(dv, dv);
+                len = sqrt_(d2);
+#ifdef VP_ARITH_FAST
+                sd = dv * rsqrt_(d2);   // (the fast mode keeps its two instructions, v_sqrt_f32 and v_rsq_f32, and its bits)
+#else
+                sd = dv * rcp_(len);
+#endif
+                hitv = intersect_box(ro, sd, S, tn, tf);
+            }
             if (!hitv)
             {
                 nee_a = f3{1.0f, 1.0f, 1.0f};

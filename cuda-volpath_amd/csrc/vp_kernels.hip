@@ -1167,7 +1167,7 @@ __global__ void accumulate_k(float4* dst, const float4* src, size_t n)
 }
 
 // ---- test kernels
-// test_hg_k, test_math_k, test_log_forms_k, test_approach_walk_k: vp_test_kernels.h (compiled in both arithmetic modes)
+// test_hg_k, test_math_k, test_log_forms_k, test_approach_walk_k, test_sun_start_k: vp_test_kernels.h (compiled in both arithmetic modes)
 #include "vp_test_kernels.h"
 // vp_test_roots: the in-range root helpers of vp_math.h against the general forms compiled here, on every bit pattern in [lo, hi]
 __global__ void test_roots_k(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad)
@@ -1520,6 +1520,10 @@ void launch_test_log_forms(int which, unsigned lo, unsigned hi, unsigned long lo
 void launch_test_approach_walk(int kind, int n, const float* par, const unsigned* scr, const unsigned* words, unsigned* out_new, unsigned* out_ref, hipStream_t st)
 {
     hipLaunchKernelGGL(test_approach_walk_k, dim3((n + 63) / 64), dim3(64), 0, st, kind, n, par, scr, words, out_new, out_ref);
+}
+void launch_test_sun_start(int n, const float* origin, const float* sun_dir, const float* box, unsigned* out_new, unsigned* out_ref, hipStream_t st)
+{
+    hipLaunchKernelGGL(test_sun_start_k, dim3((n + 255) / 256), dim3(256), 0, st, n, origin, sun_dir[0], sun_dir[1], sun_dir[2], box, out_new, out_ref);
 }
 void launch_test_rng(int mode, unsigned x, unsigned y, unsigned f, unsigned k0, unsigned k1, int n, float* out, hipStream_t st)
 {

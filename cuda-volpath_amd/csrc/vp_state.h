@@ -175,9 +175,10 @@ struct State
     bool        opacity_lds = true;       // precompute_opacity stages the density grid through LDS (opacity_lds_k; VP_NO_OPACITY_LDS=1: opacity_k)
     bool        wait_lanes_set = false;   // VP_WAIT_LANES given: no per-kernel default
     unsigned    wait_lanes  = VP_WAIT_LANES, wait_iters = VP_WAIT_ITERS, setup_lanes = VP_SETUP_LANES, end_lanes = VP_END_LANES, light_wait_iters = 0;  // 0 = by estimator
-    unsigned    blocks_per_cu = 8;  // 256-thread workgroups per CU launched for a kernel that runs alone: as many as can be resident (seven of
-                                    // the achromatic global-majorant kernel, six of the other plain ones, five of the chromatic local ones; a
-                                    // workgroup too many starts when the queues are empty and ends at once)
+    unsigned    blocks_per_cu = 8;  // 256-thread workgroups per CU launched for a kernel that runs alone: as many as can be resident (eight of
+                                    // the achromatic global-majorant kernel -- 64 registers since its sun ray starts from the LDS row, seven
+                                    // at 70 before -- seven of the chromatic one, six of the other plain ones, five of the chromatic local
+                                    // ones; a workgroup too many starts when the queues are empty and ends at once)
     unsigned    chunk_fshift = 0;         // VP_CHUNK_FRAMES_LOG2: a chunk = (VP_CHUNK >> k) pixels x (1 << k) frames (general class), k <= log2(VP_CHUNK)
     bool        use_lds_bounds = true;
     bool        use_lds_compact = true;   // a brick table of at most four distinct pairs goes through LDS as 2-bit codes (VP_NO_LDS_COMPACT=1: as 16-bit pairs)

@@ -1,5 +1,5 @@
 // vp_test_kernels.h -- the test hooks of the integrator's arithmetic: vp_test_math (test_math_k), vp_test_hg (test_hg_k),
-// vp_test_log_forms (test_log_forms_k) and vp_test_approach_walk (test_approach_walk_k).
+// vp_test_log_forms (test_log_forms_k), vp_test_approach_walk (test_approach_walk_k) and vp_test_sun_start (test_sun_start_k).
 // Included INSIDE a namespace by both translation units, like vp_integrator.h: vp_kernels.hip (namespace vp, the exact helpers) and
 // vp_kernels_fast.hip (namespace vp::fast, VP_ARITH_FAST).  vp_context.cpp launches the pair of the context's arithmetic mode, so
 // the hooks test the helpers the context's renders run.
@@ -171,5 +171,57 @@ __global__ void test_approach_walk_k(int kind, int n, const float* par, const un
         }
         unsigned* o = (ref ? out_ref : out_new) + 5 * (size_t)i;
         o[0] = f2u(dist); o[1] = steps; o[2] = sa; o[3] = sb; o[4] = through;
+    }
+}
+
+// ---- vp_test_sun_start: the start of a sun shadow ray with the row of its constants (vp_device.h sun_start) against the form it had
+// before (profiles/experiments/sun_start_constants.txt).  TEST-ONLY code below: start_shadow's set-up as it stood, word for word.
+__device__ __forceinline__ bool sun_start_ref_(f3 ro, f3 end, const SceneDev& S, f3& sd_out, float& len_out, float& tn, float& tf)
+{
+    // the ray's length |end - ro| is the root normalize() takes: formed once (ro - end is -(end - ro) exactly, so the squares
+    // and their left-to-right sum are the same bits), then the reciprocal -- normalize's own v * (1.0f / sqrtf(dot(v, v)))
+    const f3    dv = end - ro;
+    const float d2 = dot(dv, dv);
+    const float len = sqrt_(d2);
+#ifdef VP_ARITH_FAST
+    f3 sd = dv * rsqrt_(d2);   // (the fast mode keeps its two instructions, v_sqrt_f32 and v_rsq_f32, and its bits)
+#else
+    f3 sd = dv * rcp_(len);
+#endif
+    bool  hitv = intersect_box(ro, sd, S, tn, tf);
+    sd_out = sd; len_out = len;
+    return hitv;
+}
+// One thread per origin, one sun and one box per launch, as in render_k: thread 0 of a workgroup fills the row in LDS, the waves of
+// 64 consecutive origins decide their branches together (lanes behind n are inactive, as lanes outside the collision block are).
+// box[0..2] = bmin, box[3..5] = bmax.  out_new / out_ref[8 i ..] = (bits of sd.x, sd.y, sd.z, len, tnear, tfar; hit; the branches the
+// lane's wave took -- sun_start's `taken` -- in out_new, 0 in out_ref).
+__global__ void test_sun_start_k(int n, const float* origin, float sun_x, float sun_y, float sun_z, const float* box, unsigned* out_new, unsigned* out_ref)
+{
+    const f3 sun_dir = f3{sun_x, sun_y, sun_z};
+    __shared__ float row[SR_WORDS];
+    __shared__ float lbox[6];
+    if (threadIdx.x == 0) sun_row_fill(row, sun_dir);
+    if (threadIdx.x < 6) lbox[threadIdx.x] = box[threadIdx.x];
+    __syncthreads();
+    const int i = threadIdx.x + blockIdx.x * blockDim.x;
+    if (i >= n) return;
+    const f3 ro = f3{origin[3 * (size_t)i], origin[3 * (size_t)i + 1], origin[3 * (size_t)i + 2]};
+    {
+        f3       sd;
+        float    len, tn, tf;
+        unsigned taken = 0;
+        const bool hit = sun_start(row, ro, lbox, lbox + 3, sd, len, tn, tf, &taken);
+        unsigned* o = out_new + 8 * (size_t)i;
+        o[0] = f2u(sd.x); o[1] = f2u(sd.y); o[2] = f2u(sd.z); o[3] = f2u(len); o[4] = f2u(tn); o[5] = f2u(tf); o[6] = hit ? 1u : 0u; o[7] = taken;
+    }
+    {
+        SceneDev S = {};
+        for (int c = 0; c < 3; c++) { S.bmin[c] = lbox[c]; S.bmax[c] = lbox[3 + c]; }
+        f3    sd;
+        float len, tn, tf;
+        const bool hit = sun_start_ref_(ro, sun_dir * 1e10f, S, sd, len, tn, tf);
+        unsigned* o = out_ref + 8 * (size_t)i;
+        o[0] = f2u(sd.x); o[1] = f2u(sd.y); o[2] = f2u(sd.z); o[3] = f2u(len); o[4] = f2u(tn); o[5] = f2u(tf); o[6] = hit ? 1u : 0u; o[7] = 0u;
     }
 }

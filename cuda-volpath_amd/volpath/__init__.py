@@ -34,7 +34,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
                  "vp_render_frames_layers", "vp_composite",
-                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_intersect_box",
+                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_intersect_box",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
                  "vp_upload", "vp_download"]
@@ -157,6 +157,7 @@ def lib():
         L.vp_test_roots.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.vp_test_log_forms.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.vp_test_approach_walk.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.vp_test_sun_start.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vp_test_rng.argtypes = [C.c_int] + [C.c_uint32] * 5 + [C.c_int, C.c_void_p]
         L.vp_test_sample_density.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.vp_test_hg.argtypes = [C.c_void_p] * 7 + [C.c_int]
@@ -675,6 +676,21 @@ def test_approach_walk(kind, params, script, words):
         raise ValueError("params and script describe different numbers of cases")
     new, ref = np.zeros((n, 5), np.uint32), np.zeros((n, 5), np.uint32)
     _chk(lib().vp_test_approach_walk(kind, n, _p(params), _p(script), _p(words), words.size, _p(new), _p(ref)))
+    return new, ref
+
+
+def test_sun_start(origins, sun_dir, box):
+    """(new, ref): uint32 [n, 8] starts of the sun shadow ray from the n collision points `origins` (float32 [n, 3]) toward sun_dir
+    (three floats, taken as they are) against the box (bmin xyz, bmax xyz), with the sun row and as it stood: bits of the direction,
+    the length, tnear, tfar; hit; in `new` the branches the origin's wave of 64 took (include/volpath.h)"""
+    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    sun_dir = np.ascontiguousarray(sun_dir, np.float32).ravel()
+    box = np.ascontiguousarray(box, np.float32).ravel()
+    if sun_dir.size != 3 or box.size != 6:
+        raise ValueError("sun_dir has three components, box six (bmin, bmax)")
+    n = origins.shape[0]
+    new, ref = np.zeros((n, 8), np.uint32), np.zeros((n, 8), np.uint32)
+    _chk(lib().vp_test_sun_start(n, _p(origins), _p(sun_dir), _p(box), _p(new), _p(ref)))
     return new, ref
 
 

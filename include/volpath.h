@@ -518,6 +518,14 @@ int vp_test_log_forms(int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* m
  * the device is touched, for another kind, n < 0, a null array or a script outside the n_words given. */
 int vp_test_approach_walk(int kind, int n, const float* params, const uint32_t* script, const uint32_t* words, uint32_t n_words,
                           uint32_t* out_new, uint32_t* out_ref);
+/* vp_test_sun_start: the start of a sun shadow ray -- direction, length and the box test -- as the integrator's instances with the
+ * sun row take it (memoised on the exact bits of its operands, decided per wave of 64 consecutive origins) and as it stood (kept
+ * word for word in the test kernels), on n collision points origin_xyz[3 i ..] with one sun direction (three floats, any values) and
+ * one box (bmin xyz, bmax xyz), in the current context's arithmetic mode.  out_new / out_ref[8 i ..] = (bits of the direction's x, y,
+ * z, of the length, of tnear and tfar as intersectBox leaves them; hit; in out_new the branches the origin's wave took: bit 0 = the
+ * length and the factor were read, bits 1..3 = the slab reciprocal of x, y, z was read; 0 in out_ref).  The first seven words agree
+ * bit for bit for every input.  VP_E_ARG, before the device is touched, for n < 0 or a null array. */
+int vp_test_sun_start(int n, const float* origin_xyz, const float* sun_dir, const float* box, uint32_t* out_new, uint32_t* out_ref);
 int vp_test_rng(int mode, uint32_t x, uint32_t y, uint32_t frame, uint32_t k0, uint32_t k1, int n, float* out);
 int vp_test_sample_density(const float* pos_xyz, float* out, int n);
 /* component hooks for known-answer tests against float64 closed forms (no oracle involved):
