@@ -767,6 +767,15 @@ int vp_set_shard(int rank, int world)
     G.rank = (unsigned)rank; G.world = (unsigned)world;
     return VP_OK;
 }
+int vp_test_launch_census(int unit, int kind, uint32_t* launches, uint8_t* built, size_t count, int reset)
+{
+    const size_t n = census_size(kind);
+    if (unit < 0 || unit > 1 || !n) return fail(VP_E_ARG, "vp_test_launch_census: unknown unit %d (0 exact, 1 fast) or kind %d (0 render_k, 1 layers, 2 approach)", unit, kind);
+    if (!launches && !built) return (int)n;
+    if (count != n) return fail(VP_E_ARG, "vp_test_launch_census: %zu entries given, the table of kind %d has %zu", count, kind, n);
+    census_read(unit, kind, launches, built, n, reset != 0);   // (host memory only: no device, no context)
+    return VP_OK;
+}
 int vp_test_math(int which, const float* in, float* out, int n)
 {
     if (which < 0 || which > 11) return fail(VP_E_ARG, "vp_test_math: unknown helper %d (0..11)", which);

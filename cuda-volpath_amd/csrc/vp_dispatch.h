@@ -14,7 +14,8 @@
 //   launch_layers_instance()  the same for a layers launch (LaunchDev::layers): render_k's twelfth argument, LYR, for the subset
 //                      layers_built() states -- only where the kernels above have that argument (VP_RENDER_K_HAS_LAYERS)
 // and the same, smaller, for the approach walk (approach_built(), launch_approach_walk()).  dispatch_render(), dispatch_light() and
-// dispatch_approach() are what the launch_* functions of vp_kernels.h call.
+// dispatch_approach() are what the launch_* functions of vp_kernels.h call.  Each launcher counts the launch under its table index
+// (census_record(), vp_kernels.h: the launch census, a test hook) just before it calls through the table.
 
 // ---- the build
 #ifdef VP_DEV_BUILD
@@ -168,6 +169,7 @@ static void launch_instance(const RenderInst& v, std::integer_sequence<unsigned,
     static constexpr RenderLaunchFn table[kRenderInsts] = {render_launcher<I>()...};
     const unsigned i = render_index(v);
     if (i >= kRenderInsts || !table[i]) kernel_not_built();
+    census_record(kFastArith, CENSUS_RENDER, i);
     table[i](S, L, blocks, st);
 }
 static void launch_instance(const RenderInst& v, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
@@ -203,6 +205,7 @@ static void launch_layers_instance(const RenderInst& v, std::integer_sequence<un
     static constexpr RenderLaunchFn table[kRenderInsts] = {layers_launcher<I>()...};
     const unsigned i = render_index(v);
     if (i >= kRenderInsts || !table[i]) kernel_not_built();
+    census_record(kFastArith, CENSUS_LAYERS, i);
     table[i](S, L, blocks, st);
 }
 #endif
@@ -280,10 +283,28 @@ static void launch_approach_walk(const SceneDev& S, const LaunchDev& L, int est,
     v.quant = quant || v.walk == WALK_GLOBAL;
     const unsigned i = approach_index(v);
     if (i >= kApproachInsts || !table[i]) kernel_not_built();
+    census_record(kFastArith, CENSUS_APPROACH, i);
     table[i](S, L, grid, st);
 }
 // what launch_approach / launch_approach_fast are
 static void dispatch_approach(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, hipStream_t st)
 {
     launch_approach_walk(S, L, est, rng, quant, st, std::make_integer_sequence<unsigned, kApproachInsts>{});
+}
+
+// ---- the launch census (vp_kernels.h census_record; include/volpath.h vp_test_launch_census): which of the table entries above hold
+// a kernel in this translation unit, evaluated at run time from the functions the tables are built from.  what census_built /
+// census_built_fast are
+static void dispatch_census_built(int kind, unsigned char* built, size_t count)
+{
+    for (size_t i = 0; i < count; i++)
+    {
+        bool b = false;
+        if (kind == CENSUS_RENDER) b = i < kRenderInsts && render_built(render_at((unsigned)i));
+#ifdef VP_RENDER_K_HAS_LAYERS
+        else if (kind == CENSUS_LAYERS) b = i < kRenderInsts && layers_built(render_at((unsigned)i));
+#endif
+        else if (kind == CENSUS_APPROACH) b = i < kApproachInsts && approach_built(approach_at((unsigned)i));
+        built[i] = b;
+    }
 }

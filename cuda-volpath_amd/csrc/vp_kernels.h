@@ -164,6 +164,18 @@ struct LaunchDev
 // render_k and the approach kernels: which instance a launch runs, and which of them a build compiles, is decided in vp_dispatch.h.
 // A request for an instance that the build lacks (the API refuses every such configuration first: vp_render.cpp check_render) ends here:
 [[noreturn]] void kernel_not_built();
+// The launch census (test hook: include/volpath.h vp_test_launch_census).  launch_instance(), launch_layers_instance() and
+// launch_approach_walk() of vp_dispatch.h call census_record() with the table index of the kernel they are about to name: one host
+// increment per launch, nothing on the device.  unit: 0 the exact translation unit, 1 the fast arithmetic's; kind: CENSUS_*.
+constexpr int CENSUS_RENDER = 0, CENSUS_LAYERS = 1, CENSUS_APPROACH = 2;
+void census_record(int unit, int kind, unsigned index);
+// the read side: the table length of a kind (0: no such kind); launches[i] = launches since the last reset, built[i] = 1 where the
+// unit compiles instance i (either array may be null; count = the table length); reset zeroes the counters after they are read
+size_t census_size(int kind);
+void census_read(int unit, int kind, unsigned* launches, unsigned char* built, size_t count, bool reset);
+// built[i] of one unit, from the constexpr functions of vp_dispatch.h as that unit compiled them (vp_kernels.hip / vp_kernels_fast.hip)
+void census_built(int kind, unsigned char* built, size_t count);
+void census_built_fast(int kind, unsigned char* built, size_t count);
 // lds_form: how the decomposition estimator reads its brick table -- 0 global memory, 1 the 16-bit table through LDS (512-thread
 // workgroups), 2 2-bit codes into a four-entry palette through LDS (LaunchDev::bound_codes; 256-thread workgroups, plain occupancy)
 // half (with quant = false): binary16 cells (SceneDev::cells_f16); everything else of such a volume is the float volume's

@@ -28,7 +28,9 @@
 // arithmetic mode (VP_ARITH_FAST); everything else here is shared by both modes.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
@@ -1226,6 +1228,34 @@ __global__ void test_density_k(SceneDev S, const float* pos, float* out, int n)
     fprintf(stderr, "volpath_hip: this kernel variant is not compiled (development build, fast arithmetic mode, or a configuration the API refuses)\n");
     abort();
 }
+// the launch census (vp_kernels.h): process-wide host counters, one per table entry of vp_dispatch.h, per unit and kind
+static std::atomic<uint32_t> g_census_render[2][2][kRenderInsts];   // [unit][CENSUS_RENDER / CENSUS_LAYERS]
+static std::atomic<uint32_t> g_census_approach[2][kApproachInsts];  // [unit]
+static std::atomic<uint32_t>* census_counters(int unit, int kind)
+{
+    if (unit < 0 || unit > 1) return nullptr;
+    if (kind == CENSUS_RENDER || kind == CENSUS_LAYERS) return g_census_render[unit][kind];
+    return kind == CENSUS_APPROACH ? g_census_approach[unit] : nullptr;
+}
+size_t census_size(int kind) { return kind == CENSUS_RENDER || kind == CENSUS_LAYERS ? kRenderInsts : kind == CENSUS_APPROACH ? kApproachInsts : 0; }
+void census_record(int unit, int kind, unsigned index)
+{
+    std::atomic<uint32_t>* c = census_counters(unit, kind);
+    if (c && index < census_size(kind)) c[index].fetch_add(1u, std::memory_order_relaxed);
+}
+void census_read(int unit, int kind, unsigned* launches, unsigned char* built, size_t count, bool reset)
+{
+    std::atomic<uint32_t>* c = census_counters(unit, kind);
+    if (!c) return;
+    if (count > census_size(kind)) count = census_size(kind);
+    if (built) { if (unit) census_built_fast(kind, built, count); else census_built(kind, built, count); }
+    for (size_t i = 0; i < count; i++)
+    {
+        const uint32_t n = reset ? c[i].exchange(0u, std::memory_order_relaxed) : c[i].load(std::memory_order_relaxed);
+        if (launches) launches[i] = n;
+    }
+}
+void census_built(int kind, unsigned char* built, size_t count) { dispatch_census_built(kind, built, count); }
 void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
                    int blocks, hipStream_t st)
 {

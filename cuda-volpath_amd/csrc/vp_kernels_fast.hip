@@ -54,6 +54,7 @@ void launch_light_identity_fast(const ParamDev& P, bool local, const unsigned* m
 }
 
 void launch_approach_fast(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, hipStream_t st) { fast::dispatch_approach(S, L, est, rng, quant, st); }
+void census_built_fast(int kind, unsigned char* built, size_t count) { fast::dispatch_census_built(kind, built, count); }
 
 // the test hooks in this arithmetic (vp_test_kernels.h; vp_context.cpp vp_test_math / vp_test_hg in a fast context)
 void launch_test_hg_fast(const float* g, const float* r0, const float* r1, const float* nrm, const float* cosq, float* dir, float* ev, int n, hipStream_t st)

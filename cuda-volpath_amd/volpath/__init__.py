@@ -34,7 +34,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
                  "vp_render_frames_layers", "vp_composite",
-                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_intersect_box",
+                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
                  "vp_upload", "vp_download"]
@@ -158,6 +158,7 @@ def lib():
         L.vp_test_log_forms.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.vp_test_approach_walk.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.vp_test_sun_start.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_test_launch_census.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.vp_test_rng.argtypes = [C.c_int] + [C.c_uint32] * 5 + [C.c_int, C.c_void_p]
         L.vp_test_sample_density.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.vp_test_hg.argtypes = [C.c_void_p] * 7 + [C.c_int]
@@ -692,6 +693,39 @@ def test_sun_start(origins, sun_dir, box):
     new, ref = np.zeros((n, 8), np.uint32), np.zeros((n, 8), np.uint32)
     _chk(lib().vp_test_sun_start(n, _p(origins), _p(sun_dir), _p(box), _p(new), _p(ref)))
     return new, ref
+
+
+CENSUS_EXACT, CENSUS_FAST = 0, 1                         # vp_test_launch_census: unit ...
+CENSUS_RENDER, CENSUS_LAYERS, CENSUS_APPROACH = 0, 1, 2    # ... and kind
+
+
+def census_name(kind, index):
+    """the name of table entry `index` (include/volpath.h vp_test_launch_census) as tests/golden/render_variants.txt spells it:
+    render_k's template arguments as digits, EST RNG . QUANT COUNT LDSB ACH MIS . TRK LIGHT CANCEL HALF; approach_k<RNG> gR,
+    approach_local_k<RNG, QUANT> lRQ, approach_local_tab_k<RNG> tR"""
+    i = int(index)
+    if kind == CENSUS_APPROACH:
+        i, quant = divmod(i, 2)
+        walk, rng = divmod(i, 3)
+        return f"g{rng}" if walk == 0 else f"t{rng}" if walk == 2 else f"l{rng}{quant}"
+    d = []
+    for radix in (2, 2, 2, 3, 2, 2, 3, 2, 2, 3):     # HALF CANCEL LIGHT TRK MIS ACH LDSB COUNT QUANT RNG, the least significant first
+        i, r = divmod(i, radix)
+        d.append(r)
+    half, cancel, light, trk, mis, ach, ldsb, count, quant, rng = d
+    return f"{i}{rng}.{quant}{count}{ldsb}{ach}{mis}.{trk}{light}{cancel}{half}"
+
+
+def launch_census(unit, kind, reset=False):
+    """{name: launches since the last reset} for every kernel that translation unit `unit` (CENSUS_EXACT / CENSUS_FAST) compiles of
+    `kind` (CENSUS_RENDER, CENSUS_LAYERS: render_k of a layers launch, CENSUS_APPROACH), names as census_name spells them; process-wide,
+    needs no device (vp_test_launch_census)"""
+    n = lib().vp_test_launch_census(unit, kind, None, None, 0, 0)
+    if n < 0:
+        _chk(n)
+    launches, built = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+    _chk(lib().vp_test_launch_census(unit, kind, _p(launches), _p(built), n, int(reset)))
+    return {census_name(kind, i): int(launches[i]) for i in np.flatnonzero(built)}
 
 
 def test_rng(mode, x, y, frame, n, key=(0, 0)):

@@ -526,6 +526,22 @@ int vp_test_approach_walk(int kind, int n, const float* params, const uint32_t* 
  * length and the factor were read, bits 1..3 = the slab reciprocal of x, y, z was read; 0 in out_ref).  The first seven words agree
  * bit for bit for every input.  VP_E_ARG, before the device is touched, for n < 0 or a null array. */
 int vp_test_sun_start(int n, const float* origin_xyz, const float* sun_dir, const float* box, uint32_t* out_new, uint32_t* out_ref);
+/* vp_test_launch_census: which render_k and approach kernels the library compiles, and how often each has been launched.  Every
+ * launch names its kernel through a table (csrc/vp_dispatch.h); the library counts the launches per table entry, in host memory,
+ * process-wide (all contexts and threads together).  unit: 0 the exact arithmetic's kernels, 1 the fast arithmetic's.  kind: 0
+ * render_k, 1 render_k of a layers launch (vp_render_frames_layers), 2 the approach walks.  With launches == NULL and built == NULL
+ * the call returns the table length: 10368 for kinds 0 and 1, 18 for kind 2.  Otherwise count must be that length, launches[i]
+ * (if given) receives the launches of entry i since the last reset, built[i] (if given) 1 where the unit compiles a kernel for
+ * entry i and 0 elsewhere, and reset != 0 zeroes the counters of this unit and kind after they are read.  Needs no device.
+ * The index of a render_k instance is mixed radix over its template arguments, the first the most significant:
+ *   i = (((((((((EST * 3 + RNG) * 2 + QUANT) * 2 + COUNT) * 3 + LDSB) * 2 + ACH) * 2 + MIS) * 3 + TRK) * 2 + LIGHT) * 2 + CANCEL) * 2 + HALF
+ * with EST the VP_EST_* value, RNG the VP_RNG_* value, QUANT a uchar volume (of a LIGHT instance: a uchar bound table), COUNT work
+ * counters, LDSB the brick table's LDS form (0 none, 1 byte pairs, 2 two-bit codes), ACH one-channel throughput, MIS active
+ * environment sampling, TRK 0 spectral / 1 scalar / 2 multi-channel tracking, LIGHT the light pixel class, CANCEL a look-ahead batch
+ * that can be stopped, HALF a binary16 volume.  An approach kernel's is (WALK * 3 + RNG) * 2 + QUANT with WALK 0 approach_k (global
+ * majorant), 1 approach_local_k, 2 approach_local_tab_k (the segment table's); QUANT is 1 for walks 0 and 2.
+ * VP_E_ARG for another unit or kind, or a count that is not the table length. */
+int vp_test_launch_census(int unit, int kind, uint32_t* launches, uint8_t* built, size_t count, int reset);
 int vp_test_rng(int mode, uint32_t x, uint32_t y, uint32_t frame, uint32_t k0, uint32_t k1, int n, float* out);
 int vp_test_sample_density(const float* pos_xyz, float* out, int n);
 /* component hooks for known-answer tests against float64 closed forms (no oracle involved):

@@ -88,11 +88,17 @@ def _context(vp, seed, monkeypatch):
     return ctx
 
 
+def _fast_census(vp):
+    """launches so far of the fast unit's render_k and approach kernels, by name (the launch census; read, never reset)"""
+    return {**vp.launch_census(vp.CENSUS_FAST, vp.CENSUS_RENDER), **vp.launch_census(vp.CENSUS_FAST, vp.CENSUS_APPROACH)}
+
+
 def _tolerance_zero(vp, seed, c, what):
     """check 1 in the context at hand (fast): returns the image and what the launch ran"""
     P = _setup(vp, c)
     first, n = c["first"], c["nframes"]
     vp.set_arithmetic(vp.ARITH_FAST)
+    before = _fast_census(vp)
     one = _render(vp, P, first, n)
     ran = dict(lds_form=vp.last_lds_form(), table=vp.last_approach_table(), approach=vp.last_approach_mode(),
                dtype=str(c["grid"].dtype), chromatic="sigma_t" in c["kw"], inside=_camera_inside(c), est=c["est"], frames=n)
@@ -122,7 +128,26 @@ def _tolerance_zero(vp, seed, c, what):
         vp.set_lookahead(vp.LOOKAHEAD_DEFAULT)
         vp.set_shard(0, 1)
         buf.free()
+    ran["kernels"] = {k for k, v in _fast_census(vp).items() if v > before[k]}
     return one, P, ran
+
+
+def assert_paired_agreement(d, e, what):
+    """check 3 (the bound: test_fast_random_scene's docstring) on d, e = (frames, H, W, 3) float64 one-frame renders of the same
+    samples in the fast and in the exact arithmetic; d is overwritten with the differences"""
+    frames, H, W = d.shape[:3]
+    assert np.isfinite(d).all() and (d >= 0).all(), what
+    d -= e
+    n = frames * H * W
+    mean, se = d.mean((0, 1, 2)), d.std((0, 1, 2)) / np.sqrt(n)
+    tol = 5 * se + 1e-5 * np.abs(e.mean((0, 1, 2)))
+    assert (np.abs(mean) <= tol).all(), (what, mean, se)
+    by, bx = H // 4, W // 4
+    if by and bx:
+        blk = d[:, :by * 4, :bx * 4].reshape(frames, by, 4, bx, 4, 3).transpose(1, 3, 5, 0, 2, 4).reshape(by, bx, 3, -1)
+        bm, bs = blk.mean(-1), blk.std(-1) / np.sqrt(blk.shape[-1])
+        out = np.abs(bm) > 5 * bs + 1e-5 * np.abs(e.mean())
+        assert out.mean() < 0.01, (what, float(out.mean()))
 
 
 @pytest.mark.parametrize("seed", range(SEEDS))
@@ -165,18 +190,7 @@ def test_fast_random_scene(vp, seed, monkeypatch):
                         out[i] = buf.download()[..., :3]
             finally:
                 buf.free()
-            assert np.isfinite(d).all() and (d >= 0).all(), what
-            d -= e
-            n = d.shape[0] * H * W
-            mean, se = d.mean((0, 1, 2)), d.std((0, 1, 2)) / np.sqrt(n)
-            tol = 5 * se + 1e-5 * np.abs(e.mean((0, 1, 2)))
-            assert (np.abs(mean) <= tol).all(), (what, mean, se)
-            by, bx = H // 4, W // 4
-            if by and bx:
-                blk = d[:, :by * 4, :bx * 4].reshape(PAIRED_FRAMES, by, 4, bx, 4, 3).transpose(1, 3, 5, 0, 2, 4).reshape(by, bx, 3, -1)
-                bm, bs = blk.mean(-1), blk.std(-1) / np.sqrt(blk.shape[-1])
-                out = np.abs(bm) > 5 * bs + 1e-5 * np.abs(e.mean())
-                assert out.mean() < 0.01, (what, float(out.mean()))
+            assert_paired_agreement(d, e, what)
     finally:
         ctx.destroy()
 
@@ -205,6 +219,13 @@ def test_fast_fuzz_coverage(vp, monkeypatch):
     assert {True, False} <= have("chromatic")
     assert True in have("inside")
     assert any(r["frames"] >= 64 and r["est"] == 1 for r in seen)
+    # ... and what the launch census recorded while check 1 ran: render_k with every LDS form (the fifth digit), a look-ahead
+    # instance (CANCEL, the digit before the last), and the three kinds of approach walk
+    kernels = set().union(*(r["kernels"] for r in seen))
+    render = {k for k in kernels if "." in k}
+    assert {k[5] for k in render} == {"0", "1", "2"}, sorted(render)
+    assert any(k[-2] == "1" for k in render), sorted(render)
+    assert {k[0] for k in kernels - render} == {"g", "l", "t"}, sorted(kernels - render)
 
 
 @pytest.mark.parametrize("frames", [8, 64])
