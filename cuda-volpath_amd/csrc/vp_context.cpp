@@ -105,6 +105,7 @@ int ensure_device()
     if (knob("VP_NO_APPROACH", 0, 1, v)) G.use_approach = v == 0;
     if (knob("VP_NO_APPROACH_LOCAL", 0, 1, v)) G.use_approach_local = v == 0;
     if (knob("VP_NO_APPROACH_TABLE", 0, 1, v)) G.use_approach_table = v == 0;
+    if (knob("VP_NO_RAY_TABLE", 0, 1, v)) G.use_ray_table = v == 0;
     if (knob("VP_APPROACH_FRAMES_LOG2", 0, 6, v)) G.approach_fshift_max = (unsigned)v;
     if (knob("VP_APPROACH_STEPS", 0, 1 << 30, v)) G.approach_steps = (unsigned)v;
     if (knob("VP_NO_LIGHT", 0, 1, v)) G.use_light = v == 0;
@@ -577,7 +578,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
         for (hipEvent_t e : {D.pipe_done[0], D.pipe_done[1], D.pipe_free[0], D.pipe_free[1], D.pipe_gate[0], D.pipe_gate[1], D.pipe_fence_ev, D.last_end,
                              D.class_last_end[0], D.class_last_end[1], D.class_last_end[2]})
             if (e) (void)hipEventDestroy(e);
-        D.d_crawl.release(); D.d_seg.release(); D.d_sub_cls.release(); D.d_tiles.release(); D.d_act.release(); D.d_act_scratch.release();
+        D.d_crawl.release(); D.d_seg.release(); D.d_ray.release(); D.d_sub_cls.release(); D.d_tiles.release(); D.d_act.release(); D.d_act_scratch.release();
         for (void* q : {(void*)D.d_thr, (void*)D.d_sunclip, (void*)D.d_bound_codes, (void*)D.d_light_flag, (void*)D.d_tile_rows, (void*)D.d_tile_scratch})
             if (q) (void)hipFree(q);
         for (RenderTarget& t : D.target)
@@ -699,7 +700,7 @@ int vp_set_subpixel(int s)
     // staged and tables built under one factor are never used under another)
     if (la_quiesce()) return VP_E_NODEVICE;
     G.sub_shift = shift;
-    G.crawl_key.clear(); G.tiles_key.clear(); G.seg_key.clear();
+    G.crawl_key.clear(); G.tiles_key.clear(); G.seg_key.clear(); G.ray_key.clear();
     return VP_OK;
 }
 int vp_get_subpixel(void) { return 1 << G.sub_shift; }
@@ -968,6 +969,31 @@ int vp_test_intersect_box(const float* origin_xyz, const float* dir_xyz, int* hi
     HIPCHK(hipMemcpy(hit, dh, b, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(tnear, dtn, b, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(tfar, dtf, b, hipMemcpyDeviceToHost));
+    return VP_OK;
+}
+int vp_test_camera_ray(unsigned width, unsigned height, const uint32_t* pixels, float* out, int n)
+{
+    if (n < 0) return fail(VP_E_ARG, "vp_test_camera_ray: negative count %d", n);
+    if (!pixels || !out) return fail(VP_E_ARG, "vp_test_camera_ray: null argument");
+    if (!width || !height || width > 65536u || height > 65536u) return fail(VP_E_ARG, "vp_test_camera_ray: image %ux%u out of range", width, height);
+    for (int i = 0; i < n; i++)
+        if ((pixels[i] & 0xffffu) >= width || (pixels[i] >> 16) >= height)
+            return fail(VP_E_ARG, "vp_test_camera_ray: pixel %d (%u, %u) outside the %ux%u image", i, pixels[i] & 0xffffu, pixels[i] >> 16, width, height);
+    if (!G.have_volume || !G.have_cam) return fail(VP_E_STATE, "vp_test_camera_ray needs a volume (the box) and a camera");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (n == 0) return VP_OK;
+    DevArrays D;
+    const size_t c = (size_t)n;
+    unsigned* dp = (unsigned*)D.get(c * 4);
+    float*    dd = (float*)D.get(c * 24);
+    if (!dp || !dd) return fail(VP_E_NOMEM, "vp_test_camera_ray: no device memory");
+    HIPCHK(hipMemcpy(dp, pixels, c * 4, hipMemcpyHostToDevice));
+    if (G.arith == VP_ARITH_FAST) launch_test_camera_ray_fast(G.S, width, height, dp, dd, n, G.stream);
+    else launch_test_camera_ray(G.S, width, height, dp, dd, n, G.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(G.stream));
+    HIPCHK(hipMemcpy(out, dd, c * 24, hipMemcpyDeviceToHost));
     return VP_OK;
 }
 int vp_test_eval_envmap(const float* dir_xyz, float* rgb, int n)

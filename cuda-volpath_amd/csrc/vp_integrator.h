@@ -236,6 +236,7 @@ void render_k(SceneDev S, LaunchDev L)
     // VP_EXP_FLAT_KARGS: the flat loads, for the A/B (profiles/experiments/r05_kargs_lds.txt).
     constexpr unsigned KARG_L_   = ((sizeof(SceneDev) + alignof(LaunchDev) - 1) / alignof(LaunchDev)) * alignof(LaunchDev);
     constexpr unsigned KARG_WDS_ = (KARG_L_ + sizeof(LaunchDev) + 3) / 4;
+    constexpr unsigned KARG_ROW_ = (KARG_WDS_ + 3u) & ~3u;   // where the sun row starts behind the copy: 16-byte aligned whatever the structs' size (its fill stores four words at a time)
     constexpr bool LOCAL = EST != EST_GLOBAL;  // the two local-majorant estimators share the segment logic
     constexpr bool TAB   = TRK == 0 && LDSB != 1 && !LIGHT && !MIS;   // the instances with the collision block's tables, below
     // SUNROW: the sun ray's row (vp_device.h sun_row_fill) lies behind the copy, so that the event section's opaque offset reaches it
@@ -248,7 +249,7 @@ void render_k(SceneDev S, LaunchDev L)
 #else
     constexpr bool SUNROW = TAB && EST != EST_BOUNDED;
 #endif
-    __shared__ __attribute__((aligned(16))) unsigned kargs_lds_[KARG_WDS_ + (SUNROW ? SR_WORDS : 0)];
+    __shared__ __attribute__((aligned(16))) unsigned kargs_lds_[KARG_ROW_ + (SUNROW ? SR_WORDS : 0)];
     {
         const unsigned* src = (const unsigned*)__builtin_amdgcn_kernarg_segment_ptr();
         for (unsigned w = threadIdx.x; w < KARG_WDS_; w += (LDSB == 1 ? VP_BLOCK_LDS : VP_BLOCK)) kargs_lds_[w] = src[w];
@@ -265,7 +266,7 @@ void render_k(SceneDev S, LaunchDev L)
     if (TAB && threadIdx.x < VP_COLL_ROWS)
         coll_row_fill(coll_tab_[threadIdx.x], (int)threadIdx.x, L.P.g, L.P.density, max3(f3{L.P.sigma_t[0], L.P.sigma_t[1], L.P.sigma_t[2]}), LOCAL);
     if (SUNROW && threadIdx.x == VP_COLL_ROWS)
-        sun_row_fill(reinterpret_cast<float*>(kargs_lds_ + KARG_WDS_), f3{S.sun_dir[0], S.sun_dir[1], S.sun_dir[2]});
+        sun_row_fill(reinterpret_cast<float*>(kargs_lds_ + KARG_ROW_), f3{S.sun_dir[0], S.sun_dir[1], S.sun_dir[2]});
     __syncthreads();
     auto coll_row = [&](int n) __attribute__((always_inline)) -> const float* {
         return TAB ? coll_tab_[n < 0 ? 0 : (n > VP_COLL_ROWS - 1 ? VP_COLL_ROWS - 1 : n)] : nullptr;
@@ -279,6 +280,10 @@ void render_k(SceneDev S, LaunchDev L)
     // Global majorant, counter-based streams: a new sample's camera ray may have been walked through its certified-empty stretch by
     // approach_k already (L.approach): the path is taken up where that walk stopped -- same draws, same sums, made elsewhere.
     constexpr bool APPR = EST == EST_GLOBAL && TRK == 0 && !LIGHT && !MIS;   // (any stream: the hand-over carries its state)
+    // Global majorant, general class: a fresh sample's camera ray and box test are functions of its pixel alone (quirk Q3; the box is the
+    // scene's) and come from the per-view ray table where the launch has one (L.ray, vp_kernels.hip ray_table_k); without, or with a
+    // sub-pixel factor, they are computed per sample as ever -- the same bits.
+    constexpr bool RAYT = EST == EST_GLOBAL && !LIGHT;
     // decomposition estimator: the same for the restart segments that end before the certified-empty distance (approach_local_k)
     constexpr bool APPR_L = EST == EST_DECOMP && TRK == 0 && !LIGHT && !MIS;
     // Exit flights.  A path in empty space that can do nothing but leave the box -- every cell its ray can still meet is certified
@@ -320,7 +325,7 @@ void render_k(SceneDev S, LaunchDev L)
     // DEFER: the light weight of the shadow ray in flight takes the place of `ph` (one word, achromatic) or that word and two more
     // (chromatic); one more word holds the ended ray's termination bits until the event pass has added its light
     constexpr int NCOLD = 14 + (DEFER ? (ACH ? 1 : 3) : 0);
-    static_assert(!COLD || (LOCAL ? VP_LOCAL_MIN_WAVES : VP_GLOBAL_MIN_WAVES) * (NCOLD * VP_BLOCK * 4 + KARG_WDS_ * 4 + VP_COLL_ROWS * CR_WORDS * 4 + (SUNROW ? SR_WORDS * 4 : 0) + (LDSB == 2 ? VP_LDS_BOUND_ENTRIES / 4 : 0)) <= VP_LDS_BYTES_PER_CU,
+    static_assert(!COLD || (LOCAL ? VP_LOCAL_MIN_WAVES : VP_GLOBAL_MIN_WAVES) * (NCOLD * VP_BLOCK * 4 + KARG_ROW_ * 4 + VP_COLL_ROWS * CR_WORDS * 4 + (SUNROW ? SR_WORDS * 4 : 0) + (LDSB == 2 ? VP_LDS_BOUND_ENTRIES / 4 : 0)) <= VP_LDS_BYTES_PER_CU,
                   "cold per-path state: more workgroups per CU than the LDS holds -- lower VP_*_MIN_WAVES for this ARCH");
     __shared__ float cold_[COLD ? NCOLD : 1][CS_];
     float* const cold_p = &cold_[0][COLD ? threadIdx.x : 0];
@@ -441,9 +446,9 @@ void render_k(SceneDev S, LaunchDev L)
                 // the sun ray, with the row of its constants: the same values, the roots and divisions taken only where a wave's
                 // operands differ in a bit from the row's (`end` is the row's first three words)
 #ifdef VP_EXP_FLAT_KARGS
-                const float* const srow = reinterpret_cast<const float*>(kargs_lds_ + KARG_WDS_);
+                const float* const srow = reinterpret_cast<const float*>(kargs_lds_ + KARG_ROW_);
 #else
-                const float* const srow = reinterpret_cast<const float*>(kargs_ + KARG_WDS_ * 4u);
+                const float* const srow = reinterpret_cast<const float*>(kargs_ + KARG_ROW_ * 4u);
 #endif
                 hitv = sun_start(srow, ro, S.bmin, S.bmax, sd, len, tn, tf);
             }
@@ -808,6 +813,10 @@ void render_k(SceneDev S, LaunchDev L)
             vp_pad<VP_PAD_END>();
             bool fresh = false;   // APPR: this lane took a new sample in this round, `dist` holds where approach_k left its camera ray
             bool trans = false;   // layers launch (LaunchDev::layers): the path that ends in this round is unscattered -- its sample is its throughput
+            // RAYT: this lane took a new sample in this round and read its camera ray and box test from the per-pixel table (L.ray:
+            // ray_table_k, the bits camera_ray() and intersect_box() compute): the set-up below takes t_near and t_far from there
+            bool  tabfed = false;
+            float tab_near = 0.0f, tab_far = 0.0f;
             // order: a path that ends here is written, its lane refilled and the new segment set up in ONE round
             // ---- ray left the medium: background() kernel.cu:1258-1267 (quirk Q11)
             tally(B_BG, st == EV_BG);
@@ -944,6 +953,7 @@ void render_k(SceneDev S, LaunchDev L)
                                     return (size_t)px + (size_t)py * P.width;
                                 };
                                 // camera ray, kernel.cu:1977-1987 (quirk Q3: the same ray in every frame unless a sub-pixel factor is set)
+                                float tab_te = 0.0f;
                                 if (!COUNT && L.sub_shift)
                                 {
                                     unsigned si, sj;
@@ -955,7 +965,20 @@ void render_k(SceneDev S, LaunchDev L)
                                 else
                                 {
                                     rng.init(px, py, (unsigned)frame, L.key0, L.key1);
-                                    camera_ray(S, P.width, P.height, px, py, ro, rd);
+                                    const float4* const ray = RAYT ? L.ray : nullptr;
+                                    if (RAYT && ray)
+                                    {
+                                        // the pixel's entries (slot order, as `pixels`): two divisions, a root and nine multiply-adds of
+                                        // camera_ray(), and the box test of the set-up below, done once per view instead of per sample
+                                        const float4 e0 = ray[2 * (size_t)rem], e1 = ray[2 * (size_t)rem + 1];
+                                        ro       = f3{S.cam[3], S.cam[7], S.cam[11]};
+                                        rd       = f3{e0.x, e0.y, e0.z};
+                                        tab_near = e0.w;
+                                        tab_far  = e1.x;
+                                        tab_te   = e1.y;
+                                        tabfed   = true;
+                                    }
+                                    else camera_ray(S, P.width, P.height, px, py, ro, rd);
                                 }
                                 if (TRK == 2)
                                 {
@@ -969,7 +992,8 @@ void render_k(SceneDev S, LaunchDev L)
                                 seg = 0;
                                 if (EXITC) terms = L.exit_start;
                                 if (COUNT) ex_clear = false;
-                                if (!LIGHT) t_empty = L.crawl ? L.crawl[2 * table_index() + 1].x : 0.0f;
+                                if (RAYT && tabfed) t_empty = tab_te;
+                                else if (!LIGHT) t_empty = L.crawl ? L.crawl[2 * table_index() + 1].x : 0.0f;
                                 if (LOCAL) dist = -1.0f;   // a segment starts where the ray enters it (segment_setup), unless approach_local_k got further
                                 if (APPR && L.approach)
                                 {
@@ -1035,8 +1059,13 @@ void render_k(SceneDev S, LaunchDev L)
             if (EST == EST_GLOBAL) tally(B_GSETUP, st == ST_SETUP);
             if (EST == EST_GLOBAL && st == ST_SETUP)
             {
+                // (a lane fresh from the ray table: the raw outputs of the same call, and its two compares; the others -- no table, or
+                // the non-EARLY instances' next_segment() -- compute it.  A branch, not a select: a round whose set-up lanes are all
+                // table-fed skips the box test with an empty exec mask)
                 float t_near, tf;
-                bool  hit = intersect_box(ro, rd, S, t_near, tf);
+                bool  hit;
+                if (RAYT && tabfed) { t_near = tab_near; tf = tab_far; hit = tf > t_near && tf >= 1e-3f; }
+                else hit = intersect_box(ro, rd, S, t_near, tf);
                 if (!hit) st = EV_BG;
                 else
                 {

@@ -159,6 +159,12 @@ struct LaunchDev
     // -0.0f included, marks it (the light kernel, whose every sample is one, stages heat as it is) -- and reduce_layers_k splits the
     // staged samples into the two accumulators.  0: the beauty sample, as ever.
     unsigned layers;
+    // Global-majorant estimator, general class (appended like the fields above): per pixel slot of the class what a fresh sample's
+    // set-up computes from the pixel alone (ray_table_k: two float4 per slot, sliced like `pixels`) -- [0] = (rd.x, rd.y, rd.z, t_near),
+    // [1] = (t_far, t_empty, 0, 0): camera_ray()'s direction, intersect_box()'s raw outputs for it and the crawl table's [1].x.  The hit
+    // flag is not stored: t_far > t_near && t_far >= 1e-3f.  Null (no memory, a sub-pixel factor, a caller's own lists, the light
+    // class, VP_NO_RAY_TABLE=1): render_k computes them per sample, same bits.
+    const float4* ray;
 };
 
 // render_k and the approach kernels: which instance a launch runs, and which of them a build compiles, is decided in vp_dispatch.h.
@@ -196,6 +202,9 @@ void launch_approach_fast(const SceneDev& S, const LaunchDev& L, int est, int rn
 unsigned segment_table_records(void);
 void launch_segment_table(const SceneDev& S, unsigned width, unsigned height, const float4* crawl, const unsigned* pixels, unsigned nslots, float4* seg,
                           hipStream_t st);
+// the per-pixel ray table of the global-majorant integrator (ray_table_k; LaunchDev::ray): two float4 per slot of `pixels`; crawl may be null (t_empty = 0)
+void launch_ray_table(const SceneDev& S, unsigned width, unsigned height, const float4* crawl, const unsigned* pixels, unsigned nslots, float4* table,
+                      hipStream_t st);
 // throughput of an unscattered global-majorant path after n null collisions with density +0, n = 0..count-1 (thr_table_k)
 void launch_thr_table(const ParamDev& P, float* table, unsigned count, hipStream_t st);
 // mask[8]: the bytes that occur as a maximum in a uchar bound table; flag[0] (preset to 1) is cleared unless a null collision in
@@ -268,6 +277,9 @@ void launch_accumulate(float4* dst, const float4* src, size_t n, hipStream_t st)
 void launch_test_hg(const float* g, const float* r0, const float* r1, const float* nrm, const float* cosq, float* dir, float* ev, int n, hipStream_t st);
 void launch_test_box(const SceneDev& S, const float* o, const float* d, int* hit, float* tn, float* tf, int n, hipStream_t st);
 void launch_test_env(const SceneDev& S, const float* d, float* out, int n, hipStream_t st);
+// vp_test_camera_ray (vp_test_kernels.h test_camera_ray_k): camera_ray() of n pixels (y << 16 | x) as each unit compiles it
+void launch_test_camera_ray(const SceneDev& S, unsigned width, unsigned height, const unsigned* pixels, float* dir, int n, hipStream_t st);
+void launch_test_camera_ray_fast(const SceneDev& S, unsigned width, unsigned height, const unsigned* pixels, float* dir, int n, hipStream_t st);
 void launch_test_math(int which, const float* in, float* out, int n, hipStream_t st);
 void launch_test_roots(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad, hipStream_t st);   // (exact arithmetic only)
 // the same two hooks compiled in the fast arithmetic (vp_kernels_fast.hip)

@@ -794,6 +794,26 @@ __global__ __launch_bounds__(256) void approach_segments_k(SceneDev S, unsigned 
     }
 }
 
+// ray_table_k: what the set-up of a fresh sample of the global-majorant integrator computes from its pixel alone (quirk Q3: the same
+// camera ray in every frame; the box is the scene's), once per slot of the general pixel list -- camera_ray()'s direction, the raw
+// outputs of intersect_box() for it, and the crawl table's certified-empty distance (layout: vp_kernels.h LaunchDev::ray).  The very
+// functions render_k would call, so the table holds their bits; a slot of a partial edge tile outside the image is never read.
+__global__ __launch_bounds__(256) void ray_table_k(SceneDev S, unsigned width, unsigned height, const float4* crawl, const unsigned* pixels, unsigned nslots,
+                                                   float4* table)
+{
+    const unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= nslots) return;
+    const unsigned pix = pixels[slot], px = pix & 0xffffu, py = pix >> 16;
+    if (px >= width || py >= height) { table[2 * (size_t)slot] = table[2 * (size_t)slot + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); return; }
+    f3 ro, rd;
+    camera_ray(S, width, height, px, py, ro, rd);
+    float t_near, tf;
+    (void)intersect_box(ro, rd, S, t_near, tf);
+    const float t_empty = crawl ? crawl[2 * ((size_t)px + (size_t)py * width) + 1].x : 0.0f;
+    table[2 * (size_t)slot]     = make_float4(rd.x, rd.y, rd.z, t_near);
+    table[2 * (size_t)slot + 1] = make_float4(tf, t_empty, 0.0f, 0.0f);
+}
+
 // expand a dense volume into per-voxel 2x2x2 neighbourhood cells (clamped at the border)
 __device__ __forceinline__ size_t pack_index(int nx, int ny, int i, int j, int k, int bricks)
 {
@@ -1294,6 +1314,11 @@ void launch_segment_table(const SceneDev& S, unsigned width, unsigned height, co
 {
     hipLaunchKernelGGL(approach_segments_k, dim3((nslots + 255u) / 256u), dim3(256), 0, st, S, width, height, crawl, pixels, nslots, seg);
 }
+void launch_ray_table(const SceneDev& S, unsigned width, unsigned height, const float4* crawl, const unsigned* pixels, unsigned nslots, float4* table,
+                      hipStream_t st)
+{
+    hipLaunchKernelGGL(ray_table_k, dim3((nslots + 255u) / 256u), dim3(256), 0, st, S, width, height, crawl, pixels, nslots, table);
+}
 void launch_pixel_lists(unsigned width, unsigned height, unsigned rank, unsigned world, unsigned ntiles, const unsigned* d_row_start,
                         const float4* table, const unsigned char* cls, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st)
 {
@@ -1554,6 +1579,10 @@ void launch_test_approach_walk(int kind, int n, const float* par, const unsigned
 void launch_test_sun_start(int n, const float* origin, const float* sun_dir, const float* box, unsigned* out_new, unsigned* out_ref, hipStream_t st)
 {
     hipLaunchKernelGGL(test_sun_start_k, dim3((n + 255) / 256), dim3(256), 0, st, n, origin, sun_dir[0], sun_dir[1], sun_dir[2], box, out_new, out_ref);
+}
+void launch_test_camera_ray(const SceneDev& S, unsigned width, unsigned height, const unsigned* pixels, float* dir, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(test_camera_ray_k, dim3((n + 255) / 256), dim3(256), 0, st, S, width, height, pixels, dir, n);
 }
 void launch_test_rng(int mode, unsigned x, unsigned y, unsigned f, unsigned k0, unsigned k1, int n, float* out, hipStream_t st)
 {

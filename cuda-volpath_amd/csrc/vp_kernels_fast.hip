@@ -74,6 +74,10 @@ void launch_test_approach_walk_fast(int kind, int n, const float* par, const uns
 {
     hipLaunchKernelGGL(fast::test_approach_walk_k, dim3((n + 63) / 64), dim3(64), 0, st, kind, n, par, scr, words, out_new, out_ref);
 }
+void launch_test_camera_ray_fast(const SceneDev& S, unsigned width, unsigned height, const unsigned* pixels, float* dir, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(fast::test_camera_ray_k, dim3((n + 255) / 256), dim3(256), 0, st, S, width, height, pixels, dir, n);
+}
 void launch_test_sun_start_fast(int n, const float* origin, const float* sun_dir, const float* box, unsigned* out_new, unsigned* out_ref, hipStream_t st)
 {
     hipLaunchKernelGGL(fast::test_sun_start_k, dim3((n + 255) / 256), dim3(256), 0, st, n, origin, sun_dir[0], sun_dir[1], sun_dir[2], box, out_new, out_ref);

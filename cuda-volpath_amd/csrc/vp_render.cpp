@@ -229,6 +229,7 @@ struct LaunchPlan
     // is not written as constants), i.e. where the per-pixel constants of a launch begin -- const_from and the layers reduce's range
     unsigned integrated_end() const { return PL.n_general + ((PL.n_light && !light_const) ? PL.n_light : 0u); }
     PixelLists PL;                // the lists in use: the context's cached ones, or the caller's
+    const float4* ray;            // the ray table of the general class (global majorant, the cached lists), or null
     size_t     per_frame;         // ... and their pixels = samples per frame
     bool       staged;            // samples go through the staging buffer and a reduce (false: render_k accumulates one frame directly)
     bool       light_const;       // the light class is written by miss_fill_k
@@ -253,6 +254,11 @@ static int prepare_tables(const Param* p, const Shard& sh, int nframes, const Pi
     const PixelLists& PL = A.PL = lists ? *lists : PixelLists{G.d_tiles, G.n_general, G.n_light, G.n_miss};
     A.per_frame = (size_t)PL.n_general + PL.n_light + PL.n_miss;
     if (A.per_frame == 0) return VP_OK;
+    // (global majorant: the general pixels' camera rays and box tests, tabulated per view in the order of the cached lists -- a caller's
+    // own lists are a subset of them in another order and go without)
+    A.ray = nullptr;
+    if (!lists && (rc = ensure_ray_table(p, L.crawl, &A.ray))) return rc;
+    G.last_ray_table = 0;
     if ((rc = ensure_sun_clip(&L.sun_clip, &L.clip_ds))) return rc;
     L.count_clips = getenv("VP_DEBUG_COUNT_CLIPS") ? 1u : 0u;
     if ((rc = exit_flights(L))) return rc;
@@ -422,6 +428,7 @@ static void select_class(const LaunchPlan& A, LaunchDev& L, int cls, int f)
 {
     const unsigned nt = cls ? A.PL.n_light : A.PL.n_general;
     L.pixels      = A.PL.pixels + (cls ? A.PL.n_general : 0);
+    L.ray         = cls ? nullptr : A.ray;   // (sliced like `pixels`: the table holds the general class, which comes first)
     L.nslots      = nt;
     L.slot_base   = cls ? A.PL.n_general : 0u;
     L.total_items = (unsigned)((size_t)nt * (size_t)f);
@@ -467,6 +474,7 @@ static hipError_t launch_general_class(Launch& X, const ClassGrid& g)
     {
         X.k.render(X.S, L, G.est, G.rng, G.quant, G.half(), G.count, X.lds_form, G.env_mis, G.trk, (int)g.blocks, T.stream);
         le = hipGetLastError();
+        G.last_ray_table = L.ray ? 1 : 0;
     }
     // The LDS-table kernel holds 2 x 64 KiB of a CU's LDS with 2 x 512 threads: four waves per SIMD, where the
     // registers would allow five.  The fifth comes from the SAME kernel without the LDS stage (the brick table read
@@ -837,6 +845,8 @@ int vp_prepare(const Param* p)
     const Param fine = subpixel_param(p);
     if ((rc = ensure_crawl_table(&fine, &table))) return rc;
     if ((rc = ensure_pixel_lists(p, table, sh))) return rc;
+    const float4* ray = nullptr;
+    if ((rc = ensure_ray_table(p, table, &ray))) return rc;
     if (G.have_sun && (rc = ensure_sun_clip(&sc, &ds))) return rc;
     if (G.est == VP_EST_GLOBAL && G.n_light && (rc = ensure_thr_table(p, &thr))) return rc;
     if ((rc = prepare_segment_table(p, table, &seg))) return rc;
@@ -860,6 +870,23 @@ int vp_get_segment_table(const Param* p, float* dst, size_t count, int* cap)
     HIPCHK(hipMemcpy(dst, seg, need * sizeof(float), hipMemcpyDeviceToHost));
     return VP_OK;
 }
+int vp_get_ray_table(const Param* p, float* dst, size_t count)
+{
+    if (!p || !dst) return fail(VP_E_ARG, "vp_get_ray_table: null argument");
+    int rc = vp_prepare(p);
+    if (rc) return rc;
+    // what vp_prepare has just built, if this configuration has a table at all (both tables are found cached)
+    const float4 *table = nullptr, *ray = nullptr;
+    const Param fine = subpixel_param(p);
+    if ((rc = ensure_crawl_table(&fine, &table))) return rc;
+    if ((rc = ensure_ray_table(p, table, &ray))) return rc;
+    if (!ray) return fail(VP_E_STATE, "no ray table in this configuration (global-majorant estimator, no sub-pixel factor, general pixels, the table switched on)");
+    const size_t need = (size_t)G.n_general * 8;
+    if (count < need) return fail(VP_E_ARG, "ray table needs %zu floats", need);
+    HIPCHK(hipMemcpy(dst, ray, need * sizeof(float), hipMemcpyDeviceToHost));
+    return VP_OK;
+}
+int vp_last_ray_table(void) { return G.last_ray_table; }
 int vp_reserve_frames(const Param* p, int nframes)
 {
     int rc = ensure_device();

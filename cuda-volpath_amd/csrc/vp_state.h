@@ -248,6 +248,12 @@ struct State
     bool        use_approach_table = true;    // ... with the restart segments of a pixel's camera ray tabulated per pixel (VP_NO_APPROACH_TABLE=1: set up per sample)
     DevBuf<float4> d_seg;                     // the table (approach_segments_k) and what it was built for
     std::vector<unsigned char> seg_key;
+    // global-majorant estimator: camera-ray direction, box test and certified-empty distance of every general pixel, in list order
+    // (ray_table_k; LaunchDev::ray); keyed on the camera, the box, the crawl table and the pixel lists (image size, rank, world)
+    bool        use_ray_table = true;         // VP_NO_RAY_TABLE=1: render_k computes them per sample, same bits
+    DevBuf<float4> d_ray;
+    std::vector<unsigned char> ray_key;
+    int         last_ray_table = 0;           // vp_last_ray_table
     bool        use_approach_local = true;    // ... and approach_local_k ahead of the decomposition estimator (VP_NO_APPROACH_LOCAL=1: off)
     bool        use_approach = true;          // approach_k ahead of the global-majorant integrator (VP_NO_APPROACH=1: off)
     unsigned    approach_fshift_max = 6;      // a wave of the approach kernels = one pixel x 2^6 frames (VP_APPROACH_FRAMES_LOG2: 0 = 64 pixels of one frame)
@@ -342,6 +348,7 @@ int    exit_flights(LaunchDev& L);
 int    ensure_thr_table(const Param* p, const float** out);
 int    ensure_pixel_lists(const Param* p, const float4* table, const Shard& sh);
 int    ensure_segment_table(const Param* p, const float4* crawl, const float4** out);
+int    ensure_ray_table(const Param* p, const float4* crawl, const float4** out);
 // ---- vp_render.cpp
 // where a launch runs and stages its samples: one of G.target and the stream that serves it (the caller's, a look-ahead slot's, a pipeline slot's)
 struct Target { RenderTarget* rt; hipStream_t stream; };

@@ -379,6 +379,38 @@ int ensure_segment_table(const Param* p, const float4* crawl, const float4** out
     *out = G.d_seg;
     return VP_OK;
 }
+// The ray table of the global-majorant integrator (vp_kernels.hip ray_table_k; LaunchDev::ray): per slot of the general pixel list the
+// camera ray's direction, its box test and its certified-empty distance -- what render_k otherwise computes for every fresh sample.
+// Depends on the camera, the box and the image size, on the crawl table (`crawl`: the table the launch reads, or null) and on the pixel
+// list (rank, world, classes); rebuilt with any of them, behind the pixel lists.  Not with a sub-pixel factor (the ray depends on the
+// frame).  Best effort: without it render_k computes the values as before.
+int ensure_ray_table(const Param* p, const float4* crawl, const float4** out)
+{
+    *out = nullptr;
+    if (!G.use_ray_table || G.est != VP_EST_GLOBAL || G.sub_shift || !G.n_general || !G.d_tiles) return VP_OK;
+    struct K { float cam[12], cam_z, bmin[3], bmax[3]; unsigned w, h, rank, world, n_general; int crawl; };
+    std::vector<unsigned char> key(sizeof(K), 0);
+    K* k = reinterpret_cast<K*>(key.data());
+    memcpy(k->cam, G.S.cam, sizeof k->cam); k->cam_z = G.S.cam_z;
+    memcpy(k->bmin, G.S.bmin, sizeof k->bmin); memcpy(k->bmax, G.S.bmax, sizeof k->bmax);
+    k->w = p->width; k->h = p->height; k->rank = G.rank; k->world = G.world; k->n_general = G.n_general; k->crawl = crawl ? 1 : 0;
+    if (crawl) key.insert(key.end(), G.crawl_key.begin(), G.crawl_key.end());   // (t_empty is the crawl table's word)
+    key.insert(key.end(), G.tiles_key.begin(), G.tiles_key.end());
+    const size_t need = (size_t)G.n_general * 2 * sizeof(float4);
+    if (key != G.ray_key || !G.d_ray)
+    {
+        if (la_quiesce()) return VP_E_NODEVICE;   // batches in flight read the old table
+        HIPCHK(hipStreamSynchronize(G.stream));
+        G.ray_key.clear();
+        if (G.d_ray.grow(need) != hipSuccess) return VP_OK;   // no table: every sample computes its ray and box test itself, same bits
+        launch_ray_table(G.S, p->width, p->height, crawl, G.d_tiles, G.n_general, G.d_ray, G.stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(G.stream));   // (launches on other streams read it)
+        G.ray_key = key;
+    }
+    *out = G.d_ray;
+    return VP_OK;
+}
 int ensure_pixel_lists(const Param* p, const float4* table, const Shard& sh)
 {
     const bool light = G.use_light && table && G.trk == VP_TRACK_SPECTRAL && !(G.est != VP_EST_GLOBAL && !G.use_light_local);

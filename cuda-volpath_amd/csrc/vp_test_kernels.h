@@ -1,5 +1,6 @@
 // vp_test_kernels.h -- the test hooks of the integrator's arithmetic: vp_test_math (test_math_k), vp_test_hg (test_hg_k),
-// vp_test_log_forms (test_log_forms_k), vp_test_approach_walk (test_approach_walk_k) and vp_test_sun_start (test_sun_start_k).
+// vp_test_log_forms (test_log_forms_k), vp_test_approach_walk (test_approach_walk_k), vp_test_sun_start (test_sun_start_k) and
+// vp_test_camera_ray (test_camera_ray_k).
 // Included INSIDE a namespace by both translation units, like vp_integrator.h: vp_kernels.hip (namespace vp, the exact helpers) and
 // vp_kernels_fast.hip (namespace vp::fast, VP_ARITH_FAST).  vp_context.cpp launches the pair of the context's arithmetic mode, so
 // the hooks test the helpers the context's renders run.
@@ -224,4 +225,20 @@ __global__ void test_sun_start_k(int n, const float* origin, float sun_x, float 
         unsigned* o = out_ref + 8 * (size_t)i;
         o[0] = f2u(sd.x); o[1] = f2u(sd.y); o[2] = f2u(sd.z); o[3] = f2u(len); o[4] = f2u(tn); o[5] = f2u(tf); o[6] = hit ? 1u : 0u; o[7] = 0u;
     }
+}
+
+// vp_test_camera_ray: camera_ray() of pixel (pixels[i] & 0xffff, pixels[i] >> 16) of a width x height image and intersect_box() of that
+// ray, as this unit compiles them -- what ray_table_k (vp_kernels.hip, the exact unit) tabulates for render_k in BOTH units.
+// out[6 i ..] = (rd.x, rd.y, rd.z, t_near, t_far, hit as 1.0f / 0.0f).
+__global__ void test_camera_ray_k(SceneDev S, unsigned width, unsigned height, const unsigned* pixels, float* out, int n)
+{
+    const int i = threadIdx.x + blockIdx.x * blockDim.x;
+    if (i >= n) return;
+    const unsigned pix = pixels[i];
+    f3 ro, rd;
+    camera_ray(S, width, height, pix & 0xffffu, pix >> 16, ro, rd);
+    float tn, tf;
+    const bool hit = intersect_box(ro, rd, S, tn, tf);
+    float* o = out + 6 * (size_t)i;
+    o[0] = rd.x; o[1] = rd.y; o[2] = rd.z; o[3] = tn; o[4] = tf; o[5] = hit ? 1.0f : 0.0f;
 }

@@ -30,11 +30,11 @@ PART1_SYMBOLS = ["init_cuda", "set_texture_filter_mode", "free_cuda_buffers", "p
                  "render_kernel", "scale", "gamma_correct"]
 PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_device", "vp_set_stream", "vp_get_stream", "vp_synchronize",
                  "vp_set_estimator", "vp_set_rng", "vp_set_envmap_sampling", "vp_get_env_tables", "vp_set_lookahead", "vp_set_tracking", "vp_set_bound_brick", "vp_set_shard", "vp_render_frames", "vp_init_volume", "vp_get_volume_info",
-                 "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists", "vp_get_segment_table",
+                 "vp_enable_counters", "vp_read_counters", "vp_render_time_ms", "vp_get_bound_table", "vp_get_opacity", "vp_get_pixel_table", "vp_get_null_collision_table", "vp_get_sun_clip_table", "vp_get_exit_table", "vp_set_exit_flights", "vp_render_class_time_ms", "vp_last_approach_mode", "vp_last_approach_table", "vp_last_light_const", "vp_last_lds_form", "vp_set_arithmetic", "vp_last_arithmetic", "vp_set_subpixel", "vp_get_subpixel", "vp_subpixel_offset", "vp_set_pipeline", "vp_last_pipelined", "vp_lookahead_stats", "vp_prepare", "vp_reserve_frames", "vp_get_pixel_lists", "vp_get_segment_table", "vp_get_ray_table", "vp_last_ray_table",
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
                  "vp_render_frames_layers", "vp_composite",
-                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box",
+                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
                  "vp_upload", "vp_download"]
@@ -151,6 +151,8 @@ def lib():
         L.vp_subpixel_offset.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.vp_get_pixel_lists.argtypes = [C.POINTER(Param), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
         L.vp_get_segment_table.argtypes = [C.POINTER(Param), C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+        L.vp_get_ray_table.argtypes = [C.POINTER(Param), C.c_void_p, C.c_size_t]
+        L.vp_test_camera_ray.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_int]
         L.vp_julia_voxelize.argtypes = [C.c_int, C.c_void_p]
         L.vp_cloud_voxelize.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
         L.vp_test_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
@@ -629,6 +631,21 @@ def segment_table(P):
     return out[:, 0], out[:, 1], cap.value
 
 
+def ray_table(P):
+    """float32 [n_general, 8]: the per-view ray table of the global-majorant integrator for the general pixels in the order of
+    pixel_lists(P)[0] -- (rd.x, rd.y, rd.z, t_near, t_far, t_empty, 0, 0) (include/volpath.h vp_get_ray_table).
+    Raises VolpathError where the configuration has no table."""
+    n = len(pixel_lists(P)[0])
+    out = np.empty((max(n, 1), 8), np.float32)
+    _chk(lib().vp_get_ray_table(C.byref(P), _p(out), n * 8))
+    return out[:n]
+
+
+def last_ray_table():
+    """1 if the last render launch of the general class read the ray table (vp_last_ray_table)"""
+    return int(lib().vp_last_ray_table())
+
+
 def null_collision_table(P, count):
     """float32[count]: throughput of an unscattered global-majorant path after n null collisions in empty space"""
     out = np.empty(count, np.float32)
@@ -761,6 +778,15 @@ def test_intersect_box(origin, direction):
     tf = np.empty(n, np.float32)
     _chk(lib().vp_test_intersect_box(_p(o), _p(d), _p(hit), _p(tn), _p(tf), n))
     return hit.astype(bool), tn, tf
+
+
+def test_camera_ray(width, height, pixels):
+    """(rd float32[n, 3], t_near, t_far, hit): camera_ray() and intersect_box() of the pixels (y << 16 | x) of a width x height image, in
+    the arithmetic unit of the current mode (include/volpath.h vp_test_camera_ray)"""
+    px = np.ascontiguousarray(pixels, np.uint32)
+    out = np.empty((px.shape[0], 6), np.float32)
+    _chk(lib().vp_test_camera_ray(width, height, _p(px), _p(out), px.shape[0]))
+    return out[:, :3].copy(), out[:, 3].copy(), out[:, 4].copy(), out[:, 5] != 0.0
 
 
 def test_eval_envmap(direction):

@@ -467,6 +467,19 @@ int vp_get_pixel_table(const Param* p, float* dst, size_t count);
  * VP_E_STATE where this configuration has no table: float and binary16 volumes, the other estimators, VP_NO_APPROACH_TABLE=1, or
  * no approach walk at all. */
 int vp_get_segment_table(const Param* p, float* dst, size_t count, int* cap);
+/* test hook: the per-view ray table of the global-majorant integrator (ray_table_k), built as vp_prepare builds it: what the set-up of
+ * a fresh sample computes from its pixel alone, read by render_k instead.  dst (count >= n_general * 8 floats) receives, for slot
+ * s = 0 .. n_general - 1 in the order of the general pixels of vp_get_pixel_lists, (rd.x, rd.y, rd.z, t_near, t_far, t_empty, 0, 0):
+ * the camera ray's direction, the raw (unclamped) outputs of the box test for it, and word [4] of the pixel's vp_get_pixel_table
+ * entry.  No hit flag: t_far > t_near && t_far >= 1e-3f.  VP_E_STATE where this configuration has no table: the other estimators, a
+ * sub-pixel factor, no general pixel, VP_NO_RAY_TABLE=1.  Performance only: with and without it render_k computes the same bits.
+ * vp_last_ray_table: 1 if the last render launch of this context's general class read it. */
+int vp_get_ray_table(const Param* p, float* dst, size_t count);
+int vp_last_ray_table(void);
+/* test hook: out[6 i ..] = (rd.x, rd.y, rd.z, t_near, t_far, hit as 1.0f / 0.0f): the camera ray of pixel (pixels[i] & 0xffff,
+ * pixels[i] >> 16) of a width x height image and the box test for it, computed by the device functions render_k calls, in the
+ * arithmetic unit of the context's mode (vp_set_arithmetic).  VP_E_ARG for a pixel outside the image. */
+int vp_test_camera_ray(unsigned width, unsigned height, const uint32_t* pixels, float* out, int n);
 /* Counter-based streams (VP_RNG_PHILOX / VP_RNG_PHILOX7): a shadow ray draws from a sub-stream of its own, so the path's later
  * draws do not depend on the number of steps it takes, and a sun shadow ray ends once it has only empty cells in front of it.
  * dst[cell] (x fastest, count >= nx*ny*nz) = that distance from anywhere in the cell, in units of *step (world units), or
