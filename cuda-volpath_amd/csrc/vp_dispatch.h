@@ -13,6 +13,8 @@
 //   launch_instance()  the run-time instance lifted to template arguments; kernel_not_built() (vp_kernels.h) for the rest
 //   launch_layers_instance()  the same for a layers launch (LaunchDev::layers): render_k's twelfth argument, LYR, for the subset
 //                      layers_built() states -- only where the kernels above have that argument (VP_RENDER_K_HAS_LAYERS)
+//   launch_groups_instance()  the same for a light-groups launch (LaunchDev::groups): the thirteenth argument, GRP, for the same subset
+//                      (groups_built()) -- only where the kernels above have it (VP_RENDER_K_HAS_GROUPS)
 // and the same, smaller, for the approach walk (approach_built(), launch_approach_walk()).  dispatch_render(), dispatch_light() and
 // dispatch_approach() are what the launch_* functions of vp_kernels.h call.  Each launcher counts the launch under its table index
 // (census_record(), vp_kernels.h: the launch census, a test hook) just before it calls through the table.
@@ -209,8 +211,47 @@ static void launch_layers_instance(const RenderInst& v, std::integer_sequence<un
     table[i](S, L, blocks, st);
 }
 #endif
+// ---- the instances of a light-groups launch (LaunchDev::groups; render_k's GRP argument): the same subset by the same rule, in a table
+// of its own with a census of its own (vp_kernels.h groups_census_record).  Compiled where the kernels that precede this file have
+// the argument (vp_integrator.h defines VP_RENDER_K_HAS_GROUPS).
+#ifdef VP_RENDER_K_HAS_GROUPS
+constexpr bool groups_built(const RenderInst& v) { return layers_built(v); }
+template <unsigned I>
+static void launch_groups_instance_at(const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
+{
+    constexpr RenderInst v = render_at(I);
+    using RNG = typename RngOf<v.rng>::type;
+    constexpr unsigned block = v.ldsb == 1 ? VP_BLOCK_LDS : VP_BLOCK;
+    hipLaunchKernelGGL((render_k<v.est, RNG, v.quant, v.count, v.ldsb, v.ach, v.mis, v.trk, v.light, v.cancel, v.half, false, true>), dim3(blocks), dim3(block), 0, st, S, L);
+}
+template <unsigned I>
+constexpr RenderLaunchFn groups_launcher()
+{
+    if constexpr (groups_built(render_at(I))) return &launch_groups_instance_at<I>;
+    else return nullptr;
+}
+template <unsigned... I>
+static void launch_groups_instance(const RenderInst& v, std::integer_sequence<unsigned, I...>, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
+{
+    static constexpr RenderLaunchFn table[kRenderInsts] = {groups_launcher<I>()...};
+    const unsigned i = render_index(v);
+    if (i >= kRenderInsts || !table[i]) kernel_not_built();
+    groups_census_record(i);
+    table[i](S, L, blocks, st);
+}
+// built[i] of the groups table (what groups_census_read hands out)
+static void dispatch_groups_built(unsigned char* built, size_t count)
+{
+    for (size_t i = 0; i < count; i++) built[i] = i < kRenderInsts && groups_built(render_at((unsigned)i));
+}
+#endif
 static void launch_instance_of(const RenderInst& v, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
 {
+#ifdef VP_RENDER_K_HAS_GROUPS
+    if (L.groups) { launch_groups_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st); return; }
+#else
+    if (L.groups) kernel_not_built();
+#endif
 #ifdef VP_RENDER_K_HAS_LAYERS
     if (L.layers) { launch_layers_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st); return; }
 #else

@@ -195,7 +195,12 @@ constexpr int render_min_waves(int est, bool count, int ldsb, bool ach, bool mis
 // LYR: the instance of a layers launch (include/volpath.h vp_render_frames_layers; LaunchDev::layers): vp_dispatch.h names it for the
 // subset the feature is built for.  Every other instance carries no code for it.
 #define VP_RENDER_K_HAS_LAYERS 1
-template <int EST, class RNG, bool QUANT, bool COUNT, int LDSB, bool ACH, bool MIS, int TRK, bool LIGHT = false, bool CANCEL = false, bool HALF = false, bool LYR = false>
+// GRP: the instance of a light-groups launch (include/volpath.h vp_render_frames_groups; LaunchDev::groups), named by vp_dispatch.h for
+// the same subset.  It differs at the path end only: what the environment adds there is not summed into `rad` but staged as a sample
+// of its own in the second staging plane.  Every other instance carries no code for it.
+#define VP_RENDER_K_HAS_GROUPS 1
+template <int EST, class RNG, bool QUANT, bool COUNT, int LDSB, bool ACH, bool MIS, int TRK, bool LIGHT = false, bool CANCEL = false, bool HALF = false, bool LYR = false,
+          bool GRP = false>
 // Occupancy (round 4: the cold per-path state in LDS, ColdVal above; profiles/r04_kernel_resources.txt).  The achromatic
 // global-majorant kernel needs 72 registers: SEVEN waves per SIMD (C2 2541 -> 2781 Msamples/s); the chromatic one and the plain
 // achromatic local-majorant kernels 80: six (c3ref 2398 -> 2513); the LDS-table kernel keeps its state in registers (its LDS is the
@@ -307,6 +312,8 @@ void render_k(SceneDev S, LaunchDev L)
     // without work counters and look-ahead: the host refuses the rest.
     constexpr bool LAYERS = LYR;
     static_assert(!LYR || (TRK == 0 && !MIS && !COUNT && !CANCEL), "layers instances: spectral tracking, passive environment, no counters, no look-ahead");
+    // Light-groups launches (LaunchDev::groups) likewise (GRP); never both in one instance.
+    static_assert(!GRP || (!LYR && TRK == 0 && !MIS && !COUNT && !CANCEL), "groups instances: spectral tracking, passive environment, no counters, no look-ahead, no layers");
     const ParamDev& P = L.P;
     const f3    sig_t     = f3{P.sigma_t[0], P.sigma_t[1], P.sigma_t[2]};
     const f3    sig_s     = sig_t * f3{P.albedo[0], P.albedo[1], P.albedo[2]};
@@ -813,6 +820,10 @@ void render_k(SceneDev S, LaunchDev L)
             vp_pad<VP_PAD_END>();
             bool fresh = false;   // APPR: this lane took a new sample in this round, `dist` holds where approach_k left its camera ray
             bool trans = false;   // layers launch (LaunchDev::layers): the path that ends in this round is unscattered -- its sample is its throughput
+            // groups launch (LaunchDev::groups): what the environment adds to the path that ends in this round -- the sky group's sample;
+            // nothing for a path that ends without it (the segment cap) or inside the sun's disc, whose value is the sun group's
+            f3   sky    = f3{0.0f, 0.0f, 0.0f};
+            bool to_sky = false;
             // RAYT: this lane took a new sample in this round and read its camera ray and box test from the per-pixel table (L.ray:
             // ray_table_k, the bits camera_ray() and intersect_box() compute): the set-up below takes t_near and t_far from there
             bool  tabfed = false;
@@ -831,7 +842,7 @@ void render_k(SceneDev S, LaunchDev L)
                     f3 bg;
                     if (LAYERS && trans) bg = f3{1.0f, 1.0f, 1.0f};
                     else if (nsc == 0 && dot(rd, sun_dir) > S.sun_cos) bg = f3{S.sun_orig[0], S.sun_orig[1], S.sun_orig[2]};
-                    else { bg = eval_envmap(S, rd); if (COUNT) c_env++; }
+                    else { bg = eval_envmap(S, rd); if (COUNT) c_env++; if (GRP) to_sky = true; }
                     if (LIGHT && !LOCAL)
                     {
                         // throughput after `seg` null collisions in empty space (see tracking_step)
@@ -840,7 +851,11 @@ void render_k(SceneDev S, LaunchDev L)
                         for (unsigned k = last; k < n; k++) t = null_collision_in_empty_space(t, sigma_t_prime, inv_sigma_t);
                         thr = f3{t, t, t};
                     }
-                    rad = rad + bg * (ACH ? f3{thr.x, thr.x, thr.x} : thr);
+                    // (a groups launch: the sum a render without the sun makes here, from +0 -- include/volpath.h vp_render_frames_groups)
+                    // (the light class, whose path has summed nothing: the sum stays in `rad` and EV_WRITE routes the sample -- two registers
+                    // and, local majorants, the eighth wave: profiles/groups_kernel_resources.txt)
+                    if (GRP && !LIGHT && to_sky) sky = sky + bg * (ACH ? f3{thr.x, thr.x, thr.x} : thr);
+                    else rad = rad + bg * (ACH ? f3{thr.x, thr.x, thr.x} : thr);
                 }
                 st = EV_WRITE;
             }
@@ -864,6 +879,19 @@ void render_k(SceneDev S, LaunchDev L)
                 float4 v    = make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), heat);
                 if (TRK == 2)  // kernel.cu:2311-2313: the drawn channel only, times three
                     v = make_float4(chan == 0 ? v.x * 3.0f : 0.0f, chan == 1 ? v.y * 3.0f : 0.0f, chan == 2 ? v.z * 3.0f : 0.0f, heat);
+                if (GRP && LIGHT)
+                {
+                    // every sample of the light class is the environment's term alone: it is one group's whole, the other gets (0, 0, 0, heat)
+                    // (selects per channel: a select between two float4 objects goes through scratch)
+                    L.groups[item] = make_float4(to_sky ? v.x : 0.0f, to_sky ? v.y : 0.0f, to_sky ? v.z : 0.0f, heat);
+                    v              = make_float4(to_sky ? 0.0f : v.x, to_sky ? 0.0f : v.y, to_sky ? 0.0f : v.z, heat);
+                }
+                else if (GRP)
+                {
+                    // the sky group's sample beside the sun group's: the beauty sample's operations on `sky` (a groups launch is staged)
+                    const f3 k = sky * P.brightness;
+                    L.groups[item] = make_float4(fmaxf(k.x, 0.0f), fmaxf(k.y, 0.0f), fmaxf(k.z, 0.0f), heat);
+                }
                 if (L.stage) L.stage[item] = v;
                 else
                 {

@@ -165,6 +165,11 @@ struct LaunchDev
     // flag is not stored: t_far > t_near && t_far >= 1e-3f.  Null (no memory, a sub-pixel factor, a caller's own lists, the light
     // class, VP_NO_RAY_TABLE=1): render_k computes them per sample, same bits.
     const float4* ray;
+    // A light-groups launch (include/volpath.h vp_render_frames_groups; appended like the fields above): the second staging plane, laid
+    // out like `stage` (frame * stage_stride + slot) and lying behind the launch's last staged frame.  render_k's GRP instances and the
+    // constant writers stage the sky group's sample there and the sun group's in `stage`; reduce_groups_k adds the two planes into the
+    // two accumulators.  Null: not a groups launch.
+    float4* groups;
 };
 
 // render_k and the approach kernels: which instance a launch runs, and which of them a build compiles, is decided in vp_dispatch.h.
@@ -182,6 +187,10 @@ void census_read(int unit, int kind, unsigned* launches, unsigned char* built, s
 // built[i] of one unit, from the constexpr functions of vp_dispatch.h as that unit compiled them (vp_kernels.hip / vp_kernels_fast.hip)
 void census_built(int kind, unsigned char* built, size_t count);
 void census_built_fast(int kind, unsigned char* built, size_t count);
+// The same for the table of a groups launch (launch_groups_instance() of vp_dispatch.h; test hook: vp_test_groups_census), kept apart
+// from the kinds above: the exact unit only, the index and length of CENSUS_RENDER.
+void groups_census_record(unsigned index);
+void groups_census_read(unsigned* launches, unsigned char* built, size_t count, bool reset);
 // lds_form: how the decomposition estimator reads its brick table -- 0 global memory, 1 the 16-bit table through LDS (512-thread
 // workgroups), 2 2-bit codes into a four-entry palette through LDS (LaunchDev::bound_codes; 256-thread workgroups, plain occupancy)
 // half (with quant = false): binary16 cells (SceneDev::cells_f16); everything else of such a volume is the float volume's
@@ -235,6 +244,9 @@ void launch_reduce(const LaunchDev& L, hipStream_t st);
 // the reduce of a layers launch (LaunchDev::layers): L.out is the foreground accumulator, trans the transmittance accumulator; the slots
 // [light_from, light_to) of the list are the light kernel's, whose samples are transmittance samples without the mark
 void launch_reduce_layers(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st);
+// the reduce of a groups launch (LaunchDev::groups): L.out is the sun accumulator and receives the plane L.stage, sky the sky accumulator
+// and receives the plane L.groups; constants (LaunchDev::const_from) lie in the first row of either plane
+void launch_reduce_groups(const LaunchDev& L, float4* sky, hipStream_t st);
 // Per-pixel statistics (include/volpath.h vp_pixel_stats, the same 24 bytes) and what launch_reduce_stats does with them: the
 // reduce of a staged launch that also adds each sample's luminance to its pixel's record, and -- adaptive: a round of
 // vp_render_adaptive -- freezes the records whose criterion holds (tol, fl: the binary32 arguments widened)
@@ -270,6 +282,8 @@ void launch_build_bounds(const void* d_vol, bool quant, bool half, void* d_out, 
 void launch_julia(unsigned char* grid, int n, hipStream_t st);
 void launch_cloud(float* grid, int n, unsigned seed, hipStream_t st);
 void launch_scale(float4* dst, const float4* src, int size, float s, hipStream_t st);
+// dst.c = (sun.c * s) * sun_gain[c] + (sky.c * s) * sky_gain[c], dst.w = sun.w * s (relight_k)
+void launch_relight(float4* dst, const float4* sun, const float4* sky, float3 sun_gain, float3 sky_gain, int size, float s, hipStream_t st);
 // dst = fg * s + (trans * s) o B, dst.w = 1 - trans.w * s; B = plate[i].xyz, or the constant (r, g, b) where plate is null (composite_k)
 void launch_composite(float4* dst, const float4* fg, const float4* trans, const float4* plate, float r, float g, float b, int size, float s, hipStream_t st);
 void launch_gamma(float4* dst, const float4* src, int size, float s, float inv_gamma, hipStream_t st);

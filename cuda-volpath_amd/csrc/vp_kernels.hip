@@ -420,6 +420,35 @@ __global__ __launch_bounds__(256) void reduce_layers_k(LaunchDev L, float4* tran
     trans[idx] = t;
 }
 
+// reduce_stage_k's job for a groups launch (LaunchDev::groups): the plane L.stage into L.out (the sun accumulator), the plane L.groups
+// into `sky`, each in frame order; a constant of the launch lies in the first row of either plane and is added nframes times.
+__global__ __launch_bounds__(256) void reduce_groups_k(LaunchDev L, float4* sky)
+{
+    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.nslots) return;
+    unsigned pix = L.pixels[slot];
+    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
+    float4   a = L.out[idx], k = sky[idx];
+    if (slot >= L.const_from)
+    {
+        const float4 v = L.stage_const[slot], w = L.groups[slot];
+        for (int f = 0; f < L.nframes; f++)
+        {
+            a = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
+            k = make_float4(k.x + w.x, k.y + w.y, k.z + w.z, k.w + w.w);
+        }
+    }
+    else
+        for (int f = 0; f < L.nframes; f++)
+        {
+            const float4 v = L.stage[(size_t)f * L.stage_stride + slot], w = L.groups[(size_t)f * L.stage_stride + slot];
+            a = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
+            k = make_float4(k.x + w.x, k.y + w.y, k.z + w.z, k.w + w.w);
+        }
+    L.out[idx] = a;
+    sky[idx]   = k;
+}
+
 // ---- the pixel lists of a rank, built on the GPU (vp_tables.cpp ensure_pixel_lists): a stable partition of the rank's pixels --
 // those of its 8x8 tiles, tile by tile (row-major tiles, row-major pixels within a tile) -- by pixel class (0 general, 1 the whole
 // chord is certified empty, 2 the camera ray misses the box; pixel table [1].y).  Padded slot s = 64 * (n-th owned tile) + 8 * row +
@@ -753,6 +782,61 @@ __global__ __launch_bounds__(256) void subpixel_fill_k(SceneDev S, LaunchDev L)
         size_t idx = (size_t)px + (size_t)py * P.width;
         float4 a   = L.out[idx];
         L.out[idx] = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
+    }
+}
+
+// The constant writers of a groups launch (LaunchDev::groups; include/volpath.h vp_render_frames_groups): unscattered_sample()'s
+// expressions with the environment's term kept apart -- inside the sun's disc the sample is the sun group's and the sky group gets
+// (0, 0, 0, heat); elsewhere the sun group's radiance is the +0 the path has summed and the sky group's the sum from +0.  Both are
+// staged, the sky group's in the second plane: rows as miss_fill_k / subpixel_fill_k write them (a groups launch is always staged).
+__device__ __forceinline__ void unscattered_groups(const SceneDev& S, const ParamDev& P, f3 rd, float4& sun, float4& sky)
+{
+    const f3 sun_dir = f3{S.sun_dir[0], S.sun_dir[1], S.sun_dir[2]};
+    f3       rad = f3{0.0f, 0.0f, 0.0f}, sk = f3{0.0f, 0.0f, 0.0f};
+    const f3 thr = f3{1.0f, 1.0f, 1.0f};
+    if (dot(rd, sun_dir) > S.sun_cos) rad = rad + f3{S.sun_orig[0], S.sun_orig[1], S.sun_orig[2]} * thr;
+    else sk = sk + eval_envmap(S, rd) * thr;
+    const f3 r = rad * P.brightness, k = sk * P.brightness;
+    sun = make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), 0.0f);
+    sky = make_float4(fmaxf(k.x, 0.0f), fmaxf(k.y, 0.0f), fmaxf(k.z, 0.0f), 0.0f);
+}
+__global__ __launch_bounds__(256) void miss_fill_groups_k(SceneDev S, LaunchDev L)
+{
+    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.nslots || !L.stage || !L.groups) return;
+    const ParamDev& P = L.P;
+    unsigned pix = L.pixels[slot], px = pix & 0xffffu, py = pix >> 16;
+    f3 ro, rd;
+    camera_ray(S, P.width, P.height, px, py, ro, rd);
+    float4 v, w;
+    unscattered_groups(S, P, rd, v, w);
+    const int rows = (L.slot_base + slot >= L.const_from) ? 1 : L.nframes;
+    for (int f = 0; f < rows; f++)
+    {
+        L.stage[(size_t)f * L.stage_stride + L.slot_base + slot]  = v;
+        L.groups[(size_t)f * L.stage_stride + L.slot_base + slot] = w;
+    }
+}
+__global__ __launch_bounds__(256) void subpixel_fill_groups_k(SceneDev S, LaunchDev L)
+{
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x, m = L.sub_shift, n2 = 1u << (2u * m);
+    if (t >= L.nslots * n2 || !L.stage || !L.groups) return;
+    const unsigned k = t / L.nslots, slot = t - k * L.nslots;
+    const ParamDev& P = L.P;
+    const unsigned pix = L.pixels[slot], px = pix & 0xffffu, py = pix >> 16;
+    const unsigned h = wang_hash(((px << 16) | py) ^ 0x9E3779B9u);
+    unsigned fl = (k - ((unsigned)L.frame0 + h)) & (n2 - 1u);   // (subpixel_fill_k: the first frame of the launch that uses fine pixel k)
+    if (fl >= (unsigned)L.nframes) return;
+    unsigned i, j;
+    subpixel_offset(px, py, (unsigned)L.frame0 + fl, m, i, j);
+    f3 ro, rd;
+    camera_ray(S, P.width << m, P.height << m, (px << m) + i, (py << m) + j, ro, rd);
+    float4 v, w;
+    unscattered_groups(S, P, rd, v, w);
+    for (; fl < (unsigned)L.nframes; fl += n2)
+    {
+        L.stage[(size_t)fl * L.stage_stride + L.slot_base + slot]  = v;
+        L.groups[(size_t)fl * L.stage_stride + L.slot_base + slot] = w;
     }
 }
 
@@ -1094,6 +1178,15 @@ __global__ void composite_k(float4* dst, const float4* fg, const float4* trans, 
     if (plate) { const float4 q = plate[idx]; bx = q.x; by = q.y; bz = q.z; }
     dst[idx] = make_float4(f.x * s + (t.x * s) * bx, f.y * s + (t.y * s) * by, f.z * s + (t.z * s) * bz, 1.0f - t.w * s);
 }
+// include/volpath.h vp_relight: the two light groups scaled, then weighted per channel and added; one rounding per operation in this
+// order (the build has no contraction); w = the sun group's (both groups carry the same heat)
+__global__ void relight_k(float4* dst, const float4* sun, const float4* sky, float3 gs, float3 gk, int size, float s)
+{
+    int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= size) return;
+    const float4 u = sun[idx], k = sky[idx];
+    dst[idx] = make_float4((u.x * s) * gs.x + (k.x * s) * gk.x, (u.y * s) * gs.y + (k.y * s) * gk.y, (u.z * s) * gs.z + (k.z * s) * gk.z, u.w * s);
+}
 __device__ __forceinline__ float pow_pos(float x, float y) { return x <= 0.0f ? 0.0f : expf_(logf_(x) * y); }
 // __gamma_correct kernel.cu:2348-2357 (inv_gamma = 1/gamma computed by the host wrapper, :2361)
 __global__ void gamma_k(float4* dst, const float4* src, int size, float s, float inv_gamma)
@@ -1276,6 +1369,22 @@ void census_read(int unit, int kind, unsigned* launches, unsigned char* built, s
     }
 }
 void census_built(int kind, unsigned char* built, size_t count) { dispatch_census_built(kind, built, count); }
+// the groups table's census (vp_kernels.h): counters of its own beside the kinds above
+static std::atomic<uint32_t> g_census_groups[kRenderInsts];
+void groups_census_record(unsigned index)
+{
+    if (index < kRenderInsts) g_census_groups[index].fetch_add(1u, std::memory_order_relaxed);
+}
+void groups_census_read(unsigned* launches, unsigned char* built, size_t count, bool reset)
+{
+    if (count > kRenderInsts) count = kRenderInsts;
+    if (built) dispatch_groups_built(built, count);
+    for (size_t i = 0; i < count; i++)
+    {
+        const uint32_t n = reset ? g_census_groups[i].exchange(0u, std::memory_order_relaxed) : g_census_groups[i].load(std::memory_order_relaxed);
+        if (launches) launches[i] = n;
+    }
+}
 void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
                    int blocks, hipStream_t st)
 {
@@ -1301,6 +1410,13 @@ void launch_thr_table(const ParamDev& P, float* table, unsigned count, hipStream
 }
 void launch_miss_fill(const SceneDev& S, const LaunchDev& L, bool local_estimator, hipStream_t st)
 {
+    if (L.groups)
+    {
+        // (a groups launch: writers of their own, which stage the two constants; the counting launches they have no tallies for are refused)
+        if (L.sub_shift) hipLaunchKernelGGL(subpixel_fill_groups_k, dim3(((L.nslots << (2u * L.sub_shift)) + 255) / 256), dim3(256), 0, st, S, L);
+        else hipLaunchKernelGGL(miss_fill_groups_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, S, L);
+        return;
+    }
     if (L.sub_shift)
     {
         hipLaunchKernelGGL(subpixel_fill_k, dim3(((L.nslots << (2u * L.sub_shift)) + 255) / 256), dim3(256), 0, st, S, L);
@@ -1438,6 +1554,14 @@ void launch_reduce(const LaunchDev& L, hipStream_t st)
 void launch_reduce_layers(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st)
 {
     hipLaunchKernelGGL(reduce_layers_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, trans, light_from, light_to);
+}
+void launch_reduce_groups(const LaunchDev& L, float4* sky, hipStream_t st)
+{
+    hipLaunchKernelGGL(reduce_groups_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky);
+}
+void launch_relight(float4* dst, const float4* sun, const float4* sky, float3 sun_gain, float3 sky_gain, int size, float s, hipStream_t st)
+{
+    hipLaunchKernelGGL(relight_k, dim3((size + 255) / 256), dim3(256), 0, st, dst, sun, sky, sun_gain, sky_gain, size, s);
 }
 void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st)
 {

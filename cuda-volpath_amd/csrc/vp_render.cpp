@@ -225,6 +225,8 @@ struct LaunchPlan
     bool       stage_only;        // ... which is staged whole and not reduced
     const StatsDev* stats;        // the reduce also takes the statistics
     float4*    layers;            // a layers call (vp_render_frames_layers): the transmittance accumulator; the reduce splits the samples (reduce_layers_k)
+    float4*    groups;            // a light-groups call (vp_render_frames_groups): the sky accumulator; a launch stages two planes (reduce_groups_k)
+    size_t planes() const { return groups ? 2u : 1u; }   // staging planes per frame
     // the slots of the list, general pixels first: where the class a kernel integrates ends (the general class and a light class that
     // is not written as constants), i.e. where the per-pixel constants of a launch begin -- const_from and the layers reduce's range
     unsigned integrated_end() const { return PL.n_general + ((PL.n_light && !light_const) ? PL.n_light : 0u); }
@@ -306,9 +308,9 @@ static int plan_target(int nframes, const Target* tgt, const PixelLists* lists, 
 {
     // a call with statistics is staged whatever its length (render_k's direct accumulation has none) and stays on the caller's stream
     // (a layers call too: the direct accumulation has no second target)
-    A.staged = nframes > 1 || A.stage_only || A.stats || A.layers;
+    A.staged = nframes > 1 || A.stage_only || A.stats || A.layers || A.groups;
     A.T      = tgt ? *tgt : Target{&G.target[0], G.stream};   // (a pipelined call: a slot's, below)
-    A.max_f  = A.staged ? stage_frames_cap(A.per_frame, A.T.rt->stage.bytes) : 1;
+    A.max_f  = A.staged ? stage_frames_cap(A.per_frame, A.T.rt->stage.bytes, A.planes()) : 1;
     // The staging slot of the decomposition estimator's hand-over holds the segment origin and the distance reached in it: the stream's
     // state (a pair index, or sampler.h's two words) goes beside it.  Sized ONCE, before the launch loop (no synchronisation, no early
     // return between a launch's events).
@@ -316,7 +318,7 @@ static int plan_target(int nframes, const Target* tgt, const PixelLists* lists, 
     // A staged call of vp_render_frames goes to the next pipeline slot when the slot holds it in one launch (counting launches stay on the
     // caller's stream).  Otherwise -- VP_NO_PIPELINE, no memory for the slot -- the caller's stream, as before: same bits either way.
     A.slot  = G.pipe_next;
-    A.piped = !tgt && !A.stage_only && !lists && !A.stats && !A.layers && nframes > 1 && G.pipeline && !G.count && pipe_target(A.per_frame, nframes, A.appr_aux_needed, &A.T);
+    A.piped = !tgt && !A.stage_only && !lists && !A.stats && !A.layers && !A.groups && nframes > 1 && G.pipeline && !G.count && pipe_target(A.per_frame, nframes, A.appr_aux_needed, &A.T);
     if (A.piped) A.max_f = (size_t)nframes;
     else if (!tgt) G.pipe_fence = true;   // (the caller's stream uses slot 0's buffers: the next pipelined launch waits for it)
     G.last_pipelined = A.piped ? 1 : 0;
@@ -329,8 +331,8 @@ static int plan_target(int nframes, const Target* tgt, const PixelLists* lists, 
 static int reserve_launch_stage(LaunchPlan& A, int f, bool* smaller)
 {
     *smaller = false;
-    const size_t exact = A.per_frame * (size_t)f * sizeof(float4);
-    const int rc = reserve_stage(A.T, exact, A.per_frame * A.sized_frames(f) * sizeof(float4));
+    const size_t exact = A.per_frame * (size_t)f * sizeof(float4) * A.planes();
+    const int rc = reserve_stage(A.T, exact, A.per_frame * A.sized_frames(f) * sizeof(float4) * A.planes());
     if (rc || exact <= A.T.rt->stage.bytes) return rc;
     if (A.stage_only) return fail(VP_E_NOMEM, "no memory for a look-ahead batch of %d frames", f);
     if (f <= 1) return fail(VP_E_NOMEM, "no memory for one staged frame (%zu bytes)", exact);
@@ -573,6 +575,7 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
         R.adaptive = A.stats->adaptive && last ? 1u : 0u;
         launch_reduce_stats(L, R, G.stream);
     }
+    else if (A.groups) launch_reduce_groups(L, A.groups, G.stream);
     else if (A.layers) launch_reduce_layers(L, A.layers, A.PL.n_general, A.integrated_end(), G.stream);   // (the light kernel's slots: its samples carry no mark)
     else launch_reduce(L, G.stream);
     HIPCHK(hipGetLastError());
@@ -587,7 +590,7 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
 // One render call: check, prepare the tables, plan, then launch by launch -- reserve the staging, wire the pipeline, launch the
 // classes (timed), reduce
 int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only, const Target* tgt, const PixelLists* lists, const StatsDev* stats,
-              vp_float4* d_trans)
+              vp_float4* d_trans, vp_float4* d_sky)
 {
     int rc = ensure_device();
     if (rc) return rc;
@@ -611,10 +614,11 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     // default of rounds 1-4, stays 0.8 % ahead of 28 on the reference's live configuration (profiles/r05_raw/sweep_samplerh.txt)
     if (!G.wait_lanes_set && G.rng == VP_RNG_SAMPLERH && G.trk == VP_TRACK_SPECTRAL) L.wait_lanes = 24;
     if (sh.per_frame == 0) return VP_OK;
-    if ((lists || stats || d_trans) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics or layers");
-    if (d_trans && (lists || stats)) return fail(VP_E_ARG, "a layers call renders the cached lists without statistics");
+    if ((lists || stats || d_trans || d_sky) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics, layers or groups");
+    if ((d_trans || d_sky) && (lists || stats)) return fail(VP_E_ARG, "a layers or groups call renders the cached lists without statistics");
+    if (d_trans && d_sky) return fail(VP_E_ARG, "layers and light groups in one call are not built");
     LaunchPlan A = {};
-    A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats; A.layers = (float4*)d_trans;
+    A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats; A.layers = (float4*)d_trans; A.groups = (float4*)d_sky;
     L.layers = d_trans ? 1u : 0u;
     if ((rc = prepare_tables(p, sh, nframes, lists, L, A)) || A.per_frame == 0) return rc;
     if (0xfffffff0u / A.per_frame < 1) return fail(VP_E_ARG, "image too large for the 32-bit sample queue");
@@ -634,6 +638,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         L.frame0 = first + done;
         L.nframes = f;
         L.stage = A.staged ? A.T.rt->stage.p : nullptr;
+        L.groups = A.groups ? L.stage + A.per_frame * (size_t)f : nullptr;   // (the second plane: behind the f frames of the first)
         // per-pixel constants of the launch (the box-missing pixels; the light class where it is written by miss_fill_k) are staged once,
         // in the launch's first row: the slots behind the general (and an integrated light) class
         L.const_from = 0xffffffffu; L.stage_const = nullptr;
@@ -690,6 +695,32 @@ int vp_render_frames_layers(vp_float4* d_fg, vp_float4* d_trans, int first_frame
     // the call is serial and runs on the caller's stream: look-ahead batches stop, pipelined launches are waited for
     if ((rc = la_quiesce())) return rc;
     return do_render(d_fg, first_frame, n_frames, p, false, nullptr, nullptr, nullptr, d_trans);
+}
+// Light groups (include/volpath.h): the same call with the environment's term of every sample kept apart -- render_k's GRP instances
+// and the groups forms of the constant writers stage it in a second plane (LaunchDev::groups), reduce_groups_k adds the two planes into
+// the two accumulators.  Refusals as above.
+int vp_render_frames_groups(vp_float4* d_sun, vp_float4* d_sky, int first_frame, int n_frames, const Param* p)
+{
+    if (!d_sun || !d_sky || d_sun == d_sky || !p || n_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "vp_render_frames_groups: bad arguments");
+    if (G.env_mis) return fail(VP_E_STATE, "vp_render_frames_groups is defined for passive environment lighting only (VP_ENV_MIS: the environment is sampled as a light, another estimator)");
+    if (G.trk) return fail(VP_E_STATE, "vp_render_frames_groups is built for spectral tracking only");
+    if (G.count) return fail(VP_E_STATE, "vp_render_frames_groups is not built for work counters");
+    if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "vp_render_frames_groups is built for the exact arithmetic only (its kernel instances are the exact unit's)");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = la_quiesce())) return rc;
+    return do_render(d_sun, first_frame, n_frames, p, false, nullptr, nullptr, nullptr, nullptr, d_sky);
+}
+int vp_relight(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const float sun_gain[3], const float sky_gain[3], int size, float scale)
+{
+    if (!dst || !sun || !sky || !sun_gain || !sky_gain || size < 0) return fail(VP_E_ARG, "vp_relight: bad arguments");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (size)
+        launch_relight((float4*)dst, (const float4*)sun, (const float4*)sky, make_float3(sun_gain[0], sun_gain[1], sun_gain[2]),
+                       make_float3(sky_gain[0], sky_gain[1], sky_gain[2]), size, scale, G.stream);
+    HIPCHK(hipGetLastError());
+    return VP_OK;
 }
 int vp_composite(vp_float4* dst, const vp_float4* fg, const vp_float4* trans, const vp_float4* plate, const float plate_rgb[3], int size, float scale)
 {
@@ -887,18 +918,19 @@ int vp_get_ray_table(const Param* p, float* dst, size_t count)
     return VP_OK;
 }
 int vp_last_ray_table(void) { return G.last_ray_table; }
-int vp_reserve_frames(const Param* p, int nframes)
+// planes: 1 for vp_render_frames, 2 for vp_render_frames_groups (whose calls are staged for one frame too and never pipelined)
+static int reserve_frames(const Param* p, int nframes, size_t planes)
 {
     int rc = ensure_device();
     if (rc) return rc;
     if (!p || nframes <= 0) return fail(VP_E_ARG, "vp_reserve_frames: bad arguments");
     if ((rc = check_render(CHK_IMAGE, p))) return rc;
     const Shard sh = shard_of(p);
-    if (sh.per_frame == 0 || nframes == 1) return VP_OK;
+    if (sh.per_frame == 0 || (nframes == 1 && planes == 1)) return VP_OK;
     // what do_render would allocate for the first launch of such a job (a one-frame call accumulates directly and stages nothing)
     const Target T      = {&G.target[0], G.stream};
-    const size_t f      = std::min<size_t>((size_t)nframes, stage_frames_cap(sh.per_frame, T.rt->stage.bytes));
-    const size_t need   = sh.per_frame * f * sizeof(float4);
+    const size_t f      = std::min<size_t>((size_t)nframes, stage_frames_cap(sh.per_frame, T.rt->stage.bytes, planes));
+    const size_t need   = sh.per_frame * f * sizeof(float4) * planes;
     // (decomposition estimator: the stream's state beside each staging slot of the approach kernel's hand-over, where a launch of this
     // configuration can walk ahead at all -- do_render asks the same)
     const size_t need4  = (G.est == VP_EST_DECOMP && approach_built()) ? sh.per_frame * f * sizeof(uint2) : 0;
@@ -911,7 +943,18 @@ int vp_reserve_frames(const Param* p, int nframes)
         if (need > T.rt->stage.bytes) return VP_OK;   // the render call will stage smaller batches: same bits
     }
     // ... and pipeline slot 1 where the job goes in one launch (best effort: a call the slot cannot hold renders on the caller's stream)
-    if (G.pipeline && f == (size_t)nframes && pipe_streams()) (void)pipe_reserve(1, sh.per_frame, nframes, need4 > 0);
+    if (planes == 1 && G.pipeline && f == (size_t)nframes && pipe_streams()) (void)pipe_reserve(1, sh.per_frame, nframes, need4 > 0);
     return VP_OK;
+}
+int vp_reserve_frames(const Param* p, int nframes) { return reserve_frames(p, nframes, 1); }
+int vp_reserve_frames_groups(const Param* p, int nframes) { return reserve_frames(p, nframes, 2); }
+int vp_groups_frames_per_launch(const Param* p, int planes)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (!p || planes < 1 || planes > 2) return fail(VP_E_ARG, "vp_groups_frames_per_launch: bad arguments");
+    const Shard sh = shard_of(p);
+    if (sh.per_frame == 0) return 0;
+    return (int)std::min<size_t>(stage_frames_cap(sh.per_frame, G.target[0].stage.bytes, (size_t)planes), 0x7fffffff);
 }
 }  // extern "C"

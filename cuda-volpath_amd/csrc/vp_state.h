@@ -334,7 +334,7 @@ inline void put_event(hipEvent_t e) { if (e) G.event_pool.push_back(e); }
 // the shard of this context (include/volpath.h vp_tile_owner): its 8x8 tiles and the pixels of the image they hold
 struct Shard { unsigned tiles_x, tiles_y, owned; size_t per_frame; };  // owned = tiles, per_frame = pixels = samples per frame
 Shard  shard_of(const Param* p);
-size_t stage_frames_cap(size_t per_frame, size_t have_bytes);
+size_t stage_frames_cap(size_t per_frame, size_t have_bytes, size_t planes = 1);
 int    do_opacity(const float* dir);
 int    ensure_crawl_table(const Param* p, const float4** out);
 Param  subpixel_param(const Param* p);   // p for the image the samples are computed on: (width, height) << sub_shift
@@ -358,9 +358,10 @@ struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss;
 // subset of them (vp_adaptive.cpp).  stats: the reduce also takes the statistics of include/volpath.h (launch_reduce_stats); such a
 // call is staged even for one frame and runs on the caller's stream, not on a pipeline slot.  d_trans: a layers call
 // (vp_render_frames_layers) -- d_out is the foreground accumulator, d_trans the transmittance accumulator; staged and on the caller's
-// stream likewise, with the cached lists and without statistics.
+// stream likewise, with the cached lists and without statistics.  d_sky: a light-groups call (vp_render_frames_groups) -- d_out is the
+// sun accumulator, d_sky the sky accumulator; staged in two planes, otherwise as a layers call (never both).
 int  do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only = false, const Target* tgt = nullptr,
-               const PixelLists* lists = nullptr, const StatsDev* stats = nullptr, vp_float4* d_trans = nullptr);
+               const PixelLists* lists = nullptr, const StatsDev* stats = nullptr, vp_float4* d_trans = nullptr, vp_float4* d_sky = nullptr);
 // the preconditions of a render call, each caller with the subset it needs (p: the image checks; last_frame: the opacity rule)
 enum : unsigned { CHK_STATE = 1, CHK_IMAGE = 2, CHK_IMAGE_NOTE = 4, CHK_MODES = 8, CHK_OPACITY = 16 };
 int  check_render(unsigned what, const Param* p, long long last_frame = 0);

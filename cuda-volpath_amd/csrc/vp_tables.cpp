@@ -83,14 +83,15 @@ Shard shard_of(const Param* p)
     return s;
 }
 // frames of per_frame samples one staged launch may hold: the configured cap, a quarter of the memory that is free
-// now (plus what the target buffer already holds), and the 32-bit sample queue
-size_t stage_frames_cap(size_t per_frame, size_t have_bytes)
+// now (plus what the target buffer already holds), and the 32-bit sample queue.  planes: the staging planes a frame takes (2 for a
+// light-groups launch, whose second plane halves the frames)
+size_t stage_frames_cap(size_t per_frame, size_t have_bytes, size_t planes)
 {
     size_t cap = G.max_stage_bytes;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) cap = std::min(cap, std::max(have_bytes, (free_b + have_bytes) / 4));
     else (void)hipGetLastError();
-    size_t f = cap / (per_frame * sizeof(float4));
+    size_t f = cap / (per_frame * sizeof(float4) * planes);
     f = std::min<size_t>(f, 0xfffffff0u / per_frame);
     return std::max<size_t>(f, 1);
 }

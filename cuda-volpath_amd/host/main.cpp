@@ -51,6 +51,13 @@ static void usage()
            "                                                the composite over the constant colour (R, G, B) to --out (vp_composite; its w is\n"
            "                                                coverage).  Without --over no --out image is written: the context's own sky is in\n"
            "                                                neither layer.  One GPU; not with --noise or --denoise; spectral, --env passive, --arith exact\n"
+           "               [--groups-out PREFIX] [--sun-gain R G B] [--sky-gain R G B]\n"
+           "                                                light groups (vp_render_frames_groups): the frames are rendered once, what the\n"
+           "                                                sun lights and what the sky lights in accumulators of their own.  --groups-out\n"
+           "                                                writes the two mean images as PREFIX_sun.hdr and PREFIX_sky.hdr; --out receives\n"
+           "                                                sun * sun-gain + sky * sky-gain per channel (vp_relight; gains default to 1 1 1).\n"
+           "                                                One GPU; not with --noise, --denoise or --layers-out / --over; spectral, --env\n"
+           "                                                passive, --arith exact\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -79,6 +86,9 @@ int main(int argc, char** argv)
     std::string layers_out;
     bool        over = false;
     float       over_rgb[3] = {0.0f, 0.0f, 0.0f};
+    std::string groups_out;
+    bool        relit = false;
+    float       sun_gain[3] = {1.0f, 1.0f, 1.0f}, sky_gain[3] = {1.0f, 1.0f, 1.0f};
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -174,6 +184,19 @@ int main(int argc, char** argv)
             }
             over = true;
         }
+        else if (a == "--groups-out") { need(1); groups_out = argv[++i]; }
+        else if (a == "--sun-gain" || a == "--sky-gain")
+        {
+            need(3);
+            float* gain = a == "--sun-gain" ? sun_gain : sky_gain;
+            for (int c = 0; c < 3; c++)
+            {
+                char* end = nullptr;
+                gain[c] = strtof(argv[++i], &end);
+                if (end == argv[i] || *end || !std::isfinite(gain[c])) { fprintf(stderr, "%s %s: three finite numbers\n", a.c_str(), argv[i]); usage(); return 2; }
+            }
+            relit = true;
+        }
         else if (a == "--sun") { need(2); sunx = (float)atof(argv[++i]); suny = (float)atof(argv[++i]); }
         else if (a == "--batch") { need(1); batch = atoi(argv[++i]); }
         else if (a == "--out") { need(1); out = argv[++i]; }
@@ -223,6 +246,19 @@ int main(int argc, char** argv)
     if (layers && (tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE || arith != VP_ARITH_EXACT))
     {
         fprintf(stderr, "--layers-out / --over need spectral tracking, --env passive and --arith exact\n");
+        return 2;
+    }
+    const bool groups = relit || !groups_out.empty();
+    if (groups && (gpus > 1 || adaptive || denoise || layers))
+    {
+        fprintf(stderr, "--groups-out / --sun-gain / --sky-gain with %s: light groups are not reduced across ranks, carry no per-pixel statistics and are not combined with layers; "
+                "use one GPU without --noise, --denoise, --layers-out and --over\n",
+                gpus > 1 ? "--gpus" : adaptive ? "--noise" : denoise ? "--denoise" : over ? "--over" : "--layers-out");
+        return 2;
+    }
+    if (groups && (tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE || arith != VP_ARITH_EXACT))
+    {
+        fprintf(stderr, "--groups-out / --sun-gain / --sky-gain need spectral tracking, --env passive and --arith exact\n");
         return 2;
     }
     if (adaptive && (min_spp < 2 || round_frames < 1)) { fprintf(stderr, "--noise needs --min-spp >= 2 and --round >= 1\n"); usage(); return 2; }
@@ -337,7 +373,8 @@ int main(int argc, char** argv)
         if (!stats || vp_memset(stats, 0, (size_t)npix * sizeof(vp_pixel_stats))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
     }
     vp_float4* trans = nullptr;   // --layers-out / --over: accum[0] is the foreground accumulator, this the transmittance accumulator
-    if (layers)
+    // (--groups-out / --sun-gain / --sky-gain: accum[0] is the sun accumulator, this the sky accumulator)
+    if (layers || groups)
     {
         trans = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
         if (!trans || vp_memset(trans, 0, (size_t)npix * sizeof(vp_float4))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
@@ -353,6 +390,12 @@ int main(int argc, char** argv)
         {
             const int n = batch > 0 ? std::min(batch, spp - s) : 1;
             if (vp_render_frames_layers(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            s += n;
+        }
+        else if (groups)
+        {
+            const int n = batch > 0 ? std::min(batch, spp - s) : 1;
+            if (vp_render_frames_groups(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
             s += n;
         }
         else if (denoise)
@@ -426,6 +469,21 @@ int main(int argc, char** argv)
             if (vp_composite(disp, accum[0], trans, nullptr, over_rgb, npix, 1.0f / spp)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
             if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
         }
+    }
+    else if (groups)
+    {
+        // the two mean groups as they are; their weighted sum in place of the beauty image
+        if (!groups_out.empty())
+            for (int k = 0; k < 2; k++)
+            {
+                const std::string name = groups_out + (k ? "_sky.hdr" : "_sun.hdr");
+                scale(disp, k ? trans : accum[0], npix, 1.0f / spp);
+                vp_download(image.buffer(), disp, (size_t)npix * sizeof(vp_float4));
+                image.dump_hdr(name.c_str());
+                printf("wrote %s\n", name.c_str());
+            }
+        if (vp_relight(disp, accum[0], trans, sun_gain, sky_gain, npix, 1.0f / spp)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
     }
     else if (denoise)
     {

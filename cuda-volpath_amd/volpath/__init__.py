@@ -34,6 +34,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_frames_stats", "vp_render_adaptive", "vp_scale_by_count", "vp_stats_rel_error",
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
                  "vp_render_frames_layers", "vp_composite",
+                 "vp_render_frames_groups", "vp_relight", "vp_reserve_frames_groups", "vp_groups_frames_per_launch", "vp_test_groups_census",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -138,6 +139,11 @@ def lib():
         L.vp_set_denoise_form.argtypes = [C.c_int]
         L.vp_render_frames_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_int, C.c_float]
+        L.vp_render_frames_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_relight.argtypes = [C.c_void_p] * 3 + [C.POINTER(C.c_float)] * 2 + [C.c_int, C.c_float]
+        L.vp_reserve_frames_groups.argtypes = [C.POINTER(Param), C.c_int]
+        L.vp_groups_frames_per_launch.argtypes = [C.POINTER(Param), C.c_int]
+        L.vp_test_groups_census.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.vp_read_counters.argtypes = [C.POINTER(Counters), C.c_int]
         L.vp_render_time_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
         L.vp_get_bound_table.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 5
@@ -431,6 +437,32 @@ def composite(dst_ptr, fg_ptr, trans_ptr, n, s, plate_ptr=None, plate_rgb=None):
     plate_rgb where plate_ptr is None"""
     rgb = (C.c_float * 3)(*[float(v) for v in plate_rgb]) if plate_rgb is not None else None
     _chk(lib().vp_composite(dst_ptr, fg_ptr, trans_ptr, plate_ptr, rgb, n, s))
+
+
+def render_frames_groups(sun_ptr, sky_ptr, first, n, P):
+    """the frames of render_frames as two light groups (vp_render_frames_groups): what the sun lights sums into sun_ptr, what the sky
+    lights into sky_ptr; both carry the heat channel in w"""
+    _chk(lib().vp_render_frames_groups(sun_ptr, sky_ptr, first, n, C.byref(P)))
+
+
+def relight(dst_ptr, sun_ptr, sky_ptr, n, s, sun_gain=(1.0, 1.0, 1.0), sky_gain=(1.0, 1.0, 1.0)):
+    """dst.c = (sun.c * s) * sun_gain[c] + (sky.c * s) * sky_gain[c], dst.w = sun.w * s (vp_relight); in place is allowed"""
+    gs = (C.c_float * 3)(*[float(v) for v in sun_gain])
+    gk = (C.c_float * 3)(*[float(v) for v in sky_gain])
+    _chk(lib().vp_relight(dst_ptr, sun_ptr, sky_ptr, gs, gk, n, s))
+
+
+def reserve_frames_groups(P, nframes):
+    """reserve_frames for a coming render_frames_groups job: two staging planes per frame (vp_reserve_frames_groups)"""
+    _chk(lib().vp_reserve_frames_groups(C.byref(P), int(nframes)))
+
+
+def groups_frames_per_launch(P, planes=2):
+    """the frames one staged launch holds for this image now: planes = 1 render_frames, 2 render_frames_groups (vp_groups_frames_per_launch)"""
+    n = lib().vp_groups_frames_per_launch(C.byref(P), int(planes))
+    if n < 0:
+        _chk(n)
+    return n
 
 
 def scale_by_count(dst_ptr, src_ptr, stats_ptr, n, s):
@@ -743,6 +775,17 @@ def launch_census(unit, kind, reset=False):
     launches, built = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
     _chk(lib().vp_test_launch_census(unit, kind, _p(launches), _p(built), n, int(reset)))
     return {census_name(kind, i): int(launches[i]) for i in np.flatnonzero(built)}
+
+
+def groups_census(reset=False):
+    """launch_census for the table a render_frames_groups launch goes through: {name: launches since the last reset} for every groups
+    instance of render_k the exact unit compiles (vp_test_groups_census); needs no device"""
+    n = lib().vp_test_groups_census(None, None, 0, 0)
+    if n < 0:
+        _chk(n)
+    launches, built = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+    _chk(lib().vp_test_groups_census(_p(launches), _p(built), n, int(reset)))
+    return {census_name(CENSUS_RENDER, i): int(launches[i]) for i in np.flatnonzero(built)}
 
 
 def test_rng(mode, x, y, frame, n, key=(0, 0)):

@@ -383,6 +383,48 @@ int vp_last_denoise_form(void);
 int vp_render_frames_layers(vp_float4* d_fg, vp_float4* d_trans, int first_frame, int n_frames, const Param* p);
 int vp_composite(vp_float4* dst, const vp_float4* fg, const vp_float4* trans, const vp_float4* plate, const float plate_rgb[3], int size, float scale);
 
+/* Light groups: the sun's light and the sky's light of one render in separate accumulators, to be weighted
+ * against each other afterwards.  The integrator is linear in its lights: the sun's power enters a sample only as a factor of each
+ * shadow-ray term, the environment only once, where the path ends; with the passive environment neither influences a draw.
+ *
+ * vp_render_frames_groups.  Take the sample (x, y, frame) that vp_render_frames computes: same path, same draws, same streams.  Let R
+ * be the radiance the path has summed from its sun shadow rays when it ends, E the term its end adds -- thr o background(dir, depth)
+ * if the path leaves for the environment, otherwise nothing --, b the brightness and heat the fourth channel.  vp_render_frames
+ * writes (max(b (R + E), 0), heat).  This call writes
+ *   E is the sun disc's value (background at depth 0 inside the disc):
+ *                 sun sample (max(b (R + E), 0), heat)        sky sample (0, 0, 0, heat)
+ *   otherwise:    sun sample (max(b R, 0), heat)              sky sample (max(b E, 0), heat); a path with no E: (0, 0, 0, heat)
+ * with the operations of the beauty sample in its order (the sky sample's sum starts from +0 as the path's does).  Both caller-owned
+ * accumulators (width * height float4 each, not the same buffer) receive their samples per pixel in frame order, like
+ * vp_render_frames' accumulator.  Equivalently, wherever the path's throughput is finite: the sun accumulator is bit for bit what
+ * vp_render_frames renders on the same scene with every environment texel (0, 0, 0), the sky accumulator what it renders after
+ * set_sun(dir, (0, 0, 0)).  Where a throughput is not finite (0 * inf in such a render) the in-kernel form above is the definition.
+ *   Obeys vp_set_shard, vp_set_estimator, vp_set_rng and vp_set_subpixel (every value each), every volume format, cell order and LDS
+ *   form of the brick table.  It runs kernel instances of its own, built in the exact arithmetic only; vp_render_frames' kernels
+ *   carry no code for it.  The call stops look-ahead batches, waits for pipelined launches and runs staged on the context's stream,
+ *   for one frame too, in two staging planes: a launch holds half the frames a vp_render_frames launch holds
+ *   (vp_reserve_frames_groups sizes the staging for it).  It leaves nothing behind: a vp_render_frames call after it renders the
+ *   bits it rendered before.
+ *   Refused before anything is launched and before the device is touched, with VP_E_ARG: NULL pointers, d_sun == d_sky,
+ *   n_frames <= 0, first_frame < 0; with VP_E_STATE: VP_ENV_MIS (the environment is sampled as a light there: another estimator),
+ *   scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST.  Both buffers are then untouched.  Other errors as
+ *   vp_render_frames.
+ *   Not built: groups combined with layers in one call; statistics, adaptive rounds or vp_denoise on groups; reducing groups across
+ *   processes.
+ *
+ * vp_relight, the output stage: for i < size and each channel c of x, y, z, in binary32, one rounding per operation, no contraction,
+ *   a = (sun[i].c * scale) * sun_gain[c]     k = (sky[i].c * scale) * sky_gain[c]     dst[i].c = a + k     dst[i].w = sun[i].w * scale
+ * scale is 1 / frames.  dst may be sun or sky.  Needs no scene; runs asynchronously on the context's stream.  VP_E_ARG: NULL dst,
+ * sun, sky or either gain, size < 0.
+ *
+ * vp_reserve_frames_groups: vp_reserve_frames for a coming vp_render_frames_groups job (two planes per frame, one-frame calls too).
+ * vp_groups_frames_per_launch: the frames one staged launch of this context holds for this image now, with planes = 1
+ * (vp_render_frames) or 2 (vp_render_frames_groups); negative: an error code. */
+int vp_render_frames_groups(vp_float4* d_sun, vp_float4* d_sky, int first_frame, int n_frames, const Param* p);
+int vp_relight(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const float sun_gain[3], const float sky_gain[3], int size, float scale);
+int vp_reserve_frames_groups(const Param* p, int n_frames);
+int vp_groups_frames_per_launch(const Param* p, int planes);
+
 typedef struct
 {
     uint64_t samples;
@@ -555,6 +597,10 @@ int vp_test_sun_start(int n, const float* origin_xyz, const float* sun_dir, cons
  * majorant), 1 approach_local_k, 2 approach_local_tab_k (the segment table's); QUANT is 1 for walks 0 and 2.
  * VP_E_ARG for another unit or kind, or a count that is not the table length. */
 int vp_test_launch_census(int unit, int kind, uint32_t* launches, uint8_t* built, size_t count, int reset);
+/* vp_test_groups_census: the same for the table a vp_render_frames_groups launch goes through (the exact unit's; render_k's index and
+ * length, 10368), counted apart from the kinds above.  With both arrays NULL the call returns the length; VP_E_ARG for a count that is
+ * not the length.  Needs no device. */
+int vp_test_groups_census(uint32_t* launches, uint8_t* built, size_t count, int reset);
 int vp_test_rng(int mode, uint32_t x, uint32_t y, uint32_t frame, uint32_t k0, uint32_t k1, int n, float* out);
 int vp_test_sample_density(const float* pos_xyz, float* out, int n);
 /* component hooks for known-answer tests against float64 closed forms (no oracle involved):

@@ -52,7 +52,11 @@ def parse(text):
                 break
         # render_k's twelfth argument (LYR: a layers instance) is not part of the name here, so that HALF
         # stays the last one: a plain instance drops it, a layers instance is listed as render_k[layers]<...>
-        if "render_k<" in d and d.count(",") == 11:
+        # (the thirteenth, GRP: a light-groups instance, section 2.7, likewise -- render_k[groups]<...>)
+        if "render_k<" in d and d.count(",") == 12:
+            d, grp = d.rsplit(", ", 1)
+            d = (d if grp == "false>" else d.replace("render_k<", "render_k[groups]<")) + ">"
+        if "render_k" in d and d.count(",") == 11:
             d, lyr = d.rsplit(", ", 1)
             d = (d if lyr == "false>" else d.replace("render_k<", "render_k[layers]<")) + ">"
         out[d] = rows[n]
@@ -68,6 +72,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--parent", default=None)
 ap.add_argument("--log", nargs="*", default=None)
 ap.add_argument("--parent-log", nargs="*", default=None)
+ap.add_argument("--groups", action="store_true", help="list the light-groups instances of render_k beside their plain twins instead of the binary16 ones")
 a = ap.parse_args()
 new = parse("".join(open(f, errors="replace").read() for f in a.log) if a.log else remarks(ROOT))
 old = None
@@ -83,6 +88,18 @@ if old:
             changed += 1
             print("# CHANGED", n, "|", fmt(o), "->", fmt(v))
     print(f"# instances of the other checkout whose registers, spills, scratch, occupancy or LDS changed: {changed}")
+if a.groups:
+    short = lambda v: "VGPR %3s SGPR %3s spill %s/%s scratch %s occ %s" % (v["VGPRs"], v["TotalSGPRs"], v["SGPRs Spill"], v["VGPRs Spill"], v["ScratchSize [bytes/lane]"],
+                                                                           v["Occupancy [waves/SIMD]"])
+    grp = [n for n in new if n.startswith("render_k[groups]<")]
+    more = lower = 0
+    for n in grp:
+        v, t = new[n], new[n.replace("render_k[groups]<", "render_k<")]
+        more += int(v["VGPRs"]) > int(t["VGPRs"]) or int(v["ScratchSize [bytes/lane]"]) > int(t["ScratchSize [bytes/lane]"])
+        lower += int(v["Occupancy [waves/SIMD]"]) < int(t["Occupancy [waves/SIMD]"])
+        print(f"{n} | {short(v)} | plain twin {short(t)}")
+    print(f"# {len(grp)} groups instances; with more registers or scratch than the plain twin: {more}; with a lower occupancy: {lower}")
+    raise SystemExit(0)
 more, occ = 0, 0
 for n in half:
     v, t = new[n], new[re.sub(r", true>$", ", false>", n)]
