@@ -257,8 +257,14 @@ struct StatsDev
     unsigned adaptive;      // 1: evaluate the criterion and set VP_STATS_FROZEN; 0: `flags` is neither read nor written
     unsigned min_frames;
     double   tol, fl;
+    PixelStatsDev* plane2;  // a groups or layers call with statistics: the records of the second plane (sky, trans); `stats` is the first plane's
 };
 void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st);
+// the reduces of a groups and of a layers launch (above) with one record per plane and pixel: each plane's sample, as its accumulator
+// receives it, goes into that plane's record by the definition of vp_pixel_stats; `flags` is neither read nor written
+void launch_reduce_groups_stats(const LaunchDev& L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, hipStream_t st);
+void launch_reduce_layers_stats(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats, PixelStatsDev* trans_stats,
+                                hipStream_t st);
 // the pixels of the class-ordered list src (n[0] general, n[1] light, n[2] box-missing) whose record is not frozen, in src's order,
 // class by class, into d_out (room for all of src), and their three counts into d_totals; d_block_counts[3 * compact_blocks(n)] scratch
 inline unsigned compact_blocks(unsigned n) { return (n + 1023u) / 1024u; }

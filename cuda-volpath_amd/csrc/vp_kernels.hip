@@ -605,6 +605,71 @@ __global__ __launch_bounds__(256) void reduce_stats_k(LaunchDev L, StatsDev T)
     rec->sum_y = sy; rec->sum_y2 = sy2; rec->n = n;
     if (T.adaptive && n >= T.min_frames && stats_converged(sy, sy2, n, T.tol, T.fl)) rec->flags |= 1u;   // VP_STATS_FROZEN
 }
+// ---- statistics on planes (include/volpath.h vp_render_frames_groups_stats / vp_render_frames_layers_stats): reduce_groups_k's and
+// reduce_layers_k's jobs with one record per plane and pixel.  The definition's step, once: the sample v that a plane's accumulator
+// receives adds its luminance to that plane's record (w never enters it).  One read and one write per record; `flags` is not touched.
+__device__ __forceinline__ void stats_add_sample(double& sy, double& sy2, const float4& v)
+{
+    const double y = (double)stats_luminance(v);
+    sy  = sy + y;
+    sy2 = sy2 + y * y;
+}
+__device__ __forceinline__ void stats_store(PixelStatsDev* rec, double sy, double sy2, unsigned nframes)
+{
+    const unsigned n = rec->n + nframes;
+    rec->sum_y = sy; rec->sum_y2 = sy2; rec->n = n;
+}
+__global__ __launch_bounds__(256) void reduce_groups_stats_k(LaunchDev L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats)
+{
+    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.nslots) return;
+    unsigned pix = L.pixels[slot];
+    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
+    float4   a = L.out[idx], k = sky[idx];
+    double   ay = sun_stats[idx].sum_y, ay2 = sun_stats[idx].sum_y2, ky = sky_stats[idx].sum_y, ky2 = sky_stats[idx].sum_y2;
+    const bool   constant = slot >= L.const_from;   // (a constant of the launch: the first row of either plane, added nframes times)
+    const size_t stride   = constant ? 0 : L.stage_stride;
+    for (int f = 0; f < L.nframes; f++)
+    {
+        const float4 v = L.stage[(size_t)f * stride + slot], w = L.groups[(size_t)f * stride + slot];
+        a = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
+        k = make_float4(k.x + w.x, k.y + w.y, k.z + w.z, k.w + w.w);
+        stats_add_sample(ay, ay2, v);
+        stats_add_sample(ky, ky2, w);
+    }
+    L.out[idx] = a;
+    sky[idx]   = k;
+    stats_store(sun_stats + idx, ay, ay2, (unsigned)L.nframes);
+    stats_store(sky_stats + idx, ky, ky2, (unsigned)L.nframes);
+}
+// (layers: the samples are those add_layer_sample adds -- the fg sample of an unscattered path is (0, 0, 0, heat), its trans sample
+// (x, y, z, 1); a scattered path's are the staged word and (0, 0, 0, 0))
+__device__ __forceinline__ void add_layer_sample_stats(float4& a, float4& t, double& ay, double& ay2, double& ty, double& ty2, const float4 v, bool unmarked)
+{
+    const bool   through = unmarked || __builtin_signbit(v.w);
+    const float4 fg = through ? make_float4(0.0f, 0.0f, 0.0f, __builtin_fabsf(v.w)) : v;
+    const float4 tr = through ? make_float4(v.x, v.y, v.z, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    add_layer_sample(a, t, v, unmarked);
+    stats_add_sample(ay, ay2, fg);
+    stats_add_sample(ty, ty2, tr);
+}
+__global__ __launch_bounds__(256) void reduce_layers_stats_k(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats,
+                                                             PixelStatsDev* trans_stats)
+{
+    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.nslots) return;
+    unsigned pix = L.pixels[slot];
+    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
+    float4   a = L.out[idx], t = trans[idx];
+    double   ay = fg_stats[idx].sum_y, ay2 = fg_stats[idx].sum_y2, ty = trans_stats[idx].sum_y, ty2 = trans_stats[idx].sum_y2;
+    const bool   unmarked = slot >= light_from && slot < light_to;
+    const size_t stride   = slot >= L.const_from ? 0 : L.stage_stride;
+    for (int f = 0; f < L.nframes; f++) add_layer_sample_stats(a, t, ay, ay2, ty, ty2, L.stage[(size_t)f * stride + slot], unmarked);
+    L.out[idx] = a;
+    trans[idx] = t;
+    stats_store(fg_stats + idx, ay, ay2, (unsigned)L.nframes);
+    stats_store(trans_stats + idx, ty, ty2, (unsigned)L.nframes);
+}
 // A stable compaction of a class-ordered pixel list (src: n[0] general, n[1] light, n[2] box-missing pixels) by the FROZEN bit of the
 // pixels' records: the active pixels of each class in the order they have in src, class by class, and the three counts.  The pattern of
 // pixlist_*_k: per-block class counts, pixlist_scan_k over them, the scatter with wave-ballot ranks.
@@ -1566,6 +1631,15 @@ void launch_relight(float4* dst, const float4* sun, const float4* sky, float3 su
 void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st)
 {
     hipLaunchKernelGGL(reduce_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, T);
+}
+void launch_reduce_groups_stats(const LaunchDev& L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, hipStream_t st)
+{
+    hipLaunchKernelGGL(reduce_groups_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky, sun_stats, sky_stats);
+}
+void launch_reduce_layers_stats(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats, PixelStatsDev* trans_stats,
+                                hipStream_t st)
+{
+    hipLaunchKernelGGL(reduce_layers_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, trans, light_from, light_to, fg_stats, trans_stats);
 }
 void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PixelStatsDev* stats, unsigned* d_block_counts,
                            unsigned* d_totals, unsigned* d_out, hipStream_t st)

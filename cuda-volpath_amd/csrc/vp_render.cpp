@@ -223,7 +223,7 @@ struct LaunchPlan
     Target     T;                 // where its launches run: the caller's stream, the look-ahead slot handed in, or a pipeline slot
     bool       lookahead;         // ... a look-ahead batch (cancellable, never one of the caller's timed launches)
     bool       stage_only;        // ... which is staged whole and not reduced
-    const StatsDev* stats;        // the reduce also takes the statistics
+    const StatsDev* stats;        // the reduce also takes the statistics (of both planes of a layers or groups call: StatsDev::plane2)
     float4*    layers;            // a layers call (vp_render_frames_layers): the transmittance accumulator; the reduce splits the samples (reduce_layers_k)
     float4*    groups;            // a light-groups call (vp_render_frames_groups): the sky accumulator; a launch stages two planes (reduce_groups_k)
     size_t planes() const { return groups ? 2u : 1u; }   // staging planes per frame
@@ -567,7 +567,9 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
     if (!L.stage || A.stage_only) return VP_OK;
     if (A.piped)
         if (int rc = pipe_await_launch(A.slot, A.T.stream)) return rc;
-    if (A.stats)
+    if (A.stats && A.groups) launch_reduce_groups_stats(L, A.groups, A.stats->stats, A.stats->plane2, G.stream);
+    else if (A.stats && A.layers) launch_reduce_layers_stats(L, A.layers, A.PL.n_general, A.integrated_end(), A.stats->stats, A.stats->plane2, G.stream);
+    else if (A.stats)
     {
         // (an adaptive round that the staging cap splits into several launches: the criterion is the ROUND's, evaluated in its
         // last launch -- a record frozen on a part of the round would stay frozen)
@@ -615,7 +617,10 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     if (!G.wait_lanes_set && G.rng == VP_RNG_SAMPLERH && G.trk == VP_TRACK_SPECTRAL) L.wait_lanes = 24;
     if (sh.per_frame == 0) return VP_OK;
     if ((lists || stats || d_trans || d_sky) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics, layers or groups");
-    if ((d_trans || d_sky) && (lists || stats)) return fail(VP_E_ARG, "a layers or groups call renders the cached lists without statistics");
+    // (statistics on planes -- vp_render_frames_groups_stats / _layers_stats -- bring one record buffer per plane and never a criterion)
+    if ((d_trans || d_sky) && lists) return fail(VP_E_ARG, "a layers or groups call renders the cached lists");
+    if (stats && (!stats->plane2 != !(d_trans || d_sky) || (stats->plane2 && stats->adaptive)))
+        return fail(VP_E_ARG, "statistics on planes: one record buffer per plane of a layers or groups call, without adaptive rounds");
     if (d_trans && d_sky) return fail(VP_E_ARG, "layers and light groups in one call are not built");
     LaunchPlan A = {};
     A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats; A.layers = (float4*)d_trans; A.groups = (float4*)d_sky;
@@ -671,6 +676,32 @@ static int await_launches(bool lookahead, bool aux)
     return VP_OK;
 }
 
+// Compositing layers (include/volpath.h): the call's samples are vp_render_frames' -- same plan, lists, tables, walks and kernels, with
+// LaunchDev::layers set --, staged on the caller's stream whatever the frame count, and reduce_layers_k splits them into the two
+// accumulators.  What the switch is not built for is refused before anything is launched (and before the device is asked for).
+// Light groups (include/volpath.h): the same call with the environment's term of every sample kept apart -- render_k's GRP instances
+// and the groups forms of the constant writers stage it in a second plane (LaunchDev::groups), reduce_groups_k adds the two planes into
+// the two accumulators.  Refusals likewise.
+// Either with statistics (the _stats calls): the same launches, and the reduce also folds each plane's samples into that plane's records
+// (reduce_layers_stats_k, reduce_groups_stats_k); r0 / r1 are then the two record buffers, else null.
+struct PlaneCall { const char* fn; const char* why_mis; bool groups, with_stats; };
+static int plane_call(const PlaneCall& c, vp_float4* d0, vp_float4* d1, vp_pixel_stats* r0, vp_pixel_stats* r1, int first_frame, int n_frames, const Param* p)
+{
+    if (!d0 || !d1 || d0 == d1 || !p || n_frames <= 0 || first_frame < 0 || (c.with_stats && (!r0 || !r1 || r0 == r1))) return fail(VP_E_ARG, "%s: bad arguments", c.fn);
+    if (G.env_mis) return fail(VP_E_STATE, "%s is defined for passive environment lighting only (VP_ENV_MIS: %s)", c.fn, c.why_mis);
+    if (G.trk) return fail(VP_E_STATE, "%s is built for spectral tracking only", c.fn);
+    if (G.count) return fail(VP_E_STATE, "%s is not built for work counters", c.fn);
+    if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "%s is built for the exact arithmetic only (its kernel instances are the exact unit's)", c.fn);
+    int rc = ensure_device();
+    if (rc) return rc;
+    // the call is serial and runs on the caller's stream: look-ahead batches stop, pipelined launches are waited for
+    if ((rc = la_quiesce())) return rc;
+    StatsDev T = {};
+    T.stats = (PixelStatsDev*)r0; T.plane2 = (PixelStatsDev*)r1;
+    return do_render(d0, first_frame, n_frames, p, false, nullptr, nullptr, c.with_stats ? &T : nullptr, c.groups ? nullptr : d1, c.groups ? d1 : nullptr);
+}
+static const char kLayersMis[] = "scattered paths never see the sky", kGroupsMis[] = "the environment is sampled as a light, another estimator";
+
 }  // namespace vph
 
 using namespace vph;
@@ -680,36 +711,23 @@ int vp_render_frames(vp_float4* d_output, int first_frame, int n_frames, const P
 {
     return do_render(d_output, first_frame, n_frames, p);
 }
-// Compositing layers (include/volpath.h): the call's samples are vp_render_frames' -- same plan, lists, tables, walks and kernels, with
-// LaunchDev::layers set --, staged on the caller's stream whatever the frame count, and reduce_layers_k splits them into the two
-// accumulators.  What the switch is not built for is refused before anything is launched (and before the device is asked for).
 int vp_render_frames_layers(vp_float4* d_fg, vp_float4* d_trans, int first_frame, int n_frames, const Param* p)
 {
-    if (!d_fg || !d_trans || d_fg == d_trans || !p || n_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "vp_render_frames_layers: bad arguments");
-    if (G.env_mis) return fail(VP_E_STATE, "vp_render_frames_layers is defined for passive environment lighting only (VP_ENV_MIS: scattered paths never see the sky)");
-    if (G.trk) return fail(VP_E_STATE, "vp_render_frames_layers is built for spectral tracking only");
-    if (G.count) return fail(VP_E_STATE, "vp_render_frames_layers is not built for work counters");
-    if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "vp_render_frames_layers is built for the exact arithmetic only (its kernel instances are the exact unit's)");
-    int rc = ensure_device();
-    if (rc) return rc;
-    // the call is serial and runs on the caller's stream: look-ahead batches stop, pipelined launches are waited for
-    if ((rc = la_quiesce())) return rc;
-    return do_render(d_fg, first_frame, n_frames, p, false, nullptr, nullptr, nullptr, d_trans);
+    return plane_call({"vp_render_frames_layers", kLayersMis, false, false}, d_fg, d_trans, nullptr, nullptr, first_frame, n_frames, p);
 }
-// Light groups (include/volpath.h): the same call with the environment's term of every sample kept apart -- render_k's GRP instances
-// and the groups forms of the constant writers stage it in a second plane (LaunchDev::groups), reduce_groups_k adds the two planes into
-// the two accumulators.  Refusals as above.
 int vp_render_frames_groups(vp_float4* d_sun, vp_float4* d_sky, int first_frame, int n_frames, const Param* p)
 {
-    if (!d_sun || !d_sky || d_sun == d_sky || !p || n_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "vp_render_frames_groups: bad arguments");
-    if (G.env_mis) return fail(VP_E_STATE, "vp_render_frames_groups is defined for passive environment lighting only (VP_ENV_MIS: the environment is sampled as a light, another estimator)");
-    if (G.trk) return fail(VP_E_STATE, "vp_render_frames_groups is built for spectral tracking only");
-    if (G.count) return fail(VP_E_STATE, "vp_render_frames_groups is not built for work counters");
-    if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "vp_render_frames_groups is built for the exact arithmetic only (its kernel instances are the exact unit's)");
-    int rc = ensure_device();
-    if (rc) return rc;
-    if ((rc = la_quiesce())) return rc;
-    return do_render(d_sun, first_frame, n_frames, p, false, nullptr, nullptr, nullptr, nullptr, d_sky);
+    return plane_call({"vp_render_frames_groups", kGroupsMis, true, false}, d_sun, d_sky, nullptr, nullptr, first_frame, n_frames, p);
+}
+int vp_render_frames_layers_stats(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stats* d_fg_stats, vp_pixel_stats* d_trans_stats, int first_frame, int n_frames,
+                                  const Param* p)
+{
+    return plane_call({"vp_render_frames_layers_stats", kLayersMis, false, true}, d_fg, d_trans, d_fg_stats, d_trans_stats, first_frame, n_frames, p);
+}
+int vp_render_frames_groups_stats(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, int first_frame, int n_frames,
+                                  const Param* p)
+{
+    return plane_call({"vp_render_frames_groups_stats", kGroupsMis, true, true}, d_sun, d_sky, d_sun_stats, d_sky_stats, first_frame, n_frames, p);
 }
 int vp_relight(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const float sun_gain[3], const float sky_gain[3], int size, float scale)
 {

@@ -358,8 +358,9 @@ struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss;
 // subset of them (vp_adaptive.cpp).  stats: the reduce also takes the statistics of include/volpath.h (launch_reduce_stats); such a
 // call is staged even for one frame and runs on the caller's stream, not on a pipeline slot.  d_trans: a layers call
 // (vp_render_frames_layers) -- d_out is the foreground accumulator, d_trans the transmittance accumulator; staged and on the caller's
-// stream likewise, with the cached lists and without statistics.  d_sky: a light-groups call (vp_render_frames_groups) -- d_out is the
-// sun accumulator, d_sky the sky accumulator; staged in two planes, otherwise as a layers call (never both).
+// stream likewise, with the cached lists.  d_sky: a light-groups call (vp_render_frames_groups) -- d_out is the
+// sun accumulator, d_sky the sky accumulator; staged in two planes, otherwise as a layers call (never both).  A layers or groups call
+// with statistics (the _stats calls) brings both planes' records in `stats` (StatsDev::plane2), never a criterion and never lists.
 int  do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only = false, const Target* tgt = nullptr,
                const PixelLists* lists = nullptr, const StatsDev* stats = nullptr, vp_float4* d_trans = nullptr, vp_float4* d_sky = nullptr);
 // the preconditions of a render call, each caller with the subset it needs (p: the image checks; last_frame: the opacity rule)

@@ -58,6 +58,14 @@ static void usage()
            "                                                sun * sun-gain + sky * sky-gain per channel (vp_relight; gains default to 1 1 1).\n"
            "                                                One GPU; not with --noise, --denoise or --layers-out / --over; spectral, --env\n"
            "                                                passive, --arith exact\n"
+           "               [--groups-denoise] [--layers-denoise]\n"
+           "                                                with --groups-out / a gain flag, or with --layers-out / --over: the frames go\n"
+           "                                                through vp_render_frames_groups_stats / vp_render_frames_layers_stats (the same\n"
+           "                                                accumulator bits, one record buffer per plane) and each plane is filtered by\n"
+           "                                                vp_denoise with its own records as guide (--denoise-radius, --denoise-patch and\n"
+           "                                                --denoise-k apply).  The PREFIX files are then the denoised means, --out their\n"
+           "                                                vp_relight / vp_composite; w is never filtered, so coverage stays exact.  One GPU;\n"
+           "                                                not with --noise or --denoise\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -89,6 +97,7 @@ int main(int argc, char** argv)
     std::string groups_out;
     bool        relit = false;
     float       sun_gain[3] = {1.0f, 1.0f, 1.0f}, sky_gain[3] = {1.0f, 1.0f, 1.0f};
+    bool        groups_denoise = false, layers_denoise = false;
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -197,6 +206,8 @@ int main(int argc, char** argv)
             }
             relit = true;
         }
+        else if (a == "--groups-denoise") groups_denoise = true;
+        else if (a == "--layers-denoise") layers_denoise = true;
         else if (a == "--sun") { need(2); sunx = (float)atof(argv[++i]); suny = (float)atof(argv[++i]); }
         else if (a == "--batch") { need(1); batch = atoi(argv[++i]); }
         else if (a == "--out") { need(1); out = argv[++i]; }
@@ -237,6 +248,25 @@ int main(int argc, char** argv)
         return 2;
     }
     const bool layers = over || !layers_out.empty();
+    const bool groups = relit || !groups_out.empty();
+    // the per-plane filters: each needs its plane flag, one GPU, and neither the beauty image's filter nor adaptive rounds
+    for (int k = 0; k < 2; k++)
+    {
+        const char* flag = k ? "--layers-denoise" : "--groups-denoise";
+        if (!(k ? layers_denoise : groups_denoise)) continue;
+        if (!(k ? layers : groups))
+        {
+            fprintf(stderr, "%s needs %s: it filters the planes of a %s render\n", flag, k ? "--layers-out or --over" : "--groups-out, --sun-gain or --sky-gain", k ? "layers" : "light-groups");
+            return 2;
+        }
+        if (gpus > 1 || adaptive || denoise)
+        {
+            fprintf(stderr, "%s with %s: per-plane records are not reduced across ranks, adaptive rounds on planes are not built, and --denoise filters the beauty image; "
+                    "use one GPU without --noise and --denoise\n", flag, gpus > 1 ? "--gpus" : adaptive ? "--noise" : "--denoise");
+            return 2;
+        }
+    }
+    const bool plane_denoise = groups_denoise || layers_denoise;
     if (layers && (gpus > 1 || adaptive || denoise))
     {
         fprintf(stderr, "--layers-out / --over with %s: layers are not reduced across ranks and carry no per-pixel statistics; use one GPU without --noise and --denoise\n",
@@ -248,7 +278,6 @@ int main(int argc, char** argv)
         fprintf(stderr, "--layers-out / --over need spectral tracking, --env passive and --arith exact\n");
         return 2;
     }
-    const bool groups = relit || !groups_out.empty();
     if (groups && (gpus > 1 || adaptive || denoise || layers))
     {
         fprintf(stderr, "--groups-out / --sun-gain / --sky-gain with %s: light groups are not reduced across ranks, carry no per-pixel statistics and are not combined with layers; "
@@ -379,6 +408,20 @@ int main(int argc, char** argv)
         trans = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
         if (!trans || vp_memset(trans, 0, (size_t)npix * sizeof(vp_float4))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
     }
+    // --groups-denoise / --layers-denoise: one record buffer per plane (`stats` the first plane's), and the two denoised means
+    vp_pixel_stats* stats2 = nullptr;
+    vp_float4*      mean[2] = {nullptr, nullptr};
+    if (plane_denoise)
+    {
+        stats  = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
+        stats2 = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
+        for (vp_float4*& m2 : mean) m2 = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+        if (!stats || !stats2 || !mean[0] || !mean[1] || vp_memset(stats, 0, (size_t)npix * sizeof(vp_pixel_stats)) || vp_memset(stats2, 0, (size_t)npix * sizeof(vp_pixel_stats)))
+        {
+            fprintf(stderr, "%s\n", vp_last_error());
+            return 1;
+        }
+    }
     for (int s = adaptive ? spp : 0; s < spp;)
     {
         if (!have_opacity && est == VP_EST_DECOMP && (s > 10 || (batch > 0 && s + batch > 11)))
@@ -389,13 +432,13 @@ int main(int argc, char** argv)
         if (layers)
         {
             const int n = batch > 0 ? std::min(batch, spp - s) : 1;
-            if (vp_render_frames_layers(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            if (layers_denoise ? vp_render_frames_layers_stats(accum[0], trans, stats, stats2, s, n, &P) : vp_render_frames_layers(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
             s += n;
         }
         else if (groups)
         {
             const int n = batch > 0 ? std::min(batch, spp - s) : 1;
-            if (vp_render_frames_groups(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            if (groups_denoise ? vp_render_frames_groups_stats(accum[0], trans, stats, stats2, s, n, &P) : vp_render_frames_groups(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
             s += n;
         }
         else if (denoise)
@@ -452,7 +495,30 @@ int main(int argc, char** argv)
     use(0);
     bool  hdr = out.size() > 4 && out.substr(out.size() - 4) == ".hdr";
     Image image(W, H);
-    if (layers)
+    if (plane_denoise)
+    {
+        // each plane filtered with its own records as guide: two MEAN images (the division by the count is part of vp_denoise; w is
+        // never filtered), written in place of the raw means and combined with scale 1
+        const bool        lay = layers_denoise;
+        const std::string prefix = lay ? layers_out : groups_out;
+        for (int k = 0; k < 2; k++)
+        {
+            if (vp_denoise(mean[k], k ? trans : accum[0], k ? stats2 : stats, nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            if (prefix.empty()) continue;
+            const std::string name = prefix + (lay ? (k ? "_trans.hdr" : "_fg.hdr") : (k ? "_sky.hdr" : "_sun.hdr"));
+            vp_download(image.buffer(), mean[k], (size_t)npix * sizeof(vp_float4));
+            image.dump_hdr(name.c_str());
+            printf("wrote %s\n", name.c_str());
+        }
+        if (lay ? (over && vp_composite(disp, mean[0], mean[1], nullptr, over_rgb, npix, 1.0f)) : vp_relight(disp, mean[0], mean[1], sun_gain, sky_gain, npix, 1.0f))
+        {
+            fprintf(stderr, "%s\n", vp_last_error());
+            return 1;
+        }
+        if (!hdr && (!lay || over)) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
+        printf("denoised per plane: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
+    }
+    else if (layers)
     {
         // the two mean layers as they are; the composite over --over's colour in place of the beauty image
         if (!layers_out.empty())
@@ -524,6 +590,8 @@ int main(int argc, char** argv)
         vp_free(d_noise);
     }
     if (stats) vp_free(stats);
+    if (stats2) vp_free(stats2);
+    for (vp_float4* m2 : mean) if (m2) vp_free(m2);
     if (trans) vp_free(trans);
     vp_free(disp);
     for (int r = 0; r < gpus; r++)

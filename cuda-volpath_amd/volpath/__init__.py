@@ -35,6 +35,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_denoise", "vp_set_denoise_form", "vp_last_denoise_form",
                  "vp_render_frames_layers", "vp_composite",
                  "vp_render_frames_groups", "vp_relight", "vp_reserve_frames_groups", "vp_groups_frames_per_launch", "vp_test_groups_census",
+                 "vp_render_frames_groups_stats", "vp_render_frames_layers_stats",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -144,6 +145,8 @@ def lib():
         L.vp_reserve_frames_groups.argtypes = [C.POINTER(Param), C.c_int]
         L.vp_groups_frames_per_launch.argtypes = [C.POINTER(Param), C.c_int]
         L.vp_test_groups_census.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        L.vp_render_frames_groups_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_render_frames_layers_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_read_counters.argtypes = [C.POINTER(Counters), C.c_int]
         L.vp_render_time_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
         L.vp_get_bound_table.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 5
@@ -450,6 +453,17 @@ def relight(dst_ptr, sun_ptr, sky_ptr, n, s, sun_gain=(1.0, 1.0, 1.0), sky_gain=
     gs = (C.c_float * 3)(*[float(v) for v in sun_gain])
     gk = (C.c_float * 3)(*[float(v) for v in sky_gain])
     _chk(lib().vp_relight(dst_ptr, sun_ptr, sky_ptr, gs, gk, n, s))
+
+
+def render_frames_groups_stats(sun_ptr, sky_ptr, sun_stats_ptr, sky_stats_ptr, first, n, P):
+    """render_frames_groups that also adds every sample's luminance to its pixel's record of the sample's group
+    (vp_render_frames_groups_stats): the same accumulator bits, one StatsBuffer per group"""
+    _chk(lib().vp_render_frames_groups_stats(sun_ptr, sky_ptr, sun_stats_ptr, sky_stats_ptr, first, n, C.byref(P)))
+
+
+def render_frames_layers_stats(fg_ptr, trans_ptr, fg_stats_ptr, trans_stats_ptr, first, n, P):
+    """render_frames_layers likewise (vp_render_frames_layers_stats): the same accumulator bits, one StatsBuffer per layer"""
+    _chk(lib().vp_render_frames_layers_stats(fg_ptr, trans_ptr, fg_stats_ptr, trans_stats_ptr, first, n, C.byref(P)))
 
 
 def reserve_frames_groups(P, nframes):

@@ -374,7 +374,8 @@ int vp_last_denoise_form(void);
  *   Refused before anything is launched and before the device is touched, with VP_E_ARG: NULL pointers, d_fg == d_trans,
  *   n_frames <= 0, first_frame < 0; with VP_E_STATE: VP_ENV_MIS (scattered paths never see the sky there: another definition),
  *   scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST.  Both buffers are then untouched.  Other errors as vp_render_frames.
- *   Statistics, adaptive rounds and vp_denoise on layers, and reducing layers across processes, are not built.
+ *   This call takes no statistics (vp_render_frames_layers_stats below does); adaptive rounds on layers, and reducing layers across
+ *   processes, are not built.
  *
  * vp_composite, the output stage: for i < size, with B = plate[i].xyz where plate is non-NULL, else plate_rgb[0..2],
  *   dst[i].xyz = fg[i].xyz * scale + (trans[i].xyz * scale) * B        dst[i].w = 1 - trans[i].w * scale   (coverage)
@@ -410,7 +411,8 @@ int vp_composite(vp_float4* dst, const vp_float4* fg, const vp_float4* trans, co
  *   scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST.  Both buffers are then untouched.  Other errors as
  *   vp_render_frames.
  *   Not built: groups combined with layers in one call; statistics, adaptive rounds or vp_denoise on groups; reducing groups across
- *   processes.
+ *   processes.  (Of THIS call: it writes no records.  vp_render_frames_groups_stats, below, is the same render with one record buffer
+ *   per group, which is what vp_denoise needs.)
  *
  * vp_relight, the output stage: for i < size and each channel c of x, y, z, in binary32, one rounding per operation, no contraction,
  *   a = (sun[i].c * scale) * sun_gain[c]     k = (sky[i].c * scale) * sky_gain[c]     dst[i].c = a + k     dst[i].w = sun[i].w * scale
@@ -424,6 +426,43 @@ int vp_render_frames_groups(vp_float4* d_sun, vp_float4* d_sky, int first_frame,
 int vp_relight(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const float sun_gain[3], const float sky_gain[3], int size, float scale);
 int vp_reserve_frames_groups(const Param* p, int n_frames);
 int vp_groups_frames_per_launch(const Param* p, int planes);
+
+/* Statistics on planes: vp_render_frames_groups and vp_render_frames_layers with one buffer of per-pixel
+ * records per plane, so that each plane can be filtered by vp_denoise with its own noise estimate as guide.
+ *
+ * vp_render_frames_groups_stats / vp_render_frames_layers_stats.  THE DEFINITION:
+ *   The two accumulators end bit-identical to what vp_render_frames_groups / vp_render_frames_layers write with the same arguments
+ *   and state.  Each record buffer holds width * height vp_pixel_stats, caller-owned and caller-zeroed (vp_memset), indexed like the
+ *   accumulators.  For every sample v that the call adds to a PLANE's accumulator at pixel i, record i of THAT plane receives exactly
+ *   what vp_render_frames_stats defines:
+ *     y = (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z      in binary32, no contraction
+ *     sum_y  += (double)y        sum_y2 += (double)y * (double)y        n += 1
+ *   per pixel in frame order.  v is the sample as the underlying call's definition names it, not a staged word: for an unscattered
+ *   path of a layers call the fg sample is (0, 0, 0, heat), so its y is +0, and the trans sample is (max(thr, 0), 1), whose y comes
+ *   from its RGB; a scattered path gives the trans record y = 0.  w never enters a luminance.  Every owned pixel's two records gain
+ *   n_frames in n -- the per-pixel-constant classes (box-missing pixels, a light class written as constants) included, and theirs are
+ *   n_frames sequential additions, never a product.  `flags` is neither read nor written.  Only the records of the pixels this
+ *   context owns (vp_set_shard) are touched.  There is no hidden state: a second call continues a first one, records and accumulators
+ *   carry over, and a job that the staging cap splits into several launches gives the bits of one launch.
+ *   Equivalently, wherever the path's throughput is finite (as for vp_render_frames_groups): the sun records are bit for bit what
+ *   vp_render_frames_stats leaves on the same scene with every environment texel (0, 0, 0), the sky records what it leaves after
+ *   set_sun(dir, (0, 0, 0)).
+ *   Everything else is as the underlying call: it obeys vp_set_shard, vp_set_estimator, vp_set_rng and vp_set_subpixel, every volume
+ *   format and LDS form; it runs staged on the context's stream, for one frame too; it stops look-ahead batches and waits for
+ *   pipelined launches; it leaves no per-context state behind.  The render launches are the underlying call's own; only the reduce
+ *   that adds the staged samples differs.  A groups call needs the two-plane staging: vp_reserve_frames_groups serves it unchanged.
+ *   Refused before the device is touched, all four buffers untouched, with VP_E_ARG: any NULL pointer, d_sun == d_sky
+ *   (d_fg == d_trans), the two record pointers equal, n_frames <= 0, first_frame < 0; with VP_E_STATE exactly where the underlying
+ *   call gives it (VP_ENV_MIS, scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST).
+ *   Still not built: adaptive rounds on planes (which plane's record would freeze a pixel is a design question of its own), groups
+ *   combined with layers, and reducing planes or their records across processes.
+ * The pipeline these calls exist for: the _stats call, then per plane vp_denoise(dst, plane, plane's records, NULL, NULL, ...) -- a
+ * MEAN image each --, then vp_relight or vp_composite of the two means with scale 1.  vp_denoise never filters w, so a layers
+ * composite keeps its exact coverage. */
+int vp_render_frames_groups_stats(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats,
+                                  int first_frame, int n_frames, const Param* p);
+int vp_render_frames_layers_stats(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stats* d_fg_stats, vp_pixel_stats* d_trans_stats,
+                                  int first_frame, int n_frames, const Param* p);
 
 typedef struct
 {

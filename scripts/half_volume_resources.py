@@ -1,7 +1,7 @@
 """registers, scratch and occupancy of the binary16 kernel instances beside their float twins, and of every other kernel against another
 checkout (no GPU needed):
 
-    python scripts/half_volume_resources.py [--parent DIR_OF_ANOTHER_CHECKOUT] [--log FILE ...] [--parent-log FILE ...]
+    python scripts/half_volume_resources.py [--parent DIR_OF_ANOTHER_CHECKOUT] [--log FILE ...] [--parent-log FILE ...] [--groups | --list REGEX]
 
 Compiles csrc/vp_kernels.hip and csrc/vp_kernels_fast.hip for gfx950 with -Rpass-analysis=kernel-resource-usage (minutes), or reads
 the remarks of such a compilation from --log / --parent-log.  A binary16 instance is one whose last template argument, HALF, is true;
@@ -73,6 +73,7 @@ ap.add_argument("--parent", default=None)
 ap.add_argument("--log", nargs="*", default=None)
 ap.add_argument("--parent-log", nargs="*", default=None)
 ap.add_argument("--groups", action="store_true", help="list the light-groups instances of render_k beside their plain twins instead of the binary16 ones")
+ap.add_argument("--list", default=None, metavar="REGEX", help="list the kernels whose name matches instead (e.g. 'reduce_': the add-kernels of a staged launch)")
 a = ap.parse_args()
 new = parse("".join(open(f, errors="replace").read() for f in a.log) if a.log else remarks(ROOT))
 old = None
@@ -88,6 +89,13 @@ if old:
             changed += 1
             print("# CHANGED", n, "|", fmt(o), "->", fmt(v))
     print(f"# instances of the other checkout whose registers, spills, scratch, occupancy or LDS changed: {changed}")
+if a.list:
+    hits = [n for n in new if re.search(a.list, n)]
+    for n in hits:
+        print(f"{n} | {fmt(new[n])}" + ("" if old is None or n in old else "   NEW"))
+    spills = sum(int(new[n]["ScratchSize [bytes/lane]"]) > 0 or int(new[n]["VGPRs Spill"]) > 0 or int(new[n]["SGPRs Spill"]) > 0 for n in hits)
+    print(f"# {len(hits)} kernels match {a.list!r}; with scratch or spills: {spills}")
+    raise SystemExit(0)
 if a.groups:
     short = lambda v: "VGPR %3s SGPR %3s spill %s/%s scratch %s occ %s" % (v["VGPRs"], v["TotalSGPRs"], v["SGPRs Spill"], v["VGPRs Spill"], v["ScratchSize [bytes/lane]"],
                                                                            v["Occupancy [waves/SIMD]"])
