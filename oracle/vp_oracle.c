@@ -794,6 +794,17 @@ static int subnormal_component(f3 t)
         }                                                                     \
     } while (0)
 
+/* test hook: samples whose throughput was not finite when the path ended (a non-finite component stays non-finite).  The equivalent
+ * forms of include/volpath.h's plane calls hold only where it is finite: fmaxf turns the NaN of such a sample's sum into 0, so the
+ * values do not show it (tests/planes_fuzz_lib.py leaves a case with such a sample out) */
+static uint64_t g_nonfinite_throughput = 0;
+uint64_t vpo_debug_nonfinite_throughput(void) { return __atomic_load_n(&g_nonfinite_throughput, __ATOMIC_RELAXED); }
+#define NOTE_NONFINITE(t)                                                                                                       \
+    do                                                                                                                          \
+    {                                                                                                                           \
+        if (!(isfinite((t).x) && isfinite((t).y) && isfinite((t).z))) __atomic_fetch_add(&g_nonfinite_throughput, 1, __ATOMIC_RELAXED); \
+    } while (0)
+
 /* test hook: how often the zero-pdf `continue` of the MIS block was taken (it needs a draw of exactly 0) */
 static uint64_t g_mis_zero_pdf = 0;
 uint64_t vpo_debug_mis_zero_pdf(void) { return __atomic_load_n(&g_mis_zero_pdf, __ATOMIC_RELAXED); }
@@ -1035,6 +1046,7 @@ static void sample_decomp(const vpo_scene* S, const vpo_param* P, uint32_t x, ui
         cr_d = new_dir;
     }
 
+    NOTE_NONFINITE(throughput);
     radiance = muls(radiance, brightness);
     out[0] = fmaxf(radiance.x, 0.0f);
     out[1] = fmaxf(radiance.y, 0.0f);
@@ -1154,6 +1166,7 @@ static void sample_bounded(const vpo_scene* S, const vpo_param* P, uint32_t x, u
         cr_d = new_dir;
     }
 
+    NOTE_NONFINITE(throughput);
     radiance = muls(radiance, brightness);
     out[0] = fmaxf(radiance.x, 0.0f);
     out[1] = fmaxf(radiance.y, 0.0f);
@@ -1261,6 +1274,7 @@ static void sample_global(const vpo_scene* S, const vpo_param* P, uint32_t x, ui
         cr_o = pos;
         cr_d = new_dir;
     }
+    NOTE_NONFINITE(throughput);
     radiance = muls(radiance, brightness);
     out[0] = fmaxf(radiance.x, 0.0f);
     out[1] = fmaxf(radiance.y, 0.0f);
@@ -1402,6 +1416,7 @@ static void sample_scalar(const vpo_scene* S, const vpo_param* P, uint32_t x, ui
         cr_d = new_dir;
         if (est != VPO_EST_DECOMP) i++;
     }
+    NOTE_NONFINITE(throughput);
     radiance = muls(radiance, brightness);
     float heat = est == VPO_EST_DECOMP ? (float)num_scatters : (float)((double)i * 0.001);
     if (S->track_mode == 2)
@@ -1478,6 +1493,25 @@ void vpo_render_frame(const vpo_scene* S, const vpo_param* P, int frame, float* 
         C->env_lookups += tot.env_lookups; C->scatters += tot.scatters; C->rng_draws += tot.rng_draws;
         C->control_segments += tot.control_segments;
     }
+}
+
+/* one frame, every sample on its own: vpo_render_sample for each pixel, nothing accumulated (tests/planes_fuzz_lib.py) */
+void vpo_render_samples(const vpo_scene* S, const vpo_param* P, int frame, float* out, vpo_counters* cnt, int threads)
+{
+#ifdef _OPENMP
+    if (threads <= 0) threads = omp_get_max_threads();
+#else
+    (void)threads;
+#endif
+    int W = (int)P->width, H = (int)P->height;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++)
+        {
+            size_t i = (size_t)x + (size_t)y * W;
+            memset(&cnt[i], 0, sizeof cnt[i]);
+            vpo_render_sample(S, P, x, y, frame, out + 4 * i, &cnt[i]);
+        }
 }
 
 /* -------------------------------------------- A10: _precompute_opacity -- */

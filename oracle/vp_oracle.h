@@ -111,6 +111,9 @@ void vpo_render_frame(const vpo_scene* S, const vpo_param* P, int frame, float* 
 /* one (x,y,frame) sample, returned instead of accumulated */
 void vpo_render_sample(const vpo_scene* S, const vpo_param* P, int x, int y, int frame, float out[4],
                        vpo_counters* C);
+/* vpo_render_sample for every pixel of frame `frame`: out[4 * (x + y*W)] and cnt[x + y*W] (zeroed here) hold each sample's own
+ * value and counters; nothing is accumulated.  threads<=0: all. */
+void vpo_render_samples(const vpo_scene* S, const vpo_param* P, int frame, float* out, vpo_counters* cnt, int threads);
 
 /* building blocks (each cites the reference lines it follows in vp_oracle.c) */
 uint32_t vpo_hash(uint32_t seed);
@@ -138,6 +141,7 @@ void     vpo_debug_set_what_if(int mask); /* test hook: variants of the restatem
 uint64_t vpo_debug_shadow_overflow(void); /* test hook: shadow rays that drew more than the 2^20 pairs of their sub-stream (must stay 0) */
 uint64_t vpo_debug_mis_zero_pdf(void); /* test hook: zero-pdf `continue`s taken so far (kernel.cu:2266) */
 uint64_t vpo_debug_subnormal_throughput(void); /* test hook: samples whose throughput had a nonzero subnormal component at a collision */
+uint64_t vpo_debug_nonfinite_throughput(void); /* test hook: samples whose throughput was not finite when the path ended */
 uint64_t vpo_debug_hg_nan_clamp(void); /* test hook: phase-function samples whose cos(theta) was a NaN before the clamp (g = 1, a draw of 0) */
 void     vpo_eval_envmap(const vpo_scene* S, const float dir[3], float rgb[3]);
 void     vpo_hg_sample(float g, const float n[3], float u0, float u1, float out[3]);

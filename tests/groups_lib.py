@@ -32,9 +32,10 @@ def scenes_for(oracle, grid, env, sun_dir, sun_power, **kw):
     return real, sun, sky
 
 
-def sample(real, sun, sky, P, x, y, frame):
-    """(sun sample, sky sample, the real scene's sample, its counters) of one (x, y, frame)"""
-    v, cnt = real.render_sample(P, x, y, frame)
+def sample(real, sun, sky, P, x, y, frame, base=None):
+    """(sun sample, sky sample, the real scene's sample, its counters) of one (x, y, frame); base: the real scene's (sample, counters)
+    where the caller has them already"""
+    v, cnt = real.render_sample(P, x, y, frame) if base is None else base
     out = []
     for twin in (sun, sky):
         t, tc = twin.render_sample(P, x, y, frame)

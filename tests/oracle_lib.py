@@ -52,6 +52,9 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+COUNTERS_DTYPE = np.dtype([(n, np.uint64) for n, _ in Counters._fields_])
+
+
 def build():
     subprocess.check_call(["make", "-s", "-C", ORACLE_DIR, "libvp_oracle.so"])
 
@@ -78,6 +81,7 @@ def lib():
         L.vpo_debug_shadow_overflow.restype = C.c_uint64
         L.vpo_debug_subnormal_throughput.restype = C.c_uint64
         L.vpo_debug_hg_nan_clamp.restype = C.c_uint64
+        L.vpo_debug_nonfinite_throughput.restype = C.c_uint64
         L.vpo_hg_sample.argtypes = [C.c_float, C.c_float * 3, C.c_float, C.c_float, C.c_float * 3]
         L.vpo_debug_set_what_if.argtypes = [C.c_int]
         L.vpo_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
@@ -228,6 +232,13 @@ class OracleScene:
         cnt = Counters()
         lib().vpo_render_sample(C.byref(self.S), C.byref(P), x, y, frame, out, C.byref(cnt))
         return np.array(out[:], np.float32), cnt
+
+    def render_samples(self, P, frame, threads=0):
+        """render_sample for every pixel of one frame, in C: ((H, W, 4) float32, (H, W) array of COUNTERS_DTYPE)"""
+        out = np.empty((P.height, P.width, 4), np.float32)
+        cnt = np.empty((P.height, P.width), COUNTERS_DTYPE)
+        lib().vpo_render_samples(C.byref(self.S), C.byref(P), frame, _p(out), _p(cnt), threads or DEFAULT_THREADS)
+        return out, cnt
 
 
 def env_tables_pdf(env):
