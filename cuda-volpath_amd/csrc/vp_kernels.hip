@@ -33,6 +33,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 
 #include "vp_device.h"
@@ -607,19 +608,37 @@ __global__ __launch_bounds__(256) void reduce_stats_k(LaunchDev L, StatsDev T)
 }
 // ---- statistics on planes (include/volpath.h vp_render_frames_groups_stats / vp_render_frames_layers_stats): reduce_groups_k's and
 // reduce_layers_k's jobs with one record per plane and pixel.  The definition's step, once: the sample v that a plane's accumulator
-// receives adds its luminance to that plane's record (w never enters it).  One read and one write per record; `flags` is not touched.
+// receives adds its luminance to that plane's record (w never enters it).  One read and one write per record; `flags` is not touched
+// -- except by the adaptive form of either reduce (the last launch of a round of vp_render_adaptive_groups / _layers), which sets bit 0.
 __device__ __forceinline__ void stats_add_sample(double& sy, double& sy2, const float4& v)
 {
     const double y = (double)stats_luminance(v);
     sy  = sy + y;
     sy2 = sy2 + y * y;
 }
-__device__ __forceinline__ void stats_store(PixelStatsDev* rec, double sy, double sy2, unsigned nframes)
+__device__ __forceinline__ unsigned stats_store(PixelStatsDev* rec, double sy, double sy2, unsigned nframes)
 {
     const unsigned n = rec->n + nframes;
     rec->sum_y = sy; rec->sum_y2 = sy2; rec->n = n;
+    return n;
 }
-__global__ __launch_bounds__(256) void reduce_groups_stats_k(LaunchDev L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats)
+// The adaptive form of the two reduces (include/volpath.h vp_render_adaptive_groups / _layers; the last launch of a round): both records
+// of the pixel are frozen iff each has its min_frames and meets vp_render_adaptive's criterion with its own n, tolerance and floor.
+// ADAPT false: the plain _stats reduce, which neither reads nor writes `flags` (nothing of C is looked at).  The bodies take L by value,
+// as the kernels do: by reference the plain instances' scalar registers moved.
+template <bool ADAPT>
+__device__ __forceinline__ void stats_freeze_planes(const PlaneCriterionDev& C, PixelStatsDev* r0, double y0, double y02, unsigned n0, PixelStatsDev* r1, double y1,
+                                                    double y12, unsigned n1)
+{
+    if constexpr (ADAPT)
+        if (n0 >= C.min_frames && n1 >= C.min_frames && stats_converged(y0, y02, n0, C.tol[0], C.fl[0]) && stats_converged(y1, y12, n1, C.tol[1], C.fl[1]))
+        {
+            r0->flags |= 1u;   // VP_STATS_FROZEN, in both
+            r1->flags |= 1u;
+        }
+}
+template <bool ADAPT>
+__device__ __forceinline__ void reduce_groups_stats_body(LaunchDev L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, const PlaneCriterionDev& C)
 {
     unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= L.nslots) return;
@@ -639,8 +658,17 @@ __global__ __launch_bounds__(256) void reduce_groups_stats_k(LaunchDev L, float4
     }
     L.out[idx] = a;
     sky[idx]   = k;
-    stats_store(sun_stats + idx, ay, ay2, (unsigned)L.nframes);
-    stats_store(sky_stats + idx, ky, ky2, (unsigned)L.nframes);
+    const unsigned n0 = stats_store(sun_stats + idx, ay, ay2, (unsigned)L.nframes);
+    const unsigned n1 = stats_store(sky_stats + idx, ky, ky2, (unsigned)L.nframes);
+    stats_freeze_planes<ADAPT>(C, sun_stats + idx, ay, ay2, n0, sky_stats + idx, ky, ky2, n1);
+}
+__global__ __launch_bounds__(256) void reduce_groups_stats_k(LaunchDev L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats)
+{
+    reduce_groups_stats_body<false>(L, sky, sun_stats, sky_stats, PlaneCriterionDev{});
+}
+__global__ __launch_bounds__(256) void reduce_groups_stats_adaptive_k(LaunchDev L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PlaneCriterionDev C)
+{
+    reduce_groups_stats_body<true>(L, sky, sun_stats, sky_stats, C);
 }
 // (layers: the samples are those add_layer_sample adds -- the fg sample of an unscattered path is (0, 0, 0, heat), its trans sample
 // (x, y, z, 1); a scattered path's are the staged word and (0, 0, 0, 0))
@@ -653,8 +681,9 @@ __device__ __forceinline__ void add_layer_sample_stats(float4& a, float4& t, dou
     stats_add_sample(ay, ay2, fg);
     stats_add_sample(ty, ty2, tr);
 }
-__global__ __launch_bounds__(256) void reduce_layers_stats_k(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats,
-                                                             PixelStatsDev* trans_stats)
+template <bool ADAPT>
+__device__ __forceinline__ void reduce_layers_stats_body(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats,
+                                                         PixelStatsDev* trans_stats, const PlaneCriterionDev& C)
 {
     unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= L.nslots) return;
@@ -667,8 +696,19 @@ __global__ __launch_bounds__(256) void reduce_layers_stats_k(LaunchDev L, float4
     for (int f = 0; f < L.nframes; f++) add_layer_sample_stats(a, t, ay, ay2, ty, ty2, L.stage[(size_t)f * stride + slot], unmarked);
     L.out[idx] = a;
     trans[idx] = t;
-    stats_store(fg_stats + idx, ay, ay2, (unsigned)L.nframes);
-    stats_store(trans_stats + idx, ty, ty2, (unsigned)L.nframes);
+    const unsigned n0 = stats_store(fg_stats + idx, ay, ay2, (unsigned)L.nframes);
+    const unsigned n1 = stats_store(trans_stats + idx, ty, ty2, (unsigned)L.nframes);
+    stats_freeze_planes<ADAPT>(C, fg_stats + idx, ay, ay2, n0, trans_stats + idx, ty, ty2, n1);
+}
+__global__ __launch_bounds__(256) void reduce_layers_stats_k(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats,
+                                                             PixelStatsDev* trans_stats)
+{
+    reduce_layers_stats_body<false>(L, trans, light_from, light_to, fg_stats, trans_stats, PlaneCriterionDev{});
+}
+__global__ __launch_bounds__(256) void reduce_layers_stats_adaptive_k(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats,
+                                                                      PixelStatsDev* trans_stats, PlaneCriterionDev C)
+{
+    reduce_layers_stats_body<true>(L, trans, light_from, light_to, fg_stats, trans_stats, C);
 }
 // A stable compaction of a class-ordered pixel list (src: n[0] general, n[1] light, n[2] box-missing pixels) by the FROZEN bit of the
 // pixels' records: the active pixels of each class in the order they have in src, class by class, and the three counts.  The pattern of
@@ -680,16 +720,27 @@ struct CompactDev
     unsigned width;
     const PixelStatsDev* stats;
 };
-__device__ __forceinline__ unsigned compact_slot(const CompactDev& D, unsigned s, unsigned& pix)
+// ... with the second plane's records of an adaptive plane call: a slot is dropped if EITHER record is frozen (a descriptor of its own,
+// so that the one-record kernels keep their kernel arguments and registers: profiles/adaptive_planes_kernel_resources.txt)
+struct CompactPlanesDev : CompactDev
+{
+    const PixelStatsDev* stats2;
+};
+template <class Dev>
+__device__ __forceinline__ unsigned compact_slot(const Dev& D, unsigned s, unsigned& pix)
 {
     // class of slot s of src (3 = beyond the list, or frozen) and its pixel
     pix = 0;
     if (s >= D.n[0] + D.n[1] + D.n[2]) return 3u;
     pix = D.src[s];
-    if (D.stats[(size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * D.width].flags & 1u) return 3u;
+    const size_t idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * D.width;
+    if (D.stats[idx].flags & 1u) return 3u;
+    if constexpr (std::is_same<Dev, CompactPlanesDev>::value)
+        if (D.stats2[idx].flags & 1u) return 3u;
     return s < D.n[0] ? 0u : s < D.n[0] + D.n[1] ? 1u : 2u;
 }
-__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_count_k(CompactDev D, unsigned* block_counts)
+template <class Dev>
+__device__ __forceinline__ void compact_count_body(const Dev& D, unsigned* block_counts)
 {
     __shared__ unsigned cnt[3];
     if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
@@ -704,7 +755,11 @@ __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_count_k(CompactDev D
     __syncthreads();
     if (threadIdx.x < 3) block_counts[3 * blockIdx.x + threadIdx.x] = cnt[threadIdx.x];
 }
-__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_write_k(CompactDev D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
+// (compact_*_k: one record buffer, vp_render_adaptive's; compact_planes_*_k: the two of an adaptive plane call)
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_count_k(CompactDev D, unsigned* block_counts) { compact_count_body(D, block_counts); }
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes_count_k(CompactPlanesDev D, unsigned* block_counts) { compact_count_body(D, block_counts); }
+template <class Dev>
+__device__ __forceinline__ void compact_write_body(const Dev& D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
 {
     __shared__ unsigned wave_cnt[VP_PIXLIST_BLOCK / 64][3];
     unsigned pix;
@@ -724,6 +779,14 @@ __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_write_k(CompactDev D
     const unsigned class_base = c == 0 ? 0u : c == 1 ? totals[0] : totals[0] + totals[1];
     // (at most as many active pixels as src holds: `out` has room for all of src)
     out[class_base + block_offsets[3 * blockIdx.x + c] + before + rank_in_wave] = pix;
+}
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_write_k(CompactDev D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
+{
+    compact_write_body(D, block_offsets, totals, out);
+}
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes_write_k(CompactPlanesDev D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
+{
+    compact_write_body(D, block_offsets, totals, out);
 }
 // the output stage of a render with per-pixel sample counts: dst = src * (scale / n), a correctly rounded binary32 divide; n = 0 gives 0
 __global__ void scale_by_count_k(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float scale)
@@ -1632,24 +1695,31 @@ void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st)
 {
     hipLaunchKernelGGL(reduce_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, T);
 }
-void launch_reduce_groups_stats(const LaunchDev& L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, hipStream_t st)
+void launch_reduce_groups_stats(const LaunchDev& L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, const PlaneCriterionDev* C, hipStream_t st)
 {
-    hipLaunchKernelGGL(reduce_groups_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky, sun_stats, sky_stats);
+    const dim3 grid((L.nslots + 255) / 256);
+    if (C) hipLaunchKernelGGL(reduce_groups_stats_adaptive_k, grid, dim3(256), 0, st, L, sky, sun_stats, sky_stats, *C);
+    else hipLaunchKernelGGL(reduce_groups_stats_k, grid, dim3(256), 0, st, L, sky, sun_stats, sky_stats);
 }
 void launch_reduce_layers_stats(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats, PixelStatsDev* trans_stats,
-                                hipStream_t st)
+                                const PlaneCriterionDev* C, hipStream_t st)
 {
-    hipLaunchKernelGGL(reduce_layers_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, trans, light_from, light_to, fg_stats, trans_stats);
+    const dim3 grid((L.nslots + 255) / 256);
+    if (C) hipLaunchKernelGGL(reduce_layers_stats_adaptive_k, grid, dim3(256), 0, st, L, trans, light_from, light_to, fg_stats, trans_stats, *C);
+    else hipLaunchKernelGGL(reduce_layers_stats_k, grid, dim3(256), 0, st, L, trans, light_from, light_to, fg_stats, trans_stats);
 }
-void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PixelStatsDev* stats, unsigned* d_block_counts,
-                           unsigned* d_totals, unsigned* d_out, hipStream_t st)
+void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PixelStatsDev* stats, const PixelStatsDev* stats2,
+                           unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st)
 {
-    CompactDev D;
-    D.src = src; D.n[0] = n[0]; D.n[1] = n[1]; D.n[2] = n[2]; D.width = width; D.stats = stats;
+    CompactPlanesDev D;
+    D.src = src; D.n[0] = n[0]; D.n[1] = n[1]; D.n[2] = n[2]; D.width = width; D.stats = stats; D.stats2 = stats2;
     const unsigned nblocks = compact_blocks(n[0] + n[1] + n[2]);
-    hipLaunchKernelGGL(compact_count_k, dim3(nblocks), dim3(VP_PIXLIST_BLOCK), 0, st, D, d_block_counts);
-    hipLaunchKernelGGL(pixlist_scan_k, dim3(1), dim3(VP_PIXLIST_BLOCK), 0, st, d_block_counts, nblocks, d_totals);
-    hipLaunchKernelGGL(compact_write_k, dim3(nblocks), dim3(VP_PIXLIST_BLOCK), 0, st, D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
+    const dim3 grid(nblocks), block(VP_PIXLIST_BLOCK);
+    if (stats2) hipLaunchKernelGGL(compact_planes_count_k, grid, block, 0, st, D, d_block_counts);
+    else hipLaunchKernelGGL(compact_count_k, grid, block, 0, st, (CompactDev)D, d_block_counts);
+    hipLaunchKernelGGL(pixlist_scan_k, dim3(1), block, 0, st, d_block_counts, nblocks, d_totals);
+    if (stats2) hipLaunchKernelGGL(compact_planes_write_k, grid, block, 0, st, D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
+    else hipLaunchKernelGGL(compact_write_k, grid, block, 0, st, (CompactDev)D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
 }
 void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st)
 {

@@ -567,8 +567,15 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
     if (!L.stage || A.stage_only) return VP_OK;
     if (A.piped)
         if (int rc = pipe_await_launch(A.slot, A.T.stream)) return rc;
-    if (A.stats && A.groups) launch_reduce_groups_stats(L, A.groups, A.stats->stats, A.stats->plane2, G.stream);
-    else if (A.stats && A.layers) launch_reduce_layers_stats(L, A.layers, A.PL.n_general, A.integrated_end(), A.stats->stats, A.stats->plane2, G.stream);
+    // (an adaptive round on planes -- vp_adaptive.cpp render_adaptive_planes --: the plain form for every launch but the round's last,
+    // the adaptive form, with the per-plane criterion, for that one; the unmarked range of a layers reduce is the light KERNEL's slots
+    // of the list in use, the caller's included)
+    PlaneCriterionDev C = {};
+    const bool freeze = A.stats && A.stats->plane2 && A.stats->adaptive && last;
+    if (freeze) C = {{A.stats->plane_tol[0], A.stats->plane_tol[1]}, {A.stats->plane_fl[0], A.stats->plane_fl[1]}, A.stats->min_frames};
+    if (A.stats && A.groups) launch_reduce_groups_stats(L, A.groups, A.stats->stats, A.stats->plane2, freeze ? &C : nullptr, G.stream);
+    else if (A.stats && A.layers)
+        launch_reduce_layers_stats(L, A.layers, A.PL.n_general, A.integrated_end(), A.stats->stats, A.stats->plane2, freeze ? &C : nullptr, G.stream);
     else if (A.stats)
     {
         // (an adaptive round that the staging cap splits into several launches: the criterion is the ROUND's, evaluated in its
@@ -617,10 +624,12 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     if (!G.wait_lanes_set && G.rng == VP_RNG_SAMPLERH && G.trk == VP_TRACK_SPECTRAL) L.wait_lanes = 24;
     if (sh.per_frame == 0) return VP_OK;
     if ((lists || stats || d_trans || d_sky) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics, layers or groups");
-    // (statistics on planes -- vp_render_frames_groups_stats / _layers_stats -- bring one record buffer per plane and never a criterion)
-    if ((d_trans || d_sky) && lists) return fail(VP_E_ARG, "a layers or groups call renders the cached lists");
-    if (stats && (!stats->plane2 != !(d_trans || d_sky) || (stats->plane2 && stats->adaptive)))
-        return fail(VP_E_ARG, "statistics on planes: one record buffer per plane of a layers or groups call, without adaptive rounds");
+    // (statistics on planes -- vp_render_frames_groups_stats / _layers_stats -- bring one record buffer per plane; a criterion and the
+    // caller's lists come with the adaptive rounds on planes only: vp_render_adaptive_groups / _layers)
+    if ((d_trans || d_sky) && lists && !(stats && stats->plane2 && stats->adaptive))
+        return fail(VP_E_ARG, "a layers or groups call renders the cached lists, or the active lists of an adaptive round with both planes' records");
+    if (stats && !stats->plane2 != !(d_trans || d_sky))
+        return fail(VP_E_ARG, "statistics on planes: one record buffer per plane of a layers or groups call");
     if (d_trans && d_sky) return fail(VP_E_ARG, "layers and light groups in one call are not built");
     LaunchPlan A = {};
     A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats; A.layers = (float4*)d_trans; A.groups = (float4*)d_sky;
@@ -684,23 +693,29 @@ static int await_launches(bool lookahead, bool aux)
 // the two accumulators.  Refusals likewise.
 // Either with statistics (the _stats calls): the same launches, and the reduce also folds each plane's samples into that plane's records
 // (reduce_layers_stats_k, reduce_groups_stats_k); r0 / r1 are then the two record buffers, else null.
-struct PlaneCall { const char* fn; const char* why_mis; bool groups, with_stats; };
+struct PlaneCall { const char* fn; bool groups, with_stats; };
+static const char kLayersMis[] = "scattered paths never see the sky", kGroupsMis[] = "the environment is sampled as a light, another estimator";
+// the state a plane call is built for, checked before the device is asked for; fn: the entry point the message names
+int plane_state_check(const char* fn, bool groups)
+{
+    if (G.env_mis) return fail(VP_E_STATE, "%s is defined for passive environment lighting only (VP_ENV_MIS: %s)", fn, groups ? kGroupsMis : kLayersMis);
+    if (G.trk) return fail(VP_E_STATE, "%s is built for spectral tracking only", fn);
+    if (G.count) return fail(VP_E_STATE, "%s is not built for work counters", fn);
+    if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "%s is built for the exact arithmetic only (its kernel instances are the exact unit's)", fn);
+    return VP_OK;
+}
 static int plane_call(const PlaneCall& c, vp_float4* d0, vp_float4* d1, vp_pixel_stats* r0, vp_pixel_stats* r1, int first_frame, int n_frames, const Param* p)
 {
     if (!d0 || !d1 || d0 == d1 || !p || n_frames <= 0 || first_frame < 0 || (c.with_stats && (!r0 || !r1 || r0 == r1))) return fail(VP_E_ARG, "%s: bad arguments", c.fn);
-    if (G.env_mis) return fail(VP_E_STATE, "%s is defined for passive environment lighting only (VP_ENV_MIS: %s)", c.fn, c.why_mis);
-    if (G.trk) return fail(VP_E_STATE, "%s is built for spectral tracking only", c.fn);
-    if (G.count) return fail(VP_E_STATE, "%s is not built for work counters", c.fn);
-    if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "%s is built for the exact arithmetic only (its kernel instances are the exact unit's)", c.fn);
-    int rc = ensure_device();
+    int rc = plane_state_check(c.fn, c.groups);
     if (rc) return rc;
+    if ((rc = ensure_device())) return rc;
     // the call is serial and runs on the caller's stream: look-ahead batches stop, pipelined launches are waited for
     if ((rc = la_quiesce())) return rc;
     StatsDev T = {};
     T.stats = (PixelStatsDev*)r0; T.plane2 = (PixelStatsDev*)r1;
     return do_render(d0, first_frame, n_frames, p, false, nullptr, nullptr, c.with_stats ? &T : nullptr, c.groups ? nullptr : d1, c.groups ? d1 : nullptr);
 }
-static const char kLayersMis[] = "scattered paths never see the sky", kGroupsMis[] = "the environment is sampled as a light, another estimator";
 
 }  // namespace vph
 
@@ -713,21 +728,21 @@ int vp_render_frames(vp_float4* d_output, int first_frame, int n_frames, const P
 }
 int vp_render_frames_layers(vp_float4* d_fg, vp_float4* d_trans, int first_frame, int n_frames, const Param* p)
 {
-    return plane_call({"vp_render_frames_layers", kLayersMis, false, false}, d_fg, d_trans, nullptr, nullptr, first_frame, n_frames, p);
+    return plane_call({"vp_render_frames_layers", false, false}, d_fg, d_trans, nullptr, nullptr, first_frame, n_frames, p);
 }
 int vp_render_frames_groups(vp_float4* d_sun, vp_float4* d_sky, int first_frame, int n_frames, const Param* p)
 {
-    return plane_call({"vp_render_frames_groups", kGroupsMis, true, false}, d_sun, d_sky, nullptr, nullptr, first_frame, n_frames, p);
+    return plane_call({"vp_render_frames_groups", true, false}, d_sun, d_sky, nullptr, nullptr, first_frame, n_frames, p);
 }
 int vp_render_frames_layers_stats(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stats* d_fg_stats, vp_pixel_stats* d_trans_stats, int first_frame, int n_frames,
                                   const Param* p)
 {
-    return plane_call({"vp_render_frames_layers_stats", kLayersMis, false, true}, d_fg, d_trans, d_fg_stats, d_trans_stats, first_frame, n_frames, p);
+    return plane_call({"vp_render_frames_layers_stats", false, true}, d_fg, d_trans, d_fg_stats, d_trans_stats, first_frame, n_frames, p);
 }
 int vp_render_frames_groups_stats(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, int first_frame, int n_frames,
                                   const Param* p)
 {
-    return plane_call({"vp_render_frames_groups_stats", kGroupsMis, true, true}, d_sun, d_sky, d_sun_stats, d_sky_stats, first_frame, n_frames, p);
+    return plane_call({"vp_render_frames_groups_stats", true, true}, d_sun, d_sky, d_sun_stats, d_sky_stats, first_frame, n_frames, p);
 }
 int vp_relight(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const float sun_gain[3], const float sky_gain[3], int size, float scale)
 {

@@ -360,12 +360,17 @@ struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss;
 // (vp_render_frames_layers) -- d_out is the foreground accumulator, d_trans the transmittance accumulator; staged and on the caller's
 // stream likewise, with the cached lists.  d_sky: a light-groups call (vp_render_frames_groups) -- d_out is the
 // sun accumulator, d_sky the sky accumulator; staged in two planes, otherwise as a layers call (never both).  A layers or groups call
-// with statistics (the _stats calls) brings both planes' records in `stats` (StatsDev::plane2), never a criterion and never lists.
+// with statistics (the _stats calls) brings both planes' records in `stats` (StatsDev::plane2), without a criterion or lists; an adaptive
+// round on planes (vp_render_adaptive_groups / _layers) brings the records, the per-plane criterion (StatsDev::plane_tol, plane_fl) and the
+// active lists together.
 int  do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only = false, const Target* tgt = nullptr,
                const PixelLists* lists = nullptr, const StatsDev* stats = nullptr, vp_float4* d_trans = nullptr, vp_float4* d_sky = nullptr);
 // the preconditions of a render call, each caller with the subset it needs (p: the image checks; last_frame: the opacity rule)
 enum : unsigned { CHK_STATE = 1, CHK_IMAGE = 2, CHK_IMAGE_NOTE = 4, CHK_MODES = 8, CHK_OPACITY = 16 };
 int  check_render(unsigned what, const Param* p, long long last_frame = 0);
+// VP_E_STATE where a layers (groups: a light-groups) call is not built -- VP_ENV_MIS, scalar or multi-channel tracking, work counters,
+// VP_ARITH_FAST --, the message naming fn; touches no device
+int  plane_state_check(const char* fn, bool groups);
 void trim_events();
 int  pipe_quiesce();   // waits for the pipelined launches in flight; the next one waits for the caller's stream (every change to what launches read)
 // ---- vp_lookahead.cpp

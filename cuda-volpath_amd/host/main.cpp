@@ -66,6 +66,16 @@ static void usage()
            "                                                --denoise-k apply).  The PREFIX files are then the denoised means, --out their\n"
            "                                                vp_relight / vp_composite; w is never filtered, so coverage stays exact.  One GPU;\n"
            "                                                not with --noise or --denoise\n"
+           "               [--plane-noise TOL0 TOL1 [--min-spp N] [--round N] [--plane-noise-out PREFIX]]\n"
+           "                                                with --groups-out / a gain flag, or with --layers-out / --over: adaptive sampling\n"
+           "                                                on the two planes (vp_render_adaptive_groups / vp_render_adaptive_layers).  A pixel\n"
+           "                                                is sampled, in both planes, until the estimated standard error of EACH plane's mean\n"
+           "                                                luminance is at most TOLk x max(mean, floor): TOL0 and a floor of 1e-3 for sun / fg,\n"
+           "                                                TOL1 for sky (floor 1e-3) / trans (floor 1e-2); --min-spp and --round as for\n"
+           "                                                --noise, --spp the maximum.  Each plane is written as sum / n per pixel, --out is\n"
+           "                                                their vp_relight / vp_composite; with --groups-denoise / --layers-denoise the means\n"
+           "                                                are vp_denoise's from the adaptive records.  --plane-noise-out writes one noise map\n"
+           "                                                per plane (PREFIX_sun.hdr ...).  One GPU; not with --noise or --denoise\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -98,6 +108,9 @@ int main(int argc, char** argv)
     bool        relit = false;
     float       sun_gain[3] = {1.0f, 1.0f, 1.0f}, sky_gain[3] = {1.0f, 1.0f, 1.0f};
     bool        groups_denoise = false, layers_denoise = false;
+    bool        plane_adaptive = false;
+    float       plane_tol[2] = {0.0f, 0.0f};
+    std::string plane_noise_out;
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -157,6 +170,18 @@ int main(int argc, char** argv)
             if (end == argv[i] || *end || !(noise_tol >= 0.0f)) { fprintf(stderr, "--noise %s: a tolerance >= 0\n", argv[i]); usage(); return 2; }
             adaptive = true;
         }
+        else if (a == "--plane-noise")
+        {
+            need(2);
+            for (int c = 0; c < 2; c++)
+            {
+                char* end = nullptr;
+                plane_tol[c] = strtof(argv[++i], &end);
+                if (end == argv[i] || *end || !(plane_tol[c] >= 0.0f)) { fprintf(stderr, "--plane-noise %s: two tolerances >= 0\n", argv[i]); usage(); return 2; }
+            }
+            plane_adaptive = true;
+        }
+        else if (a == "--plane-noise-out") { need(1); plane_noise_out = argv[++i]; }
         else if (a == "--min-spp") { need(1); min_spp = atoi(argv[++i]); }
         else if (a == "--round") { need(1); round_frames = atoi(argv[++i]); }
         else if (a == "--noise-out") { need(1); noise_out = argv[++i]; }
@@ -261,12 +286,26 @@ int main(int argc, char** argv)
         }
         if (gpus > 1 || adaptive || denoise)
         {
-            fprintf(stderr, "%s with %s: per-plane records are not reduced across ranks, adaptive rounds on planes are not built, and --denoise filters the beauty image; "
+            fprintf(stderr, "%s with %s: per-plane records are not reduced across ranks, adaptive rounds on planes are --plane-noise's, and --denoise filters the beauty image; "
                     "use one GPU without --noise and --denoise\n", flag, gpus > 1 ? "--gpus" : adaptive ? "--noise" : "--denoise");
             return 2;
         }
     }
     const bool plane_denoise = groups_denoise || layers_denoise;
+    // adaptive rounds on planes: a plane flag, one GPU, and neither the beauty image's rounds nor its filter
+    if (plane_adaptive && !layers && !groups)
+    {
+        fprintf(stderr, "--plane-noise needs --groups-out, --sun-gain or --sky-gain, or --layers-out or --over: it samples the planes of a light-groups or layers render\n");
+        return 2;
+    }
+    if (plane_adaptive && (gpus > 1 || adaptive || denoise))
+    {
+        fprintf(stderr, "--plane-noise with %s: per-plane records are not reduced across ranks, --noise samples the beauty image and --denoise filters it; "
+                "use one GPU without --noise and --denoise\n", gpus > 1 ? "--gpus" : adaptive ? "--noise" : "--denoise");
+        return 2;
+    }
+    if (plane_adaptive && (min_spp < 2 || round_frames < 1)) { fprintf(stderr, "--plane-noise needs --min-spp >= 2 and --round >= 1\n"); usage(); return 2; }
+    if (!plane_adaptive && !plane_noise_out.empty()) { fprintf(stderr, "--plane-noise-out needs --plane-noise\n"); return 2; }
     if (layers && (gpus > 1 || adaptive || denoise))
     {
         fprintf(stderr, "--layers-out / --over with %s: layers are not reduced across ranks and carry no per-pixel statistics; use one GPU without --noise and --denoise\n",
@@ -408,10 +447,11 @@ int main(int argc, char** argv)
         trans = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
         if (!trans || vp_memset(trans, 0, (size_t)npix * sizeof(vp_float4))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
     }
-    // --groups-denoise / --layers-denoise: one record buffer per plane (`stats` the first plane's), and the two denoised means
+    // --groups-denoise / --layers-denoise / --plane-noise: one record buffer per plane (`stats` the first plane's), and the two means
     vp_pixel_stats* stats2 = nullptr;
     vp_float4*      mean[2] = {nullptr, nullptr};
-    if (plane_denoise)
+    const float     plane_floor[2] = {1e-3f, layers ? 1e-2f : 1e-3f};   // (trans lives in [0, 1])
+    if (plane_denoise || plane_adaptive)
     {
         stats  = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
         stats2 = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
@@ -422,7 +462,18 @@ int main(int argc, char** argv)
             return 1;
         }
     }
-    for (int s = adaptive ? spp : 0; s < spp;)
+    if (plane_adaptive)
+    {
+        // rounds on the pixels neither of whose planes has met its tolerance, --spp frames at most
+        if (est == VP_EST_DECOMP && spp > 11) precompute_opacity(&sky.sun_dir.x);   // host.cpp:336-343
+        const vp_adaptive_planes ap = {{plane_tol[0], plane_tol[1]}, {plane_floor[0], plane_floor[1]}, min_spp, round_frames};
+        if ((layers ? vp_render_adaptive_layers : vp_render_adaptive_groups)(accum[0], trans, stats, stats2, 0, spp, &P, &ap, &ares))
+        {
+            fprintf(stderr, "%s\n", vp_last_error());
+            return 1;
+        }
+    }
+    for (int s = adaptive || plane_adaptive ? spp : 0; s < spp;)
     {
         if (!have_opacity && est == VP_EST_DECOMP && (s > 10 || (batch > 0 && s + batch > 11)))
         {
@@ -468,11 +519,14 @@ int main(int argc, char** argv)
     if (gpus > 1 && !reducer.reduce_to_root(ctx, accum, streams, (size_t)npix, rerr)) { fprintf(stderr, "%s\n", rerr.c_str()); return 1; }
     for (int r = gpus - 1; r >= 0; r--) { use(r); vp_synchronize(); }
     double sec = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    if (adaptive)
+    if (adaptive || plane_adaptive)
     {
         const double all = (double)W * H * spp;
-        printf("adaptive: %llu of %.0f samples (%.1f %%), %u rounds of %d frames, %u pixels still above --noise %g after %u frames\n",
-               (unsigned long long)ares.samples, all, 100.0 * (double)ares.samples / all, ares.rounds, round_frames, ares.active_left, noise_tol, ares.frames_used);
+        char what[64];
+        if (adaptive) snprintf(what, sizeof what, "--noise %g", noise_tol);
+        else snprintf(what, sizeof what, "--plane-noise %g %g", plane_tol[0], plane_tol[1]);
+        printf("adaptive: %llu of %.0f samples (%.1f %%), %u rounds of %d frames, %u pixels still above %s after %u frames\n",
+               (unsigned long long)ares.samples, all, 100.0 * (double)ares.samples / all, ares.rounds, round_frames, ares.active_left, what, ares.frames_used);
         printf("%f M samples / s, %d x %d, at most %d spp, %f s\n", (double)ares.samples / sec / 1e6, W, H, spp, sec);
     }
     else printf("%f M samples / s, %d x %d, %d spp, %f s\n", (double)W * H * spp / sec / 1e6, W, H, spp, sec);
@@ -495,15 +549,21 @@ int main(int argc, char** argv)
     use(0);
     bool  hdr = out.size() > 4 && out.substr(out.size() - 4) == ".hdr";
     Image image(W, H);
-    if (plane_denoise)
+    if (plane_denoise || plane_adaptive)
     {
         // each plane filtered with its own records as guide: two MEAN images (the division by the count is part of vp_denoise; w is
         // never filtered), written in place of the raw means and combined with scale 1
-        const bool        lay = layers_denoise;
+        // (--plane-noise without the filter: each plane by its own counts, sum / n per pixel)
+        const bool        lay = layers;
         const std::string prefix = lay ? layers_out : groups_out;
         for (int k = 0; k < 2; k++)
         {
-            if (vp_denoise(mean[k], k ? trans : accum[0], k ? stats2 : stats, nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            if (plane_denoise ? vp_denoise(mean[k], k ? trans : accum[0], k ? stats2 : stats, nullptr, nullptr, W, H, &dn)
+                              : vp_scale_by_count(mean[k], k ? trans : accum[0], k ? stats2 : stats, npix, 1.0f))
+            {
+                fprintf(stderr, "%s\n", vp_last_error());
+                return 1;
+            }
             if (prefix.empty()) continue;
             const std::string name = prefix + (lay ? (k ? "_trans.hdr" : "_fg.hdr") : (k ? "_sky.hdr" : "_sun.hdr"));
             vp_download(image.buffer(), mean[k], (size_t)npix * sizeof(vp_float4));
@@ -516,7 +576,7 @@ int main(int argc, char** argv)
             return 1;
         }
         if (!hdr && (!lay || over)) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
-        printf("denoised per plane: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
+        if (plane_denoise) printf("denoised per plane: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
     }
     else if (layers)
     {
@@ -589,6 +649,24 @@ int main(int argc, char** argv)
         printf("wrote %s\n", noise_out.c_str());
         vp_free(d_noise);
     }
+    if (plane_adaptive && !plane_noise_out.empty())
+        for (int k = 0; k < 2; k++)
+        {
+            // one noise map per plane, each with its plane's floor
+            const std::string name = plane_noise_out + (layers ? (k ? "_trans.hdr" : "_fg.hdr") : (k ? "_sky.hdr" : "_sun.hdr"));
+            float* d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
+            std::vector<float> noise((size_t)npix);
+            if (!d_noise || vp_stats_rel_error(d_noise, k ? stats2 : stats, npix, plane_floor[k]) || vp_download(noise.data(), d_noise, (size_t)npix * sizeof(float)))
+            {
+                fprintf(stderr, "%s\n", vp_last_error());
+                return 1;
+            }
+            Image nm(W, H);
+            for (int q = 0; q < npix; q++) { float* px = nm.buffer() + 4 * (size_t)q; px[0] = px[1] = px[2] = noise[(size_t)q]; px[3] = 1.0f; }
+            nm.dump_hdr(name.c_str());
+            printf("wrote %s\n", name.c_str());
+            vp_free(d_noise);
+        }
     if (stats) vp_free(stats);
     if (stats2) vp_free(stats2);
     for (vp_float4* m2 : mean) if (m2) vp_free(m2);

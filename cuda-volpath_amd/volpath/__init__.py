@@ -36,6 +36,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_frames_layers", "vp_composite",
                  "vp_render_frames_groups", "vp_relight", "vp_reserve_frames_groups", "vp_groups_frames_per_launch", "vp_test_groups_census",
                  "vp_render_frames_groups_stats", "vp_render_frames_layers_stats",
+                 "vp_render_adaptive_groups", "vp_render_adaptive_layers",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -87,6 +88,11 @@ STATS_FROZEN = 1
 class Adaptive(C.Structure):
     """include/volpath.h vp_adaptive"""
     _fields_ = [("rel_tol", C.c_float), ("floor_y", C.c_float), ("min_frames", C.c_int), ("round_frames", C.c_int)]
+
+
+class AdaptivePlanes(C.Structure):
+    """include/volpath.h vp_adaptive_planes: [0] the first plane's (sun / fg), [1] the second's (sky / trans)"""
+    _fields_ = [("rel_tol", C.c_float * 2), ("floor_y", C.c_float * 2), ("min_frames", C.c_int), ("round_frames", C.c_int)]
 
 
 class AdaptiveResult(C.Structure):
@@ -147,6 +153,8 @@ def lib():
         L.vp_test_groups_census.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.vp_render_frames_groups_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_render_frames_layers_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param)]
+        for f in (L.vp_render_adaptive_groups, L.vp_render_adaptive_layers):
+            f.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param), C.POINTER(AdaptivePlanes), C.POINTER(AdaptiveResult)]
         L.vp_read_counters.argtypes = [C.POINTER(Counters), C.c_int]
         L.vp_render_time_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
         L.vp_get_bound_table.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 5
@@ -464,6 +472,26 @@ def render_frames_groups_stats(sun_ptr, sky_ptr, sun_stats_ptr, sky_stats_ptr, f
 def render_frames_layers_stats(fg_ptr, trans_ptr, fg_stats_ptr, trans_stats_ptr, first, n, P):
     """render_frames_layers likewise (vp_render_frames_layers_stats): the same accumulator bits, one StatsBuffer per layer"""
     _chk(lib().vp_render_frames_layers_stats(fg_ptr, trans_ptr, fg_stats_ptr, trans_stats_ptr, first, n, C.byref(P)))
+
+
+def _render_adaptive_planes(fn, p0, p1, s0, s1, first, max_frames, P, rel_tol, floor_y, min_frames, round_frames):
+    a = AdaptivePlanes((C.c_float * 2)(*[float(v) for v in rel_tol]), (C.c_float * 2)(*[float(v) for v in floor_y]), min_frames, round_frames)
+    r = AdaptiveResult()
+    _chk(fn(p0, p1, s0, s1, first, max_frames, C.byref(P), C.byref(a), C.byref(r)))
+    return r.as_dict()
+
+
+def render_adaptive_groups(sun_ptr, sky_ptr, sun_stats_ptr, sky_stats_ptr, first, max_frames, P, rel_tol, floor_y=(1e-3, 1e-3), min_frames=16, round_frames=32):
+    """render_adaptive's rounds on the two light groups (vp_render_adaptive_groups): a pixel is sampled, in both groups, while neither
+    of its records is frozen, and both are frozen once each meets its own (rel_tol[k], floor_y[k]); returns render_adaptive's dict"""
+    return _render_adaptive_planes(lib().vp_render_adaptive_groups, sun_ptr, sky_ptr, sun_stats_ptr, sky_stats_ptr, first, max_frames, P, rel_tol, floor_y,
+                                   min_frames, round_frames)
+
+
+def render_adaptive_layers(fg_ptr, trans_ptr, fg_stats_ptr, trans_stats_ptr, first, max_frames, P, rel_tol, floor_y=(1e-3, 1e-2), min_frames=16, round_frames=32):
+    """the same on the two compositing layers (vp_render_adaptive_layers): [0] the foreground, [1] the transmittance"""
+    return _render_adaptive_planes(lib().vp_render_adaptive_layers, fg_ptr, trans_ptr, fg_stats_ptr, trans_stats_ptr, first, max_frames, P, rel_tol, floor_y,
+                                   min_frames, round_frames)
 
 
 def reserve_frames_groups(P, nframes):

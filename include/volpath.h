@@ -374,8 +374,8 @@ int vp_last_denoise_form(void);
  *   Refused before anything is launched and before the device is touched, with VP_E_ARG: NULL pointers, d_fg == d_trans,
  *   n_frames <= 0, first_frame < 0; with VP_E_STATE: VP_ENV_MIS (scattered paths never see the sky there: another definition),
  *   scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST.  Both buffers are then untouched.  Other errors as vp_render_frames.
- *   This call takes no statistics (vp_render_frames_layers_stats below does); adaptive rounds on layers, and reducing layers across
- *   processes, are not built.
+ *   This call takes no statistics (vp_render_frames_layers_stats below does) and runs no adaptive rounds (vp_render_adaptive_layers
+ *   below does); reducing layers across processes is not built.
  *
  * vp_composite, the output stage: for i < size, with B = plate[i].xyz where plate is non-NULL, else plate_rgb[0..2],
  *   dst[i].xyz = fg[i].xyz * scale + (trans[i].xyz * scale) * B        dst[i].w = 1 - trans[i].w * scale   (coverage)
@@ -410,9 +410,9 @@ int vp_composite(vp_float4* dst, const vp_float4* fg, const vp_float4* trans, co
  *   n_frames <= 0, first_frame < 0; with VP_E_STATE: VP_ENV_MIS (the environment is sampled as a light there: another estimator),
  *   scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST.  Both buffers are then untouched.  Other errors as
  *   vp_render_frames.
- *   Not built: groups combined with layers in one call; statistics, adaptive rounds or vp_denoise on groups; reducing groups across
- *   processes.  (Of THIS call: it writes no records.  vp_render_frames_groups_stats, below, is the same render with one record buffer
- *   per group, which is what vp_denoise needs.)
+ *   Not built: groups combined with layers in one call; reducing groups across processes.  Not part of THIS call, which writes no
+ *   records: statistics, adaptive rounds or vp_denoise on groups.  vp_render_frames_groups_stats, below, is the same render with one
+ *   record buffer per group, which is what vp_denoise needs; vp_render_adaptive_groups, below it, runs the adaptive rounds.
  *
  * vp_relight, the output stage: for i < size and each channel c of x, y, z, in binary32, one rounding per operation, no contraction,
  *   a = (sun[i].c * scale) * sun_gain[c]     k = (sky[i].c * scale) * sky_gain[c]     dst[i].c = a + k     dst[i].w = sun[i].w * scale
@@ -454,8 +454,8 @@ int vp_groups_frames_per_launch(const Param* p, int planes);
  *   Refused before the device is touched, all four buffers untouched, with VP_E_ARG: any NULL pointer, d_sun == d_sky
  *   (d_fg == d_trans), the two record pointers equal, n_frames <= 0, first_frame < 0; with VP_E_STATE exactly where the underlying
  *   call gives it (VP_ENV_MIS, scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST).
- *   Still not built: adaptive rounds on planes (which plane's record would freeze a pixel is a design question of its own), groups
- *   combined with layers, and reducing planes or their records across processes.
+ *   These calls run no adaptive rounds on planes: vp_render_adaptive_groups / vp_render_adaptive_layers of the next section do.  Still
+ *   not built: groups combined with layers, reducing planes or their records across processes, and these calls under VP_ARITH_FAST.
  * The pipeline these calls exist for: the _stats call, then per plane vp_denoise(dst, plane, plane's records, NULL, NULL, ...) -- a
  * MEAN image each --, then vp_relight or vp_composite of the two means with scale 1.  vp_denoise never filters w, so a layers
  * composite keeps its exact coverage. */
@@ -463,6 +463,46 @@ int vp_render_frames_groups_stats(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_s
                                   int first_frame, int n_frames, const Param* p);
 int vp_render_frames_layers_stats(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stats* d_fg_stats, vp_pixel_stats* d_trans_stats,
                                   int first_frame, int n_frames, const Param* p);
+
+/* Adaptive sampling on planes: vp_render_adaptive's rounds on the two planes of a light-groups or a layers
+ * render.  [0] of the parameter arrays is the first plane's (sun / fg), [1] the second's (sky / trans).
+ *
+ * vp_render_adaptive_groups / vp_render_adaptive_layers.  THE DEFINITION:
+ *   A pixel is ACTIVE while the FROZEN bit is clear in BOTH of its records.  The frozen set is exactly what the two caller-owned
+ *   record buffers say: there is no hidden state, so a second call continues a first one.  Rounds are vp_render_adaptive's: with
+ *   B = round_frames, round k covers frames [first_frame + k B, first_frame + min((k + 1) B, max_frames)).  Every owned pixel that is
+ *   active at the start of a round receives all frames of the round in both planes: the samples, accumulators and records are exactly
+ *   those that vp_render_frames_groups_stats / vp_render_frames_layers_stats define for that pixel and those frames, added in frame
+ *   order (the per-pixel-constant classes: sequential additions).  A pixel that is not active receives nothing, in either accumulator
+ *   or record.  After the round each pixel that was active in it is frozen iff, for both k = 0 and k = 1, record k has
+ *   n >= min_frames and vp_render_adaptive's criterion holds on it with (rel_tol[k], floor_y[k]) -- the same binary64 operations in the
+ *   same order, false on NaN, each record with its own n.  Freezing sets the FROZEN bit in both records and changes no other flag
+ *   bit; it is permanent.  The call ends when no owned pixel is active or the frames are used up.  `result` is as in
+ *   vp_render_adaptive; `samples` counts one per pixel and frame, not per plane.  The samples a pixel receives depend on nothing but
+ *   this definition: a round that the staging cap splits into several launches gives the bits of one launch.
+ *   Why AND, and why per plane: the product of these calls is weighted afterwards -- vp_relight's gains, any plate in vp_composite.
+ *   The weights are unknown at render time and the records hold no cross-covariance, so a criterion on the sum would be wrong for every
+ *   other weighting: each plane must be converged by its own measure.  The planes live on different scales (radiance times brightness
+ *   for sun, sky and fg; [0, 1] for trans), hence one tolerance and one floor per plane.  A large floor_y[k] with rel_tol[k] > 0
+ *   (1e30f, say) makes plane k's criterion hold from two samples on, i.e. takes plane k out of the decision: the frozen set is then the
+ *   other plane's own.
+ *   What it is not, as for vp_render_adaptive: the stopping rule looks at the estimate it stops, which gives a small bias.  The image
+ *   of a plane is sum / n per pixel: vp_scale_by_count with THAT plane's records, then vp_relight / vp_composite with scale 1.  The
+ *   exact-parity products stay the uniform calls.
+ *   Refused before the device is touched, all four buffers untouched, with VP_E_ARG: any NULL pointer (result excepted), equal
+ *   accumulators or equal record buffers, max_frames <= 0 or first_frame < 0, min_frames < 2, round_frames < 1, any tolerance or floor
+ *   negative or NaN; with VP_E_STATE exactly where the underlying plane call gives it (VP_ENV_MIS, scalar and multi-channel tracking,
+ *   enabled work counters, VP_ARITH_FAST).  VP_E_NOOPACITY as vp_render_frames gives for frame first_frame + max_frames - 1.
+ *   Everything else is as the underlying plane call: it obeys vp_set_shard, vp_set_estimator, vp_set_rng, vp_set_stream,
+ *   vp_set_subpixel and every volume format; it stops look-ahead batches, waits for pipelined launches and runs on the context's
+ *   stream, reading three counts back per round (it synchronises); it leaves nothing behind -- a vp_render_frames, a plain plane call or
+ *   a vp_render_adaptive after it renders the bits it rendered before -- and never modifies the cached pixel lists.
+ *   Not built: groups combined with layers, reducing planes or records across processes, these calls under VP_ARITH_FAST. */
+typedef struct { float rel_tol[2], floor_y[2]; int min_frames, round_frames; } vp_adaptive_planes;   /* [0]: sun / fg, [1]: sky / trans */
+int vp_render_adaptive_groups(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats,
+                              int first_frame, int max_frames, const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result);
+int vp_render_adaptive_layers(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stats* d_fg_stats, vp_pixel_stats* d_trans_stats,
+                              int first_frame, int max_frames, const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result);
 
 typedef struct
 {
