@@ -785,6 +785,14 @@ int vp_test_groups_census(uint32_t* launches, uint8_t* built, size_t count, int 
     groups_census_read(launches, built, n, reset != 0);   // (host memory only: no device, no context)
     return VP_OK;
 }
+int vp_test_group_layers_census(uint32_t* launches, uint8_t* built, size_t count, int reset)
+{
+    const size_t n = census_size(CENSUS_RENDER);   // (the group-layers table has render_k's index)
+    if (!launches && !built) return (int)n;
+    if (count != n) return fail(VP_E_ARG, "vp_test_group_layers_census: %zu entries given, the table has %zu", count, n);
+    group_layers_census_read(launches, built, n, reset != 0);   // (host memory only: no device, no context)
+    return VP_OK;
+}
 int vp_test_math(int which, const float* in, float* out, int n)
 {
     if (which < 0 || which > 11) return fail(VP_E_ARG, "vp_test_math: unknown helper %d (0..11)", which);

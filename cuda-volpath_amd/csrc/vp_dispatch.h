@@ -15,6 +15,8 @@
 //                      layers_built() states -- only where the kernels above have that argument (VP_RENDER_K_HAS_LAYERS)
 //   launch_groups_instance()  the same for a light-groups launch (LaunchDev::groups): the thirteenth argument, GRP, for the same subset
 //                      (groups_built()) -- only where the kernels above have it (VP_RENDER_K_HAS_GROUPS)
+//   launch_group_layers_instance()  the same for a group-layers launch (both fields set): LYR and GRP together, the same subset
+//                      (group_layers_built()) -- only where the kernels above take the pair (VP_RENDER_K_HAS_GROUP_LAYERS)
 // and the same, smaller, for the approach walk (approach_built(), launch_approach_walk()).  dispatch_render(), dispatch_light() and
 // dispatch_approach() are what the launch_* functions of vp_kernels.h call.  Each launcher counts the launch under its table index
 // (census_record(), vp_kernels.h: the launch census, a test hook) just before it calls through the table.
@@ -245,8 +247,47 @@ static void dispatch_groups_built(unsigned char* built, size_t count)
     for (size_t i = 0; i < count; i++) built[i] = i < kRenderInsts && groups_built(render_at((unsigned)i));
 }
 #endif
+// ---- the instances of a group-layers launch (LaunchDev::layers and LaunchDev::groups; render_k's LYR and GRP arguments together): the
+// same subset by the same rule, in a third table with a census of its own (vp_kernels.h group_layers_census_record).  Compiled where
+// the kernels that precede this file take the pair (vp_integrator.h defines VP_RENDER_K_HAS_GROUP_LAYERS).
+#ifdef VP_RENDER_K_HAS_GROUP_LAYERS
+constexpr bool group_layers_built(const RenderInst& v) { return layers_built(v); }
+template <unsigned I>
+static void launch_group_layers_instance_at(const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
+{
+    constexpr RenderInst v = render_at(I);
+    using RNG = typename RngOf<v.rng>::type;
+    constexpr unsigned block = v.ldsb == 1 ? VP_BLOCK_LDS : VP_BLOCK;
+    hipLaunchKernelGGL((render_k<v.est, RNG, v.quant, v.count, v.ldsb, v.ach, v.mis, v.trk, v.light, v.cancel, v.half, true, true>), dim3(blocks), dim3(block), 0, st, S, L);
+}
+template <unsigned I>
+constexpr RenderLaunchFn group_layers_launcher()
+{
+    if constexpr (group_layers_built(render_at(I))) return &launch_group_layers_instance_at<I>;
+    else return nullptr;
+}
+template <unsigned... I>
+static void launch_group_layers_instance(const RenderInst& v, std::integer_sequence<unsigned, I...>, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
+{
+    static constexpr RenderLaunchFn table[kRenderInsts] = {group_layers_launcher<I>()...};
+    const unsigned i = render_index(v);
+    if (i >= kRenderInsts || !table[i]) kernel_not_built();
+    group_layers_census_record(i);
+    table[i](S, L, blocks, st);
+}
+// built[i] of the group-layers table (what group_layers_census_read hands out)
+static void dispatch_group_layers_built(unsigned char* built, size_t count)
+{
+    for (size_t i = 0; i < count; i++) built[i] = i < kRenderInsts && group_layers_built(render_at((unsigned)i));
+}
+#endif
 static void launch_instance_of(const RenderInst& v, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
 {
+#ifdef VP_RENDER_K_HAS_GROUP_LAYERS
+    if (L.layers && L.groups) { launch_group_layers_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st); return; }
+#else
+    if (L.layers && L.groups) kernel_not_built();
+#endif
 #ifdef VP_RENDER_K_HAS_GROUPS
     if (L.groups) { launch_groups_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st); return; }
 #else

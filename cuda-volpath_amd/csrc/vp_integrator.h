@@ -199,6 +199,10 @@ constexpr int render_min_waves(int est, bool count, int ldsb, bool ach, bool mis
 // the same subset.  It differs at the path end only: what the environment adds there is not summed into `rad` but staged as a sample
 // of its own in the second staging plane.  Every other instance carries no code for it.
 #define VP_RENDER_K_HAS_GROUPS 1
+// LYR and GRP: the instance of a group-layers launch (include/volpath.h vp_render_frames_group_layers; LaunchDev::layers and
+// LaunchDev::groups), named by vp_dispatch.h for the same subset.  An unscattered path ends as in a layers launch (its marked
+// throughput in the first plane, nothing in the second), a scattered one as in a groups launch.
+#define VP_RENDER_K_HAS_GROUP_LAYERS 1
 template <int EST, class RNG, bool QUANT, bool COUNT, int LDSB, bool ACH, bool MIS, int TRK, bool LIGHT = false, bool CANCEL = false, bool HALF = false, bool LYR = false,
           bool GRP = false>
 // Occupancy (round 4: the cold per-path state in LDS, ColdVal above; profiles/r04_kernel_resources.txt).  The achromatic
@@ -312,8 +316,9 @@ void render_k(SceneDev S, LaunchDev L)
     // without work counters and look-ahead: the host refuses the rest.
     constexpr bool LAYERS = LYR;
     static_assert(!LYR || (TRK == 0 && !MIS && !COUNT && !CANCEL), "layers instances: spectral tracking, passive environment, no counters, no look-ahead");
-    // Light-groups launches (LaunchDev::groups) likewise (GRP); never both in one instance.
-    static_assert(!GRP || (!LYR && TRK == 0 && !MIS && !COUNT && !CANCEL), "groups instances: spectral tracking, passive environment, no counters, no look-ahead, no layers");
+    // Light-groups launches (LaunchDev::groups) likewise (GRP).  Both: a group-layers launch (include/volpath.h
+    // vp_render_frames_group_layers) -- an unscattered path ends as in a layers launch, a scattered one as in a groups launch.
+    static_assert(!GRP || (TRK == 0 && !MIS && !COUNT && !CANCEL), "groups instances: spectral tracking, passive environment, no counters, no look-ahead");
     const ParamDev& P = L.P;
     const f3    sig_t     = f3{P.sigma_t[0], P.sigma_t[1], P.sigma_t[2]};
     const f3    sig_s     = sig_t * f3{P.albedo[0], P.albedo[1], P.albedo[2]};
@@ -879,14 +884,17 @@ void render_k(SceneDev S, LaunchDev L)
                 float4 v    = make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), heat);
                 if (TRK == 2)  // kernel.cu:2311-2313: the drawn channel only, times three
                     v = make_float4(chan == 0 ? v.x * 3.0f : 0.0f, chan == 1 ? v.y * 3.0f : 0.0f, chan == 2 ? v.z * 3.0f : 0.0f, heat);
-                if (GRP && LIGHT)
+                // (a group-layers launch, LYR and GRP: a marked sample and every sample of the light class is a transmittance sample, whose
+                // second-plane word reduce_group_layers_k derives -- the light instances are the layers launch's code, the general ones
+                // stage the sky group's sample of a scattered path only)
+                if (GRP && LIGHT && !LYR)
                 {
                     // every sample of the light class is the environment's term alone: it is one group's whole, the other gets (0, 0, 0, heat)
                     // (selects per channel: a select between two float4 objects goes through scratch)
                     L.groups[item] = make_float4(to_sky ? v.x : 0.0f, to_sky ? v.y : 0.0f, to_sky ? v.z : 0.0f, heat);
                     v              = make_float4(to_sky ? 0.0f : v.x, to_sky ? 0.0f : v.y, to_sky ? 0.0f : v.z, heat);
                 }
-                else if (GRP)
+                else if (GRP && !LIGHT && !(LAYERS && trans))
                 {
                     // the sky group's sample beside the sun group's: the beauty sample's operations on `sky` (a groups launch is staged)
                     const f3 k = sky * P.brightness;

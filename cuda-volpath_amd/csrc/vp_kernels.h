@@ -191,6 +191,9 @@ void census_built_fast(int kind, unsigned char* built, size_t count);
 // from the kinds above: the exact unit only, the index and length of CENSUS_RENDER.
 void groups_census_record(unsigned index);
 void groups_census_read(unsigned* launches, unsigned char* built, size_t count, bool reset);
+// ... and for the table of a group-layers launch (launch_group_layers_instance(); test hook: vp_test_group_layers_census), apart again
+void group_layers_census_record(unsigned index);
+void group_layers_census_read(unsigned* launches, unsigned char* built, size_t count, bool reset);
 // lds_form: how the decomposition estimator reads its brick table -- 0 global memory, 1 the 16-bit table through LDS (512-thread
 // workgroups), 2 2-bit codes into a four-entry palette through LDS (LaunchDev::bound_codes; 256-thread workgroups, plain occupancy)
 // half (with quant = false): binary16 cells (SceneDev::cells_f16); everything else of such a volume is the float volume's
@@ -247,6 +250,11 @@ void launch_reduce_layers(const LaunchDev& L, float4* trans, unsigned light_from
 // the reduce of a groups launch (LaunchDev::groups): L.out is the sun accumulator and receives the plane L.stage, sky the sky accumulator
 // and receives the plane L.groups; constants (LaunchDev::const_from) lie in the first row of either plane
 void launch_reduce_groups(const LaunchDev& L, float4* sky, hipStream_t st);
+// the reduce of a group-layers launch (LaunchDev::layers and LaunchDev::groups): L.out is the sun accumulator.  A sample of the plane
+// L.stage that carries the mark, or lies in the slots [light_from, light_to) of the light kernel or behind LaunchDev::const_from (the
+// constants of a layers launch), is a transmittance sample: (x, y, z, 1) goes to trans and (0, 0, 0, |w|) to sun and to sky -- the plane
+// L.groups is not read for it.  Any other goes to sun whole, its word of L.groups to sky and (0, 0, 0, 0) to trans
+void launch_reduce_group_layers(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st);
 // Per-pixel statistics (include/volpath.h vp_pixel_stats, the same 24 bytes) and what launch_reduce_stats does with them: the
 // reduce of a staged launch that also adds each sample's luminance to its pixel's record, and -- adaptive: a round of
 // vp_render_adaptive -- freezes the records whose criterion holds (tol, fl: the binary32 arguments widened)
@@ -260,6 +268,7 @@ struct StatsDev
     PixelStatsDev* plane2;  // a groups or layers call with statistics: the records of the second plane (sky, trans); `stats` is the first plane's
     // ... with adaptive rounds (vp_render_adaptive_groups / _layers): the criterion per plane, [0] the first plane's; tol and fl above are unused
     double   plane_tol[2], plane_fl[2];
+    PixelStatsDev* plane3;  // a group-layers call with statistics: the records of the third plane (trans); `stats` is sun's, plane2 sky's
 };
 // what the adaptive form of a plane reduce evaluates after the last launch of a round: each record with its own tolerance and floor
 struct PlaneCriterionDev { double tol[2], fl[2]; unsigned min_frames; };
@@ -271,6 +280,9 @@ void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st);
 void launch_reduce_groups_stats(const LaunchDev& L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, const PlaneCriterionDev* C, hipStream_t st);
 void launch_reduce_layers_stats(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats, PixelStatsDev* trans_stats,
                                 const PlaneCriterionDev* C, hipStream_t st);
+// the reduce of a group-layers launch (above) likewise, with one record per plane; `flags` is neither read nor written
+void launch_reduce_group_layers_stats(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* sun_stats,
+                                      PixelStatsDev* sky_stats, PixelStatsDev* trans_stats, hipStream_t st);
 // the pixels of the class-ordered list src (n[0] general, n[1] light, n[2] box-missing) whose record is not frozen, in src's order,
 // class by class, into d_out (room for all of src), and their three counts into d_totals; d_block_counts[3 * compact_blocks(n)] scratch.
 // stats2 (may be null): the records of a second plane -- a pixel is then dropped if either of its records is frozen
@@ -299,6 +311,10 @@ void launch_scale(float4* dst, const float4* src, int size, float s, hipStream_t
 void launch_relight(float4* dst, const float4* sun, const float4* sky, float3 sun_gain, float3 sky_gain, int size, float s, hipStream_t st);
 // dst = fg * s + (trans * s) o B, dst.w = 1 - trans.w * s; B = plate[i].xyz, or the constant (r, g, b) where plate is null (composite_k)
 void launch_composite(float4* dst, const float4* fg, const float4* trans, const float4* plate, float r, float g, float b, int size, float s, hipStream_t st);
+// the two in one pass: f.c = (sun.c * s) * sun_gain[c] + (sky.c * s) * sky_gain[c], dst.c = f.c + (trans.c * s) * B.c,
+// dst.w = 1 - trans.w * s (relight_composite_k: the bits of relight_k, scale_k and composite_k with s = 1 in sequence)
+void launch_relight_composite(float4* dst, const float4* sun, const float4* sky, const float4* trans, float3 sun_gain, float3 sky_gain, const float4* plate,
+                              float r, float g, float b, int size, float s, hipStream_t st);
 void launch_gamma(float4* dst, const float4* src, int size, float s, float inv_gamma, hipStream_t st);
 void launch_accumulate(float4* dst, const float4* src, size_t n, hipStream_t st);
 void launch_test_hg(const float* g, const float* r0, const float* r1, const float* nrm, const float* cosq, float* dir, float* ev, int n, hipStream_t st);

@@ -450,6 +450,48 @@ __global__ __launch_bounds__(256) void reduce_groups_k(LaunchDev L, float4* sky)
     sky[idx]   = k;
 }
 
+// reduce_stage_k's job for a group-layers launch (LaunchDev::layers and LaunchDev::groups; include/volpath.h
+// vp_render_frames_group_layers): L.out is the sun accumulator.  A staged sample of the plane L.stage is a transmittance sample where
+// its w has the sign bit set (render_k's marked samples; the constant writers of a layers launch, which serve this one and mark every
+// sample) and where its slot is the light kernel's ([light_from, light_to): no mark).  Such a sample adds (x, y, z, 1) to `trans`
+// and (0, 0, 0, |w|) to both groups; the plane L.groups holds nothing for it and is not read.  Any other adds itself to sun, its word
+// of L.groups to sky and (0, 0, 0, 0) to trans.  All three in frame order; a constant is added nframes times.
+__device__ __forceinline__ void add_group_layer_sample(float4& a, float4& k, float4& t, const float4 v, const float4* plane2, bool unmarked, float4& sun, float4& sky,
+                                                       float4& tr)
+{
+    if (unmarked || __builtin_signbit(v.w))
+    {
+        sun = sky = make_float4(0.0f, 0.0f, 0.0f, __builtin_fabsf(v.w));
+        tr  = make_float4(v.x, v.y, v.z, 1.0f);
+    }
+    else
+    {
+        sun = v;
+        sky = *plane2;
+        tr  = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    a = make_float4(a.x + sun.x, a.y + sun.y, a.z + sun.z, a.w + sun.w);
+    k = make_float4(k.x + sky.x, k.y + sky.y, k.z + sky.z, k.w + sky.w);
+    t = make_float4(t.x + tr.x, t.y + tr.y, t.z + tr.z, t.w + tr.w);
+}
+__global__ __launch_bounds__(256) void reduce_group_layers_k(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to)
+{
+    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.nslots) return;
+    unsigned pix = L.pixels[slot];
+    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
+    float4   a = L.out[idx], k = sky[idx], t = trans[idx];
+    const bool   constant = slot >= L.const_from;
+    const bool   unmarked = slot >= light_from && slot < light_to;
+    const size_t stride   = constant ? 0 : L.stage_stride;
+    float4 s0, s1, s2;
+    for (int f = 0; f < L.nframes; f++)
+        add_group_layer_sample(a, k, t, L.stage[(size_t)f * stride + slot], L.groups + (size_t)f * stride + slot, unmarked, s0, s1, s2);
+    L.out[idx] = a;
+    sky[idx]   = k;
+    trans[idx] = t;
+}
+
 // ---- the pixel lists of a rank, built on the GPU (vp_tables.cpp ensure_pixel_lists): a stable partition of the rank's pixels --
 // those of its 8x8 tiles, tile by tile (row-major tiles, row-major pixels within a tile) -- by pixel class (0 general, 1 the whole
 // chord is certified empty, 2 the camera ray misses the box; pixel table [1].y).  Padded slot s = 64 * (n-th owned tile) + 8 * row +
@@ -709,6 +751,35 @@ __global__ __launch_bounds__(256) void reduce_layers_stats_adaptive_k(LaunchDev 
                                                                       PixelStatsDev* trans_stats, PlaneCriterionDev C)
 {
     reduce_layers_stats_body<true>(L, trans, light_from, light_to, fg_stats, trans_stats, C);
+}
+// (group layers, include/volpath.h vp_render_frames_group_layers_stats: reduce_group_layers_k's job with one record per plane -- the three
+// samples add_group_layer_sample adds are the ones whose luminances go into the three records; `flags` is neither read nor written)
+__global__ __launch_bounds__(256) void reduce_group_layers_stats_k(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to,
+                                                                   PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PixelStatsDev* trans_stats)
+{
+    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.nslots) return;
+    unsigned pix = L.pixels[slot];
+    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
+    float4   a = L.out[idx], k = sky[idx], t = trans[idx];
+    double   ay = sun_stats[idx].sum_y, ay2 = sun_stats[idx].sum_y2, ky = sky_stats[idx].sum_y, ky2 = sky_stats[idx].sum_y2;
+    double   ty = trans_stats[idx].sum_y, ty2 = trans_stats[idx].sum_y2;
+    const bool   unmarked = slot >= light_from && slot < light_to;
+    const size_t stride   = slot >= L.const_from ? 0 : L.stage_stride;
+    for (int f = 0; f < L.nframes; f++)
+    {
+        float4 s0, s1, s2;
+        add_group_layer_sample(a, k, t, L.stage[(size_t)f * stride + slot], L.groups + (size_t)f * stride + slot, unmarked, s0, s1, s2);
+        stats_add_sample(ay, ay2, s0);
+        stats_add_sample(ky, ky2, s1);
+        stats_add_sample(ty, ty2, s2);
+    }
+    L.out[idx] = a;
+    sky[idx]   = k;
+    trans[idx] = t;
+    stats_store(sun_stats + idx, ay, ay2, (unsigned)L.nframes);
+    stats_store(sky_stats + idx, ky, ky2, (unsigned)L.nframes);
+    stats_store(trans_stats + idx, ty, ty2, (unsigned)L.nframes);
 }
 // A stable compaction of a class-ordered pixel list (src: n[0] general, n[1] light, n[2] box-missing pixels) by the FROZEN bit of the
 // pixels' records: the active pixels of each class in the order they have in src, class by class, and the three counts.  The pattern of
@@ -1315,6 +1386,19 @@ __global__ void relight_k(float4* dst, const float4* sun, const float4* sky, flo
     const float4 u = sun[idx], k = sky[idx];
     dst[idx] = make_float4((u.x * s) * gs.x + (k.x * s) * gk.x, (u.y * s) * gs.y + (k.y * s) * gk.y, (u.z * s) * gs.z + (k.z * s) * gk.z, u.w * s);
 }
+// include/volpath.h vp_relight_composite: relight_k's sum, then composite_k's with a scale of 1 on a transmittance scaled first -- one
+// rounding per operation in the order of the three kernels it stands for (x * 1 is x)
+__global__ void relight_composite_k(float4* dst, const float4* sun, const float4* sky, const float4* trans, float3 gs, float3 gk, const float4* plate, float r,
+                                    float g, float b, int size, float s)
+{
+    int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= size) return;
+    const float4 u = sun[idx], k = sky[idx], t = trans[idx];
+    float bx = r, by = g, bz = b;
+    if (plate) { const float4 q = plate[idx]; bx = q.x; by = q.y; bz = q.z; }
+    const float fx = (u.x * s) * gs.x + (k.x * s) * gk.x, fy = (u.y * s) * gs.y + (k.y * s) * gk.y, fz = (u.z * s) * gs.z + (k.z * s) * gk.z;
+    dst[idx] = make_float4(fx + (t.x * s) * bx, fy + (t.y * s) * by, fz + (t.z * s) * bz, 1.0f - t.w * s);
+}
 __device__ __forceinline__ float pow_pos(float x, float y) { return x <= 0.0f ? 0.0f : expf_(logf_(x) * y); }
 // __gamma_correct kernel.cu:2348-2357 (inv_gamma = 1/gamma computed by the host wrapper, :2361)
 __global__ void gamma_k(float4* dst, const float4* src, int size, float s, float inv_gamma)
@@ -1513,6 +1597,22 @@ void groups_census_read(unsigned* launches, unsigned char* built, size_t count, 
         if (launches) launches[i] = n;
     }
 }
+// ... and the group-layers table's
+static std::atomic<uint32_t> g_census_group_layers[kRenderInsts];
+void group_layers_census_record(unsigned index)
+{
+    if (index < kRenderInsts) g_census_group_layers[index].fetch_add(1u, std::memory_order_relaxed);
+}
+void group_layers_census_read(unsigned* launches, unsigned char* built, size_t count, bool reset)
+{
+    if (count > kRenderInsts) count = kRenderInsts;
+    if (built) dispatch_group_layers_built(built, count);
+    for (size_t i = 0; i < count; i++)
+    {
+        const uint32_t n = reset ? g_census_group_layers[i].exchange(0u, std::memory_order_relaxed) : g_census_group_layers[i].load(std::memory_order_relaxed);
+        if (launches) launches[i] = n;
+    }
+}
 void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
                    int blocks, hipStream_t st)
 {
@@ -1538,9 +1638,11 @@ void launch_thr_table(const ParamDev& P, float* table, unsigned count, hipStream
 }
 void launch_miss_fill(const SceneDev& S, const LaunchDev& L, bool local_estimator, hipStream_t st)
 {
-    if (L.groups)
+    if (L.groups && !L.layers)
     {
-        // (a groups launch: writers of their own, which stage the two constants; the counting launches they have no tallies for are refused)
+        // (a groups launch: writers of their own, which stage the two constants; the counting launches they have no tallies for are refused.
+        // A group-layers launch: the writers below, as in a layers launch -- its constants are marked transmittance samples, for which
+        // reduce_group_layers_k reads no second plane)
         if (L.sub_shift) hipLaunchKernelGGL(subpixel_fill_groups_k, dim3(((L.nslots << (2u * L.sub_shift)) + 255) / 256), dim3(256), 0, st, S, L);
         else hipLaunchKernelGGL(miss_fill_groups_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, S, L);
         return;
@@ -1686,6 +1788,21 @@ void launch_reduce_layers(const LaunchDev& L, float4* trans, unsigned light_from
 void launch_reduce_groups(const LaunchDev& L, float4* sky, hipStream_t st)
 {
     hipLaunchKernelGGL(reduce_groups_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky);
+}
+void launch_reduce_group_layers(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st)
+{
+    hipLaunchKernelGGL(reduce_group_layers_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky, trans, light_from, light_to);
+}
+void launch_reduce_group_layers_stats(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* sun_stats,
+                                      PixelStatsDev* sky_stats, PixelStatsDev* trans_stats, hipStream_t st)
+{
+    hipLaunchKernelGGL(reduce_group_layers_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky, trans, light_from, light_to, sun_stats, sky_stats,
+                       trans_stats);
+}
+void launch_relight_composite(float4* dst, const float4* sun, const float4* sky, const float4* trans, float3 sun_gain, float3 sky_gain, const float4* plate,
+                              float r, float g, float b, int size, float s, hipStream_t st)
+{
+    hipLaunchKernelGGL(relight_composite_k, dim3((size + 255) / 256), dim3(256), 0, st, dst, sun, sky, trans, sun_gain, sky_gain, plate, r, g, b, size, s);
 }
 void launch_relight(float4* dst, const float4* sun, const float4* sky, float3 sun_gain, float3 sky_gain, int size, float s, hipStream_t st)
 {

@@ -226,6 +226,7 @@ struct LaunchPlan
     const StatsDev* stats;        // the reduce also takes the statistics (of both planes of a layers or groups call: StatsDev::plane2)
     float4*    layers;            // a layers call (vp_render_frames_layers): the transmittance accumulator; the reduce splits the samples (reduce_layers_k)
     float4*    groups;            // a light-groups call (vp_render_frames_groups): the sky accumulator; a launch stages two planes (reduce_groups_k)
+                                  // (both: a group-layers call, vp_render_frames_group_layers -- two staging planes, three accumulators: reduce_group_layers_k)
     size_t planes() const { return groups ? 2u : 1u; }   // staging planes per frame
     // the slots of the list, general pixels first: where the class a kernel integrates ends (the general class and a light class that
     // is not written as constants), i.e. where the per-pixel constants of a launch begin -- const_from and the layers reduce's range
@@ -573,7 +574,11 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
     PlaneCriterionDev C = {};
     const bool freeze = A.stats && A.stats->plane2 && A.stats->adaptive && last;
     if (freeze) C = {{A.stats->plane_tol[0], A.stats->plane_tol[1]}, {A.stats->plane_fl[0], A.stats->plane_fl[1]}, A.stats->min_frames};
-    if (A.stats && A.groups) launch_reduce_groups_stats(L, A.groups, A.stats->stats, A.stats->plane2, freeze ? &C : nullptr, G.stream);
+    const unsigned light_from = A.PL.n_general, light_to = A.integrated_end();   // (the light kernel's slots: its samples carry no mark)
+    if (A.groups && A.layers && A.stats)
+        launch_reduce_group_layers_stats(L, A.groups, A.layers, light_from, light_to, A.stats->stats, A.stats->plane2, A.stats->plane3, G.stream);
+    else if (A.groups && A.layers) launch_reduce_group_layers(L, A.groups, A.layers, light_from, light_to, G.stream);
+    else if (A.stats && A.groups) launch_reduce_groups_stats(L, A.groups, A.stats->stats, A.stats->plane2, freeze ? &C : nullptr, G.stream);
     else if (A.stats && A.layers)
         launch_reduce_layers_stats(L, A.layers, A.PL.n_general, A.integrated_end(), A.stats->stats, A.stats->plane2, freeze ? &C : nullptr, G.stream);
     else if (A.stats)
@@ -630,7 +635,9 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         return fail(VP_E_ARG, "a layers or groups call renders the cached lists, or the active lists of an adaptive round with both planes' records");
     if (stats && !stats->plane2 != !(d_trans || d_sky))
         return fail(VP_E_ARG, "statistics on planes: one record buffer per plane of a layers or groups call");
-    if (d_trans && d_sky) return fail(VP_E_ARG, "layers and light groups in one call are not built");
+    // (both: a group-layers call, vp_render_frames_group_layers -- three planes from the two staging planes; no adaptive rounds)
+    if (d_trans && d_sky && (lists || (stats && !stats->plane3))) return fail(VP_E_ARG, "a group-layers call renders the cached lists, with no records or all three planes'");
+    if (stats && stats->plane3 && !(d_trans && d_sky)) return fail(VP_E_ARG, "statistics on three planes: a group-layers call");
     LaunchPlan A = {};
     A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats; A.layers = (float4*)d_trans; A.groups = (float4*)d_sky;
     L.layers = d_trans ? 1u : 0u;
@@ -693,7 +700,10 @@ static int await_launches(bool lookahead, bool aux)
 // the two accumulators.  Refusals likewise.
 // Either with statistics (the _stats calls): the same launches, and the reduce also folds each plane's samples into that plane's records
 // (reduce_layers_stats_k, reduce_groups_stats_k); r0 / r1 are then the two record buffers, else null.
-struct PlaneCall { const char* fn; bool groups, with_stats; };
+// Group layers (include/volpath.h vp_render_frames_group_layers): both switches at once -- render_k's instances with LYR and GRP, the
+// constant writers of a layers call, two staging planes, and reduce_group_layers_k adds them into the three accumulators (d0 sun, d1 sky,
+// d2 trans; r0 .. r2 their records).
+struct PlaneCall { const char* fn; bool groups, with_stats, both = false; };
 static const char kLayersMis[] = "scattered paths never see the sky", kGroupsMis[] = "the environment is sampled as a light, another estimator";
 // the state a plane call is built for, checked before the device is asked for; fn: the entry point the message names
 int plane_state_check(const char* fn, bool groups)
@@ -704,16 +714,19 @@ int plane_state_check(const char* fn, bool groups)
     if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "%s is built for the exact arithmetic only (its kernel instances are the exact unit's)", fn);
     return VP_OK;
 }
-static int plane_call(const PlaneCall& c, vp_float4* d0, vp_float4* d1, vp_pixel_stats* r0, vp_pixel_stats* r1, int first_frame, int n_frames, const Param* p)
+static int plane_call(const PlaneCall& c, vp_float4* d0, vp_float4* d1, vp_pixel_stats* r0, vp_pixel_stats* r1, int first_frame, int n_frames, const Param* p,
+                      vp_float4* d2 = nullptr, vp_pixel_stats* r2 = nullptr)
 {
     if (!d0 || !d1 || d0 == d1 || !p || n_frames <= 0 || first_frame < 0 || (c.with_stats && (!r0 || !r1 || r0 == r1))) return fail(VP_E_ARG, "%s: bad arguments", c.fn);
+    if (c.both && (!d2 || d2 == d0 || d2 == d1 || (c.with_stats && (!r2 || r2 == r0 || r2 == r1)))) return fail(VP_E_ARG, "%s: bad arguments", c.fn);
     int rc = plane_state_check(c.fn, c.groups);
     if (rc) return rc;
     if ((rc = ensure_device())) return rc;
     // the call is serial and runs on the caller's stream: look-ahead batches stop, pipelined launches are waited for
     if ((rc = la_quiesce())) return rc;
     StatsDev T = {};
-    T.stats = (PixelStatsDev*)r0; T.plane2 = (PixelStatsDev*)r1;
+    T.stats = (PixelStatsDev*)r0; T.plane2 = (PixelStatsDev*)r1; T.plane3 = (PixelStatsDev*)r2;
+    if (c.both) return do_render(d0, first_frame, n_frames, p, false, nullptr, nullptr, c.with_stats ? &T : nullptr, d2, d1);
     return do_render(d0, first_frame, n_frames, p, false, nullptr, nullptr, c.with_stats ? &T : nullptr, c.groups ? nullptr : d1, c.groups ? d1 : nullptr);
 }
 
@@ -743,6 +756,29 @@ int vp_render_frames_groups_stats(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_s
                                   const Param* p)
 {
     return plane_call({"vp_render_frames_groups_stats", true, true}, d_sun, d_sky, d_sun_stats, d_sky_stats, first_frame, n_frames, p);
+}
+int vp_render_frames_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans, int first_frame, int n_frames, const Param* p)
+{
+    return plane_call({"vp_render_frames_group_layers", true, false, true}, d_sun, d_sky, nullptr, nullptr, first_frame, n_frames, p, d_trans);
+}
+int vp_render_frames_group_layers_stats(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats,
+                                        vp_pixel_stats* d_trans_stats, int first_frame, int n_frames, const Param* p)
+{
+    return plane_call({"vp_render_frames_group_layers_stats", true, true, true}, d_sun, d_sky, d_sun_stats, d_sky_stats, first_frame, n_frames, p, d_trans,
+                      d_trans_stats);
+}
+int vp_relight_composite(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const vp_float4* trans, const float sun_gain[3], const float sky_gain[3],
+                         const vp_float4* plate, const float plate_rgb[3], int size, float scale)
+{
+    if (!dst || !sun || !sky || !trans || !sun_gain || !sky_gain || size < 0 || (!plate && !plate_rgb)) return fail(VP_E_ARG, "vp_relight_composite: bad arguments");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (size)
+        launch_relight_composite((float4*)dst, (const float4*)sun, (const float4*)sky, (const float4*)trans, make_float3(sun_gain[0], sun_gain[1], sun_gain[2]),
+                                 make_float3(sky_gain[0], sky_gain[1], sky_gain[2]), (const float4*)plate, plate ? 0.0f : plate_rgb[0], plate ? 0.0f : plate_rgb[1],
+                                 plate ? 0.0f : plate_rgb[2], size, scale, G.stream);
+    HIPCHK(hipGetLastError());
+    return VP_OK;
 }
 int vp_relight(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const float sun_gain[3], const float sky_gain[3], int size, float scale)
 {

@@ -359,7 +359,9 @@ struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss;
 // call is staged even for one frame and runs on the caller's stream, not on a pipeline slot.  d_trans: a layers call
 // (vp_render_frames_layers) -- d_out is the foreground accumulator, d_trans the transmittance accumulator; staged and on the caller's
 // stream likewise, with the cached lists.  d_sky: a light-groups call (vp_render_frames_groups) -- d_out is the
-// sun accumulator, d_sky the sky accumulator; staged in two planes, otherwise as a layers call (never both).  A layers or groups call
+// sun accumulator, d_sky the sky accumulator; staged in two planes, otherwise as a layers call.  Both: a group-layers call
+// (vp_render_frames_group_layers) -- d_out sun, d_sky sky, d_trans the transmittance; the two staging planes of a groups call, the cached
+// lists, no records or all three planes' (StatsDev::plane3), no adaptive rounds.  A layers or groups call
 // with statistics (the _stats calls) brings both planes' records in `stats` (StatsDev::plane2), without a criterion or lists; an adaptive
 // round on planes (vp_render_adaptive_groups / _layers) brings the records, the per-plane criterion (StatsDev::plane_tol, plane_fl) and the
 // active lists together.

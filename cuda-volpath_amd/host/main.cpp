@@ -76,6 +76,16 @@ static void usage()
            "                                                their vp_relight / vp_composite; with --groups-denoise / --layers-denoise the means\n"
            "                                                are vp_denoise's from the adaptive records.  --plane-noise-out writes one noise map\n"
            "                                                per plane (PREFIX_sun.hdr ...).  One GPU; not with --noise or --denoise\n"
+           "               [--planes-out PREFIX] [--planes-denoise]\n"
+           "                                                light groups and layers of the same paths in one render\n"
+           "                                                (vp_render_frames_group_layers): --planes-out writes the three mean planes as\n"
+           "                                                PREFIX_sun.hdr, PREFIX_sky.hdr and PREFIX_trans.hdr.  --sun-gain, --sky-gain and\n"
+           "                                                --over (default 0 0 0) are then its parameters and --out receives\n"
+           "                                                sun * sun-gain + sky * sky-gain + trans * over (vp_relight_composite; w: coverage).\n"
+           "                                                --planes-denoise: the frames go through vp_render_frames_group_layers_stats and each\n"
+           "                                                plane is filtered by vp_denoise with its own records.  One GPU; not with --noise,\n"
+           "                                                --denoise, --groups-out, --layers-out or --plane-noise; spectral, --env passive,\n"
+           "                                                --arith exact\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -111,6 +121,8 @@ int main(int argc, char** argv)
     bool        plane_adaptive = false;
     float       plane_tol[2] = {0.0f, 0.0f};
     std::string plane_noise_out;
+    std::string planes_out;
+    bool        planes_denoise = false;
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -231,6 +243,8 @@ int main(int argc, char** argv)
             }
             relit = true;
         }
+        else if (a == "--planes-out") { need(1); planes_out = argv[++i]; }
+        else if (a == "--planes-denoise") planes_denoise = true;
         else if (a == "--groups-denoise") groups_denoise = true;
         else if (a == "--layers-denoise") layers_denoise = true;
         else if (a == "--sun") { need(2); sunx = (float)atof(argv[++i]); suny = (float)atof(argv[++i]); }
@@ -272,8 +286,27 @@ int main(int argc, char** argv)
         fprintf(stderr, "--denoise with --gpus %d: the filter reads per-pixel statistics, which are not reduced across ranks; use one GPU\n", gpus);
         return 2;
     }
-    const bool layers = over || !layers_out.empty();
-    const bool groups = relit || !groups_out.empty();
+    // --planes-out: sun, sky and trans from one render; the gains and --over are then its parameters, not a groups or a layers render's
+    const bool planes = !planes_out.empty();
+    if (planes_denoise && !planes) { fprintf(stderr, "--planes-denoise needs --planes-out: it filters the three planes of that render\n"); return 2; }
+    if (planes)
+    {
+        const char* other = gpus > 1 ? "--gpus" : adaptive ? "--noise" : denoise ? "--denoise" : !groups_out.empty() ? "--groups-out" : !layers_out.empty() ? "--layers-out"
+                          : plane_adaptive ? "--plane-noise" : groups_denoise ? "--groups-denoise" : layers_denoise ? "--layers-denoise" : nullptr;
+        if (other)
+        {
+            fprintf(stderr, "--planes-out with %s: the three planes are not reduced across ranks, are filtered by --planes-denoise only, have no adaptive rounds and "
+                    "replace the groups and the layers render; use one GPU without --noise, --denoise, --groups-out, --layers-out and --plane-noise\n", other);
+            return 2;
+        }
+        if (tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE || arith != VP_ARITH_EXACT)
+        {
+            fprintf(stderr, "--planes-out needs spectral tracking, --env passive and --arith exact\n");
+            return 2;
+        }
+    }
+    const bool layers = !planes && (over || !layers_out.empty());
+    const bool groups = !planes && (relit || !groups_out.empty());
     // the per-plane filters: each needs its plane flag, one GPU, and neither the beauty image's filter nor adaptive rounds
     for (int k = 0; k < 2; k++)
     {
@@ -442,7 +475,22 @@ int main(int argc, char** argv)
     }
     vp_float4* trans = nullptr;   // --layers-out / --over: accum[0] is the foreground accumulator, this the transmittance accumulator
     // (--groups-out / --sun-gain / --sky-gain: accum[0] is the sun accumulator, this the sky accumulator)
-    if (layers || groups)
+    // (--planes-out: accum[0] sun, this sky, trans3 the transmittance; stats3 and mean3 its records and its filtered mean)
+    vp_float4*      trans3 = nullptr;
+    vp_float4*      mean3  = nullptr;
+    vp_pixel_stats* stats3 = nullptr;
+    if (planes)
+    {
+        trans3 = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+        if (!trans3 || vp_memset(trans3, 0, (size_t)npix * sizeof(vp_float4))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        if (planes_denoise)
+        {
+            stats3 = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
+            mean3  = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+            if (!stats3 || !mean3 || vp_memset(stats3, 0, (size_t)npix * sizeof(vp_pixel_stats))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        }
+    }
+    if (layers || groups || planes)
     {
         trans = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
         if (!trans || vp_memset(trans, 0, (size_t)npix * sizeof(vp_float4))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
@@ -451,7 +499,7 @@ int main(int argc, char** argv)
     vp_pixel_stats* stats2 = nullptr;
     vp_float4*      mean[2] = {nullptr, nullptr};
     const float     plane_floor[2] = {1e-3f, layers ? 1e-2f : 1e-3f};   // (trans lives in [0, 1])
-    if (plane_denoise || plane_adaptive)
+    if (plane_denoise || plane_adaptive || planes_denoise)
     {
         stats  = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
         stats2 = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
@@ -480,7 +528,14 @@ int main(int argc, char** argv)
             for (int r = 0; r < gpus; r++) { use(r); precompute_opacity(&sky.sun_dir.x); }  // host.cpp:336-343
             have_opacity = true;
         }
-        if (layers)
+        if (planes)
+        {
+            const int n = batch > 0 ? std::min(batch, spp - s) : 1;
+            if (planes_denoise ? vp_render_frames_group_layers_stats(accum[0], trans, trans3, stats, stats2, stats3, s, n, &P)
+                               : vp_render_frames_group_layers(accum[0], trans, trans3, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            s += n;
+        }
+        else if (layers)
         {
             const int n = batch > 0 ? std::min(batch, spp - s) : 1;
             if (layers_denoise ? vp_render_frames_layers_stats(accum[0], trans, stats, stats2, s, n, &P) : vp_render_frames_layers(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
@@ -549,7 +604,33 @@ int main(int argc, char** argv)
     use(0);
     bool  hdr = out.size() > 4 && out.substr(out.size() - 4) == ".hdr";
     Image image(W, H);
-    if (plane_denoise || plane_adaptive)
+    if (planes)
+    {
+        // the three mean planes -- as they are, or each filtered with its own records as guide (a MEAN image: the division by the count
+        // is part of vp_denoise; w is never filtered) --, then their relit composite over --over's colour in place of the beauty image
+        vp_float4* const       acc3[3] = {accum[0], trans, trans3};
+        vp_float4* const       mean_of[3] = {mean[0], mean[1], mean3};
+        vp_pixel_stats* const  rec3[3] = {stats, stats2, stats3};
+        static const char* const suffix[3] = {"_sun.hdr", "_sky.hdr", "_trans.hdr"};
+        for (int k = 0; k < 3; k++)
+        {
+            if (planes_denoise) { if (vp_denoise(mean_of[k], acc3[k], rec3[k], nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; } }
+            else scale(disp, acc3[k], npix, 1.0f / spp);
+            const std::string name = planes_out + suffix[k];
+            vp_download(image.buffer(), planes_denoise ? mean_of[k] : disp, (size_t)npix * sizeof(vp_float4));
+            image.dump_hdr(name.c_str());
+            printf("wrote %s\n", name.c_str());
+        }
+        if (planes_denoise ? vp_relight_composite(disp, mean_of[0], mean_of[1], mean_of[2], sun_gain, sky_gain, nullptr, over_rgb, npix, 1.0f)
+                           : vp_relight_composite(disp, accum[0], trans, trans3, sun_gain, sky_gain, nullptr, over_rgb, npix, 1.0f / spp))
+        {
+            fprintf(stderr, "%s\n", vp_last_error());
+            return 1;
+        }
+        if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
+        if (planes_denoise) printf("denoised per plane: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
+    }
+    else if (plane_denoise || plane_adaptive)
     {
         // each plane filtered with its own records as guide: two MEAN images (the division by the count is part of vp_denoise; w is
         // never filtered), written in place of the raw means and combined with scale 1
@@ -669,6 +750,9 @@ int main(int argc, char** argv)
         }
     if (stats) vp_free(stats);
     if (stats2) vp_free(stats2);
+    if (stats3) vp_free(stats3);
+    if (mean3) vp_free(mean3);
+    if (trans3) vp_free(trans3);
     for (vp_float4* m2 : mean) if (m2) vp_free(m2);
     if (trans) vp_free(trans);
     vp_free(disp);

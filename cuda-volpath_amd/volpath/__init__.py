@@ -37,6 +37,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_frames_groups", "vp_relight", "vp_reserve_frames_groups", "vp_groups_frames_per_launch", "vp_test_groups_census",
                  "vp_render_frames_groups_stats", "vp_render_frames_layers_stats",
                  "vp_render_adaptive_groups", "vp_render_adaptive_layers",
+                 "vp_render_frames_group_layers", "vp_render_frames_group_layers_stats", "vp_relight_composite", "vp_test_group_layers_census",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -155,6 +156,10 @@ def lib():
         L.vp_render_frames_layers_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param)]
         for f in (L.vp_render_adaptive_groups, L.vp_render_adaptive_layers):
             f.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param), C.POINTER(AdaptivePlanes), C.POINTER(AdaptiveResult)]
+        L.vp_render_frames_group_layers.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_render_frames_group_layers_stats.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_relight_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float)] * 2 + [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_float]
+        L.vp_test_group_layers_census.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.vp_read_counters.argtypes = [C.POINTER(Counters), C.c_int]
         L.vp_render_time_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
         L.vp_get_bound_table.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 5
@@ -494,6 +499,27 @@ def render_adaptive_layers(fg_ptr, trans_ptr, fg_stats_ptr, trans_stats_ptr, fir
                                    min_frames, round_frames)
 
 
+def render_frames_group_layers(sun_ptr, sky_ptr, trans_ptr, first, n, P):
+    """light groups and layers of the same paths in one render (vp_render_frames_group_layers): what the sun lights on scattered paths
+    sums into sun_ptr, what the sky lights on them into sky_ptr, the unscattered paths' per-channel transmittance (w: their count) into
+    trans_ptr; pixel = gain_sun * sun + gain_sky * sky + trans * background"""
+    _chk(lib().vp_render_frames_group_layers(sun_ptr, sky_ptr, trans_ptr, first, n, C.byref(P)))
+
+
+def render_frames_group_layers_stats(sun_ptr, sky_ptr, trans_ptr, sun_stats_ptr, sky_stats_ptr, trans_stats_ptr, first, n, P):
+    """render_frames_group_layers with one StatsBuffer per plane (vp_render_frames_group_layers_stats): the same accumulator bits"""
+    _chk(lib().vp_render_frames_group_layers_stats(sun_ptr, sky_ptr, trans_ptr, sun_stats_ptr, sky_stats_ptr, trans_stats_ptr, first, n, C.byref(P)))
+
+
+def relight_composite(dst_ptr, sun_ptr, sky_ptr, trans_ptr, n, s, sun_gain=(1.0, 1.0, 1.0), sky_gain=(1.0, 1.0, 1.0), plate_ptr=None, plate_rgb=None):
+    """relight, then composite, in one pass (vp_relight_composite): dst.c = ((sun.c * s) * sun_gain[c] + (sky.c * s) * sky_gain[c]) +
+    (trans.c * s) * B.c, dst.w = 1 - trans.w * s; B is the plate's pixel, or the constant plate_rgb where plate_ptr is None"""
+    gs = (C.c_float * 3)(*[float(v) for v in sun_gain])
+    gk = (C.c_float * 3)(*[float(v) for v in sky_gain])
+    rgb = (C.c_float * 3)(*[float(v) for v in plate_rgb]) if plate_rgb is not None else None
+    _chk(lib().vp_relight_composite(dst_ptr, sun_ptr, sky_ptr, trans_ptr, gs, gk, plate_ptr, rgb, n, s))
+
+
 def reserve_frames_groups(P, nframes):
     """reserve_frames for a coming render_frames_groups job: two staging planes per frame (vp_reserve_frames_groups)"""
     _chk(lib().vp_reserve_frames_groups(C.byref(P), int(nframes)))
@@ -827,6 +853,16 @@ def groups_census(reset=False):
         _chk(n)
     launches, built = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
     _chk(lib().vp_test_groups_census(_p(launches), _p(built), n, int(reset)))
+    return {census_name(CENSUS_RENDER, i): int(launches[i]) for i in np.flatnonzero(built)}
+
+
+def group_layers_census(reset=False):
+    """the same for the table a render_frames_group_layers launch goes through (vp_test_group_layers_census); needs no device"""
+    n = lib().vp_test_group_layers_census(None, None, 0, 0)
+    if n < 0:
+        _chk(n)
+    launches, built = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+    _chk(lib().vp_test_group_layers_census(_p(launches), _p(built), n, int(reset)))
     return {census_name(CENSUS_RENDER, i): int(launches[i]) for i in np.flatnonzero(built)}
 
 

@@ -410,7 +410,7 @@ int vp_composite(vp_float4* dst, const vp_float4* fg, const vp_float4* trans, co
  *   n_frames <= 0, first_frame < 0; with VP_E_STATE: VP_ENV_MIS (the environment is sampled as a light there: another estimator),
  *   scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST.  Both buffers are then untouched.  Other errors as
  *   vp_render_frames.
- *   Not built: groups combined with layers in one call; reducing groups across processes.  Not part of THIS call, which writes no
+ *   Not built: reducing groups across processes.  With layers in one call: vp_render_frames_group_layers, below.  Not part of THIS call, which writes no
  *   records: statistics, adaptive rounds or vp_denoise on groups.  vp_render_frames_groups_stats, below, is the same render with one
  *   record buffer per group, which is what vp_denoise needs; vp_render_adaptive_groups, below it, runs the adaptive rounds.
  *
@@ -455,7 +455,7 @@ int vp_groups_frames_per_launch(const Param* p, int planes);
  *   (d_fg == d_trans), the two record pointers equal, n_frames <= 0, first_frame < 0; with VP_E_STATE exactly where the underlying
  *   call gives it (VP_ENV_MIS, scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST).
  *   These calls run no adaptive rounds on planes: vp_render_adaptive_groups / vp_render_adaptive_layers of the next section do.  Still
- *   not built: groups combined with layers, reducing planes or their records across processes, and these calls under VP_ARITH_FAST.
+ *   not built: adaptive rounds on three planes, reducing planes or their records across processes, and these calls under VP_ARITH_FAST.
  * The pipeline these calls exist for: the _stats call, then per plane vp_denoise(dst, plane, plane's records, NULL, NULL, ...) -- a
  * MEAN image each --, then vp_relight or vp_composite of the two means with scale 1.  vp_denoise never filters w, so a layers
  * composite keeps its exact coverage. */
@@ -497,12 +497,66 @@ int vp_render_frames_layers_stats(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_
  *   vp_set_subpixel and every volume format; it stops look-ahead batches, waits for pipelined launches and runs on the context's
  *   stream, reading three counts back per round (it synchronises); it leaves nothing behind -- a vp_render_frames, a plain plane call or
  *   a vp_render_adaptive after it renders the bits it rendered before -- and never modifies the cached pixel lists.
- *   Not built: groups combined with layers, reducing planes or records across processes, these calls under VP_ARITH_FAST. */
+ *   Not built: adaptive rounds on three planes, reducing planes or records across processes, these calls under VP_ARITH_FAST. */
 typedef struct { float rel_tol[2], floor_y[2]; int min_frames, round_frames; } vp_adaptive_planes;   /* [0]: sun / fg, [1]: sky / trans */
 int vp_render_adaptive_groups(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats,
                               int first_frame, int max_frames, const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result);
 int vp_render_adaptive_layers(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stats* d_fg_stats, vp_pixel_stats* d_trans_stats,
                               int first_frame, int max_frames, const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result);
+
+/* Group layers: light groups combined with layers in one render -- the sun's light, the sky's light and the
+ * per-channel transmittance of the same paths in three accumulators, for a cloud element that is relit AND put over a new background.
+ * The groups planes bake the background into unscattered paths, the layers foreground has sun and sky summed: either call discards
+ * what the other keeps, so the pair costs two renders of the same paths.  This call costs one.
+ *
+ * vp_render_frames_group_layers.  THE DEFINITION:
+ *   Take the sample (x, y, frame) that vp_render_frames computes: same path, same draws, same streams.  Let R, E, b and heat be as for
+ *   vp_render_frames_groups, thr and UNSCATTERED as for vp_render_frames_layers.  This call writes
+ *     unscattered:  sun sample (0, 0, 0, heat)         sky sample (0, 0, 0, heat)          trans sample (max(thr.x, 0), max(thr.y, 0), max(thr.z, 0), 1)
+ *     otherwise:    sun sample (max(b R, 0), heat)     sky sample (max(b E, 0), heat);     trans sample (0, 0, 0, 0)
+ *                                                      a path with no E: (0, 0, 0, heat)
+ *   with the operations of the beauty sample in its order; the sky sample's sum starts from +0.  A scattered path never sees the sun's
+ *   disc (background at depth 0), so the disc case of vp_render_frames_groups arises in the unscattered row only -- and there the path
+ *   is a transmittance sample like any other unscattered path: no background enters it.  The three caller-owned accumulators
+ *   (width * height float4 each, all distinct) receive their samples per pixel in frame order; a per-pixel constant of a launch is
+ *   n_frames sequential additions, never a product.
+ *   Equivalently, wherever the path's throughput is finite and the path reaches the environment: trans is bit for bit the trans
+ *   accumulator of vp_render_frames_layers; sun is the fg accumulator of vp_render_frames_layers on the same scene with every
+ *   environment texel (0, 0, 0); sky is its fg accumulator after set_sun(dir, (0, 0, 0)); on a sample whose path scattered, sun and
+ *   sky are the two samples of vp_render_frames_groups; sun.w, sky.w and the layers call's fg.w are equal bits.
+ *   Built for exactly what the two plane calls are built for: it obeys vp_set_shard, vp_set_estimator, vp_set_rng, vp_set_stream and
+ *   vp_set_subpixel (every value each), every volume format, cell order and LDS form of the brick table.  It runs kernel instances of
+ *   its own (the existing ones carry no code for it), stops look-ahead batches, waits for pipelined launches and runs staged on the
+ *   context's stream, for one frame too, in the two staging planes of a groups call -- two planes carry the three products, since an
+ *   unscattered sample is marked in the first and needs no word in the second: vp_reserve_frames_groups and
+ *   vp_groups_frames_per_launch(p, 2) serve it unchanged.  It leaves nothing behind: a vp_render_frames, groups or layers call after it
+ *   renders the bits it rendered before.
+ *   Refused before the device is touched, all buffers untouched, with VP_E_ARG: any NULL pointer, any two accumulators equal,
+ *   n_frames <= 0, first_frame < 0; with VP_E_STATE exactly where the two plane calls give it (VP_ENV_MIS, scalar and multi-channel
+ *   tracking, enabled work counters, VP_ARITH_FAST).  Other errors as vp_render_frames.
+ *
+ * vp_render_frames_group_layers_stats: the same render with one record buffer per plane.  The three accumulators end bit-identical to
+ *   the plain call's.  For every sample v that the call adds to a PLANE's accumulator at pixel i, record i of THAT plane receives
+ *   exactly what the section "Statistics on planes" defines (y from v's RGB in binary32; sum_y, sum_y2, n), in frame order; w never
+ *   enters a luminance; constants are sequential additions; `flags` is neither read nor written; only owned pixels are touched; there
+ *   is no hidden state, a second call continues a first.  Refusals as the plain call's, plus NULL records and any two record pointers
+ *   equal.  Only the reduce differs from the plain call.
+ *
+ * vp_relight_composite, the output stage: for i < size and each channel c of x, y, z, in binary32, one rounding per operation, no
+ * contraction, with B as in vp_composite,
+ *   f = (sun[i].c * scale) * sun_gain[c] + (sky[i].c * scale) * sky_gain[c]
+ *   dst[i].c = f + (trans[i].c * scale) * B.c          dst[i].w = 1 - trans[i].w * scale
+ * Its bits are those of vp_relight(tmp, sun, sky, gains, size, scale), scale(t, trans, size, scale) and
+ * vp_composite(dst, tmp, t, plate, plate_rgb, size, 1.0f) in sequence.  dst may be any of the three inputs.  Needs no scene; runs
+ * asynchronously on the context's stream.  VP_E_ARG as for the two calls it fuses: NULL dst, sun, sky, trans or either gain, both
+ * plate pointers NULL, size < 0.
+ *   Not built: adaptive rounds on three planes, reducing planes or records across processes, these calls under VP_ARITH_FAST. */
+int vp_render_frames_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans, int first_frame, int n_frames, const Param* p);
+int vp_render_frames_group_layers_stats(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans,
+                                        vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, vp_pixel_stats* d_trans_stats,
+                                        int first_frame, int n_frames, const Param* p);
+int vp_relight_composite(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const vp_float4* trans,
+                         const float sun_gain[3], const float sky_gain[3], const vp_float4* plate, const float plate_rgb[3], int size, float scale);
 
 typedef struct
 {
@@ -680,6 +734,8 @@ int vp_test_launch_census(int unit, int kind, uint32_t* launches, uint8_t* built
  * length, 10368), counted apart from the kinds above.  With both arrays NULL the call returns the length; VP_E_ARG for a count that is
  * not the length.  Needs no device. */
 int vp_test_groups_census(uint32_t* launches, uint8_t* built, size_t count, int reset);
+/* vp_test_group_layers_census: the same for the table a vp_render_frames_group_layers launch goes through, kept apart again. */
+int vp_test_group_layers_census(uint32_t* launches, uint8_t* built, size_t count, int reset);
 int vp_test_rng(int mode, uint32_t x, uint32_t y, uint32_t frame, uint32_t k0, uint32_t k1, int n, float* out);
 int vp_test_sample_density(const float* pos_xyz, float* out, int n);
 /* component hooks for known-answer tests against float64 closed forms (no oracle involved):

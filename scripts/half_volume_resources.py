@@ -1,7 +1,7 @@
 """registers, scratch and occupancy of the binary16 kernel instances beside their float twins, and of every other kernel against another
 checkout (no GPU needed):
 
-    python scripts/half_volume_resources.py [--parent DIR_OF_ANOTHER_CHECKOUT] [--log FILE ...] [--parent-log FILE ...] [--groups | --list REGEX]
+    python scripts/half_volume_resources.py [--parent DIR_OF_ANOTHER_CHECKOUT] [--log FILE ...] [--parent-log FILE ...] [--groups | --group-layers | --list REGEX]
 
 Compiles csrc/vp_kernels.hip and csrc/vp_kernels_fast.hip for gfx950 with -Rpass-analysis=kernel-resource-usage (minutes), or reads
 the remarks of such a compilation from --log / --parent-log.  A binary16 instance is one whose last template argument, HALF, is true;
@@ -53,12 +53,15 @@ def parse(text):
         # render_k's twelfth argument (LYR: a layers instance) is not part of the name here, so that HALF
         # stays the last one: a plain instance drops it, a layers instance is listed as render_k[layers]<...>
         # (the thirteenth, GRP: a light-groups instance, section 2.7, likewise -- render_k[groups]<...>)
+        # (both, a group-layers instance, section 2.10: render_k[group-layers]<...>)
         if "render_k<" in d and d.count(",") == 12:
             d, grp = d.rsplit(", ", 1)
             d = (d if grp == "false>" else d.replace("render_k<", "render_k[groups]<")) + ">"
         if "render_k" in d and d.count(",") == 11:
             d, lyr = d.rsplit(", ", 1)
-            d = (d if lyr == "false>" else d.replace("render_k<", "render_k[layers]<")) + ">"
+            if lyr != "false>":
+                d = d.replace("render_k[groups]<", "render_k[group-layers]<") if "render_k[groups]<" in d else d.replace("render_k<", "render_k[layers]<")
+            d += ">"
         out[d] = rows[n]
     return out
 
@@ -74,6 +77,7 @@ ap.add_argument("--log", nargs="*", default=None)
 ap.add_argument("--parent-log", nargs="*", default=None)
 ap.add_argument("--groups", action="store_true", help="list the light-groups instances of render_k beside their plain twins instead of the binary16 ones")
 ap.add_argument("--list", default=None, metavar="REGEX", help="list the kernels whose name matches instead (e.g. 'reduce_': the add-kernels of a staged launch)")
+ap.add_argument("--group-layers", action="store_true", help="list the group-layers instances of render_k beside their groups and layers siblings")
 a = ap.parse_args()
 new = parse("".join(open(f, errors="replace").read() for f in a.log) if a.log else remarks(ROOT))
 old = None
@@ -107,6 +111,19 @@ if a.groups:
         lower += int(v["Occupancy [waves/SIMD]"]) < int(t["Occupancy [waves/SIMD]"])
         print(f"{n} | {short(v)} | plain twin {short(t)}")
     print(f"# {len(grp)} groups instances; with more registers or scratch than the plain twin: {more}; with a lower occupancy: {lower}")
+    raise SystemExit(0)
+if a.group_layers:
+    short = lambda v: "VGPR %3s SGPR %3s spill %s/%s scratch %s occ %s" % (v["VGPRs"], v["TotalSGPRs"], v["SGPRs Spill"], v["VGPRs Spill"], v["ScratchSize [bytes/lane]"],
+                                                                           v["Occupancy [waves/SIMD]"])
+    both = [n for n in new if n.startswith("render_k[group-layers]<")]
+    spills = lower = more = 0
+    for n in both:
+        v, g, l = new[n], new[n.replace("[group-layers]", "[groups]")], new[n.replace("[group-layers]", "[layers]")]
+        spills += int(v["ScratchSize [bytes/lane]"]) > 0 or int(v["VGPRs Spill"]) > 0 or int(v["SGPRs Spill"]) > 0
+        lower += int(v["Occupancy [waves/SIMD]"]) < int(g["Occupancy [waves/SIMD]"])
+        more += int(v["VGPRs"]) > int(g["VGPRs"])
+        print(f"{n} | {short(v)} | groups sibling {short(g)} | layers sibling {short(l)}")
+    print(f"# {len(both)} group-layers instances; with scratch or spills: {spills}; with a lower occupancy than the groups sibling: {lower}; with more VGPRs than it: {more}")
     raise SystemExit(0)
 more, occ = 0, 0
 for n in half:
