@@ -4,6 +4,7 @@
 // The integrator kernels are the plain calls', on shorter lists; the frozen set lives in the caller's buffer and nowhere else.
 // vp_render_adaptive_groups / vp_render_adaptive_layers: the same rounds on the two planes of a groups or layers render -- active means
 // frozen in neither plane's record, and a round freezes both records of a pixel when both meet their plane's criterion.
+// vp_render_adaptive_group_layers: the same on the three planes of a group-layers render, with three records per pixel.
 // vp_denoise: the filter of the output stage that reads the records (vp_denoise.hip).
 #include <climits>
 
@@ -12,18 +13,22 @@
 static_assert(sizeof(vp_pixel_stats) == 24 && sizeof(vp::PixelStatsDev) == sizeof(vp_pixel_stats), "vp_pixel_stats layout (include/volpath.h)");
 static_assert(offsetof(vp_pixel_stats, sum_y2) == 8 && offsetof(vp_pixel_stats, n) == 16 && offsetof(vp_pixel_stats, flags) == 20, "vp_pixel_stats layout");
 static_assert(sizeof(vp_adaptive_planes) == 24, "vp_adaptive_planes layout (include/volpath.h)");
+static_assert(sizeof(vp_adaptive_planes3) == 32 && offsetof(vp_adaptive_planes3, floor_y) == 12, "vp_adaptive_planes3 layout (include/volpath.h)");
+static_assert(offsetof(vp_adaptive_planes3, min_frames) == 24 && offsetof(vp_adaptive_planes3, round_frames) == 28, "vp_adaptive_planes3 layout");
 static_assert(offsetof(vp::PixelStatsDev, n) == 16 && offsetof(vp::PixelStatsDev, flags) == 20, "PixelStatsDev mirrors vp_pixel_stats");
 
 namespace vph __attribute__((visibility("hidden")))
 {
 // the active pixels of the cached lists into G.d_act, their three counts into cnt: one small synchronisation
-// (d_stats2: the second plane's records of an adaptive plane call, else null -- active then means: frozen in neither)
-static int compact_active(const Param* p, const vp_pixel_stats* d_stats, const vp_pixel_stats* d_stats2, unsigned cnt[3])
+// (d_stats2: the second plane's records of an adaptive plane call, else null -- active then means: frozen in neither; d_stats3: the third
+// plane's of an adaptive group-layers call, else null -- frozen in none of the three)
+static int compact_active(const Param* p, const vp_pixel_stats* d_stats, const vp_pixel_stats* d_stats2, const vp_pixel_stats* d_stats3, unsigned cnt[3])
 {
     const unsigned n[3] = {G.n_general, G.n_light, G.n_miss};
     const unsigned nblocks = compact_blocks(n[0] + n[1] + n[2]);
     unsigned* d_totals = G.d_act_scratch + (size_t)3 * nblocks;
-    launch_compact_active(G.d_tiles, n, p->width, (const PixelStatsDev*)d_stats, (const PixelStatsDev*)d_stats2, G.d_act_scratch, d_totals, G.d_act, G.stream);
+    launch_compact_active(G.d_tiles, n, p->width, (const PixelStatsDev*)d_stats, (const PixelStatsDev*)d_stats2, (const PixelStatsDev*)d_stats3,
+                          G.d_act_scratch, d_totals, G.d_act, G.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(cnt, d_totals, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, G.stream));
     HIPCHK(hipStreamSynchronize(G.stream));
@@ -42,9 +47,10 @@ static int reserve_active(size_t n)
 }
 // What vp_render_adaptive and the adaptive plane calls share once their arguments are checked: the rounds.  T carries the records
 // and the criterion (one record buffer, or one per plane: StatsDev::plane2); d1 is the second accumulator of a plane call (groups:
-// the sky accumulator, else the transmittance accumulator), null for vp_render_adaptive.  Rounds are serial and run on the caller's
+// the sky accumulator, else the transmittance accumulator), null for vp_render_adaptive; d2 is the transmittance accumulator of a
+// group-layers call (d1 then the sky accumulator, T.plane3 the third record buffer), else null.  Rounds are serial and run on the caller's
 // stream: look-ahead batches stop, pipelined launches are waited for.
-static int adaptive_rounds(vp_float4* d0, vp_float4* d1, bool groups, const StatsDev& T, int first_frame, int max_frames, int round_frames, const Param* p,
+static int adaptive_rounds(vp_float4* d0, vp_float4* d1, vp_float4* d2, bool groups, const StatsDev& T, int first_frame, int max_frames, int round_frames, const Param* p,
                            vp_adaptive_result* result)
 {
     int rc = la_quiesce();
@@ -53,9 +59,10 @@ static int adaptive_rounds(vp_float4* d0, vp_float4* d1, bool groups, const Stat
     const size_t n_all = (size_t)G.n_general + G.n_light + G.n_miss;
     if (n_all == 0) return VP_OK;          // a shard without a tile
     if ((rc = reserve_active(n_all))) return rc;
-    const vp_pixel_stats *r0 = (const vp_pixel_stats*)T.stats, *r1 = (const vp_pixel_stats*)T.plane2;
+    const vp_pixel_stats *r0 = (const vp_pixel_stats*)T.stats, *r1 = (const vp_pixel_stats*)T.plane2, *r2 = (const vp_pixel_stats*)T.plane3;
+    vp_float4 *d_trans = d2 ? d2 : d1 && !groups ? d1 : nullptr, *d_sky = d1 && groups ? d1 : nullptr;
     unsigned cnt[3] = {0, 0, 0};
-    if ((rc = compact_active(p, r0, r1, cnt))) return rc;
+    if ((rc = compact_active(p, r0, r1, r2, cnt))) return rc;
     int done = 0;
     unsigned rounds = 0;
     unsigned long long samples = 0;
@@ -63,11 +70,11 @@ static int adaptive_rounds(vp_float4* d0, vp_float4* d1, bool groups, const Stat
     {
         const int f = std::min(round_frames, max_frames - done);
         const PixelLists PL = {G.d_act, cnt[0], cnt[1], cnt[2]};
-        if ((rc = do_render(d0, first_frame + done, f, p, false, nullptr, &PL, &T, d1 && !groups ? d1 : nullptr, d1 && groups ? d1 : nullptr))) return rc;
+        if ((rc = do_render(d0, first_frame + done, f, p, false, nullptr, &PL, &T, d_trans, d_sky))) return rc;
         samples += ((unsigned long long)cnt[0] + cnt[1] + cnt[2]) * (unsigned long long)f;   // (one per pixel and frame, not per plane)
         done += f; rounds++;
         if (result) { result->samples = samples; result->rounds = rounds; result->frames_used = (uint32_t)done; }
-        if ((rc = compact_active(p, r0, r1, cnt))) return rc;   // round k + 1 needs round k's decisions
+        if ((rc = compact_active(p, r0, r1, r2, cnt))) return rc;   // round k + 1 needs round k's decisions
     }
     if (result) result->active_left = cnt[0] + cnt[1] + cnt[2];
     return VP_OK;
@@ -91,7 +98,7 @@ static int render_adaptive_planes(const char* fn, bool groups, vp_float4* d0, vp
     StatsDev T = {};
     T.stats = (PixelStatsDev*)r0; T.plane2 = (PixelStatsDev*)r1; T.adaptive = 1u; T.min_frames = (unsigned)a->min_frames;
     for (int k = 0; k < 2; k++) { T.plane_tol[k] = (double)a->rel_tol[k]; T.plane_fl[k] = (double)a->floor_y[k]; }
-    return adaptive_rounds(d0, d1, groups, T, first_frame, max_frames, a->round_frames, p, result);
+    return adaptive_rounds(d0, d1, nullptr, groups, T, first_frame, max_frames, a->round_frames, p, result);
 }
 }  // namespace vph
 
@@ -121,7 +128,7 @@ int vp_render_adaptive(vp_float4* d_output, vp_pixel_stats* d_stats, int first_f
     StatsDev T = {};
     T.stats = (PixelStatsDev*)d_stats; T.adaptive = 1u; T.min_frames = (unsigned)a->min_frames;
     T.tol = (double)a->rel_tol; T.fl = (double)a->floor_y;
-    return adaptive_rounds(d_output, nullptr, false, T, first_frame, max_frames, a->round_frames, p, result);
+    return adaptive_rounds(d_output, nullptr, nullptr, false, T, first_frame, max_frames, a->round_frames, p, result);
 }
 int vp_render_adaptive_groups(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, int first_frame, int max_frames,
                               const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result)
@@ -132,6 +139,30 @@ int vp_render_adaptive_layers(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stat
                               const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result)
 {
     return render_adaptive_planes("vp_render_adaptive_layers", false, d_fg, d_trans, d_fg_stats, d_trans_stats, first_frame, max_frames, p, a, result);
+}
+int vp_render_adaptive_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats,
+                                    vp_pixel_stats* d_trans_stats, int first_frame, int max_frames, const Param* p, const vp_adaptive_planes3* a,
+                                    vp_adaptive_result* result)
+{
+    static const char fn[] = "vp_render_adaptive_group_layers";
+    if (result) memset(result, 0, sizeof *result);
+    if (!d_sun || !d_sky || !d_trans || !d_sun_stats || !d_sky_stats || !d_trans_stats || !p || !a) return fail(VP_E_ARG, "%s: null pointer", fn);
+    if (d_sun == d_sky || d_sun == d_trans || d_sky == d_trans || d_sun_stats == d_sky_stats || d_sun_stats == d_trans_stats || d_sky_stats == d_trans_stats)
+        return fail(VP_E_ARG, "%s: the three accumulators, and the three record buffers, are different buffers", fn);
+    if (max_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "%s: frames [%d, %d + %d) out of range", fn, first_frame, first_frame, max_frames);
+    if (a->min_frames < 2) return fail(VP_E_ARG, "%s: min_frames %d (a variance estimate needs two samples)", fn, a->min_frames);
+    if (a->round_frames < 1) return fail(VP_E_ARG, "%s: round_frames %d", fn, a->round_frames);
+    for (int k = 0; k < 3; k++)
+        if (!(a->rel_tol[k] >= 0.0f) || !(a->floor_y[k] >= 0.0f)) return fail(VP_E_ARG, "%s: rel_tol and floor_y must be numbers >= 0 (plane %d)", fn, k);
+    int rc = plane_state_check(fn, true);
+    if (rc) return rc;
+    if ((rc = ensure_device())) return rc;
+    if ((rc = check_render(CHK_STATE | CHK_OPACITY, p, (long long)first_frame + max_frames - 1))) return rc;
+    StatsDev T = {};
+    T.stats = (PixelStatsDev*)d_sun_stats; T.plane2 = (PixelStatsDev*)d_sky_stats; T.plane3 = (PixelStatsDev*)d_trans_stats;
+    T.adaptive = 1u; T.min_frames = (unsigned)a->min_frames;
+    for (int k = 0; k < 3; k++) { T.plane_tol[k] = (double)a->rel_tol[k]; T.plane_fl[k] = (double)a->floor_y[k]; }
+    return adaptive_rounds(d_sun, d_sky, d_trans, true, T, first_frame, max_frames, a->round_frames, p, result);
 }
 int vp_scale_by_count(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, int size, float scale)
 {

@@ -267,11 +267,14 @@ struct StatsDev
     double   tol, fl;
     PixelStatsDev* plane2;  // a groups or layers call with statistics: the records of the second plane (sky, trans); `stats` is the first plane's
     // ... with adaptive rounds (vp_render_adaptive_groups / _layers): the criterion per plane, [0] the first plane's; tol and fl above are unused
-    double   plane_tol[2], plane_fl[2];
+    // ([2]: the third plane's, vp_render_adaptive_group_layers)
+    double   plane_tol[3], plane_fl[3];
     PixelStatsDev* plane3;  // a group-layers call with statistics: the records of the third plane (trans); `stats` is sun's, plane2 sky's
 };
 // what the adaptive form of a plane reduce evaluates after the last launch of a round: each record with its own tolerance and floor
 struct PlaneCriterionDev { double tol[2], fl[2]; unsigned min_frames; };
+// ... and that of the group-layers reduce ([0] sun, [1] sky, [2] trans): a descriptor of its own, the two-plane kernels keep their arguments
+struct Plane3CriterionDev { double tol[3], fl[3]; unsigned min_frames; };
 void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st);
 // the reduces of a groups and of a layers launch (above) with one record per plane and pixel: each plane's sample, as its accumulator
 // receives it, goes into that plane's record by the definition of vp_pixel_stats.  C null: `flags` is neither read nor written (the
@@ -280,15 +283,18 @@ void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st);
 void launch_reduce_groups_stats(const LaunchDev& L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, const PlaneCriterionDev* C, hipStream_t st);
 void launch_reduce_layers_stats(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats, PixelStatsDev* trans_stats,
                                 const PlaneCriterionDev* C, hipStream_t st);
-// the reduce of a group-layers launch (above) likewise, with one record per plane; `flags` is neither read nor written
+// the reduce of a group-layers launch (above) likewise, with one record per plane.  C null: `flags` is neither read nor written; C given
+// -- the last launch of a round of vp_render_adaptive_group_layers --: the adaptive form, which freezes all three records of a slot iff
+// each has C->min_frames and meets the criterion with its own n, tolerance and floor
 void launch_reduce_group_layers_stats(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* sun_stats,
-                                      PixelStatsDev* sky_stats, PixelStatsDev* trans_stats, hipStream_t st);
+                                      PixelStatsDev* sky_stats, PixelStatsDev* trans_stats, const Plane3CriterionDev* C, hipStream_t st);
 // the pixels of the class-ordered list src (n[0] general, n[1] light, n[2] box-missing) whose record is not frozen, in src's order,
 // class by class, into d_out (room for all of src), and their three counts into d_totals; d_block_counts[3 * compact_blocks(n)] scratch.
-// stats2 (may be null): the records of a second plane -- a pixel is then dropped if either of its records is frozen
+// stats2 (may be null): the records of a second plane -- a pixel is then dropped if either of its records is frozen; stats3 (may be
+// null, comes with stats2): those of a third -- dropped if any of the three is
 inline unsigned compact_blocks(unsigned n) { return (n + 1023u) / 1024u; }
 void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PixelStatsDev* stats, const PixelStatsDev* stats2,
-                           unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st);
+                           const PixelStatsDev* stats3, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st);
 void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st);
 void launch_stats_rel_error(float* dst, const PixelStatsDev* stats, int size, float floor_y, hipStream_t st);
 // the NL-means filter of the output stage (vp_denoise.hip; include/volpath.h vp_denoise): weights from (guide, gstats), colours from

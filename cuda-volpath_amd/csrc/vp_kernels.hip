@@ -753,9 +753,27 @@ __global__ __launch_bounds__(256) void reduce_layers_stats_adaptive_k(LaunchDev 
     reduce_layers_stats_body<true>(L, trans, light_from, light_to, fg_stats, trans_stats, C);
 }
 // (group layers, include/volpath.h vp_render_frames_group_layers_stats: reduce_group_layers_k's job with one record per plane -- the three
-// samples add_group_layer_sample adds are the ones whose luminances go into the three records; `flags` is neither read nor written)
-__global__ __launch_bounds__(256) void reduce_group_layers_stats_k(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to,
-                                                                   PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PixelStatsDev* trans_stats)
+// samples add_group_layer_sample adds are the ones whose luminances go into the three records; `flags` is neither read nor written --
+// except by the adaptive form, the last launch of a round of vp_render_adaptive_group_layers: all three records of the pixel are frozen
+// iff each has its min_frames and meets the criterion with its own n, tolerance and floor.  A descriptor of its own, so that the
+// two-plane reduces keep their kernel arguments: profiles/adaptive_group_layers_kernel_resources.txt)
+template <bool ADAPT>
+__device__ __forceinline__ void stats_freeze_planes3(const Plane3CriterionDev& C, PixelStatsDev* r0, double y0, double y02, unsigned n0, PixelStatsDev* r1, double y1,
+                                                     double y12, unsigned n1, PixelStatsDev* r2, double y2, double y22, unsigned n2)
+{
+    if constexpr (ADAPT)
+        if (n0 >= C.min_frames && n1 >= C.min_frames && n2 >= C.min_frames && stats_converged(y0, y02, n0, C.tol[0], C.fl[0]) &&
+            stats_converged(y1, y12, n1, C.tol[1], C.fl[1]) && stats_converged(y2, y22, n2, C.tol[2], C.fl[2]))
+        {
+            r0->flags |= 1u;   // VP_STATS_FROZEN, in all three
+            r1->flags |= 1u;
+            r2->flags |= 1u;
+        }
+}
+template <bool ADAPT>
+__device__ __forceinline__ void reduce_group_layers_stats_body(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to,
+                                                               PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PixelStatsDev* trans_stats,
+                                                               const Plane3CriterionDev& C)
 {
     unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= L.nslots) return;
@@ -777,9 +795,21 @@ __global__ __launch_bounds__(256) void reduce_group_layers_stats_k(LaunchDev L, 
     L.out[idx] = a;
     sky[idx]   = k;
     trans[idx] = t;
-    stats_store(sun_stats + idx, ay, ay2, (unsigned)L.nframes);
-    stats_store(sky_stats + idx, ky, ky2, (unsigned)L.nframes);
-    stats_store(trans_stats + idx, ty, ty2, (unsigned)L.nframes);
+    const unsigned n0 = stats_store(sun_stats + idx, ay, ay2, (unsigned)L.nframes);
+    const unsigned n1 = stats_store(sky_stats + idx, ky, ky2, (unsigned)L.nframes);
+    const unsigned n2 = stats_store(trans_stats + idx, ty, ty2, (unsigned)L.nframes);
+    stats_freeze_planes3<ADAPT>(C, sun_stats + idx, ay, ay2, n0, sky_stats + idx, ky, ky2, n1, trans_stats + idx, ty, ty2, n2);
+}
+__global__ __launch_bounds__(256) void reduce_group_layers_stats_k(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to,
+                                                                   PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PixelStatsDev* trans_stats)
+{
+    reduce_group_layers_stats_body<false>(L, sky, trans, light_from, light_to, sun_stats, sky_stats, trans_stats, Plane3CriterionDev{});
+}
+__global__ __launch_bounds__(256) void reduce_group_layers_stats_adaptive_k(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to,
+                                                                            PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PixelStatsDev* trans_stats,
+                                                                            Plane3CriterionDev C)
+{
+    reduce_group_layers_stats_body<true>(L, sky, trans, light_from, light_to, sun_stats, sky_stats, trans_stats, C);
 }
 // A stable compaction of a class-ordered pixel list (src: n[0] general, n[1] light, n[2] box-missing pixels) by the FROZEN bit of the
 // pixels' records: the active pixels of each class in the order they have in src, class by class, and the three counts.  The pattern of
@@ -797,6 +827,11 @@ struct CompactPlanesDev : CompactDev
 {
     const PixelStatsDev* stats2;
 };
+// ... and with the three of an adaptive group-layers call: a slot is dropped if ANY of the three records is frozen (again its own descriptor)
+struct CompactPlanes3Dev : CompactDev
+{
+    const PixelStatsDev *stats2, *stats3;
+};
 template <class Dev>
 __device__ __forceinline__ unsigned compact_slot(const Dev& D, unsigned s, unsigned& pix)
 {
@@ -808,6 +843,8 @@ __device__ __forceinline__ unsigned compact_slot(const Dev& D, unsigned s, unsig
     if (D.stats[idx].flags & 1u) return 3u;
     if constexpr (std::is_same<Dev, CompactPlanesDev>::value)
         if (D.stats2[idx].flags & 1u) return 3u;
+    if constexpr (std::is_same<Dev, CompactPlanes3Dev>::value)
+        if ((D.stats2[idx].flags | D.stats3[idx].flags) & 1u) return 3u;
     return s < D.n[0] ? 0u : s < D.n[0] + D.n[1] ? 1u : 2u;
 }
 template <class Dev>
@@ -826,9 +863,11 @@ __device__ __forceinline__ void compact_count_body(const Dev& D, unsigned* block
     __syncthreads();
     if (threadIdx.x < 3) block_counts[3 * blockIdx.x + threadIdx.x] = cnt[threadIdx.x];
 }
-// (compact_*_k: one record buffer, vp_render_adaptive's; compact_planes_*_k: the two of an adaptive plane call)
+// (compact_*_k: one record buffer, vp_render_adaptive's; compact_planes_*_k: the two of an adaptive plane call; compact_planes3_*_k: the
+// three of vp_render_adaptive_group_layers)
 __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_count_k(CompactDev D, unsigned* block_counts) { compact_count_body(D, block_counts); }
 __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes_count_k(CompactPlanesDev D, unsigned* block_counts) { compact_count_body(D, block_counts); }
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes3_count_k(CompactPlanes3Dev D, unsigned* block_counts) { compact_count_body(D, block_counts); }
 template <class Dev>
 __device__ __forceinline__ void compact_write_body(const Dev& D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
 {
@@ -856,6 +895,10 @@ __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_write_k(CompactDev D
     compact_write_body(D, block_offsets, totals, out);
 }
 __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes_write_k(CompactPlanesDev D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
+{
+    compact_write_body(D, block_offsets, totals, out);
+}
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes3_write_k(CompactPlanes3Dev D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
 {
     compact_write_body(D, block_offsets, totals, out);
 }
@@ -1794,10 +1837,12 @@ void launch_reduce_group_layers(const LaunchDev& L, float4* sky, float4* trans, 
     hipLaunchKernelGGL(reduce_group_layers_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky, trans, light_from, light_to);
 }
 void launch_reduce_group_layers_stats(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* sun_stats,
-                                      PixelStatsDev* sky_stats, PixelStatsDev* trans_stats, hipStream_t st)
+                                      PixelStatsDev* sky_stats, PixelStatsDev* trans_stats, const Plane3CriterionDev* C, hipStream_t st)
 {
-    hipLaunchKernelGGL(reduce_group_layers_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky, trans, light_from, light_to, sun_stats, sky_stats,
-                       trans_stats);
+    const dim3 grid((L.nslots + 255) / 256);
+    if (C)
+        hipLaunchKernelGGL(reduce_group_layers_stats_adaptive_k, grid, dim3(256), 0, st, L, sky, trans, light_from, light_to, sun_stats, sky_stats, trans_stats, *C);
+    else hipLaunchKernelGGL(reduce_group_layers_stats_k, grid, dim3(256), 0, st, L, sky, trans, light_from, light_to, sun_stats, sky_stats, trans_stats);
 }
 void launch_relight_composite(float4* dst, const float4* sun, const float4* sky, const float4* trans, float3 sun_gain, float3 sky_gain, const float4* plate,
                               float r, float g, float b, int size, float s, hipStream_t st)
@@ -1826,16 +1871,20 @@ void launch_reduce_layers_stats(const LaunchDev& L, float4* trans, unsigned ligh
     else hipLaunchKernelGGL(reduce_layers_stats_k, grid, dim3(256), 0, st, L, trans, light_from, light_to, fg_stats, trans_stats);
 }
 void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PixelStatsDev* stats, const PixelStatsDev* stats2,
-                           unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st)
+                           const PixelStatsDev* stats3, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st)
 {
     CompactPlanesDev D;
     D.src = src; D.n[0] = n[0]; D.n[1] = n[1]; D.n[2] = n[2]; D.width = width; D.stats = stats; D.stats2 = stats2;
+    CompactPlanes3Dev D3;
+    (CompactDev&)D3 = D; D3.stats2 = stats2; D3.stats3 = stats3;
     const unsigned nblocks = compact_blocks(n[0] + n[1] + n[2]);
     const dim3 grid(nblocks), block(VP_PIXLIST_BLOCK);
-    if (stats2) hipLaunchKernelGGL(compact_planes_count_k, grid, block, 0, st, D, d_block_counts);
+    if (stats3) hipLaunchKernelGGL(compact_planes3_count_k, grid, block, 0, st, D3, d_block_counts);
+    else if (stats2) hipLaunchKernelGGL(compact_planes_count_k, grid, block, 0, st, D, d_block_counts);
     else hipLaunchKernelGGL(compact_count_k, grid, block, 0, st, (CompactDev)D, d_block_counts);
     hipLaunchKernelGGL(pixlist_scan_k, dim3(1), block, 0, st, d_block_counts, nblocks, d_totals);
-    if (stats2) hipLaunchKernelGGL(compact_planes_write_k, grid, block, 0, st, D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
+    if (stats3) hipLaunchKernelGGL(compact_planes3_write_k, grid, block, 0, st, D3, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
+    else if (stats2) hipLaunchKernelGGL(compact_planes_write_k, grid, block, 0, st, D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
     else hipLaunchKernelGGL(compact_write_k, grid, block, 0, st, (CompactDev)D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
 }
 void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st)

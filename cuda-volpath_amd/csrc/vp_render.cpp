@@ -576,7 +576,17 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
     if (freeze) C = {{A.stats->plane_tol[0], A.stats->plane_tol[1]}, {A.stats->plane_fl[0], A.stats->plane_fl[1]}, A.stats->min_frames};
     const unsigned light_from = A.PL.n_general, light_to = A.integrated_end();   // (the light kernel's slots: its samples carry no mark)
     if (A.groups && A.layers && A.stats)
-        launch_reduce_group_layers_stats(L, A.groups, A.layers, light_from, light_to, A.stats->stats, A.stats->plane2, A.stats->plane3, G.stream);
+    {
+        // (three planes, vp_render_adaptive_group_layers: likewise, with the three-record criterion)
+        Plane3CriterionDev C3 = {};
+        if (freeze)
+        {
+            for (int k = 0; k < 3; k++) { C3.tol[k] = A.stats->plane_tol[k]; C3.fl[k] = A.stats->plane_fl[k]; }
+            C3.min_frames = A.stats->min_frames;
+        }
+        launch_reduce_group_layers_stats(L, A.groups, A.layers, light_from, light_to, A.stats->stats, A.stats->plane2, A.stats->plane3, freeze ? &C3 : nullptr,
+                                         G.stream);
+    }
     else if (A.groups && A.layers) launch_reduce_group_layers(L, A.groups, A.layers, light_from, light_to, G.stream);
     else if (A.stats && A.groups) launch_reduce_groups_stats(L, A.groups, A.stats->stats, A.stats->plane2, freeze ? &C : nullptr, G.stream);
     else if (A.stats && A.layers)
@@ -635,8 +645,10 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         return fail(VP_E_ARG, "a layers or groups call renders the cached lists, or the active lists of an adaptive round with both planes' records");
     if (stats && !stats->plane2 != !(d_trans || d_sky))
         return fail(VP_E_ARG, "statistics on planes: one record buffer per plane of a layers or groups call");
-    // (both: a group-layers call, vp_render_frames_group_layers -- three planes from the two staging planes; no adaptive rounds)
-    if (d_trans && d_sky && (lists || (stats && !stats->plane3))) return fail(VP_E_ARG, "a group-layers call renders the cached lists, with no records or all three planes'");
+    // (both: a group-layers call, vp_render_frames_group_layers -- three planes from the two staging planes; the caller's lists come with
+    // the adaptive rounds on three planes only: vp_render_adaptive_group_layers)
+    if (d_trans && d_sky && ((stats && !stats->plane3) || (lists && !(stats && stats->adaptive))))
+        return fail(VP_E_ARG, "a group-layers call renders the cached lists, with no records or all three planes', or the active lists of an adaptive round with all three");
     if (stats && stats->plane3 && !(d_trans && d_sky)) return fail(VP_E_ARG, "statistics on three planes: a group-layers call");
     LaunchPlan A = {};
     A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats; A.layers = (float4*)d_trans; A.groups = (float4*)d_sky;

@@ -361,7 +361,8 @@ struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss;
 // stream likewise, with the cached lists.  d_sky: a light-groups call (vp_render_frames_groups) -- d_out is the
 // sun accumulator, d_sky the sky accumulator; staged in two planes, otherwise as a layers call.  Both: a group-layers call
 // (vp_render_frames_group_layers) -- d_out sun, d_sky sky, d_trans the transmittance; the two staging planes of a groups call, the cached
-// lists, no records or all three planes' (StatsDev::plane3), no adaptive rounds.  A layers or groups call
+// lists, no records or all three planes' (StatsDev::plane3); an adaptive round on three planes (vp_render_adaptive_group_layers) brings
+// the three record buffers, the per-plane criterion ([0] sun, [1] sky, [2] trans) and the active lists together.  A layers or groups call
 // with statistics (the _stats calls) brings both planes' records in `stats` (StatsDev::plane2), without a criterion or lists; an adaptive
 // round on planes (vp_render_adaptive_groups / _layers) brings the records, the per-plane criterion (StatsDev::plane_tol, plane_fl) and the
 // active lists together.

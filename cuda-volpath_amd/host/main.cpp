@@ -86,6 +86,16 @@ static void usage()
            "                                                plane is filtered by vp_denoise with its own records.  One GPU; not with --noise,\n"
            "                                                --denoise, --groups-out, --layers-out or --plane-noise; spectral, --env passive,\n"
            "                                                --arith exact\n"
+           "               [--planes-noise TOL_SUN TOL_SKY TOL_TRANS [--min-spp N] [--round N] [--planes-noise-out PREFIX]]\n"
+           "                                                with --planes-out: adaptive sampling on the three planes\n"
+           "                                                (vp_render_adaptive_group_layers).  A pixel is sampled, in all three planes, until\n"
+           "                                                the estimated standard error of EACH plane's mean luminance is at most\n"
+           "                                                TOLk x max(mean, floor), with floors 1e-3 (sun), 1e-3 (sky) and 1e-2 (trans);\n"
+           "                                                --min-spp and --round as for --noise, --spp the maximum.  Each plane is written as\n"
+           "                                                sum / n per pixel, --out is their vp_relight_composite; with --planes-denoise the\n"
+           "                                                means are vp_denoise's from the adaptive records.  --planes-noise-out writes one\n"
+           "                                                noise map per plane (PREFIX_sun.hdr, PREFIX_sky.hdr, PREFIX_trans.hdr).  One GPU;\n"
+           "                                                not with --noise or --denoise\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -123,6 +133,10 @@ int main(int argc, char** argv)
     std::string plane_noise_out;
     std::string planes_out;
     bool        planes_denoise = false;
+    bool        planes_adaptive = false;
+    float       planes_tol[3] = {0.0f, 0.0f, 0.0f};
+    const float planes_floor[3] = {1e-3f, 1e-3f, 1e-2f};   // (trans lives in [0, 1])
+    std::string planes_noise_out;
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -194,6 +208,18 @@ int main(int argc, char** argv)
             plane_adaptive = true;
         }
         else if (a == "--plane-noise-out") { need(1); plane_noise_out = argv[++i]; }
+        else if (a == "--planes-noise")
+        {
+            need(3);
+            for (int c = 0; c < 3; c++)
+            {
+                char* end = nullptr;
+                planes_tol[c] = strtof(argv[++i], &end);
+                if (end == argv[i] || *end || !(planes_tol[c] >= 0.0f)) { fprintf(stderr, "--planes-noise %s: three tolerances >= 0\n", argv[i]); usage(); return 2; }
+            }
+            planes_adaptive = true;
+        }
+        else if (a == "--planes-noise-out") { need(1); planes_noise_out = argv[++i]; }
         else if (a == "--min-spp") { need(1); min_spp = atoi(argv[++i]); }
         else if (a == "--round") { need(1); round_frames = atoi(argv[++i]); }
         else if (a == "--noise-out") { need(1); noise_out = argv[++i]; }
@@ -295,8 +321,9 @@ int main(int argc, char** argv)
                           : plane_adaptive ? "--plane-noise" : groups_denoise ? "--groups-denoise" : layers_denoise ? "--layers-denoise" : nullptr;
         if (other)
         {
-            fprintf(stderr, "--planes-out with %s: the three planes are not reduced across ranks, are filtered by --planes-denoise only, have no adaptive rounds and "
-                    "replace the groups and the layers render; use one GPU without --noise, --denoise, --groups-out, --layers-out and --plane-noise\n", other);
+            fprintf(stderr, "--planes-out with %s: the three planes are not reduced across ranks, are filtered by --planes-denoise only, are sampled adaptively by "
+                    "--planes-noise only and replace the groups and the layers render; use one GPU without --noise, --denoise, --groups-out, --layers-out and "
+                    "--plane-noise (three tolerances: --planes-noise TOL_SUN TOL_SKY TOL_TRANS)\n", other);
             return 2;
         }
         if (tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE || arith != VP_ARITH_EXACT)
@@ -305,6 +332,10 @@ int main(int argc, char** argv)
             return 2;
         }
     }
+    // adaptive rounds on the three planes: --planes-out, one GPU, and neither the beauty image's rounds nor its filter (refused above)
+    if (planes_adaptive && !planes) { fprintf(stderr, "--planes-noise needs --planes-out: it samples the three planes of that render\n"); return 2; }
+    if (planes_adaptive && (min_spp < 2 || round_frames < 1)) { fprintf(stderr, "--planes-noise needs --min-spp >= 2 and --round >= 1\n"); usage(); return 2; }
+    if (!planes_adaptive && !planes_noise_out.empty()) { fprintf(stderr, "--planes-noise-out needs --planes-noise\n"); return 2; }
     const bool layers = !planes && (over || !layers_out.empty());
     const bool groups = !planes && (relit || !groups_out.empty());
     // the per-plane filters: each needs its plane flag, one GPU, and neither the beauty image's filter nor adaptive rounds
@@ -483,7 +514,7 @@ int main(int argc, char** argv)
     {
         trans3 = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
         if (!trans3 || vp_memset(trans3, 0, (size_t)npix * sizeof(vp_float4))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        if (planes_denoise)
+        if (planes_denoise || planes_adaptive)
         {
             stats3 = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
             mean3  = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
@@ -499,7 +530,7 @@ int main(int argc, char** argv)
     vp_pixel_stats* stats2 = nullptr;
     vp_float4*      mean[2] = {nullptr, nullptr};
     const float     plane_floor[2] = {1e-3f, layers ? 1e-2f : 1e-3f};   // (trans lives in [0, 1])
-    if (plane_denoise || plane_adaptive || planes_denoise)
+    if (plane_denoise || plane_adaptive || planes_denoise || planes_adaptive)
     {
         stats  = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
         stats2 = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
@@ -521,7 +552,14 @@ int main(int argc, char** argv)
             return 1;
         }
     }
-    for (int s = adaptive || plane_adaptive ? spp : 0; s < spp;)
+    if (planes_adaptive)
+    {
+        // rounds on the pixels none of whose three planes has met its tolerance, --spp frames at most
+        if (est == VP_EST_DECOMP && spp > 11) precompute_opacity(&sky.sun_dir.x);   // host.cpp:336-343
+        const vp_adaptive_planes3 ap = {{planes_tol[0], planes_tol[1], planes_tol[2]}, {planes_floor[0], planes_floor[1], planes_floor[2]}, min_spp, round_frames};
+        if (vp_render_adaptive_group_layers(accum[0], trans, trans3, stats, stats2, stats3, 0, spp, &P, &ap, &ares)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+    }
+    for (int s = adaptive || plane_adaptive || planes_adaptive ? spp : 0; s < spp;)
     {
         if (!have_opacity && est == VP_EST_DECOMP && (s > 10 || (batch > 0 && s + batch > 11)))
         {
@@ -574,11 +612,12 @@ int main(int argc, char** argv)
     if (gpus > 1 && !reducer.reduce_to_root(ctx, accum, streams, (size_t)npix, rerr)) { fprintf(stderr, "%s\n", rerr.c_str()); return 1; }
     for (int r = gpus - 1; r >= 0; r--) { use(r); vp_synchronize(); }
     double sec = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    if (adaptive || plane_adaptive)
+    if (adaptive || plane_adaptive || planes_adaptive)
     {
         const double all = (double)W * H * spp;
-        char what[64];
+        char what[96];
         if (adaptive) snprintf(what, sizeof what, "--noise %g", noise_tol);
+        else if (planes_adaptive) snprintf(what, sizeof what, "--planes-noise %g %g %g", planes_tol[0], planes_tol[1], planes_tol[2]);
         else snprintf(what, sizeof what, "--plane-noise %g %g", plane_tol[0], plane_tol[1]);
         printf("adaptive: %llu of %.0f samples (%.1f %%), %u rounds of %d frames, %u pixels still above %s after %u frames\n",
                (unsigned long long)ares.samples, all, 100.0 * (double)ares.samples / all, ares.rounds, round_frames, ares.active_left, what, ares.frames_used);
@@ -608,6 +647,8 @@ int main(int argc, char** argv)
     {
         // the three mean planes -- as they are, or each filtered with its own records as guide (a MEAN image: the division by the count
         // is part of vp_denoise; w is never filtered) --, then their relit composite over --over's colour in place of the beauty image
+        // (--planes-noise without the filter: each plane by its own counts, sum / n per pixel, combined with scale 1)
+        const bool means = planes_denoise || planes_adaptive;
         vp_float4* const       acc3[3] = {accum[0], trans, trans3};
         vp_float4* const       mean_of[3] = {mean[0], mean[1], mean3};
         vp_pixel_stats* const  rec3[3] = {stats, stats2, stats3};
@@ -615,14 +656,15 @@ int main(int argc, char** argv)
         for (int k = 0; k < 3; k++)
         {
             if (planes_denoise) { if (vp_denoise(mean_of[k], acc3[k], rec3[k], nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; } }
+            else if (planes_adaptive) { if (vp_scale_by_count(mean_of[k], acc3[k], rec3[k], npix, 1.0f)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; } }
             else scale(disp, acc3[k], npix, 1.0f / spp);
             const std::string name = planes_out + suffix[k];
-            vp_download(image.buffer(), planes_denoise ? mean_of[k] : disp, (size_t)npix * sizeof(vp_float4));
+            vp_download(image.buffer(), means ? mean_of[k] : disp, (size_t)npix * sizeof(vp_float4));
             image.dump_hdr(name.c_str());
             printf("wrote %s\n", name.c_str());
         }
-        if (planes_denoise ? vp_relight_composite(disp, mean_of[0], mean_of[1], mean_of[2], sun_gain, sky_gain, nullptr, over_rgb, npix, 1.0f)
-                           : vp_relight_composite(disp, accum[0], trans, trans3, sun_gain, sky_gain, nullptr, over_rgb, npix, 1.0f / spp))
+        if (means ? vp_relight_composite(disp, mean_of[0], mean_of[1], mean_of[2], sun_gain, sky_gain, nullptr, over_rgb, npix, 1.0f)
+                  : vp_relight_composite(disp, accum[0], trans, trans3, sun_gain, sky_gain, nullptr, over_rgb, npix, 1.0f / spp))
         {
             fprintf(stderr, "%s\n", vp_last_error());
             return 1;
@@ -738,6 +780,26 @@ int main(int argc, char** argv)
             float* d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
             std::vector<float> noise((size_t)npix);
             if (!d_noise || vp_stats_rel_error(d_noise, k ? stats2 : stats, npix, plane_floor[k]) || vp_download(noise.data(), d_noise, (size_t)npix * sizeof(float)))
+            {
+                fprintf(stderr, "%s\n", vp_last_error());
+                return 1;
+            }
+            Image nm(W, H);
+            for (int q = 0; q < npix; q++) { float* px = nm.buffer() + 4 * (size_t)q; px[0] = px[1] = px[2] = noise[(size_t)q]; px[3] = 1.0f; }
+            nm.dump_hdr(name.c_str());
+            printf("wrote %s\n", name.c_str());
+            vp_free(d_noise);
+        }
+    if (planes_adaptive && !planes_noise_out.empty())
+        for (int k = 0; k < 3; k++)
+        {
+            // one noise map per plane, each with its plane's floor
+            static const char* const suffix[3] = {"_sun.hdr", "_sky.hdr", "_trans.hdr"};
+            vp_pixel_stats* const    rec3[3] = {stats, stats2, stats3};
+            const std::string name = planes_noise_out + suffix[k];
+            float* d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
+            std::vector<float> noise((size_t)npix);
+            if (!d_noise || vp_stats_rel_error(d_noise, rec3[k], npix, planes_floor[k]) || vp_download(noise.data(), d_noise, (size_t)npix * sizeof(float)))
             {
                 fprintf(stderr, "%s\n", vp_last_error());
                 return 1;

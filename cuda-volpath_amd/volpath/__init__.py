@@ -38,6 +38,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_frames_groups_stats", "vp_render_frames_layers_stats",
                  "vp_render_adaptive_groups", "vp_render_adaptive_layers",
                  "vp_render_frames_group_layers", "vp_render_frames_group_layers_stats", "vp_relight_composite", "vp_test_group_layers_census",
+                 "vp_render_adaptive_group_layers",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -94,6 +95,11 @@ class Adaptive(C.Structure):
 class AdaptivePlanes(C.Structure):
     """include/volpath.h vp_adaptive_planes: [0] the first plane's (sun / fg), [1] the second's (sky / trans)"""
     _fields_ = [("rel_tol", C.c_float * 2), ("floor_y", C.c_float * 2), ("min_frames", C.c_int), ("round_frames", C.c_int)]
+
+
+class AdaptivePlanes3(C.Structure):
+    """include/volpath.h vp_adaptive_planes3: [0] sun, [1] sky, [2] trans"""
+    _fields_ = [("rel_tol", C.c_float * 3), ("floor_y", C.c_float * 3), ("min_frames", C.c_int), ("round_frames", C.c_int)]
 
 
 class AdaptiveResult(C.Structure):
@@ -158,6 +164,7 @@ def lib():
             f.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param), C.POINTER(AdaptivePlanes), C.POINTER(AdaptiveResult)]
         L.vp_render_frames_group_layers.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_render_frames_group_layers_stats.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_render_adaptive_group_layers.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(Param), C.POINTER(AdaptivePlanes3), C.POINTER(AdaptiveResult)]
         L.vp_relight_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float)] * 2 + [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_float]
         L.vp_test_group_layers_census.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.vp_read_counters.argtypes = [C.POINTER(Counters), C.c_int]
@@ -509,6 +516,18 @@ def render_frames_group_layers(sun_ptr, sky_ptr, trans_ptr, first, n, P):
 def render_frames_group_layers_stats(sun_ptr, sky_ptr, trans_ptr, sun_stats_ptr, sky_stats_ptr, trans_stats_ptr, first, n, P):
     """render_frames_group_layers with one StatsBuffer per plane (vp_render_frames_group_layers_stats): the same accumulator bits"""
     _chk(lib().vp_render_frames_group_layers_stats(sun_ptr, sky_ptr, trans_ptr, sun_stats_ptr, sky_stats_ptr, trans_stats_ptr, first, n, C.byref(P)))
+
+
+def render_adaptive_group_layers(sun_ptr, sky_ptr, trans_ptr, sun_stats_ptr, sky_stats_ptr, trans_stats_ptr, first, max_frames, P, rel_tol,
+                                 floor_y=(1e-3, 1e-3, 1e-2), min_frames=16, round_frames=32):
+    """render_adaptive's rounds on the three planes of a group-layers render (vp_render_adaptive_group_layers): a pixel is sampled, in
+    all three planes, while none of its records is frozen, and all three are frozen once each meets its own (rel_tol[k], floor_y[k]);
+    [0] sun, [1] sky, [2] trans; returns render_adaptive's dict"""
+    a = AdaptivePlanes3((C.c_float * 3)(*[float(v) for v in rel_tol]), (C.c_float * 3)(*[float(v) for v in floor_y]), min_frames, round_frames)
+    r = AdaptiveResult()
+    _chk(lib().vp_render_adaptive_group_layers(sun_ptr, sky_ptr, trans_ptr, sun_stats_ptr, sky_stats_ptr, trans_stats_ptr, first, max_frames, C.byref(P),
+                                               C.byref(a), C.byref(r)))
+    return r.as_dict()
 
 
 def relight_composite(dst_ptr, sun_ptr, sky_ptr, trans_ptr, n, s, sun_gain=(1.0, 1.0, 1.0), sky_gain=(1.0, 1.0, 1.0), plate_ptr=None, plate_rgb=None):

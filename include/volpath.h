@@ -454,8 +454,9 @@ int vp_groups_frames_per_launch(const Param* p, int planes);
  *   Refused before the device is touched, all four buffers untouched, with VP_E_ARG: any NULL pointer, d_sun == d_sky
  *   (d_fg == d_trans), the two record pointers equal, n_frames <= 0, first_frame < 0; with VP_E_STATE exactly where the underlying
  *   call gives it (VP_ENV_MIS, scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST).
- *   These calls run no adaptive rounds on planes: vp_render_adaptive_groups / vp_render_adaptive_layers of the next section do.  Still
- *   not built: adaptive rounds on three planes, reducing planes or their records across processes, and these calls under VP_ARITH_FAST.
+ *   These calls run no adaptive rounds on planes: vp_render_adaptive_groups / vp_render_adaptive_layers of the next section do, and
+ *   vp_render_adaptive_group_layers (section 2.11) runs the adaptive rounds on three planes.  Still not built: reducing planes or their
+ *   records across processes, and these calls under VP_ARITH_FAST.
  * The pipeline these calls exist for: the _stats call, then per plane vp_denoise(dst, plane, plane's records, NULL, NULL, ...) -- a
  * MEAN image each --, then vp_relight or vp_composite of the two means with scale 1.  vp_denoise never filters w, so a layers
  * composite keeps its exact coverage. */
@@ -497,7 +498,8 @@ int vp_render_frames_layers_stats(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_
  *   vp_set_subpixel and every volume format; it stops look-ahead batches, waits for pipelined launches and runs on the context's
  *   stream, reading three counts back per round (it synchronises); it leaves nothing behind -- a vp_render_frames, a plain plane call or
  *   a vp_render_adaptive after it renders the bits it rendered before -- and never modifies the cached pixel lists.
- *   Not built: adaptive rounds on three planes, reducing planes or records across processes, these calls under VP_ARITH_FAST. */
+ *   Adaptive rounds on three planes: vp_render_adaptive_group_layers, below (section 2.11).  Still not built: reducing planes or records
+ *   across processes, these calls under VP_ARITH_FAST. */
 typedef struct { float rel_tol[2], floor_y[2]; int min_frames, round_frames; } vp_adaptive_planes;   /* [0]: sun / fg, [1]: sky / trans */
 int vp_render_adaptive_groups(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats,
                               int first_frame, int max_frames, const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result);
@@ -550,13 +552,53 @@ int vp_render_adaptive_layers(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stat
  * vp_composite(dst, tmp, t, plate, plate_rgb, size, 1.0f) in sequence.  dst may be any of the three inputs.  Needs no scene; runs
  * asynchronously on the context's stream.  VP_E_ARG as for the two calls it fuses: NULL dst, sun, sky, trans or either gain, both
  * plate pointers NULL, size < 0.
- *   Not built: adaptive rounds on three planes, reducing planes or records across processes, these calls under VP_ARITH_FAST. */
+ *   These calls run no adaptive rounds on three planes: vp_render_adaptive_group_layers, below, does.  Still not built: reducing planes
+ *   or records across processes, these calls under VP_ARITH_FAST. */
 int vp_render_frames_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans, int first_frame, int n_frames, const Param* p);
 int vp_render_frames_group_layers_stats(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans,
                                         vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, vp_pixel_stats* d_trans_stats,
                                         int first_frame, int n_frames, const Param* p);
 int vp_relight_composite(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const vp_float4* trans,
                          const float sun_gain[3], const float sky_gain[3], const vp_float4* plate, const float plate_rgb[3], int size, float scale);
+
+/* Adaptive sampling on group layers: vp_render_adaptive's rounds on the three planes of a group-layers
+ * render.  [0] of the parameter arrays is sun's, [1] sky's, [2] trans's.
+ *
+ * vp_render_adaptive_group_layers.  THE DEFINITION is that of "Adaptive sampling on planes", with three planes where it says two:
+ *   A pixel is ACTIVE while the FROZEN bit is clear in ALL THREE of its records.  The frozen set is exactly what the three caller-owned
+ *   record buffers say: there is no hidden state, so a second call continues a first one.  Rounds are vp_render_adaptive's: with
+ *   B = round_frames, round k covers frames [first_frame + k B, first_frame + min((k + 1) B, max_frames)).  Every owned pixel that is
+ *   active at the start of a round receives all frames of the round in all three planes: the samples, accumulators and records are
+ *   exactly those that vp_render_frames_group_layers_stats defines for that pixel and those frames, added in frame order (the
+ *   per-pixel-constant classes: sequential additions).  A pixel that is not active receives nothing, in any accumulator or record.
+ *   After the round each pixel that was active in it is frozen iff, for k = 0, 1 and 2, record k has n >= min_frames and
+ *   vp_render_adaptive's criterion holds on it with (rel_tol[k], floor_y[k]) -- the same binary64 operations in the same order, false
+ *   on NaN, each record with its own n.  Freezing sets the FROZEN bit in all three records and changes no other flag bit; it is
+ *   permanent.  The call ends when no owned pixel is active or the frames are used up.  `result` is as in vp_render_adaptive;
+ *   `samples` counts one per pixel and frame, not per plane.  A round that the staging cap splits into several launches gives the bits
+ *   of one launch.
+ *   Why AND, and why per plane: as for two planes -- vp_relight_composite's gains and plate are unknown at render time.  A large
+ *   floor_y[k] with rel_tol[k] > 0 (1e30f, say) takes plane k out of the decision; two planes out leaves the third plane's own frozen
+ *   set.
+ *   What it is not, as for vp_render_adaptive: the stopping rule looks at the estimate it stops, which gives a small bias.  The image
+ *   of a plane is sum / n per pixel: vp_scale_by_count with THAT plane's records, then vp_relight_composite with scale 1.  The
+ *   exact-parity product stays the uniform call.
+ *   Refused before the device is touched, all six buffers untouched and *result zeroed, with VP_E_ARG: any NULL pointer (result
+ *   excepted), any two accumulators equal or any two record buffers equal, max_frames <= 0 or first_frame < 0, min_frames < 2,
+ *   round_frames < 1, any tolerance or floor negative or NaN; with VP_E_STATE exactly where vp_render_frames_group_layers gives it
+ *   (VP_ENV_MIS, scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST); an argument error comes before a state
+ *   error.  VP_E_NOOPACITY as vp_render_frames gives for frame first_frame + max_frames - 1.
+ *   Everything else is as vp_render_frames_group_layers: it obeys vp_set_shard, vp_set_estimator, vp_set_rng, vp_set_stream,
+ *   vp_set_subpixel and every volume format; vp_reserve_frames_groups serves it; it stops look-ahead batches, waits for pipelined
+ *   launches and runs on the context's stream, reading three counts back per round (it synchronises); it leaves nothing behind -- a
+ *   vp_render_frames, a plain plane call or another adaptive call after it renders the bits it rendered before -- and never modifies
+ *   the cached pixel lists.  The render launches are the plain call's instances on shorter lists; only the reduce and the compaction
+ *   have three-record forms.
+ *   Still not built: reducing planes or records across processes, these calls under VP_ARITH_FAST. */
+typedef struct { float rel_tol[3], floor_y[3]; int min_frames, round_frames; } vp_adaptive_planes3;   /* [0] sun, [1] sky, [2] trans; 32 bytes */
+int vp_render_adaptive_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans,
+                                    vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, vp_pixel_stats* d_trans_stats,
+                                    int first_frame, int max_frames, const Param* p, const vp_adaptive_planes3* a, vp_adaptive_result* result);
 
 typedef struct
 {
