@@ -758,6 +758,19 @@ __device__ __forceinline__ void sun_start_slab(const float* row, int c, bool axi
     const float tb = ir * (bmin[c] - oc), tt = ir * (bmax[c] - oc);
     tmn = fminf(tt, tb); tmx = fmaxf(tt, tb);
 }
+// A lane's bit of a wave mask as a predicate (render_k's fast states): the mask stays in a scalar register pair and is the branch's
+// exec operand -- no vector instruction.  The mask must be wave-uniform for the compiler, i.e. be formed from ballots in uniform
+// control flow: updated under a divergent branch it is moved into vector registers and read back lane by lane.
+__device__ __forceinline__ bool lane_in(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// st = CODE.  INPLACE: as an update in place, under the exec of the branch it stands in -- the old value is an operand, so the
+// assignment stays where it is written and the lanes that keep their state keep their register.  (A plain assignment of a constant
+// is hoisted above the branch into a temporary, and the other lanes' value is copied there and back: three moves per step for one.)
+template <int CODE, bool INPLACE>
+__device__ __forceinline__ void set_code(int& st)
+{
+    if constexpr (INPLACE) asm("v_mov_b32 %0, %1" : "+v"(st) : "n"(CODE));
+    else st = CODE;
+}
 // The start of a sun shadow ray (render_k start_shadow, stage 0) for instances that have the row: direction sd, length len and the
 // box test, with the values start_shadow and intersect_box compute, bit for bit.  MEMOISATION ON EXACT OPERAND BITS, decided per
 // wave at run time: a root, a reciprocal or a division is skipped only where its operands have the bit patterns the row's results

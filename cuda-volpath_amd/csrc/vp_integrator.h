@@ -1155,6 +1155,24 @@ ends_done:
         // =========================================================== fast path: tracking
         // one segment set-up (local-majorant estimators) and one tracking step, as lambdas: the loop below runs
         // them twice per pass so that the wave-level bookkeeping (ballots, wait policy) is paid once per two steps
+        // Global majorant: which lanes are in which fast state is kept in wave masks while the loop runs -- formed here from `st`, one
+        // ballot each; from then on every "is this lane TRACK / SHADOW" is the lane's bit of a mask (lane_in: the branch's exec operand,
+        // no vector instruction) and the loop's exit test is scalar arithmetic on them.  `st` stays complete all the while: a lane
+        // writes its new code once, where it leaves a state (set_code); a lane that stays writes nothing.
+        // The masks are formed anew after each step's divergent body, in UNIFORM control flow, never inside it (there the compiler
+        // keeps them per lane, in vector registers): by one compare of `st` per mask.  Without any -- flags set where a lane leaves
+        // and balloted after the body, or the step's blocks side by side under masks of compares made between them -- was tried:
+        // this compiler widens a branch-carried flag to 0 / 1 and compares it again (two vector instructions per ballot), and the
+        // side-by-side form costs the achromatic instance seven registers and its eighth wave.  The local-majorant estimators keep
+        // the enum (MASKS false: their code is what it was): with masks 23 of their instances need 2-8 registers more and lose a wave
+        // (profiles/experiments/fast_state_masks.txt).
+        constexpr bool MASKS = !LOCAL;
+        unsigned long long m_track = MASKS ? __ballot(st == ST_TRACK) : 0ull, m_shadow = MASKS ? __ballot(st == ST_SHADOW) : 0ull;
+        // lanes that hold or want a sample (no lane becomes ST_DONE in the loop): those of them in no fast state wait for the event pass
+        const unsigned long long m_live = MASKS ? __ballot(!(st == ST_DONE && exhausted)) : 0ull;
+        auto in_track  = [&]() __attribute__((always_inline)) { return MASKS ? lane_in(m_track) : st == ST_TRACK; };
+        auto in_shadow = [&]() __attribute__((always_inline)) { return MASKS ? lane_in(m_shadow) : st == ST_SHADOW; };
+        auto in_flight = [&]() __attribute__((always_inline)) { return MASKS ? lane_in(m_track | m_shadow) : (st == ST_TRACK || st == ST_SHADOW); };
         auto segment_setup = [&]() __attribute__((always_inline)) {
             if (LOCAL) tally(B_SETUP, st == ST_SETUP);
             if (LOCAL && st == ST_SETUP)
@@ -1191,7 +1209,7 @@ ends_done:
                 if (COUNT) c_bnd++;
                 float d_min = by;
                 d_max       = fmaxf(0.0001f, bx);
-                if (!hit) st = EV_BG;
+                if (!hit) set_code<EV_BG, MASKS>(st);
                 else
                 {
                     // (where the free flight of this segment starts: where the ray enters it -- or, in the one segment approach_local_k
@@ -1221,7 +1239,7 @@ ends_done:
                         inv_sigma = inv_sigma_t;
                     }
                     t_end = fminf(distc, t_far);  // dist >= distc || dist >= t_far  (kernel.cu:2086)
-                    st    = ST_TRACK;
+                    set_code<ST_TRACK, MASKS>(st);
                 }
             }
         };
@@ -1249,8 +1267,8 @@ ends_done:
             if (EST == EST_GLOBAL)
             {
                 nsc = nsc + 1;
-                if (nsc >= 800) st = EV_WRITE;
-                else if (t_far < 0.0f) { st = EV_BG; t_empty = 0.0f; }
+                if (nsc >= 800) set_code<EV_WRITE, MASKS>(st);
+                else if (t_far < 0.0f) { set_code<EV_BG, MASKS>(st); t_empty = 0.0f; }
                 else
                 {
                     // __d_render's segment set-up kernel.cu:1355-1370 for the depth index just reached
@@ -1279,15 +1297,15 @@ ends_done:
                         inv_sigma   = rcp_(sigma_t_prime);
                         inv_sigma_t = inv_sigma;
                     }
-                    st            = ST_TRACK;
+                    set_code<ST_TRACK, MASKS>(st);
                 }
             }
             else
             {
-                st   = ST_SETUP;
+                set_code<ST_SETUP, MASKS>(st);
                 dist = -1.0f;
                 if (EST == EST_BOUNDED) seg++;
-                if ((EST == EST_BOUNDED ? seg : nsc) >= 800) st = EV_WRITE;
+                if ((EST == EST_BOUNDED ? seg : nsc) >= 800) set_code<EV_WRITE, MASKS>(st);
                 if (TAB) cur_density = coll_row(nsc - 5)[CR_DENS];
                 else
                 {
@@ -1299,17 +1317,17 @@ ends_done:
             }
         };
         auto tracking_step = [&]() __attribute__((always_inline)) {
-            tally(B_HALF, st == ST_TRACK || st == ST_SHADOW);
+            tally(B_HALF, in_flight());
             if (LIGHT && !LOCAL)
             {
                 // Every fetch of this path would filter eight zero texels (certified: the whole chord): the general expressions
                 // below with den = +0 reduce exactly to sigma_t_den = +0, Ps = +0, c = Pn, `real` false for any draw and
                 // sigma_null_den = sigma_t_prime -- no position, fetch or filter.  (A throughput that is not
                 // finite stays NaN either way and the sample is written as 0.)
-                if (st == ST_TRACK)
+                if (in_track())
                 {
                     dist += -logf_(rng.next_a()) * inv_sigma;  // kernel.cu:1419
-                    if (dist >= t_end) st = EV_BG;              // transmitted through the box kernel.cu:1444-1452
+                    if (dist >= t_end) set_code<EV_BG, MASKS>(st);   // transmitted through the box kernel.cu:1444-1452
                     else
                     {
                         // the collision test's variate is not needed (`real` is false whatever it is), but a sequential stream
@@ -1323,11 +1341,12 @@ ends_done:
                         seg++;
                     }
                 }
+                if (MASKS) m_track &= __ballot(st == ST_TRACK);
                 return;
             }
-            if (st == ST_TRACK || st == ST_SHADOW)
+            if (in_flight())
             {
-                const bool shadow = st == ST_SHADOW;
+                const bool shadow = in_shadow();
                 vp_pad<VP_PAD_STEP>();
                 dist += -logf_(rng.next_a()) * inv_sigma;  // kernel.cu:2085 / :784
                 tally(B_EXIT, dist >= t_end || (shadow && terms == 7));
@@ -1339,7 +1358,7 @@ ends_done:
                     {
                         // Tr_spectral returns 1 - terminated flags (kernel.cu:807)
                         if (!DEFER) nee_a = f3{(float)(1 - (terms & 1)), (float)(1 - ((terms >> 1) & 1)), (float)(1 - ((terms >> 2) & 1))};
-                        st    = EV_NEE;
+                        if (!EARLY) set_code<EV_NEE, MASKS>(st);   // (EARLY: light_done writes the code)
                         rng.leave_shadow(rng_saved);
                         if (EARLY) light_done();
                     }
@@ -1350,22 +1369,22 @@ ends_done:
                         {
                             ro = ro + rd * t_far;  // tracking restart kernel.cu:2151-2155 / :1809-1813
                             t_empty -= t_far;      // the certified-empty distance is measured from the segment origin
-                            st   = ST_SETUP;
+                            set_code<ST_SETUP, MASKS>(st);
                             dist = -1.0f;
                             if (EXITC) terms += d_max <= 0.0001f ? VP_EXIT_TRIP : 0;   // exit flights: a segment through a brick with maximum zero
-                            if (EST == EST_BOUNDED && ++seg >= 800) st = EV_WRITE;  // `continue` still counts, :1716
+                            if (EST == EST_BOUNDED && ++seg >= 800) set_code<EV_WRITE, MASKS>(st);  // `continue` still counts, :1716
                         }
                         else
                         {
                             if (MIS) seg_o = ro;
                             if (PARK) dist = distc;  // control collision kernel.cu:2088: ro + rd * distc, formed in the collision block
                             else ro = ro + rd * distc;
-                            st = LIGHT ? EV_WRITE : EV_SCATTER;  // (LIGHT: excluded by the pixel class, which checks the brick minima)
+                            set_code<LIGHT ? EV_WRITE : EV_SCATTER, MASKS>(st);  // (LIGHT: excluded by the pixel class, which checks the brick minima)
                         }
                     }
                     else
                     {
-                        st = EV_BG;  // transmitted through the box kernel.cu:1444-1452
+                        set_code<EV_BG, MASKS>(st);  // transmitted through the box kernel.cu:1444-1452
                         if (PROF) { c_xout += zrun; zrun = 0; }
                     }
                 }
@@ -1406,8 +1425,8 @@ ends_done:
                         // scalar delta tracking: kernel.cu:2137-2142 / :745-748 (Tr stops AT its collision, no further draw)
                         if (e < den * inv_sigma)
                         {
-                            if (shadow) { nee_a = f3{0.0f, 0.0f, 0.0f}; st = EV_NEE; rng.leave_shadow(rng_saved); if (EARLY) light_done(); }
-                            else { if (!PARK) ro = p; st = EV_SCATTER; }
+                            if (shadow) { nee_a = f3{0.0f, 0.0f, 0.0f}; if (!EARLY) set_code<EV_NEE, MASKS>(st); rng.leave_shadow(rng_saved); if (EARLY) light_done(); }
+                            else { if (!PARK) ro = p; set_code<EV_SCATTER, MASKS>(st); }
                         }
                     }
                     else if (shadow)
@@ -1433,14 +1452,15 @@ ends_done:
                         float Ps   = (mt + mt) + mt;
                         float Pn   = (mn + mn) + mn;
                         float c    = Ps + Pn;
-                        bool  real = e * c < Ps;
+                        // (MASKS: one compare -- "not real" is the complement of this mask within the block's exec: !(a < b), NaN included)
+                        const bool real = MASKS ? lane_in(__ballot(e * c < Ps)) : e * c < Ps;
                         float f    = wdiv_(inv_sigma_t * c, real ? Ps : Pn);
                         thr.x      = thr.x * ((real ? a_s : a_n) * f);
                         if (real)
                         {
                             if (MIS) seg_o = ro;
                             if (!PARK) ro = p;
-                            st = LIGHT ? EV_WRITE : EV_SCATTER;  // (LIGHT: den = +0 makes `real` false)
+                            set_code<LIGHT ? EV_WRITE : EV_SCATTER, MASKS>(st);  // (LIGHT: den = +0 makes `real` false)
                         }
                         else if (EXITC && den == 0.0f)
                         {
@@ -1465,7 +1485,8 @@ ends_done:
                         float Pn = __builtin_fabsf(sigma_null_den.x * thr.x) + __builtin_fabsf(sigma_null_den.y * thr.y) +
                                    __builtin_fabsf(sigma_null_den.z * thr.z);
                         float c    = Ps + Pn;
-                        bool  real = e * c < Ps;
+                        // (MASKS: one compare -- "not real" is the complement of this mask within the block's exec: !(a < b), NaN included)
+                        const bool real = MASKS ? lane_in(__ballot(e * c < Ps)) : e * c < Ps;
                         float f    = wdiv_(inv_sigma_t * c, real ? Ps : Pn);
                         f3    sel  = real ? sigma_s_den : sigma_null_den;
                         thr        = thr * (sel * f);
@@ -1473,7 +1494,7 @@ ends_done:
                         {
                             if (MIS) seg_o = ro;
                             if (!PARK) ro = p;
-                            st = LIGHT ? EV_WRITE : EV_SCATTER;  // (LIGHT: den = +0 makes `real` false)
+                            set_code<LIGHT ? EV_WRITE : EV_SCATTER, MASKS>(st);  // (LIGHT: den = +0 makes `real` false)
                         }
                         else if (EXITC && den == 0.0f)
                         {
@@ -1483,6 +1504,14 @@ ends_done:
                     }
                 }
             }
+            // the masks after the step, from the codes, where the wave is whole: two compares for everything the step and the loop
+            // ask about the lanes' states
+            if (MASKS)
+            {
+                const unsigned long long actm = m_track | m_shadow;
+                m_track  = __ballot(st == ST_TRACK) & actm;
+                m_shadow = __ballot(st == ST_SHADOW) & actm;
+            }
         };
         // the light kernel of the global-majorant estimator has the shortest step (a draw, a logarithm, an add and a compare):
         // more of them per round of wave-level bookkeeping
@@ -1490,17 +1519,26 @@ ends_done:
 #pragma unroll 1
         for (int iter = 0;; iter += STEPS)
         {
-            bool active = (st == ST_TRACK) || (st == ST_SHADOW) || (LOCAL && st == ST_SETUP);
-            unsigned long long am = __ballot(active);
-            unsigned long long wm = __ballot(!active && !(st == ST_DONE && exhausted));
+            // lanes in a fast state; lanes that wait for the event pass
+            bool active = true;
+            unsigned long long am, wm;
+            if (MASKS) { am = m_track | m_shadow; wm = m_live & ~am; }
+            else
+            {
+                active = (st == ST_TRACK) || (st == ST_SHADOW) || (LOCAL && st == ST_SETUP);
+                am     = __ballot(active);
+                wm     = __ballot(!active && !(st == ST_DONE && exhausted));
+            }
             unsigned nwait = (unsigned)__popcll(wm);
             if (am == 0ull || nwait >= L.wait_lanes || (nwait > 0u && iter >= (int)L.wait_iters)) break;
             if (PROF)
             {
-                const unsigned long long sm = __ballot(st == ST_SHADOW);   // (a ballot under `lane == 0` would see lane 0 only)
+                const unsigned long long sm = MASKS ? m_shadow : __ballot(st == ST_SHADOW);   // (a ballot under `lane == 0` would see lane 0 only)
                 if (lane == 0) { d_iter++; d_act += (unsigned)__popcll(am); d_shadow += (unsigned)__popcll(sm); }
             }
-            if (!active) continue;
+            // (MASKS: no branch around the pass for the other lanes -- each step runs under its own mask, and the masks are formed
+            // between the steps, where the wave is whole)
+            if (!MASKS && !active) continue;
             segment_setup();
             tracking_step();
 #pragma unroll
@@ -1508,8 +1546,8 @@ ends_done:
             {
                 if (PROF)
                 {
-                    unsigned long long am2 = __ballot((st == ST_TRACK) || (st == ST_SHADOW) || (LOCAL && st == ST_SETUP));
-                    const unsigned long long sm2 = __ballot(st == ST_SHADOW);
+                    unsigned long long am2 = MASKS ? (m_track | m_shadow) : __ballot((st == ST_TRACK) || (st == ST_SHADOW) || (LOCAL && st == ST_SETUP));
+                    const unsigned long long sm2 = MASKS ? m_shadow : __ballot(st == ST_SHADOW);
                     if (lane == 0) { d_iter++; d_act += (unsigned)__popcll(am2); d_shadow += (unsigned)__popcll(sm2); }
                 }
                 // a restart segment is set up at once while many lanes ask for one (the crawl toward and through empty bricks,
