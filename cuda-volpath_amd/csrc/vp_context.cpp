@@ -126,6 +126,7 @@ int ensure_device()
     if (knob("VP_NO_EXIT", 0, 1, v)) G.use_exit = v == 0;
     if (knob("VP_EXIT_LOCAL", 0, 1, v)) { G.exit_local = v != 0; G.exit_local_auto = false; }
     if (knob("VP_EXIT_K", 1, VP_EXIT_TRIP, v)) G.exit_k = (unsigned)v;
+    if (knob("VP_NO_FEATURE_SKIP", 0, 1, v)) G.use_feature_skip = v == 0;
     G.dev_ready = true;
     return VP_OK;
 }

@@ -310,6 +310,21 @@ void launch_pack_f16(const unsigned short* vol, uint4* cells, int nx, int ny, in
 void launch_opacity(const SceneDev& S, bool quant, bool half, bool lds, const float dir[3], float* out, hipStream_t st);
 void launch_build_bounds(const void* d_vol, bool quant, bool half, void* d_out, void* d_tmp_a, void* d_tmp_b, int nx, int ny, int nz, int radius, int brick,
                          hipStream_t st);
+// the feature pass (include/volpath.h vp_render_features): a launch works on `n` slots of a pixel list (y << 16 | x) of a width x height
+// image and writes alpha / depth at y * width + x.  table: the per-pixel table of that image (vp_get_pixel_table's; two float4 per
+// pixel) where the march may skip the certified-empty stretch of a chord, or null
+struct FeatureDev
+{
+    const unsigned* pixels;
+    unsigned        n, width, height;
+    const float4*   table;
+    float           step, tau_z, density, sigma_t[3];
+    float4 *        alpha, *depth;
+};
+// features_k: every slot marches (a ray that misses the box writes the miss constant)
+void launch_features(const SceneDev& S, bool quant, bool half, const FeatureDev& F, hipStream_t st);
+// features_fill_k: slots [0, n_light) get the result of a march of zeros, the rest the miss constant
+void launch_features_fill(const FeatureDev& F, unsigned n_light, hipStream_t st);
 void launch_julia(unsigned char* grid, int n, hipStream_t st);
 void launch_cloud(float* grid, int n, unsigned seed, hipStream_t st);
 void launch_scale(float4* dst, const float4* src, int size, float s, hipStream_t st);

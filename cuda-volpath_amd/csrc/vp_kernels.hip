@@ -1401,6 +1401,100 @@ __global__ __launch_bounds__(VP_OPA_B * VP_OPA_B * VP_OPA_B) void opacity_lds_k(
     if (inside) out[(size_t)i + (size_t)S.nx * ((size_t)j + (size_t)S.ny * (size_t)k)] = hit ? opacity * dt : 0.0f;
 }
 
+// ---- the feature pass (include/volpath.h vp_render_features): the same kind of march along each pixel's CAMERA
+// ray -- midpoint rule, fixed step -- writing the expected opacity and three depths of the pixel.  One lane per pixel of a pixel list
+// (8x8-tile order: a wave is one tile, its lanes fetch neighbouring cells).  The header's definition is the loop below read one step
+// at a time; the kernel takes FOUR steps per pass so that a lane has four independent cell fetches in flight -- the steps' own
+// operations, in the steps' order -- and, given the per-pixel table (F.table; null: VP_NO_FEATURE_SKIP=1 or no table in this
+// configuration), starts behind the certified-empty stretch of the chord: a step in there would fetch exactly +0 (empty_table_k),
+// add it to s and meet none of the three conditions.
+__device__ __forceinline__ float feature_luminance_sigma(const FeatureDev& F) { return (0.2126f * F.sigma_t[0] + 0.7152f * F.sigma_t[1]) + 0.0722f * F.sigma_t[2]; }
+__device__ __forceinline__ void feature_write(const FeatureDev& F, size_t i, float s, float zf, float zt, float zb, float cover)
+{
+    const float tau = (s * F.step) * F.density;
+    F.alpha[i] = make_float4(1.0f - expf_(-(tau * F.sigma_t[0])), 1.0f - expf_(-(tau * F.sigma_t[1])), 1.0f - expf_(-(tau * F.sigma_t[2])), tau);
+    F.depth[i] = make_float4(zf, zt, zb, cover);
+}
+template <bool QUANT, bool HALF = false>
+__global__ __launch_bounds__(64) void features_k(SceneDev S, FeatureDev F)
+{
+    const unsigned slot = blockIdx.x * 64u + threadIdx.x;
+    if (slot >= F.n) return;
+    const unsigned pix = F.pixels[slot], px = pix & 0xffffu, py = pix >> 16;
+    const size_t   i   = (size_t)py * F.width + px;
+    const float    inf = __builtin_inff();
+    f3 ro, rd;
+    camera_ray(S, F.width, F.height, px, py, ro, rd);
+    float tn, tf;
+    const bool hit = intersect_box(ro, rd, S, tn, tf);
+    if (tn <= 0.0f) tn = 0.0f;
+    if (!hit)
+    {
+        F.alpha[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        F.depth[i] = make_float4(inf, inf, inf, 0.0f);
+        return;
+    }
+    const float sy = feature_luminance_sigma(F);
+    unsigned k = 0;
+    if (F.table)
+    {
+        // the certified-empty distance counts from the table's origin: the camera (global majorant), or where the restart crawl ends on
+        // the ray (local majorants; its place on the ray is known to 1e-5, the certificate has three quarters of a cell to spare)
+        const float4 a = F.table[2 * i], b = F.table[2 * i + 1];
+        // (a chord that is empty throughout has 1e30 there: the stretch ends with the chord at the latest)
+        const float  te = b.x > 0.0f ? fminf(dot(f3{a.x, a.y, a.z} - ro, rd) + b.x, tf) : 0.0f;
+        if (te > tn)
+        {
+            // two steps short of the estimate, then down to a k whose predecessor is inside the stretch: t is monotone in k
+            const float q = (te - tn) / F.step - 2.0f;
+            if (q >= 1.0f) k = (unsigned)fminf(q, 16777216.0f);
+            while (k > 0 && !(tn + ((float)(k - 1u) + 0.5f) * F.step < te)) k--;
+        }
+    }
+    float s = 0.0f, zf = inf, zt = inf, zb = inf, cover = 0.0f;
+    bool  reached = false;
+    for (; k < (1u << 24); k += 4u)
+    {
+        float t[4], rho[4];
+        bool  in[4];
+#pragma unroll
+        for (unsigned j = 0; j < 4u; j++)
+        {
+            t[j]  = tn + ((float)(k + j) + 0.5f) * F.step;
+            in[j] = (j == 0u || in[j - 1u]) && t[j] < tf;
+        }
+#pragma unroll
+        for (unsigned j = 0; j < 4u; j++) rho[j] = in[j] ? sample_density01<QUANT, HALF>(S, ro + rd * t[j]) : 0.0f;
+#pragma unroll
+        for (unsigned j = 0; j < 4u; j++)
+            if (in[j])
+            {
+                s = s + rho[j];
+                if (rho[j] > 0.0f) { if (cover == 0.0f) zf = t[j]; zb = t[j]; cover = 1.0f; }
+                // (a step that adds a zero leaves s, hence the product, hence the answer of the step before -- or of s = 0 -- as it is)
+                if (rho[j] != 0.0f && !reached && (((s * F.step) * F.density) * sy >= F.tau_z)) { zt = t[j]; reached = true; }
+            }
+        if (!in[3]) break;
+    }
+    feature_write(F, i, s, zf, zt, zb, cover);
+}
+// the two classes that do not march: slots [0, n_light) the light class -- what the definition gives for a march of zeros, computed here
+// with its own operations --, the rest the box-missing class's constant
+__global__ __launch_bounds__(256) void features_fill_k(FeatureDev F, unsigned n_light)
+{
+    const unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= F.n) return;
+    const unsigned pix = F.pixels[slot];
+    const size_t   i   = (size_t)(pix >> 16) * F.width + (pix & 0xffffu);
+    const float    inf = __builtin_inff();
+    if (slot < n_light) feature_write(F, i, 0.0f, inf, inf, inf, 0.0f);
+    else
+    {
+        F.alpha[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        F.depth[i] = make_float4(inf, inf, inf, 0.0f);
+    }
+}
+
 // __scale kernel.cu:2333-2341
 __global__ void scale_k(float4* dst, const float4* src, int size, float s)
 {
@@ -1929,6 +2023,17 @@ void launch_opacity(const SceneDev& S, bool quant, bool half, bool lds, const fl
     else if (quant) hipLaunchKernelGGL(opacity_k<true>, g, dim3(256), 0, st, S, d, out);
     else if (half) hipLaunchKernelGGL((opacity_k<false, true>), g, dim3(256), 0, st, S, d, out);
     else hipLaunchKernelGGL(opacity_k<false>, g, dim3(256), 0, st, S, d, out);
+}
+void launch_features(const SceneDev& S, bool quant, bool half, const FeatureDev& F, hipStream_t st)
+{
+    const dim3 g((F.n + 63u) / 64u);
+    if (quant) hipLaunchKernelGGL(features_k<true>, g, dim3(64), 0, st, S, F);
+    else if (half) hipLaunchKernelGGL((features_k<false, true>), g, dim3(64), 0, st, S, F);
+    else hipLaunchKernelGGL(features_k<false>, g, dim3(64), 0, st, S, F);
+}
+void launch_features_fill(const FeatureDev& F, unsigned n_light, hipStream_t st)
+{
+    hipLaunchKernelGGL(features_fill_k, dim3((F.n + 255u) / 256u), dim3(256), 0, st, F, n_light);
 }
 template <class PR>
 static void build_bounds_t(const void* d_vol, bool half, void* d_out, void* d_tmp_a, void* d_tmp_b, int nx, int ny, int nz, int radius, int brick, hipStream_t st)

@@ -96,6 +96,15 @@ static void usage()
            "                                                means are vp_denoise's from the adaptive records.  --planes-noise-out writes one\n"
            "                                                noise map per plane (PREFIX_sun.hdr, PREFIX_sky.hdr, PREFIX_trans.hdr).  One GPU;\n"
            "                                                not with --noise or --denoise\n"
+           "               [--features-out PREFIX [--feature-step DT] [--depth-tau TAU]]\n"
+           "                                                the feature pass (vp_render_features), a deterministic march along every pixel's\n"
+           "                                                camera ray with step DT (default 0.001), after the render and beside every other\n"
+           "                                                output: PREFIX_alpha.hdr = the expected per-channel opacity, PREFIX_depth.hdr =\n"
+           "                                                (first matter, where the luminance optical depth reaches TAU (default ln 2), last\n"
+           "                                                matter) as distances along the ray.  RGBE cannot hold inf: a depth that does not\n"
+           "                                                exist (no matter on the ray, TAU never reached) is written as 0 here; the library\n"
+           "                                                call keeps +inf.  Pixel-centre rays whatever --aa says; rank 0 marches the whole\n"
+           "                                                image with --gpus\n"
            "               [--sun X Y] [--batch F] [--out name(.ppm|.hdr)]\n"
            "               [--gpus N [--devices a,b,...]]   N contexts, pixel tiles dealt by vp_set_shard, one RCCL reduce;\n"
            "                                                a repeated device (e.g. --gpus 2 --devices 0,0) shares one GPU\n"
@@ -137,6 +146,8 @@ int main(int argc, char** argv)
     float       planes_tol[3] = {0.0f, 0.0f, 0.0f};
     const float planes_floor[3] = {1e-3f, 1e-3f, 1e-2f};   // (trans lives in [0, 1])
     std::string planes_noise_out;
+    std::string features_out;
+    vp_feature_params feat = {0.001f, VP_FEATURE_TAU_Z_DEFAULT};
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
@@ -268,6 +279,15 @@ int main(int argc, char** argv)
                 if (end == argv[i] || *end || !std::isfinite(gain[c])) { fprintf(stderr, "%s %s: three finite numbers\n", a.c_str(), argv[i]); usage(); return 2; }
             }
             relit = true;
+        }
+        else if (a == "--features-out") { need(1); features_out = argv[++i]; }
+        else if (a == "--feature-step" || a == "--depth-tau")
+        {
+            need(1);
+            char* end = nullptr;
+            const float v = strtof(argv[++i], &end);
+            if (end == argv[i] || *end || !std::isfinite(v) || !(v > 0.0f)) { fprintf(stderr, "%s %s: a finite number > 0\n", a.c_str(), argv[i]); usage(); return 2; }
+            (a == "--feature-step" ? feat.step : feat.tau_z) = v;
         }
         else if (a == "--planes-out") { need(1); planes_out = argv[++i]; }
         else if (a == "--planes-denoise") planes_denoise = true;
@@ -810,6 +830,29 @@ int main(int argc, char** argv)
             printf("wrote %s\n", name.c_str());
             vp_free(d_noise);
         }
+    if (!features_out.empty())
+    {
+        // the feature pass: a pass of its own behind the render, on rank 0 over the whole image, one camera ray per pixel
+        vp_float4* d_alpha = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+        vp_float4* d_depth = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+        if (!d_alpha || !d_depth || vp_set_shard(0, 1) || vp_set_subpixel(1) || vp_render_features(d_alpha, d_depth, &P, &feat) || vp_synchronize())
+        {
+            fprintf(stderr, "%s\n", vp_last_error());
+            return 1;
+        }
+        for (int k = 0; k < 2; k++)
+        {
+            const std::string name = features_out + (k ? "_depth.hdr" : "_alpha.hdr");
+            Image fi(W, H);
+            vp_download(fi.buffer(), k ? d_depth : d_alpha, (size_t)npix * sizeof(vp_float4));
+            if (k)   // RGBE has no inf: a depth that does not exist is written as 0
+                for (size_t q = 0; q < (size_t)npix * 4; q++) if (std::isinf(fi.buffer()[q])) fi.buffer()[q] = 0.0f;
+            fi.dump_hdr(name.c_str());
+            printf("wrote %s\n", name.c_str());
+        }
+        vp_free(d_alpha);
+        vp_free(d_depth);
+    }
     if (stats) vp_free(stats);
     if (stats2) vp_free(stats2);
     if (stats3) vp_free(stats3);

@@ -39,6 +39,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_adaptive_groups", "vp_render_adaptive_layers",
                  "vp_render_frames_group_layers", "vp_render_frames_group_layers_stats", "vp_relight_composite", "vp_test_group_layers_census",
                  "vp_render_adaptive_group_layers",
+                 "vp_render_features",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -118,6 +119,16 @@ class DenoiseParams(C.Structure):
 DENOISE_MAX_RADIUS, DENOISE_MAX_PATCH = 10, 3
 
 
+class FeatureParams(C.Structure):
+    """include/volpath.h vp_feature_params"""
+    _fields_ = [("step", C.c_float), ("tau_z", C.c_float)]
+
+
+# include/volpath.h VP_FEATURE_TAU_Z_DEFAULT (ln 2 as a float32 literal), VP_FEATURE_MAX_STEPS
+FEATURE_TAU_Z_DEFAULT = float(np.float32(0.6931472))
+FEATURE_MAX_STEPS = 1 << 20
+
+
 class VolpathError(RuntimeError):
     pass
 
@@ -165,6 +176,7 @@ def lib():
         L.vp_render_frames_group_layers.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_render_frames_group_layers_stats.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_render_adaptive_group_layers.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(Param), C.POINTER(AdaptivePlanes3), C.POINTER(AdaptiveResult)]
+        L.vp_render_features.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Param), C.POINTER(FeatureParams)]
         L.vp_relight_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float)] * 2 + [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_float]
         L.vp_test_group_layers_census.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.vp_read_counters.argtypes = [C.POINTER(Counters), C.c_int]
@@ -577,6 +589,27 @@ def denoise(dst_ptr, src_ptr, stats_ptr, width, height, radius=5, patch=1, k=0.4
     (default: src itself), colours from src; queued on the context's stream, never synchronises"""
     dp = DenoiseParams(radius, patch, k)
     _chk(lib().vp_denoise(dst_ptr, src_ptr, stats_ptr, guide_ptr, guide_stats_ptr, width, height, C.byref(dp)))
+
+
+def render_features(P, step, tau_z=FEATURE_TAU_Z_DEFAULT, alpha_ptr=None, depth_ptr=None):
+    """the feature pass (vp_render_features): the deterministic march along every camera ray with a fixed step.  alpha = per-channel
+    opacity (w: optical depth per unit sigma_t), depth = (first matter, where the luminance optical depth reaches tau_z, last matter,
+    cover), +inf where a depth does not exist.  With both device pointers: fills them (queued on the context's stream, only the pixels
+    the context owns) and returns None; with neither: returns the two (height, width, 4) float32 arrays"""
+    fp = FeatureParams(step, tau_z)
+    if (alpha_ptr is None) != (depth_ptr is None):
+        raise ValueError("render_features: give both device buffers or neither")
+    if alpha_ptr is not None:
+        _chk(lib().vp_render_features(alpha_ptr, depth_ptr, C.byref(P), C.byref(fp)))
+        return None
+    a, d = DeviceBuffer(P.width, P.height), DeviceBuffer(P.width, P.height)
+    try:
+        _chk(lib().vp_render_features(a.ptr, d.ptr, C.byref(P), C.byref(fp)))
+        synchronize()
+        return a.download(), d.download()
+    finally:
+        a.free()
+        d.free()
 
 
 def set_denoise_form(form):

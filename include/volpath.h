@@ -600,6 +600,51 @@ int vp_render_adaptive_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float
                                     vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, vp_pixel_stats* d_trans_stats,
                                     int first_frame, int max_frames, const Param* p, const vp_adaptive_planes3* a, vp_adaptive_result* result);
 
+/* ---- Feature pass: ray-marched opacity and depth planes per pixel
+ * Every plane above is a Monte-Carlo estimate.  vp_render_features is deterministic: the march of precompute_opacity -- midpoint rule,
+ * fixed step -- along each pixel's CAMERA ray, writing the expected per-channel opacity of the pixel and three depths (a Z pass).
+ *
+ * THE DEFINITION.  binary32 throughout, one rounding per operation, no contraction, in the order written; the exact arithmetic whatever
+ * vp_set_arithmetic says (as scale, gamma_correct and vp_denoise).  For every pixel (x, y) the context owns (vp_set_shard), i = y * width + x:
+ *   (ro, rd) = camera_ray of the pixel; hit, tn, tf = what intersect_box(ro, rd) leaves -- the seven values vp_test_camera_ray reports
+ *   for the pixel in an exact-mode context.  if (tn <= 0.0f) tn = 0.0f (as precompute_opacity).
+ *   sy = (0.2126f * sigma_t.x + 0.7152f * sigma_t.y) + 0.0722f * sigma_t.z, once.
+ *   Not hit: alpha[i] = (0, 0, 0, 0), depth[i] = (+inf, +inf, +inf, 0).
+ *   Hit: s = 0.0f, zf = zt = zb = +inf, cover = 0.0f, reached = false; then for k = 0, 1, 2, ... (k < 2^24: never reached, see step below)
+ *       t = tn + ((float)k + 0.5f) * step;      stop as soon as !(t < tf)
+ *       rho = sample_density01(ro + rd * t)     -- the integrator's fetch (vp_test_sample_density): current filter mode, any volume format
+ *       s = s + rho
+ *       if (rho > 0.0f) { if (cover == 0.0f) zf = t;  zb = t;  cover = 1.0f; }
+ *       if (!reached && (((s * step) * p->density) * sy >= tau_z)) { zt = t; reached = true; }
+ *     and after the loop
+ *       tau = (s * step) * p->density
+ *       alpha[i].c = 1.0f - expf_(-(tau * sigma_t.c)) for c = x, y, z, expf_ the exact-mode exponential of vp_test_math (which = 1)
+ *       alpha[i].w = tau;   depth[i] = (zf, zt, zb, cover)
+ *   alpha.xyz: the expected per-channel opacity of the pixel by the midpoint rule -- what 1 - trans.xyz / n of a layers render converges
+ *   to; alpha.w: the optical depth per unit sigma_t.  zf / zb: where the ray first / last meets matter; zt: where the luminance optical
+ *   depth reaches tau_z (a "surface" depth that ignores wisps; VP_FEATURE_TAU_Z_DEFAULT = ln 2: half of what lies behind is gone).
+ *   Depths are distances along the unit camera ray; a depth that does not exist is +inf, the far convention of Z passes, and cover
+ *   (1.0f: the ray met matter) tells the two cases apart.
+ *   Obeys vp_set_shard (owned pixels only are written), every volume format, cell order, filter mode and estimator setting -- the
+ *   estimator only selects which per-pixel tables exist and never changes a result.  Ignores the random stream, the environment, the
+ *   sun, brightness, albedo and g; needs a volume and a camera, no environment map.  Asynchronous on the context's stream, behind what
+ *   is queued there.  It builds the per-view table and the pixel lists as vp_prepare does (found cached after a render of the view),
+ *   stops no look-ahead batch for anything else and leaves nothing behind: a vp_render_frames, plane or adaptive call after it renders
+ *   the bits it rendered before.
+ *   Performance only, same bits: the box-missing pixel class is filled with its constant, the light class (whole chord certified empty)
+ *   with what the definition gives for a march of zeros, and a general pixel starts behind the certified-empty stretch of its chord
+ *   (word [4] of vp_get_pixel_table: a step in there adds +0.0f to s and meets none of the three conditions).  VP_NO_FEATURE_SKIP=1
+ *   (read when the context first uses its device) switches the three off: every pixel whose ray hits the box marches its whole chord.
+ *   VP_E_ARG, before the device is touched and with both buffers untouched: any NULL pointer, d_alpha == d_depth, a step or a tau_z that
+ *   is not finite or not > 0, width or height < 1 (or > 65535, as every render call).  VP_E_STATE likewise: no volume or no camera; a
+ *   sub-pixel factor above 1 -- NOT BUILT: the box-filtered mean of depths that may be infinite is another definition.  Then, with the
+ *   volume's box, VP_E_ARG for a step so small that the box diagonal (computed on the host in binary64) takes more than
+ *   VP_FEATURE_MAX_STEPS steps -- no chord is longer, so (float)k stays exact. */
+typedef struct { float step, tau_z; } vp_feature_params;   /* 8 bytes */
+#define VP_FEATURE_TAU_Z_DEFAULT 0.6931472f            /* ln 2: half of what lies behind is gone */
+#define VP_FEATURE_MAX_STEPS (1u << 20)
+int vp_render_features(vp_float4* d_alpha, vp_float4* d_depth, const Param* p, const vp_feature_params* fp);
+
 typedef struct
 {
     uint64_t samples;
