@@ -5,7 +5,7 @@
 // vp_render_adaptive_groups / vp_render_adaptive_layers: the same rounds on the two planes of a groups or layers render -- active means
 // frozen in neither plane's record, and a round freezes both records of a pixel when both meet their plane's criterion.
 // vp_render_adaptive_group_layers: the same on the three planes of a group-layers render, with three records per pixel.
-// vp_denoise: the filter of the output stage that reads the records (vp_denoise.hip).
+// vp_denoise: the filter of the output stage that reads the records (vp_denoise.hip); vp_denoise_guided: the same with feature planes.
 #include <climits>
 
 #include "vp_state.h"
@@ -15,6 +15,8 @@ static_assert(offsetof(vp_pixel_stats, sum_y2) == 8 && offsetof(vp_pixel_stats, 
 static_assert(sizeof(vp_adaptive_planes) == 24, "vp_adaptive_planes layout (include/volpath.h)");
 static_assert(sizeof(vp_adaptive_planes3) == 32 && offsetof(vp_adaptive_planes3, floor_y) == 12, "vp_adaptive_planes3 layout (include/volpath.h)");
 static_assert(offsetof(vp_adaptive_planes3, min_frames) == 24 && offsetof(vp_adaptive_planes3, round_frames) == 28, "vp_adaptive_planes3 layout");
+static_assert(sizeof(vp_denoise_feature) == 16 && offsetof(vp_denoise_feature, channel) == 8 && offsetof(vp_denoise_feature, sigma) == 12, "vp_denoise_feature layout");
+static_assert(VP_DENOISE_MAX_FEATURES == sizeof(vp::DenoiseFeaturesDev::chan) / sizeof(const float*), "DenoiseFeaturesDev holds VP_DENOISE_MAX_FEATURES features");
 static_assert(offsetof(vp::PixelStatsDev, n) == 16 && offsetof(vp::PixelStatsDev, flags) == 20, "PixelStatsDev mirrors vp_pixel_stats");
 
 namespace vph __attribute__((visibility("hidden")))
@@ -197,6 +199,46 @@ int vp_denoise(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_sta
     if (!guide) { guide = src; d_guide_stats = d_stats; }
     launch_denoise((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, width, height,
                    dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
+    HIPCHK(hipGetLastError());
+    G.last_denoise_form = G.denoise_form;
+    return VP_OK;
+}
+int vp_denoise_guided(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
+                      const vp_denoise_feature* features, int n_features, int width, int height, const vp_denoise_params* dp)
+{
+    if (n_features < 0 || n_features > VP_DENOISE_MAX_FEATURES)
+        return fail(VP_E_ARG, "vp_denoise_guided: %d features outside 0..%d", n_features, VP_DENOISE_MAX_FEATURES);
+    if (n_features > 0 && !features) return fail(VP_E_ARG, "vp_denoise_guided: %d features and no array of them", n_features);
+    DenoiseFeaturesDev fd = {};
+    for (int j = 0; j < n_features; j++)
+    {
+        const vp_denoise_feature& f = features[j];
+        if (!f.plane) return fail(VP_E_ARG, "vp_denoise_guided: feature %d has no plane", j);
+        if (f.plane == dst) return fail(VP_E_ARG, "vp_denoise_guided: feature %d is dst (the call reads neighbours)", j);
+        if (f.channel < 0 || f.channel > 3) return fail(VP_E_ARG, "vp_denoise_guided: feature %d: channel %d outside 0..3", j, f.channel);
+        if (!std::isfinite(f.sigma) || !(f.sigma > 0.0f)) return fail(VP_E_ARG, "vp_denoise_guided: feature %d: sigma must be a finite number > 0", j);
+        const float g = 1.0f / ((2.0f * f.sigma) * f.sigma);
+        if (!std::isfinite(g) || !(g > 0.0f)) return fail(VP_E_ARG, "vp_denoise_guided: feature %d: 1 / (2 sigma^2) of sigma %g is not a finite number > 0", j, (double)f.sigma);
+        fd.chan[j] = (const float*)f.plane + f.channel;
+        fd.g[j] = g;
+    }
+    fd.n = n_features;
+    if (n_features == 0) return vp_denoise(dst, src, d_stats, guide, d_guide_stats, width, height, dp);
+    if (!dst || !src || !d_stats || !dp) return fail(VP_E_ARG, "vp_denoise_guided: null pointer");
+    if (!guide != !d_guide_stats) return fail(VP_E_ARG, "vp_denoise_guided: guide and d_guide_stats are given together or not at all");
+    if (dst == src || dst == guide) return fail(VP_E_ARG, "vp_denoise_guided: in place is not possible (the call reads neighbours)");
+    if (width < 1 || height < 1 || (long long)width * height > INT_MAX) return fail(VP_E_ARG, "vp_denoise_guided: image %d x %d", width, height);
+    if (dp->radius < 0 || dp->radius > VP_DENOISE_MAX_RADIUS) return fail(VP_E_ARG, "vp_denoise_guided: radius %d outside 0..%d", dp->radius, VP_DENOISE_MAX_RADIUS);
+    if (dp->patch < 0 || dp->patch > VP_DENOISE_MAX_PATCH) return fail(VP_E_ARG, "vp_denoise_guided: patch %d outside 0..%d", dp->patch, VP_DENOISE_MAX_PATCH);
+    if (!std::isfinite(dp->k) || !(dp->k > 0.0f)) return fail(VP_E_ARG, "vp_denoise_guided: k must be a finite number > 0");
+    if (G.denoise_form == 0 && denoise_guided_lds_bytes(dp->radius, dp->patch, n_features) > DENOISE_LDS_LIMIT)
+        return fail(VP_E_STATE, "vp_denoise_guided: radius %d, patch %d, %d features need %zu bytes of LDS, a workgroup has %zu", dp->radius, dp->patch, n_features,
+                    denoise_guided_lds_bytes(dp->radius, dp->patch, n_features), DENOISE_LDS_LIMIT);
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (!guide) { guide = src; d_guide_stats = d_stats; }
+    launch_denoise_guided((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, fd, width,
+                          height, dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
     HIPCHK(hipGetLastError());
     G.last_denoise_form = G.denoise_form;
     return VP_OK;

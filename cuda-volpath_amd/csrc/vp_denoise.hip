@@ -8,6 +8,9 @@
 //     tile's F-halo plane are computed once each into LDS (2.1 per thread at F = 3 instead of 49) and every thread sums its patch
 //     from there.  The plane is double buffered: one barrier per offset.
 //   denoise_plain_k (form 1): one thread per pixel, straight from global memory, looping over the definition.  The cross-check.
+//   denoise_guided_tiled_k / denoise_guided_plain_k: the two forms of vp_denoise_guided, kernels of their
+//     own so that the two above stay as they are: the same passes, plus NF feature channels staged once into LDS planes shaped like
+//     the colour planes and a per-pixel-pair feature distance that caps the weight.
 // LDS layout (cdna_hip_programming.md section 2: ds_read_b32 / ds_write_b32 bank = dword address mod 32 within a 32-lane half):
 // every plane is one float per element, structure of arrays, and a half-wave is one tile row, so the patch reads and the colour
 // reads of a half-wave are 32 consecutive dwords whatever the pitch.  The fill of the e plane walks it linearly, so a half-wave can
@@ -190,6 +193,181 @@ __global__ __launch_bounds__(256) void denoise_plain_k(float4* dst, const float4
     }
     dst[idx] = out;
 }
+
+// ---- vp_denoise_guided: the same filter with the weight of an offset cut by a distance of noise-free features
+// the patch distance as patch_weight scales and clamps it, before the exponential
+__device__ __forceinline__ float patch_distance(float D, float inv_area)
+{
+    D = D * inv_area;
+    return D > 0.0f ? D : 0.0f;
+}
+// t_j of the header: equal values -- two equal infinities among them -- agree exactly
+__device__ __forceinline__ float feature_term(float fa, float fb, float g)
+{
+    const float d = fa - fb;
+    return fa == fb ? 0.0f : (d * d) * g;
+}
+__device__ __forceinline__ float guided_weight(float D, float Df) { return expf_(-(Df > D ? Df : D)); }
+
+// denoise_tiled_k with NF feature planes of the tile plus an R halo behind the e planes, pitch and indexing of the colour planes:
+// fb of a half-wave is 32 consecutive dwords, fa stays in registers, no barrier more than denoise_tiled_k has
+template <int F, int NF>
+__global__ __launch_bounds__(DN_TX * DN_TY) void denoise_guided_tiled_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
+                                                                         const PixelStatsDev* gstats, DenoiseFeaturesDev feat, int W, int H, int R, float k2)
+{
+    constexpr int EW = DN_TX + 2 * F, EH = DN_TY + 2 * F;
+    constexpr int YW = EW + 32;
+    extern __shared__ float lds[];
+    const int YH = DN_TY + 2 * (R + F), CW = DN_TX + 2 * R, CH = DN_TY + 2 * R;
+    float* Ly = lds;
+    float* Lv = Ly + YW * YH;
+    float* Lc = Lv + YW * YH;             // three planes of CW * CH
+    float* Le = Lc + 3 * CW * CH;         // two planes of EW * EH
+    float* Lf = Le + 2 * EW * EH;         // NF planes of CW * CH
+    const int tid = threadIdx.x, tx = tid & (DN_TX - 1), ty = tid / DN_TX;
+    const int x0 = blockIdx.x * DN_TX, y0 = blockIdx.y * DN_TY;
+    const int px = x0 + tx, py = y0 + ty;
+    const bool inside = px < W && py < H;
+    const int  pi = clampi(py, H - 1) * W + clampi(px, W - 1);
+    const float4 A  = src[pi];
+    const float  sp = inv_count(stats[pi].n);
+    const float  vme = mean_variance(gstats[pi]);
+    float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
+    if (!__syncthreads_or(inside && vme != 0.0f))
+    {
+        if (inside) dst[pi] = out;
+        return;
+    }
+    const int halo = R + F;
+    for (int i = tid; i < (DN_TX + 2 * halo) * YH; i += DN_TX * DN_TY)
+    {
+        const int r = i / (DN_TX + 2 * halo), c = i - r * (DN_TX + 2 * halo);
+        float y, v;
+        guide_yv(guide, gstats, clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1), y, v);
+        Ly[r * YW + c] = y;
+        Lv[r * YW + c] = v;
+    }
+    for (int i = tid; i < CW * CH; i += DN_TX * DN_TY)
+    {
+        const int r = i / CW, c = i - r * CW;
+        const int g = clampi(y0 - R + r, H - 1) * W + clampi(x0 - R + c, W - 1);
+        const float4 B = src[g];
+        const float  s = inv_count(stats[g].n);
+        Lc[i] = B.x * s;
+        Lc[CW * CH + i] = B.y * s;
+        Lc[2 * CW * CH + i] = B.z * s;
+        // (a clamped position's feature is staged but never read: offsets that leave the image are skipped)
+#pragma unroll
+        for (int j = 0; j < NF; j++) Lf[j * (CW * CH) + i] = feat.chan[j][4 * (size_t)g];
+    }
+    __syncthreads();
+    const bool  filtered = inside && vme != 0.0f;
+    const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
+    float fa[NF];
+#pragma unroll
+    for (int j = 0; j < NF; j++) fa[j] = Lf[j * (CW * CH) + (ty + R) * CW + tx + R];
+    float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
+    int buf = 0;
+    for (int oy = -R; oy <= R; oy++)
+        for (int ox = -R; ox <= R; ox++, buf ^= 1)
+        {
+            float* E = Le + buf * (EW * EH);
+            const int shift = oy * YW + ox;
+            for (int i = tid; i < EW * EH; i += DN_TX * DN_TY)
+            {
+                const int r = i / EW, c = i - r * EW;
+                const int a = (r + R) * YW + (c + R);
+                E[i] = pair_term(Ly[a], Lv[a], Ly[a + shift], Lv[a + shift], k2);
+            }
+            __syncthreads();   // (the other buffer is written next: its readers passed this barrier)
+            const int qx = px + ox, qy = py + oy;
+            if (filtered && qx >= 0 && qx < W && qy >= 0 && qy < H)
+            {
+                float D = 0.0f;
+#pragma unroll
+                for (int dy = 0; dy <= 2 * F; dy++)
+                {
+                    float row = 0.0f;
+#pragma unroll
+                    for (int dx = 0; dx <= 2 * F; dx++) row = row + E[(ty + dy) * EW + tx + dx];
+                    D = D + row;
+                }
+                const int ci = (ty + R + oy) * CW + tx + R + ox;
+                float Df = 0.0f;
+#pragma unroll
+                for (int j = 0; j < NF; j++) Df = Df + feature_term(fa[j], Lf[j * (CW * CH) + ci], feat.g[j]);
+                const float w = guided_weight(patch_distance(D, inv_area), Df);
+                den = den + w;
+                nr  = nr + w * Lc[ci];
+                ng  = ng + w * Lc[CW * CH + ci];
+                nb  = nb + w * Lc[2 * CW * CH + ci];
+            }
+        }
+    if (filtered) { out.x = nr / den; out.y = ng / den; out.z = nb / den; }
+    if (inside) dst[pi] = out;
+}
+
+__global__ __launch_bounds__(256) void denoise_guided_plain_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
+                                                              const PixelStatsDev* gstats, DenoiseFeaturesDev feat, int W, int H, int R, int F, float k2)
+{
+    const int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= W * H) return;
+    const int py = idx / W, px = idx - py * W;
+    const float4 A  = src[idx];
+    const float  sp = inv_count(stats[idx].n);
+    float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
+    if (mean_variance(gstats[idx]) != 0.0f)
+    {
+        const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
+        float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
+        for (int oy = -R; oy <= R; oy++)
+            for (int ox = -R; ox <= R; ox++)
+            {
+                const int qx = px + ox, qy = py + oy;
+                if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                float D = 0.0f;
+                for (int dy = -F; dy <= F; dy++)
+                {
+                    float row = 0.0f;
+                    for (int dx = -F; dx <= F; dx++)
+                    {
+                        float ya, va, yb, vb;
+                        guide_yv(guide, gstats, clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1), ya, va);
+                        guide_yv(guide, gstats, clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1), yb, vb);
+                        row = row + pair_term(ya, va, yb, vb, k2);
+                    }
+                    D = D + row;
+                }
+                const int q = qy * W + qx;
+                float Df = 0.0f;
+#pragma unroll   // (constant indices into the by-value struct: it stays in scalar registers)
+                for (int j = 0; j < 4; j++)
+                    if (j < feat.n) Df = Df + feature_term(feat.chan[j][4 * (size_t)idx], feat.chan[j][4 * (size_t)q], feat.g[j]);
+                const float  w = guided_weight(patch_distance(D, inv_area), Df);
+                const float4 B = src[q];
+                const float  s = inv_count(stats[q].n);
+                den = den + w;
+                nr  = nr + w * (B.x * s);
+                ng  = ng + w * (B.y * s);
+                nb  = nb + w * (B.z * s);
+            }
+        out.x = nr / den; out.y = ng / den; out.z = nb / den;
+    }
+    dst[idx] = out;
+}
+
+template <int F>
+void launch_guided_tiled(int NF, dim3 grid, dim3 block, size_t lds, hipStream_t st, float4* dst, const float4* src, const PixelStatsDev* stats,
+                         const float4* guide, const PixelStatsDev* gstats, const DenoiseFeaturesDev& feat, int W, int H, int R, float k2)
+{
+    switch (NF)
+    {
+    case 1: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 1>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
+    case 2: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 2>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
+    case 3: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 3>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
+    default: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 4>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
+    }
+}
 }  // namespace
 
 size_t denoise_lds_bytes(int R, int F)
@@ -215,6 +393,29 @@ void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, 
     case 1: hipLaunchKernelGGL(denoise_tiled_k<1>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
     case 2: hipLaunchKernelGGL(denoise_tiled_k<2>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
     default: hipLaunchKernelGGL(denoise_tiled_k<3>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
+    }
+}
+size_t denoise_guided_lds_bytes(int R, int F, int n_features)
+{
+    return denoise_lds_bytes(R, F) + (size_t)n_features * (DN_TX + 2 * R) * (DN_TY + 2 * R) * sizeof(float);
+}
+void launch_denoise_guided(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats,
+                           const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st)
+{
+    if (form == 1)
+    {
+        hipLaunchKernelGGL(denoise_guided_plain_k, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, st, dst, src, stats, guide, gstats, feat, W, H, R,
+                           F, k2);
+        return;
+    }
+    const dim3   grid((W + DN_TX - 1) / DN_TX, (H + DN_TY - 1) / DN_TY), block(DN_TX * DN_TY);
+    const size_t lds = denoise_guided_lds_bytes(R, F, feat.n);
+    switch (F)
+    {
+    case 0: launch_guided_tiled<0>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
+    case 1: launch_guided_tiled<1>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
+    case 2: launch_guided_tiled<2>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
+    default: launch_guided_tiled<3>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
     }
 }
 }  // namespace vp

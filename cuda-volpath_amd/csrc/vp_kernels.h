@@ -302,6 +302,16 @@ void launch_stats_rel_error(float* dst, const PixelStatsDev* stats, int size, fl
 size_t denoise_lds_bytes(int R, int F);
 void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, int W, int H, int R,
                     int F, float k2, int form, hipStream_t st);
+// the same filter with the feature term (include/volpath.h vp_denoise_guided): n >= 1 features, chan[j] the address of feature j's
+// channel at pixel 0 (pixel i at chan[j][4 * i]), g[j] = 1 / (2 sigma_j^2) as the host rounded it.  Form 0 stages the channels into
+// n more LDS planes: denoise_guided_lds_bytes(R, F, n) dynamic bytes per workgroup, which the caller holds against
+// DENOISE_LDS_LIMIT before it launches
+struct DenoiseFeaturesDev { const float* chan[4]; float g[4]; int n; };
+// what a workgroup may take without an attribute call, less the kernels' 256 static bytes (the vote of __syncthreads_or)
+constexpr size_t DENOISE_LDS_LIMIT = 64 * 1024 - 256;
+size_t denoise_guided_lds_bytes(int R, int F, int n_features);
+void launch_denoise_guided(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats,
+                           const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st);
 // bricks: cells in 4x4x4 bricks (vp_device.h cell_index); the buffer then holds ceil(n/4)^3 * 64 cells
 void launch_pack_u8(const unsigned char* vol, uint2* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);
 void launch_pack_f32(const float* vol, float* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);

@@ -43,6 +43,12 @@ static void usage()
            "                                                per-pixel luminance variance; search window (2R+1)^2, R <= 10, default 5; patch\n"
            "                                                (2F+1)^2, F <= 3, default 1; strength K > 0, default 0.45).  The frames then go\n"
            "                                                through vp_render_frames_stats (or --noise).  One GPU, like --noise\n"
+           "               [--denoise-features [--denoise-sigma-alpha SA] [--denoise-sigma-depth SZ]]\n"
+           "                                                with --denoise: the filter is vp_denoise_guided, its weights cut by the feature\n"
+           "                                                pass's planes (vp_render_features at --feature-step / --depth-tau, run first):\n"
+           "                                                the green opacity alpha.y with sigma SA (default 0.2), the depth at which the\n"
+           "                                                optical depth reaches TAU with sigma SZ (default 0.2, in scene units) and the\n"
+           "                                                cover flag with SA.  One GPU; not with --aa above 1\n"
            "               [--layers-out PREFIX] [--over R G B]\n"
            "                                                compositing layers (vp_render_frames_layers): the frames are rendered as a\n"
            "                                                foreground F and a per-channel transmittance T, pixel = F + T o B for any\n"
@@ -130,6 +136,8 @@ int main(int argc, char** argv)
     std::string noise_out;
     bool        denoise = false;
     vp_denoise_params dn = {5, 1, 0.45f};   // (from a 64 x 48 table, not tuned: DESIGN.md section 2.4)
+    bool        denoise_features = false;
+    float       dn_sigma_alpha = 0.2f, dn_sigma_depth = 0.2f;   // (the best cell of a 3 x 3 grid on that scene: DESIGN.md section 2.13)
     std::string layers_out;
     bool        over = false;
     float       over_rgb[3] = {0.0f, 0.0f, 0.0f};
@@ -255,6 +263,15 @@ int main(int argc, char** argv)
                 return 2;
             }
         }
+        else if (a == "--denoise-features") denoise_features = true;
+        else if (a == "--denoise-sigma-alpha" || a == "--denoise-sigma-depth")
+        {
+            need(1);
+            char* end = nullptr;
+            const float v = strtof(argv[++i], &end);
+            if (end == argv[i] || *end || !std::isfinite(v) || !(v > 0.0f)) { fprintf(stderr, "%s %s: a finite number > 0\n", a.c_str(), argv[i]); usage(); return 2; }
+            (a == "--denoise-sigma-alpha" ? dn_sigma_alpha : dn_sigma_depth) = v;
+        }
         else if (a == "--layers-out") { need(1); layers_out = argv[++i]; }
         else if (a == "--over")
         {
@@ -330,6 +347,12 @@ int main(int argc, char** argv)
     if (denoise && gpus > 1)
     {
         fprintf(stderr, "--denoise with --gpus %d: the filter reads per-pixel statistics, which are not reduced across ranks; use one GPU\n", gpus);
+        return 2;
+    }
+    if (denoise_features && (!denoise || aa > 1))
+    {
+        if (!denoise) fprintf(stderr, "--denoise-features needs --denoise: it cuts the weights of that filter (the per-plane filters do not take it)\n");
+        else fprintf(stderr, "--denoise-features with --aa %d: the feature pass marches pixel-centre rays and refuses a sub-pixel factor; use --aa 1\n", aa);
         return 2;
     }
     // --planes-out: sun, sky and trans from one render; the gains and --over are then its parameters, not a groups or a layers render's
@@ -757,9 +780,25 @@ int main(int argc, char** argv)
     else if (denoise)
     {
         // the filtered mean image: the division by each pixel's count is part of the call
-        if (vp_denoise(disp, accum[0], stats, nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        if (denoise_features)
+        {
+            // the feature pass first, then the filter with three of its channels: alpha.y, zt and the cover flag
+            vp_float4* d_alpha = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+            vp_float4* d_depth = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+            const vp_denoise_feature f3[3] = {{d_alpha, 1, dn_sigma_alpha}, {d_depth, 1, dn_sigma_depth}, {d_depth, 3, dn_sigma_alpha}};
+            if (!d_alpha || !d_depth || vp_render_features(d_alpha, d_depth, &P, &feat) || vp_denoise_guided(disp, accum[0], stats, nullptr, nullptr, f3, 3, W, H, &dn)
+                || vp_synchronize())
+            {
+                fprintf(stderr, "%s\n", vp_last_error());
+                return 1;
+            }
+            vp_free(d_alpha);
+            vp_free(d_depth);
+        }
+        else if (vp_denoise(disp, accum[0], stats, nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
         if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
         printf("denoised: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
+        if (denoise_features) printf("  weights cut by features: sigma alpha %g, sigma depth %g\n", dn_sigma_alpha, dn_sigma_depth);
     }
     else if (adaptive)
     {

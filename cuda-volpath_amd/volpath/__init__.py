@@ -40,6 +40,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_frames_group_layers", "vp_render_frames_group_layers_stats", "vp_relight_composite", "vp_test_group_layers_census",
                  "vp_render_adaptive_group_layers",
                  "vp_render_features",
+                 "vp_denoise_guided",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -119,6 +120,14 @@ class DenoiseParams(C.Structure):
 DENOISE_MAX_RADIUS, DENOISE_MAX_PATCH = 10, 3
 
 
+class DenoiseFeature(C.Structure):
+    """include/volpath.h vp_denoise_feature: channel `channel` (0..3 = x, y, z, w) of a float4 plane and its sigma"""
+    _fields_ = [("plane", C.c_void_p), ("channel", C.c_int), ("sigma", C.c_float)]
+
+
+DENOISE_MAX_FEATURES = 4
+
+
 class FeatureParams(C.Structure):
     """include/volpath.h vp_feature_params"""
     _fields_ = [("step", C.c_float), ("tau_z", C.c_float)]
@@ -162,6 +171,7 @@ def lib():
         L.vp_stats_rel_error.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
         L.vp_denoise.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(DenoiseParams)]
         L.vp_set_denoise_form.argtypes = [C.c_int]
+        L.vp_denoise_guided.argtypes = [C.c_void_p] * 5 + [C.POINTER(DenoiseFeature), C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseParams)]
         L.vp_render_frames_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_int, C.c_float]
         L.vp_render_frames_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
@@ -589,6 +599,15 @@ def denoise(dst_ptr, src_ptr, stats_ptr, width, height, radius=5, patch=1, k=0.4
     (default: src itself), colours from src; queued on the context's stream, never synchronises"""
     dp = DenoiseParams(radius, patch, k)
     _chk(lib().vp_denoise(dst_ptr, src_ptr, stats_ptr, guide_ptr, guide_stats_ptr, width, height, C.byref(dp)))
+
+
+def denoise_guided(dst_ptr, src_ptr, stats_ptr, width, height, features=(), radius=5, patch=1, k=0.45, guide_ptr=None, guide_stats_ptr=None):
+    """denoise() with the weight of an offset cut by noise-free features (vp_denoise_guided): features is a sequence of
+    (plane_ptr, channel, sigma), at most DENOISE_MAX_FEATURES of them; none: denoise()'s bytes"""
+    dp = DenoiseParams(radius, patch, k)
+    feats = [(getattr(p, "value", p), c, s) for p, c, s in features]
+    arr = (DenoiseFeature * len(feats))(*[DenoiseFeature(p, c, s) for p, c, s in feats]) if feats else None
+    _chk(lib().vp_denoise_guided(dst_ptr, src_ptr, stats_ptr, guide_ptr, guide_stats_ptr, arr, len(feats), width, height, C.byref(dp)))
 
 
 def render_features(P, step, tau_z=FEATURE_TAU_Z_DEFAULT, alpha_ptr=None, depth_ptr=None):

@@ -352,6 +352,36 @@ int vp_denoise(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_sta
 int vp_set_denoise_form(int form);
 int vp_last_denoise_form(void);
 
+/* vp_denoise_guided: vp_denoise with the weight of an offset cut by a second distance, computed from noise-free feature planes
+ * (Rousselle, Manzi and Zwicker 2013: the weight is the smaller of the colour weight and the feature weight).  The planes are
+ * meant to be vp_render_features' (below); any vp_float4 image of the size of src serves.  DESIGN.md section 2.13.
+ *   The definition is vp_denoise's, word for word, with one change to the weight of an offset.  Let p be a pixel and o an offset
+ *   with q = p + o inside the image (offsets that leave the image are skipped as before: no feature is read at a clamped position),
+ *   and D vp_denoise's patch distance after the scaling by 1 / (2F+1)^2 and the clamp at 0.  Binary32, one rounding per operation,
+ *   no contraction, in the order written:
+ *     g_j = 1.0f / ((2.0f * sigma_j) * sigma_j)        once per call, on the host; the kernel receives it as it is
+ *     fa  = features[j].plane[p].channel_j             fb = features[j].plane[q].channel_j
+ *     t_j = (fa == fb) ? 0.0f : ((fa - fb) * (fa - fb)) * g_j
+ *     Df  = 0.0f;  Df = Df + t_j  for j = 0 .. n_features-1 in order
+ *     Dg  = Df > D ? Df : D
+ *     w   = expf_(-Dg), the exact-mode exponential whatever vp_set_arithmetic says
+ *   fa == fb makes two equal infinities agree: a depth that "does not exist" on both sides gives 0.  An infinity against a finite
+ *   value gives t = +inf, Dg = +inf and w = expf_(-inf) = 0 (the first line of expf_): such a pair is never mixed.  At the centre
+ *   offset Df = 0 and D = 0, so w = 1 and the denominator stays >= 1.  Features are assumed free of NaN.
+ *   Everything else is vp_denoise's: the mean colours, y, v and the pair term, the two sum orders, the v_p == 0 exception,
+ *   dst.w = src.w * s_p, the role of the guide pair; no scene needed, asynchronous on the context's stream, never synchronises.
+ *   vp_set_denoise_form applies and vp_last_denoise_form reports it.  With n_features == 0 (features may then be NULL) the output is
+ *   vp_denoise's byte for byte.  Feature planes may be src, guide or each other.
+ *   Refused with VP_E_ARG before the device is touched, dst untouched: everything vp_denoise refuses; n_features outside
+ *   0..VP_DENOISE_MAX_FEATURES; features == NULL with n_features > 0; a NULL plane; a plane equal to dst; a channel outside 0..3; a
+ *   sigma that is not finite or not > 0; a sigma whose g_j is not finite or not > 0 (this keeps 0 * inf out of the kernel). */
+typedef struct { const vp_float4* plane; int channel; float sigma; } vp_denoise_feature;   /* channel 0..3 = x, y, z, w; 16 bytes */
+#define VP_DENOISE_MAX_FEATURES 4
+int vp_denoise_guided(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats,
+                      const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
+                      const vp_denoise_feature* features, int n_features,
+                      int width, int height, const vp_denoise_params* dp);
+
 /* Compositing layers: a foreground F and a per-channel transmittance T with  pixel = F + T o B  for any
  * background B -- another sky, a plate, a second render.  vp_render_frames bakes the context's own sky into every sample and keeps
  * the reference's heat value in w; these two calls are what a compositor needs instead.
