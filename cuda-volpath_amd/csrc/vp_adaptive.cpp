@@ -21,16 +21,14 @@ static_assert(offsetof(vp::PixelStatsDev, n) == 16 && offsetof(vp::PixelStatsDev
 
 namespace vph __attribute__((visibility("hidden")))
 {
-// the active pixels of the cached lists into G.d_act, their three counts into cnt: one small synchronisation
-// (d_stats2: the second plane's records of an adaptive plane call, else null -- active then means: frozen in neither; d_stats3: the third
-// plane's of an adaptive group-layers call, else null -- frozen in none of the three)
-static int compact_active(const Param* p, const vp_pixel_stats* d_stats, const vp_pixel_stats* d_stats2, const vp_pixel_stats* d_stats3, unsigned cnt[3])
+// the active pixels of the cached lists into G.d_act, their three counts into cnt: one small synchronisation (active: frozen in none of
+// the records of S's planes)
+static int compact_active(const Param* p, const PlaneSet& S, unsigned cnt[3])
 {
     const unsigned n[3] = {G.n_general, G.n_light, G.n_miss};
     const unsigned nblocks = compact_blocks(n[0] + n[1] + n[2]);
     unsigned* d_totals = G.d_act_scratch + (size_t)3 * nblocks;
-    launch_compact_active(G.d_tiles, n, p->width, (const PixelStatsDev*)d_stats, (const PixelStatsDev*)d_stats2, (const PixelStatsDev*)d_stats3,
-                          G.d_act_scratch, d_totals, G.d_act, G.stream);
+    launch_compact_active(G.d_tiles, n, p->width, S, G.d_act_scratch, d_totals, G.d_act, G.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(cnt, d_totals, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, G.stream));
     HIPCHK(hipStreamSynchronize(G.stream));
@@ -47,13 +45,9 @@ static int reserve_active(size_t n)
     HIPCHK(G.d_act_scratch.grow(words * sizeof(unsigned)));
     return VP_OK;
 }
-// What vp_render_adaptive and the adaptive plane calls share once their arguments are checked: the rounds.  T carries the records
-// and the criterion (one record buffer, or one per plane: StatsDev::plane2); d1 is the second accumulator of a plane call (groups:
-// the sky accumulator, else the transmittance accumulator), null for vp_render_adaptive; d2 is the transmittance accumulator of a
-// group-layers call (d1 then the sky accumulator, T.plane3 the third record buffer), else null.  Rounds are serial and run on the caller's
-// stream: look-ahead batches stop, pipelined launches are waited for.
-static int adaptive_rounds(vp_float4* d0, vp_float4* d1, vp_float4* d2, bool groups, const StatsDev& T, int first_frame, int max_frames, int round_frames, const Param* p,
-                           vp_adaptive_result* result)
+// What the adaptive calls share once their arguments are checked: the rounds.  S carries the planes, their records and the criterion.
+// Rounds are serial and run on the caller's stream: look-ahead batches stop, pipelined launches are waited for.
+static int adaptive_rounds(const PlaneSet& S, int first_frame, int max_frames, int round_frames, const Param* p, vp_adaptive_result* result)
 {
     int rc = la_quiesce();
     if (rc) return rc;
@@ -61,10 +55,8 @@ static int adaptive_rounds(vp_float4* d0, vp_float4* d1, vp_float4* d2, bool gro
     const size_t n_all = (size_t)G.n_general + G.n_light + G.n_miss;
     if (n_all == 0) return VP_OK;          // a shard without a tile
     if ((rc = reserve_active(n_all))) return rc;
-    const vp_pixel_stats *r0 = (const vp_pixel_stats*)T.stats, *r1 = (const vp_pixel_stats*)T.plane2, *r2 = (const vp_pixel_stats*)T.plane3;
-    vp_float4 *d_trans = d2 ? d2 : d1 && !groups ? d1 : nullptr, *d_sky = d1 && groups ? d1 : nullptr;
     unsigned cnt[3] = {0, 0, 0};
-    if ((rc = compact_active(p, r0, r1, r2, cnt))) return rc;
+    if ((rc = compact_active(p, S, cnt))) return rc;
     int done = 0;
     unsigned rounds = 0;
     unsigned long long samples = 0;
@@ -72,35 +64,38 @@ static int adaptive_rounds(vp_float4* d0, vp_float4* d1, vp_float4* d2, bool gro
     {
         const int f = std::min(round_frames, max_frames - done);
         const PixelLists PL = {G.d_act, cnt[0], cnt[1], cnt[2]};
-        if ((rc = do_render(d0, first_frame + done, f, p, false, nullptr, &PL, &T, d_trans, d_sky))) return rc;
+        if ((rc = do_render((vp_float4*)S.acc[0], first_frame + done, f, p, false, nullptr, &PL, &S))) return rc;
         samples += ((unsigned long long)cnt[0] + cnt[1] + cnt[2]) * (unsigned long long)f;   // (one per pixel and frame, not per plane)
         done += f; rounds++;
         if (result) { result->samples = samples; result->rounds = rounds; result->frames_used = (uint32_t)done; }
-        if ((rc = compact_active(p, r0, r1, r2, cnt))) return rc;   // round k + 1 needs round k's decisions
+        if ((rc = compact_active(p, S, cnt))) return rc;   // round k + 1 needs round k's decisions
     }
     if (result) result->active_left = cnt[0] + cnt[1] + cnt[2];
     return VP_OK;
 }
-// vp_render_adaptive_groups / vp_render_adaptive_layers: the refusals of the definition, in its order, then the rounds
-static int render_adaptive_planes(const char* fn, bool groups, vp_float4* d0, vp_float4* d1, vp_pixel_stats* r0, vp_pixel_stats* r1, int first_frame,
-                                  int max_frames, const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result)
+// vp_adaptive_planes / vp_adaptive_planes3 by their fields (all null / zero: the caller gave no struct)
+struct AdaptiveArgs { const float *rel_tol, *floor_y; int min_frames, round_frames; };
+template <class A> static AdaptiveArgs adaptive_args(const A* a) { return a ? AdaptiveArgs{a->rel_tol, a->floor_y, a->min_frames, a->round_frames} : AdaptiveArgs{}; }
+// vp_render_adaptive_groups / _layers / _group_layers: the refusals of the definition, in its order, then the rounds
+static int render_adaptive_planes(const char* fn, PlaneSet S, int first_frame, int max_frames, const Param* p, const AdaptiveArgs& a, vp_adaptive_result* result)
 {
+    static const char* const kCount[] = {"", "one", "two", "three"};
     if (result) memset(result, 0, sizeof *result);
-    if (!d0 || !d1 || !r0 || !r1 || !p || !a) return fail(VP_E_ARG, "%s: null pointer", fn);
-    if (d0 == d1 || r0 == r1) return fail(VP_E_ARG, "%s: the two accumulators, and the two record buffers, are different buffers", fn);
+    const int bad = plane_buffers_check(S, true);
+    if (bad == 1 || !p || !a.rel_tol) return fail(VP_E_ARG, "%s: null pointer", fn);
+    if (bad) return fail(VP_E_ARG, "%s: the %s accumulators, and the %s record buffers, are different buffers", fn, kCount[S.n()], kCount[S.n()]);
     if (max_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "%s: frames [%d, %d + %d) out of range", fn, first_frame, first_frame, max_frames);
-    if (a->min_frames < 2) return fail(VP_E_ARG, "%s: min_frames %d (a variance estimate needs two samples)", fn, a->min_frames);
-    if (a->round_frames < 1) return fail(VP_E_ARG, "%s: round_frames %d", fn, a->round_frames);
-    for (int k = 0; k < 2; k++)
-        if (!(a->rel_tol[k] >= 0.0f) || !(a->floor_y[k] >= 0.0f)) return fail(VP_E_ARG, "%s: rel_tol and floor_y must be numbers >= 0 (plane %d)", fn, k);
-    int rc = plane_state_check(fn, groups);
+    if (a.min_frames < 2) return fail(VP_E_ARG, "%s: min_frames %d (a variance estimate needs two samples)", fn, a.min_frames);
+    if (a.round_frames < 1) return fail(VP_E_ARG, "%s: round_frames %d", fn, a.round_frames);
+    for (int k = 0; k < S.n(); k++)
+        if (!(a.rel_tol[k] >= 0.0f) || !(a.floor_y[k] >= 0.0f)) return fail(VP_E_ARG, "%s: rel_tol and floor_y must be numbers >= 0 (plane %d)", fn, k);
+    int rc = plane_state_check(fn, S.groups());
     if (rc) return rc;
     if ((rc = ensure_device())) return rc;
     if ((rc = check_render(CHK_STATE | CHK_OPACITY, p, (long long)first_frame + max_frames - 1))) return rc;
-    StatsDev T = {};
-    T.stats = (PixelStatsDev*)r0; T.plane2 = (PixelStatsDev*)r1; T.adaptive = 1u; T.min_frames = (unsigned)a->min_frames;
-    for (int k = 0; k < 2; k++) { T.plane_tol[k] = (double)a->rel_tol[k]; T.plane_fl[k] = (double)a->floor_y[k]; }
-    return adaptive_rounds(d0, d1, nullptr, groups, T, first_frame, max_frames, a->round_frames, p, result);
+    S.adaptive = true; S.min_frames = (unsigned)a.min_frames;
+    for (int k = 0; k < S.n(); k++) { S.tol[k] = (double)a.rel_tol[k]; S.fl[k] = (double)a.floor_y[k]; }
+    return adaptive_rounds(S, first_frame, max_frames, a.round_frames, p, result);
 }
 }  // namespace vph
 
@@ -110,9 +105,8 @@ extern "C" {
 int vp_render_frames_stats(vp_float4* d_output, vp_pixel_stats* d_stats, int first_frame, int n_frames, const Param* p)
 {
     if (!d_output || !d_stats || !p || n_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "vp_render_frames_stats: bad arguments");
-    StatsDev T = {};
-    T.stats = (PixelStatsDev*)d_stats;
-    return do_render(d_output, first_frame, n_frames, p, false, nullptr, nullptr, &T);
+    const PlaneSet S = plane_set(PLANES_ONE, d_output, nullptr, nullptr, d_stats);
+    return do_render(d_output, first_frame, n_frames, p, false, nullptr, nullptr, &S);
 }
 int vp_render_adaptive(vp_float4* d_output, vp_pixel_stats* d_stats, int first_frame, int max_frames, const Param* p, const vp_adaptive* a,
                        vp_adaptive_result* result)
@@ -127,44 +121,29 @@ int vp_render_adaptive(vp_float4* d_output, vp_pixel_stats* d_stats, int first_f
     if (rc) return rc;
     if (G.count) return fail(VP_E_STATE, "vp_render_adaptive is not built for work counters");
     if ((rc = check_render(CHK_STATE | CHK_OPACITY, p, (long long)first_frame + max_frames - 1))) return rc;
-    StatsDev T = {};
-    T.stats = (PixelStatsDev*)d_stats; T.adaptive = 1u; T.min_frames = (unsigned)a->min_frames;
-    T.tol = (double)a->rel_tol; T.fl = (double)a->floor_y;
-    return adaptive_rounds(d_output, nullptr, nullptr, false, T, first_frame, max_frames, a->round_frames, p, result);
+    PlaneSet S = plane_set(PLANES_ONE, d_output, nullptr, nullptr, d_stats);
+    S.adaptive = true; S.min_frames = (unsigned)a->min_frames;
+    S.tol[0] = (double)a->rel_tol; S.fl[0] = (double)a->floor_y;
+    return adaptive_rounds(S, first_frame, max_frames, a->round_frames, p, result);
 }
 int vp_render_adaptive_groups(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, int first_frame, int max_frames,
                               const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result)
 {
-    return render_adaptive_planes("vp_render_adaptive_groups", true, d_sun, d_sky, d_sun_stats, d_sky_stats, first_frame, max_frames, p, a, result);
+    return render_adaptive_planes("vp_render_adaptive_groups", plane_set(PLANES_GROUPS, d_sun, d_sky, nullptr, d_sun_stats, d_sky_stats), first_frame, max_frames, p,
+                                  adaptive_args(a), result);
 }
 int vp_render_adaptive_layers(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stats* d_fg_stats, vp_pixel_stats* d_trans_stats, int first_frame, int max_frames,
                               const Param* p, const vp_adaptive_planes* a, vp_adaptive_result* result)
 {
-    return render_adaptive_planes("vp_render_adaptive_layers", false, d_fg, d_trans, d_fg_stats, d_trans_stats, first_frame, max_frames, p, a, result);
+    return render_adaptive_planes("vp_render_adaptive_layers", plane_set(PLANES_LAYERS, d_fg, d_trans, nullptr, d_fg_stats, d_trans_stats), first_frame, max_frames, p,
+                                  adaptive_args(a), result);
 }
 int vp_render_adaptive_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats,
                                     vp_pixel_stats* d_trans_stats, int first_frame, int max_frames, const Param* p, const vp_adaptive_planes3* a,
                                     vp_adaptive_result* result)
 {
-    static const char fn[] = "vp_render_adaptive_group_layers";
-    if (result) memset(result, 0, sizeof *result);
-    if (!d_sun || !d_sky || !d_trans || !d_sun_stats || !d_sky_stats || !d_trans_stats || !p || !a) return fail(VP_E_ARG, "%s: null pointer", fn);
-    if (d_sun == d_sky || d_sun == d_trans || d_sky == d_trans || d_sun_stats == d_sky_stats || d_sun_stats == d_trans_stats || d_sky_stats == d_trans_stats)
-        return fail(VP_E_ARG, "%s: the three accumulators, and the three record buffers, are different buffers", fn);
-    if (max_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "%s: frames [%d, %d + %d) out of range", fn, first_frame, first_frame, max_frames);
-    if (a->min_frames < 2) return fail(VP_E_ARG, "%s: min_frames %d (a variance estimate needs two samples)", fn, a->min_frames);
-    if (a->round_frames < 1) return fail(VP_E_ARG, "%s: round_frames %d", fn, a->round_frames);
-    for (int k = 0; k < 3; k++)
-        if (!(a->rel_tol[k] >= 0.0f) || !(a->floor_y[k] >= 0.0f)) return fail(VP_E_ARG, "%s: rel_tol and floor_y must be numbers >= 0 (plane %d)", fn, k);
-    int rc = plane_state_check(fn, true);
-    if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
-    if ((rc = check_render(CHK_STATE | CHK_OPACITY, p, (long long)first_frame + max_frames - 1))) return rc;
-    StatsDev T = {};
-    T.stats = (PixelStatsDev*)d_sun_stats; T.plane2 = (PixelStatsDev*)d_sky_stats; T.plane3 = (PixelStatsDev*)d_trans_stats;
-    T.adaptive = 1u; T.min_frames = (unsigned)a->min_frames;
-    for (int k = 0; k < 3; k++) { T.plane_tol[k] = (double)a->rel_tol[k]; T.plane_fl[k] = (double)a->floor_y[k]; }
-    return adaptive_rounds(d_sun, d_sky, d_trans, true, T, first_frame, max_frames, a->round_frames, p, result);
+    return render_adaptive_planes("vp_render_adaptive_group_layers", plane_set(PLANES_GROUP_LAYERS, d_sun, d_sky, d_trans, d_sun_stats, d_sky_stats, d_trans_stats),
+                                  first_frame, max_frames, p, adaptive_args(a), result);
 }
 int vp_scale_by_count(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, int size, float scale)
 {

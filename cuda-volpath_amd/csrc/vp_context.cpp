@@ -771,7 +771,7 @@ int vp_set_shard(int rank, int world)
 }
 int vp_test_launch_census(int unit, int kind, uint32_t* launches, uint8_t* built, size_t count, int reset)
 {
-    const size_t n = census_size(kind);
+    const size_t n = kind >= CENSUS_RENDER && kind <= CENSUS_APPROACH ? census_size(kind) : 0;   // (the other tables: the hooks below)
     if (unit < 0 || unit > 1 || !n) return fail(VP_E_ARG, "vp_test_launch_census: unknown unit %d (0 exact, 1 fast) or kind %d (0 render_k, 1 layers, 2 approach)", unit, kind);
     if (!launches && !built) return (int)n;
     if (count != n) return fail(VP_E_ARG, "vp_test_launch_census: %zu entries given, the table of kind %d has %zu", count, kind, n);
@@ -780,18 +780,18 @@ int vp_test_launch_census(int unit, int kind, uint32_t* launches, uint8_t* built
 }
 int vp_test_groups_census(uint32_t* launches, uint8_t* built, size_t count, int reset)
 {
-    const size_t n = census_size(CENSUS_RENDER);   // (the groups table has render_k's index)
+    const size_t n = census_size(CENSUS_GROUPS);   // (render_k's index)
     if (!launches && !built) return (int)n;
     if (count != n) return fail(VP_E_ARG, "vp_test_groups_census: %zu entries given, the table has %zu", count, n);
-    groups_census_read(launches, built, n, reset != 0);   // (host memory only: no device, no context)
+    census_read(0, CENSUS_GROUPS, launches, built, n, reset != 0);   // (the exact unit's; host memory only: no device, no context)
     return VP_OK;
 }
 int vp_test_group_layers_census(uint32_t* launches, uint8_t* built, size_t count, int reset)
 {
-    const size_t n = census_size(CENSUS_RENDER);   // (the group-layers table has render_k's index)
+    const size_t n = census_size(CENSUS_GROUP_LAYERS);
     if (!launches && !built) return (int)n;
     if (count != n) return fail(VP_E_ARG, "vp_test_group_layers_census: %zu entries given, the table has %zu", count, n);
-    group_layers_census_read(launches, built, n, reset != 0);   // (host memory only: no device, no context)
+    census_read(0, CENSUS_GROUP_LAYERS, launches, built, n, reset != 0);
     return VP_OK;
 }
 int vp_test_math(int which, const float* in, float* out, int n)

@@ -11,12 +11,9 @@
 //   render_built()     which instances this translation unit compiles -- its truth set IS the set of render_k kernels in the object,
 //                      because launch_instance() names a kernel only under `if constexpr (render_built(...))`
 //   launch_instance()  the run-time instance lifted to template arguments; kernel_not_built() (vp_kernels.h) for the rest
-//   launch_layers_instance()  the same for a layers launch (LaunchDev::layers): render_k's twelfth argument, LYR, for the subset
-//                      layers_built() states -- only where the kernels above have that argument (VP_RENDER_K_HAS_LAYERS)
-//   launch_groups_instance()  the same for a light-groups launch (LaunchDev::groups): the thirteenth argument, GRP, for the same subset
-//                      (groups_built()) -- only where the kernels above have it (VP_RENDER_K_HAS_GROUPS)
-//   launch_group_layers_instance()  the same for a group-layers launch (both fields set): LYR and GRP together, the same subset
-//                      (group_layers_built()) -- only where the kernels above take the pair (VP_RENDER_K_HAS_GROUP_LAYERS)
+//   launch_plane_instance()  the same for a launch with planes (LaunchDev::layers and / or LaunchDev::groups): render_k's twelfth and
+//                      thirteenth arguments, LYR and GRP, for the subset planes_built() states, one table per plane mode -- only where
+//                      the kernels above have the two arguments (VP_RENDER_K_HAS_PLANES)
 // and the same, smaller, for the approach walk (approach_built(), launch_approach_walk()).  dispatch_render(), dispatch_light() and
 // dispatch_approach() are what the launch_* functions of vp_kernels.h call.  Each launcher counts the launch under its table index
 // (census_record(), vp_kernels.h: the launch census, a test hook) just before it calls through the table.
@@ -176,129 +173,54 @@ static void launch_instance(const RenderInst& v, std::integer_sequence<unsigned,
     census_record(kFastArith, CENSUS_RENDER, i);
     table[i](S, L, blocks, st);
 }
-static void launch_instance(const RenderInst& v, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
-{
-    launch_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st);
-}
-// ---- the instances of a layers launch (LaunchDev::layers; render_k's LYR argument).  Compiled where the kernels that precede this
-// file have the argument (vp_integrator.h defines VP_RENDER_K_HAS_LAYERS).  The subset: spectral tracking, passive environment, the
+// ---- the instances of a launch with planes (vp_kernels.h PLANES_*: LaunchDev::layers -> render_k's LYR argument, LaunchDev::groups ->
+// its GRP argument, both for a group-layers launch).  Compiled where the kernels that precede this file have the two arguments
+// (vp_integrator.h defines VP_RENDER_K_HAS_PLANES).  The subset, the same for every mode: spectral tracking, passive environment, the
 // three estimators, the three streams, the three volume formats, every LDS form, general and light class; no work counters, no
-// look-ahead (a layers call quiesces it), the exact translation unit only -- vp_render.cpp refuses everything else first.
-#ifdef VP_RENDER_K_HAS_LAYERS
-constexpr bool layers_built(const RenderInst& v)
+// look-ahead (a plane call quiesces it), the exact translation unit only -- vp_render.cpp refuses everything else first.  One table
+// per mode, each with a census of its own (census_of_planes).
+#ifdef VP_RENDER_K_HAS_PLANES
+constexpr bool planes_built(const RenderInst& v)
 {
     return render_built(v) && !kFastArith && !v.trk && !v.mis && !v.count && !v.cancel;
 }
-template <unsigned I>
-static void launch_layers_instance_at(const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
+template <unsigned I, bool LYR, bool GRP>
+static void launch_plane_instance_at(const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
 {
     constexpr RenderInst v = render_at(I);
     using RNG = typename RngOf<v.rng>::type;
     constexpr unsigned block = v.ldsb == 1 ? VP_BLOCK_LDS : VP_BLOCK;
-    hipLaunchKernelGGL((render_k<v.est, RNG, v.quant, v.count, v.ldsb, v.ach, v.mis, v.trk, v.light, v.cancel, v.half, true>), dim3(blocks), dim3(block), 0, st, S, L);
+    hipLaunchKernelGGL((render_k<v.est, RNG, v.quant, v.count, v.ldsb, v.ach, v.mis, v.trk, v.light, v.cancel, v.half, LYR, GRP>), dim3(blocks), dim3(block), 0, st, S, L);
 }
-template <unsigned I>
-constexpr RenderLaunchFn layers_launcher()
+template <unsigned I, bool LYR, bool GRP>
+constexpr RenderLaunchFn plane_launcher()
 {
-    if constexpr (layers_built(render_at(I))) return &launch_layers_instance_at<I>;
+    if constexpr (planes_built(render_at(I))) return &launch_plane_instance_at<I, LYR, GRP>;
     else return nullptr;
 }
-template <unsigned... I>
-static void launch_layers_instance(const RenderInst& v, std::integer_sequence<unsigned, I...>, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
+template <bool LYR, bool GRP, unsigned... I>
+static void launch_plane_instance(const RenderInst& v, std::integer_sequence<unsigned, I...>, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
 {
-    static constexpr RenderLaunchFn table[kRenderInsts] = {layers_launcher<I>()...};
+    static constexpr RenderLaunchFn table[kRenderInsts] = {plane_launcher<I, LYR, GRP>()...};
     const unsigned i = render_index(v);
     if (i >= kRenderInsts || !table[i]) kernel_not_built();
-    census_record(kFastArith, CENSUS_LAYERS, i);
+    census_record(kFastArith, census_of_planes(plane_mode(LYR, GRP)), i);
     table[i](S, L, blocks, st);
-}
-#endif
-// ---- the instances of a light-groups launch (LaunchDev::groups; render_k's GRP argument): the same subset by the same rule, in a table
-// of its own with a census of its own (vp_kernels.h groups_census_record).  Compiled where the kernels that precede this file have
-// the argument (vp_integrator.h defines VP_RENDER_K_HAS_GROUPS).
-#ifdef VP_RENDER_K_HAS_GROUPS
-constexpr bool groups_built(const RenderInst& v) { return layers_built(v); }
-template <unsigned I>
-static void launch_groups_instance_at(const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
-{
-    constexpr RenderInst v = render_at(I);
-    using RNG = typename RngOf<v.rng>::type;
-    constexpr unsigned block = v.ldsb == 1 ? VP_BLOCK_LDS : VP_BLOCK;
-    hipLaunchKernelGGL((render_k<v.est, RNG, v.quant, v.count, v.ldsb, v.ach, v.mis, v.trk, v.light, v.cancel, v.half, false, true>), dim3(blocks), dim3(block), 0, st, S, L);
-}
-template <unsigned I>
-constexpr RenderLaunchFn groups_launcher()
-{
-    if constexpr (groups_built(render_at(I))) return &launch_groups_instance_at<I>;
-    else return nullptr;
-}
-template <unsigned... I>
-static void launch_groups_instance(const RenderInst& v, std::integer_sequence<unsigned, I...>, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
-{
-    static constexpr RenderLaunchFn table[kRenderInsts] = {groups_launcher<I>()...};
-    const unsigned i = render_index(v);
-    if (i >= kRenderInsts || !table[i]) kernel_not_built();
-    groups_census_record(i);
-    table[i](S, L, blocks, st);
-}
-// built[i] of the groups table (what groups_census_read hands out)
-static void dispatch_groups_built(unsigned char* built, size_t count)
-{
-    for (size_t i = 0; i < count; i++) built[i] = i < kRenderInsts && groups_built(render_at((unsigned)i));
-}
-#endif
-// ---- the instances of a group-layers launch (LaunchDev::layers and LaunchDev::groups; render_k's LYR and GRP arguments together): the
-// same subset by the same rule, in a third table with a census of its own (vp_kernels.h group_layers_census_record).  Compiled where
-// the kernels that precede this file take the pair (vp_integrator.h defines VP_RENDER_K_HAS_GROUP_LAYERS).
-#ifdef VP_RENDER_K_HAS_GROUP_LAYERS
-constexpr bool group_layers_built(const RenderInst& v) { return layers_built(v); }
-template <unsigned I>
-static void launch_group_layers_instance_at(const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
-{
-    constexpr RenderInst v = render_at(I);
-    using RNG = typename RngOf<v.rng>::type;
-    constexpr unsigned block = v.ldsb == 1 ? VP_BLOCK_LDS : VP_BLOCK;
-    hipLaunchKernelGGL((render_k<v.est, RNG, v.quant, v.count, v.ldsb, v.ach, v.mis, v.trk, v.light, v.cancel, v.half, true, true>), dim3(blocks), dim3(block), 0, st, S, L);
-}
-template <unsigned I>
-constexpr RenderLaunchFn group_layers_launcher()
-{
-    if constexpr (group_layers_built(render_at(I))) return &launch_group_layers_instance_at<I>;
-    else return nullptr;
-}
-template <unsigned... I>
-static void launch_group_layers_instance(const RenderInst& v, std::integer_sequence<unsigned, I...>, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
-{
-    static constexpr RenderLaunchFn table[kRenderInsts] = {group_layers_launcher<I>()...};
-    const unsigned i = render_index(v);
-    if (i >= kRenderInsts || !table[i]) kernel_not_built();
-    group_layers_census_record(i);
-    table[i](S, L, blocks, st);
-}
-// built[i] of the group-layers table (what group_layers_census_read hands out)
-static void dispatch_group_layers_built(unsigned char* built, size_t count)
-{
-    for (size_t i = 0; i < count; i++) built[i] = i < kRenderInsts && group_layers_built(render_at((unsigned)i));
 }
 #endif
 static void launch_instance_of(const RenderInst& v, const SceneDev& S, const LaunchDev& L, int blocks, hipStream_t st)
 {
-#ifdef VP_RENDER_K_HAS_GROUP_LAYERS
-    if (L.layers && L.groups) { launch_group_layers_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st); return; }
-#else
-    if (L.layers && L.groups) kernel_not_built();
+    constexpr std::make_integer_sequence<unsigned, kRenderInsts> all{};
+    switch (plane_mode(L.layers != 0, L.groups != nullptr))
+    {
+    case PLANES_ONE: launch_instance(v, all, S, L, blocks, st); return;
+#ifdef VP_RENDER_K_HAS_PLANES
+    case PLANES_LAYERS: launch_plane_instance<true, false>(v, all, S, L, blocks, st); return;
+    case PLANES_GROUPS: launch_plane_instance<false, true>(v, all, S, L, blocks, st); return;
+    case PLANES_GROUP_LAYERS: launch_plane_instance<true, true>(v, all, S, L, blocks, st); return;
 #endif
-#ifdef VP_RENDER_K_HAS_GROUPS
-    if (L.groups) { launch_groups_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st); return; }
-#else
-    if (L.groups) kernel_not_built();
-#endif
-#ifdef VP_RENDER_K_HAS_LAYERS
-    if (L.layers) { launch_layers_instance(v, std::make_integer_sequence<unsigned, kRenderInsts>{}, S, L, blocks, st); return; }
-#else
-    if (L.layers) kernel_not_built();
-#endif
-    launch_instance(v, S, L, blocks, st);
+    }
+    kernel_not_built();
 }
 // what launch_render / launch_render_fast and launch_render_light are
 static void dispatch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
@@ -383,10 +305,10 @@ static void dispatch_census_built(int kind, unsigned char* built, size_t count)
     {
         bool b = false;
         if (kind == CENSUS_RENDER) b = i < kRenderInsts && render_built(render_at((unsigned)i));
-#ifdef VP_RENDER_K_HAS_LAYERS
-        else if (kind == CENSUS_LAYERS) b = i < kRenderInsts && layers_built(render_at((unsigned)i));
-#endif
         else if (kind == CENSUS_APPROACH) b = i < kApproachInsts && approach_built(approach_at((unsigned)i));
+#ifdef VP_RENDER_K_HAS_PLANES
+        else b = i < kRenderInsts && planes_built(render_at((unsigned)i));   // (the tables of the plane modes: one subset)
+#endif
         built[i] = b;
     }
 }

@@ -194,15 +194,13 @@ constexpr int render_min_waves(int est, bool count, int ldsb, bool ach, bool mis
 }
 // LYR: the instance of a layers launch (include/volpath.h vp_render_frames_layers; LaunchDev::layers): vp_dispatch.h names it for the
 // subset the feature is built for.  Every other instance carries no code for it.
-#define VP_RENDER_K_HAS_LAYERS 1
 // GRP: the instance of a light-groups launch (include/volpath.h vp_render_frames_groups; LaunchDev::groups), named by vp_dispatch.h for
 // the same subset.  It differs at the path end only: what the environment adds there is not summed into `rad` but staged as a sample
 // of its own in the second staging plane.  Every other instance carries no code for it.
-#define VP_RENDER_K_HAS_GROUPS 1
 // LYR and GRP: the instance of a group-layers launch (include/volpath.h vp_render_frames_group_layers; LaunchDev::layers and
 // LaunchDev::groups), named by vp_dispatch.h for the same subset.  An unscattered path ends as in a layers launch (its marked
 // throughput in the first plane, nothing in the second), a scattered one as in a groups launch.
-#define VP_RENDER_K_HAS_GROUP_LAYERS 1
+#define VP_RENDER_K_HAS_PLANES 1
 template <int EST, class RNG, bool QUANT, bool COUNT, int LDSB, bool ACH, bool MIS, int TRK, bool LIGHT = false, bool CANCEL = false, bool HALF = false, bool LYR = false,
           bool GRP = false>
 // Occupancy (round 4: the cold per-path state in LDS, ColdVal above; profiles/r04_kernel_resources.txt).  The achromatic
@@ -842,7 +840,7 @@ void render_k(SceneDev S, LaunchDev L)
                 if (!MIS || nsc == 0)
                 {
                     // (a layers launch: an unscattered path's sample is the transmittance layer's, its throughput -- the sum below with a
-                    // background of 1 --, marked for reduce_layers_k in EV_WRITE; include/volpath.h vp_render_frames_layers)
+                    // background of 1 --, marked for the reduce in EV_WRITE; include/volpath.h vp_render_frames_layers)
                     if (LAYERS) trans = nsc == 0;
                     f3 bg;
                     if (LAYERS && trans) bg = f3{1.0f, 1.0f, 1.0f};
@@ -878,14 +876,14 @@ void render_k(SceneDev S, LaunchDev L)
                 // heat: num_scatters (:2307) or loop index * 0.001 in double (:1581, :1942)
                 float  heat = (EST == EST_DECOMP) ? (float)nsc : (float)((double)(EST == EST_BOUNDED ? seg : nsc) * 0.001);
                 // (never negative otherwise: the sign bit, -0.0f included, marks a transmittance sample.  Not in the light kernels: every
-                // sample of theirs is one, reduce_layers_k knows their slots, and the mark costs the local-majorant ones two registers
+                // sample of theirs is one, the reduce knows their slots, and the mark costs the local-majorant ones two registers
                 // and their eighth wave: profiles/layers_kernel_resources.txt)
                 if (LAYERS && !LIGHT && trans) heat = -heat;
                 float4 v    = make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), heat);
                 if (TRK == 2)  // kernel.cu:2311-2313: the drawn channel only, times three
                     v = make_float4(chan == 0 ? v.x * 3.0f : 0.0f, chan == 1 ? v.y * 3.0f : 0.0f, chan == 2 ? v.z * 3.0f : 0.0f, heat);
                 // (a group-layers launch, LYR and GRP: a marked sample and every sample of the light class is a transmittance sample, whose
-                // second-plane word reduce_group_layers_k derives -- the light instances are the layers launch's code, the general ones
+                // second-plane word the reduce (split_sample) derives -- the light instances are the layers launch's code, the general ones
                 // stage the sky group's sample of a scattered path only)
                 if (GRP && LIGHT && !LYR)
                 {

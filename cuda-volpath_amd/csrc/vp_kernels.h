@@ -156,7 +156,7 @@ struct LaunchDev
     unsigned sub_shift;
     // A layers launch (include/volpath.h vp_render_frames_layers; appended like the fields above): 1 = a sample that reaches the
     // environment unscattered is staged as (max(thr, 0), -heat) -- its throughput, no background, no brightness; the sign bit of w,
-    // -0.0f included, marks it (the light kernel, whose every sample is one, stages heat as it is) -- and reduce_layers_k splits the
+    // -0.0f included, marks it (the light kernel, whose every sample is one, stages heat as it is) -- and the reduce (split_sample) splits the
     // staged samples into the two accumulators.  0: the beauty sample, as ever.
     unsigned layers;
     // Global-majorant estimator, general class (appended like the fields above): per pixel slot of the class what a fresh sample's
@@ -167,7 +167,7 @@ struct LaunchDev
     const float4* ray;
     // A light-groups launch (include/volpath.h vp_render_frames_groups; appended like the fields above): the second staging plane, laid
     // out like `stage` (frame * stage_stride + slot) and lying behind the launch's last staged frame.  render_k's GRP instances and the
-    // constant writers stage the sky group's sample there and the sun group's in `stage`; reduce_groups_k adds the two planes into the
+    // constant writers stage the sky group's sample there and the sun group's in `stage`; the reduce adds the two planes into the
     // two accumulators.  Null: not a groups launch.
     float4* groups;
 };
@@ -175,10 +175,23 @@ struct LaunchDev
 // render_k and the approach kernels: which instance a launch runs, and which of them a build compiles, is decided in vp_dispatch.h.
 // A request for an instance that the build lacks (the API refuses every such configuration first: vp_render.cpp check_render) ends here:
 [[noreturn]] void kernel_not_built();
-// The launch census (test hook: include/volpath.h vp_test_launch_census).  launch_instance(), launch_layers_instance() and
-// launch_approach_walk() of vp_dispatch.h call census_record() with the table index of the kernel they are about to name: one host
-// increment per launch, nothing on the device.  unit: 0 the exact translation unit, 1 the fast arithmetic's; kind: CENSUS_*.
-constexpr int CENSUS_RENDER = 0, CENSUS_LAYERS = 1, CENSUS_APPROACH = 2;
+// The planes of a render call.  A call has one to three planes; a staged sample splits into one sample per plane by the rule of the
+// call's mode (split_sample, vp_kernels.hip).  The mode is two bits -- layers, groups -- and is also which of render_k's LYR / GRP
+// instances the call launches (vp_dispatch.h):
+//   PLANES_ONE           out                 the beauty sample, whole
+//   PLANES_LAYERS        fg, trans           an unscattered path's throughput goes to trans, its heat to fg; any other sample to fg
+//   PLANES_GROUPS        sun, sky            the first staging plane to sun, the second (LaunchDev::groups) to sky
+//   PLANES_GROUP_LAYERS  sun, sky, trans     unscattered: as a layers call, the heat to both groups; else as a groups call
+constexpr int PLANES_ONE = 0, PLANES_LAYERS = 1, PLANES_GROUPS = 2, PLANES_GROUP_LAYERS = 3, kPlaneModes = 4, kMaxPlanes = 3;
+constexpr int plane_mode(bool layers, bool groups) { return (layers ? PLANES_LAYERS : 0) | (groups ? PLANES_GROUPS : 0); }
+constexpr int planes_of(int mode) { return mode == PLANES_ONE ? 1 : mode == PLANES_GROUP_LAYERS ? 3 : 2; }
+// The launch census (test hook: include/volpath.h vp_test_launch_census).  The launchers of vp_dispatch.h call census_record() with the
+// table index of the kernel they are about to name: one host increment per launch, nothing on the device.  unit: 0 the exact
+// translation unit, 1 the fast arithmetic's; kind: CENSUS_* -- one table per plane mode of render_k (census_of_planes), and the
+// approach walk's.  The public hook takes the first three kinds; the groups and group-layers tables have entry points of their own
+// (vp_test_groups_census, vp_test_group_layers_census), views of the same store.
+constexpr int CENSUS_RENDER = 0, CENSUS_LAYERS = 1, CENSUS_APPROACH = 2, CENSUS_GROUPS = 3, CENSUS_GROUP_LAYERS = 4;
+constexpr int census_of_planes(int mode) { return mode < PLANES_GROUPS ? mode : mode + 1; }
 void census_record(int unit, int kind, unsigned index);
 // the read side: the table length of a kind (0: no such kind); launches[i] = launches since the last reset, built[i] = 1 where the
 // unit compiles instance i (either array may be null; count = the table length); reset zeroes the counters after they are read
@@ -187,13 +200,6 @@ void census_read(int unit, int kind, unsigned* launches, unsigned char* built, s
 // built[i] of one unit, from the constexpr functions of vp_dispatch.h as that unit compiled them (vp_kernels.hip / vp_kernels_fast.hip)
 void census_built(int kind, unsigned char* built, size_t count);
 void census_built_fast(int kind, unsigned char* built, size_t count);
-// The same for the table of a groups launch (launch_groups_instance() of vp_dispatch.h; test hook: vp_test_groups_census), kept apart
-// from the kinds above: the exact unit only, the index and length of CENSUS_RENDER.
-void groups_census_record(unsigned index);
-void groups_census_read(unsigned* launches, unsigned char* built, size_t count, bool reset);
-// ... and for the table of a group-layers launch (launch_group_layers_instance(); test hook: vp_test_group_layers_census), apart again
-void group_layers_census_record(unsigned index);
-void group_layers_census_read(unsigned* launches, unsigned char* built, size_t count, bool reset);
 // lds_form: how the decomposition estimator reads its brick table -- 0 global memory, 1 the 16-bit table through LDS (512-thread
 // workgroups), 2 2-bit codes into a four-entry palette through LDS (LaunchDev::bound_codes; 256-thread workgroups, plain occupancy)
 // half (with quant = false): binary16 cells (SceneDev::cells_f16); everything else of such a volume is the float volume's
@@ -243,58 +249,38 @@ void launch_sun_clip(const SceneDev& S, const unsigned char* danger, float ds, u
 void launch_empty_table(const SceneDev& S, unsigned width, unsigned height, const unsigned char* danger, float4* table, hipStream_t st);
 // the direction table of the exit flights from the danger volume: planes = 3 * nx*ny*nz bytes; one small kernel per slice and direction
 void launch_exit_table(const unsigned char* danger, unsigned char* planes, int nx, int ny, int nz, hipStream_t st);
+// the reduce of a one-plane launch without statistics (reduce_stage_k): the call the benchmark times, and the look-ahead's
 void launch_reduce(const LaunchDev& L, hipStream_t st);
-// the reduce of a layers launch (LaunchDev::layers): L.out is the foreground accumulator, trans the transmittance accumulator; the slots
-// [light_from, light_to) of the list are the light kernel's, whose samples are transmittance samples without the mark
-void launch_reduce_layers(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st);
-// the reduce of a groups launch (LaunchDev::groups): L.out is the sun accumulator and receives the plane L.stage, sky the sky accumulator
-// and receives the plane L.groups; constants (LaunchDev::const_from) lie in the first row of either plane
-void launch_reduce_groups(const LaunchDev& L, float4* sky, hipStream_t st);
-// the reduce of a group-layers launch (LaunchDev::layers and LaunchDev::groups): L.out is the sun accumulator.  A sample of the plane
-// L.stage that carries the mark, or lies in the slots [light_from, light_to) of the light kernel or behind LaunchDev::const_from (the
-// constants of a layers launch), is a transmittance sample: (x, y, z, 1) goes to trans and (0, 0, 0, |w|) to sun and to sky -- the plane
-// L.groups is not read for it.  Any other goes to sun whole, its word of L.groups to sky and (0, 0, 0, 0) to trans
-void launch_reduce_group_layers(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st);
-// Per-pixel statistics (include/volpath.h vp_pixel_stats, the same 24 bytes) and what launch_reduce_stats does with them: the
-// reduce of a staged launch that also adds each sample's luminance to its pixel's record, and -- adaptive: a round of
-// vp_render_adaptive -- freezes the records whose criterion holds (tol, fl: the binary32 arguments widened)
+// Per-pixel statistics (include/volpath.h vp_pixel_stats, the same 24 bytes)
 struct PixelStatsDev { double sum_y, sum_y2; unsigned n, flags; };
-struct StatsDev
+// What a render call accumulates into, as the host describes it (do_render; vp_adaptive.cpp): the planes of its mode in the order of
+// the table above, each with an accumulator and -- all planes or none -- a record buffer; an adaptive call adds each plane's criterion.
+struct PlaneSet
 {
-    PixelStatsDev* stats;   // width * height records, indexed like the accumulator
-    unsigned adaptive;      // 1: evaluate the criterion and set VP_STATS_FROZEN; 0: `flags` is neither read nor written
-    unsigned min_frames;
-    double   tol, fl;
-    PixelStatsDev* plane2;  // a groups or layers call with statistics: the records of the second plane (sky, trans); `stats` is the first plane's
-    // ... with adaptive rounds (vp_render_adaptive_groups / _layers): the criterion per plane, [0] the first plane's; tol and fl above are unused
-    // ([2]: the third plane's, vp_render_adaptive_group_layers)
-    double   plane_tol[3], plane_fl[3];
-    PixelStatsDev* plane3;  // a group-layers call with statistics: the records of the third plane (trans); `stats` is sun's, plane2 sky's
+    int            mode;                // PLANES_*
+    float4*        acc[kMaxPlanes];     // planes_of(mode) accumulators of width * height pixels
+    PixelStatsDev* rec[kMaxPlanes];     // their records, indexed like the accumulators; rec[0] null: a call without statistics
+    double         tol[kMaxPlanes], fl[kMaxPlanes];   // adaptive: each plane's tolerance and floor (the binary32 arguments widened)
+    unsigned       min_frames;          // adaptive: the samples a record needs before its criterion is asked
+    bool           adaptive;            // a round of an adaptive call: its last launch freezes; false: `flags` is neither read nor written
+    int  n() const { return planes_of(mode); }
+    bool layers() const { return (mode & PLANES_LAYERS) != 0; }
+    bool groups() const { return (mode & PLANES_GROUPS) != 0; }
+    bool stats() const { return rec[0] != nullptr; }
 };
-// what the adaptive form of a plane reduce evaluates after the last launch of a round: each record with its own tolerance and floor
-struct PlaneCriterionDev { double tol[2], fl[2]; unsigned min_frames; };
-// ... and that of the group-layers reduce ([0] sun, [1] sky, [2] trans): a descriptor of its own, the two-plane kernels keep their arguments
-struct Plane3CriterionDev { double tol[3], fl[3]; unsigned min_frames; };
-void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st);
-// the reduces of a groups and of a layers launch (above) with one record per plane and pixel: each plane's sample, as its accumulator
-// receives it, goes into that plane's record by the definition of vp_pixel_stats.  C null: `flags` is neither read nor written (the
-// _stats calls).  C given -- the last launch of an adaptive round --: the adaptive form, which then freezes both records of a slot iff
-// each has C->min_frames and meets the criterion of reduce_stats_k with its own n, tolerance and floor
-void launch_reduce_groups_stats(const LaunchDev& L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, const PlaneCriterionDev* C, hipStream_t st);
-void launch_reduce_layers_stats(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats, PixelStatsDev* trans_stats,
-                                const PlaneCriterionDev* C, hipStream_t st);
-// the reduce of a group-layers launch (above) likewise, with one record per plane.  C null: `flags` is neither read nor written; C given
-// -- the last launch of a round of vp_render_adaptive_group_layers --: the adaptive form, which freezes all three records of a slot iff
-// each has C->min_frames and meets the criterion with its own n, tolerance and floor
-void launch_reduce_group_layers_stats(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* sun_stats,
-                                      PixelStatsDev* sky_stats, PixelStatsDev* trans_stats, const Plane3CriterionDev* C, hipStream_t st);
-// the pixels of the class-ordered list src (n[0] general, n[1] light, n[2] box-missing) whose record is not frozen, in src's order,
-// class by class, into d_out (room for all of src), and their three counts into d_totals; d_block_counts[3 * compact_blocks(n)] scratch.
-// stats2 (may be null): the records of a second plane -- a pixel is then dropped if either of its records is frozen; stats3 (may be
-// null, comes with stats2): those of a third -- dropped if any of the three is
+// The reduce of a staged launch into the planes of S (reduce_planes_k<MODE, STATS, ADAPT>): per slot of L.pixels the staged frames in
+// frame order, each split into one sample per plane; every plane's sample is added to its accumulator (S.acc[0] is L.out) and, with
+// records, its luminance to the plane's record by the definition of vp_pixel_stats.  The slots [light_from, light_to) of the list are
+// the light kernel's, whose samples are unscattered without carrying the mark (layers modes).  last: the last launch of the call --
+// where S.adaptive, the one that evaluates the criterion: all records of a slot are frozen iff each has S.min_frames and meets the
+// criterion with its own n, tolerance and floor (a record frozen on a part of a round would stay frozen).
+void launch_reduce_planes(const LaunchDev& L, const PlaneSet& S, unsigned light_from, unsigned light_to, bool last, hipStream_t st);
+// the pixels of the class-ordered list src (n[0] general, n[1] light, n[2] box-missing) that are frozen in none of S's records, in
+// src's order, class by class, into d_out (room for all of src), and their three counts into d_totals;
+// d_block_counts[3 * compact_blocks(n)] scratch
 inline unsigned compact_blocks(unsigned n) { return (n + 1023u) / 1024u; }
-void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PixelStatsDev* stats, const PixelStatsDev* stats2,
-                           const PixelStatsDev* stats3, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st);
+void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PlaneSet& S, unsigned* d_block_counts, unsigned* d_totals,
+                           unsigned* d_out, hipStream_t st);
 void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st);
 void launch_stats_rel_error(float* dst, const PixelStatsDev* stats, int size, float floor_y, hipStream_t st);
 // the NL-means filter of the output stage (vp_denoise.hip; include/volpath.h vp_denoise): weights from (guide, gstats), colours from

@@ -385,113 +385,6 @@ __global__ __launch_bounds__(256) void reduce_stage_k(LaunchDev L)
     L.out[idx] = a;
 }
 
-// reduce_stage_k's job for a layers launch (LaunchDev::layers): a staged sample whose w has the sign bit clear is a foreground sample
-// and goes to L.out whole; one with the sign bit set is an unscattered path's throughput: (x, y, z, 1) goes to `trans`, its heat |w| to
-// L.out.  The slots [light_from, light_to) are those of the light kernel (render_k<LIGHT>), whose every sample is such a throughput
-// and carries no mark.  Both accumulators in frame order; a constant of the launch is added nframes times, as reduce_stage_k adds it.
-__device__ __forceinline__ void add_layer_sample(float4& a, float4& t, const float4 v, bool unmarked)
-{
-    if (unmarked || __builtin_signbit(v.w))
-    {
-        a = make_float4(a.x + 0.0f, a.y + 0.0f, a.z + 0.0f, a.w + __builtin_fabsf(v.w));
-        t = make_float4(t.x + v.x, t.y + v.y, t.z + v.z, t.w + 1.0f);
-    }
-    else
-    {
-        a = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
-        t = make_float4(t.x + 0.0f, t.y + 0.0f, t.z + 0.0f, t.w + 0.0f);
-    }
-}
-__global__ __launch_bounds__(256) void reduce_layers_k(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to)
-{
-    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= L.nslots) return;
-    unsigned pix = L.pixels[slot];
-    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
-    float4   a = L.out[idx], t = trans[idx];
-    const bool unmarked = slot >= light_from && slot < light_to;
-    if (slot >= L.const_from)
-    {
-        const float4 v = L.stage_const[slot];
-        for (int f = 0; f < L.nframes; f++) add_layer_sample(a, t, v, unmarked);
-    }
-    else
-        for (int f = 0; f < L.nframes; f++) add_layer_sample(a, t, L.stage[(size_t)f * L.stage_stride + slot], unmarked);
-    L.out[idx] = a;
-    trans[idx] = t;
-}
-
-// reduce_stage_k's job for a groups launch (LaunchDev::groups): the plane L.stage into L.out (the sun accumulator), the plane L.groups
-// into `sky`, each in frame order; a constant of the launch lies in the first row of either plane and is added nframes times.
-__global__ __launch_bounds__(256) void reduce_groups_k(LaunchDev L, float4* sky)
-{
-    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= L.nslots) return;
-    unsigned pix = L.pixels[slot];
-    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
-    float4   a = L.out[idx], k = sky[idx];
-    if (slot >= L.const_from)
-    {
-        const float4 v = L.stage_const[slot], w = L.groups[slot];
-        for (int f = 0; f < L.nframes; f++)
-        {
-            a = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
-            k = make_float4(k.x + w.x, k.y + w.y, k.z + w.z, k.w + w.w);
-        }
-    }
-    else
-        for (int f = 0; f < L.nframes; f++)
-        {
-            const float4 v = L.stage[(size_t)f * L.stage_stride + slot], w = L.groups[(size_t)f * L.stage_stride + slot];
-            a = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
-            k = make_float4(k.x + w.x, k.y + w.y, k.z + w.z, k.w + w.w);
-        }
-    L.out[idx] = a;
-    sky[idx]   = k;
-}
-
-// reduce_stage_k's job for a group-layers launch (LaunchDev::layers and LaunchDev::groups; include/volpath.h
-// vp_render_frames_group_layers): L.out is the sun accumulator.  A staged sample of the plane L.stage is a transmittance sample where
-// its w has the sign bit set (render_k's marked samples; the constant writers of a layers launch, which serve this one and mark every
-// sample) and where its slot is the light kernel's ([light_from, light_to): no mark).  Such a sample adds (x, y, z, 1) to `trans`
-// and (0, 0, 0, |w|) to both groups; the plane L.groups holds nothing for it and is not read.  Any other adds itself to sun, its word
-// of L.groups to sky and (0, 0, 0, 0) to trans.  All three in frame order; a constant is added nframes times.
-__device__ __forceinline__ void add_group_layer_sample(float4& a, float4& k, float4& t, const float4 v, const float4* plane2, bool unmarked, float4& sun, float4& sky,
-                                                       float4& tr)
-{
-    if (unmarked || __builtin_signbit(v.w))
-    {
-        sun = sky = make_float4(0.0f, 0.0f, 0.0f, __builtin_fabsf(v.w));
-        tr  = make_float4(v.x, v.y, v.z, 1.0f);
-    }
-    else
-    {
-        sun = v;
-        sky = *plane2;
-        tr  = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    a = make_float4(a.x + sun.x, a.y + sun.y, a.z + sun.z, a.w + sun.w);
-    k = make_float4(k.x + sky.x, k.y + sky.y, k.z + sky.z, k.w + sky.w);
-    t = make_float4(t.x + tr.x, t.y + tr.y, t.z + tr.z, t.w + tr.w);
-}
-__global__ __launch_bounds__(256) void reduce_group_layers_k(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to)
-{
-    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= L.nslots) return;
-    unsigned pix = L.pixels[slot];
-    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
-    float4   a = L.out[idx], k = sky[idx], t = trans[idx];
-    const bool   constant = slot >= L.const_from;
-    const bool   unmarked = slot >= light_from && slot < light_to;
-    const size_t stride   = constant ? 0 : L.stage_stride;
-    float4 s0, s1, s2;
-    for (int f = 0; f < L.nframes; f++)
-        add_group_layer_sample(a, k, t, L.stage[(size_t)f * stride + slot], L.groups + (size_t)f * stride + slot, unmarked, s0, s1, s2);
-    L.out[idx] = a;
-    sky[idx]   = k;
-    trans[idx] = t;
-}
-
 // ---- the pixel lists of a rank, built on the GPU (vp_tables.cpp ensure_pixel_lists): a stable partition of the rank's pixels --
 // those of its 8x8 tiles, tile by tile (row-major tiles, row-major pixels within a tile) -- by pixel class (0 general, 1 the whole
 // chord is certified empty, 2 the camera ray misses the box; pixel table [1].y).  Padded slot s = 64 * (n-th owned tile) + 8 * row +
@@ -598,12 +491,12 @@ __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void pixlist_write_k(PixListDev D
     out[class_base + block_offsets[3 * blockIdx.x + c] + before + rank_in_wave] = pix;
 }
 
-// ---- per-pixel statistics and adaptive sampling (include/volpath.h vp_pixel_stats; vp_adaptive.cpp).  reduce_stage_k's job with the
-// statistics of the definition taken where the samples are summed: per slot of L.pixels (ALL pixels of the launch -- the rank's, or the
-// ACTIVE ones of an adaptive round) the staged frames are added to the accumulator in frame order, exactly as reduce_stage_k adds
-// them, and each sample's luminance goes into the record of its pixel: binary32 luminance, binary64 sums, one after the other (no
-// closed form for the per-pixel constants either: n sequential additions are not one product).  T.adaptive: the record's criterion
-// is evaluated after the round and the FROZEN bit set; otherwise `flags` is neither read nor written.
+// ---- the reduce of a staged launch into the planes of a call (vp_kernels.h PlaneSet; include/volpath.h vp_render_frames_layers,
+// _groups, _group_layers, their _stats forms, vp_render_frames_stats and the adaptive calls; vp_adaptive.cpp).  reduce_stage_k's job,
+// per slot of L.pixels (ALL pixels of the launch -- the rank's, or the ACTIVE ones of an adaptive round): the staged frames in frame
+// order, each split into one sample per plane, each plane's sample added to its accumulator exactly as reduce_stage_k adds -- one
+// binary32 addition per frame, a per-pixel constant of the launch nframes times (n sequential additions are not one product) -- and,
+// with records, its luminance to the plane's record: binary32 luminance, binary64 sums, one after the other (w never enters it).
 __device__ __forceinline__ float stats_luminance(const float4& v) { return (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z; }
 __device__ __forceinline__ bool stats_converged(double sy, double sy2, unsigned n, double tol, double fl)
 {
@@ -614,241 +507,135 @@ __device__ __forceinline__ bool stats_converged(double sy, double sy2, unsigned 
     const double rhs = ((tol * tol) * (nd - 1.0)) * (m * m);
     return lhs <= rhs;   // (false when either side is NaN)
 }
-__global__ __launch_bounds__(256) void reduce_stats_k(LaunchDev L, StatsDev T)
+// The split rule of each mode (vp_kernels.h): the samples s[0 .. N) that the planes receive from the staged word v of the first
+// staging plane.  plane2: its word of the second plane (LaunchDev::groups), read where the rule asks for it only.  through: the sample
+// is an unscattered path's throughput -- the sign bit of w, -0.0f included, marks it, and the light kernel's slots carry it without the
+// mark (`unmarked`): (x, y, z, 1) is the transmittance sample and the heat |w| goes to the other planes.  A plane that a sample does
+// not feed receives +0.0f in that channel, and the caller ADDS it like any other: the addition turns a -0.0f accumulator into +0.0f.
+template <int MODE>
+__device__ __forceinline__ void split_sample(const float4 v, const float4* plane2, bool unmarked, float4 (&s)[planes_of(MODE)])
 {
-    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= L.nslots) return;
-    unsigned pix = L.pixels[slot];
-    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
-    float4   a   = L.out[idx];
-    PixelStatsDev* rec = T.stats + idx;
-    double   sy = rec->sum_y, sy2 = rec->sum_y2;
-    if (slot >= L.const_from)
+    if constexpr (MODE == PLANES_ONE) s[0] = v;
+    else if constexpr (MODE == PLANES_GROUPS)
     {
-        const float4 v = L.stage_const[slot];
-        const double y = (double)stats_luminance(v), yy = y * y;
-        for (int f = 0; f < L.nframes; f++)
-        {
-            a   = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
-            sy  = sy + y;
-            sy2 = sy2 + yy;
-        }
+        s[0] = v;
+        s[1] = *plane2;
     }
     else
-        for (int f = 0; f < L.nframes; f++)
+    {
+        constexpr int T = planes_of(MODE) - 1;   // the transmittance plane: the last
+        if (unmarked || __builtin_signbit(v.w))
         {
-            float4 v = L.stage[(size_t)f * L.stage_stride + slot];
-            a        = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
-            const double y = (double)stats_luminance(v);
-            sy  = sy + y;
-            sy2 = sy2 + y * y;
+            for (int k = 0; k < T; k++) s[k] = make_float4(0.0f, 0.0f, 0.0f, __builtin_fabsf(v.w));
+            s[T] = make_float4(v.x, v.y, v.z, 1.0f);
         }
-    L.out[idx] = a;
-    const unsigned n = rec->n + (unsigned)L.nframes;
-    rec->sum_y = sy; rec->sum_y2 = sy2; rec->n = n;
-    if (T.adaptive && n >= T.min_frames && stats_converged(sy, sy2, n, T.tol, T.fl)) rec->flags |= 1u;   // VP_STATS_FROZEN
-}
-// ---- statistics on planes (include/volpath.h vp_render_frames_groups_stats / vp_render_frames_layers_stats): reduce_groups_k's and
-// reduce_layers_k's jobs with one record per plane and pixel.  The definition's step, once: the sample v that a plane's accumulator
-// receives adds its luminance to that plane's record (w never enters it).  One read and one write per record; `flags` is not touched
-// -- except by the adaptive form of either reduce (the last launch of a round of vp_render_adaptive_groups / _layers), which sets bit 0.
-__device__ __forceinline__ void stats_add_sample(double& sy, double& sy2, const float4& v)
-{
-    const double y = (double)stats_luminance(v);
-    sy  = sy + y;
-    sy2 = sy2 + y * y;
-}
-__device__ __forceinline__ unsigned stats_store(PixelStatsDev* rec, double sy, double sy2, unsigned nframes)
-{
-    const unsigned n = rec->n + nframes;
-    rec->sum_y = sy; rec->sum_y2 = sy2; rec->n = n;
-    return n;
-}
-// The adaptive form of the two reduces (include/volpath.h vp_render_adaptive_groups / _layers; the last launch of a round): both records
-// of the pixel are frozen iff each has its min_frames and meets vp_render_adaptive's criterion with its own n, tolerance and floor.
-// ADAPT false: the plain _stats reduce, which neither reads nor writes `flags` (nothing of C is looked at).  The bodies take L by value,
-// as the kernels do: by reference the plain instances' scalar registers moved.
-template <bool ADAPT>
-__device__ __forceinline__ void stats_freeze_planes(const PlaneCriterionDev& C, PixelStatsDev* r0, double y0, double y02, unsigned n0, PixelStatsDev* r1, double y1,
-                                                    double y12, unsigned n1)
-{
-    if constexpr (ADAPT)
-        if (n0 >= C.min_frames && n1 >= C.min_frames && stats_converged(y0, y02, n0, C.tol[0], C.fl[0]) && stats_converged(y1, y12, n1, C.tol[1], C.fl[1]))
+        else
         {
-            r0->flags |= 1u;   // VP_STATS_FROZEN, in both
-            r1->flags |= 1u;
+            s[0] = v;
+            if constexpr (MODE == PLANES_GROUP_LAYERS) s[1] = *plane2;
+            s[T] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
+    }
 }
-template <bool ADAPT>
-__device__ __forceinline__ void reduce_groups_stats_body(LaunchDev L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, const PlaneCriterionDev& C)
+// What a reduce instance receives beside L, sized by its planes: the accumulators and the light kernel's slots; with STATS the record
+// buffers; with ADAPT the criterion.  (A one-plane instance carries one pointer of each, a two-plane one no third plane's.)
+template <int N> struct ReducePlanesDev { float4* acc[N]; unsigned light_from, light_to; };
+template <int N> struct ReduceStatsDev : ReducePlanesDev<N> { PixelStatsDev* rec[N]; };
+template <int N> struct ReduceAdaptDev : ReduceStatsDev<N> { double tol[N], fl[N]; unsigned min_frames; };
+template <int N, bool STATS, bool ADAPT>
+using ReduceDev = std::conditional_t<ADAPT, ReduceAdaptDev<N>, std::conditional_t<STATS, ReduceStatsDev<N>, ReducePlanesDev<N>>>;
+// One read and one write per accumulator and record.  ADAPT (the last launch of an adaptive round): all records of the slot are frozen
+// iff each has min_frames and meets the criterion with its own n, tolerance and floor; otherwise `flags` is neither read nor written.
+// L by value, as in reduce_stage_k.
+template <int MODE, bool STATS, bool ADAPT>
+__global__ __launch_bounds__(256) void reduce_planes_k(LaunchDev L, ReduceDev<planes_of(MODE), STATS, ADAPT> D)
 {
+    static_assert(STATS || !ADAPT, "the criterion is a statement about the records");
+    constexpr int N = planes_of(MODE);
     unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= L.nslots) return;
     unsigned pix = L.pixels[slot];
     size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
-    float4   a = L.out[idx], k = sky[idx];
-    double   ay = sun_stats[idx].sum_y, ay2 = sun_stats[idx].sum_y2, ky = sky_stats[idx].sum_y, ky2 = sky_stats[idx].sum_y2;
-    const bool   constant = slot >= L.const_from;   // (a constant of the launch: the first row of either plane, added nframes times)
-    const size_t stride   = constant ? 0 : L.stage_stride;
+    float4   a[N];
+    double   sy[N], sy2[N];
+#pragma unroll
+    for (int k = 0; k < N; k++)
+    {
+        a[k] = D.acc[k][idx];
+        if constexpr (STATS) { sy[k] = D.rec[k][idx].sum_y; sy2[k] = D.rec[k][idx].sum_y2; }
+    }
+    const bool unmarked = (MODE & PLANES_LAYERS) && slot >= D.light_from && slot < D.light_to;
+    // (a constant of the launch lies in the first row of either staging plane, once: the same word for every frame)
+    const bool    constant = slot >= L.const_from;
+    const size_t  stride   = constant ? 0 : L.stage_stride;
+    const float4* stage    = (constant ? L.stage_const : L.stage) + slot;
+    const float4* plane2   = (MODE & PLANES_GROUPS) ? L.groups + slot : nullptr;
     for (int f = 0; f < L.nframes; f++)
     {
-        const float4 v = L.stage[(size_t)f * stride + slot], w = L.groups[(size_t)f * stride + slot];
-        a = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
-        k = make_float4(k.x + w.x, k.y + w.y, k.z + w.z, k.w + w.w);
-        stats_add_sample(ay, ay2, v);
-        stats_add_sample(ky, ky2, w);
-    }
-    L.out[idx] = a;
-    sky[idx]   = k;
-    const unsigned n0 = stats_store(sun_stats + idx, ay, ay2, (unsigned)L.nframes);
-    const unsigned n1 = stats_store(sky_stats + idx, ky, ky2, (unsigned)L.nframes);
-    stats_freeze_planes<ADAPT>(C, sun_stats + idx, ay, ay2, n0, sky_stats + idx, ky, ky2, n1);
-}
-__global__ __launch_bounds__(256) void reduce_groups_stats_k(LaunchDev L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats)
-{
-    reduce_groups_stats_body<false>(L, sky, sun_stats, sky_stats, PlaneCriterionDev{});
-}
-__global__ __launch_bounds__(256) void reduce_groups_stats_adaptive_k(LaunchDev L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PlaneCriterionDev C)
-{
-    reduce_groups_stats_body<true>(L, sky, sun_stats, sky_stats, C);
-}
-// (layers: the samples are those add_layer_sample adds -- the fg sample of an unscattered path is (0, 0, 0, heat), its trans sample
-// (x, y, z, 1); a scattered path's are the staged word and (0, 0, 0, 0))
-__device__ __forceinline__ void add_layer_sample_stats(float4& a, float4& t, double& ay, double& ay2, double& ty, double& ty2, const float4 v, bool unmarked)
-{
-    const bool   through = unmarked || __builtin_signbit(v.w);
-    const float4 fg = through ? make_float4(0.0f, 0.0f, 0.0f, __builtin_fabsf(v.w)) : v;
-    const float4 tr = through ? make_float4(v.x, v.y, v.z, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    add_layer_sample(a, t, v, unmarked);
-    stats_add_sample(ay, ay2, fg);
-    stats_add_sample(ty, ty2, tr);
-}
-template <bool ADAPT>
-__device__ __forceinline__ void reduce_layers_stats_body(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats,
-                                                         PixelStatsDev* trans_stats, const PlaneCriterionDev& C)
-{
-    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= L.nslots) return;
-    unsigned pix = L.pixels[slot];
-    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
-    float4   a = L.out[idx], t = trans[idx];
-    double   ay = fg_stats[idx].sum_y, ay2 = fg_stats[idx].sum_y2, ty = trans_stats[idx].sum_y, ty2 = trans_stats[idx].sum_y2;
-    const bool   unmarked = slot >= light_from && slot < light_to;
-    const size_t stride   = slot >= L.const_from ? 0 : L.stage_stride;
-    for (int f = 0; f < L.nframes; f++) add_layer_sample_stats(a, t, ay, ay2, ty, ty2, L.stage[(size_t)f * stride + slot], unmarked);
-    L.out[idx] = a;
-    trans[idx] = t;
-    const unsigned n0 = stats_store(fg_stats + idx, ay, ay2, (unsigned)L.nframes);
-    const unsigned n1 = stats_store(trans_stats + idx, ty, ty2, (unsigned)L.nframes);
-    stats_freeze_planes<ADAPT>(C, fg_stats + idx, ay, ay2, n0, trans_stats + idx, ty, ty2, n1);
-}
-__global__ __launch_bounds__(256) void reduce_layers_stats_k(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats,
-                                                             PixelStatsDev* trans_stats)
-{
-    reduce_layers_stats_body<false>(L, trans, light_from, light_to, fg_stats, trans_stats, PlaneCriterionDev{});
-}
-__global__ __launch_bounds__(256) void reduce_layers_stats_adaptive_k(LaunchDev L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats,
-                                                                      PixelStatsDev* trans_stats, PlaneCriterionDev C)
-{
-    reduce_layers_stats_body<true>(L, trans, light_from, light_to, fg_stats, trans_stats, C);
-}
-// (group layers, include/volpath.h vp_render_frames_group_layers_stats: reduce_group_layers_k's job with one record per plane -- the three
-// samples add_group_layer_sample adds are the ones whose luminances go into the three records; `flags` is neither read nor written --
-// except by the adaptive form, the last launch of a round of vp_render_adaptive_group_layers: all three records of the pixel are frozen
-// iff each has its min_frames and meets the criterion with its own n, tolerance and floor.  A descriptor of its own, so that the
-// two-plane reduces keep their kernel arguments: profiles/adaptive_group_layers_kernel_resources.txt)
-template <bool ADAPT>
-__device__ __forceinline__ void stats_freeze_planes3(const Plane3CriterionDev& C, PixelStatsDev* r0, double y0, double y02, unsigned n0, PixelStatsDev* r1, double y1,
-                                                     double y12, unsigned n1, PixelStatsDev* r2, double y2, double y22, unsigned n2)
-{
-    if constexpr (ADAPT)
-        if (n0 >= C.min_frames && n1 >= C.min_frames && n2 >= C.min_frames && stats_converged(y0, y02, n0, C.tol[0], C.fl[0]) &&
-            stats_converged(y1, y12, n1, C.tol[1], C.fl[1]) && stats_converged(y2, y22, n2, C.tol[2], C.fl[2]))
+        float4 s[N];
+        split_sample<MODE>(stage[(size_t)f * stride], plane2 + (size_t)f * stride, unmarked, s);
+#pragma unroll
+        for (int k = 0; k < N; k++)
         {
-            r0->flags |= 1u;   // VP_STATS_FROZEN, in all three
-            r1->flags |= 1u;
-            r2->flags |= 1u;
+            a[k] = make_float4(a[k].x + s[k].x, a[k].y + s[k].y, a[k].z + s[k].z, a[k].w + s[k].w);
+            if constexpr (STATS)
+            {
+                const double y = (double)stats_luminance(s[k]);
+                sy[k]  = sy[k] + y;
+                sy2[k] = sy2[k] + y * y;
+            }
         }
-}
-template <bool ADAPT>
-__device__ __forceinline__ void reduce_group_layers_stats_body(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to,
-                                                               PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PixelStatsDev* trans_stats,
-                                                               const Plane3CriterionDev& C)
-{
-    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= L.nslots) return;
-    unsigned pix = L.pixels[slot];
-    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
-    float4   a = L.out[idx], k = sky[idx], t = trans[idx];
-    double   ay = sun_stats[idx].sum_y, ay2 = sun_stats[idx].sum_y2, ky = sky_stats[idx].sum_y, ky2 = sky_stats[idx].sum_y2;
-    double   ty = trans_stats[idx].sum_y, ty2 = trans_stats[idx].sum_y2;
-    const bool   unmarked = slot >= light_from && slot < light_to;
-    const size_t stride   = slot >= L.const_from ? 0 : L.stage_stride;
-    for (int f = 0; f < L.nframes; f++)
-    {
-        float4 s0, s1, s2;
-        add_group_layer_sample(a, k, t, L.stage[(size_t)f * stride + slot], L.groups + (size_t)f * stride + slot, unmarked, s0, s1, s2);
-        stats_add_sample(ay, ay2, s0);
-        stats_add_sample(ky, ky2, s1);
-        stats_add_sample(ty, ty2, s2);
     }
-    L.out[idx] = a;
-    sky[idx]   = k;
-    trans[idx] = t;
-    const unsigned n0 = stats_store(sun_stats + idx, ay, ay2, (unsigned)L.nframes);
-    const unsigned n1 = stats_store(sky_stats + idx, ky, ky2, (unsigned)L.nframes);
-    const unsigned n2 = stats_store(trans_stats + idx, ty, ty2, (unsigned)L.nframes);
-    stats_freeze_planes3<ADAPT>(C, sun_stats + idx, ay, ay2, n0, sky_stats + idx, ky, ky2, n1, trans_stats + idx, ty, ty2, n2);
-}
-__global__ __launch_bounds__(256) void reduce_group_layers_stats_k(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to,
-                                                                   PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PixelStatsDev* trans_stats)
-{
-    reduce_group_layers_stats_body<false>(L, sky, trans, light_from, light_to, sun_stats, sky_stats, trans_stats, Plane3CriterionDev{});
-}
-__global__ __launch_bounds__(256) void reduce_group_layers_stats_adaptive_k(LaunchDev L, float4* sky, float4* trans, unsigned light_from, unsigned light_to,
-                                                                            PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, PixelStatsDev* trans_stats,
-                                                                            Plane3CriterionDev C)
-{
-    reduce_group_layers_stats_body<true>(L, sky, trans, light_from, light_to, sun_stats, sky_stats, trans_stats, C);
+#pragma unroll
+    for (int k = 0; k < N; k++) D.acc[k][idx] = a[k];
+    if constexpr (STATS)
+    {
+        unsigned n[N];
+        bool     freeze = ADAPT;
+#pragma unroll
+        for (int k = 0; k < N; k++)
+        {
+            PixelStatsDev* rec = D.rec[k] + idx;
+            n[k] = rec->n + (unsigned)L.nframes;
+            rec->sum_y = sy[k]; rec->sum_y2 = sy2[k]; rec->n = n[k];
+            if constexpr (ADAPT) freeze = freeze && n[k] >= D.min_frames && stats_converged(sy[k], sy2[k], n[k], D.tol[k], D.fl[k]);
+        }
+        if constexpr (ADAPT)
+            if (freeze)
+            {
+#pragma unroll
+                for (int k = 0; k < N; k++) D.rec[k][idx].flags |= 1u;   // VP_STATS_FROZEN, in all of them
+            }
+    }
 }
 // A stable compaction of a class-ordered pixel list (src: n[0] general, n[1] light, n[2] box-missing pixels) by the FROZEN bit of the
 // pixels' records: the active pixels of each class in the order they have in src, class by class, and the three counts.  The pattern of
-// pixlist_*_k: per-block class counts, pixlist_scan_k over them, the scatter with wave-ballot ranks.
+// pixlist_*_k: per-block class counts, pixlist_scan_k over them, the scatter with wave-ballot ranks.  N: the record buffers of the
+// adaptive call's planes -- a slot is dropped if ANY of its N records is frozen.
+template <int N>
 struct CompactDev
 {
     const unsigned* src;
     unsigned n[3];
     unsigned width;
-    const PixelStatsDev* stats;
+    const PixelStatsDev* stats[N];
 };
-// ... with the second plane's records of an adaptive plane call: a slot is dropped if EITHER record is frozen (a descriptor of its own,
-// so that the one-record kernels keep their kernel arguments and registers: profiles/adaptive_planes_kernel_resources.txt)
-struct CompactPlanesDev : CompactDev
-{
-    const PixelStatsDev* stats2;
-};
-// ... and with the three of an adaptive group-layers call: a slot is dropped if ANY of the three records is frozen (again its own descriptor)
-struct CompactPlanes3Dev : CompactDev
-{
-    const PixelStatsDev *stats2, *stats3;
-};
-template <class Dev>
-__device__ __forceinline__ unsigned compact_slot(const Dev& D, unsigned s, unsigned& pix)
+template <int N>
+__device__ __forceinline__ unsigned compact_slot(const CompactDev<N>& D, unsigned s, unsigned& pix)
 {
     // class of slot s of src (3 = beyond the list, or frozen) and its pixel
     pix = 0;
     if (s >= D.n[0] + D.n[1] + D.n[2]) return 3u;
     pix = D.src[s];
     const size_t idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * D.width;
-    if (D.stats[idx].flags & 1u) return 3u;
-    if constexpr (std::is_same<Dev, CompactPlanesDev>::value)
-        if (D.stats2[idx].flags & 1u) return 3u;
-    if constexpr (std::is_same<Dev, CompactPlanes3Dev>::value)
-        if ((D.stats2[idx].flags | D.stats3[idx].flags) & 1u) return 3u;
+    unsigned flags = 0;
+#pragma unroll
+    for (int k = 0; k < N; k++) flags |= D.stats[k][idx].flags;
+    if (flags & 1u) return 3u;
     return s < D.n[0] ? 0u : s < D.n[0] + D.n[1] ? 1u : 2u;
 }
-template <class Dev>
-__device__ __forceinline__ void compact_count_body(const Dev& D, unsigned* block_counts)
+template <int N>
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_count_k(CompactDev<N> D, unsigned* block_counts)
 {
     __shared__ unsigned cnt[3];
     if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
@@ -863,13 +650,8 @@ __device__ __forceinline__ void compact_count_body(const Dev& D, unsigned* block
     __syncthreads();
     if (threadIdx.x < 3) block_counts[3 * blockIdx.x + threadIdx.x] = cnt[threadIdx.x];
 }
-// (compact_*_k: one record buffer, vp_render_adaptive's; compact_planes_*_k: the two of an adaptive plane call; compact_planes3_*_k: the
-// three of vp_render_adaptive_group_layers)
-__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_count_k(CompactDev D, unsigned* block_counts) { compact_count_body(D, block_counts); }
-__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes_count_k(CompactPlanesDev D, unsigned* block_counts) { compact_count_body(D, block_counts); }
-__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes3_count_k(CompactPlanes3Dev D, unsigned* block_counts) { compact_count_body(D, block_counts); }
-template <class Dev>
-__device__ __forceinline__ void compact_write_body(const Dev& D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
+template <int N>
+__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_write_k(CompactDev<N> D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
 {
     __shared__ unsigned wave_cnt[VP_PIXLIST_BLOCK / 64][3];
     unsigned pix;
@@ -889,18 +671,6 @@ __device__ __forceinline__ void compact_write_body(const Dev& D, const unsigned*
     const unsigned class_base = c == 0 ? 0u : c == 1 ? totals[0] : totals[0] + totals[1];
     // (at most as many active pixels as src holds: `out` has room for all of src)
     out[class_base + block_offsets[3 * blockIdx.x + c] + before + rank_in_wave] = pix;
-}
-__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_write_k(CompactDev D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
-{
-    compact_write_body(D, block_offsets, totals, out);
-}
-__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes_write_k(CompactPlanesDev D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
-{
-    compact_write_body(D, block_offsets, totals, out);
-}
-__global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_planes3_write_k(CompactPlanes3Dev D, const unsigned* block_offsets, const unsigned* totals, unsigned* out)
-{
-    compact_write_body(D, block_offsets, totals, out);
 }
 // the output stage of a render with per-pixel sample counts: dst = src * (scale / n), a correctly rounded binary32 divide; n = 0 gives 0
 __global__ void scale_by_count_k(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float scale)
@@ -1690,16 +1460,19 @@ __global__ void test_density_k(SceneDev S, const float* pos, float* out, int n)
     fprintf(stderr, "volpath_hip: this kernel variant is not compiled (development build, fast arithmetic mode, or a configuration the API refuses)\n");
     abort();
 }
-// the launch census (vp_kernels.h): process-wide host counters, one per table entry of vp_dispatch.h, per unit and kind
-static std::atomic<uint32_t> g_census_render[2][2][kRenderInsts];   // [unit][CENSUS_RENDER / CENSUS_LAYERS]
-static std::atomic<uint32_t> g_census_approach[2][kApproachInsts];  // [unit]
+// the launch census (vp_kernels.h): process-wide host counters, one per table entry of vp_dispatch.h -- per unit, render_k's tables by
+// plane mode and the approach walk's
+static std::atomic<uint32_t> g_census_render[2][kPlaneModes][kRenderInsts];
+static std::atomic<uint32_t> g_census_approach[2][kApproachInsts];
 static std::atomic<uint32_t>* census_counters(int unit, int kind)
 {
     if (unit < 0 || unit > 1) return nullptr;
-    if (kind == CENSUS_RENDER || kind == CENSUS_LAYERS) return g_census_render[unit][kind];
-    return kind == CENSUS_APPROACH ? g_census_approach[unit] : nullptr;
+    if (kind == CENSUS_APPROACH) return g_census_approach[unit];
+    for (int mode = 0; mode < kPlaneModes; mode++)
+        if (kind == census_of_planes(mode)) return g_census_render[unit][mode];
+    return nullptr;
 }
-size_t census_size(int kind) { return kind == CENSUS_RENDER || kind == CENSUS_LAYERS ? kRenderInsts : kind == CENSUS_APPROACH ? kApproachInsts : 0; }
+size_t census_size(int kind) { return kind == CENSUS_APPROACH ? kApproachInsts : census_counters(0, kind) ? kRenderInsts : 0; }
 void census_record(int unit, int kind, unsigned index)
 {
     std::atomic<uint32_t>* c = census_counters(unit, kind);
@@ -1718,38 +1491,6 @@ void census_read(int unit, int kind, unsigned* launches, unsigned char* built, s
     }
 }
 void census_built(int kind, unsigned char* built, size_t count) { dispatch_census_built(kind, built, count); }
-// the groups table's census (vp_kernels.h): counters of its own beside the kinds above
-static std::atomic<uint32_t> g_census_groups[kRenderInsts];
-void groups_census_record(unsigned index)
-{
-    if (index < kRenderInsts) g_census_groups[index].fetch_add(1u, std::memory_order_relaxed);
-}
-void groups_census_read(unsigned* launches, unsigned char* built, size_t count, bool reset)
-{
-    if (count > kRenderInsts) count = kRenderInsts;
-    if (built) dispatch_groups_built(built, count);
-    for (size_t i = 0; i < count; i++)
-    {
-        const uint32_t n = reset ? g_census_groups[i].exchange(0u, std::memory_order_relaxed) : g_census_groups[i].load(std::memory_order_relaxed);
-        if (launches) launches[i] = n;
-    }
-}
-// ... and the group-layers table's
-static std::atomic<uint32_t> g_census_group_layers[kRenderInsts];
-void group_layers_census_record(unsigned index)
-{
-    if (index < kRenderInsts) g_census_group_layers[index].fetch_add(1u, std::memory_order_relaxed);
-}
-void group_layers_census_read(unsigned* launches, unsigned char* built, size_t count, bool reset)
-{
-    if (count > kRenderInsts) count = kRenderInsts;
-    if (built) dispatch_group_layers_built(built, count);
-    for (size_t i = 0; i < count; i++)
-    {
-        const uint32_t n = reset ? g_census_group_layers[i].exchange(0u, std::memory_order_relaxed) : g_census_group_layers[i].load(std::memory_order_relaxed);
-        if (launches) launches[i] = n;
-    }
-}
 void launch_render(const SceneDev& S, const LaunchDev& L, int est, int rng, bool quant, bool half, bool count, int lds_form, bool mis, int trk,
                    int blocks, hipStream_t st)
 {
@@ -1779,7 +1520,7 @@ void launch_miss_fill(const SceneDev& S, const LaunchDev& L, bool local_estimato
     {
         // (a groups launch: writers of their own, which stage the two constants; the counting launches they have no tallies for are refused.
         // A group-layers launch: the writers below, as in a layers launch -- its constants are marked transmittance samples, for which
-        // reduce_group_layers_k reads no second plane)
+        // the reduce reads no second plane: split_sample)
         if (L.sub_shift) hipLaunchKernelGGL(subpixel_fill_groups_k, dim3(((L.nslots << (2u * L.sub_shift)) + 255) / 256), dim3(256), 0, st, S, L);
         else hipLaunchKernelGGL(miss_fill_groups_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, S, L);
         return;
@@ -1918,26 +1659,6 @@ void launch_reduce(const LaunchDev& L, hipStream_t st)
     unsigned per_frame = L.nslots;
     hipLaunchKernelGGL(reduce_stage_k, dim3((per_frame + 255) / 256), dim3(256), 0, st, L);
 }
-void launch_reduce_layers(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st)
-{
-    hipLaunchKernelGGL(reduce_layers_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, trans, light_from, light_to);
-}
-void launch_reduce_groups(const LaunchDev& L, float4* sky, hipStream_t st)
-{
-    hipLaunchKernelGGL(reduce_groups_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky);
-}
-void launch_reduce_group_layers(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, hipStream_t st)
-{
-    hipLaunchKernelGGL(reduce_group_layers_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, sky, trans, light_from, light_to);
-}
-void launch_reduce_group_layers_stats(const LaunchDev& L, float4* sky, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* sun_stats,
-                                      PixelStatsDev* sky_stats, PixelStatsDev* trans_stats, const Plane3CriterionDev* C, hipStream_t st)
-{
-    const dim3 grid((L.nslots + 255) / 256);
-    if (C)
-        hipLaunchKernelGGL(reduce_group_layers_stats_adaptive_k, grid, dim3(256), 0, st, L, sky, trans, light_from, light_to, sun_stats, sky_stats, trans_stats, *C);
-    else hipLaunchKernelGGL(reduce_group_layers_stats_k, grid, dim3(256), 0, st, L, sky, trans, light_from, light_to, sun_stats, sky_stats, trans_stats);
-}
 void launch_relight_composite(float4* dst, const float4* sun, const float4* sky, const float4* trans, float3 sun_gain, float3 sky_gain, const float4* plate,
                               float r, float g, float b, int size, float s, hipStream_t st)
 {
@@ -1947,39 +1668,65 @@ void launch_relight(float4* dst, const float4* sun, const float4* sky, float3 su
 {
     hipLaunchKernelGGL(relight_k, dim3((size + 255) / 256), dim3(256), 0, st, dst, sun, sky, sun_gain, sky_gain, size, s);
 }
-void launch_reduce_stats(const LaunchDev& L, const StatsDev& T, hipStream_t st)
+template <int MODE, bool STATS, bool ADAPT>
+static void launch_reduce_instance(const LaunchDev& L, const PlaneSet& S, unsigned light_from, unsigned light_to, hipStream_t st)
 {
-    hipLaunchKernelGGL(reduce_stats_k, dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, T);
+    constexpr int N = planes_of(MODE);
+    ReduceDev<N, STATS, ADAPT> D;
+    D.light_from = light_from; D.light_to = light_to;
+    for (int k = 0; k < N; k++)
+    {
+        D.acc[k] = S.acc[k];
+        if constexpr (STATS) D.rec[k] = S.rec[k];
+        if constexpr (ADAPT) { D.tol[k] = S.tol[k]; D.fl[k] = S.fl[k]; }
+    }
+    if constexpr (ADAPT) D.min_frames = S.min_frames;
+    hipLaunchKernelGGL((reduce_planes_k<MODE, STATS, ADAPT>), dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, D);
 }
-void launch_reduce_groups_stats(const LaunchDev& L, float4* sky, PixelStatsDev* sun_stats, PixelStatsDev* sky_stats, const PlaneCriterionDev* C, hipStream_t st)
+template <int MODE>
+static void launch_reduce_mode(const LaunchDev& L, const PlaneSet& S, unsigned light_from, unsigned light_to, bool last, hipStream_t st)
 {
-    const dim3 grid((L.nslots + 255) / 256);
-    if (C) hipLaunchKernelGGL(reduce_groups_stats_adaptive_k, grid, dim3(256), 0, st, L, sky, sun_stats, sky_stats, *C);
-    else hipLaunchKernelGGL(reduce_groups_stats_k, grid, dim3(256), 0, st, L, sky, sun_stats, sky_stats);
+    if (!S.stats())
+    {
+        // (one plane, no records: reduce_stage_k, the reduce the benchmark times, stays the kernel it was)
+        if constexpr (MODE == PLANES_ONE) launch_reduce(L, st);
+        else launch_reduce_instance<MODE, false, false>(L, S, light_from, light_to, st);
+    }
+    else if (S.adaptive && last) launch_reduce_instance<MODE, true, true>(L, S, light_from, light_to, st);
+    else launch_reduce_instance<MODE, true, false>(L, S, light_from, light_to, st);
 }
-void launch_reduce_layers_stats(const LaunchDev& L, float4* trans, unsigned light_from, unsigned light_to, PixelStatsDev* fg_stats, PixelStatsDev* trans_stats,
-                                const PlaneCriterionDev* C, hipStream_t st)
+void launch_reduce_planes(const LaunchDev& L, const PlaneSet& S, unsigned light_from, unsigned light_to, bool last, hipStream_t st)
 {
-    const dim3 grid((L.nslots + 255) / 256);
-    if (C) hipLaunchKernelGGL(reduce_layers_stats_adaptive_k, grid, dim3(256), 0, st, L, trans, light_from, light_to, fg_stats, trans_stats, *C);
-    else hipLaunchKernelGGL(reduce_layers_stats_k, grid, dim3(256), 0, st, L, trans, light_from, light_to, fg_stats, trans_stats);
+    switch (S.mode)
+    {
+    case PLANES_ONE: launch_reduce_mode<PLANES_ONE>(L, S, light_from, light_to, last, st); break;
+    case PLANES_LAYERS: launch_reduce_mode<PLANES_LAYERS>(L, S, light_from, light_to, last, st); break;
+    case PLANES_GROUPS: launch_reduce_mode<PLANES_GROUPS>(L, S, light_from, light_to, last, st); break;
+    default: launch_reduce_mode<PLANES_GROUP_LAYERS>(L, S, light_from, light_to, last, st); break;
+    }
 }
-void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PixelStatsDev* stats, const PixelStatsDev* stats2,
-                           const PixelStatsDev* stats3, unsigned* d_block_counts, unsigned* d_totals, unsigned* d_out, hipStream_t st)
+template <int N>
+static void launch_compact_planes(const unsigned* src, const unsigned n[3], unsigned width, const PlaneSet& S, unsigned* d_block_counts, unsigned* d_totals,
+                                  unsigned* d_out, hipStream_t st)
 {
-    CompactPlanesDev D;
-    D.src = src; D.n[0] = n[0]; D.n[1] = n[1]; D.n[2] = n[2]; D.width = width; D.stats = stats; D.stats2 = stats2;
-    CompactPlanes3Dev D3;
-    (CompactDev&)D3 = D; D3.stats2 = stats2; D3.stats3 = stats3;
+    CompactDev<N> D;
+    D.src = src; D.n[0] = n[0]; D.n[1] = n[1]; D.n[2] = n[2]; D.width = width;
+    for (int k = 0; k < N; k++) D.stats[k] = S.rec[k];
     const unsigned nblocks = compact_blocks(n[0] + n[1] + n[2]);
     const dim3 grid(nblocks), block(VP_PIXLIST_BLOCK);
-    if (stats3) hipLaunchKernelGGL(compact_planes3_count_k, grid, block, 0, st, D3, d_block_counts);
-    else if (stats2) hipLaunchKernelGGL(compact_planes_count_k, grid, block, 0, st, D, d_block_counts);
-    else hipLaunchKernelGGL(compact_count_k, grid, block, 0, st, (CompactDev)D, d_block_counts);
+    hipLaunchKernelGGL(compact_count_k<N>, grid, block, 0, st, D, d_block_counts);
     hipLaunchKernelGGL(pixlist_scan_k, dim3(1), block, 0, st, d_block_counts, nblocks, d_totals);
-    if (stats3) hipLaunchKernelGGL(compact_planes3_write_k, grid, block, 0, st, D3, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
-    else if (stats2) hipLaunchKernelGGL(compact_planes_write_k, grid, block, 0, st, D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
-    else hipLaunchKernelGGL(compact_write_k, grid, block, 0, st, (CompactDev)D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
+    hipLaunchKernelGGL(compact_write_k<N>, grid, block, 0, st, D, (const unsigned*)d_block_counts, (const unsigned*)d_totals, d_out);
+}
+void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PlaneSet& S, unsigned* d_block_counts, unsigned* d_totals,
+                           unsigned* d_out, hipStream_t st)
+{
+    switch (S.n())
+    {
+    case 1: launch_compact_planes<1>(src, n, width, S, d_block_counts, d_totals, d_out, st); break;
+    case 2: launch_compact_planes<2>(src, n, width, S, d_block_counts, d_totals, d_out, st); break;
+    default: launch_compact_planes<3>(src, n, width, S, d_block_counts, d_totals, d_out, st); break;
+    }
 }
 void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st)
 {

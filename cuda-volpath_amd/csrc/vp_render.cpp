@@ -223,11 +223,9 @@ struct LaunchPlan
     Target     T;                 // where its launches run: the caller's stream, the look-ahead slot handed in, or a pipeline slot
     bool       lookahead;         // ... a look-ahead batch (cancellable, never one of the caller's timed launches)
     bool       stage_only;        // ... which is staged whole and not reduced
-    const StatsDev* stats;        // the reduce also takes the statistics (of both planes of a layers or groups call: StatsDev::plane2)
-    float4*    layers;            // a layers call (vp_render_frames_layers): the transmittance accumulator; the reduce splits the samples (reduce_layers_k)
-    float4*    groups;            // a light-groups call (vp_render_frames_groups): the sky accumulator; a launch stages two planes (reduce_groups_k)
-                                  // (both: a group-layers call, vp_render_frames_group_layers -- two staging planes, three accumulators: reduce_group_layers_k)
-    size_t planes() const { return groups ? 2u : 1u; }   // staging planes per frame
+    PlaneSet   PS;                // what the call accumulates into (vp_kernels.h): its mode, accumulators, records and criterion; PS.acc[0] is d_out
+    size_t stage_planes() const { return PS.groups() ? 2u : 1u; }   // staging planes per frame: a groups mode stages the sky's samples in a second
+    bool plain() const { return PS.mode == PLANES_ONE && !PS.stats(); }   // vp_render_frames' own call: one plane, no records
     // the slots of the list, general pixels first: where the class a kernel integrates ends (the general class and a light class that
     // is not written as constants), i.e. where the per-pixel constants of a launch begin -- const_from and the layers reduce's range
     unsigned integrated_end() const { return PL.n_general + ((PL.n_light && !light_const) ? PL.n_light : 0u); }
@@ -309,9 +307,9 @@ static int plan_target(int nframes, const Target* tgt, const PixelLists* lists, 
 {
     // a call with statistics is staged whatever its length (render_k's direct accumulation has none) and stays on the caller's stream
     // (a layers call too: the direct accumulation has no second target)
-    A.staged = nframes > 1 || A.stage_only || A.stats || A.layers || A.groups;
+    A.staged = nframes > 1 || A.stage_only || !A.plain();
     A.T      = tgt ? *tgt : Target{&G.target[0], G.stream};   // (a pipelined call: a slot's, below)
-    A.max_f  = A.staged ? stage_frames_cap(A.per_frame, A.T.rt->stage.bytes, A.planes()) : 1;
+    A.max_f  = A.staged ? stage_frames_cap(A.per_frame, A.T.rt->stage.bytes, A.stage_planes()) : 1;
     // The staging slot of the decomposition estimator's hand-over holds the segment origin and the distance reached in it: the stream's
     // state (a pair index, or sampler.h's two words) goes beside it.  Sized ONCE, before the launch loop (no synchronisation, no early
     // return between a launch's events).
@@ -319,7 +317,7 @@ static int plan_target(int nframes, const Target* tgt, const PixelLists* lists, 
     // A staged call of vp_render_frames goes to the next pipeline slot when the slot holds it in one launch (counting launches stay on the
     // caller's stream).  Otherwise -- VP_NO_PIPELINE, no memory for the slot -- the caller's stream, as before: same bits either way.
     A.slot  = G.pipe_next;
-    A.piped = !tgt && !A.stage_only && !lists && !A.stats && !A.layers && !A.groups && nframes > 1 && G.pipeline && !G.count && pipe_target(A.per_frame, nframes, A.appr_aux_needed, &A.T);
+    A.piped = !tgt && !A.stage_only && !lists && A.plain() && nframes > 1 && G.pipeline && !G.count && pipe_target(A.per_frame, nframes, A.appr_aux_needed, &A.T);
     if (A.piped) A.max_f = (size_t)nframes;
     else if (!tgt) G.pipe_fence = true;   // (the caller's stream uses slot 0's buffers: the next pipelined launch waits for it)
     G.last_pipelined = A.piped ? 1 : 0;
@@ -332,8 +330,8 @@ static int plan_target(int nframes, const Target* tgt, const PixelLists* lists, 
 static int reserve_launch_stage(LaunchPlan& A, int f, bool* smaller)
 {
     *smaller = false;
-    const size_t exact = A.per_frame * (size_t)f * sizeof(float4) * A.planes();
-    const int rc = reserve_stage(A.T, exact, A.per_frame * A.sized_frames(f) * sizeof(float4) * A.planes());
+    const size_t exact = A.per_frame * (size_t)f * sizeof(float4) * A.stage_planes();
+    const int rc = reserve_stage(A.T, exact, A.per_frame * A.sized_frames(f) * sizeof(float4) * A.stage_planes());
     if (rc || exact <= A.T.rt->stage.bytes) return rc;
     if (A.stage_only) return fail(VP_E_NOMEM, "no memory for a look-ahead batch of %d frames", f);
     if (f <= 1) return fail(VP_E_NOMEM, "no memory for one staged frame (%zu bytes)", exact);
@@ -568,40 +566,9 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
     if (!L.stage || A.stage_only) return VP_OK;
     if (A.piped)
         if (int rc = pipe_await_launch(A.slot, A.T.stream)) return rc;
-    // (an adaptive round on planes -- vp_adaptive.cpp render_adaptive_planes --: the plain form for every launch but the round's last,
-    // the adaptive form, with the per-plane criterion, for that one; the unmarked range of a layers reduce is the light KERNEL's slots
-    // of the list in use, the caller's included)
-    PlaneCriterionDev C = {};
-    const bool freeze = A.stats && A.stats->plane2 && A.stats->adaptive && last;
-    if (freeze) C = {{A.stats->plane_tol[0], A.stats->plane_tol[1]}, {A.stats->plane_fl[0], A.stats->plane_fl[1]}, A.stats->min_frames};
-    const unsigned light_from = A.PL.n_general, light_to = A.integrated_end();   // (the light kernel's slots: its samples carry no mark)
-    if (A.groups && A.layers && A.stats)
-    {
-        // (three planes, vp_render_adaptive_group_layers: likewise, with the three-record criterion)
-        Plane3CriterionDev C3 = {};
-        if (freeze)
-        {
-            for (int k = 0; k < 3; k++) { C3.tol[k] = A.stats->plane_tol[k]; C3.fl[k] = A.stats->plane_fl[k]; }
-            C3.min_frames = A.stats->min_frames;
-        }
-        launch_reduce_group_layers_stats(L, A.groups, A.layers, light_from, light_to, A.stats->stats, A.stats->plane2, A.stats->plane3, freeze ? &C3 : nullptr,
-                                         G.stream);
-    }
-    else if (A.groups && A.layers) launch_reduce_group_layers(L, A.groups, A.layers, light_from, light_to, G.stream);
-    else if (A.stats && A.groups) launch_reduce_groups_stats(L, A.groups, A.stats->stats, A.stats->plane2, freeze ? &C : nullptr, G.stream);
-    else if (A.stats && A.layers)
-        launch_reduce_layers_stats(L, A.layers, A.PL.n_general, A.integrated_end(), A.stats->stats, A.stats->plane2, freeze ? &C : nullptr, G.stream);
-    else if (A.stats)
-    {
-        // (an adaptive round that the staging cap splits into several launches: the criterion is the ROUND's, evaluated in its
-        // last launch -- a record frozen on a part of the round would stay frozen)
-        StatsDev R = *A.stats;
-        R.adaptive = A.stats->adaptive && last ? 1u : 0u;
-        launch_reduce_stats(L, R, G.stream);
-    }
-    else if (A.groups) launch_reduce_groups(L, A.groups, G.stream);
-    else if (A.layers) launch_reduce_layers(L, A.layers, A.PL.n_general, A.integrated_end(), G.stream);   // (the light kernel's slots: its samples carry no mark)
-    else launch_reduce(L, G.stream);
+    // (an adaptive round that the staging cap splits into several launches: the criterion is the ROUND's, evaluated in its last launch;
+    // the unmarked range of a layers mode is the light KERNEL's slots of the list in use, the caller's included)
+    launch_reduce_planes(L, A.PS, A.PL.n_general, A.integrated_end(), last, G.stream);
     HIPCHK(hipGetLastError());
     if (A.piped)
     {
@@ -613,8 +580,7 @@ static int reduce_launch(const LaunchPlan& A, LaunchDev& L, bool last)
 
 // One render call: check, prepare the tables, plan, then launch by launch -- reserve the staging, wire the pipeline, launch the
 // classes (timed), reduce
-int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only, const Target* tgt, const PixelLists* lists, const StatsDev* stats,
-              vp_float4* d_trans, vp_float4* d_sky)
+int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only, const Target* tgt, const PixelLists* lists, const PlaneSet* planes)
 {
     int rc = ensure_device();
     if (rc) return rc;
@@ -638,21 +604,12 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
     // default of rounds 1-4, stays 0.8 % ahead of 28 on the reference's live configuration (profiles/r05_raw/sweep_samplerh.txt)
     if (!G.wait_lanes_set && G.rng == VP_RNG_SAMPLERH && G.trk == VP_TRACK_SPECTRAL) L.wait_lanes = 24;
     if (sh.per_frame == 0) return VP_OK;
-    if ((lists || stats || d_trans || d_sky) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics, layers or groups");
-    // (statistics on planes -- vp_render_frames_groups_stats / _layers_stats -- bring one record buffer per plane; a criterion and the
-    // caller's lists come with the adaptive rounds on planes only: vp_render_adaptive_groups / _layers)
-    if ((d_trans || d_sky) && lists && !(stats && stats->plane2 && stats->adaptive))
-        return fail(VP_E_ARG, "a layers or groups call renders the cached lists, or the active lists of an adaptive round with both planes' records");
-    if (stats && !stats->plane2 != !(d_trans || d_sky))
-        return fail(VP_E_ARG, "statistics on planes: one record buffer per plane of a layers or groups call");
-    // (both: a group-layers call, vp_render_frames_group_layers -- three planes from the two staging planes; the caller's lists come with
-    // the adaptive rounds on three planes only: vp_render_adaptive_group_layers)
-    if (d_trans && d_sky && ((stats && !stats->plane3) || (lists && !(stats && stats->adaptive))))
-        return fail(VP_E_ARG, "a group-layers call renders the cached lists, with no records or all three planes', or the active lists of an adaptive round with all three");
-    if (stats && stats->plane3 && !(d_trans && d_sky)) return fail(VP_E_ARG, "statistics on three planes: a group-layers call");
+    if ((lists || planes) && (tgt || stage_only)) return fail(VP_E_ARG, "look-ahead batches render the cached lists without statistics, layers or groups");
     LaunchPlan A = {};
-    A.lookahead = tgt != nullptr; A.stage_only = stage_only; A.stats = stats; A.layers = (float4*)d_trans; A.groups = (float4*)d_sky;
-    L.layers = d_trans ? 1u : 0u;
+    A.lookahead = tgt != nullptr; A.stage_only = stage_only;
+    if (planes) A.PS = *planes;
+    A.PS.acc[0] = L.out;
+    L.layers = A.PS.layers() ? 1u : 0u;
     if ((rc = prepare_tables(p, sh, nframes, lists, L, A)) || A.per_frame == 0) return rc;
     if (0xfffffff0u / A.per_frame < 1) return fail(VP_E_ARG, "image too large for the 32-bit sample queue");
     L.stage_stride = (unsigned)A.per_frame;
@@ -671,7 +628,7 @@ int do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool sta
         L.frame0 = first + done;
         L.nframes = f;
         L.stage = A.staged ? A.T.rt->stage.p : nullptr;
-        L.groups = A.groups ? L.stage + A.per_frame * (size_t)f : nullptr;   // (the second plane: behind the f frames of the first)
+        L.groups = A.PS.groups() ? L.stage + A.per_frame * (size_t)f : nullptr;   // (the second plane: behind the f frames of the first)
         // per-pixel constants of the launch (the box-missing pixels; the light class where it is written by miss_fill_k) are staged once,
         // in the launch's first row: the slots behind the general (and an integrated light) class
         L.const_from = 0xffffffffu; L.stage_const = nullptr;
@@ -704,18 +661,15 @@ static int await_launches(bool lookahead, bool aux)
     return VP_OK;
 }
 
-// Compositing layers (include/volpath.h): the call's samples are vp_render_frames' -- same plan, lists, tables, walks and kernels, with
-// LaunchDev::layers set --, staged on the caller's stream whatever the frame count, and reduce_layers_k splits them into the two
-// accumulators.  What the switch is not built for is refused before anything is launched (and before the device is asked for).
-// Light groups (include/volpath.h): the same call with the environment's term of every sample kept apart -- render_k's GRP instances
-// and the groups forms of the constant writers stage it in a second plane (LaunchDev::groups), reduce_groups_k adds the two planes into
-// the two accumulators.  Refusals likewise.
-// Either with statistics (the _stats calls): the same launches, and the reduce also folds each plane's samples into that plane's records
-// (reduce_layers_stats_k, reduce_groups_stats_k); r0 / r1 are then the two record buffers, else null.
-// Group layers (include/volpath.h vp_render_frames_group_layers): both switches at once -- render_k's instances with LYR and GRP, the
-// constant writers of a layers call, two staging planes, and reduce_group_layers_k adds them into the three accumulators (d0 sun, d1 sky,
-// d2 trans; r0 .. r2 their records).
-struct PlaneCall { const char* fn; bool groups, with_stats, both = false; };
+// Calls with planes (include/volpath.h; vp_kernels.h PLANES_*): the call's samples are vp_render_frames' -- same plan, lists, tables,
+// walks and kernels, render_k in the instance of the mode --, staged on the caller's stream whatever the frame count, and the reduce
+// splits each staged sample into the planes' samples (launch_reduce_planes).
+// Layers: LaunchDev::layers set; the reduce splits the samples into the foreground and the transmittance accumulator.
+// Light groups: the environment's term of every sample is kept apart -- render_k's GRP instances and the groups forms of the constant
+// writers stage it in a second plane (LaunchDev::groups).
+// Group layers: both switches at once -- the constant writers of a layers call, two staging planes, three accumulators.
+// Any of them with statistics (the _stats calls): the same launches, and the reduce also folds each plane's samples into that plane's records.
+// What a mode is not built for is refused before anything is launched (and before the device is asked for).
 static const char kLayersMis[] = "scattered paths never see the sky", kGroupsMis[] = "the environment is sampled as a light, another estimator";
 // the state a plane call is built for, checked before the device is asked for; fn: the entry point the message names
 int plane_state_check(const char* fn, bool groups)
@@ -726,20 +680,35 @@ int plane_state_check(const char* fn, bool groups)
     if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "%s is built for the exact arithmetic only (its kernel instances are the exact unit's)", fn);
     return VP_OK;
 }
-static int plane_call(const PlaneCall& c, vp_float4* d0, vp_float4* d1, vp_pixel_stats* r0, vp_pixel_stats* r1, int first_frame, int n_frames, const Param* p,
-                      vp_float4* d2 = nullptr, vp_pixel_stats* r2 = nullptr)
+// the planes a caller hands in: planes_of(mode) accumulators, all given and all different; with_stats: as many record buffers likewise.
+// 0: so they are; 1: a null pointer among them; 2: one buffer given twice
+int plane_buffers_check(const PlaneSet& S, bool with_stats)
 {
-    if (!d0 || !d1 || d0 == d1 || !p || n_frames <= 0 || first_frame < 0 || (c.with_stats && (!r0 || !r1 || r0 == r1))) return fail(VP_E_ARG, "%s: bad arguments", c.fn);
-    if (c.both && (!d2 || d2 == d0 || d2 == d1 || (c.with_stats && (!r2 || r2 == r0 || r2 == r1)))) return fail(VP_E_ARG, "%s: bad arguments", c.fn);
-    int rc = plane_state_check(c.fn, c.groups);
+    for (int k = 0; k < S.n(); k++)
+        if (!S.acc[k] || (with_stats && !S.rec[k])) return 1;
+    for (int k = 1; k < S.n(); k++)
+        for (int j = 0; j < k; j++)
+            if (S.acc[j] == S.acc[k] || (with_stats && S.rec[j] == S.rec[k])) return 2;
+    return 0;
+}
+PlaneSet plane_set(int mode, vp_float4* d0, vp_float4* d1, vp_float4* d2, vp_pixel_stats* r0, vp_pixel_stats* r1, vp_pixel_stats* r2)
+{
+    PlaneSet S = {};
+    S.mode = mode;
+    S.acc[0] = (float4*)d0; S.acc[1] = (float4*)d1; S.acc[2] = (float4*)d2;
+    S.rec[0] = (PixelStatsDev*)r0; S.rec[1] = (PixelStatsDev*)r1; S.rec[2] = (PixelStatsDev*)r2;
+    return S;
+}
+// the vp_render_frames_* calls with planes: S as the caller handed it in, records (with_stats) or none
+static int plane_call(const char* fn, const PlaneSet& S, bool with_stats, int first_frame, int n_frames, const Param* p)
+{
+    if (plane_buffers_check(S, with_stats) || !p || n_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "%s: bad arguments", fn);
+    int rc = plane_state_check(fn, S.groups());
     if (rc) return rc;
     if ((rc = ensure_device())) return rc;
     // the call is serial and runs on the caller's stream: look-ahead batches stop, pipelined launches are waited for
     if ((rc = la_quiesce())) return rc;
-    StatsDev T = {};
-    T.stats = (PixelStatsDev*)r0; T.plane2 = (PixelStatsDev*)r1; T.plane3 = (PixelStatsDev*)r2;
-    if (c.both) return do_render(d0, first_frame, n_frames, p, false, nullptr, nullptr, c.with_stats ? &T : nullptr, d2, d1);
-    return do_render(d0, first_frame, n_frames, p, false, nullptr, nullptr, c.with_stats ? &T : nullptr, c.groups ? nullptr : d1, c.groups ? d1 : nullptr);
+    return do_render((vp_float4*)S.acc[0], first_frame, n_frames, p, false, nullptr, nullptr, &S);
 }
 
 }  // namespace vph
@@ -753,31 +722,31 @@ int vp_render_frames(vp_float4* d_output, int first_frame, int n_frames, const P
 }
 int vp_render_frames_layers(vp_float4* d_fg, vp_float4* d_trans, int first_frame, int n_frames, const Param* p)
 {
-    return plane_call({"vp_render_frames_layers", false, false}, d_fg, d_trans, nullptr, nullptr, first_frame, n_frames, p);
+    return plane_call("vp_render_frames_layers", plane_set(PLANES_LAYERS, d_fg, d_trans), false, first_frame, n_frames, p);
 }
 int vp_render_frames_groups(vp_float4* d_sun, vp_float4* d_sky, int first_frame, int n_frames, const Param* p)
 {
-    return plane_call({"vp_render_frames_groups", true, false}, d_sun, d_sky, nullptr, nullptr, first_frame, n_frames, p);
+    return plane_call("vp_render_frames_groups", plane_set(PLANES_GROUPS, d_sun, d_sky), false, first_frame, n_frames, p);
 }
 int vp_render_frames_layers_stats(vp_float4* d_fg, vp_float4* d_trans, vp_pixel_stats* d_fg_stats, vp_pixel_stats* d_trans_stats, int first_frame, int n_frames,
                                   const Param* p)
 {
-    return plane_call({"vp_render_frames_layers_stats", false, true}, d_fg, d_trans, d_fg_stats, d_trans_stats, first_frame, n_frames, p);
+    return plane_call("vp_render_frames_layers_stats", plane_set(PLANES_LAYERS, d_fg, d_trans, nullptr, d_fg_stats, d_trans_stats), true, first_frame, n_frames, p);
 }
 int vp_render_frames_groups_stats(vp_float4* d_sun, vp_float4* d_sky, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, int first_frame, int n_frames,
                                   const Param* p)
 {
-    return plane_call({"vp_render_frames_groups_stats", true, true}, d_sun, d_sky, d_sun_stats, d_sky_stats, first_frame, n_frames, p);
+    return plane_call("vp_render_frames_groups_stats", plane_set(PLANES_GROUPS, d_sun, d_sky, nullptr, d_sun_stats, d_sky_stats), true, first_frame, n_frames, p);
 }
 int vp_render_frames_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans, int first_frame, int n_frames, const Param* p)
 {
-    return plane_call({"vp_render_frames_group_layers", true, false, true}, d_sun, d_sky, nullptr, nullptr, first_frame, n_frames, p, d_trans);
+    return plane_call("vp_render_frames_group_layers", plane_set(PLANES_GROUP_LAYERS, d_sun, d_sky, d_trans), false, first_frame, n_frames, p);
 }
 int vp_render_frames_group_layers_stats(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans, vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats,
                                         vp_pixel_stats* d_trans_stats, int first_frame, int n_frames, const Param* p)
 {
-    return plane_call({"vp_render_frames_group_layers_stats", true, true, true}, d_sun, d_sky, d_sun_stats, d_sky_stats, first_frame, n_frames, p, d_trans,
-                      d_trans_stats);
+    return plane_call("vp_render_frames_group_layers_stats", plane_set(PLANES_GROUP_LAYERS, d_sun, d_sky, d_trans, d_sun_stats, d_sky_stats, d_trans_stats), true,
+                      first_frame, n_frames, p);
 }
 int vp_relight_composite(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const vp_float4* trans, const float sun_gain[3], const float sky_gain[3],
                          const vp_float4* plate, const float plate_rgb[3], int size, float scale)

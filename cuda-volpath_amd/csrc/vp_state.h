@@ -356,19 +356,18 @@ struct Target { RenderTarget* rt; hipStream_t stream; };
 // the pixel lists a launch runs on, class by class: n_general general pixels, n_light light ones, n_miss box-missing ones (y << 16 | x)
 struct PixelLists { const unsigned* pixels; unsigned n_general, n_light, n_miss; };
 // lists: null = the context's cached lists of p (built on demand: the plain entry points), else the caller's own -- a class-ordered
-// subset of them (vp_adaptive.cpp).  stats: the reduce also takes the statistics of include/volpath.h (launch_reduce_stats); such a
-// call is staged even for one frame and runs on the caller's stream, not on a pipeline slot.  d_trans: a layers call
-// (vp_render_frames_layers) -- d_out is the foreground accumulator, d_trans the transmittance accumulator; staged and on the caller's
-// stream likewise, with the cached lists.  d_sky: a light-groups call (vp_render_frames_groups) -- d_out is the
-// sun accumulator, d_sky the sky accumulator; staged in two planes, otherwise as a layers call.  Both: a group-layers call
-// (vp_render_frames_group_layers) -- d_out sun, d_sky sky, d_trans the transmittance; the two staging planes of a groups call, the cached
-// lists, no records or all three planes' (StatsDev::plane3); an adaptive round on three planes (vp_render_adaptive_group_layers) brings
-// the three record buffers, the per-plane criterion ([0] sun, [1] sky, [2] trans) and the active lists together.  A layers or groups call
-// with statistics (the _stats calls) brings both planes' records in `stats` (StatsDev::plane2), without a criterion or lists; an adaptive
-// round on planes (vp_render_adaptive_groups / _layers) brings the records, the per-plane criterion (StatsDev::plane_tol, plane_fl) and the
-// active lists together.
+// subset of them (vp_adaptive.cpp: the active lists of an adaptive round).  planes: null = vp_render_frames' own call, one plane (d_out)
+// without records; else what the call accumulates into (vp_kernels.h PlaneSet; acc[0] is d_out) -- further planes, a record buffer per
+// plane, the criterion of an adaptive round.  Such a call is staged even for one frame and runs on the caller's stream, not on a
+// pipeline slot; a groups mode stages two planes.
 int  do_render(vp_float4* d_out, int first, int nframes, const Param* p, bool stage_only = false, const Target* tgt = nullptr,
-               const PixelLists* lists = nullptr, const StatsDev* stats = nullptr, vp_float4* d_trans = nullptr, vp_float4* d_sky = nullptr);
+               const PixelLists* lists = nullptr, const PlaneSet* planes = nullptr);
+// the PlaneSet of an entry point's arguments, as the caller handed them in (unused planes null), and what every entry point asks of
+// it before anything else: planes_of(mode) accumulators, all given and all different -- with_stats: as many record buffers likewise
+// (0: so they are; 1: a null pointer among them; 2: one buffer given twice)
+PlaneSet plane_set(int mode, vp_float4* d0, vp_float4* d1 = nullptr, vp_float4* d2 = nullptr, vp_pixel_stats* r0 = nullptr, vp_pixel_stats* r1 = nullptr,
+                   vp_pixel_stats* r2 = nullptr);
+int  plane_buffers_check(const PlaneSet& S, bool with_stats);
 // the preconditions of a render call, each caller with the subset it needs (p: the image checks; last_frame: the opacity rule)
 enum : unsigned { CHK_STATE = 1, CHK_IMAGE = 2, CHK_IMAGE_NOTE = 4, CHK_MODES = 8, CHK_OPACITY = 16 };
 int  check_render(unsigned what, const Param* p, long long last_frame = 0);

@@ -2,7 +2,7 @@
 
 tests/golden/render_variants.txt tabulates, through the launcher of csrc/vp_dispatch.h and host stand-ins, which render_k instance and
 which approach kernel every admitted request SELECTS.  The census reports, from the shipped library, which table entries hold a
-kernel: render_built(), layers_built() and approach_built() evaluated at run time in each translation unit.  The two sets must be
+kernel: render_built(), planes_built() and approach_built() evaluated at run time in each translation unit.  The two sets must be
 the same set of names: a kernel compiled but never selectable fails here, and so does one selectable but not compiled.  No GPU:
 the `built` half of the census is host arithmetic."""
 import numpy as np

@@ -101,7 +101,7 @@ def test_light_class_as_a_kernel_and_as_constants(vp, oracle, ctx, est, density,
     """The light pixel class (camera rays through certified-empty cells only) of the Julia set.  A majorant of 61 has a reciprocal
     that does not multiply back to 1: a null collision in empty space moves the throughput, so the light kernel runs -- the
     global-majorant one and the local-majorant ones of the decomposition and bounded estimators.  Its samples carry no mark:
-    reduce_layers_k is told their slots, and a sample it took for a foreground sample would put the throughput into fg.  At 64 the
+    the reduce is told their slots, and a sample it took for a foreground sample would put the throughput into fg.  At 64 the
     collision is neutral and the class is written as constants (1, 1, 1, -0.0f), like the box-missing pixels."""
     E = LL.expected(oracle, "julia", est, 1, density=density)
     P = _scene(vp, oracle, "julia", est, 1, density=density)

@@ -171,7 +171,7 @@ def test_group_records_equal_the_stats_renders_of_the_twins(vp, oracle, ctx, nam
 @pytest.mark.parametrize("est,density,const", ((0, 61.0, False), (0, 64.0, True), (1, 61.0, False), (2, 61.0, False)))
 def test_light_class_as_a_kernel_and_as_constants(vp, oracle, ctx, kind, est, density, const):
     """The light pixel class of the Julia set (tests/test_layers_gpu.py has the reasons for the two densities): at a majorant of 61 the
-    light kernel runs -- in a layers launch its samples carry no mark, and reduce_layers_stats_k is told their slots --, at 64 the class
+    light kernel runs -- in a layers launch its samples carry no mark, and the reduce is told their slots --, at 64 the class
     is written as constants, staged once and folded into the records frame by frame all the same."""
     want = PS.expected(oracle, kind, "julia", est, 1, density=density)
     P = _scene(vp, oracle, "julia", est, 1, density=density)
