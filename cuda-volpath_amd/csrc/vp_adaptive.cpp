@@ -163,6 +163,29 @@ int vp_stats_rel_error(float* dst, const vp_pixel_stats* d_stats, int size, floa
     HIPCHK(hipGetLastError());
     return VP_OK;
 }
+int vp_merge_halves(vp_float4* dst, float* d_resid, const vp_float4* a, const vp_pixel_stats* a_stats, const vp_float4* b, const vp_pixel_stats* b_stats,
+                    int size, float floor_y)
+{
+    if (!dst || !a || !b || !a_stats || !b_stats) return fail(VP_E_ARG, "vp_merge_halves: null pointer");
+    if (size < 0) return fail(VP_E_ARG, "vp_merge_halves: size %d", size);
+    if (d_resid && (!std::isfinite(floor_y) || !(floor_y > 0.0f))) return fail(VP_E_ARG, "vp_merge_halves: floor_y must be a finite number > 0");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (size)
+        launch_merge_halves((float4*)dst, d_resid, (const float4*)a, (const PixelStatsDev*)a_stats, (const float4*)b, (const PixelStatsDev*)b_stats, size, floor_y,
+                            G.stream);
+    HIPCHK(hipGetLastError());
+    return VP_OK;
+}
+int vp_accumulate_stats(vp_pixel_stats* dst, const vp_pixel_stats* src, size_t n)
+{
+    if (!dst || !src) return fail(VP_E_ARG, "vp_accumulate_stats: null pointer");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (n) launch_accumulate_stats((PixelStatsDev*)dst, (const PixelStatsDev*)src, n, G.stream);
+    HIPCHK(hipGetLastError());
+    return VP_OK;
+}
 int vp_denoise(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
                int width, int height, const vp_denoise_params* dp)
 {

@@ -182,9 +182,17 @@ struct LaunchDev
 //   PLANES_LAYERS        fg, trans           an unscattered path's throughput goes to trans, its heat to fg; any other sample to fg
 //   PLANES_GROUPS        sun, sky            the first staging plane to sun, the second (LaunchDev::groups) to sky
 //   PLANES_GROUP_LAYERS  sun, sky, trans     unscattered: as a layers call, the heat to both groups; else as a groups call
-constexpr int PLANES_ONE = 0, PLANES_LAYERS = 1, PLANES_GROUPS = 2, PLANES_GROUP_LAYERS = 3, kPlaneModes = 4, kMaxPlanes = 3;
+// A fifth mode is no mode of render_k (kPlaneModes stays the number of those): its launches are PLANES_ONE's, instance for instance --
+// the beauty kernels, their walks and constant writers, one staging plane, LaunchDev::layers 0 and LaunchDev::groups null, census kind
+// CENSUS_RENDER --, and only the reduce knows it:
+//   PLANES_HALVES        h0, h1              the beauty sample of frame f, whole, to plane half_of_frame(f) ALONE; the other plane
+//                                            receives no sample of that frame -- no +0.0f, no count (include/volpath.h
+//                                            vp_render_frames_halves_stats).  Records always; no adaptive and no compaction instance.
+constexpr int PLANES_ONE = 0, PLANES_LAYERS = 1, PLANES_GROUPS = 2, PLANES_GROUP_LAYERS = 3, kPlaneModes = 4, PLANES_HALVES = 4, kMaxPlanes = 3;
 constexpr int plane_mode(bool layers, bool groups) { return (layers ? PLANES_LAYERS : 0) | (groups ? PLANES_GROUPS : 0); }
 constexpr int planes_of(int mode) { return mode == PLANES_ONE ? 1 : mode == PLANES_GROUP_LAYERS ? 3 : 2; }
+// the half a frame belongs to: blocks of S^2 = 4^sub_shift consecutive ABSOLUTE frames alternate (S = 1: even frames 0, odd frames 1)
+__host__ __device__ constexpr int half_of_frame(int frame, unsigned sub_shift) { return (int)(((unsigned)frame >> (2u * sub_shift)) & 1u); }
 // The launch census (test hook: include/volpath.h vp_test_launch_census).  The launchers of vp_dispatch.h call census_record() with the
 // table index of the kernel they are about to name: one host increment per launch, nothing on the device.  unit: 0 the exact
 // translation unit, 1 the fast arithmetic's; kind: CENSUS_* -- one table per plane mode of render_k (census_of_planes), and the
@@ -264,8 +272,8 @@ struct PlaneSet
     unsigned       min_frames;          // adaptive: the samples a record needs before its criterion is asked
     bool           adaptive;            // a round of an adaptive call: its last launch freezes; false: `flags` is neither read nor written
     int  n() const { return planes_of(mode); }
-    bool layers() const { return (mode & PLANES_LAYERS) != 0; }
-    bool groups() const { return (mode & PLANES_GROUPS) != 0; }
+    bool layers() const { return mode < kPlaneModes && (mode & PLANES_LAYERS) != 0; }   // (render_k's two bits: PLANES_HALVES has neither)
+    bool groups() const { return mode < kPlaneModes && (mode & PLANES_GROUPS) != 0; }
     bool stats() const { return rec[0] != nullptr; }
 };
 // The reduce of a staged launch into the planes of S (reduce_planes_k<MODE, STATS, ADAPT>): per slot of L.pixels the staged frames in
@@ -282,6 +290,12 @@ inline unsigned compact_blocks(unsigned n) { return (n + 1023u) / 1024u; }
 void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PlaneSet& S, unsigned* d_block_counts, unsigned* d_totals,
                            unsigned* d_out, hipStream_t st);
 void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st);
+// the merge of two half-buffer MEAN images by their records' counts and the residual map of their disagreement (merge_halves_k;
+// include/volpath.h vp_merge_halves): resid may be null, dst may be a or b
+void launch_merge_halves(float4* dst, float* resid, const float4* a, const PixelStatsDev* a_stats, const float4* b, const PixelStatsDev* b_stats, int size,
+                         float floor_y, hipStream_t st);
+// dst += src for records: binary64 sums, n added, flags or-ed (accumulate_stats_k)
+void launch_accumulate_stats(PixelStatsDev* dst, const PixelStatsDev* src, size_t n, hipStream_t st);
 void launch_stats_rel_error(float* dst, const PixelStatsDev* stats, int size, float floor_y, hipStream_t st);
 // the NL-means filter of the output stage (vp_denoise.hip; include/volpath.h vp_denoise): weights from (guide, gstats), colours from
 // (src, stats), k2 = k * k; form 0 tiled through LDS (denoise_lds_bytes(R, F) of it per workgroup), 1 one thread per pixel from global memory

@@ -608,6 +608,57 @@ __global__ __launch_bounds__(256) void reduce_planes_k(LaunchDev L, ReduceDev<pl
             }
     }
 }
+// PLANES_HALVES (vp_render_frames_halves_stats) is the one mode in which a plane does NOT receive every frame: its one form is an explicit
+// specialisation, so that the body above stays, textually, what the other modes' instances are compiled from.
+// One thread per slot like the body above, the staged frames in frame order.  Frame f -- the ABSOLUTE frame
+// L.frame0 + f, so that a launch beginning on any frame continues the one before it -- goes whole to plane half_of_frame(f), with the
+// additions of the one-plane form (a constant of the launch: the same word, one addition per frame of the half, never a product).  The
+// other plane receives nothing for that frame: split_sample's convention, "a plane the sample does not feed is ADDED +0.0f", does not
+// hold here, so a -0.0f in it stays -0.0f.  Every plane does not receive every frame: a record gains the frames of its own half
+// (not L.nframes), and a plane without a frame in the launch is read and neither written nor counted.  `flags` is never touched.
+template <>
+__global__ __launch_bounds__(256) void reduce_planes_k<PLANES_HALVES, true, false>(LaunchDev L, ReduceDev<2, true, false> D)
+{
+    unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.nslots) return;
+    unsigned pix = L.pixels[slot];
+    size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
+    float4   a[2];
+    double   sy[2], sy2[2];
+    unsigned cnt[2] = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+    {
+        a[k] = D.acc[k][idx];
+        sy[k] = D.rec[k][idx].sum_y; sy2[k] = D.rec[k][idx].sum_y2;
+    }
+    const bool    constant = slot >= L.const_from;
+    const size_t  stride   = constant ? 0 : L.stage_stride;
+    const float4* stage    = (constant ? L.stage_const : L.stage) + slot;
+    for (int f = 0; f < L.nframes; f++)
+    {
+        const float4 s    = stage[(size_t)f * stride];
+        const int    half = half_of_frame(L.frame0 + f, L.sub_shift);
+        const double y    = (double)stats_luminance(s);
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+        {
+            if (k != half) continue;
+            a[k]   = make_float4(a[k].x + s.x, a[k].y + s.y, a[k].z + s.z, a[k].w + s.w);
+            sy[k]  = sy[k] + y;
+            sy2[k] = sy2[k] + y * y;
+            cnt[k]++;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+    {
+        if (!cnt[k]) continue;
+        D.acc[k][idx] = a[k];
+        PixelStatsDev* rec = D.rec[k] + idx;
+        rec->sum_y = sy[k]; rec->sum_y2 = sy2[k]; rec->n = rec->n + cnt[k];
+    }
+}
 // A stable compaction of a class-ordered pixel list (src: n[0] general, n[1] light, n[2] box-missing pixels) by the FROZEN bit of the
 // pixels' records: the active pixels of each class in the order they have in src, class by class, and the three counts.  The pattern of
 // pixlist_*_k: per-block class counts, pixlist_scan_k over them, the scatter with wave-ballot ranks.  N: the record buffers of the
@@ -682,6 +733,44 @@ __global__ void scale_by_count_k(float4* dst, const float4* src, const PixelStat
     if (!n) { dst[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); return; }
     const float s = scale / (float)n;
     dst[idx] = make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
+}
+// The merge of two half-buffer MEAN images (include/volpath.h vp_merge_halves): each channel (a * na + b * nb) / nt with the records'
+// counts as binary32, and the residual map: half the luminance disagreement of the halves over max(lum(dst), floor); 0 where either
+// half has no sample.  a[i] and b[i] are read before dst[i] is written: dst may be either.
+__global__ void merge_halves_k(float4* dst, float* resid, const float4* a, const PixelStatsDev* a_stats, const float4* b, const PixelStatsDev* b_stats,
+                               int size, float floor_y)
+{
+    int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= size) return;
+    const unsigned ua = a_stats[idx].n, ub = b_stats[idx].n;
+    const float4   va = a[idx], vb = b[idx];
+    const float    na = (float)ua, nb = (float)ub, nt = na + nb;
+    if (nt == 0.0f)
+    {
+        dst[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (resid) resid[idx] = 0.0f;
+        return;
+    }
+    const float4 m = make_float4((va.x * na + vb.x * nb) / nt, (va.y * na + vb.y * nb) / nt, (va.z * na + vb.z * nb) / nt, (va.w * na + vb.w * nb) / nt);
+    dst[idx] = m;
+    if (!resid) return;
+    const float d   = stats_luminance(va) - stats_luminance(vb);
+    const float e   = 0.5f * __builtin_fabsf(d);
+    const float ym  = stats_luminance(m);
+    const float den = ym > floor_y ? ym : floor_y;
+    resid[idx] = (ua == 0u || ub == 0u) ? 0.0f : e / den;
+}
+// dst += src for records (include/volpath.h vp_accumulate_stats): the halves of a half-buffer render into the records of all frames,
+// the records of sharded contexts on one device into one
+__global__ void accumulate_stats_k(PixelStatsDev* dst, const PixelStatsDev* src, size_t n)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    PixelStatsDev d = dst[i];
+    const PixelStatsDev s = src[i];
+    d.sum_y = d.sum_y + s.sum_y; d.sum_y2 = d.sum_y2 + s.sum_y2;
+    d.n += s.n; d.flags |= s.flags;
+    dst[i] = d;
 }
 // the noise map: the estimated standard error of the mean luminance over max(mean, floor), binary64, rounded once
 __global__ void stats_rel_error_k(float* dst, const PixelStatsDev* stats, int size, double fl)
@@ -1702,6 +1791,8 @@ void launch_reduce_planes(const LaunchDev& L, const PlaneSet& S, unsigned light_
     case PLANES_ONE: launch_reduce_mode<PLANES_ONE>(L, S, light_from, light_to, last, st); break;
     case PLANES_LAYERS: launch_reduce_mode<PLANES_LAYERS>(L, S, light_from, light_to, last, st); break;
     case PLANES_GROUPS: launch_reduce_mode<PLANES_GROUPS>(L, S, light_from, light_to, last, st); break;
+    // (one form: the entry point always hands in records and never runs adaptive rounds)
+    case PLANES_HALVES: launch_reduce_instance<PLANES_HALVES, true, false>(L, S, light_from, light_to, st); break;
     default: launch_reduce_mode<PLANES_GROUP_LAYERS>(L, S, light_from, light_to, last, st); break;
     }
 }
@@ -1731,6 +1822,15 @@ void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned wi
 void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st)
 {
     hipLaunchKernelGGL(scale_by_count_k, dim3((size + 255) / 256), dim3(256), 0, st, dst, src, stats, size, s);
+}
+void launch_merge_halves(float4* dst, float* resid, const float4* a, const PixelStatsDev* a_stats, const float4* b, const PixelStatsDev* b_stats, int size,
+                         float floor_y, hipStream_t st)
+{
+    hipLaunchKernelGGL(merge_halves_k, dim3((size + 255) / 256), dim3(256), 0, st, dst, resid, a, a_stats, b, b_stats, size, floor_y);
+}
+void launch_accumulate_stats(PixelStatsDev* dst, const PixelStatsDev* src, size_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(accumulate_stats_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dst, src, n);
 }
 void launch_stats_rel_error(float* dst, const PixelStatsDev* stats, int size, float floor_y, hipStream_t st)
 {

@@ -225,7 +225,9 @@ struct LaunchPlan
     bool       stage_only;        // ... which is staged whole and not reduced
     PlaneSet   PS;                // what the call accumulates into (vp_kernels.h): its mode, accumulators, records and criterion; PS.acc[0] is d_out
     size_t stage_planes() const { return PS.groups() ? 2u : 1u; }   // staging planes per frame: a groups mode stages the sky's samples in a second
-    bool plain() const { return PS.mode == PLANES_ONE && !PS.stats(); }   // vp_render_frames' own call: one plane, no records
+                                                                    // (NOT the call's planes: PLANES_HALVES has two accumulators and stages one)
+    bool plain() const { return PS.mode == PLANES_ONE && !PS.stats(); }   // vp_render_frames' own call: one plane, no records (a halves call
+                                                                          // is not: staged for one frame too, never pipelined)
     // the slots of the list, general pixels first: where the class a kernel integrates ends (the general class and a light class that
     // is not written as constants), i.e. where the per-pixel constants of a launch begin -- const_from and the layers reduce's range
     unsigned integrated_end() const { return PL.n_general + ((PL.n_light && !light_const) ? PL.n_light : 0u); }
@@ -747,6 +749,23 @@ int vp_render_frames_group_layers_stats(vp_float4* d_sun, vp_float4* d_sky, vp_f
 {
     return plane_call("vp_render_frames_group_layers_stats", plane_set(PLANES_GROUP_LAYERS, d_sun, d_sky, d_trans, d_sun_stats, d_sky_stats, d_trans_stats), true,
                       first_frame, n_frames, p);
+}
+// Half-buffer renders (include/volpath.h; vp_kernels.h PLANES_HALVES): vp_render_frames_stats' launches -- the mode sets neither
+// LaunchDev::layers nor LaunchDev::groups, so every kernel is the beauty instance and nothing a plane call refuses is refused -- into one
+// staging plane, and a reduce that hands frame f to half_of_frame(f).  Serial on the caller's stream like a plane call.
+int vp_render_frames_halves_stats(vp_float4* d_h0, vp_float4* d_h1, vp_pixel_stats* d_h0_stats, vp_pixel_stats* d_h1_stats, int first_frame, int n_frames,
+                                  const Param* p)
+{
+    const PlaneSet S = plane_set(PLANES_HALVES, d_h0, d_h1, nullptr, d_h0_stats, d_h1_stats);
+    const int bad = plane_buffers_check(S, true);
+    if (bad == 1 || !p) return fail(VP_E_ARG, "vp_render_frames_halves_stats: null pointer");
+    if (bad) return fail(VP_E_ARG, "vp_render_frames_halves_stats: the two accumulators, and the two record buffers, are different buffers");
+    if (n_frames <= 0 || first_frame < 0)
+        return fail(VP_E_ARG, "vp_render_frames_halves_stats: frames [%d, %d + %d) out of range", first_frame, first_frame, n_frames);
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = la_quiesce())) return rc;
+    return do_render(d_h0, first_frame, n_frames, p, false, nullptr, nullptr, &S);
 }
 int vp_relight_composite(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const vp_float4* trans, const float sun_gain[3], const float sky_gain[3],
                          const vp_float4* plate, const float plate_rgb[3], int size, float scale)

@@ -49,6 +49,14 @@ static void usage()
            "                                                the green opacity alpha.y with sigma SA (default 0.2), the depth at which the\n"
            "                                                optical depth reaches TAU with sigma SZ (default 0.2, in scene units) and the\n"
            "                                                cover flag with SA.  One GPU; not with --aa above 1\n"
+           "               [--denoise-cross [--resid-out FILE.hdr]]\n"
+           "                                                implies --denoise; the frames go through vp_render_frames_halves_stats into\n"
+           "                                                two half-buffers (even and odd frames; with --aa S blocks of S^2 frames), each\n"
+           "                                                half is filtered with the weights of the OTHER (two vp_denoise_guided calls,\n"
+           "                                                roles swapped) and --out is their vp_merge_halves.  --denoise-radius, -patch, -k\n"
+           "                                                and --denoise-features apply.  --resid-out writes the residual-error map: half\n"
+           "                                                the disagreement of the two filtered halves over max(mean, 1e-3), as HDR.\n"
+           "                                                One GPU; not with --noise or any plane output or plane filter\n"
            "               [--layers-out PREFIX] [--over R G B]\n"
            "                                                compositing layers (vp_render_frames_layers): the frames are rendered as a\n"
            "                                                foreground F and a per-channel transmittance T, pixel = F + T o B for any\n"
@@ -137,6 +145,8 @@ int main(int argc, char** argv)
     bool        denoise = false;
     vp_denoise_params dn = {5, 1, 0.45f};   // (from a 64 x 48 table, not tuned: DESIGN.md section 2.4)
     bool        denoise_features = false;
+    bool        denoise_cross = false;   // --denoise-cross: two half-buffers, each filtered with the other's weights, merged
+    std::string resid_out;
     float       dn_sigma_alpha = 0.2f, dn_sigma_depth = 0.2f;   // (the best cell of a 3 x 3 grid on that scene: DESIGN.md section 2.13)
     std::string layers_out;
     bool        over = false;
@@ -243,6 +253,8 @@ int main(int argc, char** argv)
         else if (a == "--round") { need(1); round_frames = atoi(argv[++i]); }
         else if (a == "--noise-out") { need(1); noise_out = argv[++i]; }
         else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-cross") denoise_cross = denoise = true;
+        else if (a == "--resid-out") { need(1); resid_out = argv[++i]; }
         else if (a == "--denoise-radius" || a == "--denoise-patch" || a == "--denoise-k")
         {
             need(1);
@@ -343,6 +355,19 @@ int main(int argc, char** argv)
     {
         fprintf(stderr, "--noise with --gpus %d: reducing per-pixel statistics across ranks is not part of adaptive sampling; use one GPU\n", gpus);
         return 2;
+    }
+    if (!denoise_cross && !resid_out.empty()) { fprintf(stderr, "--resid-out needs --denoise-cross: the map is the disagreement of the two filtered halves\n"); return 2; }
+    if (denoise_cross)
+    {
+        const char* other = gpus > 1 ? "--gpus" : adaptive ? "--noise" : !planes_out.empty() ? "--planes-out" : !groups_out.empty() ? "--groups-out" : relit ? "--sun-gain / --sky-gain"
+                          : !layers_out.empty() ? "--layers-out" : over ? "--over" : plane_adaptive ? "--plane-noise" : planes_adaptive ? "--planes-noise"
+                          : groups_denoise ? "--groups-denoise" : layers_denoise ? "--layers-denoise" : planes_denoise ? "--planes-denoise" : nullptr;
+        if (other)
+        {
+            fprintf(stderr, "--denoise-cross with %s: the half-buffers' records are not reduced across ranks, adaptive rounds on halves are not built and the halves are "
+                    "the beauty image's, not a plane's; use one GPU without --noise and without plane outputs or plane filters\n", other);
+            return 2;
+        }
     }
     if (denoise && gpus > 1)
     {
@@ -547,6 +572,23 @@ int main(int argc, char** argv)
         stats = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
         if (!stats || vp_memset(stats, 0, (size_t)npix * sizeof(vp_pixel_stats))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
     }
+    // --denoise-cross: accum[0] and `stats` are half 0's, these half 1's; the two filtered means
+    vp_float4*      half1 = nullptr;
+    vp_pixel_stats* half1_stats = nullptr;
+    vp_float4*      half_mean[2] = {nullptr, nullptr};
+    float*          d_resid = nullptr;   // --resid-out: the residual map, written with the merge
+    if (denoise_cross)
+    {
+        half1       = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+        half1_stats = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
+        for (vp_float4*& m2 : half_mean) m2 = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+        if (!half1 || !half1_stats || !half_mean[0] || !half_mean[1] || vp_memset(half1, 0, (size_t)npix * sizeof(vp_float4)) ||
+            vp_memset(half1_stats, 0, (size_t)npix * sizeof(vp_pixel_stats)))
+        {
+            fprintf(stderr, "%s\n", vp_last_error());
+            return 1;
+        }
+    }
     vp_float4* trans = nullptr;   // --layers-out / --over: accum[0] is the foreground accumulator, this the transmittance accumulator
     // (--groups-out / --sun-gain / --sky-gain: accum[0] is the sun accumulator, this the sky accumulator)
     // (--planes-out: accum[0] sun, this sky, trans3 the transmittance; stats3 and mean3 its records and its filtered mean)
@@ -631,7 +673,11 @@ int main(int argc, char** argv)
         else if (denoise)
         {
             const int n = batch > 0 ? std::min(batch, spp - s) : 1;
-            if (vp_render_frames_stats(accum[0], stats, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+            if (denoise_cross ? vp_render_frames_halves_stats(accum[0], half1, stats, half1_stats, s, n, &P) : vp_render_frames_stats(accum[0], stats, s, n, &P))
+            {
+                fprintf(stderr, "%s\n", vp_last_error());
+                return 1;
+            }
             s += n;
         }
         else if (batch > 0)
@@ -780,13 +826,21 @@ int main(int argc, char** argv)
     else if (denoise)
     {
         // the filtered mean image: the division by each pixel's count is part of the call
+        // (--denoise-cross: each half with the other as guide, then the merge -- and the residual map, kept in d_resid for --resid-out)
+        auto filter = [&](const vp_denoise_feature* f, int nf) -> int {
+            if (!denoise_cross) return nf ? vp_denoise_guided(disp, accum[0], stats, nullptr, nullptr, f, nf, W, H, &dn) : vp_denoise(disp, accum[0], stats, nullptr, nullptr, W, H, &dn);
+            if (!resid_out.empty() && !(d_resid = (float*)vp_malloc((size_t)npix * sizeof(float)))) return 1;
+            return vp_denoise_guided(half_mean[0], accum[0], stats, half1, half1_stats, f, nf, W, H, &dn) ||
+                   vp_denoise_guided(half_mean[1], half1, half1_stats, accum[0], stats, f, nf, W, H, &dn) ||
+                   vp_merge_halves(disp, d_resid, half_mean[0], stats, half_mean[1], half1_stats, npix, noise_floor);
+        };
         if (denoise_features)
         {
             // the feature pass first, then the filter with three of its channels: alpha.y, zt and the cover flag
             vp_float4* d_alpha = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
             vp_float4* d_depth = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
             const vp_denoise_feature f3[3] = {{d_alpha, 1, dn_sigma_alpha}, {d_depth, 1, dn_sigma_depth}, {d_depth, 3, dn_sigma_alpha}};
-            if (!d_alpha || !d_depth || vp_render_features(d_alpha, d_depth, &P, &feat) || vp_denoise_guided(disp, accum[0], stats, nullptr, nullptr, f3, 3, W, H, &dn)
+            if (!d_alpha || !d_depth || vp_render_features(d_alpha, d_depth, &P, &feat) || filter(f3, 3)
                 || vp_synchronize())
             {
                 fprintf(stderr, "%s\n", vp_last_error());
@@ -795,9 +849,10 @@ int main(int argc, char** argv)
             vp_free(d_alpha);
             vp_free(d_depth);
         }
-        else if (vp_denoise(disp, accum[0], stats, nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        else if (filter(nullptr, 0)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
         if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
         printf("denoised: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
+        if (denoise_cross) printf("  cross-filtered: two half-buffers, each with the other's weights, merged by their counts\n");
         if (denoise_features) printf("  weights cut by features: sigma alpha %g, sigma depth %g\n", dn_sigma_alpha, dn_sigma_depth);
     }
     else if (adaptive)
@@ -814,6 +869,17 @@ int main(int argc, char** argv)
         if (hdr) image.dump_hdr(out.c_str());
         else image.dump_ppm(out.c_str());
         printf("wrote %s\n", out.c_str());
+    }
+    if (d_resid)
+    {
+        // the residual map of the cross-filter, grey, as HDR
+        std::vector<float> resid((size_t)npix);
+        if (vp_download(resid.data(), d_resid, (size_t)npix * sizeof(float))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        Image rm(W, H);
+        for (int k = 0; k < npix; k++) { float* px = rm.buffer() + 4 * (size_t)k; px[0] = px[1] = px[2] = resid[(size_t)k]; px[3] = 1.0f; }
+        rm.dump_hdr(resid_out.c_str());
+        printf("wrote %s\n", resid_out.c_str());
+        vp_free(d_resid);
     }
     if (adaptive && !noise_out.empty())
     {
@@ -899,6 +965,9 @@ int main(int argc, char** argv)
     if (trans3) vp_free(trans3);
     for (vp_float4* m2 : mean) if (m2) vp_free(m2);
     if (trans) vp_free(trans);
+    if (half1) vp_free(half1);
+    if (half1_stats) vp_free(half1_stats);
+    for (vp_float4* m2 : half_mean) if (m2) vp_free(m2);
     vp_free(disp);
     for (int r = 0; r < gpus; r++)
     {

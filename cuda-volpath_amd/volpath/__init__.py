@@ -41,6 +41,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_adaptive_group_layers",
                  "vp_render_features",
                  "vp_denoise_guided",
+                 "vp_render_frames_halves_stats", "vp_merge_halves", "vp_accumulate_stats",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -172,6 +173,9 @@ def lib():
         L.vp_denoise.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(DenoiseParams)]
         L.vp_set_denoise_form.argtypes = [C.c_int]
         L.vp_denoise_guided.argtypes = [C.c_void_p] * 5 + [C.POINTER(DenoiseFeature), C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseParams)]
+        L.vp_render_frames_halves_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_merge_halves.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_float]
+        L.vp_accumulate_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.vp_render_frames_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_int, C.c_float]
         L.vp_render_frames_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
@@ -608,6 +612,38 @@ def denoise_guided(dst_ptr, src_ptr, stats_ptr, width, height, features=(), radi
     feats = [(getattr(p, "value", p), c, s) for p, c, s in features]
     arr = (DenoiseFeature * len(feats))(*[DenoiseFeature(p, c, s) for p, c, s in feats]) if feats else None
     _chk(lib().vp_denoise_guided(dst_ptr, src_ptr, stats_ptr, guide_ptr, guide_stats_ptr, arr, len(feats), width, height, C.byref(dp)))
+
+
+def half_of_frame(frame, subpixel=1):
+    """the half frame `frame` belongs to under sub-pixel factor `subpixel` (vp_render_frames_halves_stats): (f >> 2 log2 S) & 1"""
+    return (int(frame) >> (2 * (int(subpixel).bit_length() - 1))) & 1
+
+
+def render_frames_halves_stats(h0_ptr, h1_ptr, h0_stats_ptr, h1_stats_ptr, first, n, P):
+    """render_frames_stats with the frames split between two (accumulator, records) pairs by half_of_frame: each half ends with the
+    bits of its own frames' one-frame calls (vp_render_frames_halves_stats)"""
+    _chk(lib().vp_render_frames_halves_stats(h0_ptr, h1_ptr, h0_stats_ptr, h1_stats_ptr, first, n, C.byref(P)))
+
+
+def merge_halves(dst_ptr, resid_ptr, a_ptr, a_stats_ptr, b_ptr, b_stats_ptr, n, floor_y=1e-3):
+    """dst = the count-weighted mean of the MEAN images a and b; resid (may be None) = half their luminance disagreement over
+    max(lum(dst), floor_y) (vp_merge_halves); dst may be a or b"""
+    _chk(lib().vp_merge_halves(dst_ptr, resid_ptr, a_ptr, a_stats_ptr, b_ptr, b_stats_ptr, n, floor_y))
+
+
+def accumulate_stats(dst_ptr, src_ptr, n_records):
+    """dst += src for records: sums added in binary64, n added, flags or-ed (vp_accumulate_stats)"""
+    _chk(lib().vp_accumulate_stats(dst_ptr, src_ptr, n_records))
+
+
+def denoise_cross(dst_ptr, resid_ptr, h0, h0_stats, h1, h1_stats, tmp_a_ptr, tmp_b_ptr, width, height, radius, patch, k, features=None, floor_y=1e-3):
+    """the cross-filter of two half-buffers (accumulators h0, h1 and their records): each half filtered with the weights of the other into
+    the caller's temporaries, then merged into dst and, where resid_ptr is given, the residual map -- three calls queued on the
+    context's stream, nothing allocated"""
+    feats = tuple(features) if features else ()
+    denoise_guided(tmp_a_ptr, h0, h0_stats, width, height, feats, radius, patch, k, guide_ptr=h1, guide_stats_ptr=h1_stats)
+    denoise_guided(tmp_b_ptr, h1, h1_stats, width, height, feats, radius, patch, k, guide_ptr=h0, guide_stats_ptr=h0_stats)
+    merge_halves(dst_ptr, resid_ptr, tmp_a_ptr, h0_stats, tmp_b_ptr, h1_stats, width * height, floor_y)
 
 
 def render_features(P, step, tau_z=FEATURE_TAU_Z_DEFAULT, alpha_ptr=None, depth_ptr=None):

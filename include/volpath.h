@@ -284,7 +284,8 @@ int vp_render_frames(vp_float4* d_output, int first_frame, int n_frames, const P
  *   min_frames < 2, round_frames < 1, rel_tol or floor_y negative or NaN.  VP_E_STATE: work counters enabled (the context stays
  *   usable).  VP_E_NOOPACITY as vp_render_frames would give for frame first_frame + max_frames - 1.
  *   Built for: every estimator, stream, tracking and environment mode, both arithmetic modes, uchar and float volumes, shards
- *   (each context its own pixels; reducing statistics across processes is the caller's business) and every sub-pixel factor.
+ *   (each context its own pixels; reducing statistics across processes is the caller's business; the records of sharded contexts on ONE
+ *   device add up with vp_accumulate_stats, below) and every sub-pixel factor.
  *   Rounds are serial -- round k + 1 needs round k's decisions -- and run on the context's stream: the call stops look-ahead
  *   batches, waits for pipelined launches and reads three counts back per round (it synchronises).  The cached pixel lists of the
  *   view and vp_get_pixel_lists are never modified by it.
@@ -312,8 +313,8 @@ int vp_stats_rel_error(float* dst, const vp_pixel_stats* d_stats, int size, floa
  * denoise -> gamma_correct, is OptiX; this is what stands in its place: the NL-means filter with a variance-cancelled patch distance
  * of Rousselle, Knaus and Zwicker 2012, which needs exactly the per-pixel records above).  `src` is an accumulator of sums and
  * d_stats its records; dst receives a MEAN image (the division by the count is part of the call).  The pair (guide, d_guide_stats)
- * supplies the weights, `src` the colours; both NULL: the guide is src itself.  With two half-buffers (even frames in one, odd
- * frames in the other) a caller cross-filters: two calls with the roles swapped, then vp_accumulate and scale.
+ * supplies the weights, `src` the colours; both NULL: the guide is src itself.  Cross-filtering two half-buffers is a
+ * pipeline of existing calls: vp_render_frames_halves_stats, two filter calls with the roles swapped, vp_merge_halves (below).
  *   Everything is binary32, no contraction, operations in the order written, unless marked binary64.  min(a, b) is a < b ? a : b,
  *   max(a, b) is a > b ? a : b, clamp() clamps a coordinate pair into the image.  Per pixel a of a pair (accumulator A, records T):
  *     s_a = T.n == 0 ? 0 : 1.0f / (float)T.n          c_a = A.xyz * s_a   (the bits vp_scale_by_count(..., 1.0f) writes)
@@ -381,6 +382,59 @@ int vp_denoise_guided(vp_float4* dst, const vp_float4* src, const vp_pixel_stats
                       const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
                       const vp_denoise_feature* features, int n_features,
                       int width, int height, const vp_denoise_params* dp);
+
+/* Half-buffer renders and the cross-filtered output stage: the dual buffers of Rousselle, Knaus and Zwicker
+ * 2012.  One render call splits its frames between two (accumulator, records) pairs, so that each half can supply the filter
+ * weights for the OTHER one -- weights that are independent of the noise they filter.
+ *
+ * vp_render_frames_halves_stats.  THE DEFINITION: let S be the context's sub-pixel factor and m = log2 S.  Frame f belongs to half
+ *   h(f) = (f >> 2m) & 1
+ * -- S = 1: even frames to h0, odd frames to h1.  S > 1: blocks of S^2 consecutive frames alternate, NOT plain parity:
+ * vp_subpixel_offset bit-reverses (f + hash) mod S^2, so the frames of one parity see half of the pixel's footprint only, while any
+ * aligned block of S^2 frames covers the whole S x S lattice whatever the per-pixel hash.  For h = 0, 1 the accumulator d_h and the
+ * records d_h_stats end bit-identical to what vp_render_frames_stats(d_h, d_h_stats, f, 1, p), called once for each f of
+ * [first_frame, first_frame + n_frames) with h(f) == h in ascending order, leaves in the same context state.  Hence:
+ *   - a frame adds nothing to the other half, no +0.0f either: a -0.0f already in the other accumulator stays -0.0f;
+ *   - record h gains in n exactly the number of its own frames; `flags` is neither read nor written;
+ *   - a per-pixel constant of a launch is one sequential addition per frame of that half, never a product;
+ *   - only owned pixels are touched (vp_set_shard);
+ *   - there is no hidden state: a second call continues a first one, a job that the staging cap splits into launches of any size
+ *     gives the bits of one launch, and the half is a function of the ABSOLUTE frame number, never of the index within a launch.
+ *   Built for: everything vp_render_frames_stats accepts -- every estimator, stream, tracking and environment mode, both arithmetic
+ *   modes, every volume format and sub-pixel factor, shards: the render launches are that call's own kernel instances, and only the
+ *   reduce is new.  Like the calls with planes it stops look-ahead batches, waits for pipelined launches and runs staged on the
+ *   context's stream, for one frame too; it stages ONE plane, so vp_reserve_frames serves it unchanged.  It leaves nothing behind.
+ *   Refused with VP_E_ARG before the device is touched, all four buffers untouched: any NULL pointer, d_h0 == d_h1, equal record
+ *   pointers, n_frames <= 0, first_frame < 0.  Other errors as vp_render_frames_stats gives them.
+ *   Not built: a form without records, adaptive rounds on halves, halves of calls with planes (layers, groups, group layers).
+ *
+ * vp_merge_halves: a and b are MEAN images of the two halves -- what vp_denoise, vp_denoise_guided or vp_scale_by_count(..., 1.0f)
+ * write -- and of the records only n is read.  Binary32, one rounding per operation, no contraction, in the order written:
+ *   na = (float)a_stats[i].n;   nb = (float)b_stats[i].n;   nt = na + nb
+ *   nt == 0:   dst[i] = (0, 0, 0, 0),  resid[i] = 0
+ *   else, each channel c of x, y, z, w:   dst[i].c = (a[i].c * na + b[i].c * nb) / nt          the divide correctly rounded
+ *   lum(v)   = (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z
+ *   d = lum(a[i]) - lum(b[i]);   e = 0.5f * fabsf(d);   ym = lum(dst[i]);   den = ym > floor_y ? ym : floor_y
+ *   resid[i] = (a_stats[i].n == 0 || b_stats[i].n == 0) ? 0.0f : e / den
+ * resid estimates the relative standard error of the merged image from the disagreement of two independent estimates; for filtered
+ * halves it therefore includes the filter's residual noise, which the records can no longer tell.  A diagnostic image like
+ * vp_stats_rel_error's; a pixel that vp_denoise leaves unfiltered because it is a constant gives exactly 0.  d_resid may be NULL; dst
+ * may be a or b; no scene is needed; asynchronous on the context's stream, never synchronises.  Refused with VP_E_ARG before the device
+ * is touched: NULL dst, a, b or either records pointer; size < 0; with d_resid given, a floor_y that is not finite or not > 0.
+ * The cross-filter is these calls in sequence (no entry point of its own: the filter takes a fraction of a millisecond):
+ *   vp_render_frames_halves_stats(h0, h1, s0, s1, ...)
+ *   vp_denoise_guided(A, h0, s0, h1, s1, ...)   vp_denoise_guided(B, h1, s1, h0, s0, ...)   vp_merge_halves(dst, resid, A, s0, B, s1, ...)
+ *
+ * vp_accumulate_stats: vp_accumulate for records.  Per record dst.sum_y = dst.sum_y + src.sum_y and dst.sum_y2 = dst.sum_y2 +
+ * src.sum_y2 (binary64), dst.n += src.n, dst.flags |= src.flags.  NULL pointers: VP_E_ARG.  With vp_accumulate it turns two halves
+ * into the (accumulator, records) pair of all their frames, and it merges the records of sharded contexts on one device (disjoint
+ * owned pixels: every addition is against zero and exact).  The union of two halves is NOT bit-equal to vp_render_frames_stats over
+ * the same frames -- the order of the additions differs; the exact-parity product stays the uniform call. */
+int vp_render_frames_halves_stats(vp_float4* d_h0, vp_float4* d_h1, vp_pixel_stats* d_h0_stats, vp_pixel_stats* d_h1_stats,
+                                  int first_frame, int n_frames, const Param* p);
+int vp_merge_halves(vp_float4* dst, float* d_resid, const vp_float4* a, const vp_pixel_stats* a_stats,
+                    const vp_float4* b, const vp_pixel_stats* b_stats, int size, float floor_y);
+int vp_accumulate_stats(vp_pixel_stats* dst, const vp_pixel_stats* src, size_t n);
 
 /* Compositing layers: a foreground F and a per-channel transmittance T with  pixel = F + T o B  for any
  * background B -- another sky, a plate, a second render.  vp_render_frames bakes the context's own sky into every sample and keeps
