@@ -4,10 +4,13 @@
 // scale / gamma_correct) and writes what the 'c' key captures (host.cpp:585-610): a .ppm of the
 // gamma-corrected image or a .hdr of the scaled accumulator.
 #include <chrono>
+#include <cstdarg>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -127,7 +130,43 @@ static void usage()
            "               [--rccl-selftest [device]]       load RCCL, one-rank communicator, one reduce: the calls of the N > 1 path\n");
 }
 
-int main(int argc, char** argv)
+// ---- the two ways a run ends early
+enum Hint { PLAIN, USAGE };
+// a refused command line: the message, usage() where the refusal is about a flag's operand, status 2
+[[noreturn]] static void refuse(Hint hint, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    fputc('\n', stderr);
+    if (hint == USAGE) usage();
+    exit(2);
+}
+// a failed library call: its message, status 1 (exit() flushes what was printed; files already written stay; nothing is freed)
+static void must(bool failed)
+{
+    if (!failed) return;
+    fprintf(stderr, "%s\n", vp_last_error());
+    exit(1);
+}
+
+static void need(int argc, int i, int n) { if (i + n >= argc) { usage(); exit(2); } }
+// the n floats behind flag argv[i], each passing ok(): else "FLAG OPERAND: what", usage(), status 2
+static void parse_floats(int argc, char** argv, int& i, int n, float* dst, bool (*ok)(float), const char* what)
+{
+    const char* flag = argv[i];
+    need(argc, i, n);
+    for (int c = 0; c < n; c++)
+    {
+        char* end = nullptr;
+        dst[c] = strtof(argv[++i], &end);
+        if (end == argv[i] || *end || !ok(dst[c])) refuse(USAGE, "%s %s: %s", flag, argv[i], what);
+    }
+}
+
+// ---- what the flags say, with the defaults
+struct Options
 {
     int         julia = 128, W = 400, H = 300, spp = 16, preset = 12, brick = 1, batch = 0;
     float       density = 800.0f, g = 0.877f, sunx = 0.5f, suny = 0.2f;
@@ -135,11 +174,9 @@ int main(int argc, char** argv)
     int         est = VP_EST_DECOMP, tracking = VP_TRACK_SPECTRAL, env_mode = VP_ENV_PASSIVE, arith = VP_ARITH_EXACT;
     std::string bin, vdb, out = "output0.ppm", devlist;
     int         vol_format = VP_VOL_U8;
-    static_assert((int)VOLUME_U8 == (int)VP_VOL_U8 && (int)VOLUME_F32 == (int)VP_VOL_F32 && (int)VOLUME_F16 == (int)VP_VOL_F16, "the loaders' formats are vp_init_volume's");
     int         gpus = 1, aa = 0;   // (0: not given -- the contexts keep their default, VP_SUBPIXEL)
     bool        adaptive = false;
     float       noise_tol = 0.0f;
-    const float noise_floor = 1e-3f;
     int         min_spp = 16, round_frames = 32;   // (the round: not measured yet)
     std::string noise_out;
     bool        denoise = false;
@@ -162,14 +199,23 @@ int main(int argc, char** argv)
     bool        planes_denoise = false;
     bool        planes_adaptive = false;
     float       planes_tol[3] = {0.0f, 0.0f, 0.0f};
-    const float planes_floor[3] = {1e-3f, 1e-3f, 1e-2f};   // (trans lives in [0, 1])
     std::string planes_noise_out;
     std::string features_out;
     vp_feature_params feat = {0.001f, VP_FEATURE_TAU_Z_DEFAULT};
+
+    void parse(int argc, char** argv);
+};
+static_assert((int)VOLUME_U8 == (int)VP_VOL_U8 && (int)VOLUME_F32 == (int)VP_VOL_F32 && (int)VOLUME_F16 == (int)VP_VOL_F16, "the loaders' formats are vp_init_volume's");
+
+void Options::parse(int argc, char** argv)
+{
+    const auto at_least_0 = [](float v) { return v >= 0.0f; };
+    const auto above_0    = [](float v) { return std::isfinite(v) && v > 0.0f; };
+    const auto finite     = [](float v) { return (bool)std::isfinite(v); };
     for (int i = 1; i < argc; i++)
     {
         std::string a = argv[i];
-        auto need = [&](int n) { if (i + n >= argc) { usage(); exit(2); } };
+        auto need = [&](int n) { ::need(argc, i, n); };
         if (a == "--julia") { need(1); julia = atoi(argv[++i]); }
         else if (a == "--bin") { need(1); bin = argv[++i]; }
         else if (a == "--vdb") { need(1); vdb = argv[++i]; }
@@ -180,7 +226,7 @@ int main(int argc, char** argv)
             if (!strcmp(f, "u8")) vol_format = VP_VOL_U8;
             else if (!strcmp(f, "f32")) vol_format = VP_VOL_F32;
             else if (!strcmp(f, "f16")) vol_format = VP_VOL_F16;
-            else { fprintf(stderr, "unknown --volume-format %s (u8, f32 or f16)\n", f); usage(); return 2; }
+            else refuse(USAGE, "unknown --volume-format %s (u8, f32 or f16)", f);
         }
         else if (a == "--size") { need(2); W = atoi(argv[++i]); H = atoi(argv[++i]); }
         else if (a == "--spp") { need(1); spp = atoi(argv[++i]); }
@@ -208,46 +254,19 @@ int main(int argc, char** argv)
             const char* m = argv[++i];
             if (!strcmp(m, "exact")) arith = VP_ARITH_EXACT;
             else if (!strcmp(m, "fast")) arith = VP_ARITH_FAST;
-            else { fprintf(stderr, "unknown --arith %s\n", m); usage(); return 2; }
+            else refuse(USAGE, "unknown --arith %s", m);
         }
         else if (a == "--aa")
         {
             need(1);
             const char* m = argv[++i];
             aa = !strcmp(m, "1") ? 1 : !strcmp(m, "2") ? 2 : !strcmp(m, "4") ? 4 : !strcmp(m, "8") ? 8 : 0;
-            if (!aa) { fprintf(stderr, "unknown --aa %s (1, 2, 4 or 8)\n", m); usage(); return 2; }
+            if (!aa) refuse(USAGE, "unknown --aa %s (1, 2, 4 or 8)", m);
         }
-        else if (a == "--noise")
-        {
-            need(1);
-            char* end = nullptr;
-            noise_tol = strtof(argv[++i], &end);
-            if (end == argv[i] || *end || !(noise_tol >= 0.0f)) { fprintf(stderr, "--noise %s: a tolerance >= 0\n", argv[i]); usage(); return 2; }
-            adaptive = true;
-        }
-        else if (a == "--plane-noise")
-        {
-            need(2);
-            for (int c = 0; c < 2; c++)
-            {
-                char* end = nullptr;
-                plane_tol[c] = strtof(argv[++i], &end);
-                if (end == argv[i] || *end || !(plane_tol[c] >= 0.0f)) { fprintf(stderr, "--plane-noise %s: two tolerances >= 0\n", argv[i]); usage(); return 2; }
-            }
-            plane_adaptive = true;
-        }
+        else if (a == "--noise") { parse_floats(argc, argv, i, 1, &noise_tol, at_least_0, "a tolerance >= 0"); adaptive = true; }
+        else if (a == "--plane-noise") { parse_floats(argc, argv, i, 2, plane_tol, at_least_0, "two tolerances >= 0"); plane_adaptive = true; }
         else if (a == "--plane-noise-out") { need(1); plane_noise_out = argv[++i]; }
-        else if (a == "--planes-noise")
-        {
-            need(3);
-            for (int c = 0; c < 3; c++)
-            {
-                char* end = nullptr;
-                planes_tol[c] = strtof(argv[++i], &end);
-                if (end == argv[i] || *end || !(planes_tol[c] >= 0.0f)) { fprintf(stderr, "--planes-noise %s: three tolerances >= 0\n", argv[i]); usage(); return 2; }
-            }
-            planes_adaptive = true;
-        }
+        else if (a == "--planes-noise") { parse_floats(argc, argv, i, 3, planes_tol, at_least_0, "three tolerances >= 0"); planes_adaptive = true; }
         else if (a == "--planes-noise-out") { need(1); planes_noise_out = argv[++i]; }
         else if (a == "--min-spp") { need(1); min_spp = atoi(argv[++i]); }
         else if (a == "--round") { need(1); round_frames = atoi(argv[++i]); }
@@ -268,56 +287,18 @@ int main(int argc, char** argv)
                 ok = end != v && !*end && n >= 0 && n <= (a == "--denoise-radius" ? VP_DENOISE_MAX_RADIUS : VP_DENOISE_MAX_PATCH);
                 (a == "--denoise-radius" ? dn.radius : dn.patch) = (int)n;
             }
-            if (!ok)
-            {
-                fprintf(stderr, "%s %s: radius 0..%d, patch 0..%d, k a finite number > 0\n", a.c_str(), v, VP_DENOISE_MAX_RADIUS, VP_DENOISE_MAX_PATCH);
-                usage();
-                return 2;
-            }
+            if (!ok) refuse(USAGE, "%s %s: radius 0..%d, patch 0..%d, k a finite number > 0", a.c_str(), v, VP_DENOISE_MAX_RADIUS, VP_DENOISE_MAX_PATCH);
         }
         else if (a == "--denoise-features") denoise_features = true;
-        else if (a == "--denoise-sigma-alpha" || a == "--denoise-sigma-depth")
-        {
-            need(1);
-            char* end = nullptr;
-            const float v = strtof(argv[++i], &end);
-            if (end == argv[i] || *end || !std::isfinite(v) || !(v > 0.0f)) { fprintf(stderr, "%s %s: a finite number > 0\n", a.c_str(), argv[i]); usage(); return 2; }
-            (a == "--denoise-sigma-alpha" ? dn_sigma_alpha : dn_sigma_depth) = v;
-        }
+        else if (a == "--denoise-sigma-alpha") parse_floats(argc, argv, i, 1, &dn_sigma_alpha, above_0, "a finite number > 0");
+        else if (a == "--denoise-sigma-depth") parse_floats(argc, argv, i, 1, &dn_sigma_depth, above_0, "a finite number > 0");
         else if (a == "--layers-out") { need(1); layers_out = argv[++i]; }
-        else if (a == "--over")
-        {
-            need(3);
-            for (int c = 0; c < 3; c++)
-            {
-                char* end = nullptr;
-                over_rgb[c] = strtof(argv[++i], &end);
-                if (end == argv[i] || *end || !std::isfinite(over_rgb[c])) { fprintf(stderr, "--over %s: three finite numbers\n", argv[i]); usage(); return 2; }
-            }
-            over = true;
-        }
+        else if (a == "--over") { parse_floats(argc, argv, i, 3, over_rgb, finite, "three finite numbers"); over = true; }
         else if (a == "--groups-out") { need(1); groups_out = argv[++i]; }
-        else if (a == "--sun-gain" || a == "--sky-gain")
-        {
-            need(3);
-            float* gain = a == "--sun-gain" ? sun_gain : sky_gain;
-            for (int c = 0; c < 3; c++)
-            {
-                char* end = nullptr;
-                gain[c] = strtof(argv[++i], &end);
-                if (end == argv[i] || *end || !std::isfinite(gain[c])) { fprintf(stderr, "%s %s: three finite numbers\n", a.c_str(), argv[i]); usage(); return 2; }
-            }
-            relit = true;
-        }
+        else if (a == "--sun-gain" || a == "--sky-gain") { parse_floats(argc, argv, i, 3, a == "--sun-gain" ? sun_gain : sky_gain, finite, "three finite numbers"); relit = true; }
         else if (a == "--features-out") { need(1); features_out = argv[++i]; }
-        else if (a == "--feature-step" || a == "--depth-tau")
-        {
-            need(1);
-            char* end = nullptr;
-            const float v = strtof(argv[++i], &end);
-            if (end == argv[i] || *end || !std::isfinite(v) || !(v > 0.0f)) { fprintf(stderr, "%s %s: a finite number > 0\n", a.c_str(), argv[i]); usage(); return 2; }
-            (a == "--feature-step" ? feat.step : feat.tau_z) = v;
-        }
+        else if (a == "--feature-step") parse_floats(argc, argv, i, 1, &feat.step, above_0, "a finite number > 0");
+        else if (a == "--depth-tau") parse_floats(argc, argv, i, 1, &feat.tau_z, above_0, "a finite number > 0");
         else if (a == "--planes-out") { need(1); planes_out = argv[++i]; }
         else if (a == "--planes-denoise") planes_denoise = true;
         else if (a == "--groups-denoise") groups_denoise = true;
@@ -334,174 +315,225 @@ int main(int argc, char** argv)
             std::string report;
             const bool  ok = volpath::rccl_selftest(dev, (size_t)1280 * 720 * 4, report);
             printf("%s\n", report.c_str());
-            return ok ? 0 : 1;
+            exit(ok ? 0 : 1);
         }
-        else { usage(); return a == "--help" ? 0 : 2; }
+        else { usage(); exit(a == "--help" ? 0 : 2); }
     }
+}
 
-    Param P = default_param(W, H);  // host.cpp:1286-1292
-    P.density = density;
-    P.g       = g;
-    if (!material_preset(P, preset)) { fprintf(stderr, "preset must be 0..12\n"); return 2; }
+// ---- what the run is
+// One image plane of the render: the suffix of its files, the floor of its adaptive criterion and noise map, and its device buffers
+// (the sum of its samples; a record per pixel where the job keeps records; its mean image where the job forms one).
+struct Plane
+{
+    const char*     suffix;
+    float           floor;
+    vp_float4*      acc;
+    vp_pixel_stats* rec;
+    vp_float4*      mean;
+};
+static const float kFloor = 1e-3f, kFloorTrans = 1e-2f;   // (the transmittance lives in [0, 1])
+static const Plane kBeauty = {"", kFloor}, kSun = {"_sun.hdr", kFloor}, kSky = {"_sky.hdr", kFloor}, kFg = {"_fg.hdr", kFloor}, kTrans = {"_trans.hdr", kFloorTrans};
 
-    if (vol_format != VP_VOL_U8 && bin.empty() && vdb.empty())
-    {
-        fprintf(stderr, "--volume-format %s needs --bin or --vdb: --julia voxelises to bytes (u8)\n", vol_format == VP_VOL_F16 ? "f16" : "f32");
-        return 2;
-    }
-    // ---- the GPUs: one context per rank (a single rank runs in the default context, as the reference's host would)
-    if (gpus < 1) { usage(); return 2; }
-    if (adaptive && gpus > 1)
-    {
-        fprintf(stderr, "--noise with --gpus %d: reducing per-pixel statistics across ranks is not part of adaptive sampling; use one GPU\n", gpus);
-        return 2;
-    }
-    if (!denoise_cross && !resid_out.empty()) { fprintf(stderr, "--resid-out needs --denoise-cross: the map is the disagreement of the two filtered halves\n"); return 2; }
-    if (denoise_cross)
-    {
-        const char* other = gpus > 1 ? "--gpus" : adaptive ? "--noise" : !planes_out.empty() ? "--planes-out" : !groups_out.empty() ? "--groups-out" : relit ? "--sun-gain / --sky-gain"
-                          : !layers_out.empty() ? "--layers-out" : over ? "--over" : plane_adaptive ? "--plane-noise" : planes_adaptive ? "--planes-noise"
-                          : groups_denoise ? "--groups-denoise" : layers_denoise ? "--layers-denoise" : planes_denoise ? "--planes-denoise" : nullptr;
-        if (other)
-        {
-            fprintf(stderr, "--denoise-cross with %s: the half-buffers' records are not reduced across ranks, adaptive rounds on halves are not built and the halves are "
-                    "the beauty image's, not a plane's; use one GPU without --noise and without plane outputs or plane filters\n", other);
-            return 2;
-        }
-    }
-    if (denoise && gpus > 1)
-    {
-        fprintf(stderr, "--denoise with --gpus %d: the filter reads per-pixel statistics, which are not reduced across ranks; use one GPU\n", gpus);
-        return 2;
-    }
-    if (denoise_features && (!denoise || aa > 1))
-    {
-        if (!denoise) fprintf(stderr, "--denoise-features needs --denoise: it cuts the weights of that filter (the per-plane filters do not take it)\n");
-        else fprintf(stderr, "--denoise-features with --aa %d: the feature pass marches pixel-centre rays and refuses a sub-pixel factor; use --aa 1\n", aa);
-        return 2;
-    }
+enum Mode { BEAUTY, LAYERS, GROUPS, PLANES };
+struct Job
+{
+    Options          o;
+    Param            P;
+    std::vector<int> devices;
+    int              batch = 0;
+    bool             hdr = false;        // --out is the scaled accumulator, not its gamma-corrected bytes
+    Mode             mode = BEAUTY;
+    int              n = 1;              // planes: beauty 1 (--denoise-cross 2: its half-buffers), layers fg trans, groups sun sky, planes sun sky trans
+    Plane            plane[3] = {};
+    bool             filter = false;     // the mean of a plane is vp_denoise's (beauty: --denoise and its variants)
+    bool             adaptive = false;   // rounds to the tolerances tol[k], then no batch loop
+    bool             records = false;    // the frames go through the mode's _stats call / its adaptive call
+    bool             means = false;      // a mean buffer per plane
+    float            tol[3] = {};
+    const char*      noise_flag = "";    // the adaptive flag, for the report
+    std::string      prefix, noise_prefix;   // plane files and noise maps: PREFIX + suffix (beauty: --noise-out's one name)
+};
+
+struct Conflict { bool given; const char* flag; };
+// the first flag of the list that was given, or nullptr
+static const char* first_of(std::initializer_list<Conflict> list)
+{
+    for (const Conflict& c : list) if (c.given) return c.flag;
+    return nullptr;
+}
+
+// the refusals of flags that do not go together, in their order; what passes them is one of the four modes
+static Mode refuse_conflicts(const Options& o)
+{
+    if (o.vol_format != VP_VOL_U8 && o.bin.empty() && o.vdb.empty())
+        refuse(PLAIN, "--volume-format %s needs --bin or --vdb: --julia voxelises to bytes (u8)", o.vol_format == VP_VOL_F16 ? "f16" : "f32");
+    if (o.gpus < 1) { usage(); exit(2); }
+    // what every mode with per-pixel records refuses: they are not reduced across ranks, and the beauty image's rounds and filter are its own
+    const auto  beauty_flag = [&] { return first_of({{o.gpus > 1, "--gpus"}, {o.adaptive, "--noise"}, {o.denoise, "--denoise"}}); };
+    const bool  plain_lights = o.tracking == VP_TRACK_SPECTRAL && o.env_mode == VP_ENV_PASSIVE && o.arith == VP_ARITH_EXACT;
+    const bool  bad_rounds = o.min_spp < 2 || o.round_frames < 1;
+    const char* other;
+    if (o.adaptive && o.gpus > 1)
+        refuse(PLAIN, "--noise with --gpus %d: reducing per-pixel statistics across ranks is not part of adaptive sampling; use one GPU", o.gpus);
+    if (!o.denoise_cross && !o.resid_out.empty()) refuse(PLAIN, "--resid-out needs --denoise-cross: the map is the disagreement of the two filtered halves");
+    if (o.denoise_cross && (other = first_of({{o.gpus > 1, "--gpus"}, {o.adaptive, "--noise"}, {!o.planes_out.empty(), "--planes-out"}, {!o.groups_out.empty(), "--groups-out"},
+                                              {o.relit, "--sun-gain / --sky-gain"}, {!o.layers_out.empty(), "--layers-out"}, {o.over, "--over"}, {o.plane_adaptive, "--plane-noise"},
+                                              {o.planes_adaptive, "--planes-noise"}, {o.groups_denoise, "--groups-denoise"}, {o.layers_denoise, "--layers-denoise"},
+                                              {o.planes_denoise, "--planes-denoise"}})))
+        refuse(PLAIN, "--denoise-cross with %s: the half-buffers' records are not reduced across ranks, adaptive rounds on halves are not built and the halves are "
+               "the beauty image's, not a plane's; use one GPU without --noise and without plane outputs or plane filters", other);
+    if (o.denoise && o.gpus > 1)
+        refuse(PLAIN, "--denoise with --gpus %d: the filter reads per-pixel statistics, which are not reduced across ranks; use one GPU", o.gpus);
+    if (o.denoise_features && !o.denoise) refuse(PLAIN, "--denoise-features needs --denoise: it cuts the weights of that filter (the per-plane filters do not take it)");
+    if (o.denoise_features && o.aa > 1)
+        refuse(PLAIN, "--denoise-features with --aa %d: the feature pass marches pixel-centre rays and refuses a sub-pixel factor; use --aa 1", o.aa);
     // --planes-out: sun, sky and trans from one render; the gains and --over are then its parameters, not a groups or a layers render's
-    const bool planes = !planes_out.empty();
-    if (planes_denoise && !planes) { fprintf(stderr, "--planes-denoise needs --planes-out: it filters the three planes of that render\n"); return 2; }
-    if (planes)
-    {
-        const char* other = gpus > 1 ? "--gpus" : adaptive ? "--noise" : denoise ? "--denoise" : !groups_out.empty() ? "--groups-out" : !layers_out.empty() ? "--layers-out"
-                          : plane_adaptive ? "--plane-noise" : groups_denoise ? "--groups-denoise" : layers_denoise ? "--layers-denoise" : nullptr;
-        if (other)
-        {
-            fprintf(stderr, "--planes-out with %s: the three planes are not reduced across ranks, are filtered by --planes-denoise only, are sampled adaptively by "
-                    "--planes-noise only and replace the groups and the layers render; use one GPU without --noise, --denoise, --groups-out, --layers-out and "
-                    "--plane-noise (three tolerances: --planes-noise TOL_SUN TOL_SKY TOL_TRANS)\n", other);
-            return 2;
-        }
-        if (tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE || arith != VP_ARITH_EXACT)
-        {
-            fprintf(stderr, "--planes-out needs spectral tracking, --env passive and --arith exact\n");
-            return 2;
-        }
-    }
+    const bool planes = !o.planes_out.empty();
+    if (o.planes_denoise && !planes) refuse(PLAIN, "--planes-denoise needs --planes-out: it filters the three planes of that render");
+    if (planes && (other = first_of({{o.gpus > 1, "--gpus"}, {o.adaptive, "--noise"}, {o.denoise, "--denoise"}, {!o.groups_out.empty(), "--groups-out"},
+                                     {!o.layers_out.empty(), "--layers-out"}, {o.plane_adaptive, "--plane-noise"}, {o.groups_denoise, "--groups-denoise"},
+                                     {o.layers_denoise, "--layers-denoise"}})))
+        refuse(PLAIN, "--planes-out with %s: the three planes are not reduced across ranks, are filtered by --planes-denoise only, are sampled adaptively by "
+               "--planes-noise only and replace the groups and the layers render; use one GPU without --noise, --denoise, --groups-out, --layers-out and "
+               "--plane-noise (three tolerances: --planes-noise TOL_SUN TOL_SKY TOL_TRANS)", other);
+    if (planes && !plain_lights) refuse(PLAIN, "--planes-out needs spectral tracking, --env passive and --arith exact");
     // adaptive rounds on the three planes: --planes-out, one GPU, and neither the beauty image's rounds nor its filter (refused above)
-    if (planes_adaptive && !planes) { fprintf(stderr, "--planes-noise needs --planes-out: it samples the three planes of that render\n"); return 2; }
-    if (planes_adaptive && (min_spp < 2 || round_frames < 1)) { fprintf(stderr, "--planes-noise needs --min-spp >= 2 and --round >= 1\n"); usage(); return 2; }
-    if (!planes_adaptive && !planes_noise_out.empty()) { fprintf(stderr, "--planes-noise-out needs --planes-noise\n"); return 2; }
-    const bool layers = !planes && (over || !layers_out.empty());
-    const bool groups = !planes && (relit || !groups_out.empty());
+    if (o.planes_adaptive && !planes) refuse(PLAIN, "--planes-noise needs --planes-out: it samples the three planes of that render");
+    if (o.planes_adaptive && bad_rounds) refuse(USAGE, "--planes-noise needs --min-spp >= 2 and --round >= 1");
+    if (!o.planes_adaptive && !o.planes_noise_out.empty()) refuse(PLAIN, "--planes-noise-out needs --planes-noise");
+    const bool layers = !planes && (o.over || !o.layers_out.empty());
+    const bool groups = !planes && (o.relit || !o.groups_out.empty());
     // the per-plane filters: each needs its plane flag, one GPU, and neither the beauty image's filter nor adaptive rounds
     for (int k = 0; k < 2; k++)
     {
         const char* flag = k ? "--layers-denoise" : "--groups-denoise";
-        if (!(k ? layers_denoise : groups_denoise)) continue;
+        if (!(k ? o.layers_denoise : o.groups_denoise)) continue;
         if (!(k ? layers : groups))
-        {
-            fprintf(stderr, "%s needs %s: it filters the planes of a %s render\n", flag, k ? "--layers-out or --over" : "--groups-out, --sun-gain or --sky-gain", k ? "layers" : "light-groups");
-            return 2;
-        }
-        if (gpus > 1 || adaptive || denoise)
-        {
-            fprintf(stderr, "%s with %s: per-plane records are not reduced across ranks, adaptive rounds on planes are --plane-noise's, and --denoise filters the beauty image; "
-                    "use one GPU without --noise and --denoise\n", flag, gpus > 1 ? "--gpus" : adaptive ? "--noise" : "--denoise");
-            return 2;
-        }
+            refuse(PLAIN, "%s needs %s: it filters the planes of a %s render", flag, k ? "--layers-out or --over" : "--groups-out, --sun-gain or --sky-gain", k ? "layers" : "light-groups");
+        if ((other = beauty_flag()))
+            refuse(PLAIN, "%s with %s: per-plane records are not reduced across ranks, adaptive rounds on planes are --plane-noise's, and --denoise filters the beauty image; "
+                   "use one GPU without --noise and --denoise", flag, other);
     }
-    const bool plane_denoise = groups_denoise || layers_denoise;
     // adaptive rounds on planes: a plane flag, one GPU, and neither the beauty image's rounds nor its filter
-    if (plane_adaptive && !layers && !groups)
+    if (o.plane_adaptive && !layers && !groups)
+        refuse(PLAIN, "--plane-noise needs --groups-out, --sun-gain or --sky-gain, or --layers-out or --over: it samples the planes of a light-groups or layers render");
+    if (o.plane_adaptive && (other = beauty_flag()))
+        refuse(PLAIN, "--plane-noise with %s: per-plane records are not reduced across ranks, --noise samples the beauty image and --denoise filters it; "
+               "use one GPU without --noise and --denoise", other);
+    if (o.plane_adaptive && bad_rounds) refuse(USAGE, "--plane-noise needs --min-spp >= 2 and --round >= 1");
+    if (!o.plane_adaptive && !o.plane_noise_out.empty()) refuse(PLAIN, "--plane-noise-out needs --plane-noise");
+    if (layers && (other = beauty_flag()))
+        refuse(PLAIN, "--layers-out / --over with %s: layers are not reduced across ranks and carry no per-pixel statistics; use one GPU without --noise and --denoise", other);
+    if (layers && !plain_lights) refuse(PLAIN, "--layers-out / --over need spectral tracking, --env passive and --arith exact");
+    if (groups && ((other = beauty_flag()) || (other = first_of({{o.over, "--over"}, {layers, "--layers-out"}}))))
+        refuse(PLAIN, "--groups-out / --sun-gain / --sky-gain with %s: light groups are not reduced across ranks, carry no per-pixel statistics and are not combined with layers; "
+               "use one GPU without --noise, --denoise, --layers-out and --over", other);
+    if (groups && !plain_lights) refuse(PLAIN, "--groups-out / --sun-gain / --sky-gain need spectral tracking, --env passive and --arith exact");
+    if (o.adaptive && bad_rounds) refuse(USAGE, "--noise needs --min-spp >= 2 and --round >= 1");
+    if (!o.adaptive && !o.noise_out.empty()) refuse(PLAIN, "--noise-out needs --noise");
+    if (o.arith == VP_ARITH_FAST && (o.philox == 0 || o.est == VP_EST_BOUNDED || o.tracking != VP_TRACK_SPECTRAL || o.env_mode != VP_ENV_PASSIVE))
+        refuse(PLAIN, "--arith fast needs --rng philox|philox7, --estimator decomp|global, spectral tracking and --env passive");
+    return planes ? PLANES : layers ? LAYERS : groups ? GROUPS : BEAUTY;
+}
+
+// the one place that decides what the run is
+static Job validate(const Options& o)
+{
+    Job j;
+    j.o = o;
+    j.P = default_param(o.W, o.H);  // host.cpp:1286-1292
+    j.P.density = o.density;
+    j.P.g       = o.g;
+    if (!material_preset(j.P, o.preset)) refuse(PLAIN, "preset must be 0..12");
+    j.mode = refuse_conflicts(o);
+    for (size_t pos = 0; pos < o.devlist.size();)
     {
-        fprintf(stderr, "--plane-noise needs --groups-out, --sun-gain or --sky-gain, or --layers-out or --over: it samples the planes of a light-groups or layers render\n");
-        return 2;
-    }
-    if (plane_adaptive && (gpus > 1 || adaptive || denoise))
-    {
-        fprintf(stderr, "--plane-noise with %s: per-plane records are not reduced across ranks, --noise samples the beauty image and --denoise filters it; "
-                "use one GPU without --noise and --denoise\n", gpus > 1 ? "--gpus" : adaptive ? "--noise" : "--denoise");
-        return 2;
-    }
-    if (plane_adaptive && (min_spp < 2 || round_frames < 1)) { fprintf(stderr, "--plane-noise needs --min-spp >= 2 and --round >= 1\n"); usage(); return 2; }
-    if (!plane_adaptive && !plane_noise_out.empty()) { fprintf(stderr, "--plane-noise-out needs --plane-noise\n"); return 2; }
-    if (layers && (gpus > 1 || adaptive || denoise))
-    {
-        fprintf(stderr, "--layers-out / --over with %s: layers are not reduced across ranks and carry no per-pixel statistics; use one GPU without --noise and --denoise\n",
-                gpus > 1 ? "--gpus" : adaptive ? "--noise" : "--denoise");
-        return 2;
-    }
-    if (layers && (tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE || arith != VP_ARITH_EXACT))
-    {
-        fprintf(stderr, "--layers-out / --over need spectral tracking, --env passive and --arith exact\n");
-        return 2;
-    }
-    if (groups && (gpus > 1 || adaptive || denoise || layers))
-    {
-        fprintf(stderr, "--groups-out / --sun-gain / --sky-gain with %s: light groups are not reduced across ranks, carry no per-pixel statistics and are not combined with layers; "
-                "use one GPU without --noise, --denoise, --layers-out and --over\n",
-                gpus > 1 ? "--gpus" : adaptive ? "--noise" : denoise ? "--denoise" : over ? "--over" : "--layers-out");
-        return 2;
-    }
-    if (groups && (tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE || arith != VP_ARITH_EXACT))
-    {
-        fprintf(stderr, "--groups-out / --sun-gain / --sky-gain need spectral tracking, --env passive and --arith exact\n");
-        return 2;
-    }
-    if (adaptive && (min_spp < 2 || round_frames < 1)) { fprintf(stderr, "--noise needs --min-spp >= 2 and --round >= 1\n"); usage(); return 2; }
-    if (!adaptive && !noise_out.empty()) { fprintf(stderr, "--noise-out needs --noise\n"); return 2; }
-    if (arith == VP_ARITH_FAST && (philox == 0 || est == VP_EST_BOUNDED || tracking != VP_TRACK_SPECTRAL || env_mode != VP_ENV_PASSIVE))
-    {
-        fprintf(stderr, "--arith fast needs --rng philox|philox7, --estimator decomp|global, spectral tracking and --env passive\n");
-        return 2;
-    }
-    std::vector<int> devices;
-    for (size_t pos = 0; pos < devlist.size();)
-    {
-        size_t e = devlist.find(',', pos);
-        if (e == std::string::npos) e = devlist.size();
-        devices.push_back(atoi(devlist.substr(pos, e - pos).c_str()));
+        size_t e = o.devlist.find(',', pos);
+        if (e == std::string::npos) e = o.devlist.size();
+        j.devices.push_back(atoi(o.devlist.substr(pos, e - pos).c_str()));
         pos = e + 1;
     }
-    if (devices.empty()) for (int r = 0; r < gpus; r++) devices.push_back(r);
-    if ((int)devices.size() != gpus) { fprintf(stderr, "--devices must list %d devices\n", gpus); return 2; }
-    if (gpus > 1 && batch <= 0) batch = std::min(spp, 256);  // shards render in batches: one launch per rank keeps every GPU busy
-    std::vector<vp_ctx*> ctx(gpus, nullptr);
-    if (gpus > 1)
-        for (int r = 0; r < gpus; r++)
-        {
-            ctx[r] = vp_ctx_create(devices[r]);
-            if (!ctx[r]) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        }
-    else if (vp_set_device(devices[0])) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-    auto use = [&](int r) { if (gpus > 1) vp_ctx_set_current(ctx[r]); };
+    if (j.devices.empty()) for (int r = 0; r < o.gpus; r++) j.devices.push_back(r);
+    if ((int)j.devices.size() != o.gpus) refuse(PLAIN, "--devices must list %d devices", o.gpus);
+    j.batch = o.gpus > 1 && o.batch <= 0 ? std::min(o.spp, 256) : o.batch;  // shards render in batches: one launch per rank keeps every GPU busy
+    j.hdr   = o.out.size() > 4 && o.out.substr(o.out.size() - 4) == ".hdr";
+
+    // ---- the plane table of the mode, with its one filter flag and its one adaptive flag
+    const bool   layers = j.mode == LAYERS;
+    const float* tol = &o.noise_tol;
+    switch (j.mode)
+    {
+    case BEAUTY:
+        j.plane[0] = kBeauty, j.plane[1] = kBeauty, j.n = o.denoise_cross ? 2 : 1;
+        j.filter = o.denoise, j.adaptive = o.adaptive, j.noise_flag = "--noise", j.noise_prefix = o.noise_out;
+        break;
+    case LAYERS:
+    case GROUPS:
+        j.plane[0] = layers ? kFg : kSun, j.plane[1] = layers ? kTrans : kSky, j.n = 2;
+        j.filter = layers ? o.layers_denoise : o.groups_denoise, j.prefix = layers ? o.layers_out : o.groups_out;
+        j.adaptive = o.plane_adaptive, j.noise_flag = "--plane-noise", j.noise_prefix = o.plane_noise_out, tol = o.plane_tol;
+        break;
+    case PLANES:
+        j.plane[0] = kSun, j.plane[1] = kSky, j.plane[2] = kTrans, j.n = 3;
+        j.filter = o.planes_denoise, j.prefix = o.planes_out;
+        j.adaptive = o.planes_adaptive, j.noise_flag = "--planes-noise", j.noise_prefix = o.planes_noise_out, tol = o.planes_tol;
+        break;
+    }
+    for (int k = 0; k < j.n && j.adaptive; k++) j.tol[k] = tol[k];
+    j.records = j.filter || j.adaptive;
+    j.means   = j.mode == BEAUTY ? o.denoise_cross : j.records;   // (the beauty image's mean is formed in the display buffer)
+    return j;
+}
+
+// ---- the devices of the run: one context per rank (a single rank runs in the default context, as the reference's host would)
+struct Run
+{
+    int                     gpus = 1, npix = 0;
+    std::vector<vp_ctx*>    ctx;
+    std::vector<vp_float4*> accum;     // full frame on every rank: zero outside its tiles
+    std::vector<void*>      streams;
+    volpath::SunSky         sky;
+    volpath::NodeReducer    reducer;
+    vp_float4*              disp = nullptr;
+    vp_adaptive_result      ares = {};
+
+    void use(int r) const { if (gpus > 1) vp_ctx_set_current(ctx[r]); }
+};
+
+template <class T> static T* device_alloc(int n, bool zeroed)
+{
+    T* p = (T*)vp_malloc((size_t)n * sizeof(T));
+    must(!p || (zeroed && vp_memset(p, 0, (size_t)n * sizeof(T))));
+    return p;
+}
+
+// contexts, the volume and the scene on every rank, the accumulators, the reducer, the display buffer
+static void set_up(const Job& j, Run& run)
+{
+    const Options& o = j.o;
+    run.gpus = o.gpus;
+    run.npix = o.W * o.H;
+    run.ctx.assign(o.gpus, nullptr);
+    run.accum.assign(o.gpus, nullptr);
+    run.streams.assign(o.gpus, nullptr);
+    if (o.gpus > 1)
+        for (int r = 0; r < o.gpus; r++) must(!(run.ctx[r] = vp_ctx_create(j.devices[r])));
+    else must(vp_set_device(j.devices[0]));
 
     // ---- volume (host.cpp:1330-1344): loaded once, uploaded to every rank (all read-only scene data is replicated)
     int   width = 0, height = 0, depth = 0;
     void* h_volume = nullptr;
-    if (!bin.empty()) h_volume = loadBinaryFileAs(bin.c_str(), width, height, depth, vol_format);
-    else if (!vdb.empty()) h_volume = loadVdbFileAs(vdb.c_str(), width, height, depth, vol_format);
+    if (!o.bin.empty()) h_volume = loadBinaryFileAs(o.bin.c_str(), width, height, depth, o.vol_format);
+    else if (!o.vdb.empty()) h_volume = loadVdbFileAs(o.vdb.c_str(), width, height, depth, o.vol_format);
     else
     {
-        width = height = depth = julia;
-        h_volume = malloc((size_t)julia * julia * julia);
-        use(0);
-        if (!h_volume || vp_julia_voxelize(julia, (unsigned char*)h_volume)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        width = height = depth = o.julia;
+        h_volume = malloc((size_t)o.julia * o.julia * o.julia);
+        run.use(0);
+        must(!h_volume || vp_julia_voxelize(o.julia, (unsigned char*)h_volume));
     }
-    if (!h_volume) return 1;
+    if (!h_volume) exit(1);
     vp_float3 box_min = {-1.0f, -(float)height / (float)width, -(float)depth / (float)width};
     vp_float3 box_max = {1.0f, (float)height / (float)width, (float)depth / (float)width};
     float identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -509,474 +541,345 @@ int main(int argc, char** argv)
     float  m[12];
     cam.inv_view_matrix(m);
     // sun / sky (host.cpp:1388-1390 -> update_sunsky)
-    volpath::SunSky sky = volpath::bake_sunsky(sunx, suny);
+    run.sky = volpath::bake_sunsky(o.sunx, o.suny);
+    volpath::SunSky& sky = run.sky;
     printf("sun power = %f, %f, %f\n", sky.sun_power.x, sky.sun_power.y, sky.sun_power.z);
 
-    const int               npix = W * H;
-    std::vector<vp_float4*> accum(gpus, nullptr);
-    std::vector<void*>      streams(gpus, nullptr);
-    for (int r = 0; r < gpus; r++)
+    for (int r = 0; r < o.gpus; r++)
     {
-        use(r);
-        vp_set_bound_brick(brick);
-        if (vol_format == VP_VOL_U8) init_cuda(h_volume, vp_extent{(size_t)width, (size_t)height, (size_t)depth}, true, &box_min, &box_max);
-        else if (vp_init_volume(h_volume, vp_extent{(size_t)width, (size_t)height, (size_t)depth}, vol_format, &box_min, &box_max))
-        {
-            fprintf(stderr, "%s\n", vp_last_error());
-            return 1;
-        }
+        run.use(r);
+        vp_set_bound_brick(o.brick);
+        if (o.vol_format == VP_VOL_U8) init_cuda(h_volume, vp_extent{(size_t)width, (size_t)height, (size_t)depth}, true, &box_min, &box_max);
+        else must(vp_init_volume(h_volume, vp_extent{(size_t)width, (size_t)height, (size_t)depth}, o.vol_format, &box_min, &box_max));
         set_texture_filter_mode(true);
         copy_inv_model_matrix(identity, sizeof(identity));  // host.cpp:1350-1353
         copy_inv_view_matrix(m, sizeof(m));                 // host.cpp:617-623
         init_envmap(reinterpret_cast<const vp_float4*>(sky.envmap.data()), sky.width, sky.height);
         set_sun(&sky.sun_dir.x, &sky.sun_power.x);
-        vp_set_estimator(est);
-        if (vp_set_tracking(tracking) || vp_set_envmap_sampling(env_mode) || vp_set_shard(r, gpus)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        vp_set_rng(philox == 2 ? VP_RNG_PHILOX7 : philox ? VP_RNG_PHILOX : VP_RNG_SAMPLERH, 0x9E3779B9u, 0x85EBCA6Bu);
-        if (vp_set_arithmetic(arith)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        if (aa && vp_set_subpixel(aa)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        // frame buffer (CudaFrameBuffer host.cpp:358-389), full frame on every rank: zero outside its tiles
-        accum[r] = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-        if (!accum[r]) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        vp_memset(accum[r], 0, (size_t)npix * sizeof(vp_float4));
-        streams[r] = vp_get_stream();
+        vp_set_estimator(o.est);
+        must(vp_set_tracking(o.tracking) || vp_set_envmap_sampling(o.env_mode) || vp_set_shard(r, o.gpus));
+        vp_set_rng(o.philox == 2 ? VP_RNG_PHILOX7 : o.philox ? VP_RNG_PHILOX : VP_RNG_SAMPLERH, 0x9E3779B9u, 0x85EBCA6Bu);
+        must(vp_set_arithmetic(o.arith));
+        must(o.aa && vp_set_subpixel(o.aa));
+        // frame buffer (CudaFrameBuffer host.cpp:358-389)
+        must(!(run.accum[r] = (vp_float4*)vp_malloc((size_t)run.npix * sizeof(vp_float4))));
+        vp_memset(run.accum[r], 0, (size_t)run.npix * sizeof(vp_float4));
+        run.streams[r] = vp_get_stream();
     }
     free(h_volume);
-    volpath::NodeReducer reducer;
-    std::string          rerr;
-    if (!reducer.init(devices, rerr)) { fprintf(stderr, "%s\n", rerr.c_str()); return 1; }
-    if (gpus > 1) printf("multi-GPU reducer: %s\n", reducer.describe().c_str());
-    use(0);
-    vp_float4* disp = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-    if (!disp) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-    for (int r = 0; r < gpus; r++) { use(r); vp_synchronize(); vp_render_time_ms(nullptr, nullptr, 1); }
+    std::string rerr;
+    if (!run.reducer.init(j.devices, rerr)) { fprintf(stderr, "%s\n", rerr.c_str()); exit(1); }
+    if (o.gpus > 1) printf("multi-GPU reducer: %s\n", run.reducer.describe().c_str());
+    run.use(0);
+    run.disp = device_alloc<vp_float4>(run.npix, false);
+    for (int r = 0; r < o.gpus; r++) { run.use(r); vp_synchronize(); vp_render_time_ms(nullptr, nullptr, 1); }
+}
 
-    auto t0 = std::chrono::high_resolution_clock::now();
-    vp_dim3 block = {8, 8, 1}, grid = {(unsigned)(W + 7) / 8, (unsigned)(H + 7) / 8, 1};
-    bool    have_opacity = false;
-    vp_pixel_stats*    stats = nullptr;
-    vp_adaptive_result ares = {};
-    if (adaptive)
+// the plane table's buffers (more than one plane: one rank): accumulators zeroed (plane 0's is the rank's own), records zeroed where kept, means where formed
+static void alloc_planes(Job& j, const Run& run)
+{
+    for (int k = 0; k < j.n; k++)
     {
-        // rounds on the pixels that still need samples, --spp frames at most (vp_render_adaptive)
-        use(0);
-        stats = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
-        if (!stats || vp_memset(stats, 0, (size_t)npix * sizeof(vp_pixel_stats))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        if (est == VP_EST_DECOMP && spp > 11) precompute_opacity(&sky.sun_dir.x);   // host.cpp:336-343
-        const vp_adaptive ad = {noise_tol, noise_floor, min_spp, round_frames};
-        if (vp_render_adaptive(accum[0], stats, 0, spp, &P, &ad, &ares)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        Plane& p = j.plane[k];
+        p.acc = k ? device_alloc<vp_float4>(run.npix, true) : run.accum[0];
+        if (j.records) p.rec = device_alloc<vp_pixel_stats>(run.npix, true);
+        if (j.means) p.mean = device_alloc<vp_float4>(run.npix, false);
     }
-    if (denoise && !adaptive)
+}
+static void free_planes(Job& j)
+{
+    for (int k = 0; k < j.n; k++)
     {
-        // the filter needs the records: the frames go through vp_render_frames_stats (the same accumulator bits)
-        stats = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
-        if (!stats || vp_memset(stats, 0, (size_t)npix * sizeof(vp_pixel_stats))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
+        Plane& p = j.plane[k];
+        if (p.rec) vp_free(p.rec);
+        if (p.mean) vp_free(p.mean);
+        if (k) vp_free(p.acc);
     }
-    // --denoise-cross: accum[0] and `stats` are half 0's, these half 1's; the two filtered means
-    vp_float4*      half1 = nullptr;
-    vp_pixel_stats* half1_stats = nullptr;
-    vp_float4*      half_mean[2] = {nullptr, nullptr};
-    float*          d_resid = nullptr;   // --resid-out: the residual map, written with the merge
-    if (denoise_cross)
+}
+
+// frames s .. s + n - 1 by the mode's call on rank 0, with the records where the job keeps them (the same accumulator bits)
+static int render_frames(const Job& j, int s, int n)
+{
+    const Plane* p = j.plane;
+    const Param* P = &j.P;
+    switch (j.mode)
     {
-        half1       = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-        half1_stats = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
-        for (vp_float4*& m2 : half_mean) m2 = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-        if (!half1 || !half1_stats || !half_mean[0] || !half_mean[1] || vp_memset(half1, 0, (size_t)npix * sizeof(vp_float4)) ||
-            vp_memset(half1_stats, 0, (size_t)npix * sizeof(vp_pixel_stats)))
+    case PLANES:
+        return j.records ? vp_render_frames_group_layers_stats(p[0].acc, p[1].acc, p[2].acc, p[0].rec, p[1].rec, p[2].rec, s, n, P)
+                         : vp_render_frames_group_layers(p[0].acc, p[1].acc, p[2].acc, s, n, P);
+    case LAYERS: return j.records ? vp_render_frames_layers_stats(p[0].acc, p[1].acc, p[0].rec, p[1].rec, s, n, P) : vp_render_frames_layers(p[0].acc, p[1].acc, s, n, P);
+    case GROUPS: return j.records ? vp_render_frames_groups_stats(p[0].acc, p[1].acc, p[0].rec, p[1].rec, s, n, P) : vp_render_frames_groups(p[0].acc, p[1].acc, s, n, P);
+    default:     // --denoise: the filter needs the records; --denoise-cross: even and odd frames (blocks of frames) into the two halves
+        return j.n == 2 ? vp_render_frames_halves_stats(p[0].acc, p[1].acc, p[0].rec, p[1].rec, s, n, P) : vp_render_frames_stats(p[0].acc, p[0].rec, s, n, P);
+    }
+}
+// rounds on the pixels none of whose planes has met its tolerance, --spp frames at most
+static int render_adaptive(const Job& j, vp_adaptive_result* res)
+{
+    const Options& o = j.o;
+    const Plane*   p = j.plane;
+    switch (j.mode)
+    {
+    case PLANES:
+    {
+        const vp_adaptive_planes3 ap = {{j.tol[0], j.tol[1], j.tol[2]}, {p[0].floor, p[1].floor, p[2].floor}, o.min_spp, o.round_frames};
+        return vp_render_adaptive_group_layers(p[0].acc, p[1].acc, p[2].acc, p[0].rec, p[1].rec, p[2].rec, 0, o.spp, &j.P, &ap, res);
+    }
+    case LAYERS:
+    case GROUPS:
+    {
+        const vp_adaptive_planes ap = {{j.tol[0], j.tol[1]}, {p[0].floor, p[1].floor}, o.min_spp, o.round_frames};
+        return (j.mode == LAYERS ? vp_render_adaptive_layers : vp_render_adaptive_groups)(p[0].acc, p[1].acc, p[0].rec, p[1].rec, 0, o.spp, &j.P, &ap, res);
+    }
+    default:
+    {
+        const vp_adaptive ad = {j.tol[0], p[0].floor, o.min_spp, o.round_frames};
+        return vp_render_adaptive(p[0].acc, p[0].rec, 0, o.spp, &j.P, &ad, res);
+    }
+    }
+}
+
+static void render(const Job& j, Run& run)
+{
+    const Options& o = j.o;
+    const float*   sun_dir = &run.sky.sun_dir.x;
+    if (j.adaptive)
+    {
+        if (o.est == VP_EST_DECOMP && o.spp > 11) precompute_opacity(sun_dir);   // host.cpp:336-343
+        must(render_adaptive(j, &run.ares));
+        return;
+    }
+    const bool    own_call = j.mode != BEAUTY || j.records;   // planes or records: the mode's frames call, one rank
+    const vp_dim3 block = {8, 8, 1}, grid = {(unsigned)(o.W + 7) / 8, (unsigned)(o.H + 7) / 8, 1};
+    bool          have_opacity = false;
+    for (int s = 0; s < o.spp;)
+    {
+        if (!have_opacity && o.est == VP_EST_DECOMP && (s > 10 || (j.batch > 0 && s + j.batch > 11)))
         {
-            fprintf(stderr, "%s\n", vp_last_error());
-            return 1;
-        }
-    }
-    vp_float4* trans = nullptr;   // --layers-out / --over: accum[0] is the foreground accumulator, this the transmittance accumulator
-    // (--groups-out / --sun-gain / --sky-gain: accum[0] is the sun accumulator, this the sky accumulator)
-    // (--planes-out: accum[0] sun, this sky, trans3 the transmittance; stats3 and mean3 its records and its filtered mean)
-    vp_float4*      trans3 = nullptr;
-    vp_float4*      mean3  = nullptr;
-    vp_pixel_stats* stats3 = nullptr;
-    if (planes)
-    {
-        trans3 = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-        if (!trans3 || vp_memset(trans3, 0, (size_t)npix * sizeof(vp_float4))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        if (planes_denoise || planes_adaptive)
-        {
-            stats3 = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
-            mean3  = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-            if (!stats3 || !mean3 || vp_memset(stats3, 0, (size_t)npix * sizeof(vp_pixel_stats))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        }
-    }
-    if (layers || groups || planes)
-    {
-        trans = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-        if (!trans || vp_memset(trans, 0, (size_t)npix * sizeof(vp_float4))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-    }
-    // --groups-denoise / --layers-denoise / --plane-noise: one record buffer per plane (`stats` the first plane's), and the two means
-    vp_pixel_stats* stats2 = nullptr;
-    vp_float4*      mean[2] = {nullptr, nullptr};
-    const float     plane_floor[2] = {1e-3f, layers ? 1e-2f : 1e-3f};   // (trans lives in [0, 1])
-    if (plane_denoise || plane_adaptive || planes_denoise || planes_adaptive)
-    {
-        stats  = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
-        stats2 = (vp_pixel_stats*)vp_malloc((size_t)npix * sizeof(vp_pixel_stats));
-        for (vp_float4*& m2 : mean) m2 = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-        if (!stats || !stats2 || !mean[0] || !mean[1] || vp_memset(stats, 0, (size_t)npix * sizeof(vp_pixel_stats)) || vp_memset(stats2, 0, (size_t)npix * sizeof(vp_pixel_stats)))
-        {
-            fprintf(stderr, "%s\n", vp_last_error());
-            return 1;
-        }
-    }
-    if (plane_adaptive)
-    {
-        // rounds on the pixels neither of whose planes has met its tolerance, --spp frames at most
-        if (est == VP_EST_DECOMP && spp > 11) precompute_opacity(&sky.sun_dir.x);   // host.cpp:336-343
-        const vp_adaptive_planes ap = {{plane_tol[0], plane_tol[1]}, {plane_floor[0], plane_floor[1]}, min_spp, round_frames};
-        if ((layers ? vp_render_adaptive_layers : vp_render_adaptive_groups)(accum[0], trans, stats, stats2, 0, spp, &P, &ap, &ares))
-        {
-            fprintf(stderr, "%s\n", vp_last_error());
-            return 1;
-        }
-    }
-    if (planes_adaptive)
-    {
-        // rounds on the pixels none of whose three planes has met its tolerance, --spp frames at most
-        if (est == VP_EST_DECOMP && spp > 11) precompute_opacity(&sky.sun_dir.x);   // host.cpp:336-343
-        const vp_adaptive_planes3 ap = {{planes_tol[0], planes_tol[1], planes_tol[2]}, {planes_floor[0], planes_floor[1], planes_floor[2]}, min_spp, round_frames};
-        if (vp_render_adaptive_group_layers(accum[0], trans, trans3, stats, stats2, stats3, 0, spp, &P, &ap, &ares)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-    }
-    for (int s = adaptive || plane_adaptive || planes_adaptive ? spp : 0; s < spp;)
-    {
-        if (!have_opacity && est == VP_EST_DECOMP && (s > 10 || (batch > 0 && s + batch > 11)))
-        {
-            for (int r = 0; r < gpus; r++) { use(r); precompute_opacity(&sky.sun_dir.x); }  // host.cpp:336-343
+            for (int r = 0; r < o.gpus; r++) { run.use(r); precompute_opacity(sun_dir); }  // host.cpp:336-343
             have_opacity = true;
         }
-        if (planes)
-        {
-            const int n = batch > 0 ? std::min(batch, spp - s) : 1;
-            if (planes_denoise ? vp_render_frames_group_layers_stats(accum[0], trans, trans3, stats, stats2, stats3, s, n, &P)
-                               : vp_render_frames_group_layers(accum[0], trans, trans3, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-            s += n;
-        }
-        else if (layers)
-        {
-            const int n = batch > 0 ? std::min(batch, spp - s) : 1;
-            if (layers_denoise ? vp_render_frames_layers_stats(accum[0], trans, stats, stats2, s, n, &P) : vp_render_frames_layers(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-            s += n;
-        }
-        else if (groups)
-        {
-            const int n = batch > 0 ? std::min(batch, spp - s) : 1;
-            if (groups_denoise ? vp_render_frames_groups_stats(accum[0], trans, stats, stats2, s, n, &P) : vp_render_frames_groups(accum[0], trans, s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-            s += n;
-        }
-        else if (denoise)
-        {
-            const int n = batch > 0 ? std::min(batch, spp - s) : 1;
-            if (denoise_cross ? vp_render_frames_halves_stats(accum[0], half1, stats, half1_stats, s, n, &P) : vp_render_frames_stats(accum[0], stats, s, n, &P))
+        const int n = j.batch > 0 ? std::min(j.batch, o.spp - s) : 1;
+        if (own_call) must(render_frames(j, s, n));
+        else if (j.batch > 0)
+            for (int r = 0; r < o.gpus; r++)  // asynchronous: every rank's launch is queued before any is waited for
             {
-                fprintf(stderr, "%s\n", vp_last_error());
-                return 1;
+                run.use(r);
+                must(vp_render_frames(run.accum[r], s, n, &j.P));
             }
-            s += n;
-        }
-        else if (batch > 0)
-        {
-            int n = std::min(batch, spp - s);
-            for (int r = 0; r < gpus; r++)  // asynchronous: every rank's launch is queued before any is waited for
-            {
-                use(r);
-                if (vp_render_frames(accum[r], s, n, &P)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-            }
-            s += n;
-        }
         else
         {
-            use(0);
-            render_kernel(grid, block, accum[0], s, P);  // host.cpp:631
-            s += 1;
+            run.use(0);
+            render_kernel(grid, block, run.accum[0], s, j.P);  // host.cpp:631
         }
+        s += n;
     }
-    // ---- the one collective of the job: HDR accumulators -> rank 0
-    if (gpus > 1 && !reducer.reduce_to_root(ctx, accum, streams, (size_t)npix, rerr)) { fprintf(stderr, "%s\n", rerr.c_str()); return 1; }
-    for (int r = gpus - 1; r >= 0; r--) { use(r); vp_synchronize(); }
-    double sec = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    if (adaptive || plane_adaptive || planes_adaptive)
+}
+
+static void report(const Job& j, const Run& run, double sec)
+{
+    const Options& o = j.o;
+    if (j.adaptive)
     {
-        const double all = (double)W * H * spp;
+        const vp_adaptive_result& ares = run.ares;
+        const double all = (double)o.W * o.H * o.spp;
         char what[96];
-        if (adaptive) snprintf(what, sizeof what, "--noise %g", noise_tol);
-        else if (planes_adaptive) snprintf(what, sizeof what, "--planes-noise %g %g %g", planes_tol[0], planes_tol[1], planes_tol[2]);
-        else snprintf(what, sizeof what, "--plane-noise %g %g", plane_tol[0], plane_tol[1]);
+        int  len = snprintf(what, sizeof what, "%s", j.noise_flag);
+        for (int k = 0; k < j.n; k++) len += snprintf(what + len, sizeof what - len, " %g", j.tol[k]);
         printf("adaptive: %llu of %.0f samples (%.1f %%), %u rounds of %d frames, %u pixels still above %s after %u frames\n",
-               (unsigned long long)ares.samples, all, 100.0 * (double)ares.samples / all, ares.rounds, round_frames, ares.active_left, what, ares.frames_used);
-        printf("%f M samples / s, %d x %d, at most %d spp, %f s\n", (double)ares.samples / sec / 1e6, W, H, spp, sec);
+               (unsigned long long)ares.samples, all, 100.0 * (double)ares.samples / all, ares.rounds, o.round_frames, ares.active_left, what, ares.frames_used);
+        printf("%f M samples / s, %d x %d, at most %d spp, %f s\n", (double)ares.samples / sec / 1e6, o.W, o.H, o.spp, sec);
     }
-    else printf("%f M samples / s, %d x %d, %d spp, %f s\n", (double)W * H * spp / sec / 1e6, W, H, spp, sec);
-    if (gpus > 1)
+    else printf("%f M samples / s, %d x %d, %d spp, %f s\n", (double)o.W * o.H * o.spp / sec / 1e6, o.W, o.H, o.spp, sec);
+    if (o.gpus > 1)
     {
         double tmax = 0, tsum = 0;
-        printf("%d ranks (%s): kernel ms per rank", gpus, reducer.uses_rccl() ? "RCCL reduce" : "shared device, on-device sum");
-        for (int r = 0; r < gpus; r++)
+        printf("%d ranks (%s): kernel ms per rank", o.gpus, run.reducer.uses_rccl() ? "RCCL reduce" : "shared device, on-device sum");
+        for (int r = 0; r < o.gpus; r++)
         {
-            use(r);
+            run.use(r);
             double ms = 0; int nl = 0;
             vp_render_time_ms(&ms, &nl, 1);
             printf(" %.2f", ms);
             tmax = std::max(tmax, ms); tsum += ms;
         }
-        printf("; balance max/mean %.3f\n", tsum > 0 ? tmax / (tsum / gpus) : 1.0);
+        printf("; balance max/mean %.3f\n", tsum > 0 ? tmax / (tsum / o.gpus) : 1.0);
     }
+}
 
-    // ---- capture (host.cpp:585-610, :508-517) from rank 0
-    use(0);
-    bool  hdr = out.size() > 4 && out.substr(out.size() - 4) == ".hdr";
-    Image image(W, H);
-    if (planes)
+// ---- capture (host.cpp:585-610, :508-517) from rank 0
+static void write_image(const Job& j, const vp_float4* d_image, const std::string& name, bool hdr)
+{
+    Image image(j.o.W, j.o.H);
+    vp_download(image.buffer(), d_image, (size_t)j.o.W * j.o.H * sizeof(vp_float4));
+    if (hdr) image.dump_hdr(name.c_str());
+    else image.dump_ppm(name.c_str());
+    printf("wrote %s\n", name.c_str());
+}
+// a device map of one float per pixel, grey, as HDR
+static void write_grey_map(const Job& j, const float* d_map, const std::string& name)
+{
+    const int          npix = j.o.W * j.o.H;
+    std::vector<float> map((size_t)npix);
+    must(vp_download(map.data(), d_map, (size_t)npix * sizeof(float)));
+    Image im(j.o.W, j.o.H);
+    for (int k = 0; k < npix; k++) { float* px = im.buffer() + 4 * (size_t)k; px[0] = px[1] = px[2] = map[(size_t)k]; px[3] = 1.0f; }
+    im.dump_hdr(name.c_str());
+    printf("wrote %s\n", name.c_str());
+}
+
+// the beauty image's filter into disp: the division by each pixel's count is part of the call.  --denoise-features: the feature pass
+// first, then the filter with three of its channels (alpha.y, zt and the cover flag).  --denoise-cross: each half with the other as
+// guide, then the merge -- and, for --resid-out, the residual map, which is returned (the caller writes and frees it)
+static float* denoise_beauty(const Job& j, const Run& run)
+{
+    const Options& o = j.o;
+    const Plane*   p = j.plane;
+    const int      W = o.W, H = o.H, npix = run.npix;
+    vp_float4 *    d_alpha = nullptr, *d_depth = nullptr;
+    float*         d_resid = nullptr;
+    int            nf = 0;
+    if (o.denoise_features)
     {
-        // the three mean planes -- as they are, or each filtered with its own records as guide (a MEAN image: the division by the count
-        // is part of vp_denoise; w is never filtered) --, then their relit composite over --over's colour in place of the beauty image
-        // (--planes-noise without the filter: each plane by its own counts, sum / n per pixel, combined with scale 1)
-        const bool means = planes_denoise || planes_adaptive;
-        vp_float4* const       acc3[3] = {accum[0], trans, trans3};
-        vp_float4* const       mean_of[3] = {mean[0], mean[1], mean3};
-        vp_pixel_stats* const  rec3[3] = {stats, stats2, stats3};
-        static const char* const suffix[3] = {"_sun.hdr", "_sky.hdr", "_trans.hdr"};
-        for (int k = 0; k < 3; k++)
-        {
-            if (planes_denoise) { if (vp_denoise(mean_of[k], acc3[k], rec3[k], nullptr, nullptr, W, H, &dn)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; } }
-            else if (planes_adaptive) { if (vp_scale_by_count(mean_of[k], acc3[k], rec3[k], npix, 1.0f)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; } }
-            else scale(disp, acc3[k], npix, 1.0f / spp);
-            const std::string name = planes_out + suffix[k];
-            vp_download(image.buffer(), means ? mean_of[k] : disp, (size_t)npix * sizeof(vp_float4));
-            image.dump_hdr(name.c_str());
-            printf("wrote %s\n", name.c_str());
-        }
-        if (means ? vp_relight_composite(disp, mean_of[0], mean_of[1], mean_of[2], sun_gain, sky_gain, nullptr, over_rgb, npix, 1.0f)
-                  : vp_relight_composite(disp, accum[0], trans, trans3, sun_gain, sky_gain, nullptr, over_rgb, npix, 1.0f / spp))
-        {
-            fprintf(stderr, "%s\n", vp_last_error());
-            return 1;
-        }
-        if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
-        if (planes_denoise) printf("denoised per plane: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
+        d_alpha = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+        d_depth = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+        must(!d_alpha || !d_depth || vp_render_features(d_alpha, d_depth, &j.P, &o.feat));
+        nf = 3;
     }
-    else if (plane_denoise || plane_adaptive)
+    const vp_denoise_feature f3[3] = {{d_alpha, 1, o.dn_sigma_alpha}, {d_depth, 1, o.dn_sigma_depth}, {d_depth, 3, o.dn_sigma_alpha}};
+    const vp_denoise_feature* f = nf ? f3 : nullptr;
+    if (j.n == 2)
     {
-        // each plane filtered with its own records as guide: two MEAN images (the division by the count is part of vp_denoise; w is
-        // never filtered), written in place of the raw means and combined with scale 1
-        // (--plane-noise without the filter: each plane by its own counts, sum / n per pixel)
-        const bool        lay = layers;
-        const std::string prefix = lay ? layers_out : groups_out;
-        for (int k = 0; k < 2; k++)
-        {
-            if (plane_denoise ? vp_denoise(mean[k], k ? trans : accum[0], k ? stats2 : stats, nullptr, nullptr, W, H, &dn)
-                              : vp_scale_by_count(mean[k], k ? trans : accum[0], k ? stats2 : stats, npix, 1.0f))
-            {
-                fprintf(stderr, "%s\n", vp_last_error());
-                return 1;
-            }
-            if (prefix.empty()) continue;
-            const std::string name = prefix + (lay ? (k ? "_trans.hdr" : "_fg.hdr") : (k ? "_sky.hdr" : "_sun.hdr"));
-            vp_download(image.buffer(), mean[k], (size_t)npix * sizeof(vp_float4));
-            image.dump_hdr(name.c_str());
-            printf("wrote %s\n", name.c_str());
-        }
-        if (lay ? (over && vp_composite(disp, mean[0], mean[1], nullptr, over_rgb, npix, 1.0f)) : vp_relight(disp, mean[0], mean[1], sun_gain, sky_gain, npix, 1.0f))
-        {
-            fprintf(stderr, "%s\n", vp_last_error());
-            return 1;
-        }
-        if (!hdr && (!lay || over)) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
-        if (plane_denoise) printf("denoised per plane: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
+        must(!o.resid_out.empty() && !(d_resid = (float*)vp_malloc((size_t)npix * sizeof(float))));
+        must(vp_denoise_guided(p[0].mean, p[0].acc, p[0].rec, p[1].acc, p[1].rec, f, nf, W, H, &o.dn) ||
+             vp_denoise_guided(p[1].mean, p[1].acc, p[1].rec, p[0].acc, p[0].rec, f, nf, W, H, &o.dn) ||
+             vp_merge_halves(run.disp, d_resid, p[0].mean, p[0].rec, p[1].mean, p[1].rec, npix, p[0].floor));
     }
-    else if (layers)
+    else must(nf ? vp_denoise_guided(run.disp, p[0].acc, p[0].rec, nullptr, nullptr, f, nf, W, H, &o.dn) : vp_denoise(run.disp, p[0].acc, p[0].rec, nullptr, nullptr, W, H, &o.dn));
+    if (o.denoise_features)
     {
-        // the two mean layers as they are; the composite over --over's colour in place of the beauty image
-        if (!layers_out.empty())
-            for (int k = 0; k < 2; k++)
-            {
-                const std::string name = layers_out + (k ? "_trans.hdr" : "_fg.hdr");
-                scale(disp, k ? trans : accum[0], npix, 1.0f / spp);
-                vp_download(image.buffer(), disp, (size_t)npix * sizeof(vp_float4));
-                image.dump_hdr(name.c_str());
-                printf("wrote %s\n", name.c_str());
-            }
-        if (over)
-        {
-            if (vp_composite(disp, accum[0], trans, nullptr, over_rgb, npix, 1.0f / spp)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-            if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
-        }
-    }
-    else if (groups)
-    {
-        // the two mean groups as they are; their weighted sum in place of the beauty image
-        if (!groups_out.empty())
-            for (int k = 0; k < 2; k++)
-            {
-                const std::string name = groups_out + (k ? "_sky.hdr" : "_sun.hdr");
-                scale(disp, k ? trans : accum[0], npix, 1.0f / spp);
-                vp_download(image.buffer(), disp, (size_t)npix * sizeof(vp_float4));
-                image.dump_hdr(name.c_str());
-                printf("wrote %s\n", name.c_str());
-            }
-        if (vp_relight(disp, accum[0], trans, sun_gain, sky_gain, npix, 1.0f / spp)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
-    }
-    else if (denoise)
-    {
-        // the filtered mean image: the division by each pixel's count is part of the call
-        // (--denoise-cross: each half with the other as guide, then the merge -- and the residual map, kept in d_resid for --resid-out)
-        auto filter = [&](const vp_denoise_feature* f, int nf) -> int {
-            if (!denoise_cross) return nf ? vp_denoise_guided(disp, accum[0], stats, nullptr, nullptr, f, nf, W, H, &dn) : vp_denoise(disp, accum[0], stats, nullptr, nullptr, W, H, &dn);
-            if (!resid_out.empty() && !(d_resid = (float*)vp_malloc((size_t)npix * sizeof(float)))) return 1;
-            return vp_denoise_guided(half_mean[0], accum[0], stats, half1, half1_stats, f, nf, W, H, &dn) ||
-                   vp_denoise_guided(half_mean[1], half1, half1_stats, accum[0], stats, f, nf, W, H, &dn) ||
-                   vp_merge_halves(disp, d_resid, half_mean[0], stats, half_mean[1], half1_stats, npix, noise_floor);
-        };
-        if (denoise_features)
-        {
-            // the feature pass first, then the filter with three of its channels: alpha.y, zt and the cover flag
-            vp_float4* d_alpha = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-            vp_float4* d_depth = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-            const vp_denoise_feature f3[3] = {{d_alpha, 1, dn_sigma_alpha}, {d_depth, 1, dn_sigma_depth}, {d_depth, 3, dn_sigma_alpha}};
-            if (!d_alpha || !d_depth || vp_render_features(d_alpha, d_depth, &P, &feat) || filter(f3, 3)
-                || vp_synchronize())
-            {
-                fprintf(stderr, "%s\n", vp_last_error());
-                return 1;
-            }
-            vp_free(d_alpha);
-            vp_free(d_depth);
-        }
-        else if (filter(nullptr, 0)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
-        printf("denoised: radius %d, patch %d, k %g\n", dn.radius, dn.patch, dn.k);
-        if (denoise_cross) printf("  cross-filtered: two half-buffers, each with the other's weights, merged by their counts\n");
-        if (denoise_features) printf("  weights cut by features: sigma alpha %g, sigma depth %g\n", dn_sigma_alpha, dn_sigma_depth);
-    }
-    else if (adaptive)
-    {
-        // every pixel by its own count (the reference's scale assumes one count for all)
-        if (vp_scale_by_count(disp, accum[0], stats, npix, 1.0f)) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        if (!hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
-    }
-    else if (hdr) scale(disp, accum[0], npix, 1.0f / spp);
-    else gamma_correct(disp, accum[0], npix, 1.0f / spp, 2.2f);
-    if (!layers || over)
-    {
-        vp_download(image.buffer(), disp, (size_t)npix * sizeof(vp_float4));
-        if (hdr) image.dump_hdr(out.c_str());
-        else image.dump_ppm(out.c_str());
-        printf("wrote %s\n", out.c_str());
-    }
-    if (d_resid)
-    {
-        // the residual map of the cross-filter, grey, as HDR
-        std::vector<float> resid((size_t)npix);
-        if (vp_download(resid.data(), d_resid, (size_t)npix * sizeof(float))) { fprintf(stderr, "%s\n", vp_last_error()); return 1; }
-        Image rm(W, H);
-        for (int k = 0; k < npix; k++) { float* px = rm.buffer() + 4 * (size_t)k; px[0] = px[1] = px[2] = resid[(size_t)k]; px[3] = 1.0f; }
-        rm.dump_hdr(resid_out.c_str());
-        printf("wrote %s\n", resid_out.c_str());
-        vp_free(d_resid);
-    }
-    if (adaptive && !noise_out.empty())
-    {
-        // the noise map: estimated standard error of the mean luminance over max(mean, floor), grey, as HDR
-        float* d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
-        std::vector<float> noise((size_t)npix);
-        if (!d_noise || vp_stats_rel_error(d_noise, stats, npix, noise_floor) || vp_download(noise.data(), d_noise, (size_t)npix * sizeof(float)))
-        {
-            fprintf(stderr, "%s\n", vp_last_error());
-            return 1;
-        }
-        Image nm(W, H);
-        for (int k = 0; k < npix; k++) { float* px = nm.buffer() + 4 * (size_t)k; px[0] = px[1] = px[2] = noise[(size_t)k]; px[3] = 1.0f; }
-        nm.dump_hdr(noise_out.c_str());
-        printf("wrote %s\n", noise_out.c_str());
-        vp_free(d_noise);
-    }
-    if (plane_adaptive && !plane_noise_out.empty())
-        for (int k = 0; k < 2; k++)
-        {
-            // one noise map per plane, each with its plane's floor
-            const std::string name = plane_noise_out + (layers ? (k ? "_trans.hdr" : "_fg.hdr") : (k ? "_sky.hdr" : "_sun.hdr"));
-            float* d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
-            std::vector<float> noise((size_t)npix);
-            if (!d_noise || vp_stats_rel_error(d_noise, k ? stats2 : stats, npix, plane_floor[k]) || vp_download(noise.data(), d_noise, (size_t)npix * sizeof(float)))
-            {
-                fprintf(stderr, "%s\n", vp_last_error());
-                return 1;
-            }
-            Image nm(W, H);
-            for (int q = 0; q < npix; q++) { float* px = nm.buffer() + 4 * (size_t)q; px[0] = px[1] = px[2] = noise[(size_t)q]; px[3] = 1.0f; }
-            nm.dump_hdr(name.c_str());
-            printf("wrote %s\n", name.c_str());
-            vp_free(d_noise);
-        }
-    if (planes_adaptive && !planes_noise_out.empty())
-        for (int k = 0; k < 3; k++)
-        {
-            // one noise map per plane, each with its plane's floor
-            static const char* const suffix[3] = {"_sun.hdr", "_sky.hdr", "_trans.hdr"};
-            vp_pixel_stats* const    rec3[3] = {stats, stats2, stats3};
-            const std::string name = planes_noise_out + suffix[k];
-            float* d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
-            std::vector<float> noise((size_t)npix);
-            if (!d_noise || vp_stats_rel_error(d_noise, rec3[k], npix, planes_floor[k]) || vp_download(noise.data(), d_noise, (size_t)npix * sizeof(float)))
-            {
-                fprintf(stderr, "%s\n", vp_last_error());
-                return 1;
-            }
-            Image nm(W, H);
-            for (int q = 0; q < npix; q++) { float* px = nm.buffer() + 4 * (size_t)q; px[0] = px[1] = px[2] = noise[(size_t)q]; px[3] = 1.0f; }
-            nm.dump_hdr(name.c_str());
-            printf("wrote %s\n", name.c_str());
-            vp_free(d_noise);
-        }
-    if (!features_out.empty())
-    {
-        // the feature pass: a pass of its own behind the render, on rank 0 over the whole image, one camera ray per pixel
-        vp_float4* d_alpha = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-        vp_float4* d_depth = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
-        if (!d_alpha || !d_depth || vp_set_shard(0, 1) || vp_set_subpixel(1) || vp_render_features(d_alpha, d_depth, &P, &feat) || vp_synchronize())
-        {
-            fprintf(stderr, "%s\n", vp_last_error());
-            return 1;
-        }
-        for (int k = 0; k < 2; k++)
-        {
-            const std::string name = features_out + (k ? "_depth.hdr" : "_alpha.hdr");
-            Image fi(W, H);
-            vp_download(fi.buffer(), k ? d_depth : d_alpha, (size_t)npix * sizeof(vp_float4));
-            if (k)   // RGBE has no inf: a depth that does not exist is written as 0
-                for (size_t q = 0; q < (size_t)npix * 4; q++) if (std::isinf(fi.buffer()[q])) fi.buffer()[q] = 0.0f;
-            fi.dump_hdr(name.c_str());
-            printf("wrote %s\n", name.c_str());
-        }
+        must(vp_synchronize());
         vp_free(d_alpha);
         vp_free(d_depth);
     }
-    if (stats) vp_free(stats);
-    if (stats2) vp_free(stats2);
-    if (stats3) vp_free(stats3);
-    if (mean3) vp_free(mean3);
-    if (trans3) vp_free(trans3);
-    for (vp_float4* m2 : mean) if (m2) vp_free(m2);
-    if (trans) vp_free(trans);
-    if (half1) vp_free(half1);
-    if (half1_stats) vp_free(half1_stats);
-    for (vp_float4* m2 : half_mean) if (m2) vp_free(m2);
-    vp_free(disp);
-    for (int r = 0; r < gpus; r++)
+    printf("denoised: radius %d, patch %d, k %g\n", o.dn.radius, o.dn.patch, o.dn.k);
+    if (o.denoise_cross) printf("  cross-filtered: two half-buffers, each with the other's weights, merged by their counts\n");
+    if (o.denoise_features) printf("  weights cut by features: sigma alpha %g, sigma depth %g\n", o.dn_sigma_alpha, o.dn_sigma_depth);
+    return d_resid;
+}
+
+// the feature pass: a pass of its own behind the render, on rank 0 over the whole image, one camera ray per pixel
+static void write_features(const Job& j, const Run& run)
+{
+    const Options& o = j.o;
+    const int      npix = run.npix;
+    vp_float4*     d_alpha = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+    vp_float4*     d_depth = (vp_float4*)vp_malloc((size_t)npix * sizeof(vp_float4));
+    must(!d_alpha || !d_depth || vp_set_shard(0, 1) || vp_set_subpixel(1) || vp_render_features(d_alpha, d_depth, &j.P, &o.feat) || vp_synchronize());
+    for (int k = 0; k < 2; k++)
     {
-        use(r);
-        vp_free(accum[r]);
+        const std::string name = o.features_out + (k ? "_depth.hdr" : "_alpha.hdr");
+        Image fi(o.W, o.H);
+        vp_download(fi.buffer(), k ? d_depth : d_alpha, (size_t)npix * sizeof(vp_float4));
+        if (k)   // RGBE has no inf: a depth that does not exist is written as 0
+            for (size_t q = 0; q < (size_t)npix * 4; q++) if (std::isinf(fi.buffer()[q])) fi.buffer()[q] = 0.0f;
+        fi.dump_hdr(name.c_str());
+        printf("wrote %s\n", name.c_str());
+    }
+    vp_free(d_alpha);
+    vp_free(d_depth);
+}
+
+static void write_outputs(const Job& j, const Run& run)
+{
+    const Options& o = j.o;
+    const Plane*   p = j.plane;
+    const int      W = o.W, H = o.H, npix = run.npix;
+    vp_float4*     disp = run.disp;
+    const float    per_frame = 1.0f / o.spp;
+    float*         d_resid = nullptr;
+    bool           linear = true;   // disp holds the linear image: gamma follows unless --out is HDR
+    run.use(0);
+    if (j.mode != BEAUTY)
+    {
+        // the mean of each plane -- by the filter with the plane's own records as guide (a MEAN image: the division by the count is part of
+        // vp_denoise; w is never filtered), by the pixels' own counts after adaptive rounds, or by the one count of all --, written where a
+        // prefix is given; then the planes' combination in place of the beauty image, the means with scale 1
+        const vp_float4* m[3] = {};
+        for (int k = 0; k < j.n; k++)
+        {
+            if (j.filter) must(vp_denoise(p[k].mean, p[k].acc, p[k].rec, nullptr, nullptr, W, H, &o.dn));
+            else if (j.adaptive) must(vp_scale_by_count(p[k].mean, p[k].acc, p[k].rec, npix, 1.0f));
+            else if (!j.prefix.empty()) scale(disp, p[k].acc, npix, per_frame);
+            m[k] = j.means ? p[k].mean : p[k].acc;
+            if (!j.prefix.empty()) write_image(j, j.means ? p[k].mean : disp, j.prefix + p[k].suffix, true);
+        }
+        const float s = j.means ? 1.0f : per_frame;
+        if (j.mode == PLANES) must(vp_relight_composite(disp, m[0], m[1], m[2], o.sun_gain, o.sky_gain, nullptr, o.over_rgb, npix, s));
+        else if (j.mode == GROUPS) must(vp_relight(disp, m[0], m[1], o.sun_gain, o.sky_gain, npix, s));
+        else if (o.over) must(vp_composite(disp, m[0], m[1], nullptr, o.over_rgb, npix, s));
+        if (j.filter) printf("denoised per plane: radius %d, patch %d, k %g\n", o.dn.radius, o.dn.patch, o.dn.k);
+    }
+    else if (j.filter) d_resid = denoise_beauty(j, run);
+    else if (j.adaptive) must(vp_scale_by_count(disp, p[0].acc, p[0].rec, npix, 1.0f));   // every pixel by its own count (the reference's scale assumes one count for all)
+    else if (j.hdr) scale(disp, p[0].acc, npix, per_frame);
+    else { gamma_correct(disp, p[0].acc, npix, per_frame, 2.2f); linear = false; }   // (the reference's one call for both)
+    if (j.mode != LAYERS || o.over)   // layers without --over: the context's own sky is in neither layer, no image
+    {
+        if (linear && !j.hdr) gamma_correct(disp, disp, npix, 1.0f, 2.2f);
+        write_image(j, disp, o.out, j.hdr);
+    }
+    if (d_resid)
+    {
+        write_grey_map(j, d_resid, o.resid_out);
+        vp_free(d_resid);
+    }
+    // the noise maps: estimated standard error of the mean luminance over max(mean, floor), one per plane, each with its plane's floor
+    for (int k = 0; k < j.n && j.adaptive && !j.noise_prefix.empty(); k++)
+    {
+        float* d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
+        must(!d_noise || vp_stats_rel_error(d_noise, p[k].rec, npix, p[k].floor));
+        write_grey_map(j, d_noise, j.noise_prefix + p[k].suffix);
+        vp_free(d_noise);
+    }
+    if (!o.features_out.empty()) write_features(j, run);
+}
+
+// the buffers first, then each rank's scene, the reducer's communicators (their collectives ran on the contexts' streams), the contexts
+static void tear_down(Job& j, Run& run)
+{
+    free_planes(j);
+    vp_free(run.disp);
+    for (int r = 0; r < run.gpus; r++)
+    {
+        run.use(r);
+        vp_free(run.accum[r]);
         free_cuda_buffers();
         free_envmap();
     }
-    reducer.shutdown();   // communicators first: their collectives ran on the contexts' streams
-    if (gpus > 1) { vp_ctx_set_current(nullptr); for (auto c : ctx) vp_ctx_destroy(c); }
+    run.reducer.shutdown();
+    if (run.gpus > 1) { vp_ctx_set_current(nullptr); for (auto c : run.ctx) vp_ctx_destroy(c); }
+}
+
+int main(int argc, char** argv)
+{
+    Options o;
+    o.parse(argc, argv);
+    Job job = validate(o);
+    Run run;
+    set_up(job, run);
+
+    auto t0 = std::chrono::high_resolution_clock::now();
+    alloc_planes(job, run);
+    render(job, run);
+    // ---- the one collective of the job: HDR accumulators -> rank 0
+    std::string rerr;
+    if (o.gpus > 1 && !run.reducer.reduce_to_root(run.ctx, run.accum, run.streams, (size_t)run.npix, rerr)) { fprintf(stderr, "%s\n", rerr.c_str()); return 1; }
+    for (int r = o.gpus - 1; r >= 0; r--) { run.use(r); vp_synchronize(); }
+    double sec = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+
+    report(job, run, sec);
+    write_outputs(job, run);
+    tear_down(job, run);
     return 0;
 }
