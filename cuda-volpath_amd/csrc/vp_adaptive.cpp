@@ -6,6 +6,7 @@
 // frozen in neither plane's record, and a round freezes both records of a pixel when both meet their plane's criterion.
 // vp_render_adaptive_group_layers: the same on the three planes of a group-layers render, with three records per pixel.
 // vp_denoise: the filter of the output stage that reads the records (vp_denoise.hip); vp_denoise_guided: the same with feature planes.
+// vp_halves_variance, vp_filter_variance, vp_denoise_var: the variance stage of the cross-filter.
 #include <climits>
 
 #include "vp_state.h"
@@ -96,6 +97,50 @@ static int render_adaptive_planes(const char* fn, PlaneSet S, int first_frame, i
     S.adaptive = true; S.min_frames = (unsigned)a.min_frames;
     for (int k = 0; k < S.n(); k++) { S.tol[k] = (double)a.rel_tol[k]; S.fl[k] = (double)a.floor_y[k]; }
     return adaptive_rounds(S, first_frame, max_frames, a.round_frames, p, result);
+}
+// what the filter calls refuse alike, in the definition's order; fn is the call's name in the message
+static int denoise_params_check(const char* fn, int width, int height, const vp_denoise_params* dp)
+{
+    if (width < 1 || height < 1 || (long long)width * height > INT_MAX) return fail(VP_E_ARG, "%s: image %d x %d", fn, width, height);
+    if (dp->radius < 0 || dp->radius > VP_DENOISE_MAX_RADIUS) return fail(VP_E_ARG, "%s: radius %d outside 0..%d", fn, dp->radius, VP_DENOISE_MAX_RADIUS);
+    if (dp->patch < 0 || dp->patch > VP_DENOISE_MAX_PATCH) return fail(VP_E_ARG, "%s: patch %d outside 0..%d", fn, dp->patch, VP_DENOISE_MAX_PATCH);
+    if (!std::isfinite(dp->k) || !(dp->k > 0.0f)) return fail(VP_E_ARG, "%s: k must be a finite number > 0", fn);
+    return VP_OK;
+}
+static int denoise_args_check(const char* fn, const vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide,
+                              const vp_pixel_stats* d_guide_stats, int width, int height, const vp_denoise_params* dp)
+{
+    if (!dst || !src || !d_stats || !dp) return fail(VP_E_ARG, "%s: null pointer", fn);
+    if (!guide != !d_guide_stats) return fail(VP_E_ARG, "%s: guide and d_guide_stats are given together or not at all", fn);
+    if (dst == src || dst == guide) return fail(VP_E_ARG, "%s: in place is not possible (the call reads neighbours)", fn);
+    return denoise_params_check(fn, width, height, dp);
+}
+// the feature list of a call into what the kernels take: each channel's address and g = 1 / (2 sigma^2) as the host rounds it
+static int denoise_features_check(const char* fn, const vp_float4* dst, const vp_denoise_feature* features, int n_features, DenoiseFeaturesDev& fd)
+{
+    if (n_features < 0 || n_features > VP_DENOISE_MAX_FEATURES) return fail(VP_E_ARG, "%s: %d features outside 0..%d", fn, n_features, VP_DENOISE_MAX_FEATURES);
+    if (n_features > 0 && !features) return fail(VP_E_ARG, "%s: %d features and no array of them", fn, n_features);
+    for (int j = 0; j < n_features; j++)
+    {
+        const vp_denoise_feature& f = features[j];
+        if (!f.plane) return fail(VP_E_ARG, "%s: feature %d has no plane", fn, j);
+        if (f.plane == dst) return fail(VP_E_ARG, "%s: feature %d is dst (the call reads neighbours)", fn, j);
+        if (f.channel < 0 || f.channel > 3) return fail(VP_E_ARG, "%s: feature %d: channel %d outside 0..3", fn, j, f.channel);
+        if (!std::isfinite(f.sigma) || !(f.sigma > 0.0f)) return fail(VP_E_ARG, "%s: feature %d: sigma must be a finite number > 0", fn, j);
+        const float g = 1.0f / ((2.0f * f.sigma) * f.sigma);
+        if (!std::isfinite(g) || !(g > 0.0f)) return fail(VP_E_ARG, "%s: feature %d: 1 / (2 sigma^2) of sigma %g is not a finite number > 0", fn, j, (double)f.sigma);
+        fd.chan[j] = (const float*)f.plane + f.channel;
+        fd.g[j] = g;
+    }
+    fd.n = n_features;
+    return VP_OK;
+}
+static int denoise_lds_check(const char* fn, const vp_denoise_params* dp, int n_features)
+{
+    if (G.denoise_form == 0 && denoise_guided_lds_bytes(dp->radius, dp->patch, n_features) > DENOISE_LDS_LIMIT)
+        return fail(VP_E_STATE, "%s: radius %d, patch %d, %d features need %zu bytes of LDS, a workgroup has %zu", fn, dp->radius, dp->patch, n_features,
+                    denoise_guided_lds_bytes(dp->radius, dp->patch, n_features), DENOISE_LDS_LIMIT);
+    return VP_OK;
 }
 }  // namespace vph
 
@@ -189,15 +234,9 @@ int vp_accumulate_stats(vp_pixel_stats* dst, const vp_pixel_stats* src, size_t n
 int vp_denoise(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
                int width, int height, const vp_denoise_params* dp)
 {
-    if (!dst || !src || !d_stats || !dp) return fail(VP_E_ARG, "vp_denoise: null pointer");
-    if (!guide != !d_guide_stats) return fail(VP_E_ARG, "vp_denoise: guide and d_guide_stats are given together or not at all");
-    if (dst == src || dst == guide) return fail(VP_E_ARG, "vp_denoise: in place is not possible (the call reads neighbours)");
-    if (width < 1 || height < 1 || (long long)width * height > INT_MAX) return fail(VP_E_ARG, "vp_denoise: image %d x %d", width, height);
-    if (dp->radius < 0 || dp->radius > VP_DENOISE_MAX_RADIUS) return fail(VP_E_ARG, "vp_denoise: radius %d outside 0..%d", dp->radius, VP_DENOISE_MAX_RADIUS);
-    if (dp->patch < 0 || dp->patch > VP_DENOISE_MAX_PATCH) return fail(VP_E_ARG, "vp_denoise: patch %d outside 0..%d", dp->patch, VP_DENOISE_MAX_PATCH);
-    if (!std::isfinite(dp->k) || !(dp->k > 0.0f)) return fail(VP_E_ARG, "vp_denoise: k must be a finite number > 0");
-    int rc = ensure_device();
+    int rc = denoise_args_check("vp_denoise", dst, src, d_stats, guide, d_guide_stats, width, height, dp);
     if (rc) return rc;
+    if ((rc = ensure_device())) return rc;
     if (!guide) { guide = src; d_guide_stats = d_stats; }
     launch_denoise((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, width, height,
                    dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
@@ -208,39 +247,56 @@ int vp_denoise(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_sta
 int vp_denoise_guided(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
                       const vp_denoise_feature* features, int n_features, int width, int height, const vp_denoise_params* dp)
 {
-    if (n_features < 0 || n_features > VP_DENOISE_MAX_FEATURES)
-        return fail(VP_E_ARG, "vp_denoise_guided: %d features outside 0..%d", n_features, VP_DENOISE_MAX_FEATURES);
-    if (n_features > 0 && !features) return fail(VP_E_ARG, "vp_denoise_guided: %d features and no array of them", n_features);
     DenoiseFeaturesDev fd = {};
-    for (int j = 0; j < n_features; j++)
-    {
-        const vp_denoise_feature& f = features[j];
-        if (!f.plane) return fail(VP_E_ARG, "vp_denoise_guided: feature %d has no plane", j);
-        if (f.plane == dst) return fail(VP_E_ARG, "vp_denoise_guided: feature %d is dst (the call reads neighbours)", j);
-        if (f.channel < 0 || f.channel > 3) return fail(VP_E_ARG, "vp_denoise_guided: feature %d: channel %d outside 0..3", j, f.channel);
-        if (!std::isfinite(f.sigma) || !(f.sigma > 0.0f)) return fail(VP_E_ARG, "vp_denoise_guided: feature %d: sigma must be a finite number > 0", j);
-        const float g = 1.0f / ((2.0f * f.sigma) * f.sigma);
-        if (!std::isfinite(g) || !(g > 0.0f)) return fail(VP_E_ARG, "vp_denoise_guided: feature %d: 1 / (2 sigma^2) of sigma %g is not a finite number > 0", j, (double)f.sigma);
-        fd.chan[j] = (const float*)f.plane + f.channel;
-        fd.g[j] = g;
-    }
-    fd.n = n_features;
-    if (n_features == 0) return vp_denoise(dst, src, d_stats, guide, d_guide_stats, width, height, dp);
-    if (!dst || !src || !d_stats || !dp) return fail(VP_E_ARG, "vp_denoise_guided: null pointer");
-    if (!guide != !d_guide_stats) return fail(VP_E_ARG, "vp_denoise_guided: guide and d_guide_stats are given together or not at all");
-    if (dst == src || dst == guide) return fail(VP_E_ARG, "vp_denoise_guided: in place is not possible (the call reads neighbours)");
-    if (width < 1 || height < 1 || (long long)width * height > INT_MAX) return fail(VP_E_ARG, "vp_denoise_guided: image %d x %d", width, height);
-    if (dp->radius < 0 || dp->radius > VP_DENOISE_MAX_RADIUS) return fail(VP_E_ARG, "vp_denoise_guided: radius %d outside 0..%d", dp->radius, VP_DENOISE_MAX_RADIUS);
-    if (dp->patch < 0 || dp->patch > VP_DENOISE_MAX_PATCH) return fail(VP_E_ARG, "vp_denoise_guided: patch %d outside 0..%d", dp->patch, VP_DENOISE_MAX_PATCH);
-    if (!std::isfinite(dp->k) || !(dp->k > 0.0f)) return fail(VP_E_ARG, "vp_denoise_guided: k must be a finite number > 0");
-    if (G.denoise_form == 0 && denoise_guided_lds_bytes(dp->radius, dp->patch, n_features) > DENOISE_LDS_LIMIT)
-        return fail(VP_E_STATE, "vp_denoise_guided: radius %d, patch %d, %d features need %zu bytes of LDS, a workgroup has %zu", dp->radius, dp->patch, n_features,
-                    denoise_guided_lds_bytes(dp->radius, dp->patch, n_features), DENOISE_LDS_LIMIT);
-    int rc = ensure_device();
+    int rc = denoise_features_check("vp_denoise_guided", dst, features, n_features, fd);
     if (rc) return rc;
+    if (n_features == 0) return vp_denoise(dst, src, d_stats, guide, d_guide_stats, width, height, dp);
+    if ((rc = denoise_args_check("vp_denoise_guided", dst, src, d_stats, guide, d_guide_stats, width, height, dp))) return rc;
+    if ((rc = denoise_lds_check("vp_denoise_guided", dp, n_features))) return rc;
+    if ((rc = ensure_device())) return rc;
     if (!guide) { guide = src; d_guide_stats = d_stats; }
     launch_denoise_guided((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, fd, width,
                           height, dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
+    HIPCHK(hipGetLastError());
+    G.last_denoise_form = G.denoise_form;
+    return VP_OK;
+}
+int vp_denoise_var(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
+                   const float* d_sample_var, const vp_denoise_feature* features, int n_features, int width, int height, const vp_denoise_params* dp)
+{
+    if (!d_sample_var) return vp_denoise_guided(dst, src, d_stats, guide, d_guide_stats, features, n_features, width, height, dp);
+    DenoiseFeaturesDev fd = {};
+    int rc = denoise_features_check("vp_denoise_var", dst, features, n_features, fd);
+    if (rc) return rc;
+    if ((rc = denoise_args_check("vp_denoise_var", dst, src, d_stats, guide, d_guide_stats, width, height, dp))) return rc;
+    if ((const void*)d_sample_var == (const void*)dst) return fail(VP_E_ARG, "vp_denoise_var: d_sample_var is dst (the call reads neighbours)");
+    if ((rc = denoise_lds_check("vp_denoise_var", dp, n_features))) return rc;
+    if ((rc = ensure_device())) return rc;
+    if (!guide) { guide = src; d_guide_stats = d_stats; }
+    launch_denoise_var((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, d_sample_var, fd,
+                       width, height, dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
+    HIPCHK(hipGetLastError());
+    G.last_denoise_form = G.denoise_form;
+    return VP_OK;
+}
+int vp_halves_variance(float* d_u, float* d_q, const vp_pixel_stats* a_stats, const vp_pixel_stats* b_stats, int size)
+{
+    if (!d_u || !a_stats || !b_stats) return fail(VP_E_ARG, "vp_halves_variance: null pointer");
+    if (size < 0) return fail(VP_E_ARG, "vp_halves_variance: size %d", size);
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (size) launch_halves_variance(d_u, d_q, (const PixelStatsDev*)a_stats, (const PixelStatsDev*)b_stats, size, G.stream);
+    HIPCHK(hipGetLastError());
+    return VP_OK;
+}
+int vp_filter_variance(float* dst, const float* u, const float* q, int width, int height, const vp_denoise_params* vp)
+{
+    if (!dst || !u || !q || !vp) return fail(VP_E_ARG, "vp_filter_variance: null pointer");
+    if (dst == u || dst == q) return fail(VP_E_ARG, "vp_filter_variance: in place is not possible (the call reads neighbours)");
+    int rc = denoise_params_check("vp_filter_variance", width, height, vp);
+    if (rc) return rc;
+    if ((rc = ensure_device())) return rc;
+    launch_filter_variance(dst, u, q, width, height, vp->radius, vp->patch, vp->k * vp->k, G.denoise_form, G.stream);
     HIPCHK(hipGetLastError());
     G.last_denoise_form = G.denoise_form;
     return VP_OK;

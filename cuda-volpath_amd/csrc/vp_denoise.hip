@@ -11,6 +11,12 @@
 //   denoise_guided_tiled_k / denoise_guided_plain_k: the two forms of vp_denoise_guided, kernels of their
 //     own so that the two above stay as they are: the same passes, plus NF feature channels staged once into LDS planes shaped like
 //     the colour planes and a per-pixel-pair feature distance that caps the weight.
+//   vp_denoise_var's instances of these four: a trailing parameter pack V that is empty or one `const float*`, the caller's per-sample
+//     variance plane; v is then plane[a] * s_a in place of the records' variance, everything else as it stands.  An empty pack leaves
+//     the parameter list -- and with it the instructions -- of the instances above as they were (profiles/variance_kernel_resources.txt).
+//   variance_tiled_k / variance_plain_k: the two forms of vp_filter_variance, the same passes on one scalar
+//     plane u with its noise q: two staged planes with an R + F halo, the e planes, no colour planes -- u with its R halo is inside
+//     the staged plane.
 // LDS layout (cdna_hip_programming.md section 2: ds_read_b32 / ds_write_b32 bank = dword address mod 32 within a 32-lane half):
 // every plane is one float per element, structure of arrays, and a half-wave is one tile row, so the patch reads and the colour
 // reads of a half-wave are 32 consecutive dwords whatever the pitch.  The fill of the e plane walks it linearly, so a half-wave can
@@ -40,14 +46,29 @@ __device__ __forceinline__ float mean_variance(const PixelStatsDev& T)
     const double lhs = nd * T.sum_y2 - T.sum_y * T.sum_y;
     return (float)((lhs > 0.0 ? lhs : 0.0) / (nd * nd * (nd - 1.0)));
 }
+// the variance of the guide's mean at pixel i: from its records, or (vp_denoise_var) the caller's per-sample variance times s = 1 / n.
+// V is the kernels' trailing pack: nothing, or the one plane -- `(svar[i], ...)` is then that plane's element
+template <class... V>
+__device__ __forceinline__ float guide_variance(const PixelStatsDev& T, float s, int i, V... svar)
+{
+    if constexpr (sizeof...(V) != 0) return (svar[i], ...) * s;
+    else return mean_variance(T);
+}
+template <class... V>
+__device__ __forceinline__ float guide_variance_at(const PixelStatsDev* stats, int i, V... svar)
+{
+    if constexpr (sizeof...(V) != 0) return (svar[i], ...) * inv_count(stats[i].n);
+    else return mean_variance(stats[i]);
+}
 // (y, v) of the pair (accumulator, records) at pixel i
-__device__ __forceinline__ void guide_yv(const float4* acc, const PixelStatsDev* stats, int i, float& y, float& v)
+template <class... V>
+__device__ __forceinline__ void guide_yv(const float4* acc, const PixelStatsDev* stats, int i, float& y, float& v, V... svar)
 {
     const PixelStatsDev T = stats[i];
     const float4 A = acc[i];
     const float  s = inv_count(T.n);
     y = luminance(A.x * s, A.y * s, A.z * s);
-    v = mean_variance(T);
+    v = guide_variance(T, s, i, svar...);
 }
 __device__ __forceinline__ float pair_term(float ya, float va, float yb, float vb, float k2)
 {
@@ -61,9 +82,9 @@ __device__ __forceinline__ float patch_weight(float D, float inv_area)
     return expf_(-D);
 }
 
-template <int F>
+template <int F, class... V>
 __global__ __launch_bounds__(DN_TX * DN_TY) void denoise_tiled_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
-                                                                  const PixelStatsDev* gstats, int W, int H, int R, float k2)
+                                                                  const PixelStatsDev* gstats, int W, int H, int R, float k2, V... svar)
 {
     constexpr int EW = DN_TX + 2 * F, EH = DN_TY + 2 * F;   // the e plane: the tile plus an F halo
     constexpr int YW = EW + 32;                             // pitch of the (y, v) planes (>= DN_TX + 2 (R + F) for R <= 16)
@@ -81,7 +102,7 @@ __global__ __launch_bounds__(DN_TX * DN_TY) void denoise_tiled_k(float4* dst, co
     // the thread's own pixel: mean colour, heat and the guide's variance
     const float4 A  = src[pi];
     const float  sp = inv_count(stats[pi].n);
-    const float  vme = mean_variance(gstats[pi]);
+    const float  vme = guide_variance_at(gstats, pi, svar...);
     float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
     // a tile without a noisy pixel (the per-pixel-constant classes) is the plain output stage
     if (!__syncthreads_or(inside && vme != 0.0f))
@@ -94,7 +115,7 @@ __global__ __launch_bounds__(DN_TX * DN_TY) void denoise_tiled_k(float4* dst, co
     {
         const int r = i / (DN_TX + 2 * halo), c = i - r * (DN_TX + 2 * halo);
         float y, v;
-        guide_yv(guide, gstats, clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1), y, v);
+        guide_yv(guide, gstats, clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1), y, v, svar...);
         Ly[r * YW + c] = y;
         Lv[r * YW + c] = v;
     }
@@ -149,8 +170,9 @@ __global__ __launch_bounds__(DN_TX * DN_TY) void denoise_tiled_k(float4* dst, co
     if (inside) dst[pi] = out;
 }
 
+template <class... V>
 __global__ __launch_bounds__(256) void denoise_plain_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
-                                                       const PixelStatsDev* gstats, int W, int H, int R, int F, float k2)
+                                                       const PixelStatsDev* gstats, int W, int H, int R, int F, float k2, V... svar)
 {
     const int idx = threadIdx.x + blockIdx.x * blockDim.x;
     if (idx >= W * H) return;
@@ -158,7 +180,7 @@ __global__ __launch_bounds__(256) void denoise_plain_k(float4* dst, const float4
     const float4 A  = src[idx];
     const float  sp = inv_count(stats[idx].n);
     float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
-    if (mean_variance(gstats[idx]) != 0.0f)
+    if (guide_variance_at(gstats, idx, svar...) != 0.0f)
     {
         const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
         float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
@@ -174,8 +196,8 @@ __global__ __launch_bounds__(256) void denoise_plain_k(float4* dst, const float4
                     for (int dx = -F; dx <= F; dx++)
                     {
                         float ya, va, yb, vb;
-                        guide_yv(guide, gstats, clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1), ya, va);
-                        guide_yv(guide, gstats, clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1), yb, vb);
+                        guide_yv(guide, gstats, clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1), ya, va, svar...);
+                        guide_yv(guide, gstats, clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1), yb, vb, svar...);
                         row = row + pair_term(ya, va, yb, vb, k2);
                     }
                     D = D + row;
@@ -211,9 +233,10 @@ __device__ __forceinline__ float guided_weight(float D, float Df) { return expf_
 
 // denoise_tiled_k with NF feature planes of the tile plus an R halo behind the e planes, pitch and indexing of the colour planes:
 // fb of a half-wave is 32 consecutive dwords, fa stays in registers, no barrier more than denoise_tiled_k has
-template <int F, int NF>
+template <int F, int NF, class... V>
 __global__ __launch_bounds__(DN_TX * DN_TY) void denoise_guided_tiled_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
-                                                                         const PixelStatsDev* gstats, DenoiseFeaturesDev feat, int W, int H, int R, float k2)
+                                                                         const PixelStatsDev* gstats, DenoiseFeaturesDev feat, int W, int H, int R, float k2,
+                                                                         V... svar)
 {
     constexpr int EW = DN_TX + 2 * F, EH = DN_TY + 2 * F;
     constexpr int YW = EW + 32;
@@ -231,7 +254,7 @@ __global__ __launch_bounds__(DN_TX * DN_TY) void denoise_guided_tiled_k(float4* 
     const int  pi = clampi(py, H - 1) * W + clampi(px, W - 1);
     const float4 A  = src[pi];
     const float  sp = inv_count(stats[pi].n);
-    const float  vme = mean_variance(gstats[pi]);
+    const float  vme = guide_variance_at(gstats, pi, svar...);
     float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
     if (!__syncthreads_or(inside && vme != 0.0f))
     {
@@ -243,7 +266,7 @@ __global__ __launch_bounds__(DN_TX * DN_TY) void denoise_guided_tiled_k(float4* 
     {
         const int r = i / (DN_TX + 2 * halo), c = i - r * (DN_TX + 2 * halo);
         float y, v;
-        guide_yv(guide, gstats, clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1), y, v);
+        guide_yv(guide, gstats, clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1), y, v, svar...);
         Ly[r * YW + c] = y;
         Lv[r * YW + c] = v;
     }
@@ -307,8 +330,10 @@ __global__ __launch_bounds__(DN_TX * DN_TY) void denoise_guided_tiled_k(float4* 
     if (inside) dst[pi] = out;
 }
 
+template <class... V>
 __global__ __launch_bounds__(256) void denoise_guided_plain_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
-                                                              const PixelStatsDev* gstats, DenoiseFeaturesDev feat, int W, int H, int R, int F, float k2)
+                                                              const PixelStatsDev* gstats, DenoiseFeaturesDev feat, int W, int H, int R, int F, float k2,
+                                                              V... svar)
 {
     const int idx = threadIdx.x + blockIdx.x * blockDim.x;
     if (idx >= W * H) return;
@@ -316,7 +341,7 @@ __global__ __launch_bounds__(256) void denoise_guided_plain_k(float4* dst, const
     const float4 A  = src[idx];
     const float  sp = inv_count(stats[idx].n);
     float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
-    if (mean_variance(gstats[idx]) != 0.0f)
+    if (guide_variance_at(gstats, idx, svar...) != 0.0f)
     {
         const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
         float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
@@ -332,8 +357,8 @@ __global__ __launch_bounds__(256) void denoise_guided_plain_k(float4* dst, const
                     for (int dx = -F; dx <= F; dx++)
                     {
                         float ya, va, yb, vb;
-                        guide_yv(guide, gstats, clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1), ya, va);
-                        guide_yv(guide, gstats, clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1), yb, vb);
+                        guide_yv(guide, gstats, clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1), ya, va, svar...);
+                        guide_yv(guide, gstats, clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1), yb, vb, svar...);
                         row = row + pair_term(ya, va, yb, vb, k2);
                     }
                     D = D + row;
@@ -356,16 +381,163 @@ __global__ __launch_bounds__(256) void denoise_guided_plain_k(float4* dst, const
     dst[idx] = out;
 }
 
+// ---- vp_filter_variance: the filter on one scalar plane u with the noise q of its values: y := u, v := q and
+// the one colour c := u of vp_denoise's definition; a pixel with u == 0 stays 0.
+// denoise_tiled_k's passes with the planes it needs: (u, q) of the tile plus an R + F halo at the pitch of its (y, v) planes, and the
+// double-buffered e plane.  The colour of an offset is u itself, R inside the staged plane's halo: a half-wave reads 32 consecutive
+// dwords of one row of it, as it would of a colour plane.  2 yv + 2 e floats of LDS: denoise_tiled_k's less its three colour planes.
 template <int F>
+__global__ __launch_bounds__(DN_TX * DN_TY) void variance_tiled_k(float* dst, const float* u, const float* q, int W, int H, int R, float k2)
+{
+    constexpr int EW = DN_TX + 2 * F, EH = DN_TY + 2 * F;   // the e plane: the tile plus an F halo
+    constexpr int YW = EW + 32;                             // pitch of the (u, q) planes (>= DN_TX + 2 (R + F) for R <= 16)
+    extern __shared__ float lds[];
+    const int halo = R + F, YH = DN_TY + 2 * halo;
+    float* Lu = lds;
+    float* Lq = Lu + YW * YH;
+    float* Le = Lq + YW * YH;             // two planes of EW * EH
+    const int tid = threadIdx.x, tx = tid & (DN_TX - 1), ty = tid / DN_TX;
+    const int x0 = blockIdx.x * DN_TX, y0 = blockIdx.y * DN_TY;
+    const int px = x0 + tx, py = y0 + ty;
+    const bool inside = px < W && py < H;
+    const int  pi = clampi(py, H - 1) * W + clampi(px, W - 1);
+    const bool filtered = inside && u[pi] != 0.0f;
+    // a tile of constants -- u == 0 in both halves -- stays one
+    if (!__syncthreads_or(filtered))
+    {
+        if (inside) dst[pi] = 0.0f;
+        return;
+    }
+    for (int i = tid; i < (DN_TX + 2 * halo) * YH; i += DN_TX * DN_TY)
+    {
+        const int r = i / (DN_TX + 2 * halo), c = i - r * (DN_TX + 2 * halo);
+        const int g = clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1);
+        Lu[r * YW + c] = u[g];
+        Lq[r * YW + c] = q[g];
+    }
+    __syncthreads();
+    const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
+    float den = 0.0f, num = 0.0f;
+    int buf = 0;
+    for (int oy = -R; oy <= R; oy++)
+        for (int ox = -R; ox <= R; ox++, buf ^= 1)
+        {
+            float* E = Le + buf * (EW * EH);
+            const int shift = oy * YW + ox;
+            for (int i = tid; i < EW * EH; i += DN_TX * DN_TY)
+            {
+                const int r = i / EW, c = i - r * EW;
+                const int a = (r + R) * YW + (c + R);
+                E[i] = pair_term(Lu[a], Lq[a], Lu[a + shift], Lq[a + shift], k2);
+            }
+            __syncthreads();   // (the other buffer is written next: its readers passed this barrier)
+            const int qx = px + ox, qy = py + oy;
+            if (filtered && qx >= 0 && qx < W && qy >= 0 && qy < H)
+            {
+                float D = 0.0f;
+#pragma unroll
+                for (int dy = 0; dy <= 2 * F; dy++)
+                {
+                    float row = 0.0f;
+#pragma unroll
+                    for (int dx = 0; dx <= 2 * F; dx++) row = row + E[(ty + dy) * EW + tx + dx];
+                    D = D + row;
+                }
+                const float w = patch_weight(D, inv_area);
+                den = den + w;
+                num = num + w * Lu[(ty + halo + oy) * YW + tx + halo + ox];
+            }
+        }
+    if (inside) dst[pi] = filtered ? num / den : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void variance_plain_k(float* dst, const float* u, const float* q, int W, int H, int R, int F, float k2)
+{
+    const int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= W * H) return;
+    const int py = idx / W, px = idx - py * W;
+    float out = 0.0f;
+    if (u[idx] != 0.0f)
+    {
+        const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
+        float den = 0.0f, num = 0.0f;
+        for (int oy = -R; oy <= R; oy++)
+            for (int ox = -R; ox <= R; ox++)
+            {
+                const int qx = px + ox, qy = py + oy;
+                if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                float D = 0.0f;
+                for (int dy = -F; dy <= F; dy++)
+                {
+                    float row = 0.0f;
+                    for (int dx = -F; dx <= F; dx++)
+                    {
+                        const int a = clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1);
+                        const int b = clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1);
+                        row = row + pair_term(u[a], q[a], u[b], q[b], k2);
+                    }
+                    D = D + row;
+                }
+                const float w = patch_weight(D, inv_area);
+                den = den + w;
+                num = num + w * u[qy * W + qx];
+            }
+        out = num / den;
+    }
+    dst[idx] = out;
+}
+
+template <int F, class... V>
 void launch_guided_tiled(int NF, dim3 grid, dim3 block, size_t lds, hipStream_t st, float4* dst, const float4* src, const PixelStatsDev* stats,
-                         const float4* guide, const PixelStatsDev* gstats, const DenoiseFeaturesDev& feat, int W, int H, int R, float k2)
+                         const float4* guide, const PixelStatsDev* gstats, const DenoiseFeaturesDev& feat, int W, int H, int R, float k2, V... svar)
 {
     switch (NF)
     {
-    case 1: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 1>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
-    case 2: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 2>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
-    case 3: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 3>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
-    default: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 4>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
+    case 1: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 1, V...>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2, svar...); break;
+    case 2: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 2, V...>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2, svar...); break;
+    case 3: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 3, V...>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2, svar...); break;
+    default: hipLaunchKernelGGL((denoise_guided_tiled_k<F, 4, V...>), grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2, svar...); break;
+    }
+}
+// the two launchers with the pack of the kernels: empty for vp_denoise / vp_denoise_guided, the variance plane for vp_denoise_var
+template <class... V>
+void launch_denoise_v(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, int W, int H, int R, int F,
+                      float k2, int form, hipStream_t st, V... svar)
+{
+    if (form == 1)
+    {
+        hipLaunchKernelGGL((denoise_plain_k<V...>), dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, st, dst, src, stats, guide, gstats, W, H, R, F, k2,
+                           svar...);
+        return;
+    }
+    const dim3   grid((W + DN_TX - 1) / DN_TX, (H + DN_TY - 1) / DN_TY), block(DN_TX * DN_TY);
+    const size_t lds = denoise_lds_bytes(R, F);
+    switch (F)
+    {
+    case 0: hipLaunchKernelGGL((denoise_tiled_k<0, V...>), grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2, svar...); break;
+    case 1: hipLaunchKernelGGL((denoise_tiled_k<1, V...>), grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2, svar...); break;
+    case 2: hipLaunchKernelGGL((denoise_tiled_k<2, V...>), grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2, svar...); break;
+    default: hipLaunchKernelGGL((denoise_tiled_k<3, V...>), grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2, svar...); break;
+    }
+}
+template <class... V>
+void launch_denoise_guided_v(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats,
+                             const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st, V... svar)
+{
+    if (form == 1)
+    {
+        hipLaunchKernelGGL((denoise_guided_plain_k<V...>), dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, st, dst, src, stats, guide, gstats, feat, W,
+                           H, R, F, k2, svar...);
+        return;
+    }
+    const dim3   grid((W + DN_TX - 1) / DN_TX, (H + DN_TY - 1) / DN_TY), block(DN_TX * DN_TY);
+    const size_t lds = denoise_guided_lds_bytes(R, F, feat.n);
+    switch (F)
+    {
+    case 0: launch_guided_tiled<0>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2, svar...); break;
+    case 1: launch_guided_tiled<1>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2, svar...); break;
+    case 2: launch_guided_tiled<2>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2, svar...); break;
+    default: launch_guided_tiled<3>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2, svar...); break;
     }
 }
 }  // namespace
@@ -380,20 +552,7 @@ size_t denoise_lds_bytes(int R, int F)
 void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, int W, int H, int R,
                     int F, float k2, int form, hipStream_t st)
 {
-    if (form == 1)
-    {
-        hipLaunchKernelGGL(denoise_plain_k, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, st, dst, src, stats, guide, gstats, W, H, R, F, k2);
-        return;
-    }
-    const dim3   grid((W + DN_TX - 1) / DN_TX, (H + DN_TY - 1) / DN_TY), block(DN_TX * DN_TY);
-    const size_t lds = denoise_lds_bytes(R, F);
-    switch (F)
-    {
-    case 0: hipLaunchKernelGGL(denoise_tiled_k<0>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
-    case 1: hipLaunchKernelGGL(denoise_tiled_k<1>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
-    case 2: hipLaunchKernelGGL(denoise_tiled_k<2>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
-    default: hipLaunchKernelGGL(denoise_tiled_k<3>, grid, block, lds, st, dst, src, stats, guide, gstats, W, H, R, k2); break;
-    }
+    launch_denoise_v(dst, src, stats, guide, gstats, W, H, R, F, k2, form, st);
 }
 size_t denoise_guided_lds_bytes(int R, int F, int n_features)
 {
@@ -402,20 +561,35 @@ size_t denoise_guided_lds_bytes(int R, int F, int n_features)
 void launch_denoise_guided(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats,
                            const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st)
 {
+    launch_denoise_guided_v(dst, src, stats, guide, gstats, feat, W, H, R, F, k2, form, st);
+}
+void launch_denoise_var(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, const float* svar,
+                        const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st)
+{
+    if (feat.n) launch_denoise_guided_v(dst, src, stats, guide, gstats, feat, W, H, R, F, k2, form, st, svar);
+    else launch_denoise_v(dst, src, stats, guide, gstats, W, H, R, F, k2, form, st, svar);
+}
+size_t variance_lds_bytes(int R, int F)
+{
+    const size_t uq = (size_t)(DN_TX + 2 * F + 32) * (DN_TY + 2 * (R + F));
+    const size_t e  = (size_t)(DN_TX + 2 * F) * (DN_TY + 2 * F);
+    return (2 * uq + 2 * e) * sizeof(float);
+}
+void launch_filter_variance(float* dst, const float* u, const float* q, int W, int H, int R, int F, float k2, int form, hipStream_t st)
+{
     if (form == 1)
     {
-        hipLaunchKernelGGL(denoise_guided_plain_k, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, st, dst, src, stats, guide, gstats, feat, W, H, R,
-                           F, k2);
+        hipLaunchKernelGGL(variance_plain_k, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, st, dst, u, q, W, H, R, F, k2);
         return;
     }
     const dim3   grid((W + DN_TX - 1) / DN_TX, (H + DN_TY - 1) / DN_TY), block(DN_TX * DN_TY);
-    const size_t lds = denoise_guided_lds_bytes(R, F, feat.n);
+    const size_t lds = variance_lds_bytes(R, F);
     switch (F)
     {
-    case 0: launch_guided_tiled<0>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
-    case 1: launch_guided_tiled<1>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
-    case 2: launch_guided_tiled<2>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
-    default: launch_guided_tiled<3>(feat.n, grid, block, lds, st, dst, src, stats, guide, gstats, feat, W, H, R, k2); break;
+    case 0: hipLaunchKernelGGL(variance_tiled_k<0>, grid, block, lds, st, dst, u, q, W, H, R, k2); break;
+    case 1: hipLaunchKernelGGL(variance_tiled_k<1>, grid, block, lds, st, dst, u, q, W, H, R, k2); break;
+    case 2: hipLaunchKernelGGL(variance_tiled_k<2>, grid, block, lds, st, dst, u, q, W, H, R, k2); break;
+    default: hipLaunchKernelGGL(variance_tiled_k<3>, grid, block, lds, st, dst, u, q, W, H, R, k2); break;
     }
 }
 }  // namespace vp

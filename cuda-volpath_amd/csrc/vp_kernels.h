@@ -312,6 +312,17 @@ constexpr size_t DENOISE_LDS_LIMIT = 64 * 1024 - 256;
 size_t denoise_guided_lds_bytes(int R, int F, int n_features);
 void launch_denoise_guided(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats,
                            const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st);
+// either filter with the guide's variance taken from the caller's per-sample plane (include/volpath.h vp_denoise_var): v = svar * s in
+// place of the records' variance; feat.n == 0: the instances of launch_denoise, else those of launch_denoise_guided, LDS as theirs
+void launch_denoise_var(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, const float* svar,
+                        const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st);
+// the pooled per-sample luminance variance u of two halves' records and the noise q of that estimate (halves_variance_k; include/volpath.h
+// vp_halves_variance): q may be null
+void launch_halves_variance(float* u, float* q, const PixelStatsDev* a_stats, const PixelStatsDev* b_stats, int size, hipStream_t st);
+// the filter on the scalar plane u with the noise q of its values (include/volpath.h vp_filter_variance): form 0 tiled through
+// variance_lds_bytes(R, F) of LDS per workgroup (less than denoise_lds_bytes(R, F): no colour planes), 1 one thread per pixel
+size_t variance_lds_bytes(int R, int F);
+void launch_filter_variance(float* dst, const float* u, const float* q, int W, int H, int R, int F, float k2, int form, hipStream_t st);
 // bricks: cells in 4x4x4 bricks (vp_device.h cell_index); the buffer then holds ceil(n/4)^3 * 64 cells
 void launch_pack_u8(const unsigned char* vol, uint2* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);
 void launch_pack_f32(const float* vol, float* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);

@@ -760,6 +760,38 @@ __global__ void merge_halves_k(float4* dst, float* resid, const float4* a, const
     const float den = ym > floor_y ? ym : floor_y;
     resid[idx] = (ua == 0u || ub == 0u) ? 0.0f : e / den;
 }
+// The pooled per-sample luminance variance of two halves (include/volpath.h vp_halves_variance): per record the unbiased sample
+// variance in binary64 rounded once, 0 and "not measured" where n < 2; their mean where both halves are measured, with a quarter of
+// their squared difference as the variance of that mean; one half's value and its square where it is alone.
+__device__ __forceinline__ float sample_variance(const PixelStatsDev& T)
+{
+    if (T.n < 2u) return 0.0f;
+    const double nd  = (double)T.n;
+    const double lhs = nd * T.sum_y2 - T.sum_y * T.sum_y;
+    return (float)((lhs > 0.0 ? lhs : 0.0) / (nd * (nd - 1.0)));
+}
+__global__ void halves_variance_k(float* u, float* q, const PixelStatsDev* a_stats, const PixelStatsDev* b_stats, int size)
+{
+    int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= size) return;
+    const PixelStatsDev Ta = a_stats[idx], Tb = b_stats[idx];
+    const float ua = sample_variance(Ta), ub = sample_variance(Tb);
+    const bool  ma = Ta.n >= 2u, mb = Tb.n >= 2u;
+    float uu, qq;
+    if (ma && mb)
+    {
+        const float d = ua - ub;
+        uu = 0.5f * (ua + ub);
+        qq = 0.25f * (d * d);
+    }
+    else
+    {
+        uu = ma ? ua : ub;   // (a half that is not measured carries 0)
+        qq = uu * uu;
+    }
+    u[idx] = uu;
+    if (q) q[idx] = qq;
+}
 // dst += src for records (include/volpath.h vp_accumulate_stats): the halves of a half-buffer render into the records of all frames,
 // the records of sharded contexts on one device into one
 __global__ void accumulate_stats_k(PixelStatsDev* dst, const PixelStatsDev* src, size_t n)
@@ -1827,6 +1859,10 @@ void launch_merge_halves(float4* dst, float* resid, const float4* a, const Pixel
                          float floor_y, hipStream_t st)
 {
     hipLaunchKernelGGL(merge_halves_k, dim3((size + 255) / 256), dim3(256), 0, st, dst, resid, a, a_stats, b, b_stats, size, floor_y);
+}
+void launch_halves_variance(float* u, float* q, const PixelStatsDev* a_stats, const PixelStatsDev* b_stats, int size, hipStream_t st)
+{
+    hipLaunchKernelGGL(halves_variance_k, dim3((size + 255) / 256), dim3(256), 0, st, u, q, a_stats, b_stats, size);
 }
 void launch_accumulate_stats(PixelStatsDev* dst, const PixelStatsDev* src, size_t n, hipStream_t st)
 {

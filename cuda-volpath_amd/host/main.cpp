@@ -60,6 +60,13 @@ static void usage()
            "                                                and --denoise-features apply.  --resid-out writes the residual-error map: half\n"
            "                                                the disagreement of the two filtered halves over max(mean, 1e-3), as HDR.\n"
            "                                                One GPU; not with --noise or any plane output or plane filter\n"
+           "               [--denoise-var [--denoise-var-radius R] [--denoise-var-patch F] [--denoise-var-k K] [--var-out FILE.hdr]]\n"
+           "                                                implies --denoise-cross, with the variance stage in front: the per-sample\n"
+           "                                                luminance variance pooled from both halves (vp_halves_variance), smoothed by a\n"
+           "                                                small NL-means pass of its own (vp_filter_variance; R default 1, F default 3, K\n"
+           "                                                default 0.45), and both halves filtered with that one plane as their guide's\n"
+           "                                                variance (vp_denoise_var).  --var-out writes the filtered plane as HDR.  The\n"
+           "                                                refusals of --denoise-cross apply\n"
            "               [--layers-out PREFIX] [--over R G B]\n"
            "                                                compositing layers (vp_render_frames_layers): the frames are rendered as a\n"
            "                                                foreground F and a per-channel transmittance T, pixel = F + T o B for any\n"
@@ -184,6 +191,9 @@ struct Options
     bool        denoise_features = false;
     bool        denoise_cross = false;   // --denoise-cross: two half-buffers, each filtered with the other's weights, merged
     std::string resid_out;
+    bool        denoise_var = false;     // --denoise-var: --denoise-cross with the pooled, pre-filtered variance plane
+    vp_denoise_params dnv = {1, 3, 0.45f};   // (the paper's window; wider ones lost at (10, 3): DESIGN.md section 2.17)
+    std::string var_out;
     float       dn_sigma_alpha = 0.2f, dn_sigma_depth = 0.2f;   // (the best cell of a 3 x 3 grid on that scene: DESIGN.md section 2.13)
     std::string layers_out;
     bool        over = false;
@@ -274,18 +284,23 @@ void Options::parse(int argc, char** argv)
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-cross") denoise_cross = denoise = true;
         else if (a == "--resid-out") { need(1); resid_out = argv[++i]; }
-        else if (a == "--denoise-radius" || a == "--denoise-patch" || a == "--denoise-k")
+        else if (a == "--denoise-var") denoise_var = denoise_cross = denoise = true;
+        else if (a == "--var-out") { need(1); var_out = argv[++i]; }
+        else if (a == "--denoise-radius" || a == "--denoise-patch" || a == "--denoise-k" || a == "--denoise-var-radius" || a == "--denoise-var-patch" ||
+                 a == "--denoise-var-k")
         {
             need(1);
             char* end = nullptr;
             const char* v = argv[++i];
+            vp_denoise_params& d = a.compare(0, 13, "--denoise-var") == 0 ? dnv : dn;   // the variance pass's window or the colour pass's
+            const char what = a[a.rfind('-') + 1];                                     // r, p or k
             bool ok;
-            if (a == "--denoise-k") { dn.k = strtof(v, &end); ok = end != v && !*end && std::isfinite(dn.k) && dn.k > 0.0f; }
+            if (what == 'k') { d.k = strtof(v, &end); ok = end != v && !*end && std::isfinite(d.k) && d.k > 0.0f; }
             else
             {
                 const long n = strtol(v, &end, 10);
-                ok = end != v && !*end && n >= 0 && n <= (a == "--denoise-radius" ? VP_DENOISE_MAX_RADIUS : VP_DENOISE_MAX_PATCH);
-                (a == "--denoise-radius" ? dn.radius : dn.patch) = (int)n;
+                ok = end != v && !*end && n >= 0 && n <= (what == 'r' ? VP_DENOISE_MAX_RADIUS : VP_DENOISE_MAX_PATCH);
+                (what == 'r' ? d.radius : d.patch) = (int)n;
             }
             if (!ok) refuse(USAGE, "%s %s: radius 0..%d, patch 0..%d, k a finite number > 0", a.c_str(), v, VP_DENOISE_MAX_RADIUS, VP_DENOISE_MAX_PATCH);
         }
@@ -377,6 +392,7 @@ static Mode refuse_conflicts(const Options& o)
     if (o.adaptive && o.gpus > 1)
         refuse(PLAIN, "--noise with --gpus %d: reducing per-pixel statistics across ranks is not part of adaptive sampling; use one GPU", o.gpus);
     if (!o.denoise_cross && !o.resid_out.empty()) refuse(PLAIN, "--resid-out needs --denoise-cross: the map is the disagreement of the two filtered halves");
+    if (!o.denoise_var && !o.var_out.empty()) refuse(PLAIN, "--var-out needs --denoise-var: the map is the filtered variance plane of that stage");
     if (o.denoise_cross && (other = first_of({{o.gpus > 1, "--gpus"}, {o.adaptive, "--noise"}, {!o.planes_out.empty(), "--planes-out"}, {!o.groups_out.empty(), "--groups-out"},
                                               {o.relit, "--sun-gain / --sky-gain"}, {!o.layers_out.empty(), "--layers-out"}, {o.over, "--over"}, {o.plane_adaptive, "--plane-noise"},
                                               {o.planes_adaptive, "--planes-noise"}, {o.groups_denoise, "--groups-denoise"}, {o.layers_denoise, "--layers-denoise"},
@@ -730,7 +746,8 @@ static void write_grey_map(const Job& j, const float* d_map, const std::string& 
 
 // the beauty image's filter into disp: the division by each pixel's count is part of the call.  --denoise-features: the feature pass
 // first, then the filter with three of its channels (alpha.y, zt and the cover flag).  --denoise-cross: each half with the other as
-// guide, then the merge -- and, for --resid-out, the residual map, which is returned (the caller writes and frees it)
+// guide, then the merge -- and, for --resid-out, the residual map, which is returned (the caller writes and frees it).  --denoise-var:
+// the pooled variance of the halves and its filter in front, and both halves' filters with that plane as their guide's variance
 static float* denoise_beauty(const Job& j, const Run& run)
 {
     const Options& o = j.o;
@@ -751,9 +768,18 @@ static float* denoise_beauty(const Job& j, const Run& run)
     if (j.n == 2)
     {
         must(!o.resid_out.empty() && !(d_resid = (float*)vp_malloc((size_t)npix * sizeof(float))));
-        must(vp_denoise_guided(p[0].mean, p[0].acc, p[0].rec, p[1].acc, p[1].rec, f, nf, W, H, &o.dn) ||
-             vp_denoise_guided(p[1].mean, p[1].acc, p[1].rec, p[0].acc, p[0].rec, f, nf, W, H, &o.dn) ||
-             vp_merge_halves(run.disp, d_resid, p[0].mean, p[0].rec, p[1].mean, p[1].rec, npix, p[0].floor));
+        float* d_var[3] = {};   // --denoise-var: u, q and the filtered plane
+        for (int k = 0; k < 3 && o.denoise_var; k++) d_var[k] = device_alloc<float>(npix, false);
+        if (o.denoise_var) must(vp_halves_variance(d_var[0], d_var[1], p[0].rec, p[1].rec, npix) || vp_filter_variance(d_var[2], d_var[0], d_var[1], W, H, &o.dnv));
+        const auto half = [&](int a, int b)   // half a with the weights of half b
+        {
+            return o.denoise_var ? vp_denoise_var(p[a].mean, p[a].acc, p[a].rec, p[b].acc, p[b].rec, d_var[2], f, nf, W, H, &o.dn)
+                                 : vp_denoise_guided(p[a].mean, p[a].acc, p[a].rec, p[b].acc, p[b].rec, f, nf, W, H, &o.dn);
+        };
+        must(half(0, 1) || half(1, 0) || vp_merge_halves(run.disp, d_resid, p[0].mean, p[0].rec, p[1].mean, p[1].rec, npix, p[0].floor));
+        if (!o.var_out.empty()) write_grey_map(j, d_var[2], o.var_out);
+        if (o.denoise_var) must(vp_synchronize());
+        for (float* d : d_var) if (d) vp_free(d);
     }
     else must(nf ? vp_denoise_guided(run.disp, p[0].acc, p[0].rec, nullptr, nullptr, f, nf, W, H, &o.dn) : vp_denoise(run.disp, p[0].acc, p[0].rec, nullptr, nullptr, W, H, &o.dn));
     if (o.denoise_features)
@@ -764,6 +790,7 @@ static float* denoise_beauty(const Job& j, const Run& run)
     }
     printf("denoised: radius %d, patch %d, k %g\n", o.dn.radius, o.dn.patch, o.dn.k);
     if (o.denoise_cross) printf("  cross-filtered: two half-buffers, each with the other's weights, merged by their counts\n");
+    if (o.denoise_var) printf("  variance: pooled from both halves, filtered at radius %d, patch %d, k %g\n", o.dnv.radius, o.dnv.patch, o.dnv.k);
     if (o.denoise_features) printf("  weights cut by features: sigma alpha %g, sigma depth %g\n", o.dn_sigma_alpha, o.dn_sigma_depth);
     return d_resid;
 }

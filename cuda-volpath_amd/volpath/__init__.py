@@ -42,6 +42,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_features",
                  "vp_denoise_guided",
                  "vp_render_frames_halves_stats", "vp_merge_halves", "vp_accumulate_stats",
+                 "vp_halves_variance", "vp_filter_variance", "vp_denoise_var",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -176,6 +177,9 @@ def lib():
         L.vp_render_frames_halves_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_merge_halves.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_float]
         L.vp_accumulate_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.vp_halves_variance.argtypes = [C.c_void_p] * 4 + [C.c_int]
+        L.vp_filter_variance.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.POINTER(DenoiseParams)]
+        L.vp_denoise_var.argtypes = [C.c_void_p] * 6 + [C.POINTER(DenoiseFeature), C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseParams)]
         L.vp_render_frames_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_int, C.c_float]
         L.vp_render_frames_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
@@ -636,13 +640,48 @@ def accumulate_stats(dst_ptr, src_ptr, n_records):
     _chk(lib().vp_accumulate_stats(dst_ptr, src_ptr, n_records))
 
 
-def denoise_cross(dst_ptr, resid_ptr, h0, h0_stats, h1, h1_stats, tmp_a_ptr, tmp_b_ptr, width, height, radius, patch, k, features=None, floor_y=1e-3):
+def halves_variance(u_ptr, q_ptr, a_stats_ptr, b_stats_ptr, n):
+    """u = the pooled per-sample luminance variance of two halves' records, q (may be None) = the variance of that estimate: a quarter
+    of the halves' squared difference (vp_halves_variance)"""
+    _chk(lib().vp_halves_variance(u_ptr, q_ptr, a_stats_ptr, b_stats_ptr, n))
+
+
+def filter_variance(dst_ptr, u_ptr, q_ptr, width, height, radius=1, patch=3, k=0.45):
+    """dst = the NL-means filtered scalar plane u, weights from u itself with q as the noise of its values; a pixel with u == 0 stays 0
+    (vp_filter_variance); queued on the context's stream, never synchronises"""
+    dp = DenoiseParams(radius, patch, k)
+    _chk(lib().vp_filter_variance(dst_ptr, u_ptr, q_ptr, width, height, C.byref(dp)))
+
+
+def denoise_var(dst_ptr, src_ptr, stats_ptr, width, height, sample_var_ptr, features=(), radius=5, patch=1, k=0.45, guide_ptr=None, guide_stats_ptr=None):
+    """denoise_guided() with the guide's variance taken from the caller's per-sample variance plane, times the guide's 1 / n
+    (vp_denoise_var); sample_var_ptr None: denoise_guided()'s bytes"""
+    dp = DenoiseParams(radius, patch, k)
+    feats = [(getattr(p, "value", p), c, s) for p, c, s in features]
+    arr = (DenoiseFeature * len(feats))(*[DenoiseFeature(p, c, s) for p, c, s in feats]) if feats else None
+    _chk(lib().vp_denoise_var(dst_ptr, src_ptr, stats_ptr, guide_ptr, guide_stats_ptr, sample_var_ptr, arr, len(feats), width, height, C.byref(dp)))
+
+
+def denoise_cross(dst_ptr, resid_ptr, h0, h0_stats, h1, h1_stats, tmp_a_ptr, tmp_b_ptr, width, height, radius, patch, k, features=None, floor_y=1e-3,
+                  variance=None, var_ptrs=None):
     """the cross-filter of two half-buffers (accumulators h0, h1 and their records): each half filtered with the weights of the other into
     the caller's temporaries, then merged into dst and, where resid_ptr is given, the residual map -- three calls queued on the
-    context's stream, nothing allocated"""
+    context's stream, nothing allocated.  variance=(R, F, k): the variance stage first (halves_variance, filter_variance with these
+    parameters) and both filters through denoise_var with the one filtered plane; var_ptrs are then the caller's three float planes
+    (u, q, filtered), width * height floats each"""
     feats = tuple(features) if features else ()
-    denoise_guided(tmp_a_ptr, h0, h0_stats, width, height, feats, radius, patch, k, guide_ptr=h1, guide_stats_ptr=h1_stats)
-    denoise_guided(tmp_b_ptr, h1, h1_stats, width, height, feats, radius, patch, k, guide_ptr=h0, guide_stats_ptr=h0_stats)
+    if variance is None:
+        denoise_guided(tmp_a_ptr, h0, h0_stats, width, height, feats, radius, patch, k, guide_ptr=h1, guide_stats_ptr=h1_stats)
+        denoise_guided(tmp_b_ptr, h1, h1_stats, width, height, feats, radius, patch, k, guide_ptr=h0, guide_stats_ptr=h0_stats)
+    else:
+        if var_ptrs is None or len(var_ptrs) != 3:
+            raise ValueError("denoise_cross: variance=(R, F, k) needs var_ptrs=(u, q, filtered), three device planes of width * height floats")
+        vr, vf, vk = variance
+        u_ptr, q_ptr, uf_ptr = var_ptrs
+        halves_variance(u_ptr, q_ptr, h0_stats, h1_stats, width * height)
+        filter_variance(uf_ptr, u_ptr, q_ptr, width, height, vr, vf, vk)
+        denoise_var(tmp_a_ptr, h0, h0_stats, width, height, uf_ptr, feats, radius, patch, k, guide_ptr=h1, guide_stats_ptr=h1_stats)
+        denoise_var(tmp_b_ptr, h1, h1_stats, width, height, uf_ptr, feats, radius, patch, k, guide_ptr=h0, guide_stats_ptr=h0_stats)
     merge_halves(dst_ptr, resid_ptr, tmp_a_ptr, h0_stats, tmp_b_ptr, h1_stats, width * height, floor_y)
 
 

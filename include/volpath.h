@@ -341,7 +341,7 @@ int vp_stats_rel_error(float* dst, const vp_pixel_stats* d_stats, int size, floa
  *   there; never synchronises.
  * What this is and is not: the filter sees LUMINANCE variance only -- purely chromatic noise is invisible to it.  Like every such
  * filter it trades variance for bias.  Weights taken from the buffer they filter are correlated with it: the guide pair is the
- * remedy.  The variance estimates themselves are not pre-filtered.  The exact-parity product stays vp_render_frames plus scale.
+ * remedy.  The variance estimates themselves are not pre-filtered (vp_denoise_var, below, takes ones that are).  The exact-parity product stays vp_render_frames plus scale.
  * vp_set_denoise_form (test hook): 0 = one workgroup per pixel tile, (y, v), the colours and the pair terms of an offset shared through
  * LDS (default); 1 = one thread per pixel from global memory.  The same bits.  vp_last_denoise_form: the form of the last call. */
 typedef struct { int radius, patch; float k; } vp_denoise_params;   /* search window (2R+1)^2, patch (2F+1)^2, strength */
@@ -435,6 +435,50 @@ int vp_render_frames_halves_stats(vp_float4* d_h0, vp_float4* d_h1, vp_pixel_sta
 int vp_merge_halves(vp_float4* dst, float* d_resid, const vp_float4* a, const vp_pixel_stats* a_stats,
                     const vp_float4* b, const vp_pixel_stats* b_stats, int size, float floor_y);
 int vp_accumulate_stats(vp_pixel_stats* dst, const vp_pixel_stats* src, size_t n);
+
+/* The variance stage of the cross-filter: Rousselle, Knaus and Zwicker 2012 estimate the pixel variance from
+ * BOTH buffers and smooth it with a small NL-means pass before the colour pass.  Three calls; opt-in, the calls above keep their bits.
+ * Everything is binary32, one rounding per operation, no contraction, operations in the order written, unless marked binary64; min,
+ * max and clamp() as in vp_denoise.  All three need no scene, run asynchronously on the context's stream behind what is queued there,
+ * never synchronise, and check their arguments before the device is touched.
+ *
+ * vp_halves_variance: the pooled PER-SAMPLE luminance variance of two halves and the noise of that estimate; only the records are read.
+ *   Per record T: T.n < 2: "not measured", u(T) = 0.  Else u(T) = (float)(max(lhs, 0.0) / (nd * (nd - 1.0))) with nd and lhs as in
+ *   vp_denoise, binary64 rounded once (the unbiased sample variance: vp_denoise's v is this over n).  `flags` is never read.
+ *   Per pixel, ua = u(a_stats[i]), ub = u(b_stats[i]):
+ *     both measured:        u = 0.5f * (ua + ub);   d = ua - ub;   q = 0.25f * (d * d)
+ *     exactly one measured: u = that half's value;  q = u * u      (nothing is known about its error)
+ *     neither measured:     u = 0;  q = 0
+ *   q estimates the variance of u: two independent estimates differ by twice the variance of their mean.  d_q may be NULL.
+ *   VP_E_ARG: NULL d_u or records, size < 0.
+ *
+ * vp_filter_variance: vp_denoise's filter on one scalar plane.  The definition is vp_denoise's word for word with y := u, v := q and
+ * the one "colour" c := u: the pair term e from (u, q), row sums, their sum, the scaling by 1 / (2F+1)^2, the clamp at 0, w = expf_(-D),
+ * offsets in raster order, offsets that leave the image skipped, dst[p] = (sum of w * u_(p+o)) / (sum of w), one correctly rounded divide.
+ *   Exceptions: there is no v_p == 0 exception; instead u[p] == 0.0f gives dst[p] = 0.0f -- a pixel that is a constant in both halves
+ *   stays one, because vp_denoise's own early-outs hang on v_p == 0.  (Such a pixel still serves its neighbours as a value of 0.)
+ *   The centre weight is exactly 1, so the denominator is >= 1; radius == 0 returns u bit for bit where u != 0.
+ *   Inputs are assumed finite and small enough that d * d and q_a + q_b stay finite: u is a squared luminance and q its square, a
+ *   FOURTH power of a luminance -- luminances up to about 3e9 are safe.
+ *   Limits VP_DENOISE_MAX_RADIUS and VP_DENOISE_MAX_PATCH.  VP_E_ARG: NULL pointers; dst == u or dst == q; width or height < 1; radius
+ *   or patch outside their limits; a k that is not finite or not > 0.  vp_set_denoise_form applies (0: a workgroup per 32 x 8 tile, u and
+ *   q staged in LDS once; 1: a thread per pixel from global memory; the same bits) and vp_last_denoise_form reports it.
+ *
+ * vp_denoise_var: vp_denoise_guided with the variance supplied by the caller.  One change to the definition: wherever it reads v_a of
+ * the guide -- the pair term and the v_p == 0 exception --
+ *     v_a = d_sample_var[a'] * s_a'          s the GUIDE pair's 1.0f / (float)n, 0 where n == 0; one binary32 multiply
+ *   -- a per-sample variance becomes the variance of that guide's mean.  Everything else, the features among it, is unchanged.  With
+ *   d_sample_var == NULL the output is vp_denoise_guided's byte for byte.  Refused: everything vp_denoise_guided refuses, and a plane
+ *   that is dst.
+ * The cross-filter with the stage: vp_render_frames_halves_stats(h0, h1, s0, s1, ...);  vp_halves_variance(u, q, s0, s1, n);
+ *   vp_filter_variance(uf, u, q, ...);  vp_denoise_var(A, h0, s0, h1, s1, uf, ...);  vp_denoise_var(B, h1, s1, h0, s0, uf, ...);
+ *   vp_merge_halves(dst, resid, A, s0, B, s1, ...).  Both colour passes read the same filtered plane. */
+int vp_halves_variance(float* d_u, float* d_q, const vp_pixel_stats* a_stats, const vp_pixel_stats* b_stats, int size);
+int vp_filter_variance(float* dst, const float* u, const float* q, int width, int height, const vp_denoise_params* vp);
+int vp_denoise_var(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats,
+                   const vp_float4* guide, const vp_pixel_stats* d_guide_stats, const float* d_sample_var,
+                   const vp_denoise_feature* features, int n_features,
+                   int width, int height, const vp_denoise_params* dp);
 
 /* Compositing layers: a foreground F and a per-channel transmittance T with  pixel = F + T o B  for any
  * background B -- another sky, a plate, a second render.  vp_render_frames bakes the context's own sky into every sample and keeps

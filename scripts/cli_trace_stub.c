@@ -266,6 +266,21 @@ int vp_merge_halves(vp_float4* dst, float* resid, const vp_float4* a, const vp_p
 {
     return begin("vp_merge_halves"), ptr(dst), ptr(resid), ptr(a), ptr(ar), ptr(b), ptr(br), i64(n), flt(&floor_y, 1), fill_floats(dst), mix(7), fill_floats(resid), done();
 }
+int vp_halves_variance(float* u, float* q, const vp_pixel_stats* ar, const vp_pixel_stats* br, int n)
+{
+    return begin("vp_halves_variance"), ptr(u), ptr(q), ptr(ar), ptr(br), i64(n), fill_floats(u), mix(7), fill_floats(q), done();
+}
+int vp_filter_variance(float* dst, const float* u, const float* q, int w, int h, const vp_denoise_params* dp)
+{
+    return begin("vp_filter_variance"), ptr(dst), ptr(u), ptr(q), i64(w), i64(h), i64(dp->radius), i64(dp->patch), flt(&dp->k, 1), fill_floats(dst), done();
+}
+int vp_denoise_var(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* r, const vp_float4* g, const vp_pixel_stats* gr, const float* var,
+                   const vp_denoise_feature* f, int nf, int w, int h, const vp_denoise_params* dp)
+{
+    begin("vp_denoise_var"), ptr(dst), ptr(src), ptr(r), ptr(g), ptr(gr), ptr(var), i64(f != NULL), i64(nf);
+    for (int k = 0; k < nf; k++) say(" {"), ptr(f[k].plane), i64(f[k].channel), flt(&f[k].sigma, 1), say(" }");
+    return i64(w), i64(h), i64(dp->radius), i64(dp->patch), flt(&dp->k, 1), fill_floats(dst), done();
+}
 int vp_composite(vp_float4* dst, const vp_float4* fg, const vp_float4* trans, const vp_float4* plate, const float rgb[3], int n, float s)
 {
     return begin("vp_composite"), ptr(dst), ptr(fg), ptr(trans), ptr(plate), flt(rgb, 3), i64(n), flt(&s, 1), fill_floats(dst), done();
