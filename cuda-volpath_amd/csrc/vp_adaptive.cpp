@@ -7,6 +7,7 @@
 // vp_render_adaptive_group_layers: the same on the three planes of a group-layers render, with three records per pixel.
 // vp_denoise: the filter of the output stage that reads the records (vp_denoise.hip); vp_denoise_guided: the same with feature planes.
 // vp_halves_variance, vp_filter_variance, vp_denoise_var: the variance stage of the cross-filter.
+// vp_cross_error, vp_select: per-pixel selection among filtered candidates by cross-buffer error estimates.
 #include <climits>
 
 #include "vp_state.h"
@@ -297,6 +298,49 @@ int vp_filter_variance(float* dst, const float* u, const float* q, int width, in
     if (rc) return rc;
     if ((rc = ensure_device())) return rc;
     launch_filter_variance(dst, u, q, width, height, vp->radius, vp->patch, vp->k * vp->k, G.denoise_form, G.stream);
+    HIPCHK(hipGetLastError());
+    G.last_denoise_form = G.denoise_form;
+    return VP_OK;
+}
+int vp_cross_error(float* d_err, const vp_float4* fa, const vp_float4* fb, const vp_float4* h0, const vp_pixel_stats* s0, const vp_float4* h1,
+                   const vp_pixel_stats* s1, int size)
+{
+    if (!d_err || !fa || !fb || !h0 || !s0 || !h1 || !s1) return fail(VP_E_ARG, "vp_cross_error: null pointer");
+    for (const void* in : {(const void*)fa, (const void*)fb, (const void*)h0, (const void*)s0, (const void*)h1, (const void*)s1})
+        if (in == (const void*)d_err) return fail(VP_E_ARG, "vp_cross_error: d_err is one of the inputs");
+    if (size < 0) return fail(VP_E_ARG, "vp_cross_error: size %d", size);
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (size)
+        launch_cross_error(d_err, (const float4*)fa, (const float4*)fb, (const float4*)h0, (const PixelStatsDev*)s0, (const float4*)h1, (const PixelStatsDev*)s1, size,
+                           G.stream);
+    HIPCHK(hipGetLastError());
+    return VP_OK;
+}
+int vp_select(vp_float4* dst, uint8_t* d_index, const vp_float4* const* images, const float* const* errors, int n, int width, int height,
+              const vp_select_params* sp)
+{
+    if (!dst || !images || !errors || !sp) return fail(VP_E_ARG, "vp_select: null pointer");
+    if (n < 1 || n > VP_SELECT_MAX_CANDIDATES) return fail(VP_E_ARG, "vp_select: %d candidates outside 1..%d", n, VP_SELECT_MAX_CANDIDATES);
+    static_assert(VP_SELECT_MAX_CANDIDATES == SELECT_MAX, "the kernels' argument block holds VP_SELECT_MAX_CANDIDATES pointers of each kind");
+    SelectDev S = {};
+    for (int c = 0; c < n; c++)
+    {
+        if (!images[c] || !errors[c]) return fail(VP_E_ARG, "vp_select: candidate %d has no %s", c, images[c] ? "error plane" : "image");
+        if ((const void*)errors[c] == (const void*)dst) return fail(VP_E_ARG, "vp_select: error plane %d is dst (the call reads its neighbours)", c);
+        S.img[c] = (const float4*)images[c];
+        S.err[c] = errors[c];
+    }
+    S.n = n;
+    if (d_index && (const void*)d_index == (const void*)dst) return fail(VP_E_ARG, "vp_select: d_index is dst");
+    if (width < 1 || height < 1 || (long long)width * height > INT_MAX) return fail(VP_E_ARG, "vp_select: image %d x %d", width, height);
+    if (sp->smooth_radius < 0 || sp->smooth_radius > VP_SELECT_MAX_RADIUS)
+        return fail(VP_E_ARG, "vp_select: smooth_radius %d outside 0..%d", sp->smooth_radius, VP_SELECT_MAX_RADIUS);
+    if (sp->blend_radius < 0 || sp->blend_radius > VP_SELECT_MAX_RADIUS)
+        return fail(VP_E_ARG, "vp_select: blend_radius %d outside 0..%d", sp->blend_radius, VP_SELECT_MAX_RADIUS);
+    int rc = ensure_device();
+    if (rc) return rc;
+    launch_select((float4*)dst, d_index, S, width, height, sp->smooth_radius, sp->blend_radius, G.denoise_form, G.stream);
     HIPCHK(hipGetLastError());
     G.last_denoise_form = G.denoise_form;
     return VP_OK;

@@ -17,6 +17,8 @@
 //   variance_tiled_k / variance_plain_k: the two forms of vp_filter_variance, the same passes on one scalar
 //     plane u with its noise q: two staged planes with an R + F halo, the e planes, no colour planes -- u with its R halo is inside
 //     the staged plane.
+//   select_tiled_k / select_plain_k: the two forms of vp_select: box sums of n error planes, the smallest
+//     picked per pixel, the picks blended over a window; nothing of the filter above is shared but the tile.
 // LDS layout (cdna_hip_programming.md section 2: ds_read_b32 / ds_write_b32 bank = dword address mod 32 within a 32-lane half):
 // every plane is one float per element, structure of arrays, and a half-wave is one tile row, so the patch reads and the colour
 // reads of a half-wave are 32 consecutive dwords whatever the pitch.  The fill of the e plane walks it linearly, so a half-wave can
@@ -487,6 +489,189 @@ __global__ __launch_bounds__(256) void variance_plain_k(float* dst, const float*
     dst[idx] = out;
 }
 
+// ---- vp_select: per-pixel selection among n candidates by their smoothed error estimates
+// the number of in-image positions among p - R .. p + R
+__device__ __forceinline__ int span_in(int p, int R, int N)
+{
+    const int lo = p - R < 0 ? 0 : p - R, hi = p + R > N - 1 ? N - 1 : p + R;
+    return hi - lo + 1;
+}
+// W_c, the pick's own count and the blend of the header from the four counts and the candidates' values at p
+__device__ __forceinline__ float4 select_blend(const float4 (&v)[SELECT_MAX], const int (&cnt)[SELECT_MAX], int n, int k, int T)
+{
+    // the pick's value and count by masks (a chain of selects becomes an indexed load from a private array: scratch)
+    unsigned bx = 0, by = 0, bz = 0, bw = 0;
+    int      wk = 0;
+#pragma unroll
+    for (int c = 0; c < SELECT_MAX; c++)
+    {
+        const unsigned m = c == k ? ~0u : 0u;
+        bx |= __float_as_uint(v[c].x) & m;
+        by |= __float_as_uint(v[c].y) & m;
+        bz |= __float_as_uint(v[c].z) & m;
+        bw |= __float_as_uint(v[c].w) & m;
+        wk |= cnt[c] & (int)m;
+    }
+    const float4 pick = make_float4(__uint_as_float(bx), __uint_as_float(by), __uint_as_float(bz), __uint_as_float(bw));
+    if (wk == T) return pick;
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+#pragma unroll
+    for (int c = 0; c < SELECT_MAX; c++)
+        if (c < n)
+        {
+            const float w = (float)cnt[c];
+            nx = nx + w * v[c].x;
+            ny = ny + w * v[c].y;
+            nz = nz + w * v[c].z;
+        }
+    const float t = (float)T;
+    return make_float4(nx / t, ny / t, nz / t, pick.w);
+}
+
+// One 256-thread workgroup per 32 x 8 tile.  The n error planes of the tile plus an Rs + Rb halo are staged once, 0.0f where the
+// position is outside the image: the sums of the definition start at +0.0f and a sum of binary32 values that starts there is never
+// -0.0f, so adding +0.0f for a skipped position or a skipped row leaves every bit as it was.  Per candidate: the row sums of the tile
+// plus an Rb halo (all staged rows) into the one h plane, a barrier, the column sums, the divide and the comparison in registers -- a
+// thread owns up to 2 x 2 positions of the pick plane --, a barrier.  Then the picks into the index plane (-1 outside the image), and
+// every thread counts its blend window from there.  The candidates' colours are read from global memory at p only.
+// Every pass gives a half-wave one row and 32 consecutive columns: 32 consecutive dwords, conflict-free at any pitch, so the planes are
+// dense (the second column chunk of a row has 2 Rb lanes at work: 6 of 32 at most, on 3 of 20 rows' worth of work).  The index plane
+// is one dword per position: four lanes on the bytes of one dword would be four addresses on one bank.
+__global__ __launch_bounds__(DN_TX * DN_TY) void select_tiled_k(float4* dst, unsigned char* index, SelectDev S, int W, int H, int Rs, int Rb)
+{
+    extern __shared__ float lds[];
+    const int halo = Rs + Rb, RW = DN_TX + 2 * halo, RH = DN_TY + 2 * halo, PW = DN_TX + 2 * Rb, PH = DN_TY + 2 * Rb;
+    float* Lr = lds;                        // n planes of RW * RH
+    float* Lh = Lr + S.n * (RW * RH);       // one plane of PW * RH
+    int*   Lk = (int*)(Lh + PW * RH);       // PW * PH
+    const int tid = threadIdx.x, tx = tid & (DN_TX - 1), ty = tid / DN_TX;
+    const int x0 = blockIdx.x * DN_TX, y0 = blockIdx.y * DN_TY;
+#pragma unroll
+    for (int c = 0; c < SELECT_MAX; c++)
+        if (c < S.n)
+            for (int i = tid; i < RW * RH; i += DN_TX * DN_TY)
+            {
+                const int r = i / RW, col = i - r * RW;
+                const int gx = x0 - halo + col, gy = y0 - halo + r;
+                Lr[c * (RW * RH) + i] = (gx >= 0 && gx < W && gy >= 0 && gy < H) ? S.err[c][(size_t)gy * W + gx] : 0.0f;
+            }
+    __syncthreads();
+    // the thread's positions of the pick plane: rows ty, ty + 8, columns tx, tx + 32
+    float best[2][2];
+    int   pick[2][2] = {};
+#pragma unroll
+    for (int c = 0; c < SELECT_MAX; c++)
+        if (c < S.n)   // (uniform: the barriers inside are reached by all or none)
+        {
+            const float* R0 = Lr + c * (RW * RH);
+            for (int r = ty; r < RH; r += DN_TY)
+                for (int col = tx; col < PW; col += DN_TX)
+                {
+                    float row = 0.0f;
+                    for (int t = 0; t <= 2 * Rs; t++) row = row + R0[r * RW + col + t];
+                    Lh[r * PW + col] = row;
+                }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+                {
+                    const int r = ty + j * DN_TY, col = tx + i * DN_TX;
+                    if (r >= PH || col >= PW) continue;
+                    float sum = 0.0f;
+                    for (int t = 0; t <= 2 * Rs; t++) sum = sum + Lh[(r + t) * PW + col];
+                    const int gx = x0 - Rb + col, gy = y0 - Rb + r;
+                    // (outside the image the count is not one of a window; the position is marked below and its E never used)
+                    const float E = sum / (float)(span_in(clampi(gx, W - 1), Rs, W) * span_in(clampi(gy, H - 1), Rs, H));
+                    if (c == 0 || E < best[j][i]) { best[j][i] = E; pick[j][i] = c; }
+                }
+            __syncthreads();   // (the h plane is written next)
+        }
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+        {
+            const int r = ty + j * DN_TY, col = tx + i * DN_TX;
+            if (r >= PH || col >= PW) continue;
+            const int gx = x0 - Rb + col, gy = y0 - Rb + r;
+            Lk[r * PW + col] = (gx >= 0 && gx < W && gy >= 0 && gy < H) ? pick[j][i] : -1;
+        }
+    __syncthreads();
+    const int px = x0 + tx, py = y0 + ty;
+    if (px >= W || py >= H) return;
+    int cnt[SELECT_MAX] = {};
+    for (int dy = 0; dy <= 2 * Rb; dy++)
+        for (int dx = 0; dx <= 2 * Rb; dx++)
+        {
+            const int k = Lk[(ty + dy) * PW + tx + dx];
+#pragma unroll
+            for (int c = 0; c < SELECT_MAX; c++) cnt[c] += k == c;
+        }
+    const int    k = Lk[(ty + Rb) * PW + tx + Rb];
+    const size_t p = (size_t)py * W + px;
+    float4 v[SELECT_MAX];
+#pragma unroll
+    for (int c = 0; c < SELECT_MAX; c++) v[c] = c < S.n ? S.img[c][p] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    dst[p] = select_blend(v, cnt, S.n, k, span_in(px, Rb, W) * span_in(py, Rb, H));
+    if (index) index[p] = (unsigned char)k;
+}
+
+// k(q) of the header straight from global memory: positions outside the image skipped, as the definition says it
+__device__ __forceinline__ int select_pick_at(const SelectDev& S, int qx, int qy, int W, int H, int Rs)
+{
+    const float count = (float)(span_in(qx, Rs, W) * span_in(qy, Rs, H));
+    float best = 0.0f;
+    int   k = 0;
+#pragma unroll
+    for (int c = 0; c < SELECT_MAX; c++)
+        if (c < S.n)
+        {
+            float sum = 0.0f;
+            for (int ty = -Rs; ty <= Rs; ty++)
+            {
+                const int y = qy + ty;
+                if (y < 0 || y >= H) continue;
+                float row = 0.0f;
+                for (int tx = -Rs; tx <= Rs; tx++)
+                {
+                    const int x = qx + tx;
+                    if (x < 0 || x >= W) continue;
+                    row = row + S.err[c][(size_t)y * W + x];
+                }
+                sum = sum + row;
+            }
+            const float E = sum / count;
+            if (c == 0 || E < best) { best = E; k = c; }
+        }
+    return k;
+}
+__global__ __launch_bounds__(256) void select_plain_k(float4* dst, unsigned char* index, SelectDev S, int W, int H, int Rs, int Rb)
+{
+    const int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= W * H) return;
+    const int py = idx / W, px = idx - py * W;
+    int cnt[SELECT_MAX] = {};
+    int T = 0;
+    for (int dy = -Rb; dy <= Rb; dy++)
+        for (int dx = -Rb; dx <= Rb; dx++)
+        {
+            const int qx = px + dx, qy = py + dy;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const int k = select_pick_at(S, qx, qy, W, H, Rs);
+#pragma unroll
+            for (int c = 0; c < SELECT_MAX; c++) cnt[c] += k == c;
+            T++;
+        }
+    const int k = select_pick_at(S, px, py, W, H, Rs);
+    float4 v[SELECT_MAX];
+#pragma unroll
+    for (int c = 0; c < SELECT_MAX; c++) v[c] = c < S.n ? S.img[c][idx] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    dst[idx] = select_blend(v, cnt, S.n, k, T);
+    if (index) index[idx] = (unsigned char)k;
+}
+
 template <int F, class... V>
 void launch_guided_tiled(int NF, dim3 grid, dim3 block, size_t lds, hipStream_t st, float4* dst, const float4* src, const PixelStatsDev* stats,
                          const float4* guide, const PixelStatsDev* gstats, const DenoiseFeaturesDev& feat, int W, int H, int R, float k2, V... svar)
@@ -591,5 +776,21 @@ void launch_filter_variance(float* dst, const float* u, const float* q, int W, i
     case 2: hipLaunchKernelGGL(variance_tiled_k<2>, grid, block, lds, st, dst, u, q, W, H, R, k2); break;
     default: hipLaunchKernelGGL(variance_tiled_k<3>, grid, block, lds, st, dst, u, q, W, H, R, k2); break;
     }
+}
+size_t select_lds_bytes(int n, int Rs, int Rb)
+{
+    const size_t halo = (size_t)Rs + Rb;
+    const size_t r = (DN_TX + 2 * halo) * (DN_TY + 2 * halo), h = (size_t)(DN_TX + 2 * Rb) * (DN_TY + 2 * halo), k = (size_t)(DN_TX + 2 * Rb) * (DN_TY + 2 * Rb);
+    return (n * r + h + k) * sizeof(float);
+}
+void launch_select(float4* dst, unsigned char* index, const SelectDev& S, int W, int H, int Rs, int Rb, int form, hipStream_t st)
+{
+    if (form == 1)
+    {
+        hipLaunchKernelGGL(select_plain_k, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, st, dst, index, S, W, H, Rs, Rb);
+        return;
+    }
+    const dim3 grid((W + DN_TX - 1) / DN_TX, (H + DN_TY - 1) / DN_TY), block(DN_TX * DN_TY);
+    hipLaunchKernelGGL(select_tiled_k, grid, block, select_lds_bytes(S.n, Rs, Rb), st, dst, index, S, W, H, Rs, Rb);
 }
 }  // namespace vp

@@ -323,6 +323,17 @@ void launch_halves_variance(float* u, float* q, const PixelStatsDev* a_stats, co
 // variance_lds_bytes(R, F) of LDS per workgroup (less than denoise_lds_bytes(R, F): no colour planes), 1 one thread per pixel
 size_t variance_lds_bytes(int R, int F);
 void launch_filter_variance(float* dst, const float* u, const float* q, int W, int H, int R, int F, float k2, int form, hipStream_t st);
+// one candidate's per-pixel error estimate from the two filtered halves fa, fb against the unfiltered means of the other half
+// (cross_error_k; include/volpath.h vp_cross_error)
+void launch_cross_error(float* err, const float4* fa, const float4* fb, const float4* h0, const PixelStatsDev* s0, const float4* h1, const PixelStatsDev* s1,
+                        int size, hipStream_t st);
+// per-pixel selection among n candidates (vp_denoise.hip; include/volpath.h vp_select): the error planes box-smoothed at radius Rs, the
+// smallest picked, the picks blended over radius Rb; index may be null.  Form 0 tiled through select_lds_bytes(n, Rs, Rb) of LDS per
+// workgroup (at most 19248: n = 4, radii 3), 1 one thread per pixel from global memory.  The arrays travel by value in the arguments
+constexpr int SELECT_MAX = 4;
+struct SelectDev { const float4* img[SELECT_MAX]; const float* err[SELECT_MAX]; int n; };
+size_t select_lds_bytes(int n, int Rs, int Rb);
+void launch_select(float4* dst, unsigned char* index, const SelectDev& S, int W, int H, int Rs, int Rb, int form, hipStream_t st);
 // bricks: cells in 4x4x4 bricks (vp_device.h cell_index); the buffer then holds ceil(n/4)^3 * 64 cells
 void launch_pack_u8(const unsigned char* vol, uint2* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);
 void launch_pack_f32(const float* vol, float* cells, int nx, int ny, int nz, bool bricks, hipStream_t st);

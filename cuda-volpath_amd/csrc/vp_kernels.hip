@@ -792,6 +792,32 @@ __global__ void halves_variance_k(float* u, float* q, const PixelStatsDev* a_sta
     u[idx] = uu;
     if (q) q[idx] = qq;
 }
+// One candidate's per-pixel error estimate (include/volpath.h vp_cross_error): each filtered half's luminance held against the
+// UNFILTERED mean of the other half, less that mean's variance (vp_denoise's v: binary64, rounded once); not clamped.
+__device__ __forceinline__ float half_mean_yv(const float4& A, const PixelStatsDev& T, float& v)
+{
+    const float s = T.n ? 1.0f / (float)T.n : 0.0f;
+    v = 0.0f;
+    if (T.n >= 2u)
+    {
+        const double nd  = (double)T.n;
+        const double lhs = nd * T.sum_y2 - T.sum_y * T.sum_y;
+        v = (float)((lhs > 0.0 ? lhs : 0.0) / (nd * nd * (nd - 1.0)));
+    }
+    return stats_luminance(make_float4(A.x * s, A.y * s, A.z * s, 0.0f));
+}
+__global__ void cross_error_k(float* err, const float4* fa, const float4* fb, const float4* h0, const PixelStatsDev* s0, const float4* h1,
+                              const PixelStatsDev* s1, int size)
+{
+    int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= size) return;
+    const PixelStatsDev T0 = s0[idx], T1 = s1[idx];
+    float v0, v1;
+    const float y0 = half_mean_yv(h0[idx], T0, v0), y1 = half_mean_yv(h1[idx], T1, v1);
+    const float da = stats_luminance(fa[idx]) - y1, ea = da * da - v1;
+    const float db = stats_luminance(fb[idx]) - y0, eb = db * db - v0;
+    err[idx] = (T0.n >= 2u && T1.n >= 2u) ? 0.5f * (ea + eb) : 0.0f;
+}
 // dst += src for records (include/volpath.h vp_accumulate_stats): the halves of a half-buffer render into the records of all frames,
 // the records of sharded contexts on one device into one
 __global__ void accumulate_stats_k(PixelStatsDev* dst, const PixelStatsDev* src, size_t n)
@@ -1863,6 +1889,11 @@ void launch_merge_halves(float4* dst, float* resid, const float4* a, const Pixel
 void launch_halves_variance(float* u, float* q, const PixelStatsDev* a_stats, const PixelStatsDev* b_stats, int size, hipStream_t st)
 {
     hipLaunchKernelGGL(halves_variance_k, dim3((size + 255) / 256), dim3(256), 0, st, u, q, a_stats, b_stats, size);
+}
+void launch_cross_error(float* err, const float4* fa, const float4* fb, const float4* h0, const PixelStatsDev* s0, const float4* h1, const PixelStatsDev* s1,
+                        int size, hipStream_t st)
+{
+    hipLaunchKernelGGL(cross_error_k, dim3((size + 255) / 256), dim3(256), 0, st, err, fa, fb, h0, s0, h1, s1, size);
 }
 void launch_accumulate_stats(PixelStatsDev* dst, const PixelStatsDev* src, size_t n, hipStream_t st)
 {

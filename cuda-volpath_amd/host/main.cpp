@@ -67,6 +67,16 @@ static void usage()
            "                                                default 0.45), and both halves filtered with that one plane as their guide's\n"
            "                                                variance (vp_denoise_var).  --var-out writes the filtered plane as HDR.  The\n"
            "                                                refusals of --denoise-cross apply\n"
+           "               [--denoise-select [--denoise-select-radius R] [--denoise-select-patch F] [--denoise-select-smooth S]\n"
+           "                [--denoise-select-blend B] [--select-out FILE.hdr]]\n"
+           "                                                implies --denoise-var, at TWO windows with a per-pixel choice between them:\n"
+           "                                                candidate 0 is (--denoise-radius, --denoise-patch), candidate 1 is (R default 10,\n"
+           "                                                F default 3), --denoise-k is shared.  Each candidate's error is estimated per\n"
+           "                                                pixel from the half-buffers (vp_cross_error), the error maps are box-smoothed at\n"
+           "                                                radius S (default 1), the smaller wins, and the picks are blended over radius B\n"
+           "                                                (default 1) (vp_select; S and B 0..3).  --select-out writes the index map as HDR.\n"
+           "                                                --denoise-features applies to both candidates.  The refusals of --denoise-var\n"
+           "                                                apply; not with --resid-out\n"
            "               [--layers-out PREFIX] [--over R G B]\n"
            "                                                compositing layers (vp_render_frames_layers): the frames are rendered as a\n"
            "                                                foreground F and a per-channel transmittance T, pixel = F + T o B for any\n"
@@ -194,6 +204,10 @@ struct Options
     bool        denoise_var = false;     // --denoise-var: --denoise-cross with the pooled, pre-filtered variance plane
     vp_denoise_params dnv = {1, 3, 0.45f};   // (the paper's window; wider ones lost at (10, 3): DESIGN.md section 2.17)
     std::string var_out;
+    bool        denoise_select = false;  // --denoise-select: --denoise-var at two windows, the better one picked per pixel
+    vp_denoise_params dns = {10, 3, 0.45f};   // candidate 1's window (its k is dn's: --denoise-k is shared)
+    vp_select_params  sel = {1, 1};
+    std::string select_out;
     float       dn_sigma_alpha = 0.2f, dn_sigma_depth = 0.2f;   // (the best cell of a 3 x 3 grid on that scene: DESIGN.md section 2.13)
     std::string layers_out;
     bool        over = false;
@@ -286,13 +300,25 @@ void Options::parse(int argc, char** argv)
         else if (a == "--resid-out") { need(1); resid_out = argv[++i]; }
         else if (a == "--denoise-var") denoise_var = denoise_cross = denoise = true;
         else if (a == "--var-out") { need(1); var_out = argv[++i]; }
-        else if (a == "--denoise-radius" || a == "--denoise-patch" || a == "--denoise-k" || a == "--denoise-var-radius" || a == "--denoise-var-patch" ||
-                 a == "--denoise-var-k")
+        else if (a == "--denoise-select") denoise_select = denoise_var = denoise_cross = denoise = true;
+        else if (a == "--select-out") { need(1); select_out = argv[++i]; }
+        else if (a == "--denoise-select-smooth" || a == "--denoise-select-blend")
         {
             need(1);
             char* end = nullptr;
             const char* v = argv[++i];
-            vp_denoise_params& d = a.compare(0, 13, "--denoise-var") == 0 ? dnv : dn;   // the variance pass's window or the colour pass's
+            const long n = strtol(v, &end, 10);
+            if (end == v || *end || n < 0 || n > VP_SELECT_MAX_RADIUS) refuse(USAGE, "%s %s: a radius 0..%d", a.c_str(), v, VP_SELECT_MAX_RADIUS);
+            (a == "--denoise-select-smooth" ? sel.smooth_radius : sel.blend_radius) = (int)n;
+        }
+        else if (a == "--denoise-radius" || a == "--denoise-patch" || a == "--denoise-k" || a == "--denoise-var-radius" || a == "--denoise-var-patch" ||
+                 a == "--denoise-var-k" || a == "--denoise-select-radius" || a == "--denoise-select-patch")
+        {
+            need(1);
+            char* end = nullptr;
+            const char* v = argv[++i];
+            // the variance pass's window, the second candidate's or the colour pass's
+            vp_denoise_params& d = a.compare(0, 13, "--denoise-var") == 0 ? dnv : a.compare(0, 16, "--denoise-select") == 0 ? dns : dn;
             const char what = a[a.rfind('-') + 1];                                     // r, p or k
             bool ok;
             if (what == 'k') { d.k = strtof(v, &end); ok = end != v && !*end && std::isfinite(d.k) && d.k > 0.0f; }
@@ -393,6 +419,8 @@ static Mode refuse_conflicts(const Options& o)
         refuse(PLAIN, "--noise with --gpus %d: reducing per-pixel statistics across ranks is not part of adaptive sampling; use one GPU", o.gpus);
     if (!o.denoise_cross && !o.resid_out.empty()) refuse(PLAIN, "--resid-out needs --denoise-cross: the map is the disagreement of the two filtered halves");
     if (!o.denoise_var && !o.var_out.empty()) refuse(PLAIN, "--var-out needs --denoise-var: the map is the filtered variance plane of that stage");
+    if (!o.denoise_select && !o.select_out.empty()) refuse(PLAIN, "--select-out needs --denoise-select: the map is the index of the candidate picked per pixel");
+    if (o.denoise_select && !o.resid_out.empty()) refuse(PLAIN, "--denoise-select with --resid-out: a residual map of a blend of candidates is not defined here");
     if (o.denoise_cross && (other = first_of({{o.gpus > 1, "--gpus"}, {o.adaptive, "--noise"}, {!o.planes_out.empty(), "--planes-out"}, {!o.groups_out.empty(), "--groups-out"},
                                               {o.relit, "--sun-gain / --sky-gain"}, {!o.layers_out.empty(), "--layers-out"}, {o.over, "--over"}, {o.plane_adaptive, "--plane-noise"},
                                               {o.planes_adaptive, "--planes-noise"}, {o.groups_denoise, "--groups-denoise"}, {o.layers_denoise, "--layers-denoise"},
@@ -744,10 +772,49 @@ static void write_grey_map(const Job& j, const float* d_map, const std::string& 
     printf("wrote %s\n", name.c_str());
 }
 
+// --denoise-select: the two candidates of the cross-filter with the variance plane d_uf -- per candidate both halves filtered with the
+// roles swapped, the error estimate of the pair, the merge into the candidate's image -- and the selection into disp; --select-out: the
+// index map, the index as a grey value
+static void select_beauty(const Job& j, const Run& run, const float* d_uf, const vp_denoise_feature* f, int nf)
+{
+    const Options& o = j.o;
+    const Plane*   p = j.plane;
+    const int      W = o.W, H = o.H, npix = run.npix;
+    vp_denoise_params cand[2] = {o.dn, o.dns};
+    cand[1].k = o.dn.k;
+    vp_float4* d_img[2];
+    float*     d_err[2];
+    uint8_t*   d_index = o.select_out.empty() ? nullptr : (uint8_t*)vp_malloc((size_t)npix);
+    must(!o.select_out.empty() && !d_index);
+    for (int c = 0; c < 2; c++)
+    {
+        d_img[c] = device_alloc<vp_float4>(npix, false);
+        d_err[c] = device_alloc<float>(npix, false);
+        must(vp_denoise_var(p[0].mean, p[0].acc, p[0].rec, p[1].acc, p[1].rec, d_uf, f, nf, W, H, &cand[c]) ||
+             vp_denoise_var(p[1].mean, p[1].acc, p[1].rec, p[0].acc, p[0].rec, d_uf, f, nf, W, H, &cand[c]) ||
+             vp_cross_error(d_err[c], p[0].mean, p[1].mean, p[0].acc, p[0].rec, p[1].acc, p[1].rec, npix) ||
+             vp_merge_halves(d_img[c], nullptr, p[0].mean, p[0].rec, p[1].mean, p[1].rec, npix, p[0].floor));
+    }
+    must(vp_select(run.disp, d_index, d_img, d_err, 2, W, H, &o.sel));
+    if (d_index)
+    {
+        std::vector<uint8_t> idx((size_t)npix);
+        must(vp_download(idx.data(), d_index, (size_t)npix));
+        Image im(W, H);
+        for (int k = 0; k < npix; k++) { float* px = im.buffer() + 4 * (size_t)k; px[0] = px[1] = px[2] = px[3] = (float)idx[(size_t)k]; }
+        im.dump_hdr(o.select_out.c_str());
+        printf("wrote %s\n", o.select_out.c_str());
+    }
+    must(vp_synchronize());
+    for (int c = 0; c < 2; c++) { vp_free(d_img[c]); vp_free(d_err[c]); }
+    if (d_index) vp_free(d_index);
+}
+
 // the beauty image's filter into disp: the division by each pixel's count is part of the call.  --denoise-features: the feature pass
 // first, then the filter with three of its channels (alpha.y, zt and the cover flag).  --denoise-cross: each half with the other as
 // guide, then the merge -- and, for --resid-out, the residual map, which is returned (the caller writes and frees it).  --denoise-var:
-// the pooled variance of the halves and its filter in front, and both halves' filters with that plane as their guide's variance
+// the pooled variance of the halves and its filter in front, and both halves' filters with that plane as their guide's variance.
+// --denoise-select: that at two windows, each candidate's error estimate and merge, and the per-pixel selection into disp
 static float* denoise_beauty(const Job& j, const Run& run)
 {
     const Options& o = j.o;
@@ -776,7 +843,8 @@ static float* denoise_beauty(const Job& j, const Run& run)
             return o.denoise_var ? vp_denoise_var(p[a].mean, p[a].acc, p[a].rec, p[b].acc, p[b].rec, d_var[2], f, nf, W, H, &o.dn)
                                  : vp_denoise_guided(p[a].mean, p[a].acc, p[a].rec, p[b].acc, p[b].rec, f, nf, W, H, &o.dn);
         };
-        must(half(0, 1) || half(1, 0) || vp_merge_halves(run.disp, d_resid, p[0].mean, p[0].rec, p[1].mean, p[1].rec, npix, p[0].floor));
+        if (!o.denoise_select) must(half(0, 1) || half(1, 0) || vp_merge_halves(run.disp, d_resid, p[0].mean, p[0].rec, p[1].mean, p[1].rec, npix, p[0].floor));
+        else select_beauty(j, run, d_var[2], f, nf);
         if (!o.var_out.empty()) write_grey_map(j, d_var[2], o.var_out);
         if (o.denoise_var) must(vp_synchronize());
         for (float* d : d_var) if (d) vp_free(d);
@@ -791,6 +859,9 @@ static float* denoise_beauty(const Job& j, const Run& run)
     printf("denoised: radius %d, patch %d, k %g\n", o.dn.radius, o.dn.patch, o.dn.k);
     if (o.denoise_cross) printf("  cross-filtered: two half-buffers, each with the other's weights, merged by their counts\n");
     if (o.denoise_var) printf("  variance: pooled from both halves, filtered at radius %d, patch %d, k %g\n", o.dnv.radius, o.dnv.patch, o.dnv.k);
+    if (o.denoise_select)
+        printf("  selected per pixel against radius %d, patch %d: errors smoothed at radius %d, picks blended at radius %d\n", o.dns.radius, o.dns.patch,
+               o.sel.smooth_radius, o.sel.blend_radius);
     if (o.denoise_features) printf("  weights cut by features: sigma alpha %g, sigma depth %g\n", o.dn_sigma_alpha, o.dn_sigma_depth);
     return d_resid;
 }

@@ -43,6 +43,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_denoise_guided",
                  "vp_render_frames_halves_stats", "vp_merge_halves", "vp_accumulate_stats",
                  "vp_halves_variance", "vp_filter_variance", "vp_denoise_var",
+                 "vp_cross_error", "vp_select",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -130,6 +131,14 @@ class DenoiseFeature(C.Structure):
 DENOISE_MAX_FEATURES = 4
 
 
+class SelectParams(C.Structure):
+    """include/volpath.h vp_select_params"""
+    _fields_ = [("smooth_radius", C.c_int), ("blend_radius", C.c_int)]
+
+
+SELECT_MAX_CANDIDATES, SELECT_MAX_RADIUS = 4, 3
+
+
 class FeatureParams(C.Structure):
     """include/volpath.h vp_feature_params"""
     _fields_ = [("step", C.c_float), ("tau_z", C.c_float)]
@@ -180,6 +189,8 @@ def lib():
         L.vp_halves_variance.argtypes = [C.c_void_p] * 4 + [C.c_int]
         L.vp_filter_variance.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.POINTER(DenoiseParams)]
         L.vp_denoise_var.argtypes = [C.c_void_p] * 6 + [C.POINTER(DenoiseFeature), C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseParams)]
+        L.vp_cross_error.argtypes = [C.c_void_p] * 7 + [C.c_int]
+        L.vp_select.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(SelectParams)]
         L.vp_render_frames_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_int, C.c_float]
         L.vp_render_frames_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
@@ -704,6 +715,53 @@ def render_features(P, step, tau_z=FEATURE_TAU_Z_DEFAULT, alpha_ptr=None, depth_
     finally:
         a.free()
         d.free()
+
+
+def cross_error(err_ptr, fa_ptr, fb_ptr, h0, h0_stats, h1, h1_stats, n):
+    """err = one candidate's per-pixel error estimate: the filtered halves' MEAN images fa, fb held against the unfiltered means of the
+    other half, less their variance; unclamped (vp_cross_error); queued on the context's stream, never synchronises"""
+    _chk(lib().vp_cross_error(err_ptr, fa_ptr, fb_ptr, h0, h0_stats, h1, h1_stats, n))
+
+
+def select(dst_ptr, index_ptr, image_ptrs, error_ptrs, width, height, smooth=1, blend=1):
+    """dst = per pixel the candidate image whose box-smoothed error plane is smallest, the picks blended over (2 blend + 1)^2 pixels;
+    index_ptr (may be None) receives the pick as one byte per pixel (vp_select); dst may be one of the images"""
+    imgs = [getattr(p, "value", p) for p in image_ptrs]
+    errs = [getattr(p, "value", p) for p in error_ptrs]
+    if len(imgs) != len(errs):
+        raise ValueError("select: %d images and %d error planes" % (len(imgs), len(errs)))
+    n = len(imgs)
+    sp = SelectParams(smooth, blend)
+    _chk(lib().vp_select(dst_ptr, index_ptr, (C.c_void_p * max(n, 1))(*imgs), (C.c_void_p * max(n, 1))(*errs), n, width, height, C.byref(sp)))
+
+
+def denoise_select(dst_ptr, index_ptr, h0, h0_stats, h1, h1_stats, width, height, candidates=((5, 1, 0.45), (10, 3, 0.45)), smooth=1, blend=1,
+                   variance=(1, 3, 0.45), var_ptrs=None, tmp=None, features=None, floor_y=1e-3):
+    """the cross-filter at several windows with a per-pixel choice among them: the variance stage once; per candidate (R, F, k) both
+    halves through denoise_var with the roles swapped, cross_error of the pair, merge_halves into that candidate's image; then one
+    select() into dst (and index_ptr, may be None) -- all queued on the context's stream, nothing allocated, nothing synchronised.  The
+    caller supplies every device buffer: var_ptrs=(u, q, filtered), three planes of width * height floats, and tmp=(tmp_a, tmp_b, images,
+    errors): two float4 images for the filtered halves, and per candidate one float4 image and one float plane"""
+    cands = [tuple(c) for c in candidates]
+    if var_ptrs is None or len(var_ptrs) != 3:
+        raise ValueError("denoise_select: needs var_ptrs=(u, q, filtered), three device planes of width * height floats")
+    if tmp is None or len(tmp) != 4 or len(tmp[2]) != len(cands) or len(tmp[3]) != len(cands):
+        raise ValueError("denoise_select: needs tmp=(tmp_a, tmp_b, images, errors) with one float4 image and one float plane per candidate (%d)" % len(cands))
+    if not 1 <= len(cands) <= SELECT_MAX_CANDIDATES:
+        raise ValueError("denoise_select: %d candidates outside 1..%d" % (len(cands), SELECT_MAX_CANDIDATES))
+    tmp_a, tmp_b, images, errors = tmp
+    feats = tuple(features) if features else ()
+    vr, vf, vk = variance
+    u_ptr, q_ptr, uf_ptr = var_ptrs
+    n = width * height
+    halves_variance(u_ptr, q_ptr, h0_stats, h1_stats, n)
+    filter_variance(uf_ptr, u_ptr, q_ptr, width, height, vr, vf, vk)
+    for (radius, patch, k), img, err in zip(cands, images, errors):
+        denoise_var(tmp_a, h0, h0_stats, width, height, uf_ptr, feats, radius, patch, k, guide_ptr=h1, guide_stats_ptr=h1_stats)
+        denoise_var(tmp_b, h1, h1_stats, width, height, uf_ptr, feats, radius, patch, k, guide_ptr=h0, guide_stats_ptr=h0_stats)
+        cross_error(err, tmp_a, tmp_b, h0, h0_stats, h1, h1_stats, n)
+        merge_halves(img, None, tmp_a, h0_stats, tmp_b, h1_stats, n, floor_y)
+    select(dst_ptr, index_ptr, images, errors, width, height, smooth, blend)
 
 
 def set_denoise_form(form):

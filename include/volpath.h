@@ -480,6 +480,61 @@ int vp_denoise_var(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d
                    const vp_denoise_feature* features, int n_features,
                    int width, int height, const vp_denoise_params* dp);
 
+/* Per-pixel filter selection from cross-buffer error estimates: Rousselle, Manzi and Zwicker 2013 filter with
+ * several candidate windows, estimate each candidate's error per pixel, smooth the error maps, take the best candidate per pixel and
+ * smooth the selection.  The half-buffers supply the estimate: a half filtered with colours of its own is held against the UNFILTERED
+ * mean of the other half, whose noise the records measure.  Two calls; opt-in, the calls above keep their bits.  Binary32, one rounding
+ * per operation, no contraction, operations in the order written, unless marked binary64.  Both need no scene, run asynchronously on
+ * the context's stream behind what is queued there, never synchronise, and check their arguments before the device is touched.
+ *
+ * vp_cross_error: one candidate's per-pixel error estimate.  fa and fb are MEAN images of the two halves after some filter (what
+ * vp_denoise* or vp_scale_by_count(..., 1.0f) write), (h0, s0) and (h1, s1) the halves' accumulators and records.  Per pixel i:
+ *     c0 = h0[i].xyz * s_0,  s = n == 0 ? 0 : 1.0f / (float)n        vp_denoise's mean colours
+ *     y0 = lum(c0),  lum(x, y, z) = (0.2126f x + 0.7152f y) + 0.0722f z
+ *     v0 = vp_denoise's variance of the mean luminance from s0[i]: binary64, rounded once, 0 where n < 2
+ *     y1, v1 likewise from (h1, s1)
+ *     da = lum(fa[i]) - y1;   ea = da * da - v1;      db = lum(fb[i]) - y0;   eb = db * db - v0
+ *     err = (s0[i].n >= 2 && s1[i].n >= 2) ? 0.5f * (ea + eb) : 0.0f
+ *   err is NOT clamped: E[(f - y)^2] = (f - mu)^2 + Var(y) for f independent of y, so (f - y)^2 - v is an unbiased estimate of the
+ *   squared luminance error of the filtered half, and it may be negative.  Clamping before smoothing would bias it.  `flags` is never
+ *   read.  VP_E_ARG: any NULL pointer, d_err equal to an input, size < 0.
+ *   What the estimate is and is not: it sees LUMINANCE only, like every filter here.  It is unbiased only as far as fa is independent
+ *   of h1's noise: the WEIGHTS of a cross-filtered fa come from h1, and the variance stage pools both halves -- that dependence is
+ *   second order and it is not removed.  A self-guided candidate whose colours come from both halves is not a valid input.
+ *
+ * vp_select: smooth the errors, pick per pixel, blend the picks.  images and errors are HOST arrays of n device pointers (the kernel
+ * takes them by value in its argument block).  With Rs = smooth_radius, Rb = blend_radius:
+ *   Smoothed error: for ty = -Rs..Rs, top to bottom, row_ty = the sum over tx = -Rs..Rs, left to right and starting from 0.0f, of
+ *     errors[c] at p + (tx, ty); positions outside the image are skipped, and a row outside the image contributes nothing.  S = the sum
+ *     of the rows, top to bottom, starting from 0.0f.  E_c(p) = S / (float)count, count the number of in-image positions, one correctly
+ *     rounded divide.  The sums run row first so that a horizontal pass followed by a vertical pass gives the same bits.
+ *   Pick: k = 0; for c = 1..n-1: if (E_c(p) < E_k(p)) k = c.  Ties go to the lowest index: the order of the candidates is a
+ *     preference.  Inputs are assumed free of NaN.
+ *   Blend: W_c(p) = the number of in-image positions q in the (2 Rb + 1)^2 window of p with k(q) == c (an integer: no order matters),
+ *     T = the number of in-image positions.  W_k(p) == T: dst[p] = images[k(p)][p] bit for bit in all four channels.  Otherwise, per
+ *     channel of x, y, z:  num = 0.0f;  num = num + (float)W_c * images[c][p].ch for c = 0..n-1 in order;  dst[p].ch = num / (float)T.
+ *     dst[p].w = images[k(p)][p].w always: the heat or coverage channel is never blended, as it is never filtered.
+ *   Consequences: n = 1 is a copy.  Equal error planes give images[0].  A region where one candidate wins throughout carries that
+ *   candidate's bits.  A pixel that every candidate left unfiltered (a constant) keeps its value wherever all candidates agree on it
+ *   bit for bit and (n W c) / T rounds back to c -- always where one candidate holds the whole window.
+ *   d_index (may be NULL) receives k(p).  dst may be one of images: the call reads images at p only.
+ *   VP_E_ARG: NULL dst, images, errors or sp; n outside 1..VP_SELECT_MAX_CANDIDATES; a NULL entry; an error plane or d_index equal to
+ *   dst; width or height < 1; a radius outside 0..VP_SELECT_MAX_RADIUS.  vp_set_denoise_form applies (0: a workgroup per 32 x 8 tile,
+ *   the error planes staged in LDS once, horizontal then vertical sums; 1: a thread per pixel from global memory; the same bits) and
+ *   vp_last_denoise_form reports it.
+ * The pipeline: the variance stage once; per candidate (R, F, k): vp_denoise_var(A, h0, s0, h1, s1, uf, ...); vp_denoise_var(B, h1,
+ *   s1, h0, s0, uf, ...); vp_cross_error(err_c, A, B, h0, s0, h1, s1, n); vp_merge_halves(img_c, NULL, A, s0, B, s1, ...); then one
+ *   vp_select(dst, index, img, err, n, ...). */
+typedef struct { int smooth_radius, blend_radius; } vp_select_params;   /* 8 bytes */
+#define VP_SELECT_MAX_CANDIDATES 4
+#define VP_SELECT_MAX_RADIUS 3
+int vp_cross_error(float* d_err, const vp_float4* fa, const vp_float4* fb,
+                   const vp_float4* h0, const vp_pixel_stats* s0,
+                   const vp_float4* h1, const vp_pixel_stats* s1, int size);
+int vp_select(vp_float4* dst, uint8_t* d_index,
+              const vp_float4* const* images, const float* const* errors, int n,
+              int width, int height, const vp_select_params* sp);
+
 /* Compositing layers: a foreground F and a per-channel transmittance T with  pixel = F + T o B  for any
  * background B -- another sky, a plate, a second render.  vp_render_frames bakes the context's own sky into every sample and keeps
  * the reference's heat value in w; these two calls are what a compositor needs instead.

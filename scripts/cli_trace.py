@@ -41,6 +41,7 @@ SMALL = ["--julia", "8", "--size", "16", "8", "--spp", "4"]
 # the mode flags, each with valid operands
 MODE = [["--noise", "0.5"], ["--noise-out", "n.hdr"], ["--denoise"], ["--denoise-features"], ["--denoise-cross"], ["--resid-out", "r.hdr"],
         ["--denoise-var"], ["--var-out", "v.hdr"],
+        ["--denoise-select"], ["--select-out", "s.hdr"],
         ["--layers-out", "L"], ["--over", "0.1", "0.2", "0.3"], ["--layers-denoise"], ["--groups-out", "G"], ["--sun-gain", "1.5", "1", "0.5"],
         ["--sky-gain", "0.5", "1", "2"], ["--groups-denoise"], ["--plane-noise", "0.5", "0.25"], ["--plane-noise-out", "N"], ["--planes-out", "P"],
         ["--planes-denoise"], ["--planes-noise", "0.5", "0.25", "0.1"], ["--planes-noise-out", "M"], ["--features-out", "F"], ["--aa", "2"],
@@ -51,13 +52,13 @@ OTHER = [["--julia", "6"], ["--bin", "cloud.bin"], ["--bin", "missing.bin"], ["-
          ["--bin", "cloud.bin", "--volume-format", "f16"], ["--size", "9", "7"], ["--spp", "12"], ["--preset", "3"], ["--density", "200"], ["--g", "0.3"],
          ["--estimator", "bounded"], ["--estimator", "decomp"], ["--brick", "4"], ["--rng", "philox7"], ["--rng", "samplerh"], ["--tracking", "multichannel"],
          ["--env", "passive"], ["--arith", "exact"], ["--aa", "1"], ["--aa", "4"], ["--aa", "8"], ["--min-spp", "2"], ["--round", "1"], ["--denoise-radius", "3"],
-         ["--denoise-patch", "2"], ["--denoise-k", "0.3"], ["--denoise-var-radius", "2"], ["--denoise-var-patch", "1"], ["--denoise-var-k", "0.3"], ["--denoise-sigma-alpha", "0.5"], ["--denoise-sigma-depth", "0.5"], ["--feature-step", "0.01"],
+         ["--denoise-patch", "2"], ["--denoise-k", "0.3"], ["--denoise-var-radius", "2"], ["--denoise-var-patch", "1"], ["--denoise-var-k", "0.3"], ["--denoise-select-radius", "4"], ["--denoise-select-patch", "2"], ["--denoise-select-smooth", "2"], ["--denoise-select-blend", "0"], ["--denoise-sigma-alpha", "0.5"], ["--denoise-sigma-depth", "0.5"], ["--feature-step", "0.01"],
          ["--depth-tau", "1.5"], ["--sun", "0.3", "0.4"], ["--batch", "3"], ["--out", "x.ppm"], ["--gpus", "3", "--devices", "0,0,0"], ["--devices", "1"],
          ["--help"]]
 # invalid operands, once each; quirks: an unknown --estimator, --rng, --tracking or --env value silently means the default
 INVALID = [["--noise", "-1"], ["--noise", "x"], ["--noise", "nan"], ["--plane-noise", "0.5", "-1"], ["--plane-noise", "0.5"], ["--planes-noise", "0.1", "0.1", "nan"],
            ["--planes-noise", "0.1", "0.1", "--planes-out"], ["--over", "1", "2", "inf"], ["--over", "1", "2"], ["--sun-gain", "a", "b", "c"], ["--sky-gain", "1", "1", "1e99"],
-           ["--denoise-radius", "11"], ["--denoise-radius", "-1"], ["--denoise-patch", "4"], ["--denoise-k", "0"], ["--denoise-k", "inf"], ["--denoise-var-radius", "11"], ["--denoise-var-patch", "4"], ["--denoise-var-k", "0"],
+           ["--denoise-radius", "11"], ["--denoise-radius", "-1"], ["--denoise-patch", "4"], ["--denoise-k", "0"], ["--denoise-k", "inf"], ["--denoise-var-radius", "11"], ["--denoise-var-patch", "4"], ["--denoise-var-k", "0"], ["--denoise-select-radius", "11"], ["--denoise-select-patch", "4"], ["--denoise-select-smooth", "4"], ["--denoise-select-blend", "-1"],
            ["--denoise-sigma-alpha", "0"], ["--denoise-sigma-depth", "-1"], ["--feature-step", "0"], ["--depth-tau", "nan"], ["--aa", "3"], ["--arith", "quick"],
            ["--volume-format", "u16"], ["--estimator", "best"], ["--rng", "mt"], ["--tracking", "ratio"], ["--env", "both"], ["--preset", "13"], ["--gpus", "0"],
            ["--gpus", "2"], ["--gpus", "2", "--devices", "0"], ["--bogus"], ["--noise", "0.5", "--min-spp", "1"], ["--noise", "0.5", "--round", "0"],

@@ -281,6 +281,16 @@ int vp_denoise_var(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* r
     for (int k = 0; k < nf; k++) say(" {"), ptr(f[k].plane), i64(f[k].channel), flt(&f[k].sigma, 1), say(" }");
     return i64(w), i64(h), i64(dp->radius), i64(dp->patch), flt(&dp->k, 1), fill_floats(dst), done();
 }
+int vp_cross_error(float* err, const vp_float4* fa, const vp_float4* fb, const vp_float4* h0, const vp_pixel_stats* s0, const vp_float4* h1, const vp_pixel_stats* s1, int n)
+{
+    return begin("vp_cross_error"), ptr(err), ptr(fa), ptr(fb), ptr(h0), ptr(s0), ptr(h1), ptr(s1), i64(n), fill_floats(err), done();
+}
+int vp_select(vp_float4* dst, uint8_t* index, const vp_float4* const* images, const float* const* errors, int n, int w, int h, const vp_select_params* sp)
+{
+    begin("vp_select"), ptr(dst), ptr(index), i64(n);
+    for (int k = 0; k < n; k++) say(" {"), ptr(images[k]), ptr(errors[k]), say(" }");
+    return i64(w), i64(h), i64(sp->smooth_radius), i64(sp->blend_radius), fill_floats(dst), done();
+}
 int vp_composite(vp_float4* dst, const vp_float4* fg, const vp_float4* trans, const vp_float4* plate, const float rgb[3], int n, float s)
 {
     return begin("vp_composite"), ptr(dst), ptr(fg), ptr(trans), ptr(plate), flt(rgb, 3), i64(n), flt(&s, 1), fill_floats(dst), done();
