@@ -333,7 +333,11 @@ int vp_stats_rel_error(float* dst, const vp_pixel_stats* d_stats, int size, floa
  *   the same bits (running sums would not, and are not used).
  *   Exceptions: where the guide's v_p == 0 -- a noise-free or unmeasured pixel, every per-pixel-constant class -- dst[p].xyz = c_p,
  *   unfiltered.  dst[p].w = src[p].w * s_p always: the heat channel is never filtered.
- *   Inputs are assumed finite; then no NaN arises (e >= -1 / k2, and the centre weight is exactly 1: the denominator is >= 1).
+ *   Inputs are assumed finite and small enough that v_a + v_b and k2 * (v_a + v_b) stay finite: every variance of the mean at most
+ *   1.7e38 / max(1, k2) -- per-sample luminances up to about 1e19 / max(1, k) are safe.  Then e is no NaN and e >= -1 / k2, the centre
+ *   weight is exactly 1 and the denominator is >= 1.  In that range d * d may overflow: e = +inf and w = 0, as it should be.  Beyond
+ *   it e is (x - inf) / inf; the clamp at 0 makes D = 0 of a NaN (NaN > 0 is false), so dst still holds no NaN, but such an offset is
+ *   mixed in with weight 1: an answer without meaning.  The running sums stay finite while (2R+1)^2 |c| does.
  *   Refused with VP_E_ARG before the device is touched: NULL dst, src, d_stats or dp; exactly one of the two guide pointers; dst == src
  *   or dst == guide (the call reads neighbours: in place is not possible); width or height < 1; radius outside
  *   0..VP_DENOISE_MAX_RADIUS; patch outside 0..VP_DENOISE_MAX_PATCH; k not finite or not > 0.
@@ -370,7 +374,8 @@ int vp_last_denoise_form(void);
  *   value gives t = +inf, Dg = +inf and w = expf_(-inf) = 0 (the first line of expf_): such a pair is never mixed.  At the centre
  *   offset Df = 0 and D = 0, so w = 1 and the denominator stays >= 1.  Features are assumed free of NaN.
  *   Everything else is vp_denoise's: the mean colours, y, v and the pair term, the two sum orders, the v_p == 0 exception,
- *   dst.w = src.w * s_p, the role of the guide pair; no scene needed, asynchronous on the context's stream, never synchronises.
+ *   dst.w = src.w * s_p, the role of the guide pair, the safe range of v (Df and Dg have no NaN of their own: t_j >= 0 or +inf);
+ *   no scene needed, asynchronous on the context's stream, never synchronises.
  *   vp_set_denoise_form applies and vp_last_denoise_form reports it.  With n_features == 0 (features may then be NULL) the output is
  *   vp_denoise's byte for byte.  Feature planes may be src, guide or each other.
  *   Refused with VP_E_ARG before the device is touched, dst untouched: everything vp_denoise refuses; n_features outside
@@ -467,7 +472,8 @@ int vp_accumulate_stats(vp_pixel_stats* dst, const vp_pixel_stats* src, size_t n
  * vp_denoise_var: vp_denoise_guided with the variance supplied by the caller.  One change to the definition: wherever it reads v_a of
  * the guide -- the pair term and the v_p == 0 exception --
  *     v_a = d_sample_var[a'] * s_a'          s the GUIDE pair's 1.0f / (float)n, 0 where n == 0; one binary32 multiply
- *   -- a per-sample variance becomes the variance of that guide's mean.  Everything else, the features among it, is unchanged.  With
+ *   -- a per-sample variance becomes the variance of that guide's mean.  Everything else, the features among it, is unchanged, and
+ *   vp_denoise's safe range holds for this v: d_sample_var[a'] * s_a' at most 1.7e38 / max(1, k2).  With
  *   d_sample_var == NULL the output is vp_denoise_guided's byte for byte.  Refused: everything vp_denoise_guided refuses, and a plane
  *   that is dst.
  * The cross-filter with the stage: vp_render_frames_halves_stats(h0, h1, s0, s1, ...);  vp_halves_variance(u, q, s0, s1, n);
@@ -497,7 +503,10 @@ int vp_denoise_var(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d
  *     err = (s0[i].n >= 2 && s1[i].n >= 2) ? 0.5f * (ea + eb) : 0.0f
  *   err is NOT clamped: E[(f - y)^2] = (f - mu)^2 + Var(y) for f independent of y, so (f - y)^2 - v is an unbiased estimate of the
  *   squared luminance error of the filtered half, and it may be negative.  Clamping before smoothing would bias it.  `flags` is never
- *   read.  VP_E_ARG: any NULL pointer, d_err equal to an input, size < 0.
+ *   read.  Inputs are assumed finite with v0, v1 finite as binary32: variances of the mean up to 3.4e38, per-sample luminances up to
+ *   about 1e19.  Then err is no NaN; it is +inf where da * da or db * db overflows (|lum(f) - y| above 1.8e19) and -inf where ea + eb
+ *   does.  Nothing clamps here: a variance that rounds to +inf gives -inf, and NaN where the squared difference overflows too.
+ *   VP_E_ARG: any NULL pointer, d_err equal to an input, size < 0.
  *   What the estimate is and is not: it sees LUMINANCE only, like every filter here.  It is unbiased only as far as fa is independent
  *   of h1's noise: the WEIGHTS of a cross-filtered fa come from h1, and the variance stage pools both halves -- that dependence is
  *   second order and it is not removed.  A self-guided candidate whose colours come from both halves is not a valid input.

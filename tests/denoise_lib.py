@@ -97,9 +97,12 @@ def rel_l2(img, ref):
     return float(np.sqrt(((a - b) ** 2).sum() / (b ** 2).sum()))
 
 
-def synthetic(W, H, seed, flat_block=True):
+def synthetic(W, H, seed, flat_block=True, scale=1.0, flat_rect=None):
     """(acc, records) of a made-up render: n in {0, 1, 2, ...}, luminances from 1e-4 to 5e4, a block of identical samples (v = 0),
-    some FROZEN bits; the records are consistent with samples that could have been drawn (sum_y2 >= sum_y^2 / n up to rounding)"""
+    some FROZEN bits; the records are consistent with samples that could have been drawn (sum_y2 >= sum_y^2 / n up to rounding).
+    scale c: every luminance and colour times c -- sum_y and the colours times c, sum_y2 times c * c, in binary64; 1.0 changes no bit.
+    flat_rect (y0, y1, x0, x1): rows y0..y1-1, columns x0..x1-1 hold identical samples of dyadic luminances, lhs == 0 to the bit in
+    EVERY pixel of it (the flat block's odd columns are only rounding-small) -- a block that can cover whole 32 x 8 tiles"""
     rng = np.random.default_rng(seed)
     n = rng.choice(np.array([0, 1, 2, 3, 5, 16, 64, 1000], np.uint32), size=(H, W), p=[0.04, 0.04, 0.3, 0.25, 0.2, 0.1, 0.04, 0.03])
     # mean luminance per pixel: a ramp over the whole range with 10 % texture (so that patches resemble each other and the weights
@@ -111,6 +114,10 @@ def synthetic(W, H, seed, flat_block=True):
         by, bx = slice(H // 3, H // 3 + max(H // 4, 1)), slice(W // 4, W // 4 + max(W // 3, 1))
         spread[by, bx] = 0.0
         level[by, bx][:, ::2] = 0.5           # every other column exactly representable: lhs == 0 to the bit
+    if flat_rect is not None:
+        y0, y1, x0, x1 = flat_rect
+        spread[y0:y1, x0:x1] = 0.0
+        level[y0:y1, x0:x1] = (2.0 ** ((np.add.outer(np.arange(H), 2 * np.arange(W)) % 5) - 2))[y0:y1, x0:x1]      # 0.25 .. 4, all dyadic
     nd = n.astype(F64)
     rec = np.zeros((H, W), np.dtype([("sum_y", F64), ("sum_y2", F64), ("n", np.uint32), ("flags", np.uint32)]))
     rec["n"] = n
@@ -121,7 +128,9 @@ def synthetic(W, H, seed, flat_block=True):
     rec["flags"] = (rng.random((H, W)) < 0.3).astype(np.uint32)
     tint = rng.uniform(0.5, 1.5, size=(H, W, 3))
     acc = np.empty((H, W, 4), F32)
-    acc[..., :3] = (nd * level)[..., None] * tint
+    acc[..., :3] = ((nd * level)[..., None] * tint) * F64(scale)
     acc[..., 3] = rng.uniform(0, 50, size=(H, W)) * nd
     acc[n == 0] = 0
+    rec["sum_y"] = rec["sum_y"] * F64(scale)
+    rec["sum_y2"] = rec["sum_y2"] * (F64(scale) * F64(scale))
     return acc, rec

@@ -13,6 +13,7 @@ import variance_lib as V
 
 F32 = np.float32
 MAX_CANDIDATES, MAX_RADIUS = 4, 3
+TINY = F32(2.0 ** -137)       # error_planes(..., "tiny"): 49 values below 8 sum to less than 2^-126, the smallest normal number
 
 
 def cross_error(fa, fb, h0, r0, h1, r1):
@@ -131,7 +132,15 @@ def error_planes(W, H, n, seed, kind):
     """n synthetic error planes (H, W) float32.  kind "noise": normal values of both signs; "ties": values from a small set of dyadic
     numbers, so that whole windows sum to equal values in several candidates, and candidates 2 j and 2 j + 1 equal in the left half; "block":
     noise, with the last candidate far below the others in rows 0..23, columns 32..(whole tiles plus their halo of 6) -- clipped to the
-    image -- so that it wins 32 x 8 tiles throughout"""
+    image -- so that it wins 32 x 8 tiles throughout; "tiny": the "ties" planes in the left half of the image and the "noise" planes in
+    the right half, times TINY, a power of two that makes every value and every box sum of up to 7 x 7 of them subnormal or zero (the
+    dyadic values stay exact, so ties stay ties; the noise keeps 12 bits or so)"""
+    if kind == "tiny":
+        ties, noise = error_planes(W, H, n, seed, "ties"), error_planes(W, H, n, seed, "noise")
+        left = np.arange(W) < max(W // 2, 1)
+        out = [np.ascontiguousarray(np.where(left, t, z) * TINY, F32) for t, z in zip(ties, noise)]
+        assert all(p.dtype == F32 for p in out)
+        return out
     rng = np.random.default_rng(seed)
     if kind == "ties":
         e = rng.choice(np.array([-0.5, -0.25, 0.0, 0.25, 0.5], F32), size=(n, H, W))

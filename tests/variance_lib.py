@@ -130,13 +130,14 @@ def denoise_cross_var(h0, r0, h1, r1, radius, patch, k, variance=(1, 3, 0.45), f
     return dst, resid, fa, fb, uf
 
 
-def planes(W, H, seed, kind):
+def planes(W, H, seed, kind, scale=1.0):
     """(u, q) synthetic planes for vp_filter_variance, shaped like vp_halves_variance's output of a made-up pair of halves.
     kind "block": u == 0 in a block that covers the 32 x 8 tiles it can (rows 8..23, columns 32..95 clipped to the image; whole image
-    rows 0.. at small sizes) plus noise elsewhere; kind "isolated": single zeros scattered inside noisy tiles"""
+    rows 0.. at small sizes) plus noise elsewhere; kind "isolated": single zeros scattered inside noisy tiles.
+    scale: denoise_lib.synthetic's, on the luminances of both halves -- u grows with its square and q with its fourth power"""
     rng = np.random.default_rng(seed)
-    _, ra = D.synthetic(W, H, seed, flat_block=False)
-    _, rb = D.synthetic(W, H, seed + 1000, flat_block=False)
+    _, ra = D.synthetic(W, H, seed, flat_block=False, scale=scale)
+    _, rb = D.synthetic(W, H, seed + 1000, flat_block=False, scale=scale)
     u, q = halves_variance(ra, rb)
     if kind == "block":
         u[8:24, 32:96] = 0
