@@ -182,12 +182,16 @@ struct LaunchDev
 //   PLANES_LAYERS        fg, trans           an unscattered path's throughput goes to trans, its heat to fg; any other sample to fg
 //   PLANES_GROUPS        sun, sky            the first staging plane to sun, the second (LaunchDev::groups) to sky
 //   PLANES_GROUP_LAYERS  sun, sky, trans     unscattered: as a layers call, the heat to both groups; else as a groups call
-// A fifth mode is no mode of render_k (kPlaneModes stays the number of those): its launches are PLANES_ONE's, instance for instance --
-// the beauty kernels, their walks and constant writers, one staging plane, LaunchDev::layers 0 and LaunchDev::groups null, census kind
-// CENSUS_RENDER --, and only the reduce knows it:
+// A fifth constant is no mode of render_k (kPlaneModes stays the number of those) and names a reduce instance only: its launches are
+// PLANES_ONE's, instance for instance -- the beauty kernels, their walks and constant writers, one staging plane, LaunchDev::layers 0
+// and LaunchDev::groups null, census kind CENSUS_RENDER --, and only the reduce knows it:
 //   PLANES_HALVES        h0, h1              the beauty sample of frame f, whole, to plane half_of_frame(f) ALONE; the other plane
 //                                            receives no sample of that frame -- no +0.0f, no count (include/volpath.h
 //                                            vp_render_frames_halves_stats).  Records always; no adaptive and no compaction instance.
+// Halves are orthogonal to the split mode (PlaneSet::halves): "mode M, two halves" launches what mode M launches -- its render_k
+// instances, staging planes and census kind -- and the reduce hands the N samples that split_sample<M> makes of frame f to the N planes of
+// half half_of_frame(f) alone (include/volpath.h vp_render_frames_planes_halves_stats; reduce_plane_halves_k).  PLANES_HALVES above is
+// "PLANES_ONE, two halves": the constant stays the name of that reduce instance and is no value of PlaneSet::mode.
 constexpr int PLANES_ONE = 0, PLANES_LAYERS = 1, PLANES_GROUPS = 2, PLANES_GROUP_LAYERS = 3, kPlaneModes = 4, PLANES_HALVES = 4, kMaxPlanes = 3;
 constexpr int plane_mode(bool layers, bool groups) { return (layers ? PLANES_LAYERS : 0) | (groups ? PLANES_GROUPS : 0); }
 constexpr int planes_of(int mode) { return mode == PLANES_ONE ? 1 : mode == PLANES_GROUP_LAYERS ? 3 : 2; }
@@ -265,15 +269,17 @@ struct PixelStatsDev { double sum_y, sum_y2; unsigned n, flags; };
 // the table above, each with an accumulator and -- all planes or none -- a record buffer; an adaptive call adds each plane's criterion.
 struct PlaneSet
 {
-    int            mode;                // PLANES_*
-    float4*        acc[kMaxPlanes];     // planes_of(mode) accumulators of width * height pixels
-    PixelStatsDev* rec[kMaxPlanes];     // their records, indexed like the accumulators; rec[0] null: a call without statistics
+    int            mode;                // PLANES_ONE .. PLANES_GROUP_LAYERS: the split rule, and render_k's two bits
+    bool           halves;              // two halves of the mode's planes: half h's plane k is entry h * n() + k; records always, never adaptive
+    float4*        acc[2 * kMaxPlanes]; // count() accumulators of width * height pixels
+    PixelStatsDev* rec[2 * kMaxPlanes]; // their records, indexed like the accumulators; rec[0] null: a call without statistics
     double         tol[kMaxPlanes], fl[kMaxPlanes];   // adaptive: each plane's tolerance and floor (the binary32 arguments widened)
     unsigned       min_frames;          // adaptive: the samples a record needs before its criterion is asked
     bool           adaptive;            // a round of an adaptive call: its last launch freezes; false: `flags` is neither read nor written
     int  n() const { return planes_of(mode); }
-    bool layers() const { return mode < kPlaneModes && (mode & PLANES_LAYERS) != 0; }   // (render_k's two bits: PLANES_HALVES has neither)
-    bool groups() const { return mode < kPlaneModes && (mode & PLANES_GROUPS) != 0; }
+    int  count() const { return halves ? 2 * n() : n(); }   // the buffers of each kind the caller hands in
+    bool layers() const { return (mode & PLANES_LAYERS) != 0; }   // (render_k's two bits, with halves or without)
+    bool groups() const { return (mode & PLANES_GROUPS) != 0; }
     bool stats() const { return rec[0] != nullptr; }
 };
 // The reduce of a staged launch into the planes of S (reduce_planes_k<MODE, STATS, ADAPT>): per slot of L.pixels the staged frames in

@@ -659,6 +659,66 @@ __global__ __launch_bounds__(256) void reduce_planes_k<PLANES_HALVES, true, fals
         rec->sum_y = sy[k]; rec->sum_y2 = sy2[k]; rec->n = rec->n + cnt[k];
     }
 }
+// Halves of a call with planes (include/volpath.h vp_render_frames_planes_halves_stats; vp_kernels.h PlaneSet::halves): a body of its
+// own, so that the two above stay textually what the existing instances are compiled from.  One thread per (slot, half), the half from
+// blockIdx.y: the thread walks the staged frames of ITS half in frame order -- the ABSOLUTE frame L.frame0 + f decides --, splits each
+// by the mode's rule (split_sample<MODE>: the `unmarked` slots of the light kernel, the second staging plane of a groups mode) and adds
+// the N samples to the N planes of its half with the additions and binary64 sums of the primary body, in its order.  Within the half
+// the plane call's rule holds (a plane the sample does not feed is added +0.0f and counted); the other half's thread skips the frame,
+// so nothing is added there and a -0.0f stays.  A half without a frame in the launch writes no byte.  Every staged word is read once
+// (by the thread of its frame's half), coalesced across slots; the registers are those of the N-plane instance with records, and
+// twice the threads hide the latency of a memory-bound kernel.  `flags` is never touched.
+template <int N> struct ReduceHalvesDev { float4* acc[2][N]; PixelStatsDev* rec[2][N]; unsigned light_from, light_to; };
+template <int MODE>
+__global__ __launch_bounds__(256) void reduce_plane_halves_k(LaunchDev L, ReduceHalvesDev<planes_of(MODE)> D)
+{
+    constexpr int N = planes_of(MODE);
+    const unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    const int      half = (int)blockIdx.y;   // (uniform: the pointers below are scalar selects, not an indexed kernel argument)
+    if (slot >= L.nslots) return;
+    const unsigned pix = L.pixels[slot];
+    const size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * L.P.width;
+    float4*        acc[N];
+    PixelStatsDev* rec[N];
+    float4         a[N];
+    double         sy[N], sy2[N];
+    unsigned       cnt = 0;
+#pragma unroll
+    for (int k = 0; k < N; k++)
+    {
+        acc[k] = (half ? D.acc[1][k] : D.acc[0][k]) + idx;
+        rec[k] = (half ? D.rec[1][k] : D.rec[0][k]) + idx;
+        a[k] = *acc[k];
+        sy[k] = rec[k]->sum_y; sy2[k] = rec[k]->sum_y2;
+    }
+    const bool    unmarked = (MODE & PLANES_LAYERS) && slot >= D.light_from && slot < D.light_to;
+    const bool    constant = slot >= L.const_from;
+    const size_t  stride   = constant ? 0 : L.stage_stride;
+    const float4* stage    = (constant ? L.stage_const : L.stage) + slot;
+    const float4* plane2   = (MODE & PLANES_GROUPS) ? L.groups + slot : nullptr;
+    for (int f = 0; f < L.nframes; f++)
+    {
+        if (half_of_frame(L.frame0 + f, L.sub_shift) != half) continue;
+        float4 s[N];
+        split_sample<MODE>(stage[(size_t)f * stride], plane2 + (size_t)f * stride, unmarked, s);
+#pragma unroll
+        for (int k = 0; k < N; k++)
+        {
+            a[k] = make_float4(a[k].x + s[k].x, a[k].y + s[k].y, a[k].z + s[k].z, a[k].w + s[k].w);
+            const double y = (double)stats_luminance(s[k]);
+            sy[k]  = sy[k] + y;
+            sy2[k] = sy2[k] + y * y;
+        }
+        cnt++;
+    }
+    if (!cnt) return;
+#pragma unroll
+    for (int k = 0; k < N; k++)
+    {
+        *acc[k] = a[k];
+        rec[k]->sum_y = sy[k]; rec[k]->sum_y2 = sy2[k]; rec[k]->n = rec[k]->n + cnt;
+    }
+}
 // A stable compaction of a class-ordered pixel list (src: n[0] general, n[1] light, n[2] box-missing pixels) by the FROZEN bit of the
 // pixels' records: the active pixels of each class in the order they have in src, class by class, and the three counts.  The pattern of
 // pixlist_*_k: per-block class counts, pixlist_scan_k over them, the scatter with wave-ballot ranks.  N: the record buffers of the
@@ -1831,9 +1891,26 @@ static void launch_reduce_instance(const LaunchDev& L, const PlaneSet& S, unsign
     hipLaunchKernelGGL((reduce_planes_k<MODE, STATS, ADAPT>), dim3((L.nslots + 255) / 256), dim3(256), 0, st, L, D);
 }
 template <int MODE>
+static void launch_reduce_halves(const LaunchDev& L, const PlaneSet& S, unsigned light_from, unsigned light_to, hipStream_t st)
+{
+    // (the beauty halves keep their instance: one thread per slot for both planes)
+    if constexpr (MODE == PLANES_ONE) launch_reduce_instance<PLANES_HALVES, true, false>(L, S, light_from, light_to, st);
+    else
+    {
+        constexpr int N = planes_of(MODE);
+        ReduceHalvesDev<N> D;
+        D.light_from = light_from; D.light_to = light_to;
+        for (int h = 0; h < 2; h++)
+            for (int k = 0; k < N; k++) { D.acc[h][k] = S.acc[h * N + k]; D.rec[h][k] = S.rec[h * N + k]; }
+        hipLaunchKernelGGL((reduce_plane_halves_k<MODE>), dim3((L.nslots + 255) / 256, 2), dim3(256), 0, st, L, D);
+    }
+}
+template <int MODE>
 static void launch_reduce_mode(const LaunchDev& L, const PlaneSet& S, unsigned light_from, unsigned light_to, bool last, hipStream_t st)
 {
-    if (!S.stats())
+    // (halves -- one form per mode: the entry points always hand in records and never run adaptive rounds)
+    if (S.halves) launch_reduce_halves<MODE>(L, S, light_from, light_to, st);
+    else if (!S.stats())
     {
         // (one plane, no records: reduce_stage_k, the reduce the benchmark times, stays the kernel it was)
         if constexpr (MODE == PLANES_ONE) launch_reduce(L, st);
@@ -1849,8 +1926,6 @@ void launch_reduce_planes(const LaunchDev& L, const PlaneSet& S, unsigned light_
     case PLANES_ONE: launch_reduce_mode<PLANES_ONE>(L, S, light_from, light_to, last, st); break;
     case PLANES_LAYERS: launch_reduce_mode<PLANES_LAYERS>(L, S, light_from, light_to, last, st); break;
     case PLANES_GROUPS: launch_reduce_mode<PLANES_GROUPS>(L, S, light_from, light_to, last, st); break;
-    // (one form: the entry point always hands in records and never runs adaptive rounds)
-    case PLANES_HALVES: launch_reduce_instance<PLANES_HALVES, true, false>(L, S, light_from, light_to, st); break;
     default: launch_reduce_mode<PLANES_GROUP_LAYERS>(L, S, light_from, light_to, last, st); break;
     }
 }

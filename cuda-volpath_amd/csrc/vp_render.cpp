@@ -225,7 +225,7 @@ struct LaunchPlan
     bool       stage_only;        // ... which is staged whole and not reduced
     PlaneSet   PS;                // what the call accumulates into (vp_kernels.h): its mode, accumulators, records and criterion; PS.acc[0] is d_out
     size_t stage_planes() const { return PS.groups() ? 2u : 1u; }   // staging planes per frame: a groups mode stages the sky's samples in a second
-                                                                    // (NOT the call's planes: PLANES_HALVES has two accumulators and stages one)
+                                                                    // (NOT the call's planes: halves double the accumulators and stage what the mode stages)
     bool plain() const { return PS.mode == PLANES_ONE && !PS.stats(); }   // vp_render_frames' own call: one plane, no records (a halves call
                                                                           // is not: staged for one frame too, never pipelined)
     // the slots of the list, general pixels first: where the class a kernel integrates ends (the general class and a light class that
@@ -682,13 +682,13 @@ int plane_state_check(const char* fn, bool groups)
     if (G.arith == VP_ARITH_FAST) return fail(VP_E_STATE, "%s is built for the exact arithmetic only (its kernel instances are the exact unit's)", fn);
     return VP_OK;
 }
-// the planes a caller hands in: planes_of(mode) accumulators, all given and all different; with_stats: as many record buffers likewise.
+// the planes a caller hands in: planes_of(mode) accumulators -- of each half, with halves --, all given and all different; with_stats: as many record buffers likewise.
 // 0: so they are; 1: a null pointer among them; 2: one buffer given twice
 int plane_buffers_check(const PlaneSet& S, bool with_stats)
 {
-    for (int k = 0; k < S.n(); k++)
+    for (int k = 0; k < S.count(); k++)
         if (!S.acc[k] || (with_stats && !S.rec[k])) return 1;
-    for (int k = 1; k < S.n(); k++)
+    for (int k = 1; k < S.count(); k++)
         for (int j = 0; j < k; j++)
             if (S.acc[j] == S.acc[k] || (with_stats && S.rec[j] == S.rec[k])) return 2;
     return 0;
@@ -750,13 +750,14 @@ int vp_render_frames_group_layers_stats(vp_float4* d_sun, vp_float4* d_sky, vp_f
     return plane_call("vp_render_frames_group_layers_stats", plane_set(PLANES_GROUP_LAYERS, d_sun, d_sky, d_trans, d_sun_stats, d_sky_stats, d_trans_stats), true,
                       first_frame, n_frames, p);
 }
-// Half-buffer renders (include/volpath.h; vp_kernels.h PLANES_HALVES): vp_render_frames_stats' launches -- the mode sets neither
+// Half-buffer renders (include/volpath.h; vp_kernels.h PLANES_ONE with PlaneSet::halves): vp_render_frames_stats' launches -- the mode sets neither
 // LaunchDev::layers nor LaunchDev::groups, so every kernel is the beauty instance and nothing a plane call refuses is refused -- into one
 // staging plane, and a reduce that hands frame f to half_of_frame(f).  Serial on the caller's stream like a plane call.
 int vp_render_frames_halves_stats(vp_float4* d_h0, vp_float4* d_h1, vp_pixel_stats* d_h0_stats, vp_pixel_stats* d_h1_stats, int first_frame, int n_frames,
                                   const Param* p)
 {
-    const PlaneSet S = plane_set(PLANES_HALVES, d_h0, d_h1, nullptr, d_h0_stats, d_h1_stats);
+    PlaneSet S = plane_set(PLANES_ONE, d_h0, d_h1, nullptr, d_h0_stats, d_h1_stats);
+    S.halves = true;
     const int bad = plane_buffers_check(S, true);
     if (bad == 1 || !p) return fail(VP_E_ARG, "vp_render_frames_halves_stats: null pointer");
     if (bad) return fail(VP_E_ARG, "vp_render_frames_halves_stats: the two accumulators, and the two record buffers, are different buffers");
@@ -766,6 +767,32 @@ int vp_render_frames_halves_stats(vp_float4* d_h0, vp_float4* d_h1, vp_pixel_sta
     if (rc) return rc;
     if ((rc = la_quiesce())) return rc;
     return do_render(d_h0, first_frame, n_frames, p, false, nullptr, nullptr, &S);
+}
+// Halves of a call with planes (include/volpath.h; vp_kernels.h PlaneSet::halves): the plane call's launches, staging and state check,
+// and a reduce that hands the planes' samples of frame f to the planes of half half_of_frame(f).
+int vp_render_frames_planes_halves_stats(int mode, const vp_plane_bufs* h0, const vp_plane_bufs* h1, int first_frame, int n_frames, const Param* p)
+{
+    static const char fn[] = "vp_render_frames_planes_halves_stats";
+    if (mode != VP_PLANES_LAYERS && mode != VP_PLANES_GROUPS && mode != VP_PLANES_GROUP_LAYERS) return fail(VP_E_ARG, "%s: unknown mode %d", fn, mode);
+    if (!h0 || !h1 || !p) return fail(VP_E_ARG, "%s: null pointer", fn);
+    static_assert(VP_PLANES_LAYERS == PLANES_LAYERS && VP_PLANES_GROUPS == PLANES_GROUPS && VP_PLANES_GROUP_LAYERS == PLANES_GROUP_LAYERS, "the public modes are the plane modes");
+    PlaneSet S = {};
+    S.mode = mode; S.halves = true;
+    for (int h = 0; h < 2; h++)
+        for (int k = 0; k < S.n(); k++)
+        {
+            S.acc[h * S.n() + k] = (float4*)(h ? h1 : h0)->acc[k];
+            S.rec[h * S.n() + k] = (PixelStatsDev*)(h ? h1 : h0)->rec[k];
+        }
+    const int bad = plane_buffers_check(S, true);
+    if (bad == 1) return fail(VP_E_ARG, "%s: null pointer among the planes of a half", fn);
+    if (bad) return fail(VP_E_ARG, "%s: the accumulators of the two halves, and their record buffers, are all different buffers", fn);
+    if (n_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "%s: frames [%d, %d + %d) out of range", fn, first_frame, first_frame, n_frames);
+    int rc = plane_state_check(fn, S.groups());
+    if (rc) return rc;
+    if ((rc = ensure_device())) return rc;
+    if ((rc = la_quiesce())) return rc;
+    return do_render((vp_float4*)S.acc[0], first_frame, n_frames, p, false, nullptr, nullptr, &S);
 }
 int vp_relight_composite(vp_float4* dst, const vp_float4* sun, const vp_float4* sky, const vp_float4* trans, const float sun_gain[3], const float sky_gain[3],
                          const vp_float4* plate, const float plate_rgb[3], int size, float scale)

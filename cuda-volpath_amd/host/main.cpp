@@ -130,6 +130,21 @@ static void usage()
            "                                                means are vp_denoise's from the adaptive records.  --planes-noise-out writes one\n"
            "                                                noise map per plane (PREFIX_sun.hdr, PREFIX_sky.hdr, PREFIX_trans.hdr).  One GPU;\n"
            "                                                not with --noise or --denoise\n"
+           "               [--layers-denoise-cross] [--groups-denoise-cross] [--planes-denoise-cross]\n"
+           "               [--plane-denoise-var] [--plane-resid-out PREFIX]\n"
+           "                                                the cross-filter on planes: each implies the mode's --layers-denoise /\n"
+           "                                                --groups-denoise / --planes-denoise and needs what that flag needs.  The frames go\n"
+           "                                                through vp_render_frames_planes_halves_stats into two halves of every plane (even\n"
+           "                                                and odd frames; with --aa S blocks of S^2 frames); each plane's mean is the\n"
+           "                                                vp_merge_halves of its two halves, each filtered by vp_denoise with the OTHER\n"
+           "                                                half as guide (--denoise-radius, -patch, -k apply; no features, as for the\n"
+           "                                                mode's -denoise flag); --out is their vp_composite / vp_relight /\n"
+           "                                                vp_relight_composite as before.  --plane-denoise-var puts the variance stage in\n"
+           "                                                front of each plane's pair of filters (vp_halves_variance, vp_filter_variance,\n"
+           "                                                vp_denoise_var; --denoise-var-radius, -patch, -k apply).  --plane-resid-out\n"
+           "                                                writes one residual map per plane (PREFIX_sun.hdr ...), with the plane's floor\n"
+           "                                                (1e-3; trans 1e-2).  One GPU; not with --noise, --plane-noise, --planes-noise or\n"
+           "                                                --denoise-cross / -var / -select\n"
            "               [--features-out PREFIX [--feature-step DT] [--depth-tau TAU]]\n"
            "                                                the feature pass (vp_render_features), a deterministic march along every pixel's\n"
            "                                                camera ray with step DT (default 0.001), after the render and beside every other\n"
@@ -224,6 +239,9 @@ struct Options
     bool        planes_adaptive = false;
     float       planes_tol[3] = {0.0f, 0.0f, 0.0f};
     std::string planes_noise_out;
+    bool        layers_cross = false, groups_cross = false, planes_cross = false;   // --*-denoise-cross: the mode's filter flag, on two halves of every plane
+    bool        plane_denoise_var = false;   // --plane-denoise-var: the variance stage in front of each plane's pair of filters
+    std::string plane_resid_out;
     std::string features_out;
     vp_feature_params feat = {0.001f, VP_FEATURE_TAU_Z_DEFAULT};
 
@@ -344,6 +362,11 @@ void Options::parse(int argc, char** argv)
         else if (a == "--planes-denoise") planes_denoise = true;
         else if (a == "--groups-denoise") groups_denoise = true;
         else if (a == "--layers-denoise") layers_denoise = true;
+        else if (a == "--planes-denoise-cross") planes_cross = planes_denoise = true;
+        else if (a == "--groups-denoise-cross") groups_cross = groups_denoise = true;
+        else if (a == "--layers-denoise-cross") layers_cross = layers_denoise = true;
+        else if (a == "--plane-denoise-var") plane_denoise_var = true;
+        else if (a == "--plane-resid-out") { need(1); plane_resid_out = argv[++i]; }
         else if (a == "--sun") { need(2); sunx = (float)atof(argv[++i]); suny = (float)atof(argv[++i]); }
         else if (a == "--batch") { need(1); batch = atoi(argv[++i]); }
         else if (a == "--out") { need(1); out = argv[++i]; }
@@ -385,6 +408,8 @@ struct Job
     int              batch = 0;
     bool             hdr = false;        // --out is the scaled accumulator, not its gamma-corrected bytes
     Mode             mode = BEAUTY;
+    bool             cross = false;      // planes in two halves (--*-denoise-cross): plane[k] is half 0's, other[k] half 1's, the mean the cross-filter's
+    Plane            other[3] = {};
     int              n = 1;              // planes: beauty 1 (--denoise-cross 2: its half-buffers), layers fg trans, groups sun sky, planes sun sky trans
     Plane            plane[3] = {};
     bool             filter = false;     // the mean of a plane is vp_denoise's (beauty: --denoise and its variants)
@@ -421,6 +446,16 @@ static Mode refuse_conflicts(const Options& o)
     if (!o.denoise_var && !o.var_out.empty()) refuse(PLAIN, "--var-out needs --denoise-var: the map is the filtered variance plane of that stage");
     if (!o.denoise_select && !o.select_out.empty()) refuse(PLAIN, "--select-out needs --denoise-select: the map is the index of the candidate picked per pixel");
     if (o.denoise_select && !o.resid_out.empty()) refuse(PLAIN, "--denoise-select with --resid-out: a residual map of a blend of candidates is not defined here");
+    // the cross-filter on planes: one GPU, no adaptive rounds of any kind, and not beside the beauty image's cross-filter
+    const char* plane_cross = first_of({{o.layers_cross, "--layers-denoise-cross"}, {o.groups_cross, "--groups-denoise-cross"}, {o.planes_cross, "--planes-denoise-cross"}});
+    if (!plane_cross && o.plane_denoise_var)
+        refuse(PLAIN, "--plane-denoise-var needs --layers-denoise-cross, --groups-denoise-cross or --planes-denoise-cross: it is the variance stage of that filter");
+    if (!plane_cross && !o.plane_resid_out.empty())
+        refuse(PLAIN, "--plane-resid-out needs --layers-denoise-cross, --groups-denoise-cross or --planes-denoise-cross: the maps are the disagreement of each plane's two filtered halves");
+    if (plane_cross && (other = first_of({{o.gpus > 1, "--gpus"}, {o.adaptive, "--noise"}, {o.plane_adaptive, "--plane-noise"}, {o.planes_adaptive, "--planes-noise"},
+                                          {o.denoise_select, "--denoise-select"}, {o.denoise_var, "--denoise-var"}, {o.denoise_cross, "--denoise-cross"}})))
+        refuse(PLAIN, "%s with %s: the halves' records are not reduced across ranks, adaptive rounds on halves are not built and the beauty image's halves are "
+               "its own; use one GPU without --noise, --plane-noise, --planes-noise and --denoise-cross / -var / -select", plane_cross, other);
     if (o.denoise_cross && (other = first_of({{o.gpus > 1, "--gpus"}, {o.adaptive, "--noise"}, {!o.planes_out.empty(), "--planes-out"}, {!o.groups_out.empty(), "--groups-out"},
                                               {o.relit, "--sun-gain / --sky-gain"}, {!o.layers_out.empty(), "--layers-out"}, {o.over, "--over"}, {o.plane_adaptive, "--plane-noise"},
                                               {o.planes_adaptive, "--planes-noise"}, {o.groups_denoise, "--groups-denoise"}, {o.layers_denoise, "--layers-denoise"},
@@ -517,13 +552,17 @@ static Job validate(const Options& o)
         j.plane[0] = layers ? kFg : kSun, j.plane[1] = layers ? kTrans : kSky, j.n = 2;
         j.filter = layers ? o.layers_denoise : o.groups_denoise, j.prefix = layers ? o.layers_out : o.groups_out;
         j.adaptive = o.plane_adaptive, j.noise_flag = "--plane-noise", j.noise_prefix = o.plane_noise_out, tol = o.plane_tol;
+        j.cross = layers ? o.layers_cross : o.groups_cross;
         break;
     case PLANES:
         j.plane[0] = kSun, j.plane[1] = kSky, j.plane[2] = kTrans, j.n = 3;
         j.filter = o.planes_denoise, j.prefix = o.planes_out;
         j.adaptive = o.planes_adaptive, j.noise_flag = "--planes-noise", j.noise_prefix = o.planes_noise_out, tol = o.planes_tol;
+        j.cross = o.planes_cross;
         break;
     }
+    // (a cross flag of another mode than the run's: that mode's refusals took it above, as they take its -denoise flag)
+    for (int k = 0; k < j.n && j.cross; k++) j.other[k] = j.plane[k];
     for (int k = 0; k < j.n && j.adaptive; k++) j.tol[k] = tol[k];
     j.records = j.filter || j.adaptive;
     j.means   = j.mode == BEAUTY ? o.denoise_cross : j.records;   // (the beauty image's mean is formed in the display buffer)
@@ -628,6 +667,11 @@ static void alloc_planes(Job& j, const Run& run)
         p.acc = k ? device_alloc<vp_float4>(run.npix, true) : run.accum[0];
         if (j.records) p.rec = device_alloc<vp_pixel_stats>(run.npix, true);
         if (j.means) p.mean = device_alloc<vp_float4>(run.npix, false);
+        if (!j.cross) continue;
+        Plane& q = j.other[k];   // the second half of the plane: all three buffers its own
+        q.acc = device_alloc<vp_float4>(run.npix, true);
+        q.rec = device_alloc<vp_pixel_stats>(run.npix, true);
+        q.mean = device_alloc<vp_float4>(run.npix, false);
     }
 }
 static void free_planes(Job& j)
@@ -638,6 +682,8 @@ static void free_planes(Job& j)
         if (p.rec) vp_free(p.rec);
         if (p.mean) vp_free(p.mean);
         if (k) vp_free(p.acc);
+        const Plane& q = j.other[k];
+        if (q.acc) { vp_free(q.acc); vp_free(q.rec); vp_free(q.mean); }
     }
 }
 
@@ -646,6 +692,12 @@ static int render_frames(const Job& j, int s, int n)
 {
     const Plane* p = j.plane;
     const Param* P = &j.P;
+    if (j.cross)   // the mode's _stats call, its frames split between the two halves of every plane
+    {
+        vp_plane_bufs h[2] = {};
+        for (int k = 0; k < j.n; k++) h[0].acc[k] = p[k].acc, h[0].rec[k] = p[k].rec, h[1].acc[k] = j.other[k].acc, h[1].rec[k] = j.other[k].rec;
+        return vp_render_frames_planes_halves_stats(j.mode == PLANES ? VP_PLANES_GROUP_LAYERS : j.mode == LAYERS ? VP_PLANES_LAYERS : VP_PLANES_GROUPS, &h[0], &h[1], s, n, P);
+    }
     switch (j.mode)
     {
     case PLANES:
@@ -888,6 +940,33 @@ static void write_features(const Job& j, const Run& run)
     vp_free(d_depth);
 }
 
+// --*-denoise-cross: the mean of every plane from its two halves -- each half filtered with the other as guide, the two merged by their
+// counts into the plane's mean; --plane-denoise-var: the pooled variance of the plane's halves and its filter in front, both filters
+// with that plane as their guide's variance; --plane-resid-out: the residual map of each plane, with the plane's floor
+static void cross_planes(const Job& j, const Run& run)
+{
+    const Options& o = j.o;
+    const int      W = o.W, H = o.H, npix = run.npix;
+    float*         d_var[3] = {};   // u, q and the filtered plane, one plane after the other
+    for (int k = 0; k < 3 && o.plane_denoise_var; k++) d_var[k] = device_alloc<float>(npix, false);
+    float* d_resid = o.plane_resid_out.empty() ? nullptr : device_alloc<float>(npix, false);
+    for (int k = 0; k < j.n; k++)
+    {
+        const Plane& a = j.plane[k];
+        const Plane& b = j.other[k];
+        if (o.plane_denoise_var)
+            must(vp_halves_variance(d_var[0], d_var[1], a.rec, b.rec, npix) || vp_filter_variance(d_var[2], d_var[0], d_var[1], W, H, &o.dnv) ||
+                 vp_denoise_var(a.mean, a.acc, a.rec, b.acc, b.rec, d_var[2], nullptr, 0, W, H, &o.dn) ||
+                 vp_denoise_var(b.mean, b.acc, b.rec, a.acc, a.rec, d_var[2], nullptr, 0, W, H, &o.dn));
+        else must(vp_denoise(a.mean, a.acc, a.rec, b.acc, b.rec, W, H, &o.dn) || vp_denoise(b.mean, b.acc, b.rec, a.acc, a.rec, W, H, &o.dn));
+        must(vp_merge_halves(a.mean, d_resid, a.mean, a.rec, b.mean, b.rec, npix, a.floor));
+        if (d_resid) write_grey_map(j, d_resid, o.plane_resid_out + a.suffix);
+    }
+    must(vp_synchronize());
+    for (float* d : d_var) if (d) vp_free(d);
+    if (d_resid) vp_free(d_resid);
+}
+
 static void write_outputs(const Job& j, const Run& run)
 {
     const Options& o = j.o;
@@ -904,9 +983,11 @@ static void write_outputs(const Job& j, const Run& run)
         // vp_denoise; w is never filtered), by the pixels' own counts after adaptive rounds, or by the one count of all --, written where a
         // prefix is given; then the planes' combination in place of the beauty image, the means with scale 1
         const vp_float4* m[3] = {};
+        if (j.cross) cross_planes(j, run);
         for (int k = 0; k < j.n; k++)
         {
-            if (j.filter) must(vp_denoise(p[k].mean, p[k].acc, p[k].rec, nullptr, nullptr, W, H, &o.dn));
+            if (j.cross) {}   // (the means are the cross-filter's)
+            else if (j.filter) must(vp_denoise(p[k].mean, p[k].acc, p[k].rec, nullptr, nullptr, W, H, &o.dn));
             else if (j.adaptive) must(vp_scale_by_count(p[k].mean, p[k].acc, p[k].rec, npix, 1.0f));
             else if (!j.prefix.empty()) scale(disp, p[k].acc, npix, per_frame);
             m[k] = j.means ? p[k].mean : p[k].acc;
@@ -917,6 +998,8 @@ static void write_outputs(const Job& j, const Run& run)
         else if (j.mode == GROUPS) must(vp_relight(disp, m[0], m[1], o.sun_gain, o.sky_gain, npix, s));
         else if (o.over) must(vp_composite(disp, m[0], m[1], nullptr, o.over_rgb, npix, s));
         if (j.filter) printf("denoised per plane: radius %d, patch %d, k %g\n", o.dn.radius, o.dn.patch, o.dn.k);
+        if (j.cross) printf("  cross-filtered: two halves of every plane, each with the other's weights, merged by their counts\n");
+        if (j.cross && o.plane_denoise_var) printf("  variance: pooled from both halves of a plane, filtered at radius %d, patch %d, k %g\n", o.dnv.radius, o.dnv.patch, o.dnv.k);
     }
     else if (j.filter) d_resid = denoise_beauty(j, run);
     else if (j.adaptive) must(vp_scale_by_count(disp, p[0].acc, p[0].rec, npix, 1.0f));   // every pixel by its own count (the reference's scale assumes one count for all)

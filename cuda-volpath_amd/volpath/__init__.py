@@ -44,6 +44,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_render_frames_halves_stats", "vp_merge_halves", "vp_accumulate_stats",
                  "vp_halves_variance", "vp_filter_variance", "vp_denoise_var",
                  "vp_cross_error", "vp_select",
+                 "vp_render_frames_planes_halves_stats",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -139,6 +140,16 @@ class SelectParams(C.Structure):
 SELECT_MAX_CANDIDATES, SELECT_MAX_RADIUS = 4, 3
 
 
+# include/volpath.h VP_PLANES_*: the modes of vp_render_frames_planes_halves_stats, and each mode's planes in order
+PLANES_LAYERS, PLANES_GROUPS, PLANES_GROUP_LAYERS = 1, 2, 3
+PLANE_NAMES = {PLANES_LAYERS: ("fg", "trans"), PLANES_GROUPS: ("sun", "sky"), PLANES_GROUP_LAYERS: ("sun", "sky", "trans")}
+
+
+class PlaneBufs(C.Structure):
+    """include/volpath.h vp_plane_bufs: the accumulators and record buffers of one half's planes, in the mode's order"""
+    _fields_ = [("acc", C.c_void_p * 3), ("rec", C.c_void_p * 3)]
+
+
 class FeatureParams(C.Structure):
     """include/volpath.h vp_feature_params"""
     _fields_ = [("step", C.c_float), ("tau_z", C.c_float)]
@@ -190,6 +201,7 @@ def lib():
         L.vp_filter_variance.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.POINTER(DenoiseParams)]
         L.vp_denoise_var.argtypes = [C.c_void_p] * 6 + [C.POINTER(DenoiseFeature), C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseParams)]
         L.vp_cross_error.argtypes = [C.c_void_p] * 7 + [C.c_int]
+        L.vp_render_frames_planes_halves_stats.argtypes = [C.c_int, C.POINTER(PlaneBufs), C.POINTER(PlaneBufs), C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_select.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(SelectParams)]
         L.vp_render_frames_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_int, C.c_float]
@@ -694,6 +706,44 @@ def denoise_cross(dst_ptr, resid_ptr, h0, h0_stats, h1, h1_stats, tmp_a_ptr, tmp
         denoise_var(tmp_a_ptr, h0, h0_stats, width, height, uf_ptr, feats, radius, patch, k, guide_ptr=h1, guide_stats_ptr=h1_stats)
         denoise_var(tmp_b_ptr, h1, h1_stats, width, height, uf_ptr, feats, radius, patch, k, guide_ptr=h0, guide_stats_ptr=h0_stats)
     merge_halves(dst_ptr, resid_ptr, tmp_a_ptr, h0_stats, tmp_b_ptr, h1_stats, width * height, floor_y)
+
+
+def plane_bufs(planes):
+    """a PlaneBufs from a sequence of (acc_ptr, rec_ptr) per plane, at most three; the entries beyond it stay NULL"""
+    planes = list(planes)
+    if len(planes) > 3:
+        raise ValueError("plane_bufs: %d planes, at most 3" % len(planes))
+    b = PlaneBufs()
+    for k, (a, r) in enumerate(planes):
+        b.acc[k] = getattr(a, "value", a)
+        b.rec[k] = getattr(r, "value", r)
+    return b
+
+
+def render_frames_planes_halves_stats(mode, h0, h1, first, n, P):
+    """the mode's _stats plane call (PLANES_LAYERS, PLANES_GROUPS, PLANES_GROUP_LAYERS) with the frames split between two halves of
+    every plane by half_of_frame; h0 / h1: sequences of (acc_ptr, rec_ptr) per plane in the mode's order (PLANE_NAMES), or PlaneBufs
+    (vp_render_frames_planes_halves_stats)"""
+    b0 = h0 if isinstance(h0, PlaneBufs) else plane_bufs(h0)
+    b1 = h1 if isinstance(h1, PlaneBufs) else plane_bufs(h1)
+    _chk(lib().vp_render_frames_planes_halves_stats(mode, C.byref(b0), C.byref(b1), first, n, C.byref(P)))
+
+
+# the residual floor of a plane by its name: trans lies in [0, 1] and is constant over most pixels
+PLANE_RESID_FLOOR = {"fg": 1e-3, "sun": 1e-3, "sky": 1e-3, "trans": 1e-2}
+
+
+def denoise_cross_planes(mode, dsts, resids, h0, h1, tmp_a_ptr, tmp_b_ptr, width, height, radius, patch, k, features=None, variance=None, var_ptrs=None):
+    """denoise_cross per plane of a planes-halves render: plane j of `mode` (PLANE_NAMES) from its two halves h0[j], h1[j] -- each an
+    (acc_ptr, rec_ptr) pair -- into dsts[j] and, where resids is given and resids[j] is not None, its residual map with the plane's
+    floor (PLANE_RESID_FLOOR: 1e-3, trans 1e-2).  The temporaries and var_ptrs are shared by the planes: everything is queued in order
+    on the context's stream, nothing is allocated.  variance / var_ptrs as in denoise_cross"""
+    names = PLANE_NAMES[mode]
+    if not (len(dsts) == len(h0) == len(h1) == len(names)) or (resids is not None and len(resids) != len(names)):
+        raise ValueError("denoise_cross_planes: mode %d has %d planes" % (mode, len(names)))
+    for j, name in enumerate(names):
+        denoise_cross(dsts[j], resids[j] if resids is not None else None, h0[j][0], h0[j][1], h1[j][0], h1[j][1], tmp_a_ptr, tmp_b_ptr, width, height,
+                      radius, patch, k, features=features, floor_y=PLANE_RESID_FLOOR[name], variance=variance, var_ptrs=var_ptrs)
 
 
 def render_features(P, step, tau_z=FEATURE_TAU_Z_DEFAULT, alpha_ptr=None, depth_ptr=None):

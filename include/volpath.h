@@ -411,7 +411,8 @@ int vp_denoise_guided(vp_float4* dst, const vp_float4* src, const vp_pixel_stats
  *   context's stream, for one frame too; it stages ONE plane, so vp_reserve_frames serves it unchanged.  It leaves nothing behind.
  *   Refused with VP_E_ARG before the device is touched, all four buffers untouched: any NULL pointer, d_h0 == d_h1, equal record
  *   pointers, n_frames <= 0, first_frame < 0.  Other errors as vp_render_frames_stats gives them.
- *   Not built: a form without records, adaptive rounds on halves, halves of calls with planes (layers, groups, group layers).
+ *   Not built: a form without records, adaptive rounds on halves.  Halves of calls with planes (layers, groups, group layers):
+ *   vp_render_frames_planes_halves_stats, below (section 2.19).
  *
  * vp_merge_halves: a and b are MEAN images of the two halves -- what vp_denoise, vp_denoise_guided or vp_scale_by_count(..., 1.0f)
  * write -- and of the records only n is read.  Binary32, one rounding per operation, no contraction, in the order written:
@@ -791,6 +792,45 @@ typedef struct { float rel_tol[3], floor_y[3]; int min_frames, round_frames; } v
 int vp_render_adaptive_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float4* d_trans,
                                     vp_pixel_stats* d_sun_stats, vp_pixel_stats* d_sky_stats, vp_pixel_stats* d_trans_stats,
                                     int first_frame, int max_frames, const Param* p, const vp_adaptive_planes3* a, vp_adaptive_result* result);
+
+/* Half-buffer renders of calls with planes: vp_render_frames_halves_stats for layers, light groups and group
+ * layers, so that the cross-filter, the variance stage and the selection (vp_halves_variance, vp_filter_variance, vp_denoise_var,
+ * vp_cross_error, vp_merge_halves, vp_select -- all take arbitrary (accumulator, records) pairs) serve each plane a compositor takes.
+ * One staged call fills two independent halves of every plane.  h0 and h1 hold the planes of one half in the mode's order -- layers:
+ * fg, trans; groups: sun, sky; group layers: sun, sky, trans --; entries beyond the mode's planes are ignored, garbage included.
+ *
+ * vp_render_frames_planes_halves_stats.  THE DEFINITION: let N be the mode's number of planes, S the context's sub-pixel factor,
+ * m = log2 S and h(f) = (f >> 2m) & 1, the half rule of vp_render_frames_halves_stats.  For h = 0, 1 the N accumulators and the N
+ * record buffers of half h end bit-identical to what the mode's one-frame _stats call -- vp_render_frames_layers_stats,
+ * vp_render_frames_groups_stats or vp_render_frames_group_layers_stats with n_frames = 1 on the planes of half h --, called once for
+ * each f of [first_frame, first_frame + n_frames) with h(f) == h in ascending order, leaves in the same context state.  Hence:
+ *   - within the half that receives a frame the plane call's rule holds: a plane that the sample does not feed is ADDED +0.0f -- a
+ *     -0.0f there becomes +0.0f -- and its record gains n += 1 with y = +0;
+ *   - the other half's planes receive nothing for that frame: no +0.0f is added, so a -0.0f survives; no count is added; and no byte
+ *     is written where a launch holds no frame of that half;
+ *   - every record of half h gains in n exactly the number of its own frames; `flags` is neither read nor written;
+ *   - a per-pixel constant of a launch is one sequential addition per frame of the half, never a product;
+ *   - only owned pixels are touched (vp_set_shard);
+ *   - there is no hidden state: the half is a function of the ABSOLUTE frame number, a second call continues a first one, and a job
+ *     that the staging cap splits into launches of any size gives the bits of one launch.
+ *   Built for exactly what the underlying plane call is built for: every estimator, stream and sub-pixel factor, every volume format,
+ *   cell order and LDS form, shards.  It stages as the underlying call does -- one plane for layers, the two planes of a groups call
+ *   for the other two modes --, so vp_reserve_frames / vp_reserve_frames_groups and vp_groups_frames_per_launch serve it unchanged.
+ *   The render launches are the underlying plane call's own instances, counted under that mode's census kind; only the reduce is new.
+ *   It stops look-ahead batches, waits for pipelined launches, runs on the context's stream and leaves nothing behind.
+ *   Refused with VP_E_ARG before the device is touched, every buffer untouched: an unknown mode; a NULL h0, h1, p or used entry; any
+ *   two of the 2N accumulators equal; any two of the 2N record buffers equal; n_frames <= 0 or first_frame < 0.  VP_E_STATE exactly
+ *   where the underlying plane call gives it (VP_ENV_MIS, scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST),
+ *   the message naming this entry point; an argument error comes before a state error.  Other errors are the underlying call's.
+ *   The output stage per plane is the cross-filter's sequence with that plane's two halves (and that plane's floor for the residual:
+ *   trans is constant over most pixels and lies in [0, 1]); per-pixel selection composes in the same way from vp_cross_error and
+ *   vp_select with a plane's halves -- the volpath_render driver offers the cross-filter and the variance stage on planes, not selection.
+ *   Still not built: adaptive rounds on halves, a form without records, reduction across processes, VP_ARITH_FAST. */
+enum { VP_PLANES_LAYERS = 1, VP_PLANES_GROUPS = 2, VP_PLANES_GROUP_LAYERS = 3 };
+/* the planes of one half in the mode's order: fg trans | sun sky | sun sky trans; entries beyond the mode's planes are ignored */
+typedef struct { vp_float4* acc[3]; vp_pixel_stats* rec[3]; } vp_plane_bufs;   /* 48 bytes */
+int vp_render_frames_planes_halves_stats(int mode, const vp_plane_bufs* h0, const vp_plane_bufs* h1,
+                                         int first_frame, int n_frames, const Param* p);
 
 /* ---- Feature pass: ray-marched opacity and depth planes per pixel
  * Every plane above is a Monte-Carlo estimate.  vp_render_features is deterministic: the march of precompute_opacity -- midpoint rule,
