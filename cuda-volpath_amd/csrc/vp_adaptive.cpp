@@ -5,6 +5,9 @@
 // vp_render_adaptive_groups / vp_render_adaptive_layers: the same rounds on the two planes of a groups or layers render -- active means
 // frozen in neither plane's record, and a round freezes both records of a pixel when both meet their plane's criterion.
 // vp_render_adaptive_group_layers: the same on the three planes of a group-layers render, with three records per pixel.
+// vp_render_adaptive_halves / vp_render_adaptive_planes_halves: the same rounds into the two halves of a half-buffer render -- active means
+// frozen in none of the 2 N records; the halves reduces never freeze, so a round ends with a pass of its own (freeze_halves_k) that decides
+// on the pooled records of the two halves, plane by plane.
 // vp_denoise: the filter of the output stage that reads the records (vp_denoise.hip); vp_denoise_guided: the same with feature planes.
 // vp_halves_variance, vp_filter_variance, vp_denoise_var: the variance stage of the cross-filter.
 // vp_cross_error, vp_select: per-pixel selection among filtered candidates by cross-buffer error estimates.
@@ -67,6 +70,12 @@ static int adaptive_rounds(const PlaneSet& S, int first_frame, int max_frames, i
         const int f = std::min(round_frames, max_frames - done);
         const PixelLists PL = {G.d_act, cnt[0], cnt[1], cnt[2]};
         if ((rc = do_render((vp_float4*)S.acc[0], first_frame + done, f, p, false, nullptr, &PL, &S))) return rc;
+        if (S.halves)
+        {
+            // (the halves reduces never freeze: the round's decision, on the round's own list, before the list is compacted again)
+            launch_freeze_halves(G.d_act, cnt[0] + cnt[1] + cnt[2], p->width, S, G.stream);
+            HIPCHK(hipGetLastError());
+        }
         samples += ((unsigned long long)cnt[0] + cnt[1] + cnt[2]) * (unsigned long long)f;   // (one per pixel and frame, not per plane)
         done += f; rounds++;
         if (result) { result->samples = samples; result->rounds = rounds; result->frames_used = (uint32_t)done; }
@@ -94,6 +103,28 @@ static int render_adaptive_planes(const char* fn, PlaneSet S, int first_frame, i
     int rc = plane_state_check(fn, S.groups());
     if (rc) return rc;
     if ((rc = ensure_device())) return rc;
+    if ((rc = check_render(CHK_STATE | CHK_OPACITY, p, (long long)first_frame + max_frames - 1))) return rc;
+    S.adaptive = true; S.min_frames = (unsigned)a.min_frames;
+    for (int k = 0; k < S.n(); k++) { S.tol[k] = (double)a.rel_tol[k]; S.fl[k] = (double)a.floor_y[k]; }
+    return adaptive_rounds(S, first_frame, max_frames, a.round_frames, p, result);
+}
+// vp_render_adaptive_halves / vp_render_adaptive_planes_halves: S holds the 2 N buffers of each kind as the caller handed them in (halves
+// set); `planes`: the plane modes' state check, else the beauty call's.  The refusals of the definition, in its order, then the rounds.
+static int render_adaptive_halves(const char* fn, PlaneSet S, bool planes, int first_frame, int max_frames, const Param* p, const AdaptiveArgs& a,
+                                  vp_adaptive_result* result)
+{
+    const int bad = plane_buffers_check(S, true);
+    if (bad == 1 || !p || !a.rel_tol) return fail(VP_E_ARG, "%s: null pointer", fn);
+    if (bad) return fail(VP_E_ARG, "%s: the accumulators of the two halves, and their record buffers, are all different buffers", fn);
+    if (max_frames <= 0 || first_frame < 0) return fail(VP_E_ARG, "%s: frames [%d, %d + %d) out of range", fn, first_frame, first_frame, max_frames);
+    if (a.min_frames < 2) return fail(VP_E_ARG, "%s: min_frames %d (a variance estimate needs two samples)", fn, a.min_frames);
+    if (a.round_frames < 1) return fail(VP_E_ARG, "%s: round_frames %d", fn, a.round_frames);
+    for (int k = 0; k < S.n(); k++)
+        if (!(a.rel_tol[k] >= 0.0f) || !(a.floor_y[k] >= 0.0f)) return fail(VP_E_ARG, "%s: rel_tol and floor_y must be numbers >= 0 (plane %d)", fn, k);
+    int rc = VP_OK;
+    if (planes && (rc = plane_state_check(fn, S.groups()))) return rc;
+    if ((rc = ensure_device())) return rc;
+    if (!planes && G.count) return fail(VP_E_STATE, "%s is not built for work counters", fn);
     if ((rc = check_render(CHK_STATE | CHK_OPACITY, p, (long long)first_frame + max_frames - 1))) return rc;
     S.adaptive = true; S.min_frames = (unsigned)a.min_frames;
     for (int k = 0; k < S.n(); k++) { S.tol[k] = (double)a.rel_tol[k]; S.fl[k] = (double)a.floor_y[k]; }
@@ -190,6 +221,33 @@ int vp_render_adaptive_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float
 {
     return render_adaptive_planes("vp_render_adaptive_group_layers", plane_set(PLANES_GROUP_LAYERS, d_sun, d_sky, d_trans, d_sun_stats, d_sky_stats, d_trans_stats),
                                   first_frame, max_frames, p, adaptive_args(a), result);
+}
+int vp_render_adaptive_halves(vp_float4* d_h0, vp_float4* d_h1, vp_pixel_stats* d_h0_stats, vp_pixel_stats* d_h1_stats, int first_frame, int max_frames,
+                              const Param* p, const vp_adaptive* a, vp_adaptive_result* result)
+{
+    static const char fn[] = "vp_render_adaptive_halves";
+    if (result) memset(result, 0, sizeof *result);
+    if (!a) return fail(VP_E_ARG, "%s: null pointer", fn);
+    PlaneSet S = plane_set(PLANES_ONE, d_h0, d_h1, nullptr, d_h0_stats, d_h1_stats);
+    S.halves = true;
+    return render_adaptive_halves(fn, S, false, first_frame, max_frames, p, AdaptiveArgs{&a->rel_tol, &a->floor_y, a->min_frames, a->round_frames}, result);
+}
+int vp_render_adaptive_planes_halves(int mode, const vp_plane_bufs* h0, const vp_plane_bufs* h1, int first_frame, int max_frames, const Param* p,
+                                     const vp_adaptive_planes3* a, vp_adaptive_result* result)
+{
+    static const char fn[] = "vp_render_adaptive_planes_halves";
+    if (result) memset(result, 0, sizeof *result);
+    if (mode != VP_PLANES_LAYERS && mode != VP_PLANES_GROUPS && mode != VP_PLANES_GROUP_LAYERS) return fail(VP_E_ARG, "%s: unknown mode %d", fn, mode);
+    if (!h0 || !h1 || !a) return fail(VP_E_ARG, "%s: null pointer", fn);
+    PlaneSet S = {};
+    S.mode = mode; S.halves = true;
+    for (int h = 0; h < 2; h++)
+        for (int k = 0; k < S.n(); k++)
+        {
+            S.acc[h * S.n() + k] = (float4*)(h ? h1 : h0)->acc[k];
+            S.rec[h * S.n() + k] = (PixelStatsDev*)(h ? h1 : h0)->rec[k];
+        }
+    return render_adaptive_halves(fn, S, true, first_frame, max_frames, p, adaptive_args(a), result);
 }
 int vp_scale_by_count(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, int size, float scale)
 {

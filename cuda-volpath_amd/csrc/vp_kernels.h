@@ -187,7 +187,7 @@ struct LaunchDev
 // and LaunchDev::groups null, census kind CENSUS_RENDER --, and only the reduce knows it:
 //   PLANES_HALVES        h0, h1              the beauty sample of frame f, whole, to plane half_of_frame(f) ALONE; the other plane
 //                                            receives no sample of that frame -- no +0.0f, no count (include/volpath.h
-//                                            vp_render_frames_halves_stats).  Records always; no adaptive and no compaction instance.
+//                                            vp_render_frames_halves_stats).  Records always; no adaptive instance of the reduce.
 // Halves are orthogonal to the split mode (PlaneSet::halves): "mode M, two halves" launches what mode M launches -- its render_k
 // instances, staging planes and census kind -- and the reduce hands the N samples that split_sample<M> makes of frame f to the N planes of
 // half half_of_frame(f) alone (include/volpath.h vp_render_frames_planes_halves_stats; reduce_plane_halves_k).  PLANES_HALVES above is
@@ -270,12 +270,13 @@ struct PixelStatsDev { double sum_y, sum_y2; unsigned n, flags; };
 struct PlaneSet
 {
     int            mode;                // PLANES_ONE .. PLANES_GROUP_LAYERS: the split rule, and render_k's two bits
-    bool           halves;              // two halves of the mode's planes: half h's plane k is entry h * n() + k; records always, never adaptive
+    bool           halves;              // two halves of the mode's planes: half h's plane k is entry h * n() + k; records always
     float4*        acc[2 * kMaxPlanes]; // count() accumulators of width * height pixels
     PixelStatsDev* rec[2 * kMaxPlanes]; // their records, indexed like the accumulators; rec[0] null: a call without statistics
-    double         tol[kMaxPlanes], fl[kMaxPlanes];   // adaptive: each plane's tolerance and floor (the binary32 arguments widened)
-    unsigned       min_frames;          // adaptive: the samples a record needs before its criterion is asked
+    double         tol[kMaxPlanes], fl[kMaxPlanes];   // adaptive: each plane's tolerance and floor (the binary32 arguments widened); n() entries, halves or not
+    unsigned       min_frames;          // adaptive: the samples a record needs before its criterion is asked (halves: the two halves' records of a plane together)
     bool           adaptive;            // a round of an adaptive call: its last launch freezes; false: `flags` is neither read nor written
+                                        // (with halves the reduce never freezes: the round loop launches launch_freeze_halves after the round)
     int  n() const { return planes_of(mode); }
     int  count() const { return halves ? 2 * n() : n(); }   // the buffers of each kind the caller hands in
     bool layers() const { return (mode & PLANES_LAYERS) != 0; }   // (render_k's two bits, with halves or without)
@@ -289,8 +290,12 @@ struct PlaneSet
 // where S.adaptive, the one that evaluates the criterion: all records of a slot are frozen iff each has S.min_frames and meets the
 // criterion with its own n, tolerance and floor (a record frozen on a part of a round would stay frozen).
 void launch_reduce_planes(const LaunchDev& L, const PlaneSet& S, unsigned light_from, unsigned light_to, bool last, hipStream_t st);
+// The freeze of an adaptive round on halves (freeze_halves_k<N>; include/volpath.h vp_render_adaptive_halves): one thread per slot of
+// `pixels` -- the round's active list --, which sets FROZEN in all 2 n() records of a slot iff every plane has two samples in each half,
+// S.min_frames in both together and meets its criterion on the pooled record; nothing else is written.  S.halves && S.adaptive.
+void launch_freeze_halves(const unsigned* pixels, unsigned nslots, unsigned width, const PlaneSet& S, hipStream_t st);
 // the pixels of the class-ordered list src (n[0] general, n[1] light, n[2] box-missing) that are frozen in none of S's records, in
-// src's order, class by class, into d_out (room for all of src), and their three counts into d_totals;
+// src's order, class by class, into d_out (room for all of src), and their three counts into d_totals; S.count() records per slot: 1, 2, 3, 4 or 6;
 // d_block_counts[3 * compact_blocks(n)] scratch
 inline unsigned compact_blocks(unsigned n) { return (n + 1023u) / 1024u; }
 void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PlaneSet& S, unsigned* d_block_counts, unsigned* d_totals,

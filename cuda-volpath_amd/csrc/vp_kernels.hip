@@ -783,6 +783,41 @@ __global__ __launch_bounds__(VP_PIXLIST_BLOCK) void compact_write_k(CompactDev<N
     // (at most as many active pixels as src holds: `out` has room for all of src)
     out[class_base + block_offsets[3 * blockIdx.x + c] + before + rank_in_wave] = pix;
 }
+// The freeze of an adaptive round on halves (include/volpath.h vp_render_adaptive_halves / _planes_halves; vp_adaptive.cpp
+// adaptive_rounds): the halves reduces above never look at `flags`, and the decision needs BOTH halves' finished records of a plane, so it
+// is a pass of its own over the round's active list, once per round, after the round's last reduce.  One thread per slot of the list;
+// N: the planes of the mode, rec[h][k] plane k's records in half h.  A slot is frozen iff every plane k has r0.n >= 2, r1.n >= 2,
+// n = r0.n + r1.n >= min_frames and the criterion on the pooled record (sum_y and sum_y2 each ONE binary64 addition, half 0 + half 1:
+// what accumulate_stats_k makes of a copy of r0 and r1) with the plane's tolerance and floor.  Where it holds, FROZEN is or-ed into all
+// 2N records and nothing else is written; where not, no byte is.  Slots are independent: no LDS, no atomics.
+template <int N> struct FreezeHalvesDev { const unsigned* pixels; unsigned nslots, width, min_frames; PixelStatsDev* rec[2][N]; double tol[N], fl[N]; };
+template <int N>
+__global__ __launch_bounds__(256) void freeze_halves_k(FreezeHalvesDev<N> D)
+{
+    const unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= D.nslots) return;
+    const unsigned pix = D.pixels[slot];
+    const size_t   idx = (size_t)(pix & 0xffffu) + (size_t)(pix >> 16) * D.width;
+    unsigned flags[2][N];
+    bool     freeze = true;
+#pragma unroll
+    for (int k = 0; k < N; k++)
+    {
+        const PixelStatsDev r0 = D.rec[0][k][idx], r1 = D.rec[1][k][idx];
+        flags[0][k] = r0.flags; flags[1][k] = r1.flags;
+        const unsigned n   = r0.n + r1.n;
+        const double   sy  = r0.sum_y + r1.sum_y;
+        const double   sy2 = r0.sum_y2 + r1.sum_y2;
+        freeze = freeze && r0.n >= 2u && r1.n >= 2u && n >= D.min_frames && stats_converged(sy, sy2, n, D.tol[k], D.fl[k]);
+    }
+    if (!freeze) return;
+#pragma unroll
+    for (int k = 0; k < N; k++)
+    {
+        D.rec[0][k][idx].flags = flags[0][k] | 1u;   // VP_STATS_FROZEN, in all of them
+        D.rec[1][k][idx].flags = flags[1][k] | 1u;
+    }
+}
 // the output stage of a render with per-pixel sample counts: dst = src * (scale / n), a correctly rounded binary32 divide; n = 0 gives 0
 __global__ void scale_by_count_k(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float scale)
 {
@@ -1908,7 +1943,8 @@ static void launch_reduce_halves(const LaunchDev& L, const PlaneSet& S, unsigned
 template <int MODE>
 static void launch_reduce_mode(const LaunchDev& L, const PlaneSet& S, unsigned light_from, unsigned light_to, bool last, hipStream_t st)
 {
-    // (halves -- one form per mode: the entry points always hand in records and never run adaptive rounds)
+    // (halves -- one form per mode, whatever `last` says: the entry points always hand in records, and an adaptive round on halves
+    // freezes in a pass of its own: freeze_halves_k)
     if (S.halves) launch_reduce_halves<MODE>(L, S, light_from, light_to, st);
     else if (!S.stats())
     {
@@ -1935,7 +1971,7 @@ static void launch_compact_planes(const unsigned* src, const unsigned n[3], unsi
 {
     CompactDev<N> D;
     D.src = src; D.n[0] = n[0]; D.n[1] = n[1]; D.n[2] = n[2]; D.width = width;
-    for (int k = 0; k < N; k++) D.stats[k] = S.rec[k];
+    for (int k = 0; k < N; k++) D.stats[k] = S.rec[k];   // (N = S.count(): with halves the records of both)
     const unsigned nblocks = compact_blocks(n[0] + n[1] + n[2]);
     const dim3 grid(nblocks), block(VP_PIXLIST_BLOCK);
     hipLaunchKernelGGL(compact_count_k<N>, grid, block, 0, st, D, d_block_counts);
@@ -1945,11 +1981,35 @@ static void launch_compact_planes(const unsigned* src, const unsigned n[3], unsi
 void launch_compact_active(const unsigned* src, const unsigned n[3], unsigned width, const PlaneSet& S, unsigned* d_block_counts, unsigned* d_totals,
                            unsigned* d_out, hipStream_t st)
 {
-    switch (S.n())
+    switch (S.count())
     {
     case 1: launch_compact_planes<1>(src, n, width, S, d_block_counts, d_totals, d_out, st); break;
     case 2: launch_compact_planes<2>(src, n, width, S, d_block_counts, d_totals, d_out, st); break;
-    default: launch_compact_planes<3>(src, n, width, S, d_block_counts, d_totals, d_out, st); break;
+    case 3: launch_compact_planes<3>(src, n, width, S, d_block_counts, d_totals, d_out, st); break;
+    case 4: launch_compact_planes<4>(src, n, width, S, d_block_counts, d_totals, d_out, st); break;
+    default: launch_compact_planes<6>(src, n, width, S, d_block_counts, d_totals, d_out, st); break;
+    }
+}
+template <int N>
+static void launch_freeze_planes(const unsigned* pixels, unsigned nslots, unsigned width, const PlaneSet& S, hipStream_t st)
+{
+    FreezeHalvesDev<N> D;
+    D.pixels = pixels; D.nslots = nslots; D.width = width; D.min_frames = S.min_frames;
+    for (int k = 0; k < N; k++)
+    {
+        D.rec[0][k] = S.rec[k]; D.rec[1][k] = S.rec[N + k];
+        D.tol[k] = S.tol[k]; D.fl[k] = S.fl[k];
+    }
+    hipLaunchKernelGGL(freeze_halves_k<N>, dim3((nslots + 255) / 256), dim3(256), 0, st, D);
+}
+void launch_freeze_halves(const unsigned* pixels, unsigned nslots, unsigned width, const PlaneSet& S, hipStream_t st)
+{
+    if (!nslots) return;
+    switch (S.n())
+    {
+    case 1: launch_freeze_planes<1>(pixels, nslots, width, S, st); break;
+    case 2: launch_freeze_planes<2>(pixels, nslots, width, S, st); break;
+    default: launch_freeze_planes<3>(pixels, nslots, width, S, st); break;
     }
 }
 void launch_scale_by_count(float4* dst, const float4* src, const PixelStatsDev* stats, int size, float s, hipStream_t st)

@@ -145,6 +145,24 @@ static void usage()
            "                                                writes one residual map per plane (PREFIX_sun.hdr ...), with the plane's floor\n"
            "                                                (1e-3; trans 1e-2).  One GPU; not with --noise, --plane-noise, --planes-noise or\n"
            "                                                --denoise-cross / -var / -select\n"
+           "               [--cross-noise TOL [--min-spp N] [--round N] [--cross-noise-out FILE.hdr]]\n"
+           "                                                adaptive sampling into the two half-buffers (vp_render_adaptive_halves): implies\n"
+           "                                                --denoise-cross and composes with --denoise-var, --denoise-select,\n"
+           "                                                --denoise-features and --resid-out.  A pixel is sampled in rounds of --round frames,\n"
+           "                                                frame f into its half alone, until each half holds two samples, both together\n"
+           "                                                --min-spp and the estimated standard error of their POOLED mean luminance is at\n"
+           "                                                most TOL x max(mean, 1e-3); --spp is the maximum.  With --aa S the round is rounded\n"
+           "                                                up to a multiple of 2 S^2, so that every round feeds both halves equally.\n"
+           "                                                --cross-noise-out writes the noise map of the pooled records (vp_accumulate_stats\n"
+           "                                                of the two halves, vp_stats_rel_error) as HDR.  One GPU; not with --noise\n"
+           "               [--plane-cross-noise TOL0 TOL1] [--planes-cross-noise TOL_SUN TOL_SKY TOL_TRANS] [--plane-cross-noise-out PREFIX]\n"
+           "                                                the same on the halves of every plane (vp_render_adaptive_planes_halves):\n"
+           "                                                --plane-cross-noise with --layers-denoise-cross or --groups-denoise-cross,\n"
+           "                                                --planes-cross-noise with --planes-denoise-cross.  Each plane's two records are\n"
+           "                                                pooled and held to its own tolerance, with the floors of --plane-noise /\n"
+           "                                                --planes-noise; a pixel is sampled until every plane meets its own.\n"
+           "                                                --plane-cross-noise-out writes one pooled noise map per plane (PREFIX_sun.hdr ...).\n"
+           "                                                One GPU; not with --noise, --plane-noise or --planes-noise\n"
            "               [--features-out PREFIX [--feature-step DT] [--depth-tau TAU]]\n"
            "                                                the feature pass (vp_render_features), a deterministic march along every pixel's\n"
            "                                                camera ray with step DT (default 0.001), after the render and beside every other\n"
@@ -242,6 +260,9 @@ struct Options
     bool        layers_cross = false, groups_cross = false, planes_cross = false;   // --*-denoise-cross: the mode's filter flag, on two halves of every plane
     bool        plane_denoise_var = false;   // --plane-denoise-var: the variance stage in front of each plane's pair of filters
     std::string plane_resid_out;
+    bool        cross_adaptive = false, plane_cross_adaptive = false, planes_cross_adaptive = false;   // --cross-noise, --plane-cross-noise, --planes-cross-noise: rounds on halves
+    float       cross_tol = 0.0f, plane_cross_tol[2] = {0.0f, 0.0f}, planes_cross_tol[3] = {0.0f, 0.0f, 0.0f};
+    std::string cross_noise_out, plane_cross_noise_out;
     std::string features_out;
     vp_feature_params feat = {0.001f, VP_FEATURE_TAU_Z_DEFAULT};
 
@@ -310,6 +331,11 @@ void Options::parse(int argc, char** argv)
         else if (a == "--plane-noise-out") { need(1); plane_noise_out = argv[++i]; }
         else if (a == "--planes-noise") { parse_floats(argc, argv, i, 3, planes_tol, at_least_0, "three tolerances >= 0"); planes_adaptive = true; }
         else if (a == "--planes-noise-out") { need(1); planes_noise_out = argv[++i]; }
+        else if (a == "--cross-noise") { parse_floats(argc, argv, i, 1, &cross_tol, at_least_0, "a tolerance >= 0"); cross_adaptive = denoise_cross = denoise = true; }
+        else if (a == "--cross-noise-out") { need(1); cross_noise_out = argv[++i]; }
+        else if (a == "--plane-cross-noise") { parse_floats(argc, argv, i, 2, plane_cross_tol, at_least_0, "two tolerances >= 0"); plane_cross_adaptive = true; }
+        else if (a == "--planes-cross-noise") { parse_floats(argc, argv, i, 3, planes_cross_tol, at_least_0, "three tolerances >= 0"); planes_cross_adaptive = true; }
+        else if (a == "--plane-cross-noise-out") { need(1); plane_cross_noise_out = argv[++i]; }
         else if (a == "--min-spp") { need(1); min_spp = atoi(argv[++i]); }
         else if (a == "--round") { need(1); round_frames = atoi(argv[++i]); }
         else if (a == "--noise-out") { need(1); noise_out = argv[++i]; }
@@ -414,6 +440,8 @@ struct Job
     Plane            plane[3] = {};
     bool             filter = false;     // the mean of a plane is vp_denoise's (beauty: --denoise and its variants)
     bool             adaptive = false;   // rounds to the tolerances tol[k], then no batch loop
+    bool             halves_adaptive = false;   // ... into two halves (--cross-noise, --plane-cross-noise, --planes-cross-noise): each plane's two records pooled
+    int              ntol = 1;           // the planes the criterion is asked of (n, but 1 for the beauty image's two half-buffers)
     bool             records = false;    // the frames go through the mode's _stats call / its adaptive call
     bool             means = false;      // a mean buffer per plane
     float            tol[3] = {};
@@ -446,8 +474,28 @@ static Mode refuse_conflicts(const Options& o)
     if (!o.denoise_var && !o.var_out.empty()) refuse(PLAIN, "--var-out needs --denoise-var: the map is the filtered variance plane of that stage");
     if (!o.denoise_select && !o.select_out.empty()) refuse(PLAIN, "--select-out needs --denoise-select: the map is the index of the candidate picked per pixel");
     if (o.denoise_select && !o.resid_out.empty()) refuse(PLAIN, "--denoise-select with --resid-out: a residual map of a blend of candidates is not defined here");
+    // adaptive rounds on halves: one GPU, no other adaptive flag, and each flag with the cross-filter of its own mode
+    const char* cross_noise = first_of({{o.cross_adaptive, "--cross-noise"}, {o.plane_cross_adaptive, "--plane-cross-noise"}, {o.planes_cross_adaptive, "--planes-cross-noise"}});
+    if (cross_noise && (other = first_of({{o.gpus > 1, "--gpus"}, {o.adaptive, "--noise"}, {o.plane_adaptive, "--plane-noise"}, {o.planes_adaptive, "--planes-noise"}})))
+        refuse(PLAIN, "%s with %s: the halves' records are not reduced across ranks, and rounds on halves are the run's only adaptive rounds (they judge the "
+               "two records of a plane together); use one GPU without --noise, --plane-noise and --planes-noise", cross_noise, other);
+    if (o.cross_adaptive && (other = first_of({{o.plane_cross_adaptive, "--plane-cross-noise"}, {o.planes_cross_adaptive, "--planes-cross-noise"}})))
+        refuse(PLAIN, "--cross-noise with %s: --cross-noise samples the beauty image's half-buffers, %s the halves of planes", other, other);
+    if (o.plane_cross_adaptive && (o.planes_cross_adaptive || o.planes_cross || !(o.layers_cross || o.groups_cross)))
+        refuse(PLAIN, "--plane-cross-noise needs --layers-denoise-cross or --groups-denoise-cross: it samples the halves of that render's two planes "
+               "(three planes: --planes-cross-noise TOL_SUN TOL_SKY TOL_TRANS with --planes-denoise-cross)");
+    if (o.planes_cross_adaptive && !o.planes_cross)
+        refuse(PLAIN, "--planes-cross-noise needs --planes-denoise-cross: it samples the halves of that render's three planes "
+               "(two planes: --plane-cross-noise TOL0 TOL1 with --layers-denoise-cross or --groups-denoise-cross)");
+    if (cross_noise && bad_rounds) refuse(USAGE, "%s needs --min-spp >= 2 and --round >= 1", cross_noise);
+    if (!o.cross_adaptive && !o.cross_noise_out.empty()) refuse(PLAIN, "--cross-noise-out needs --cross-noise");
+    if (!o.plane_cross_adaptive && !o.planes_cross_adaptive && !o.plane_cross_noise_out.empty())
+        refuse(PLAIN, "--plane-cross-noise-out needs --plane-cross-noise or --planes-cross-noise");
     // the cross-filter on planes: one GPU, no adaptive rounds of any kind, and not beside the beauty image's cross-filter
     const char* plane_cross = first_of({{o.layers_cross, "--layers-denoise-cross"}, {o.groups_cross, "--groups-denoise-cross"}, {o.planes_cross, "--planes-denoise-cross"}});
+    if (o.cross_adaptive && plane_cross)
+        refuse(PLAIN, "--cross-noise with %s: --cross-noise samples the beauty image's half-buffers; the halves of planes take --plane-cross-noise TOL0 TOL1 "
+               "(layers, groups) or --planes-cross-noise TOL_SUN TOL_SKY TOL_TRANS", plane_cross);
     if (!plane_cross && o.plane_denoise_var)
         refuse(PLAIN, "--plane-denoise-var needs --layers-denoise-cross, --groups-denoise-cross or --planes-denoise-cross: it is the variance stage of that filter");
     if (!plane_cross && !o.plane_resid_out.empty())
@@ -546,6 +594,7 @@ static Job validate(const Options& o)
     case BEAUTY:
         j.plane[0] = kBeauty, j.plane[1] = kBeauty, j.n = o.denoise_cross ? 2 : 1;
         j.filter = o.denoise, j.adaptive = o.adaptive, j.noise_flag = "--noise", j.noise_prefix = o.noise_out;
+        if (o.cross_adaptive) j.halves_adaptive = true, j.noise_flag = "--cross-noise", j.noise_prefix = o.cross_noise_out, tol = &o.cross_tol;
         break;
     case LAYERS:
     case GROUPS:
@@ -553,17 +602,24 @@ static Job validate(const Options& o)
         j.filter = layers ? o.layers_denoise : o.groups_denoise, j.prefix = layers ? o.layers_out : o.groups_out;
         j.adaptive = o.plane_adaptive, j.noise_flag = "--plane-noise", j.noise_prefix = o.plane_noise_out, tol = o.plane_tol;
         j.cross = layers ? o.layers_cross : o.groups_cross;
+        if (o.plane_cross_adaptive) j.halves_adaptive = true, j.noise_flag = "--plane-cross-noise", j.noise_prefix = o.plane_cross_noise_out, tol = o.plane_cross_tol;
+        j.ntol = 2;
         break;
     case PLANES:
         j.plane[0] = kSun, j.plane[1] = kSky, j.plane[2] = kTrans, j.n = 3;
         j.filter = o.planes_denoise, j.prefix = o.planes_out;
         j.adaptive = o.planes_adaptive, j.noise_flag = "--planes-noise", j.noise_prefix = o.planes_noise_out, tol = o.planes_tol;
         j.cross = o.planes_cross;
+        if (o.planes_cross_adaptive) j.halves_adaptive = true, j.noise_flag = "--planes-cross-noise", j.noise_prefix = o.plane_cross_noise_out, tol = o.planes_cross_tol;
+        j.ntol = 3;
         break;
     }
     // (a cross flag of another mode than the run's: that mode's refusals took it above, as they take its -denoise flag)
     for (int k = 0; k < j.n && j.cross; k++) j.other[k] = j.plane[k];
-    for (int k = 0; k < j.n && j.adaptive; k++) j.tol[k] = tol[k];
+    // (a --plane-cross-noise / --planes-cross-noise of a run without its cross flag was refused above)
+    j.halves_adaptive = j.halves_adaptive && (j.mode == BEAUTY || j.cross);
+    j.adaptive = j.adaptive || j.halves_adaptive;
+    for (int k = 0; k < j.ntol && j.adaptive; k++) j.tol[k] = tol[k];
     j.records = j.filter || j.adaptive;
     j.means   = j.mode == BEAUTY ? o.denoise_cross : j.records;   // (the beauty image's mean is formed in the display buffer)
     return j;
@@ -580,6 +636,7 @@ struct Run
     volpath::NodeReducer    reducer;
     vp_float4*              disp = nullptr;
     vp_adaptive_result      ares = {};
+    int                     round_frames = 0;   // the round of an adaptive run (--round; rounded up for rounds on halves under a sub-pixel factor)
 
     void use(int r) const { if (gpus > 1) vp_ctx_set_current(ctx[r]); }
 };
@@ -687,6 +744,12 @@ static void free_planes(Job& j)
     }
 }
 
+// the two halves of a job with planes in halves as the planes-halves calls take them, and the mode
+static int plane_halves(const Job& j, vp_plane_bufs h[2])
+{
+    for (int k = 0; k < j.n; k++) h[0].acc[k] = j.plane[k].acc, h[0].rec[k] = j.plane[k].rec, h[1].acc[k] = j.other[k].acc, h[1].rec[k] = j.other[k].rec;
+    return j.mode == PLANES ? VP_PLANES_GROUP_LAYERS : j.mode == LAYERS ? VP_PLANES_LAYERS : VP_PLANES_GROUPS;
+}
 // frames s .. s + n - 1 by the mode's call on rank 0, with the records where the job keeps them (the same accumulator bits)
 static int render_frames(const Job& j, int s, int n)
 {
@@ -695,8 +758,8 @@ static int render_frames(const Job& j, int s, int n)
     if (j.cross)   // the mode's _stats call, its frames split between the two halves of every plane
     {
         vp_plane_bufs h[2] = {};
-        for (int k = 0; k < j.n; k++) h[0].acc[k] = p[k].acc, h[0].rec[k] = p[k].rec, h[1].acc[k] = j.other[k].acc, h[1].rec[k] = j.other[k].rec;
-        return vp_render_frames_planes_halves_stats(j.mode == PLANES ? VP_PLANES_GROUP_LAYERS : j.mode == LAYERS ? VP_PLANES_LAYERS : VP_PLANES_GROUPS, &h[0], &h[1], s, n, P);
+        const int     mode = plane_halves(j, h);
+        return vp_render_frames_planes_halves_stats(mode, &h[0], &h[1], s, n, P);
     }
     switch (j.mode)
     {
@@ -710,10 +773,22 @@ static int render_frames(const Job& j, int s, int n)
     }
 }
 // rounds on the pixels none of whose planes has met its tolerance, --spp frames at most
-static int render_adaptive(const Job& j, vp_adaptive_result* res)
+static int render_adaptive(const Job& j, int round_frames, vp_adaptive_result* res)
 {
     const Options& o = j.o;
     const Plane*   p = j.plane;
+    if (j.halves_adaptive && j.mode == BEAUTY)   // the two half-buffers: one criterion on their pooled records
+    {
+        const vp_adaptive ad = {j.tol[0], p[0].floor, o.min_spp, round_frames};
+        return vp_render_adaptive_halves(p[0].acc, p[1].acc, p[0].rec, p[1].rec, 0, o.spp, &j.P, &ad, res);
+    }
+    if (j.halves_adaptive)   // two halves of every plane: each plane's criterion on its two records pooled
+    {
+        vp_plane_bufs h[2] = {};
+        const int     mode = plane_halves(j, h);
+        const vp_adaptive_planes3 ap = {{j.tol[0], j.tol[1], j.tol[2]}, {p[0].floor, p[1].floor, p[2].floor}, o.min_spp, round_frames};
+        return vp_render_adaptive_planes_halves(mode, &h[0], &h[1], 0, o.spp, &j.P, &ap, res);
+    }
     switch (j.mode)
     {
     case PLANES:
@@ -742,7 +817,15 @@ static void render(const Job& j, Run& run)
     if (j.adaptive)
     {
         if (o.est == VP_EST_DECOMP && o.spp > 11) precompute_opacity(sun_dir);   // host.cpp:336-343
-        must(render_adaptive(j, &run.ares));
+        run.round_frames = o.round_frames;
+        const int s2 = j.halves_adaptive ? 2 * vp_get_subpixel() * vp_get_subpixel() : 0;
+        if (s2 > 2 && run.round_frames % s2)   // (a sub-pixel factor S: whole blocks of S^2 frames, as many for one half as for the other)
+        {
+            run.round_frames = (run.round_frames + s2 - 1) / s2 * s2;
+            fprintf(stderr, "%s: --round %d rounded up to %d, a multiple of 2 S^2 = %d, so that every round feeds both halves equally\n", j.noise_flag,
+                    o.round_frames, run.round_frames, s2);
+        }
+        must(render_adaptive(j, run.round_frames, &run.ares));
         return;
     }
     const bool    own_call = j.mode != BEAUTY || j.records;   // planes or records: the mode's frames call, one rank
@@ -781,9 +864,9 @@ static void report(const Job& j, const Run& run, double sec)
         const double all = (double)o.W * o.H * o.spp;
         char what[96];
         int  len = snprintf(what, sizeof what, "%s", j.noise_flag);
-        for (int k = 0; k < j.n; k++) len += snprintf(what + len, sizeof what - len, " %g", j.tol[k]);
+        for (int k = 0; k < j.ntol; k++) len += snprintf(what + len, sizeof what - len, " %g", j.tol[k]);
         printf("adaptive: %llu of %.0f samples (%.1f %%), %u rounds of %d frames, %u pixels still above %s after %u frames\n",
-               (unsigned long long)ares.samples, all, 100.0 * (double)ares.samples / all, ares.rounds, o.round_frames, ares.active_left, what, ares.frames_used);
+               (unsigned long long)ares.samples, all, 100.0 * (double)ares.samples / all, ares.rounds, run.round_frames, ares.active_left, what, ares.frames_used);
         printf("%f M samples / s, %d x %d, at most %d spp, %f s\n", (double)ares.samples / sec / 1e6, o.W, o.H, o.spp, sec);
     }
     else printf("%f M samples / s, %d x %d, %d spp, %f s\n", (double)o.W * o.H * o.spp / sec / 1e6, o.W, o.H, o.spp, sec);
@@ -1016,12 +1099,22 @@ static void write_outputs(const Job& j, const Run& run)
         vp_free(d_resid);
     }
     // the noise maps: estimated standard error of the mean luminance over max(mean, floor), one per plane, each with its plane's floor
-    for (int k = 0; k < j.n && j.adaptive && !j.noise_prefix.empty(); k++)
+    // (rounds on halves: of the pooled records of a plane's two halves -- a zeroed scratch copy, both halves' records added)
+    for (int k = 0; k < j.ntol && j.adaptive && !j.noise_prefix.empty(); k++)
     {
-        float* d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
-        must(!d_noise || vp_stats_rel_error(d_noise, p[k].rec, npix, p[k].floor));
+        float*                d_noise = (float*)vp_malloc((size_t)npix * sizeof(float));
+        const vp_pixel_stats* rec = p[k].rec;
+        vp_pixel_stats*       d_pooled = nullptr;
+        if (j.halves_adaptive)
+        {
+            const vp_pixel_stats* second = j.mode == BEAUTY ? p[1].rec : j.other[k].rec;
+            rec = d_pooled = device_alloc<vp_pixel_stats>(npix, true);
+            must(vp_accumulate_stats(d_pooled, p[k].rec, (size_t)npix) || vp_accumulate_stats(d_pooled, second, (size_t)npix));
+        }
+        must(!d_noise || vp_stats_rel_error(d_noise, rec, npix, p[k].floor));
         write_grey_map(j, d_noise, j.noise_prefix + p[k].suffix);
         vp_free(d_noise);
+        if (d_pooled) vp_free(d_pooled);
     }
     if (!o.features_out.empty()) write_features(j, run);
 }

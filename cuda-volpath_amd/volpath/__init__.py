@@ -45,6 +45,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_halves_variance", "vp_filter_variance", "vp_denoise_var",
                  "vp_cross_error", "vp_select",
                  "vp_render_frames_planes_halves_stats",
+                 "vp_render_adaptive_halves", "vp_render_adaptive_planes_halves",
                  "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
@@ -202,6 +203,9 @@ def lib():
         L.vp_denoise_var.argtypes = [C.c_void_p] * 6 + [C.POINTER(DenoiseFeature), C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseParams)]
         L.vp_cross_error.argtypes = [C.c_void_p] * 7 + [C.c_int]
         L.vp_render_frames_planes_halves_stats.argtypes = [C.c_int, C.POINTER(PlaneBufs), C.POINTER(PlaneBufs), C.c_int, C.c_int, C.POINTER(Param)]
+        L.vp_render_adaptive_halves.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(Param), C.POINTER(Adaptive), C.POINTER(AdaptiveResult)]
+        L.vp_render_adaptive_planes_halves.argtypes = [C.c_int, C.POINTER(PlaneBufs), C.POINTER(PlaneBufs), C.c_int, C.c_int, C.POINTER(Param),
+                                                       C.POINTER(AdaptivePlanes3), C.POINTER(AdaptiveResult)]
         L.vp_select.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(SelectParams)]
         L.vp_render_frames_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Param)]
         L.vp_composite.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_int, C.c_float]
@@ -727,6 +731,31 @@ def render_frames_planes_halves_stats(mode, h0, h1, first, n, P):
     b0 = h0 if isinstance(h0, PlaneBufs) else plane_bufs(h0)
     b1 = h1 if isinstance(h1, PlaneBufs) else plane_bufs(h1)
     _chk(lib().vp_render_frames_planes_halves_stats(mode, C.byref(b0), C.byref(b1), first, n, C.byref(P)))
+
+
+def render_adaptive_halves(h0_ptr, h1_ptr, h0_stats_ptr, h1_stats_ptr, first, max_frames, P, rel_tol, floor_y=1e-3, min_frames=16, round_frames=32):
+    """render_adaptive's rounds into two half-buffers (vp_render_adaptive_halves): a pixel is sampled while neither of its two records is
+    frozen, frame f into half half_of_frame(f) alone, and both records are frozen once each half holds two samples and the two records
+    together hold min_frames and meet the criterion; returns render_adaptive's dict"""
+    a = Adaptive(rel_tol, floor_y, min_frames, round_frames)
+    r = AdaptiveResult()
+    _chk(lib().vp_render_adaptive_halves(h0_ptr, h1_ptr, h0_stats_ptr, h1_stats_ptr, first, max_frames, C.byref(P), C.byref(a), C.byref(r)))
+    return r.as_dict()
+
+
+def render_adaptive_planes_halves(mode, h0, h1, first, max_frames, P, rel_tol, floor_y, min_frames=16, round_frames=32):
+    """the same on the two halves of every plane of a plane call (vp_render_adaptive_planes_halves): mode, h0 and h1 as in
+    render_frames_planes_halves_stats; rel_tol and floor_y one value per plane of the mode (PLANE_NAMES), each plane's two records
+    pooled, the planes AND-ed; returns render_adaptive's dict"""
+    b0 = h0 if isinstance(h0, PlaneBufs) else plane_bufs(h0)
+    b1 = h1 if isinstance(h1, PlaneBufs) else plane_bufs(h1)
+    tol, fl = [float(v) for v in rel_tol], [float(v) for v in floor_y]
+    if len(tol) > 3 or len(fl) > 3:
+        raise ValueError("render_adaptive_planes_halves: at most 3 tolerances and floors")
+    a = AdaptivePlanes3((C.c_float * 3)(*tol), (C.c_float * 3)(*fl), min_frames, round_frames)
+    r = AdaptiveResult()
+    _chk(lib().vp_render_adaptive_planes_halves(mode, C.byref(b0), C.byref(b1), first, max_frames, C.byref(P), C.byref(a), C.byref(r)))
+    return r.as_dict()
 
 
 # the residual floor of a plane by its name: trans lies in [0, 1] and is constant over most pixels

@@ -411,8 +411,8 @@ int vp_denoise_guided(vp_float4* dst, const vp_float4* src, const vp_pixel_stats
  *   context's stream, for one frame too; it stages ONE plane, so vp_reserve_frames serves it unchanged.  It leaves nothing behind.
  *   Refused with VP_E_ARG before the device is touched, all four buffers untouched: any NULL pointer, d_h0 == d_h1, equal record
  *   pointers, n_frames <= 0, first_frame < 0.  Other errors as vp_render_frames_stats gives them.
- *   Not built: a form without records, adaptive rounds on halves.  Halves of calls with planes (layers, groups, group layers):
- *   vp_render_frames_planes_halves_stats, below (section 2.19).
+ *   Not built: a form without records.  Adaptive rounds on halves: vp_render_adaptive_halves, below (section 2.20).  Halves of calls
+ *   with planes (layers, groups, group layers): vp_render_frames_planes_halves_stats, below (section 2.19).
  *
  * vp_merge_halves: a and b are MEAN images of the two halves -- what vp_denoise, vp_denoise_guided or vp_scale_by_count(..., 1.0f)
  * write -- and of the records only n is read.  Binary32, one rounding per operation, no contraction, in the order written:
@@ -825,12 +825,69 @@ int vp_render_adaptive_group_layers(vp_float4* d_sun, vp_float4* d_sky, vp_float
  *   The output stage per plane is the cross-filter's sequence with that plane's two halves (and that plane's floor for the residual:
  *   trans is constant over most pixels and lies in [0, 1]); per-pixel selection composes in the same way from vp_cross_error and
  *   vp_select with a plane's halves -- the volpath_render driver offers the cross-filter and the variance stage on planes, not selection.
- *   Still not built: adaptive rounds on halves, a form without records, reduction across processes, VP_ARITH_FAST. */
+ *   Adaptive rounds on halves: vp_render_adaptive_planes_halves, below (section 2.20).
+ *   Still not built: a form without records, reduction across processes, VP_ARITH_FAST. */
 enum { VP_PLANES_LAYERS = 1, VP_PLANES_GROUPS = 2, VP_PLANES_GROUP_LAYERS = 3 };
 /* the planes of one half in the mode's order: fg trans | sun sky | sun sky trans; entries beyond the mode's planes are ignored */
 typedef struct { vp_float4* acc[3]; vp_pixel_stats* rec[3]; } vp_plane_bufs;   /* 48 bytes */
 int vp_render_frames_planes_halves_stats(int mode, const vp_plane_bufs* h0, const vp_plane_bufs* h1,
                                          int first_frame, int n_frames, const Param* p);
+
+/* Adaptive sampling on half-buffers: vp_render_adaptive's rounds into the two halves of a half-buffer render,
+ * for the beauty image and for every plane call -- Rousselle, Knaus and Zwicker 2012 sample adaptively into their two buffers, and the
+ * cross-filter (vp_denoise_var, vp_merge_halves, vp_cross_error, vp_select) then reads halves whose pixels hold different sample counts.
+ *
+ * vp_render_adaptive_halves, vp_render_adaptive_planes_halves.  THE DEFINITION: let N be the mode's number of planes -- N = 1 for
+ * vp_render_adaptive_halves, whose one plane is (d_h0, d_h0_stats) in half 0 and (d_h1, d_h1_stats) in half 1 --, S the context's
+ * sub-pixel factor, m = log2 S and h(f) = (f >> 2m) & 1, the half rule of vp_render_frames_halves_stats.
+ *   A pixel is ACTIVE while the FROZEN bit is clear in ALL 2N of its records.  The frozen set is exactly what the caller's 2N record
+ *   buffers say: there is no hidden state, so a second call continues a first one, and a pixel that the caller froze in ONE record
+ *   only is not active.  Rounds are vp_render_adaptive's: with B = round_frames, round k covers frames
+ *   [first_frame + k B, first_frame + min((k + 1) B, max_frames)).  Every owned pixel that is active at the start of a round receives
+ *   all frames of the round: its accumulators and records change exactly as the halves call -- vp_render_frames_halves_stats for the
+ *   beauty image, vp_render_frames_planes_halves_stats for planes -- defines for that pixel and those frames.  Frame f goes to half
+ *   h(f) of the ABSOLUTE frame number and to no other: the other half receives no +0.0f and no count for that frame, and a per-pixel
+ *   constant is one sequential addition per frame of the half.  A pixel that is not active receives nothing in any of its 2N
+ *   accumulators or records.
+ *   After the round each pixel that was active in it is frozen iff the following holds for every plane k = 0 .. N - 1, with r0 and r1
+ *   plane k's records in half 0 and half 1:
+ *     r0.n >= 2  and  r1.n >= 2
+ *     n   = r0.n + r1.n >= min_frames
+ *     sy  = r0.sum_y + r1.sum_y;   sy2 = r0.sum_y2 + r1.sum_y2          binary64, one rounding each
+ *     vp_render_adaptive's criterion holds on (sy, sy2, n) with (rel_tol[k], floor_y[k]): the same binary64 operations in the same
+ *     order, false on NaN
+ *   -- equivalently: the criterion holds on the record that vp_accumulate_stats makes of a copy of r0 and r1, and each half has at
+ *   least two samples.  Freezing sets the FROZEN bit in all 2N records and changes no other flag bit; it is permanent.  The call ends
+ *   when no owned pixel is active or the frames are used up.  `result` is as in vp_render_adaptive; `samples` counts one per pixel
+ *   and frame, not per plane or half.  A round that the staging cap splits into several launches gives the bits of one launch.
+ *   Why pooled, and why two per half: the product is vp_merge_halves of the two halves, and the pooled record measures the standard
+ *   error of that merge before any filter; a filter only lowers the variance.  So the rule is conservative for noise -- and says
+ *   nothing about the bias a filter adds.  Each half needs n >= 2 because vp_denoise reads a variance from each half's OWN records.
+ *   The planes are AND-ed for the reason given under "Adaptive sampling on planes": the gains and the plate are unknown at render time;
+ *   a large floor_y[k] (1e30f, say) takes plane k out of the decision.  With a sub-pixel factor a round_frames that is a multiple of
+ *   2 S^2 feeds both halves equally in every round; the call takes any round_frames (a round that lies in one half freezes nothing
+ *   while the other half has fewer than two samples).
+ *   What it is not: bit-equal to vp_render_adaptive on one buffer -- the sums are added in another order, so even the frozen sets may
+ *   differ --; and the stopping rule looks at the estimate it stops, the small bias of every adaptive call.  The image of a half is
+ *   sum / n per pixel (vp_scale_by_count, or the filters, with THAT half's records).
+ *   Refused before the device is touched, every buffer untouched and *result zeroed, with VP_E_ARG: an unknown mode; a NULL pointer
+ *   (h0, h1, a used entry, p, a; result excepted); any two of the 2N accumulators equal; any two of the 2N record buffers equal;
+ *   max_frames <= 0 or first_frame < 0; min_frames < 2 or round_frames < 1; a used tolerance or floor that is negative or NaN.  Entries
+ *   of rel_tol[], floor_y[] and of the vp_plane_bufs beyond the mode's planes are ignored, garbage included.  VP_E_STATE exactly where
+ *   the underlying call gives it -- vp_render_adaptive_halves: enabled work counters, as vp_render_adaptive; the plane modes:
+ *   VP_ENV_MIS, scalar and multi-channel tracking, enabled work counters, VP_ARITH_FAST --, the message naming this entry point; an
+ *   argument error comes before a state error.  VP_E_NOOPACITY as vp_render_frames gives for frame first_frame + max_frames - 1.
+ *   Everything else is the underlying halves call's: shards, estimators, streams, vp_set_stream, sub-pixel factors, volume formats
+ *   and vp_reserve_frames / vp_reserve_frames_groups behave as there.  It stops look-ahead batches, waits for pipelined launches and
+ *   runs on the context's stream, reading three counts back per round (it synchronises); it leaves nothing behind and never modifies
+ *   the cached pixel lists.  The render launches are the underlying call's instances on shorter lists, under that mode's census
+ *   kind; new are one small pass per ROUND over the active pixels that takes the decision, and the compaction's 4- and 6-record forms.
+ *   Still not built: rounds driven by the FILTERED error estimate (vp_cross_error) -- a host can already loop one-round calls around
+ *   its own filter, because the frozen set lives in the caller's records --; reduction across processes; VP_ARITH_FAST on plane modes. */
+int vp_render_adaptive_halves(vp_float4* d_h0, vp_float4* d_h1, vp_pixel_stats* d_h0_stats, vp_pixel_stats* d_h1_stats,
+                              int first_frame, int max_frames, const Param* p, const vp_adaptive* a, vp_adaptive_result* result);
+int vp_render_adaptive_planes_halves(int mode, const vp_plane_bufs* h0, const vp_plane_bufs* h1, int first_frame, int max_frames,
+                                     const Param* p, const vp_adaptive_planes3* a, vp_adaptive_result* result);
 
 /* ---- Feature pass: ray-marched opacity and depth planes per pixel
  * Every plane above is a Monte-Carlo estimate.  vp_render_features is deterministic: the march of precompute_opacity -- midpoint rule,

@@ -74,7 +74,15 @@ TOGETHER = [["--layers-out", "L", "--over", "0.1", "0.2", "0.3", "--plane-noise"
             ["--denoise-cross", "--denoise-features", "--resid-out", "r.hdr", "--batch", "3", "--spp", "12"],
             ["--denoise-cross", "--denoise-features", "--aa", "2"], ["--denoise-cross", "--aa", "2", "--out", "x.hdr"],
             ["--gpus", "2", "--devices", "0,0", "--features-out", "F", "--aa", "2", "--spp", "14"], ["--spp", "14"], ["--spp", "14", "--batch", "5"],
-            ["--bin", "cloud.bin", "--volume-format", "f32", "--gpus", "2", "--devices", "0,0"]]
+            ["--bin", "cloud.bin", "--volume-format", "f32", "--gpus", "2", "--devices", "0,0"],
+            ["--cross-noise", "0.5", "--cross-noise-out", "c.hdr", "--spp", "16", "--min-spp", "4", "--round", "4"],
+            ["--cross-noise", "0.5", "--denoise-select", "--denoise-features", "--spp", "16"], ["--cross-noise", "0.5", "--aa", "2", "--round", "4", "--spp", "16"],
+            ["--cross-noise", "0.5", "--noise", "0.5"], ["--cross-noise", "0.5", "--gpus", "2", "--devices", "0,0"], ["--cross-noise", "-1"],
+            ["--layers-out", "L", "--layers-denoise-cross", "--plane-cross-noise", "0.5", "0.25", "--plane-cross-noise-out", "N", "--spp", "16"],
+            ["--groups-out", "G", "--groups-denoise-cross", "--plane-cross-noise", "0.5", "0.25", "--plane-denoise-var"],
+            ["--planes-out", "P", "--planes-denoise-cross", "--planes-cross-noise", "0.5", "0.25", "0.1", "--plane-cross-noise-out", "M", "--spp", "16"],
+            ["--planes-out", "P", "--planes-denoise-cross", "--plane-cross-noise", "0.5", "0.25"], ["--planes-out", "P", "--planes-cross-noise", "0.5", "0.25", "0.1"],
+            ["--cross-noise", "0.5", "--planes-out", "P", "--planes-denoise-cross"], ["--cross-noise-out", "c.hdr"], ["--plane-cross-noise-out", "N"]]
 
 
 # ---- the pytest plugin half: note what the test_cli_* tests give to volpath_render

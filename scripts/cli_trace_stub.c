@@ -14,7 +14,7 @@
 
 typedef struct { char* base; size_t bytes; } Alloc;
 static Alloc    g_alloc[4096];
-static int      g_nalloc, g_nctx;
+static int      g_nalloc, g_nctx, g_subpixel = 1;
 static uint64_t g_h; /* the hash of the call being made */
 
 static void say(const char* fmt, ...)
@@ -171,7 +171,9 @@ int vp_init_volume(const void* v, vp_extent e, int format, const vp_float3* bmin
     return say(" volume %016llx", (unsigned long long)g_h), done();
 }
 #define SETTER1(name) int name(int a) { return begin(#name), i64(a), done(); }
-SETTER1(vp_set_estimator) SETTER1(vp_set_tracking) SETTER1(vp_set_envmap_sampling) SETTER1(vp_set_arithmetic) SETTER1(vp_set_subpixel) SETTER1(vp_set_bound_brick)
+SETTER1(vp_set_estimator) SETTER1(vp_set_tracking) SETTER1(vp_set_envmap_sampling) SETTER1(vp_set_arithmetic) SETTER1(vp_set_bound_brick)
+int vp_set_subpixel(int s) { g_subpixel = s; return begin("vp_set_subpixel"), i64(s), done(); }
+int vp_get_subpixel(void) { return begin("vp_get_subpixel"), say(" -> %d", g_subpixel), done(), g_subpixel; }
 int vp_set_rng(int mode, uint32_t k0, uint32_t k1) { return begin("vp_set_rng"), i64(mode), i64(k0), i64(k1), done(); }
 int vp_set_shard(int r, int w) { return begin("vp_set_shard"), i64(r), i64(w), done(); }
 int vp_render_time_ms(double* ms, int* launches, int reset)
@@ -234,6 +236,35 @@ int vp_render_adaptive_group_layers(vp_float4* a, vp_float4* b, vp_float4* c, vp
     three("vp_render_adaptive_group_layers", a, b, c, r, s, t, first, n, p);
     return flt(ad->rel_tol, 6), i64(ad->min_frames), i64(ad->round_frames), fill_three(a, b, c, r, s, t), result(res), done();
 }
+/* planes in two halves: every used entry of the two vp_plane_bufs, accumulators then records, half 0 then half 1 */
+static void halves_args(const char* name, int mode, const vp_plane_bufs* h0, const vp_plane_bufs* h1, TAIL)
+{
+    const int np = mode == VP_PLANES_GROUP_LAYERS ? 3 : 2;
+    begin(name), i64(mode);
+    for (int h = 0; h < 2; h++)
+        for (int k = 0; k < np; k++) ptr((h ? h1 : h0)->acc[k]), ptr((h ? h1 : h0)->rec[k]);
+    FRAMES;
+}
+static void fill_halves(int mode, const vp_plane_bufs* h0, const vp_plane_bufs* h1)
+{
+    const int np = mode == VP_PLANES_GROUP_LAYERS ? 3 : 2;
+    for (int h = 0; h < 2; h++)
+        for (int k = 0; k < np; k++) fill_floats((h ? h1 : h0)->acc[k]), mix(7), fill_bytes((h ? h1 : h0)->rec[k]), mix(7);
+}
+int vp_render_frames_planes_halves_stats(int mode, const vp_plane_bufs* h0, const vp_plane_bufs* h1, TAIL)
+{
+    return halves_args("vp_render_frames_planes_halves_stats", mode, h0, h1, first, n, p), fill_halves(mode, h0, h1), done();
+}
+int vp_render_adaptive_planes_halves(int mode, const vp_plane_bufs* h0, const vp_plane_bufs* h1, TAIL, const vp_adaptive_planes3* ad, vp_adaptive_result* res)
+{
+    halves_args("vp_render_adaptive_planes_halves", mode, h0, h1, first, n, p);
+    return flt(ad->rel_tol, 6), i64(ad->min_frames), i64(ad->round_frames), fill_halves(mode, h0, h1), result(res), done();
+}
+int vp_render_adaptive_halves(vp_float4* a, vp_float4* b, vp_pixel_stats* r, vp_pixel_stats* s, TAIL, const vp_adaptive* ad, vp_adaptive_result* res)
+{
+    begin("vp_render_adaptive_halves"), ptr(a), ptr(b), ptr(r), ptr(s), FRAMES, flt(&ad->rel_tol, 2), i64(ad->min_frames), i64(ad->round_frames);
+    return fill_floats(a), mix(7), fill_floats(b), mix(7), fill_bytes(r), mix(7), fill_bytes(s), result(res), done();
+}
 int vp_render_features(vp_float4* alpha, vp_float4* depth, const Param* p, const vp_feature_params* fp)
 {
     begin("vp_render_features"), ptr(alpha), ptr(depth), param(p), flt(&fp->step, 2), fill_floats(alpha), mix(7), fill_floats(depth);
@@ -246,6 +277,10 @@ int vp_render_features(vp_float4* alpha, vp_float4* depth, const Param* p, const
 int vp_scale_by_count(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* r, int n, float s)
 {
     return begin("vp_scale_by_count"), ptr(dst), ptr(src), ptr(r), i64(n), flt(&s, 1), fill_floats(dst), done();
+}
+int vp_accumulate_stats(vp_pixel_stats* dst, const vp_pixel_stats* src, size_t n)
+{
+    return begin("vp_accumulate_stats"), ptr(dst), ptr(src), i64((long long)n), fill_bytes(dst), done();
 }
 int vp_stats_rel_error(float* dst, const vp_pixel_stats* r, int n, float floor_y)
 {
