@@ -127,6 +127,7 @@ int ensure_device()
     if (knob("VP_EXIT_LOCAL", 0, 1, v)) { G.exit_local = v != 0; G.exit_local_auto = false; }
     if (knob("VP_EXIT_K", 1, VP_EXIT_TRIP, v)) G.exit_k = (unsigned)v;
     if (knob("VP_NO_FEATURE_SKIP", 0, 1, v)) G.use_feature_skip = v == 0;
+    if (knob("VP_NO_FETCH_FOLD", 0, 1, v)) G.fetch_fold = v == 0;
     G.dev_ready = true;
     return VP_OK;
 }
@@ -338,6 +339,7 @@ int do_init_volume_(const void* h_volume, vp_extent ext, int format, const vp_fl
     G.bound_mask_valid = false;
     HIPCHK(hipStreamSynchronize(G.stream));  // caller may free h_volume on return (host.cpp:1343); scratch freed by the guard
     S.linear      = G.linear ? 1 : 0;
+    fetch_scales(S, G.fetch_fold);   // (with linv, n and linear all set)
     G.have_volume = true;
     return VP_OK;
 }
@@ -423,6 +425,7 @@ void set_texture_filter_mode(bool bLinearFilter)
 {
     (void)pipe_quiesce();
     G.linear = bLinearFilter; G.S.linear = bLinearFilter ? 1 : 0;
+    fetch_scales(G.S, G.fetch_fold);   // `fold` implies `linear`
 }
 
 void free_cuda_buffers(void)
@@ -944,6 +947,33 @@ int vp_test_sun_start(int n, const float* origin_xyz, const float* sun_dir, cons
     HIPCHK(hipStreamSynchronize(G.stream));
     HIPCHK(hipMemcpy(out_new, dn, c * 32, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out_ref, dr, c * 32, hipMemcpyDeviceToHost));
+    return VP_OK;
+}
+int vp_test_fetch_split(float linv, int n, int count, const uint32_t* s_bits, uint32_t* out_two_step, uint32_t* out_folded)
+{
+    if (count < 0 || n < 1 || n > 4096) return fail(VP_E_ARG, "vp_test_fetch_split: count %d < 0 or n %d outside 1..4096", count, n);
+    if (!s_bits || !out_two_step || !out_folded) return fail(VP_E_ARG, "vp_test_fetch_split: null argument");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (count == 0) return VP_OK;
+    DevArrays D;
+    const size_t c = (size_t)count;
+    unsigned *ds = (unsigned*)D.get(c * 4), *dt = (unsigned*)D.get(c * 20), *df = (unsigned*)D.get(c * 20);
+    if (!ds || !dt || !df) return fail(VP_E_NOMEM, "vp_test_fetch_split: no device memory");
+    HIPCHK(hipMemcpy(ds, s_bits, c * 4, hipMemcpyHostToDevice));
+    launch_test_fetch_split(linv, n, count, ds, dt, df, G.stream);
+    HIPCHK(hipStreamSynchronize(G.stream));
+    HIPCHK(hipMemcpy(out_two_step, dt, c * 20, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_folded, df, c * 20, hipMemcpyDeviceToHost));
+    return VP_OK;
+}
+int vp_test_fetch_fold_axis(float linv, int n) { return fetch_scale_folds(linv, n) ? 1 : 0; }
+int vp_test_fetch_form(int* fold, float* fscale, float* fmul)
+{
+    if (!fold || !fscale || !fmul) return fail(VP_E_ARG, "vp_test_fetch_form: null argument");
+    if (!G.have_volume) return fail(VP_E_STATE, "vp_test_fetch_form: no volume");
+    *fold = G.S.fold;
+    for (int a = 0; a < 3; a++) { fscale[a] = G.S.fscale[a]; fmul[a] = G.S.fmul[a]; }
     return VP_OK;
 }
 int vp_test_hg(const float* g, const float* r0, const float* r1, const float* normal_xyz, const float* cos_query, float* dir_xyz, float* eval, int n)

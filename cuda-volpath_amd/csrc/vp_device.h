@@ -87,7 +87,52 @@ struct SceneDev
     const float* env_cdf_y;  // env_h
     const float* env_cdf_x;  // env_w * env_h
     float        env_pdfnorm_alt;
+    // The density fetch's per-axis scales (fetch_scales below; set with linv): xb = fma((p - bmin) * fmul, fscale, -0.5).
+    // fold: every axis has fmul = 1 -- the fetch skips that multiply (sample_density01).  Implies `linear`: the host sets the two
+    // together, and a launch that changes `linear` on its copy of the scene may only raise it (fold = 0 with linear = 1 is the
+    // two-step form, the same bits).
+    int   fold;
+    float fscale[3], fmul[3];
 };
+
+// ---- the fetch's scales.  The texel coordinate of an axis is xb = fl(fl(s * linv) * n - 0.5) with s = p - bmin: one multiply and one
+// fma.  Where linv is a power of two 2^k the multiply changes the exponent only, so with m = linv * n (exact as well: n <= 4096 has at
+// most 13 significant bits) xb' = fl(s * m - 0.5) is the same real number rounded once -- the same bits -- for every s of which
+// s * linv is a normal number, an infinity or a NaN.  What is left:
+//   - s * linv below 2^-126 in magnitude (subnormal, or flushed, or -0/+0): |s * linv| * n < 2^-126 * 2^12 = 2^-114 whatever the unit
+//     does with the subnormal, and |s * m| < 2^-114 likewise; -0.5 absorbs either (half an ulp of 0.5 is 2^-25): xb = xb' = -0.5f.
+//   - s * linv overflows: then |s * m| >= |s * linv| overflows as well (n >= 1), both forms give the infinity of s's sign; and where
+//     only s * linv * n overflows, the fma of the first form rounds that same product once, as the second does.
+//   - s infinite or NaN: the multiply by a positive finite number hands it on as it is; the fmas see the same operand class.
+// The preconditions, checked per axis on the host where linv is formed (fetch_scale_folds): linv is a positive normal power of two
+// (mantissa field 0, exponent field 1..254) and linv * n is finite.  An axis that does not meet them keeps both steps: fmul = linv,
+// fscale = n -- the two-step form's own operands.  A folded axis has fmul = 1 (s * 1 is s, -0 and NaNs included) and fscale = m, so
+// the two-step form serves scenes whose axes differ; where all three fold, `fold` lets the fetch drop the multiply.
+inline bool fetch_scale_folds(float linv, int n)
+{
+    unsigned b;
+    static_assert(sizeof b == sizeof linv, "binary32");
+    __builtin_memcpy(&b, &linv, 4);
+    const unsigned ex = b >> 23;   // sign and exponent fields
+    if ((b & 0x007fffffu) != 0u || ex < 1u || ex > 254u) return false;   // not a power of two; zero, subnormal, negative, inf, NaN
+    const float m = linv * (float)n;
+    return n >= 1 && n <= 4096 && m <= 3.40282347e+38f;
+}
+// fills fold / fscale / fmul from linv, nx..nz and linear; enable = false (VP_NO_FETCH_FOLD=1): the two-step form on every axis
+inline void fetch_scales(SceneDev& S, bool enable)
+{
+    const int n[3] = {S.nx, S.ny, S.nz};
+    int       folded = 0;
+    for (int a = 0; a < 3; a++)
+    {
+        // point sampling (linear = 0) keeps pn * n as it stands: its product has no -0.5 to absorb anything
+        const bool f = enable && S.linear != 0 && fetch_scale_folds(S.linv[a], n[a]);
+        S.fmul[a]    = f ? 1.0f : S.linv[a];
+        S.fscale[a]  = f ? S.linv[a] * (float)n[a] : (float)n[a];
+        folded += f ? 1 : 0;
+    }
+    S.fold = folded == 3 ? 1 : 0;
+}
 
 // ------------------------------------------------------------------------------ RNG
 // sampler.h:3-11
@@ -196,6 +241,12 @@ typedef RngPhiloxR<7>  RngPhilox7;  // VP_RNG_PHILOX7: Random123's smallest Crus
 
 // ------------------------------------------------------------------ texture fetches
 VP_ARITH_BEGIN
+// which unit's render_k instances take the folded fetch (sample_density01<.., FOLD>): the fast arithmetic's lose a wave to it
+#ifdef VP_ARITH_FAST
+constexpr bool kFetchFoldUnit = false;
+#else
+constexpr bool kFetchFoldUnit = true;
+#endif
 #define VP_U8_TRI_SCALE 2.3374372e-10f  // fl(1/(255*2^24)): full scale -> exactly 1.0f
 #define VP_U8_SCALE 0.003921569f        // fl(1/255)
 
@@ -206,26 +257,39 @@ __device__ __forceinline__ f3 to_local(const SceneDev& S, f3 pos)
 
 // texel-centre split of one axis: cell index (clamped) and the 8-bit filter weight as a float w/256
 // (an exact multiple of 2^-8 in [0,1])
-__device__ __forceinline__ void axis_linear(float pn, int n, int& i, float& fw)
+// (axis_split: from the texel coordinate xb = fl(pn * n - 0.5) -- the unit's own scaling: one rounding -- however it was formed.
+// wq: 1/256; sample_density01 passes 0 where the volume is point sampled, with xb = fl(pn * n): the index is then axis_point's --
+// max(xb, 0) and the truncation are its floor and its clamp at 0, a NaN gives 0 in both -- and the weight +0, as there; only for
+// xb = +inf, which no finite position gives, the weight is a NaN here, as it is in the filtered mode.)
+// below the first texel centre both taps clamp to texel 0: the same as sitting exactly on it (i = 0, w = 0)
+__device__ __forceinline__ float axis_clamp0(float xb) { return __builtin_fmaxf(xb, 0.0f); }
+// The same instruction, written out, for sample_density01: behind the join of its two forms the compiler no longer knows xb for an
+// fma's result -- quiet if a NaN -- and puts an instruction of its own in front of the maximum to quiet it.
+__device__ __forceinline__ float axis_clamp0_quiet(float xb)
 {
-    float xb = fma_(pn, (float)n, -0.5f);  // the unit's own scaling: one rounding
-    // below the first texel centre both taps clamp to texel 0: the same as sitting exactly on it (i = 0, w = 0)
-    xb       = __builtin_fmaxf(xb, 0.0f);
+    float r;
+    asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(xb));
+    return r;
+}
+// (axis_split_nn: xb clamped already)
+__device__ __forceinline__ void axis_split_nn(float xb, int n, int& i, float& fw, float wq)
+{
     // xb >= 0: xb - floorf(xb) is exact and below 1, so v_fract_f32 (which clamps its result below 1) gives the same bits, and the
     // conversion truncates toward zero, which is the floor.  (axis_linear_f32 below cannot do this: its xb may be negative, and
     // for a tiny negative xb the difference rounds to 1.0f where the instruction clamps.)
     float fr = __builtin_amdgcn_fractf(xb);
     i        = (int)xb;
-    fw       = __builtin_floorf(fma_(fr, 256.0f, 0.5f)) * (1.0f / 256.0f);  // round-to-nearest of fr*256, /256
+    fw       = __builtin_floorf(fma_(fr, 256.0f, 0.5f)) * wq;  // round-to-nearest of fr*256, /256
     // the packed cell of voxel i already holds the clamped (i, i+1) pair
     i = i > n - 1 ? n - 1 : i;
 }
+__device__ __forceinline__ void axis_split(float xb, int n, int& i, float& fw) { axis_split_nn(axis_clamp0(xb), n, i, fw, 1.0f / 256.0f); }
+__device__ __forceinline__ void axis_linear(float pn, int n, int& i, float& fw) { axis_split(fma_(pn, (float)n, -0.5f), n, i, fw); }
 // The same split for float texels, where the short cut above is not exact: below the first texel centre the two taps are the SAME
 // texel but the weight is still the fraction of the coordinate, and a*(1-w) + a*w is not a in binary32.  `low` tells the filter
 // to use the first tap twice (the packed cell of voxel 0 holds texels 0 and 1).
-__device__ __forceinline__ void axis_linear_f32(float pn, int n, int& i, float& fw, bool& low)
+__device__ __forceinline__ void axis_split_f32(float xb, int n, int& i, float& fw, bool& low)
 {
-    float xb = fma_(pn, (float)n, -0.5f);
     float fl = __builtin_floorf(xb);
     float fr = xb - fl;
     i        = (int)fl;
@@ -234,6 +298,7 @@ __device__ __forceinline__ void axis_linear_f32(float pn, int n, int& i, float& 
     i        = i < 0 ? 0 : i;
     i        = i > n - 1 ? n - 1 : i;
 }
+__device__ __forceinline__ void axis_linear_f32(float pn, int n, int& i, float& fw, bool& low) { axis_split_f32(fma_(pn, (float)n, -0.5f), n, i, fw, low); }
 __device__ __forceinline__ int axis_point(float pn, int n)
 {
     int i = (int)__builtin_floorf(pn * (float)n);
@@ -300,35 +365,68 @@ __device__ __forceinline__ float half_hi(unsigned w) { return (float)__builtin_b
 // normalised density in [0,1] at a world position: tex3D<float>(density_tex) of kernel.cu:692
 // HALF (with QUANT = false): a binary16 volume -- one 16-byte load, eight widenings, then the float filter's lerps as they stand: the
 // bits of the float volume that holds the widened values (include/volpath.h vp_init_volume)
-template <bool QUANT, bool HALF = false>
+// FOLD (uchar volumes): the scene's scales in place of linv and n (fetch_scales above), the multiply dropped where every axis folds.
+// Off by default, and the form as it stood: the instances that take it are named where they fetch (vp_integrator.h render_k --
+// the global-majorant kernels of uchar volumes in the exact arithmetic; every other instance loses a wave per SIMD to the second
+// form's registers, profiles/fetch_fold_kernel_resources.txt) and in test_density_k, so that vp_test_sample_density runs it.
+template <bool QUANT, bool HALF = false, bool FOLD = false>
 __device__ __forceinline__ float sample_density01(const SceneDev& S, f3 pos)
 {
     static_assert(!(QUANT && HALF), "a binary16 volume takes the float branches");
-    f3    p = to_local(S, pos);
+    static_assert(QUANT || !FOLD, "the folded form is built for uchar volumes");
     int   i, j, k;
     float fx, fy, fz;
     bool  lx = false, ly = false, lz = false;
-    if (S.linear)
+    if constexpr (FOLD)
     {
-        if (QUANT)
+        // to_local's multiply and the split's fma with fmul and fscale in place of linv and n -- the same operands, or, on an axis
+        // whose box scale is a power of two, 1 and linv * n: the same bits either way
+        const f3 s = f3{pos.x - S.bmin[0], pos.y - S.bmin[1], pos.z - S.bmin[2]};
+        float    xb, yb, zb;
+        if (S.fold)
         {
-            axis_linear(p.x, S.nx, i, fx);
-            axis_linear(p.y, S.ny, j, fy);
-            axis_linear(p.z, S.nz, k, fz);
+            // every axis folds (the default box of a volume whose dimension ratios are powers of two) and the volume is filtered:
+            // no multiply.  The one uniform branch of the default scene, where it branched on `linear` before.
+            xb = fma_(s.x, S.fscale[0], -0.5f); yb = fma_(s.y, S.fscale[1], -0.5f); zb = fma_(s.z, S.fscale[2], -0.5f);
         }
         else
         {
-            axis_linear_f32(p.x, S.nx, i, fx, lx);
-            axis_linear_f32(p.y, S.ny, j, fy, ly);
-            axis_linear_f32(p.z, S.nz, k, fz, lz);
+            // the two-step form; point sampling is the same product without the half texel (fma(a, b, +0) is fl(a * b) but for
+            // the sign of a zero, which the clamp below does not see)
+            const float off = S.linear ? -0.5f : 0.0f;
+            xb = fma_(s.x * S.fmul[0], S.fscale[0], off); yb = fma_(s.y * S.fmul[1], S.fscale[1], off); zb = fma_(s.z * S.fmul[2], S.fscale[2], off);
         }
+        // one split for the three forms: the point-sampled index is the split's with the weight's scale at 0 (axis_split_nn)
+        const float wq = S.linear ? 1.0f / 256.0f : 0.0f;
+        axis_split_nn(axis_clamp0_quiet(xb), S.nx, i, fx, wq);
+        axis_split_nn(axis_clamp0_quiet(yb), S.ny, j, fy, wq);
+        axis_split_nn(axis_clamp0_quiet(zb), S.nz, k, fz, wq);
     }
     else
     {
-        i = axis_point(p.x, S.nx);
-        j = axis_point(p.y, S.ny);
-        k = axis_point(p.z, S.nz);
-        fx = fy = fz = 0.0f;
+        f3 p = to_local(S, pos);
+        if (S.linear)
+        {
+            if (QUANT)
+            {
+                axis_linear(p.x, S.nx, i, fx);
+                axis_linear(p.y, S.ny, j, fy);
+                axis_linear(p.z, S.nz, k, fz);
+            }
+            else
+            {
+                axis_linear_f32(p.x, S.nx, i, fx, lx);
+                axis_linear_f32(p.y, S.ny, j, fy, ly);
+                axis_linear_f32(p.z, S.nz, k, fz, lz);
+            }
+        }
+        else
+        {
+            i = axis_point(p.x, S.nx);
+            j = axis_point(p.y, S.ny);
+            k = axis_point(p.z, S.nz);
+            fx = fy = fz = 0.0f;
+        }
     }
     size_t idx = cell_index(S, i, j, k);
     if (QUANT)

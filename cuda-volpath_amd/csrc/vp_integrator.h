@@ -1400,7 +1400,8 @@ ends_done:
                         den = 0.0f;
                         if (shadow || !(dist < t_empty))
                         {
-                            den = sample_density01<QUANT, HALF>(S, p) * cur_density;  // vol_sigma_t kernel.cu:682-695
+                            // (uchar volumes, exact arithmetic: the fetch with the scene's folded scales, vp_device.h fetch_scales)
+                            den = sample_density01<QUANT, HALF, QUANT && kFetchFoldUnit>(S, p) * cur_density;  // vol_sigma_t kernel.cu:682-695
                             if (COUNT && !(shadow && dist >= t_clip) && !(!shadow && ex_clear)) c_load++;
                         }
                     }

@@ -401,6 +401,8 @@ void launch_test_approach_walk_fast(int kind, int n, const float* par, const uns
 // vp_test_sun_start (vp_test_kernels.h test_sun_start_k): sun_dir is a HOST array of three floats, the rest device arrays
 void launch_test_sun_start(int n, const float* origin, const float* sun_dir, const float* box, unsigned* out_new, unsigned* out_ref, hipStream_t st);
 void launch_test_sun_start_fast(int n, const float* origin, const float* sun_dir, const float* box, unsigned* out_new, unsigned* out_ref, hipStream_t st);
+// vp_test_fetch_split (vp_test_kernels.h test_fetch_split_k): device arrays; the exact unit's (the fetch is one code in both)
+void launch_test_fetch_split(float linv, int n, int count, const unsigned* s_bits, unsigned* out_two, unsigned* out_fold, hipStream_t st);
 void launch_test_rng(int mode, unsigned x, unsigned y, unsigned f, unsigned k0, unsigned k1, int n, float* out, hipStream_t st);
 void launch_test_density(const SceneDev& S, bool quant, bool half, const float* pos, float* out, int n, hipStream_t st);
 }  // namespace vp

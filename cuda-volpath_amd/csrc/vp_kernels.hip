@@ -1643,7 +1643,7 @@ __global__ void accumulate_k(float4* dst, const float4* src, size_t n)
 }
 
 // ---- test kernels
-// test_hg_k, test_math_k, test_log_forms_k, test_approach_walk_k, test_sun_start_k: vp_test_kernels.h (compiled in both arithmetic modes)
+// test_hg_k, test_math_k, test_log_forms_k, test_approach_walk_k, test_sun_start_k, test_fetch_split_k: vp_test_kernels.h (compiled in both arithmetic modes)
 #include "vp_test_kernels.h"
 // vp_test_roots: the in-range root helpers of vp_math.h against the general forms compiled here, on every bit pattern in [lo, hi]
 __global__ void test_roots_k(int which, unsigned lo, unsigned hi, unsigned long long* mismatches, unsigned* first_bad)
@@ -1691,7 +1691,7 @@ __global__ void test_density_k(SceneDev S, const float* pos, float* out, int n)
 {
     int i = threadIdx.x + blockIdx.x * blockDim.x;
     if (i >= n) return;
-    out[i] = sample_density01<QUANT, HALF>(S, f3{pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]});
+    out[i] = sample_density01<QUANT, HALF, QUANT>(S, f3{pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]});   // (uchar: the folded form's code)
 }
 
 // ------------------------------------------------------------------ host-side launchers
@@ -2167,6 +2167,10 @@ void launch_test_approach_walk(int kind, int n, const float* par, const unsigned
 void launch_test_sun_start(int n, const float* origin, const float* sun_dir, const float* box, unsigned* out_new, unsigned* out_ref, hipStream_t st)
 {
     hipLaunchKernelGGL(test_sun_start_k, dim3((n + 255) / 256), dim3(256), 0, st, n, origin, sun_dir[0], sun_dir[1], sun_dir[2], box, out_new, out_ref);
+}
+void launch_test_fetch_split(float linv, int n, int count, const unsigned* s_bits, unsigned* out_two, unsigned* out_fold, hipStream_t st)
+{
+    hipLaunchKernelGGL(test_fetch_split_k, dim3((count + 255) / 256), dim3(256), 0, st, linv, n, count, s_bits, out_two, out_fold);
 }
 void launch_test_camera_ray(const SceneDev& S, unsigned width, unsigned height, const unsigned* pixels, float* dir, int n, hipStream_t st)
 {

@@ -266,6 +266,7 @@ struct State
     bool        exit_local  = false;      // VP_EXIT_LOCAL=1 / vp_set_exit_flights(2): also for the local-majorant estimators, whatever the stream
     bool        exit_local_auto = true;   // until either is used: for the local-majorant estimators on the counter-based streams (round 5: C3 +3.9 %,
                                           // c4s +1.6 %, c3ref +1 % with six-wave kernels; sampler.h +-0.5 %: profiles/experiments/r05_exit_local.txt)
+    bool        fetch_fold  = true;       // VP_NO_FETCH_FOLD=1: the density fetch scales every axis in two steps (vp_device.h fetch_scales), same bits
     bool        use_feature_skip = true;  // VP_NO_FEATURE_SKIP=1: vp_render_features marches the whole chord of every pixel whose ray hits the box (no class fills, no skip)
     unsigned    exit_k      = 8;          // null collisions in empty space before a lane asks for the test (VP_EXIT_K)
     unsigned char* d_exit   = nullptr;

@@ -1,6 +1,6 @@
 // vp_test_kernels.h -- the test hooks of the integrator's arithmetic: vp_test_math (test_math_k), vp_test_hg (test_hg_k),
-// vp_test_log_forms (test_log_forms_k), vp_test_approach_walk (test_approach_walk_k), vp_test_sun_start (test_sun_start_k) and
-// vp_test_camera_ray (test_camera_ray_k).
+// vp_test_log_forms (test_log_forms_k), vp_test_approach_walk (test_approach_walk_k), vp_test_sun_start (test_sun_start_k),
+// vp_test_camera_ray (test_camera_ray_k) and vp_test_fetch_split (test_fetch_split_k).
 // Included INSIDE a namespace by both translation units, like vp_integrator.h: vp_kernels.hip (namespace vp, the exact helpers) and
 // vp_kernels_fast.hip (namespace vp::fast, VP_ARITH_FAST).  vp_context.cpp launches the pair of the context's arithmetic mode, so
 // the hooks test the helpers the context's renders run.
@@ -242,3 +242,27 @@ __global__ void test_camera_ray_k(SceneDev S, unsigned width, unsigned height, c
     float* o = out + 6 * (size_t)i;
     o[0] = rd.x; o[1] = rd.y; o[2] = rd.z; o[3] = tn; o[4] = tf; o[5] = hit ? 1.0f : 0.0f;
 }
+
+// ---- vp_test_fetch_split: the axis split of sample_density01 in its two forms (vp_device.h fetch_scales) on caller-supplied bit
+// patterns of s = p - bmin.  out[5 i ..] = (i, fw bits of axis_split; i, fw bits, low of axis_split_f32).  The exact unit's only:
+// the fast unit's kernels do not take the folded form (kFetchFoldUnit) and it has no launcher for this one.
+#ifndef VP_ARITH_FAST
+__global__ void test_fetch_split_k(float linv, int n, int count, const unsigned* s_bits, unsigned* out_two, unsigned* out_fold)
+{
+    const int t = threadIdx.x + blockIdx.x * blockDim.x;
+    if (t >= count) return;
+    const float s = u2f(s_bits[t]);
+    const float m = linv * (float)n;
+    for (int fold = 0; fold < 2; fold++)
+    {
+        const float xb = fold ? fma_(s, m, -0.5f) : fma_(s * linv, (float)n, -0.5f);
+        int   i, j;
+        float fw, gw;
+        bool  low;
+        axis_split(xb, n, i, fw);
+        axis_split_f32(xb, n, j, gw, low);
+        unsigned* o = (fold ? out_fold : out_two) + 5 * (size_t)t;
+        o[0] = (unsigned)i; o[1] = f2u(fw); o[2] = (unsigned)j; o[3] = f2u(gw); o[4] = low ? 1u : 0u;
+    }
+}
+#endif

@@ -46,7 +46,7 @@ PART2_SYMBOLS = ["vp_last_error", "vp_version", "vp_device_count", "vp_set_devic
                  "vp_cross_error", "vp_select",
                  "vp_render_frames_planes_halves_stats",
                  "vp_render_adaptive_halves", "vp_render_adaptive_planes_halves",
-                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
+                 "vp_julia_voxelize", "vp_cloud_voxelize", "vp_test_math", "vp_test_rng", "vp_test_sample_density", "vp_test_hg", "vp_test_roots", "vp_test_log_forms", "vp_test_approach_walk", "vp_test_sun_start", "vp_test_fetch_split", "vp_test_fetch_fold_axis", "vp_test_fetch_form", "vp_test_launch_census", "vp_test_intersect_box", "vp_test_camera_ray",
                  "vp_test_eval_envmap", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_current", "vp_ctx_get_current", "vp_ctx_device",
                  "vp_accumulate", "vp_tile_owner", "vp_malloc", "vp_free", "vp_memset",
                  "vp_upload", "vp_download"]
@@ -246,6 +246,9 @@ def lib():
         L.vp_test_log_forms.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.vp_test_approach_walk.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.vp_test_sun_start.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_test_fetch_split.argtypes = [C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_test_fetch_fold_axis.argtypes = [C.c_float, C.c_int]
+        L.vp_test_fetch_form.argtypes = [C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
         L.vp_test_launch_census.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.vp_test_rng.argtypes = [C.c_int] + [C.c_uint32] * 5 + [C.c_int, C.c_void_p]
         L.vp_test_sample_density.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -1093,6 +1096,27 @@ def test_sun_start(origins, sun_dir, box):
     new, ref = np.zeros((n, 8), np.uint32), np.zeros((n, 8), np.uint32)
     _chk(lib().vp_test_sun_start(n, _p(origins), _p(sun_dir), _p(box), _p(new), _p(ref)))
     return new, ref
+
+
+def test_fetch_split(linv, n, s_bits):
+    """(two_step, folded): uint32 [count, 5] splits of one axis of n texels with the box scale linv at the offsets s = p - bmin given
+    as bit patterns: (index, weight bits) of the uchar split, (index, weight bits, low) of the float split (include/volpath.h)"""
+    s_bits = np.ascontiguousarray(s_bits, np.uint32).ravel()
+    two, fold = np.zeros((s_bits.size, 5), np.uint32), np.zeros((s_bits.size, 5), np.uint32)
+    _chk(lib().vp_test_fetch_split(float(linv), int(n), s_bits.size, _p(s_bits), _p(two), _p(fold)))
+    return two, fold
+
+
+def fetch_fold_axis(linv, n):
+    """whether an axis of n texels with the box scale linv takes the folded form (vp_test_fetch_fold_axis); no device"""
+    return bool(lib().vp_test_fetch_fold_axis(float(np.float32(linv)), int(n)))
+
+
+def fetch_form():
+    """(fold, fscale[3], fmul[3]) of the current volume and filter mode (vp_test_fetch_form)"""
+    f, sc, mu = C.c_int(0), np.zeros(3, np.float32), np.zeros(3, np.float32)
+    _chk(lib().vp_test_fetch_form(C.byref(f), _p(sc), _p(mu)))
+    return f.value, sc, mu
 
 
 CENSUS_EXACT, CENSUS_FAST = 0, 1                         # vp_test_launch_census: unit ...

@@ -1090,6 +1090,26 @@ int vp_test_approach_walk(int kind, int n, const float* params, const uint32_t* 
  * length and the factor were read, bits 1..3 = the slab reciprocal of x, y, z was read; 0 in out_ref).  The first seven words agree
  * bit for bit for every input.  VP_E_ARG, before the device is touched, for n < 0 or a null array. */
 int vp_test_sun_start(int n, const float* origin_xyz, const float* sun_dir, const float* box, uint32_t* out_new, uint32_t* out_ref);
+/* vp_test_fetch_split: the texel-centre split of one axis of the density fetch in its two forms -- two steps, pn = s * linv then
+ * fma(pn, n, -0.5), and folded, fma(s, linv * n, -0.5), which the fetch takes on an axis whose box scale linv is a power of two
+ * (csrc/vp_device.h fetch_scales) -- on count offsets s = p - bmin given as binary32 bit patterns, with n texels on the axis.
+ * out_two_step / out_folded[5 i ..] = (cell index and bits of the filter weight of the uchar split; cell index, bits of the weight
+ * and the `low` flag of the float split).  The two agree in every word wherever vp_test_fetch_fold_axis(linv, n) is 1.  Exact
+ * arithmetic only (the fetch is the same code in both units).  VP_E_ARG, before the device is touched, for count < 0, n outside
+ * 1..4096 or a null array. */
+int vp_test_fetch_split(float linv, int n, int count, const uint32_t* s_bits, uint32_t* out_two_step, uint32_t* out_folded);
+/* vp_test_fetch_fold_axis: 1 where an axis of n texels with the box scale linv = 1 / (bmax - bmin) meets the folded form's
+ * preconditions -- linv a positive normal power of two, linv * n finite, 1 <= n <= 4096 -- and 0 elsewhere.  The host's own
+ * predicate; needs no device and no volume. */
+int vp_test_fetch_fold_axis(float linv, int n);
+/* vp_test_fetch_form: the host's fetch scales for the current volume and filter mode, as the launch arguments carry them.  *fold = 1:
+ * every axis meets the folded form's preconditions; 0: not (also for point sampling and under VP_NO_FETCH_FOLD=1).  fscale[3] /
+ * fmul[3]: the per-axis operands -- (linv * n, 1) on a folded axis, (n, linv) elsewhere.  These are the HOST's values, whatever the
+ * volume's format: only the kernels built with the folded fetch read them -- the global-majorant integrator on uchar volumes in the
+ * exact arithmetic and vp_test_sample_density on uchar volumes; every other kernel (float and binary16 volumes, the local-majorant
+ * estimators, the fast arithmetic) scales in two steps from linv and n and ignores them.  VP_E_STATE without a volume, VP_E_ARG
+ * for a null pointer.  Needs no device work. */
+int vp_test_fetch_form(int* fold, float* fscale, float* fmul);
 /* vp_test_launch_census: which render_k and approach kernels the library compiles, and how often each has been launched.  Every
  * launch names its kernel through a table (csrc/vp_dispatch.h); the library counts the launches per table entry, in host memory,
  * process-wide (all contexts and threads together).  unit: 0 the exact arithmetic's kernels, 1 the fast arithmetic's.  kind: 0
