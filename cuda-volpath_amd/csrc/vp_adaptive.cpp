@@ -9,7 +9,8 @@
 // frozen in none of the 2 N records; the halves reduces never freeze, so a round ends with a pass of its own (freeze_halves_k) that decides
 // on the pooled records of the two halves, plane by plane.
 // vp_denoise: the filter of the output stage that reads the records (vp_denoise.hip); vp_denoise_guided: the same with feature planes.
-// vp_halves_variance, vp_filter_variance, vp_denoise_var: the variance stage of the cross-filter.
+// vp_halves_variance, vp_filter_variance, vp_denoise_var: the variance stage of the cross-filter.  The three
+// colour filter calls are one function, denoise_call, with the feature list and the variance plane as its optional parts.
 // vp_cross_error, vp_select: per-pixel selection among filtered candidates by cross-buffer error estimates.
 #include <climits>
 
@@ -174,6 +175,28 @@ static int denoise_lds_check(const char* fn, const vp_denoise_params* dp, int n_
                     denoise_guided_lds_bytes(dp->radius, dp->patch, n_features), DENOISE_LDS_LIMIT);
     return VP_OK;
 }
+// vp_denoise, vp_denoise_guided and vp_denoise_var: fn is the name the call reports under, d_sample_var and features what it has of
+// the two optional parts.  vp_denoise_var without its plane is vp_denoise_guided in all it does and reports, and that one without
+// features is vp_denoise, once the feature count has been checked under the name it was given to
+static int denoise_call(const char* fn, vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide,
+                        const vp_pixel_stats* d_guide_stats, const float* d_sample_var, const vp_denoise_feature* features, int n_features, int width, int height,
+                        const vp_denoise_params* dp)
+{
+    DenoiseFeaturesDev fd = {};
+    int rc = denoise_features_check(fn, dst, features, n_features, fd);
+    if (rc) return rc;
+    if (!d_sample_var && n_features == 0) fn = "vp_denoise";
+    if ((rc = denoise_args_check(fn, dst, src, d_stats, guide, d_guide_stats, width, height, dp))) return rc;
+    if (d_sample_var && (const void*)d_sample_var == (const void*)dst) return fail(VP_E_ARG, "%s: d_sample_var is dst (the call reads neighbours)", fn);
+    if ((d_sample_var || n_features) && (rc = denoise_lds_check(fn, dp, n_features))) return rc;
+    if ((rc = ensure_device())) return rc;
+    if (!guide) { guide = src; d_guide_stats = d_stats; }
+    launch_denoise((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, d_sample_var, fd, width,
+                   height, dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
+    HIPCHK(hipGetLastError());
+    G.last_denoise_form = G.denoise_form;
+    return VP_OK;
+}
 }  // namespace vph
 
 using namespace vph;
@@ -293,50 +316,17 @@ int vp_accumulate_stats(vp_pixel_stats* dst, const vp_pixel_stats* src, size_t n
 int vp_denoise(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
                int width, int height, const vp_denoise_params* dp)
 {
-    int rc = denoise_args_check("vp_denoise", dst, src, d_stats, guide, d_guide_stats, width, height, dp);
-    if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
-    if (!guide) { guide = src; d_guide_stats = d_stats; }
-    launch_denoise((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, width, height,
-                   dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
-    HIPCHK(hipGetLastError());
-    G.last_denoise_form = G.denoise_form;
-    return VP_OK;
+    return denoise_call("vp_denoise", dst, src, d_stats, guide, d_guide_stats, nullptr, nullptr, 0, width, height, dp);
 }
 int vp_denoise_guided(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
                       const vp_denoise_feature* features, int n_features, int width, int height, const vp_denoise_params* dp)
 {
-    DenoiseFeaturesDev fd = {};
-    int rc = denoise_features_check("vp_denoise_guided", dst, features, n_features, fd);
-    if (rc) return rc;
-    if (n_features == 0) return vp_denoise(dst, src, d_stats, guide, d_guide_stats, width, height, dp);
-    if ((rc = denoise_args_check("vp_denoise_guided", dst, src, d_stats, guide, d_guide_stats, width, height, dp))) return rc;
-    if ((rc = denoise_lds_check("vp_denoise_guided", dp, n_features))) return rc;
-    if ((rc = ensure_device())) return rc;
-    if (!guide) { guide = src; d_guide_stats = d_stats; }
-    launch_denoise_guided((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, fd, width,
-                          height, dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
-    HIPCHK(hipGetLastError());
-    G.last_denoise_form = G.denoise_form;
-    return VP_OK;
+    return denoise_call("vp_denoise_guided", dst, src, d_stats, guide, d_guide_stats, nullptr, features, n_features, width, height, dp);
 }
 int vp_denoise_var(vp_float4* dst, const vp_float4* src, const vp_pixel_stats* d_stats, const vp_float4* guide, const vp_pixel_stats* d_guide_stats,
                    const float* d_sample_var, const vp_denoise_feature* features, int n_features, int width, int height, const vp_denoise_params* dp)
 {
-    if (!d_sample_var) return vp_denoise_guided(dst, src, d_stats, guide, d_guide_stats, features, n_features, width, height, dp);
-    DenoiseFeaturesDev fd = {};
-    int rc = denoise_features_check("vp_denoise_var", dst, features, n_features, fd);
-    if (rc) return rc;
-    if ((rc = denoise_args_check("vp_denoise_var", dst, src, d_stats, guide, d_guide_stats, width, height, dp))) return rc;
-    if ((const void*)d_sample_var == (const void*)dst) return fail(VP_E_ARG, "vp_denoise_var: d_sample_var is dst (the call reads neighbours)");
-    if ((rc = denoise_lds_check("vp_denoise_var", dp, n_features))) return rc;
-    if ((rc = ensure_device())) return rc;
-    if (!guide) { guide = src; d_guide_stats = d_stats; }
-    launch_denoise_var((float4*)dst, (const float4*)src, (const PixelStatsDev*)d_stats, (const float4*)guide, (const PixelStatsDev*)d_guide_stats, d_sample_var, fd,
-                       width, height, dp->radius, dp->patch, dp->k * dp->k, G.denoise_form, G.stream);
-    HIPCHK(hipGetLastError());
-    G.last_denoise_form = G.denoise_form;
-    return VP_OK;
+    return denoise_call(d_sample_var ? "vp_denoise_var" : "vp_denoise_guided", dst, src, d_stats, guide, d_guide_stats, d_sample_var, features, n_features, width, height, dp);
 }
 int vp_halves_variance(float* d_u, float* d_q, const vp_pixel_stats* a_stats, const vp_pixel_stats* b_stats, int size)
 {

@@ -1,22 +1,28 @@
 // vp_denoise.hip -- the variance-guided NL-means filter of the output stage (include/volpath.h vp_denoise).
 //
-// Both kernels compute the definition of the header to the bit: binary32, no contraction, the patch distance as row sums left to
+// Every kernel computes the definition of the header to the bit: binary32, no contraction, the patch distance as row sums left to
 // right and their sum top to bottom, the weights summed over the offsets in raster order, expf_ in the exact arithmetic (this file
 // is compiled without VP_ARITH_FAST, like the output stage of vp_kernels.hip).
-//   denoise_tiled_k (form 0): one 256-thread workgroup per 32 x 8 pixel tile.  (y, v) of the tile plus an R + F halo and the mean
-//     colours of the tile plus an R halo are staged in LDS once, fetched with clamped coordinates; per offset the pair terms e of the
-//     tile's F-halo plane are computed once each into LDS (2.1 per thread at F = 3 instead of 49) and every thread sums its patch
-//     from there.  The plane is double buffered: one barrier per offset.
-//   denoise_plain_k (form 1): one thread per pixel, straight from global memory, looping over the definition.  The cross-check.
-//   denoise_guided_tiled_k / denoise_guided_plain_k: the two forms of vp_denoise_guided, kernels of their
-//     own so that the two above stay as they are: the same passes, plus NF feature channels staged once into LDS planes shaped like
-//     the colour planes and a per-pixel-pair feature distance that caps the weight.
+// Each pass is written once, as a __device__ __forceinline__ template over a loader that gives (y, v) at a clamped pixel index and an
+// accumulator that takes an offset's patch sum; the __global__ kernels are instances of these:
+//   stage_yv + tiled_offsets (form 0): one 256-thread workgroup per 32 x 8 pixel tile.  (y, v) of the tile plus an R + F halo are
+//     staged in LDS once, fetched with clamped coordinates; per offset the pair terms e of the tile's F-halo plane are computed once
+//     each into LDS (2.1 per thread at F = 3 instead of 49) and every thread sums its patch from there.  The plane is double
+//     buffered: one barrier per offset.
+//   plain_offsets (form 1): one thread per pixel, straight from global memory, looping over the definition.  The cross-check.
+//   denoise_tiled<F, NF>: the tiled colour filter on these.  The loader is guide_yv, the mean colours of the tile plus an R halo are
+//     staged beside (y, v), the sums are a ColourSum.  NF = 0 is vp_denoise (denoise_tiled_k); otherwise vp_denoise_guided (DESIGN.md
+//     section 2.13; denoise_guided_tiled_k): NF feature channels staged once into LDS planes shaped like the colour planes and a
+//     per-pixel-pair feature distance that caps the weight.  With NF = 0 the feature planes, their staging and the distance are no code.
+//   denoise_plain_k is plain_offsets with guide_yv and a ColourSum.  denoise_guided_plain_k keeps loops of its own: on plain_offsets it
+//     was half a per cent slower on a 1280 x 720 image, the same in every run, with the same instructions in its loops in another
+//     arrangement (profiles/denoise_fold_kernel_resources.txt); as it stands it is the kernel it was, instruction for instruction.
 //   vp_denoise_var's instances of these four: a trailing parameter pack V that is empty or one `const float*`, the caller's per-sample
-//     variance plane; v is then plane[a] * s_a in place of the records' variance, everything else as it stands.  An empty pack leaves
-//     the parameter list -- and with it the instructions -- of the instances above as they were (profiles/variance_kernel_resources.txt).
+//     variance plane; v is then plane[a] * s_a in place of the records' variance, everything else as it stands.  An empty pack adds
+//     no kernel parameter (profiles/variance_kernel_resources.txt, profiles/denoise_fold_kernel_resources.txt).
 //   variance_tiled_k / variance_plain_k: the two forms of vp_filter_variance, the same passes on one scalar
-//     plane u with its noise q: two staged planes with an R + F halo, the e planes, no colour planes -- u with its R halo is inside
-//     the staged plane.
+//     plane u with its noise q: the loader is (u[g], q[g]), there are no colour planes -- u with its R halo is inside the staged
+//     plane -- and a pixel is filtered where u != 0.
 //   select_tiled_k / select_plain_k: the two forms of vp_select: box sums of n error planes, the smallest
 //     picked per pixel, the picks blended over a window; nothing of the filter above is shared but the tile.
 // LDS layout (cdna_hip_programming.md section 2: ds_read_b32 / ds_write_b32 bank = dword address mod 32 within a 32-lane half):
@@ -83,142 +89,7 @@ __device__ __forceinline__ float patch_weight(float D, float inv_area)
     D = D > 0.0f ? D : 0.0f;
     return expf_(-D);
 }
-
-template <int F, class... V>
-__global__ __launch_bounds__(DN_TX * DN_TY) void denoise_tiled_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
-                                                                  const PixelStatsDev* gstats, int W, int H, int R, float k2, V... svar)
-{
-    constexpr int EW = DN_TX + 2 * F, EH = DN_TY + 2 * F;   // the e plane: the tile plus an F halo
-    constexpr int YW = EW + 32;                             // pitch of the (y, v) planes (>= DN_TX + 2 (R + F) for R <= 16)
-    extern __shared__ float lds[];
-    const int YH = DN_TY + 2 * (R + F), CW = DN_TX + 2 * R, CH = DN_TY + 2 * R;
-    float* Ly = lds;
-    float* Lv = Ly + YW * YH;
-    float* Lc = Lv + YW * YH;             // three planes of CW * CH
-    float* Le = Lc + 3 * CW * CH;         // two planes of EW * EH
-    const int tid = threadIdx.x, tx = tid & (DN_TX - 1), ty = tid / DN_TX;
-    const int x0 = blockIdx.x * DN_TX, y0 = blockIdx.y * DN_TY;
-    const int px = x0 + tx, py = y0 + ty;
-    const bool inside = px < W && py < H;
-    const int  pi = clampi(py, H - 1) * W + clampi(px, W - 1);
-    // the thread's own pixel: mean colour, heat and the guide's variance
-    const float4 A  = src[pi];
-    const float  sp = inv_count(stats[pi].n);
-    const float  vme = guide_variance_at(gstats, pi, svar...);
-    float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
-    // a tile without a noisy pixel (the per-pixel-constant classes) is the plain output stage
-    if (!__syncthreads_or(inside && vme != 0.0f))
-    {
-        if (inside) dst[pi] = out;
-        return;
-    }
-    const int halo = R + F;
-    for (int i = tid; i < (DN_TX + 2 * halo) * YH; i += DN_TX * DN_TY)
-    {
-        const int r = i / (DN_TX + 2 * halo), c = i - r * (DN_TX + 2 * halo);
-        float y, v;
-        guide_yv(guide, gstats, clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1), y, v, svar...);
-        Ly[r * YW + c] = y;
-        Lv[r * YW + c] = v;
-    }
-    for (int i = tid; i < CW * CH; i += DN_TX * DN_TY)
-    {
-        const int r = i / CW, c = i - r * CW;
-        const int g = clampi(y0 - R + r, H - 1) * W + clampi(x0 - R + c, W - 1);
-        const float4 B = src[g];
-        const float  s = inv_count(stats[g].n);
-        Lc[i] = B.x * s;
-        Lc[CW * CH + i] = B.y * s;
-        Lc[2 * CW * CH + i] = B.z * s;
-    }
-    __syncthreads();
-    const bool  filtered = inside && vme != 0.0f;
-    const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
-    float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
-    int buf = 0;
-    for (int oy = -R; oy <= R; oy++)
-        for (int ox = -R; ox <= R; ox++, buf ^= 1)
-        {
-            float* E = Le + buf * (EW * EH);
-            const int shift = oy * YW + ox;
-            for (int i = tid; i < EW * EH; i += DN_TX * DN_TY)
-            {
-                const int r = i / EW, c = i - r * EW;
-                const int a = (r + R) * YW + (c + R);
-                E[i] = pair_term(Ly[a], Lv[a], Ly[a + shift], Lv[a + shift], k2);
-            }
-            __syncthreads();   // (the other buffer is written next: its readers passed this barrier)
-            const int qx = px + ox, qy = py + oy;
-            if (filtered && qx >= 0 && qx < W && qy >= 0 && qy < H)
-            {
-                float D = 0.0f;
-#pragma unroll
-                for (int dy = 0; dy <= 2 * F; dy++)
-                {
-                    float row = 0.0f;
-#pragma unroll
-                    for (int dx = 0; dx <= 2 * F; dx++) row = row + E[(ty + dy) * EW + tx + dx];
-                    D = D + row;
-                }
-                const float w = patch_weight(D, inv_area);
-                const int   ci = (ty + R + oy) * CW + tx + R + ox;
-                den = den + w;
-                nr  = nr + w * Lc[ci];
-                ng  = ng + w * Lc[CW * CH + ci];
-                nb  = nb + w * Lc[2 * CW * CH + ci];
-            }
-        }
-    if (filtered) { out.x = nr / den; out.y = ng / den; out.z = nb / den; }
-    if (inside) dst[pi] = out;
-}
-
-template <class... V>
-__global__ __launch_bounds__(256) void denoise_plain_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
-                                                       const PixelStatsDev* gstats, int W, int H, int R, int F, float k2, V... svar)
-{
-    const int idx = threadIdx.x + blockIdx.x * blockDim.x;
-    if (idx >= W * H) return;
-    const int py = idx / W, px = idx - py * W;
-    const float4 A  = src[idx];
-    const float  sp = inv_count(stats[idx].n);
-    float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
-    if (guide_variance_at(gstats, idx, svar...) != 0.0f)
-    {
-        const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
-        float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
-        for (int oy = -R; oy <= R; oy++)
-            for (int ox = -R; ox <= R; ox++)
-            {
-                const int qx = px + ox, qy = py + oy;
-                if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-                float D = 0.0f;
-                for (int dy = -F; dy <= F; dy++)
-                {
-                    float row = 0.0f;
-                    for (int dx = -F; dx <= F; dx++)
-                    {
-                        float ya, va, yb, vb;
-                        guide_yv(guide, gstats, clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1), ya, va, svar...);
-                        guide_yv(guide, gstats, clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1), yb, vb, svar...);
-                        row = row + pair_term(ya, va, yb, vb, k2);
-                    }
-                    D = D + row;
-                }
-                const float  w = patch_weight(D, inv_area);
-                const int    q = qy * W + qx;
-                const float4 B = src[q];
-                const float  s = inv_count(stats[q].n);
-                den = den + w;
-                nr  = nr + w * (B.x * s);
-                ng  = ng + w * (B.y * s);
-                nb  = nb + w * (B.z * s);
-            }
-        out.x = nr / den; out.y = ng / den; out.z = nb / den;
-    }
-    dst[idx] = out;
-}
-
-// ---- vp_denoise_guided: the same filter with the weight of an offset cut by a distance of noise-free features
+// vp_denoise_guided: the weight of an offset cut by a distance of noise-free features
 // the patch distance as patch_weight scales and clamps it, before the exponential
 __device__ __forceinline__ float patch_distance(float D, float inv_area)
 {
@@ -232,50 +103,166 @@ __device__ __forceinline__ float feature_term(float fa, float fb, float g)
     return fa == fb ? 0.0f : (d * d) * g;
 }
 __device__ __forceinline__ float guided_weight(float D, float Df) { return expf_(-(Df > D ? Df : D)); }
-
-// denoise_tiled_k with NF feature planes of the tile plus an R halo behind the e planes, pitch and indexing of the colour planes:
-// fb of a half-wave is 32 consecutive dwords, fa stays in registers, no barrier more than denoise_tiled_k has
-template <int F, int NF, class... V>
-__global__ __launch_bounds__(DN_TX * DN_TY) void denoise_guided_tiled_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
-                                                                         const PixelStatsDev* gstats, DenoiseFeaturesDev feat, int W, int H, int R, float k2,
-                                                                         V... svar)
+// the weight of an offset from its patch sum D; Df, the feature distance, is read by the guided filter only
+template <bool GUIDED>
+__device__ __forceinline__ float offset_weight(float D, float inv_area, float Df)
 {
-    constexpr int EW = DN_TX + 2 * F, EH = DN_TY + 2 * F;
-    constexpr int YW = EW + 32;
-    extern __shared__ float lds[];
-    const int YH = DN_TY + 2 * (R + F), CW = DN_TX + 2 * R, CH = DN_TY + 2 * R;
-    float* Ly = lds;
-    float* Lv = Ly + YW * YH;
-    float* Lc = Lv + YW * YH;             // three planes of CW * CH
-    float* Le = Lc + 3 * CW * CH;         // two planes of EW * EH
-    float* Lf = Le + 2 * EW * EH;         // NF planes of CW * CH
-    const int tid = threadIdx.x, tx = tid & (DN_TX - 1), ty = tid / DN_TX;
-    const int x0 = blockIdx.x * DN_TX, y0 = blockIdx.y * DN_TY;
-    const int px = x0 + tx, py = y0 + ty;
-    const bool inside = px < W && py < H;
-    const int  pi = clampi(py, H - 1) * W + clampi(px, W - 1);
-    const float4 A  = src[pi];
-    const float  sp = inv_count(stats[pi].n);
-    const float  vme = guide_variance_at(gstats, pi, svar...);
-    float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
-    if (!__syncthreads_or(inside && vme != 0.0f))
+    if constexpr (GUIDED) return guided_weight(patch_distance(D, inv_area), Df);
+    else return patch_weight(D, inv_area);
+}
+__device__ __forceinline__ float patch_inv_area(int F) { return 1.0f / (float)((2 * F + 1) * (2 * F + 1)); }
+// the colour kernels' sums over the offsets and the quotient that is the filtered colour
+struct ColourSum
+{
+    float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
+    __device__ __forceinline__ void add(float w, float r, float g, float b)
     {
-        if (inside) dst[pi] = out;
-        return;
+        den = den + w;
+        nr  = nr + w * r;
+        ng  = ng + w * g;
+        nb  = nb + w * b;
     }
-    const int halo = R + F;
-    for (int i = tid; i < (DN_TX + 2 * halo) * YH; i += DN_TX * DN_TY)
+    __device__ __forceinline__ void divide_into(float4& out) const { out.x = nr / den; out.y = ng / den; out.z = nb / den; }
+};
+
+// ---- form 0: the tile
+// the planes of a tile at patch radius F: the e plane is the tile plus an F halo; YW is the pitch of the two staged (y, v) planes
+// (>= DN_TX + 2 (R + F) for R <= 16), which have DN_TY + 2 (R + F) rows
+template <int F>
+struct TilePlanes
+{
+    static constexpr int EW = DN_TX + 2 * F, EH = DN_TY + 2 * F, YW = EW + 32;
+};
+// a thread's place: its tile's origin, its pixel (px, py), whether that is inside the image, and the pixel's index clamped into it.
+// Every function that needs it makes its own from the built-in indices: the compiler knows their ranges there, and merges the copies
+struct TilePos
+{
+    int  tid, tx, ty, x0, y0, px, py, pi;
+    bool inside;
+    __device__ __forceinline__ TilePos(int W, int H)
+    {
+        tid = threadIdx.x; tx = tid & (DN_TX - 1); ty = tid / DN_TX;
+        x0 = blockIdx.x * DN_TX; y0 = blockIdx.y * DN_TY;
+        px = x0 + tx; py = y0 + ty;
+        inside = px < W && py < H;
+        pi = clampi(py, H - 1) * W + clampi(px, W - 1);
+    }
+};
+// (y, v) of the tile plus a halo of R + F, YH = DN_TY + 2 halo rows, into the planes Ly, Lv, fetched with clamped coordinates:
+// load(g, y, v) gives the two at pixel g.  halo and YH are the caller's, which lays out its planes with them: derived once more in
+// here they cost the F >= 2 instances two VGPRs (profiles/denoise_fold_kernel_resources.txt)
+template <int F, class Load>
+__device__ __forceinline__ void stage_yv(float* Ly, float* Lv, int W, int H, int halo, int YH, Load load)
+{
+    constexpr int YW = TilePlanes<F>::YW;
+    const TilePos t(W, H);
+    for (int i = t.tid; i < (DN_TX + 2 * halo) * YH; i += DN_TX * DN_TY)
     {
         const int r = i / (DN_TX + 2 * halo), c = i - r * (DN_TX + 2 * halo);
         float y, v;
-        guide_yv(guide, gstats, clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1), y, v, svar...);
+        load(clampi(t.y0 - halo + r, H - 1) * W + clampi(t.x0 - halo + c, W - 1), y, v);
         Ly[r * YW + c] = y;
         Lv[r * YW + c] = v;
     }
-    for (int i = tid; i < CW * CH; i += DN_TX * DN_TY)
+}
+// the offsets in raster order.  Per offset: the e plane of the tile from the staged (y, v) into one of the two buffers at Le, one
+// barrier, and where the thread's pixel is filtered and the offset stays inside the image, acc(D, ox, oy) with the patch sum D
+template <int F, class Acc>
+__device__ __forceinline__ void tiled_offsets(const float* Ly, const float* Lv, float* Le, bool filtered, int W, int H, int R, float k2, Acc acc)
+{
+    constexpr int EW = TilePlanes<F>::EW, EH = TilePlanes<F>::EH, YW = TilePlanes<F>::YW;
+    const TilePos t(W, H);
+    int buf = 0;
+    for (int oy = -R; oy <= R; oy++)
+        for (int ox = -R; ox <= R; ox++, buf ^= 1)
+        {
+            float* E = Le + buf * (EW * EH);
+            const int shift = oy * YW + ox;
+            for (int i = t.tid; i < EW * EH; i += DN_TX * DN_TY)
+            {
+                const int r = i / EW, c = i - r * EW;
+                const int a = (r + R) * YW + (c + R);
+                E[i] = pair_term(Ly[a], Lv[a], Ly[a + shift], Lv[a + shift], k2);
+            }
+            __syncthreads();   // (the other buffer is written next: its readers passed this barrier)
+            const int qx = t.px + ox, qy = t.py + oy;
+            if (filtered && qx >= 0 && qx < W && qy >= 0 && qy < H)
+            {
+                float D = 0.0f;
+#pragma unroll
+                for (int dy = 0; dy <= 2 * F; dy++)
+                {
+                    float row = 0.0f;
+#pragma unroll
+                    for (int dx = 0; dx <= 2 * F; dx++) row = row + E[(t.ty + dy) * EW + t.tx + dx];
+                    D = D + row;
+                }
+                acc(D, ox, oy);
+            }
+        }
+}
+
+// ---- form 1: the definition at pixel (px, py) from global memory.  Per offset that stays inside the image, in raster order: the patch
+// sum D over clamped positions, load(g, y, v) giving the two planes at pixel g, and acc(D, q) with the offset's pixel index q
+template <class Load, class Acc>
+__device__ __forceinline__ void plain_offsets(int px, int py, int W, int H, int R, int F, float k2, Load load, Acc acc)
+{
+    for (int oy = -R; oy <= R; oy++)
+        for (int ox = -R; ox <= R; ox++)
+        {
+            const int qx = px + ox, qy = py + oy;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            float D = 0.0f;
+            for (int dy = -F; dy <= F; dy++)
+            {
+                float row = 0.0f;
+                for (int dx = -F; dx <= F; dx++)
+                {
+                    float ya, va, yb, vb;
+                    load(clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1), ya, va);
+                    load(clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1), yb, vb);
+                    row = row + pair_term(ya, va, yb, vb, k2);
+                }
+                D = D + row;
+            }
+            acc(D, qy * W + qx);
+        }
+}
+
+// ---- the colour filter: vp_denoise (NF == 0, feat unused), vp_denoise_guided (NF features) and vp_denoise_var's instances of both.
+// LDS: the two (y, v) planes, the mean colours of the tile plus an R halo, the two e planes (denoise_lds_bytes) and behind them NF
+// feature planes at the pitch and indexing of the colour planes (denoise_guided_lds_bytes): fb of a half-wave is 32 consecutive dwords,
+// fa stays in registers, and the features cost no barrier
+template <int F, int NF, class... V>
+__device__ __forceinline__ void denoise_tiled(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats,
+                                              DenoiseFeaturesDev feat, int W, int H, int R, float k2, V... svar)
+{
+    using P = TilePlanes<F>;
+    extern __shared__ float lds[];
+    const int YH = DN_TY + 2 * (R + F), CW = DN_TX + 2 * R, CH = DN_TY + 2 * R;
+    float* Ly = lds;
+    float* Lv = Ly + P::YW * YH;
+    float* Lc = Lv + P::YW * YH;              // three planes of CW * CH
+    float* Le = Lc + 3 * CW * CH;             // two planes of EW * EH
+    float* Lf = Le + 2 * P::EW * P::EH;       // NF planes of CW * CH
+    const TilePos t(W, H);
+    // the thread's own pixel: mean colour, heat and the guide's variance
+    const float4 A  = src[t.pi];
+    const float  sp = inv_count(stats[t.pi].n);
+    const float  vme = guide_variance_at(gstats, t.pi, svar...);
+    float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
+    // a tile without a noisy pixel (the per-pixel-constant classes) is the plain output stage
+    if (!__syncthreads_or(t.inside && vme != 0.0f))
+    {
+        if (t.inside) dst[t.pi] = out;
+        return;
+    }
+    const int halo = R + F;
+    stage_yv<F>(Ly, Lv, W, H, halo, YH, [&](int g, float& y, float& v) { guide_yv(guide, gstats, g, y, v, svar...); });
+    for (int i = t.tid; i < CW * CH; i += DN_TX * DN_TY)
     {
         const int r = i / CW, c = i - r * CW;
-        const int g = clampi(y0 - R + r, H - 1) * W + clampi(x0 - R + c, W - 1);
+        const int g = clampi(t.y0 - R + r, H - 1) * W + clampi(t.x0 - R + c, W - 1);
         const float4 B = src[g];
         const float  s = inv_count(stats[g].n);
         Lc[i] = B.x * s;
@@ -286,52 +273,60 @@ __global__ __launch_bounds__(DN_TX * DN_TY) void denoise_guided_tiled_k(float4* 
         for (int j = 0; j < NF; j++) Lf[j * (CW * CH) + i] = feat.chan[j][4 * (size_t)g];
     }
     __syncthreads();
-    const bool  filtered = inside && vme != 0.0f;
-    const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
-    float fa[NF];
+    const bool  filtered = t.inside && vme != 0.0f;
+    const float inv_area = patch_inv_area(F);
+    float fa[NF ? NF : 1];
 #pragma unroll
-    for (int j = 0; j < NF; j++) fa[j] = Lf[j * (CW * CH) + (ty + R) * CW + tx + R];
-    float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
-    int buf = 0;
-    for (int oy = -R; oy <= R; oy++)
-        for (int ox = -R; ox <= R; ox++, buf ^= 1)
-        {
-            float* E = Le + buf * (EW * EH);
-            const int shift = oy * YW + ox;
-            for (int i = tid; i < EW * EH; i += DN_TX * DN_TY)
-            {
-                const int r = i / EW, c = i - r * EW;
-                const int a = (r + R) * YW + (c + R);
-                E[i] = pair_term(Ly[a], Lv[a], Ly[a + shift], Lv[a + shift], k2);
-            }
-            __syncthreads();   // (the other buffer is written next: its readers passed this barrier)
-            const int qx = px + ox, qy = py + oy;
-            if (filtered && qx >= 0 && qx < W && qy >= 0 && qy < H)
-            {
-                float D = 0.0f;
+    for (int j = 0; j < NF; j++) fa[j] = Lf[j * (CW * CH) + (t.ty + R) * CW + t.tx + R];
+    ColourSum sum;
+    tiled_offsets<F>(Ly, Lv, Le, filtered, W, H, R, k2, [&](float D, int ox, int oy) {
+        const int ci = (t.ty + R + oy) * CW + t.tx + R + ox;
+        float Df = 0.0f;
 #pragma unroll
-                for (int dy = 0; dy <= 2 * F; dy++)
-                {
-                    float row = 0.0f;
-#pragma unroll
-                    for (int dx = 0; dx <= 2 * F; dx++) row = row + E[(ty + dy) * EW + tx + dx];
-                    D = D + row;
-                }
-                const int ci = (ty + R + oy) * CW + tx + R + ox;
-                float Df = 0.0f;
-#pragma unroll
-                for (int j = 0; j < NF; j++) Df = Df + feature_term(fa[j], Lf[j * (CW * CH) + ci], feat.g[j]);
-                const float w = guided_weight(patch_distance(D, inv_area), Df);
-                den = den + w;
-                nr  = nr + w * Lc[ci];
-                ng  = ng + w * Lc[CW * CH + ci];
-                nb  = nb + w * Lc[2 * CW * CH + ci];
-            }
-        }
-    if (filtered) { out.x = nr / den; out.y = ng / den; out.z = nb / den; }
-    if (inside) dst[pi] = out;
+        for (int j = 0; j < NF; j++) Df = Df + feature_term(fa[j], Lf[j * (CW * CH) + ci], feat.g[j]);
+        sum.add(offset_weight<NF != 0>(D, inv_area, Df), Lc[ci], Lc[CW * CH + ci], Lc[2 * CW * CH + ci]);
+    });
+    if (filtered) sum.divide_into(out);
+    if (t.inside) dst[t.pi] = out;
 }
 
+template <int F, class... V>
+__global__ __launch_bounds__(DN_TX * DN_TY) void denoise_tiled_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
+                                                                  const PixelStatsDev* gstats, int W, int H, int R, float k2, V... svar)
+{
+    denoise_tiled<F, 0>(dst, src, stats, guide, gstats, DenoiseFeaturesDev{}, W, H, R, k2, svar...);
+}
+template <class... V>
+__global__ __launch_bounds__(256) void denoise_plain_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
+                                                       const PixelStatsDev* gstats, int W, int H, int R, int F, float k2, V... svar)
+{
+    const int idx = threadIdx.x + blockIdx.x * blockDim.x;
+    if (idx >= W * H) return;
+    const int py = idx / W, px = idx - py * W;
+    const float4 A  = src[idx];
+    const float  sp = inv_count(stats[idx].n);
+    float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
+    if (guide_variance_at(gstats, idx, svar...) != 0.0f)
+    {
+        const float inv_area = patch_inv_area(F);
+        ColourSum sum;
+        plain_offsets(px, py, W, H, R, F, k2, [&](int g, float& y, float& v) { guide_yv(guide, gstats, g, y, v, svar...); }, [&](float D, int q) {
+            const float  w = patch_weight(D, inv_area);
+            const float4 B = src[q];
+            const float  s = inv_count(stats[q].n);
+            sum.add(w, B.x * s, B.y * s, B.z * s);
+        });
+        sum.divide_into(out);
+    }
+    dst[idx] = out;
+}
+template <int F, int NF, class... V>
+__global__ __launch_bounds__(DN_TX * DN_TY) void denoise_guided_tiled_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
+                                                                         const PixelStatsDev* gstats, DenoiseFeaturesDev feat, int W, int H, int R, float k2,
+                                                                         V... svar)
+{
+    denoise_tiled<F, NF>(dst, src, stats, guide, gstats, feat, W, H, R, k2, svar...);
+}
 template <class... V>
 __global__ __launch_bounds__(256) void denoise_guided_plain_k(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide,
                                                               const PixelStatsDev* gstats, DenoiseFeaturesDev feat, int W, int H, int R, int F, float k2,
@@ -345,6 +340,7 @@ __global__ __launch_bounds__(256) void denoise_guided_plain_k(float4* dst, const
     float4 out = make_float4(A.x * sp, A.y * sp, A.z * sp, A.w * sp);
     if (guide_variance_at(gstats, idx, svar...) != 0.0f)
     {
+        // (plain_offsets and ColourSum written out: see the file header)
         const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
         float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
         for (int oy = -R; oy <= R; oy++)
@@ -385,72 +381,35 @@ __global__ __launch_bounds__(256) void denoise_guided_plain_k(float4* dst, const
 
 // ---- vp_filter_variance: the filter on one scalar plane u with the noise q of its values: y := u, v := q and
 // the one colour c := u of vp_denoise's definition; a pixel with u == 0 stays 0.
-// denoise_tiled_k's passes with the planes it needs: (u, q) of the tile plus an R + F halo at the pitch of its (y, v) planes, and the
-// double-buffered e plane.  The colour of an offset is u itself, R inside the staged plane's halo: a half-wave reads 32 consecutive
-// dwords of one row of it, as it would of a colour plane.  2 yv + 2 e floats of LDS: denoise_tiled_k's less its three colour planes.
+// The colour of an offset is u itself, R inside the staged plane's halo: a half-wave reads 32 consecutive dwords of one row of it, as
+// it would of a colour plane.  2 yv + 2 e floats of LDS: denoise_tiled's less its three colour planes.
 template <int F>
 __global__ __launch_bounds__(DN_TX * DN_TY) void variance_tiled_k(float* dst, const float* u, const float* q, int W, int H, int R, float k2)
 {
-    constexpr int EW = DN_TX + 2 * F, EH = DN_TY + 2 * F;   // the e plane: the tile plus an F halo
-    constexpr int YW = EW + 32;                             // pitch of the (u, q) planes (>= DN_TX + 2 (R + F) for R <= 16)
+    using P = TilePlanes<F>;
     extern __shared__ float lds[];
     const int halo = R + F, YH = DN_TY + 2 * halo;
     float* Lu = lds;
-    float* Lq = Lu + YW * YH;
-    float* Le = Lq + YW * YH;             // two planes of EW * EH
-    const int tid = threadIdx.x, tx = tid & (DN_TX - 1), ty = tid / DN_TX;
-    const int x0 = blockIdx.x * DN_TX, y0 = blockIdx.y * DN_TY;
-    const int px = x0 + tx, py = y0 + ty;
-    const bool inside = px < W && py < H;
-    const int  pi = clampi(py, H - 1) * W + clampi(px, W - 1);
-    const bool filtered = inside && u[pi] != 0.0f;
+    float* Lq = Lu + P::YW * YH;
+    float* Le = Lq + P::YW * YH;              // two planes of EW * EH
+    const TilePos t(W, H);
+    const bool filtered = t.inside && u[t.pi] != 0.0f;
     // a tile of constants -- u == 0 in both halves -- stays one
     if (!__syncthreads_or(filtered))
     {
-        if (inside) dst[pi] = 0.0f;
+        if (t.inside) dst[t.pi] = 0.0f;
         return;
     }
-    for (int i = tid; i < (DN_TX + 2 * halo) * YH; i += DN_TX * DN_TY)
-    {
-        const int r = i / (DN_TX + 2 * halo), c = i - r * (DN_TX + 2 * halo);
-        const int g = clampi(y0 - halo + r, H - 1) * W + clampi(x0 - halo + c, W - 1);
-        Lu[r * YW + c] = u[g];
-        Lq[r * YW + c] = q[g];
-    }
+    stage_yv<F>(Lu, Lq, W, H, halo, YH, [&](int g, float& y, float& v) { y = u[g]; v = q[g]; });
     __syncthreads();
-    const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
+    const float inv_area = patch_inv_area(F);
     float den = 0.0f, num = 0.0f;
-    int buf = 0;
-    for (int oy = -R; oy <= R; oy++)
-        for (int ox = -R; ox <= R; ox++, buf ^= 1)
-        {
-            float* E = Le + buf * (EW * EH);
-            const int shift = oy * YW + ox;
-            for (int i = tid; i < EW * EH; i += DN_TX * DN_TY)
-            {
-                const int r = i / EW, c = i - r * EW;
-                const int a = (r + R) * YW + (c + R);
-                E[i] = pair_term(Lu[a], Lq[a], Lu[a + shift], Lq[a + shift], k2);
-            }
-            __syncthreads();   // (the other buffer is written next: its readers passed this barrier)
-            const int qx = px + ox, qy = py + oy;
-            if (filtered && qx >= 0 && qx < W && qy >= 0 && qy < H)
-            {
-                float D = 0.0f;
-#pragma unroll
-                for (int dy = 0; dy <= 2 * F; dy++)
-                {
-                    float row = 0.0f;
-#pragma unroll
-                    for (int dx = 0; dx <= 2 * F; dx++) row = row + E[(ty + dy) * EW + tx + dx];
-                    D = D + row;
-                }
-                const float w = patch_weight(D, inv_area);
-                den = den + w;
-                num = num + w * Lu[(ty + halo + oy) * YW + tx + halo + ox];
-            }
-        }
-    if (inside) dst[pi] = filtered ? num / den : 0.0f;
+    tiled_offsets<F>(Lu, Lq, Le, filtered, W, H, R, k2, [&](float D, int ox, int oy) {
+        const float w = patch_weight(D, inv_area);
+        den = den + w;
+        num = num + w * Lu[(t.ty + halo + oy) * P::YW + t.tx + halo + ox];
+    });
+    if (t.inside) dst[t.pi] = filtered ? num / den : 0.0f;
 }
 
 __global__ __launch_bounds__(256) void variance_plain_k(float* dst, const float* u, const float* q, int W, int H, int R, int F, float k2)
@@ -461,29 +420,13 @@ __global__ __launch_bounds__(256) void variance_plain_k(float* dst, const float*
     float out = 0.0f;
     if (u[idx] != 0.0f)
     {
-        const float inv_area = 1.0f / (float)((2 * F + 1) * (2 * F + 1));
+        const float inv_area = patch_inv_area(F);
         float den = 0.0f, num = 0.0f;
-        for (int oy = -R; oy <= R; oy++)
-            for (int ox = -R; ox <= R; ox++)
-            {
-                const int qx = px + ox, qy = py + oy;
-                if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-                float D = 0.0f;
-                for (int dy = -F; dy <= F; dy++)
-                {
-                    float row = 0.0f;
-                    for (int dx = -F; dx <= F; dx++)
-                    {
-                        const int a = clampi(py + dy, H - 1) * W + clampi(px + dx, W - 1);
-                        const int b = clampi(qy + dy, H - 1) * W + clampi(qx + dx, W - 1);
-                        row = row + pair_term(u[a], q[a], u[b], q[b], k2);
-                    }
-                    D = D + row;
-                }
-                const float w = patch_weight(D, inv_area);
-                den = den + w;
-                num = num + w * u[qy * W + qx];
-            }
+        plain_offsets(px, py, W, H, R, F, k2, [&](int g, float& y, float& v) { y = u[g]; v = q[g]; }, [&](float D, int g) {
+            const float w = patch_weight(D, inv_area);
+            den = den + w;
+            num = num + w * u[g];
+        });
         out = num / den;
     }
     dst[idx] = out;
@@ -734,25 +677,18 @@ size_t denoise_lds_bytes(int R, int F)
     const size_t e  = (size_t)(DN_TX + 2 * F) * (DN_TY + 2 * F);
     return (2 * yv + 3 * c + 2 * e) * sizeof(float);
 }
-void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, int W, int H, int R,
-                    int F, float k2, int form, hipStream_t st)
-{
-    launch_denoise_v(dst, src, stats, guide, gstats, W, H, R, F, k2, form, st);
-}
 size_t denoise_guided_lds_bytes(int R, int F, int n_features)
 {
     return denoise_lds_bytes(R, F) + (size_t)n_features * (DN_TX + 2 * R) * (DN_TY + 2 * R) * sizeof(float);
 }
-void launch_denoise_guided(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats,
-                           const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st)
+// the colour filter's one launcher: svar null or the per-sample variance plane, feat.n == 0 or the features
+void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, const float* svar,
+                    const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st)
 {
-    launch_denoise_guided_v(dst, src, stats, guide, gstats, feat, W, H, R, F, k2, form, st);
-}
-void launch_denoise_var(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, const float* svar,
-                        const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st)
-{
-    if (feat.n) launch_denoise_guided_v(dst, src, stats, guide, gstats, feat, W, H, R, F, k2, form, st, svar);
-    else launch_denoise_v(dst, src, stats, guide, gstats, W, H, R, F, k2, form, st, svar);
+    if (feat.n && svar) launch_denoise_guided_v(dst, src, stats, guide, gstats, feat, W, H, R, F, k2, form, st, svar);
+    else if (feat.n) launch_denoise_guided_v(dst, src, stats, guide, gstats, feat, W, H, R, F, k2, form, st);
+    else if (svar) launch_denoise_v(dst, src, stats, guide, gstats, W, H, R, F, k2, form, st, svar);
+    else launch_denoise_v(dst, src, stats, guide, gstats, W, H, R, F, k2, form, st);
 }
 size_t variance_lds_bytes(int R, int F)
 {

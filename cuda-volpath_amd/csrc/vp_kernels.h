@@ -308,25 +308,21 @@ void launch_merge_halves(float4* dst, float* resid, const float4* a, const Pixel
 // dst += src for records: binary64 sums, n added, flags or-ed (accumulate_stats_k)
 void launch_accumulate_stats(PixelStatsDev* dst, const PixelStatsDev* src, size_t n, hipStream_t st);
 void launch_stats_rel_error(float* dst, const PixelStatsDev* stats, int size, float floor_y, hipStream_t st);
-// the NL-means filter of the output stage (vp_denoise.hip; include/volpath.h vp_denoise): weights from (guide, gstats), colours from
-// (src, stats), k2 = k * k; form 0 tiled through LDS (denoise_lds_bytes(R, F) of it per workgroup), 1 one thread per pixel from global memory
-size_t denoise_lds_bytes(int R, int F);
-void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, int W, int H, int R,
-                    int F, float k2, int form, hipStream_t st);
-// the same filter with the feature term (include/volpath.h vp_denoise_guided): n >= 1 features, chan[j] the address of feature j's
-// channel at pixel 0 (pixel i at chan[j][4 * i]), g[j] = 1 / (2 sigma_j^2) as the host rounded it.  Form 0 stages the channels into
-// n more LDS planes: denoise_guided_lds_bytes(R, F, n) dynamic bytes per workgroup, which the caller holds against
-// DENOISE_LDS_LIMIT before it launches
+// the NL-means filter of the output stage (vp_denoise.hip; include/volpath.h vp_denoise, vp_denoise_guided, vp_denoise_var): weights from
+// (guide, gstats), colours from (src, stats), k2 = k * k; form 0 tiled through LDS, 1 one thread per pixel from global memory.
+//   feat.n == 0: the plain weight, denoise_lds_bytes(R, F) of LDS per workgroup in form 0.
+//   feat.n >= 1: the feature term as well; chan[j] is the address of feature j's channel at pixel 0 (pixel i at chan[j][4 * i]),
+//     g[j] = 1 / (2 sigma_j^2) as the host rounded it.  Form 0 stages the channels into n more LDS planes:
+//     denoise_guided_lds_bytes(R, F, n) dynamic bytes per workgroup, which the caller holds against DENOISE_LDS_LIMIT before it launches.
+//   svar != null: the guide's variance from the caller's per-sample plane, v = svar * s in place of the records' variance; the same
+//     kernels with the plane as one more parameter, LDS as theirs.
 struct DenoiseFeaturesDev { const float* chan[4]; float g[4]; int n; };
 // what a workgroup may take without an attribute call, less the kernels' 256 static bytes (the vote of __syncthreads_or)
 constexpr size_t DENOISE_LDS_LIMIT = 64 * 1024 - 256;
+size_t denoise_lds_bytes(int R, int F);
 size_t denoise_guided_lds_bytes(int R, int F, int n_features);
-void launch_denoise_guided(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats,
-                           const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st);
-// either filter with the guide's variance taken from the caller's per-sample plane (include/volpath.h vp_denoise_var): v = svar * s in
-// place of the records' variance; feat.n == 0: the instances of launch_denoise, else those of launch_denoise_guided, LDS as theirs
-void launch_denoise_var(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, const float* svar,
-                        const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st);
+void launch_denoise(float4* dst, const float4* src, const PixelStatsDev* stats, const float4* guide, const PixelStatsDev* gstats, const float* svar,
+                    const DenoiseFeaturesDev& feat, int W, int H, int R, int F, float k2, int form, hipStream_t st);
 // the pooled per-sample luminance variance u of two halves' records and the noise q of that estimate (halves_variance_k; include/volpath.h
 // vp_halves_variance): q may be null
 void launch_halves_variance(float* u, float* q, const PixelStatsDev* a_stats, const PixelStatsDev* b_stats, int size, hipStream_t st);
